@@ -2,7 +2,7 @@
 """Benchmark of the hot path: leaf-pair patristic distances (+ MRCA ids) per second
 on BASELINE's 1M-leaf tree.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[2], SURVEY.md section 8d "Config 3"): synthetic
 perfectly balanced binary tree with 2^20 leaves (2,097,151 nodes, in-order ids),
@@ -23,8 +23,13 @@ CHILD process -- before this process has imported torch or loaded any HIP librar
 the child's JSON line, returns its exit code, and kills the child's process group when
 --launch-timeout expires.  Launched by torch.distributed.run directly (the driver's form for
 N > 1) the file is simply one rank.  One JSON line on stdout from rank 0; DESIGN.md section 6
-explains the fields.  The CPU baseline (oracle, all host cores) and the parity block are
-produced by rank 0 at every N, the peers waiting at the closing barrier.
+explains the fields.
+
+A plain run sets up, warms up, times the K steps, writes the last step's results with
+--dump-outputs, and prints the line.  --full adds, after the timed steps, everything else the
+line can carry: the CPU baseline (oracle, all host cores) and the parity block, produced by
+rank 0 at every N while the peers wait at the closing barrier, the side legs of bench_legs.py
+and, at N > 1, the other gather modes and the parity across slices.
 
 Structure: `run_job` is backend-neutral (HipBackend here; the gloo test-suite injects a CPU
 backend whose compute step is the oracle, tests/test_bench_gloo.py) -- the sharded step, the
@@ -48,6 +53,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 METRIC = "leaf-pair patristic distances/sec (+ MRCA ids/sec), 1M-leaf tree"
+DUMP_PAIRS = 1 << 21     # --dump-outputs: at most this many pairs, 2 x 16 MiB of float64
+DUMP_SEED = 20251015
 
 
 def parse(argv=None):
@@ -70,7 +77,7 @@ def parse(argv=None):
                          "grouped send/recv between all pairs of GPUs); none: every rank keeps its slice (nothing travels; the "
                          "slices are gathered once, untimed, for the parity check)")
     ap.add_argument("--no-gather-sweep", action="store_true",
-                    help="N > 1, strong scaling: skip the few steps of the two OTHER gather modes timed after the timed region "
+                    help="N > 1, strong scaling, --full: skip the few steps of the two OTHER gather modes timed after the timed region "
                          "(gather_modes in the line)")
     ap.add_argument("--reserve-cus", type=int, default=0,
                     help="N > 1: CUs rank 0's kernels leave free for RCCL's receive kernels (handle option reserve_cus)")
@@ -82,6 +89,13 @@ def parse(argv=None):
     ap.add_argument("--no-microbench", action="store_true", help="skip the in-process hardware-ceiling measurements")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the short legs on BASELINE configs 2, 4 and 5 (other_configs in the line)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also everything beyond the headline figure: the CPU baseline and the parity "
+                         "block, the hardware ceilings, the MRCA-only launch, the host path, the other BASELINE configs and, at "
+                         "N > 1, the other gather modes and the parity across slices (the --no-* options leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/distances.npy and DIR/mrca_ids.npy (float64; a fixed "
+                         "sample of %d pair positions when the batch is larger)" % DUMP_PAIRS)
     ap.add_argument("--deadline", type=float, default=600.0,
                     help="seconds every rank allows for warmup + timed steps; a rank that misses it exits with code 3")
     ap.add_argument("--launch-timeout", type=float, default=3000.0,
@@ -245,6 +259,20 @@ def spread_parity(parent, dist, pairs_t, out_d, out_m, plan, per_edge=500, strid
             "mrca_bit_exact": bool(np.array_equal(O.mrca_bulk(p), m)), "checked_pairs": int(len(idx)),
             "what": "assembled result vs the oracle: %d pairs within %d of every slice / piece boundary + every %d-th "
                     "pair of the batch" % (n_edge, per_edge, max(1, plan.n // max(1, strided)))}
+
+
+def dump_outputs(directory, out_d, out_m):
+    """--dump-outputs: the float64 distances and the MRCA ids (as float64, exact) of the last timed step, as a caller of the
+    path receives them -- every pair when the batch has at most DUMP_PAIRS, else the pairs at a fixed sample of positions
+    (DUMP_SEED; increasing order), the same for every run and build with the same --pairs."""
+    import torch
+    n = out_d.shape[0]
+    if n > DUMP_PAIRS:
+        idx = torch.from_numpy(np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_PAIRS))).to(out_d.device)
+        out_d, out_m = out_d[idx], out_m[idx]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "distances.npy"), out_d.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(directory, "mrca_ids.npy"), out_m.cpu().numpy().astype(np.float64))
 
 
 def latest_traffic():
@@ -431,7 +459,7 @@ def run_job(args, be, dg, world, rank, parent, dist, peers_wait=None):
     # strong scaling: every rank generates the SAME batch (same seed) and owns a slice of it
     pairs = be.make_pairs(n, 3 + (rank if args.weak else 0))
     root_share, calib = None, None
-    sweep = strong and world > 1 and not args.no_gather_sweep
+    sweep = args.full and strong and world > 1 and not args.no_gather_sweep
     if strong and world > 1 and args.root_share != "even" and (args.gather == "root" or sweep):
         if args.root_share == "auto":
             # untimed: this GPU's kernel rate on a prefix of the batch and the rate at which rank 0
@@ -523,6 +551,8 @@ def run_job(args, be, dg, world, rank, parent, dist, peers_wait=None):
             if not (torch.equal(own_d.view(torch.int64), out_d[lo0:hi0].view(torch.int64)) and torch.equal(own_m, out_m[lo0:hi0])):
                 raise SystemExit("bench.py: --gather none: rank 0's resident slice differs from the assembled result")
         be.fault_check()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out_d, out_m)
 
     gather_modes = None
     if sweep:
@@ -603,6 +633,8 @@ def run_job(args, be, dg, world, rank, parent, dist, peers_wait=None):
         roof = line["roofline"]
         if "traffic_not_used" in roof:      # (the side figures must not borrow another configuration's counters either)
             traffic = None
+        if not args.full:      # a plain run: the headline figure only
+            return line
         if hasattr(be, "extra_legs"):
             be.extra_legs(args, line, roof, pairs, out_d, out_m, traffic, traffic_file, pairs_this_rank, kernel_ms)
         if strong and world > 1:

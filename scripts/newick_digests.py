@@ -6,13 +6,15 @@ Per file: node / leaf counts, root id, reference depth, sha256 of the parent and
 distance arrays and of the leaf-name order, and whether the native parser took the file and
 produced identical arrays.  An id-assignment divergence between the two parsers, or a change
 of either parser's numbering on any of the reference's 327 trees, shows up as a changed
-digest (tests/test_newick.py::test_reference_data_digests re-checks them when the reference
-checkout is present).  Data only: no reference source text is stored.
+digest (tests/test_newick.py::test_reference_data_digests re-checks them on the sample of the
+files that tests/golden/reference_trees.tar.xz holds, also written here).  Data only: no
+reference source text is stored.
 """
 import hashlib
 import json
 import os
 import sys
+import tarfile
 
 import numpy as np
 
@@ -48,6 +50,23 @@ def digest_file(path):
     return d
 
 
+def sampled(names):
+    """The files tests/test_newick.py::test_reference_data_digests parses: every ninth name, the two big trees and the
+    one with a quote inside an unquoted label."""
+    names = sorted(names)
+    return sorted(set(names[::9]) | {"bigtrees/ml.tree", "bigtrees/nj.tree", "plant-pollinators/rabr/plant.tree"})
+
+
+def write_sample_archive(names, dst):
+    """The sampled tree files, byte for byte, in a tar.xz whose bytes depend on the files alone (no times, owners)."""
+    with tarfile.open(dst, "w:xz") as tf:
+        for rel in sampled(names):
+            info = tf.gettarinfo(os.path.join(REF_DATA, rel), arcname=rel)
+            info.mtime, info.uid, info.gid, info.uname, info.gname, info.mode = 0, 0, 0, "", "", 0o644
+            with open(os.path.join(REF_DATA, rel), "rb") as fh:
+                tf.addfile(info, fh)
+
+
 def main():
     out = {}
     for base, _, files in sorted(os.walk(REF_DATA)):
@@ -63,6 +82,9 @@ def main():
         k = "error" if "error" in v else v["native"]
         kinds[k] = kinds.get(k, 0) + 1
     print(len(out), "files:", kinds, "->", dst)
+    archive = os.path.join(ROOT, "tests", "golden", "reference_trees.tar.xz")
+    write_sample_archive(out, archive)
+    print(len(sampled(out)), "sampled files ->", archive)
 
 
 if __name__ == "__main__":

@@ -121,7 +121,7 @@ def test_bench_job_line_on_gloo(world, share, chunks, n, wire):
     8: --wire-int32."""
     from suchtree_amd import sharding
     argv = ["--gpus", str(world), "--steps", "2", "--warmup", "1", "--pairs", str(n), "--levels", "9",
-            "--chunks", str(chunks), "--root-share", share, "--cpu-seconds", "0.2", "--deadline", "120"] + (["--wire-int32"] if wire == 8 else [])
+            "--chunks", str(chunks), "--root-share", share, "--cpu-seconds", "0.2", "--deadline", "120", "--full"] + (["--wire-int32"] if wire == 8 else [])
     procs, q, timeout = _run(world, argv)
     res = sorted(q.get(timeout=timeout) for _ in procs)
     [p.join(timeout=60) for p in procs]
@@ -183,7 +183,7 @@ def test_bench_gather_modes_on_gloo(world, mode, chunks, n, wire):
     --gather none (every rank keeps its slice; assembled once, untimed, for the parity check): even slices, the same line."""
     from suchtree_amd import sharding
     argv = ["--gpus", str(world), "--steps", "2", "--warmup", "1", "--pairs", str(n), "--levels", "9", "--gather", mode,
-            "--chunks", str(chunks), "--cpu-seconds", "0.2", "--deadline", "120"] + (["--wire-int32"] if wire == 8 else [])
+            "--chunks", str(chunks), "--cpu-seconds", "0.2", "--deadline", "120", "--full"] + (["--wire-int32"] if wire == 8 else [])
     procs, q, timeout = _run(world, argv)
     res = sorted(q.get(timeout=timeout) for _ in procs)
     [p.join(timeout=60) for p in procs]
@@ -227,7 +227,7 @@ def test_a_hung_rank_ends_the_job_at_the_deadline():
 
 
 def test_weak_mode_line_on_gloo():
-    argv = ["--gpus", "2", "--steps", "2", "--warmup", "0", "--pairs", "501", "--levels", "9", "--weak", "--cpu-seconds", "0.1"]
+    argv = ["--gpus", "2", "--steps", "2", "--warmup", "0", "--pairs", "501", "--levels", "9", "--weak", "--cpu-seconds", "0.1", "--full"]
     procs, q, timeout = _run(2, argv)
     res = sorted(q.get(timeout=timeout) for _ in procs)
     [p.join(timeout=60) for p in procs]
@@ -235,6 +235,32 @@ def test_weak_mode_line_on_gloo():
     d = json.loads(res[0][1])
     assert d["scaling"] == "weak" and d["config"]["pairs_per_step"] == 1002 and "gather_ms" not in d
     assert d["parity"]["distances_bit_exact"] and all(len(r[2]) == 2 for r in res)
+
+
+def test_plain_run_line_and_dumped_outputs_on_gloo(tmp_path):
+    """Without --full the line carries the headline figure only (no CPU baseline, parity or gather-mode sweep), and
+    --dump-outputs writes the assembled result of the last timed step on rank 0."""
+    from oracle.oracle import OracleTree
+    from suchtree_amd import synth
+    n, out = 30011, tmp_path / "outputs"
+    argv = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", str(n), "--levels", "9", "--deadline", "120",
+            "--dump-outputs", str(out)]
+    procs, q, timeout = _run(2, argv)
+    res = sorted(q.get(timeout=timeout) for _ in procs)
+    [p.join(timeout=60) for p in procs]
+    assert all(p.exitcode == 0 for p in procs)
+    d = json.loads(res[0][1])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 2 and abs(d["ms_per_step"] - n / d["value"] * 1e3) < 1e-6 * d["ms_per_step"]
+    for key in ("cpu_baseline", "parity", "parity_across_slices", "gather_modes"):
+        assert key not in d, key
+    parent, dist_ = synth.balanced_tree(9)
+    pairs = np.random.default_rng(3).integers(0, 1 << 9, (n, 2)) * 2      # (CpuBackend.make_pairs, rank 0's seed)
+    O = OracleTree(parent, dist_)
+    dd, mm = np.load(out / "distances.npy"), np.load(out / "mrca_ids.npy")
+    assert dd.dtype == mm.dtype == np.float64
+    assert np.array_equal(dd, O.distances(pairs)) and np.array_equal(mm, O.mrca_bulk(pairs))
 
 
 def _worker_closing(rank, world, port, q):

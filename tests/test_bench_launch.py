@@ -50,9 +50,19 @@ def test_self_launch_kills_the_job_at_its_timeout():
 
 
 def test_one_gpu_run_does_not_self_launch():
-    """--gpus 1 stays one plain process (the driver's N = 1 form); on this CPU box it stops at the GPU check."""
-    out = run(["--gpus", "1"])
-    assert out.returncode != 0 and "MI355X" in out.stderr and "RCCL version banner" not in out.stdout
+    """--gpus 1 stays one plain process (the driver's N = 1 form); without a GPU it stops at the GPU check, with one
+    it prints its own line (the stand-in launcher's would carry argv)."""
+    from suchtree_amd import _capi
+    out = run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--pairs", "1000000"])
+    assert "RCCL version banner" not in out.stdout
+    if _capi.device_count() == 0:
+        assert out.returncode != 0 and "MI355X" in out.stderr
+    else:
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = out.stdout.splitlines()
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert "argv" not in d and d["n_gpus"] == 1 and d["steps"] == 2
 
 
 def test_rank_count_mismatch_is_refused():

@@ -77,3 +77,21 @@ def test_headline_counters_speak_for_the_default_configuration_only():
     assert committed is not None and bench.traffic_speaks_for(committed, args, info, 1)[0], name
     foot = bench.gather_footprint_bytes({"strategy": "canopy", "a_side_bytes": 4, "b_table_bytes_per_leaf": 16, "record_bytes": 64, "n_nodes": 1}, 1 << 20)
     assert foot == 20 << 20
+
+
+def test_dumped_outputs_are_the_results_or_a_fixed_sample_of_them(tmp_path, monkeypatch):
+    """--dump-outputs: float64 files of what the step computed; beyond DUMP_PAIRS a seeded sample of positions, the
+    same from call to call."""
+    import torch
+    d = torch.from_numpy(np.random.default_rng(0).random(1000))
+    m = torch.arange(1000, dtype=torch.int32) * 3
+    bench.dump_outputs(str(tmp_path / "all"), d, m)
+    dd, mm = np.load(tmp_path / "all" / "distances.npy"), np.load(tmp_path / "all" / "mrca_ids.npy")
+    assert dd.dtype == mm.dtype == np.float64 and np.array_equal(dd, d.numpy()) and np.array_equal(mm, m.numpy())
+    monkeypatch.setattr(bench, "DUMP_PAIRS", 64)
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), d, m)
+    da, ma = np.load(tmp_path / "a" / "distances.npy"), np.load(tmp_path / "a" / "mrca_ids.npy")
+    assert np.array_equal(da, np.load(tmp_path / "b" / "distances.npy")) and np.array_equal(ma, np.load(tmp_path / "b" / "mrca_ids.npy"))
+    pos = ma.astype(np.int64) // 3      # (the ids above are 3 x position)
+    assert 32 < len(pos) <= 64 and np.all(np.diff(pos) > 0) and np.array_equal(da, d.numpy()[pos])

@@ -22,7 +22,7 @@ def _free_port():
 
 def test_bench_line_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
-                          "--pairs", "4000000", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=900)
+                          "--pairs", "4000000", "--cpu-seconds", "1", "--full"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -116,7 +116,7 @@ def test_bench_under_torchrun_one_rank():
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
                           "--gpus", "1", "--steps", "2", "--warmup", "1", "--pairs", "2000000", "--cpu-seconds", "1",
-                          "--no-host-path", "--no-microbench", "--no-other-configs"], capture_output=True, text=True, timeout=900)
+                          "--no-host-path", "--no-microbench", "--no-other-configs", "--full"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -125,3 +125,30 @@ def test_bench_under_torchrun_one_rank():
     # the CPU baseline and the parity block are produced under the process group too (every N)
     assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["kind"] in ("port", "reference")
     assert d["parity"]["distances_bit_exact"] and d["parity"]["mrca_bit_exact"]
+
+
+def test_plain_bench_run_and_dumped_outputs(tmp_path):
+    """Without --full: the headline fields only, and --dump-outputs holds the last timed step's results at a seeded
+    sample of positions (the batch is larger than DUMP_PAIRS), bit for bit what the oracle computes for those pairs."""
+    import numpy as np
+    from oracle.oracle import OracleTree
+    from suchtree_amd import synth
+    import bench
+    n, out_dir = 4_000_000, tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--pairs", str(n),
+                          "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["unit"] == "pairs/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["ms_per_step"] - n / d["value"] * 1e3) < 1e-6 * d["ms_per_step"] and d["value"] > 1e9
+    for key in ("cpu_baseline", "parity", "hardware_measured", "end_to_end_host_path", "mrca_ids_only", "other_configs"):
+        assert key not in d, key
+    idx = np.unique(np.random.default_rng(bench.DUMP_SEED).integers(0, n, bench.DUMP_PAIRS))
+    pairs = synth.random_leaf_pairs(1 << 20, n, seed=3)[idx]
+    dd, mm = np.load(out_dir / "distances.npy"), np.load(out_dir / "mrca_ids.npy")
+    assert dd.dtype == mm.dtype == np.float64 and len(dd) == len(mm) == len(idx)
+    parent, dist = synth.balanced_tree(20)
+    O = OracleTree(parent, dist)
+    assert np.array_equal(dd.view(np.int64), O.distances_mt(pairs, 16).view(np.int64)) and np.array_equal(mm, O.mrca_bulk(pairs))

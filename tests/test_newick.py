@@ -5,7 +5,6 @@ against the structural facts the reference's tests assert
 (tests/test_SuchTree.py:35-44 children ids, :22-24 polytomy resolution).
 """
 import json
-import os
 
 import numpy as np
 import pytest
@@ -222,22 +221,26 @@ class TestNativeNewick:
 
 
 def test_reference_data_digests():
-    """Every tree file under the reference's data/ directory (327 Newick files) through both
-    parsers: same arrays from both, and the same arrays as when tests/golden/newick_digests.json
-    was written (scripts/newick_digests.py).  Runs where the reference checkout exists."""
+    """Tree files of the reference's data/ directory (327 Newick files) through both parsers: same
+    arrays from both, and the same arrays as when tests/golden/newick_digests.json was written
+    (scripts/newick_digests.py).  The sampled files are stored byte for byte in
+    tests/golden/reference_trees.tar.xz (written by the same script)."""
     import hashlib
+    import io
     import json
-    ref = "/root/reference/data"
-    if not os.path.isdir(ref):
-        pytest.skip("reference checkout not present")
+    import tarfile
     want = json.load(open(golden_path("newick_digests.json")))
     assert len(want) == 327 and all(v.get("native") == "identical" for v in want.values())
     sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()[:24]   # noqa: E731
     # the big trees, the one with a quote inside an unquoted label, and a spread of the rest
     names = sorted(want)
     sample = set(names[::9]) | {"bigtrees/ml.tree", "bigtrees/nj.tree", "plant-pollinators/rabr/plant.tree"}
+    with tarfile.open(golden_path("reference_trees.tar.xz"), "r:xz") as tf:
+        # (read as open() reads a file: universal newlines -- one of the files ends its lines with CR LF)
+        files = {m.name: io.TextIOWrapper(tf.extractfile(m), encoding="utf-8").read() for m in tf.getmembers() if m.isfile()}
+    assert set(files) == sample
     for rel in sorted(sample):
-        text = open(os.path.join(ref, rel)).read()
+        text = files[rel]
         for native in (False, True):
             t = flat_tree_from_newick(text, native=native)
             w = want[rel]
