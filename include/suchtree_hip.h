@@ -37,12 +37,13 @@ extern "C" {
  * ABI version: bumped whenever an exported struct grows, or an export, option or constant goes away.  A caller built against
  * an older header must not be handed a larger st_tree_info: compare ST_API_VERSION with st_api_version() at load (the ctypes
  * binding does) and use st_tree_info_get_sized, which writes at most the bytes the caller says it has.
+ *   7: st_compare_triangle_host, st_compare_pairs_host and struct st_pair_moments added.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
  *                ST_KERNEL_CANOPY_SCALAR, the options pairs_per_lane and ladder_dynamic = 2 removed.
  */
-#define ST_API_VERSION 6
+#define ST_API_VERSION 7
 int st_api_version(void);
 
 #define ST_OK          0
@@ -293,6 +294,51 @@ int st_grid_host(st_tree *tree, const int64_t *row_ids, int64_t n_rows,
 int st_knn_host(st_tree *tree, const int64_t *queries, int64_t n_queries,
                 const int64_t *cands, int64_t n_cands, int k, int skip_self,
                 int64_t *out_index, double *out_dist, int64_t *bad_id);
+
+/*
+ * Compare two trees' distances over the same pairs, reduced on the GPU.  Pair k is evaluated in tree_x (x_k) and in
+ * tree_y (y_k) by the same kernels as the calls above (float32 sums, bit-identical to st_distances_host / st_triangle_host);
+ * out receives the moments of the joint distribution and, if edges_x, edges_y and out_hist are all given, out_hist the
+ * exact 2-D histogram of numpy.histogram2d on the float64-widened values: cell (i, j) of the C-order int64
+ * (bins_x, bins_y) array counts the pairs with x in bin i and y in bin j, bin = searchsorted(edges, v, side='right') - 1,
+ * a value equal to the last edge in the last bin, values outside [edges[0], edges[bins]] and NaN not counted.  Edges:
+ * bins + 1 finite, monotonically increasing doubles per axis, first < last; at most 16384 cells.  Nothing is returned
+ * per pair: device scratch is bounded by a chunk of pairs, host memory by the histogram.
+ *
+ * Replaces the host-side reduction of the reference's two comparison workflows: docs/examples/SuchTree_examples.md
+ * ("Comparing the topologies of two large trees") and docs/benchmarks.md, which draw random name pairs, call
+ * distances_by_name (SuchTree/MuchTree.pyx:945-979) on both trees and correlate the two lists; and
+ * SuchLinkedTrees.linked_distances (SuchTree/MuchTree.pyx:2900-2934), whose two columns every notebook correlates
+ * (sample_linked_distances, :2951-3079, samples them because the pairs are too many to enumerate on a CPU).
+ *
+ * Both trees must live on the same device (a multi-device handle: its first device), otherwise ST_ERR_ARG; tree_x ==
+ * tree_y is allowed.  Ids are checked on the host before anything is launched: ST_ERR_BOUNDS with *bad_id as for
+ * st_distances_host (tree_x's ids first).  Bad histogram arguments -- some but not all of edges_x / edges_y / out_hist
+ * NULL, a bins < 1, more than 16384 cells, edges not increasing -- are ST_ERR_ARG.
+ *
+ * The sums are taken about a shift (cx, cy), the mean of the call's first min(count, 4096) pairs (0 where that mean is
+ * not finite), against cancellation; they are reduced in one fixed order (lanes, waves, workgroups of a fixed grid,
+ * then the workgroups in index order, no float atomics): two identical calls return identical bits.  NaN distances
+ * propagate into the sums and are skipped by min / max and the histogram.  An empty range gives n = 0, zero sums,
+ * NaN min / max and a zero histogram, and launches nothing.  No counterpart in the reference.
+ */
+typedef struct st_pair_moments {
+    int64_t n;                        /* pairs reduced */
+    double  shift_x, shift_y;         /* cx, cy used for the sums below */
+    double  sx, sy, sxx, syy, sxy;    /* sums of (x-cx), (y-cy), squares, cross product */
+    double  min_x, max_x, min_y, max_y;
+} st_pair_moments;
+
+/* pair k = (ids_x[j], ids_x[i]) in tree_x and (ids_y[j], ids_y[i]) in tree_y, k = i(i-1)/2 + j, for k in
+   [k_begin, k_begin + k_count) -- the enumeration of st_triangle_host.  edges_* / out_hist may be NULL (no histogram). */
+int st_compare_triangle_host(st_tree *tree_x, st_tree *tree_y, const int64_t *ids_x, const int64_t *ids_y, int64_t m,
+                             int64_t k_begin, int64_t k_count,
+                             const double *edges_x, int32_t bins_x, const double *edges_y, int32_t bins_y,
+                             st_pair_moments *out, int64_t *out_hist, int64_t *bad_id);
+/* pair i = (pairs_x[i,0], pairs_x[i,1]) in tree_x and (pairs_y[i,0], pairs_y[i,1]) in tree_y; C-order int64 (n,2). */
+int st_compare_pairs_host(st_tree *tree_x, st_tree *tree_y, const int64_t *pairs_x, const int64_t *pairs_y, int64_t n,
+                          const double *edges_x, int32_t bins_x, const double *edges_y, int32_t bins_y,
+                          st_pair_moments *out, int64_t *out_hist, int64_t *bad_id);
 
 /*
  * Quartet topologies: for each row (a,b,c,d) of the int64 (n,4) view the row re-ordered so

@@ -32,7 +32,7 @@ class TreeOptions(ctypes.Structure):
     _fields_ = [("table_budget_bytes", ctypes.c_int64), ("reserved", ctypes.c_int64 * 7)]
 
 
-API_VERSION = 6      # include/suchtree_hip.h: ST_API_VERSION
+API_VERSION = 7      # include/suchtree_hip.h: ST_API_VERSION
 
 # every symbol include/suchtree_hip.h declares (tests check the .so exports them all)
 SYMBOLS = (
@@ -42,8 +42,17 @@ SYMBOLS = (
     "st_tree_set_option", "st_triangle_device", "st_triangle_host", "st_grid_host", "st_knn_host",
     "st_quartets_host", "st_graph_matrices_host", "st_newick_open", "st_newick_fill", "st_newick_close",
     "st_host_depths", "st_link_sample_pairs", "st_bucket_moments", "st_device_malloc", "st_device_free", "st_memcpy_h2d", "st_memcpy_d2h",
-    "st_device_synchronize",
+    "st_device_synchronize", "st_compare_triangle_host", "st_compare_pairs_host",
 )
+
+
+class PairMoments(ctypes.Structure):
+    """st_pair_moments (include/suchtree_hip.h): sums about the shift (shift_x, shift_y) of the compare path."""
+    _fields_ = [("n", ctypes.c_int64)] + [(k, ctypes.c_double) for k in
+                                          "shift_x shift_y sx sy sxx syy sxy min_x max_x min_y max_y".split()]
+
+    def as_dict(self):
+        return {k: (int(getattr(self, k)) if k == "n" else float(getattr(self, k))) for k, _ in self._fields_}
 
 
 class TreeInfo(ctypes.Structure):
@@ -198,6 +207,10 @@ def load():
         L.st_grid_host.argtypes = [vp, vp, i64, vp, i64, i32, i64, i64, vp, vp, ctypes.POINTER(i64)]
         L.st_knn_host.argtypes = [vp, vp, i64, vp, i64, i32, i32, vp, vp, ctypes.POINTER(i64)]
         L.st_quartets_host.argtypes = [vp, vp, i64, i64, i64, vp, ctypes.POINTER(i64)]
+        L.st_compare_triangle_host.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, ctypes.c_int32, vp, ctypes.c_int32,
+                                               ctypes.POINTER(PairMoments), vp, ctypes.POINTER(i64)]
+        L.st_compare_pairs_host.argtypes = [vp, vp, vp, vp, i64, vp, ctypes.c_int32, vp, ctypes.c_int32,
+                                            ctypes.POINTER(PairMoments), vp, ctypes.POINTER(i64)]
         L.st_graph_matrices_host.argtypes = [i32, i64, i64, vp, vp, vp, vp, vp]
         L.st_newick_open.argtypes = [ctypes.c_char_p, i64, ctypes.POINTER(vp), ctypes.POINTER(i64),
                                      ctypes.POINTER(i64), ctypes.POINTER(i64),
@@ -630,6 +643,60 @@ class DeviceTree:
                                         quartets.strides[1] // 8, _ptr(out), ctypes.byref(bad))
         check(rc, tree_size=self.size, bad_id=int(bad.value))
         return out
+
+    def _compare_check(self, other, rc, bad):
+        bad = int(bad.value)
+        if rc == ST_ERR_BOUNDS and 0 <= bad < self.size:      # (tree_x's ids are checked first: an id valid there is tree_y's)
+            check(rc, tree_size=other.size, bad_id=bad)
+        check(rc, tree_size=self.size, bad_id=bad)
+
+    @staticmethod
+    def _compare_hist(edges):
+        """(edges_x, bins_x, edges_y, bins_y, hist) ctypes arguments; edges = None or (xedges, yedges) float64."""
+        if edges is None:
+            return None, 0, None, 0, None
+        ex = np.ascontiguousarray(edges[0], dtype=np.float64)
+        ey = np.ascontiguousarray(edges[1], dtype=np.float64)
+        if ex.ndim != 1 or ey.ndim != 1 or len(ex) < 2 or len(ey) < 2:
+            raise ValueError("histogram edges must be 1-D arrays of at least two values")
+        bx, by = len(ex) - 1, len(ey) - 1
+        if bx * by > 16384:      # (checked again by the library, before anything is allocated here)
+            raise ValueError("histogram of %d cells: at most 16384" % (bx * by))
+        return ex, bx, ey, by, np.zeros((bx, by), dtype=np.int64)
+
+    def compare_triangle_host(self, other, ids_x, ids_y, k_begin=0, k_count=None, edges=None):
+        """Moments (``PairMoments``) and, with ``edges = (xedges, yedges)``, the int64 2-D histogram of the distances of
+        pairs k in [k_begin, k_begin + k_count) of the triangle over ``ids_x`` in this tree and ``ids_y`` in ``other``
+        (st_compare_triangle_host; the pair enumeration of triangle_host).  Returns (moments, hist or None)."""
+        ids_x = np.ascontiguousarray(ids_x, dtype=np.int64)
+        ids_y = np.ascontiguousarray(ids_y, dtype=np.int64)
+        if ids_x.ndim != 1 or ids_x.shape != ids_y.shape:
+            raise ValueError("ids_x and ids_y must be 1-D arrays of equal length")
+        m = int(ids_x.shape[0])
+        if k_count is None:
+            k_count = m * (m - 1) // 2 - int(k_begin)
+        ex, bx, ey, by, hist = self._compare_hist(edges)
+        out, bad = PairMoments(), ctypes.c_int64(0)
+        rc = self._lib.st_compare_triangle_host(self.handle, other.handle, _ptr(ids_x) if m else None, _ptr(ids_y) if m else None, m,
+                                                int(k_begin), int(k_count), _ptr(ex), bx, _ptr(ey), by, ctypes.byref(out), _ptr(hist),
+                                                ctypes.byref(bad))
+        self._compare_check(other, rc, bad)
+        return out, hist
+
+    def compare_pairs_host(self, other, pairs_x, pairs_y, edges=None):
+        """The same over explicit pairs: row i of ``pairs_x`` (int64 (n,2)) in this tree, row i of ``pairs_y`` in ``other``
+        (st_compare_pairs_host).  Returns (moments, hist or None)."""
+        pairs_x = np.ascontiguousarray(pairs_x, dtype=np.int64)
+        pairs_y = np.ascontiguousarray(pairs_y, dtype=np.int64)
+        if pairs_x.ndim != 2 or pairs_x.shape[1:] != (2,) or pairs_x.shape != pairs_y.shape:
+            raise ValueError("pairs_x and pairs_y must be (n, 2) arrays of equal shape")
+        n = int(pairs_x.shape[0])
+        ex, bx, ey, by, hist = self._compare_hist(edges)
+        out, bad = PairMoments(), ctypes.c_int64(0)
+        rc = self._lib.st_compare_pairs_host(self.handle, other.handle, _ptr(pairs_x) if n else None, _ptr(pairs_y) if n else None, n,
+                                             _ptr(ex), bx, _ptr(ey), by, ctypes.byref(out), _ptr(hist), ctypes.byref(bad))
+        self._compare_check(other, rc, bad)
+        return out, hist
 
     def triangle_device(self, d_ids, m, k_begin, k_count, d_out_dist=0, d_out_mrca=0, stream=0, id_stride=1):
         rc = self._lib.st_triangle_device(self.handle, ctypes.c_void_p(d_ids), int(m), int(id_stride),

@@ -1,0 +1,148 @@
+"""Comparing two trees' distances over the same pairs, reduced on the GPU (SuchTree.compare_distances,
+SuchLinkedTrees.linked_distances_summary; C ABI st_compare_triangle_host / st_compare_pairs_host).
+
+No counterpart in the reference: its comparison workflows (docs/examples/SuchTree_examples.md, "Comparing the
+topologies of two large trees"; SuchLinkedTrees.linked_distances, MuchTree.pyx:2900-2934) bring every distance back
+to the host and reduce it with numpy / scipy.  Here only the moments of the joint distribution and, if asked, an exact
+2-D histogram leave the GPU.
+"""
+import math
+from dataclasses import dataclass, replace
+from typing import Optional
+
+import numpy as np
+
+__all__ = ["DistanceComparison"]
+
+
+@dataclass(frozen=True)
+class DistanceComparison:
+    """Summary of n pairs' distances x (first tree) and y (second tree).
+
+    Statistics are population ones (numpy's ``var`` / ``cov(..., bias=True)``); ``pearson_r`` is NaN when a variance is 0.
+    ``hist`` is ``numpy.histogram2d(x, y, bins, range)[0]`` as int64 (None when no histogram was asked for), with
+    ``xedges`` / ``yedges`` its edges.  ``n_leaves`` is the length of the id list whose pairs were compared (None for
+    explicit pairs).  The raw sums -- ``sx`` = sum of (x - shift_x), ``sxx`` = sum of (x - shift_x)^2, ``sxy`` = sum of
+    (x - shift_x)(y - shift_y), ... -- are kept so that results over disjoint pair ranges can be combined (:meth:`merge`).
+    """
+
+    n_pairs: int
+    n_leaves: Optional[int]
+    mean_x: float
+    mean_y: float
+    var_x: float
+    var_y: float
+    cov: float
+    pearson_r: float
+    min_x: float
+    max_x: float
+    min_y: float
+    max_y: float
+    hist: Optional[np.ndarray]
+    xedges: Optional[np.ndarray]
+    yedges: Optional[np.ndarray]
+    shift_x: float = 0.0
+    shift_y: float = 0.0
+    sx: float = 0.0
+    sy: float = 0.0
+    sxx: float = 0.0
+    syy: float = 0.0
+    sxy: float = 0.0
+
+    @classmethod
+    def from_sums(cls, n, shift_x, shift_y, sx, sy, sxx, syy, sxy, min_x, max_x, min_y, max_y, hist=None, xedges=None,
+                  yedges=None, n_leaves=None):
+        """Derive the statistics from sums about a shift (st_pair_moments)."""
+        n = int(n)
+        nan = float("nan")
+        if n == 0:
+            mean_x = mean_y = var_x = var_y = cov = r = nan
+            min_x = max_x = min_y = max_y = nan
+        else:
+            mean_x = shift_x + sx / n
+            mean_y = shift_y + sy / n
+            var_x = (sxx - sx * sx / n) / n
+            var_y = (syy - sy * sy / n) / n
+            cov = (sxy - sx * sy / n) / n
+            var_x, var_y = max(var_x, 0.0), max(var_y, 0.0)      # (rounding of a constant column)
+            r = cov / math.sqrt(var_x * var_y) if var_x > 0 and var_y > 0 else nan
+            if not math.isnan(r):
+                r = min(1.0, max(-1.0, r))
+        return cls(n_pairs=n, n_leaves=n_leaves, mean_x=mean_x, mean_y=mean_y, var_x=var_x, var_y=var_y, cov=cov,
+                   pearson_r=r, min_x=float(min_x), max_x=float(max_x), min_y=float(min_y), max_y=float(max_y), hist=hist,
+                   xedges=xedges, yedges=yedges, shift_x=float(shift_x), shift_y=float(shift_y), sx=float(sx),
+                   sy=float(sy), sxx=float(sxx), syy=float(syy), sxy=float(sxy))
+
+    @classmethod
+    def from_moments(cls, m, hist=None, xedges=None, yedges=None, n_leaves=None):
+        """From the library's ``_capi.PairMoments``."""
+        return cls.from_sums(m.n, m.shift_x, m.shift_y, m.sx, m.sy, m.sxx, m.syy, m.sxy, m.min_x, m.max_x, m.min_y,
+                             m.max_y, hist, xedges, yedges, n_leaves)
+
+    @classmethod
+    def merge(cls, a: "DistanceComparison", b: "DistanceComparison") -> "DistanceComparison":
+        """Combine results over disjoint pair ranges (Chan et al.'s pairwise update, written on the shifted sums): b's
+        sums are moved to a's shift, d = b.shift - a.shift, sum(x - a.shift) = b.sx + n_b d_x,
+        sum(x - a.shift)^2 = b.sxx + 2 d_x b.sx + n_b d_x^2, and so on, then added.  Histograms add when both have the
+        same edges (otherwise ValueError)."""
+        if b.n_pairs == 0:
+            return a
+        if a.n_pairs == 0:
+            return replace(b, n_leaves=a.n_leaves if a.n_leaves == b.n_leaves else None)
+        hist = None
+        if a.hist is not None or b.hist is not None:
+            if a.hist is None or b.hist is None or not (np.array_equal(a.xedges, b.xedges) and np.array_equal(a.yedges, b.yedges)):
+                raise ValueError("cannot merge results with different histograms")
+            hist = a.hist + b.hist
+        dx, dy, nb = b.shift_x - a.shift_x, b.shift_y - a.shift_y, b.n_pairs
+        sx = a.sx + b.sx + nb * dx
+        sy = a.sy + b.sy + nb * dy
+        sxx = a.sxx + b.sxx + 2.0 * dx * b.sx + nb * dx * dx
+        syy = a.syy + b.syy + 2.0 * dy * b.sy + nb * dy * dy
+        sxy = a.sxy + b.sxy + dx * b.sy + dy * b.sx + nb * dx * dy
+        return cls.from_sums(a.n_pairs + nb, a.shift_x, a.shift_y, sx, sy, sxx, syy, sxy,
+                             np.fmin(a.min_x, b.min_x), np.fmax(a.max_x, b.max_x), np.fmin(a.min_y, b.min_y),
+                             np.fmax(a.max_y, b.max_y), hist, a.xedges if hist is not None else None,
+                             a.yedges if hist is not None else None, a.n_leaves if a.n_leaves == b.n_leaves else None)
+
+
+def histogram_edges(bins, range, min_max):
+    """(xedges, yedges) exactly as numpy.histogram2d builds them for ``bins`` / ``range``.  With ``range=None`` the range of
+    integer bins is the data's (min_x, max_x), (min_y, max_y), given as ``min_max`` (numpy widens an empty range by 0.5 on
+    each side); edge arrays need neither."""
+    if range is None and min_max is not None:
+        range = [(min_max[0], min_max[1]), (min_max[2], min_max[3])]
+    _, xedges, yedges = np.histogram2d(np.empty(0), np.empty(0), bins=bins, range=range)
+    return np.ascontiguousarray(xedges, dtype=np.float64), np.ascontiguousarray(yedges, dtype=np.float64)
+
+
+def _needs_data_range(bins, range):
+    """True when numpy would take (part of) the range from the data: integer bins and no explicit range."""
+    if range is not None:
+        return False
+    try:
+        if len(bins) == 2:      # a pair: ints and / or edge arrays
+            return any(np.ndim(b) == 0 for b in bins)
+    except TypeError:
+        return True             # one int for both axes
+    return np.ndim(bins) == 0   # one edge array for both axes
+
+
+def run(call, bins, range, n_leaves=None):
+    """call(edges) -> (PairMoments, hist): one pass of the library.  ``range=None`` with integer bins costs a second
+    pass: the first finds min and max, the second bins."""
+    if bins is None:
+        m, _ = call(None)
+        return DistanceComparison.from_moments(m, n_leaves=n_leaves)
+    if _needs_data_range(bins, range):
+        m, _ = call(None)
+        if m.n == 0:
+            raise ValueError("autodetected range of an empty set of pairs: give range=")
+        mm = (m.min_x, m.max_x, m.min_y, m.max_y)
+        if not all(np.isfinite(mm)):
+            raise ValueError("autodetected range of [%r, %r] x [%r, %r] is not finite" % mm)
+        xedges, yedges = histogram_edges(bins, None, mm)
+    else:
+        xedges, yedges = histogram_edges(bins, range, None)
+    m, hist = call((xedges, yedges))
+    return DistanceComparison.from_moments(m, hist, xedges, yedges, n_leaves=n_leaves)

@@ -27,7 +27,8 @@
 // functions, exported through launch_decl.h -- and this file: error plumbing, the C ABI and the host side in
 // between: st_tree.h / host_tree.h (handle, pipe registry), launch_policy.h + host_launch.h (which family a
 // request gets, enqueueing, faults), host_path.h (host-buffer pipeline, mailbox, copy kernels), host_upload.h
-// (tables -> device), kernels_misc.h (k nearest, graph matrices).
+// (tables -> device), kernels_misc.h (k nearest, graph matrices), kernels_compare.h (moments / 2-D histogram of two
+// trees' distances over the same pairs: st_compare_*).
 //
 // Host side of the C ABI: tree upload to one or several GPUs (tree_prep.cpp builds the tables, under a table budget
 // if one is given), the host path (host_pipe.h, host_copy.h: packed ids in through the copy engine, kernels write
@@ -129,6 +130,7 @@ private:
 
 #include "device_common.h"
 #include "kernels_misc.h"
+#include "kernels_compare.h"
 
 
 // --------------------------------------------------------------------------
@@ -901,6 +903,231 @@ try {
     cleanup();
     if (rc != ST_OK) return rc;
     return report_fault(t->n_nodes, f, bad_id);
+} ST_CATCH_ALL
+
+}  // extern "C"
+
+// ---- compare path (st_compare_triangle_host / st_compare_pairs_host) --------------------------------------------
+// Chunks of pairs go through the unchanged distance kernels of tree X and then tree Y into two float32 scratch
+// buffers on the device; kernels_compare.h reduces them.  Device scratch is bounded by the chunk, host memory by the
+// histogram: nothing grows with the pair count.
+constexpr int64_t kCompareChunkTriangle = (int64_t)1 << 25;   // 2 x 128 MiB of float32 distances
+constexpr int64_t kCompareChunkPairs = (int64_t)1 << 22;      // + 2 x 64 MiB of uploaded int64 pairs
+
+static int compare_hist_args(const double *edges_x, int32_t bins_x, const double *edges_y, int32_t bins_y, const int64_t *out_hist)
+{
+    if (!edges_x && !edges_y && !out_hist) return ST_OK;
+    if (!edges_x || !edges_y || !out_hist) return fail(ST_ERR_ARG, "edges_x, edges_y and out_hist must all be given or all be NULL");
+    if (bins_x < 1 || bins_y < 1) return fail(ST_ERR_ARG, "bins_x and bins_y must be >= 1");
+    if ((int64_t)bins_x * bins_y > kCmpMaxCells)
+        return fail(ST_ERR_ARG, "histogram of " + std::to_string((int64_t)bins_x * bins_y) + " cells: at most " + std::to_string(kCmpMaxCells));
+    const double *edges[2] = {edges_x, edges_y};
+    const int32_t bins[2] = {bins_x, bins_y};
+    for (int a = 0; a < 2; a++) {
+        const double *e = edges[a];
+        for (int32_t i = 0; i <= bins[a]; i++) {
+            if (!std::isfinite(e[i])) return fail(ST_ERR_ARG, "histogram edges must be finite");
+            if (i > 0 && e[i] < e[i - 1]) return fail(ST_ERR_ARG, "histogram edges must be monotonically increasing");
+        }
+        if (!(e[0] < e[bins[a]])) return fail(ST_ERR_ARG, "the first histogram edge must be below the last");
+    }
+    return ST_OK;
+}
+
+// ids on the host, before anything is launched: ST_ERR_BOUNDS with the id the reference reports (MuchTree.pyx:897-903)
+static int compare_check_ids(const int64_t *ids, int64_t n, int64_t n_nodes, int64_t *bad_id)
+{
+    Fault f = kFaultInit;
+    for (int64_t i = 0; i < n; i++) {
+        const long long v = ids[i];
+        if (v < 0 || v >= n_nodes) {
+            f.max_bad = std::max(f.max_bad, v);
+            f.min_bad = std::min(f.min_bad, v);
+        }
+    }
+    return report_fault(n_nodes, f, bad_id);
+}
+
+static int compare_trees_args(st_tree *tx, st_tree *ty)
+{
+    if (!tx || !ty) return fail(ST_ERR_ARG, "tree_x or tree_y is NULL");
+    if (tx->device != ty->device)
+        return fail(ST_ERR_ARG, "tree_x is on device " + std::to_string(tx->device) + ", tree_y on device " + std::to_string(ty->device) +
+                                    ": both trees must live on the same device");
+    return ST_OK;
+}
+
+static void compare_empty(st_pair_moments *out, int64_t *out_hist, int32_t bins_x, int32_t bins_y)
+{
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    *out = st_pair_moments{0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, nan, nan, nan, nan};
+    if (out_hist) std::memset(out_hist, 0, (size_t)bins_x * (size_t)bins_y * 8);
+}
+
+// count pairs in chunks of `chunk`: prep(stream, off, c) stages what chunk [off, off + c) needs, src_x(off) / src_y(off)
+// are its pair sources in tree X / Y.  `extra` device bytes are handed to `setup` once (the caller's ids or pairs).
+template <typename Setup, typename Prep, typename SrcX, typename SrcY>
+static int compare_run(st_tree *tx, st_tree *ty, int64_t count, int64_t chunk, size_t extra, Setup setup, Prep prep, SrcX src_x,
+                       SrcY src_y, const double *edges_x, int32_t bins_x, const double *edges_y, int32_t bins_y,
+                       st_pair_moments *out, int64_t *out_hist, int64_t *bad_id)
+{
+    ST_DEVICE(tx->device);
+    // both trees live on one device and so share its staging pipe and that pipe's mutex (host_tree.h): one lock,
+    // also when tree_x == tree_y; distinct mutexes (not possible today) would be taken in address order
+    std::mutex *ma = &tx->dp->m, *mb = &ty->dp->m;
+    if (mb < ma) std::swap(ma, mb);
+    std::unique_lock<std::mutex> lock_a(*ma), lock_b;
+    if (mb != ma) lock_b = std::unique_lock<std::mutex>(*mb);
+
+    const bool want_hist = out_hist != nullptr;
+    const int cells = want_hist ? bins_x * bins_y : 0;
+    const int n_edges = want_hist ? bins_x + bins_y + 2 : 0;
+    chunk = std::min(chunk, count);
+    // one device block: x | y | partials | final | shift | edges | histogram | caller's data
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_y = up((size_t)chunk * 4), o_part = o_y + up((size_t)chunk * 4);
+    const size_t o_final = o_part + up(sizeof(CmpPartial) * kCmpBlocks), o_shift = o_final + up(sizeof(CmpPartial));
+    const size_t o_edges = o_shift + up(16), o_hist = o_edges + up((size_t)n_edges * 8);
+    const size_t o_extra = o_hist + up((size_t)cells * 8), total = o_extra + up(extra);
+    char *d = nullptr;
+    hipStream_t s = nullptr;
+    auto cleanup = [&]() {
+        if (s) (void)hipStreamSynchronize(s);
+        (void)hipFree(d);
+        if (s) (void)hipStreamDestroy(s);
+    };
+    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d), total);
+    if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare setup: ") + hipGetErrorString(e)); }
+    float *d_x = reinterpret_cast<float *>(d), *d_y = reinterpret_cast<float *>(d + o_y);
+    CmpPartial *d_part = reinterpret_cast<CmpPartial *>(d + o_part), *d_final = reinterpret_cast<CmpPartial *>(d + o_final);
+    double *d_shift = reinterpret_cast<double *>(d + o_shift), *d_edges = reinterpret_cast<double *>(d + o_edges);
+    unsigned long long *d_hist = reinterpret_cast<unsigned long long *>(d + o_hist);
+    char *d_extra = d + o_extra;
+    CmpHist H{d_edges, d_edges + (want_hist ? bins_x + 1 : 0), bins_x, bins_y, 0, d_hist};
+    size_t lds = 0;
+    if (want_hist) {
+        lds = (size_t)((cells + 1) & ~1) * 4;
+        if (lds + (size_t)n_edges * 8 <= 128 * 1024) {      // edges beside the counters; else the kernel reads them from HBM (L2)
+            lds += (size_t)n_edges * 8;
+            H.edges_in_lds = 1;
+        }
+        e = hipMemcpyAsync(d_edges, edges_x, (size_t)(bins_x + 1) * 8, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_edges + bins_x + 1, edges_y, (size_t)(bins_y + 1) * 8, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemsetAsync(d_hist, 0, (size_t)cells * 8, s);
+        if (e == hipSuccess && lds > 64 * 1024 - 1024)
+            e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_pair_moments<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    }
+    if (e == hipSuccess) e = setup(d_extra, s);
+    if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare setup: ") + hipGetErrorString(e)); }
+    if (begin_host_faults(tx, s) != ST_OK || (ty != tx && begin_host_faults(ty, s) != ST_OK)) { cleanup(); return ST_ERR_HIP; }
+    for (int64_t off = 0; off < count; off += chunk) {
+        const int64_t c = std::min(chunk, count - off);
+        e = prep(d_extra, s, off, c);
+        if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare upload: ") + hipGetErrorString(e)); }
+        int rc = enqueue_src(tx, src_x(d_extra, off), c, DistSink{nullptr, d_x}, MrcaSink{nullptr, nullptr}, tx->d_fault_host, s);
+        if (rc == ST_OK)
+            rc = enqueue_src(ty, src_y(d_extra, off), c, DistSink{nullptr, d_y}, MrcaSink{nullptr, nullptr}, ty->d_fault_host, s);
+        if (rc != ST_OK) { const std::string msg = g_last_error; cleanup(); return fail(rc, msg); }
+        if (off == 0)
+            hipLaunchKernelGGL(k_pair_shift, dim3(1), dim3(kCmpThreads), 0, s, d_x, d_y, (int)std::min<int64_t>(c, kCmpShiftPairs), d_shift);
+        if (want_hist)
+            hipLaunchKernelGGL(k_pair_moments<true>, dim3(kCmpBlocks), dim3(kCmpThreads), lds, s, d_x, d_y, (long long)c, d_shift,
+                               off == 0 ? 1 : 0, d_part, H);
+        else
+            hipLaunchKernelGGL(k_pair_moments<false>, dim3(kCmpBlocks), dim3(kCmpThreads), 0, s, d_x, d_y, (long long)c, d_shift,
+                               off == 0 ? 1 : 0, d_part, H);
+        e = hipGetLastError();
+        if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare launch: ") + hipGetErrorString(e)); }
+    }
+    hipLaunchKernelGGL(k_pair_moments_final, dim3(1), dim3(64), 0, s, d_part, kCmpBlocks, d_final);
+    CmpPartial fin;
+    double shift[2];
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&fin, d_final, sizeof fin, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(shift, d_shift, sizeof shift, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && want_hist) e = hipMemcpyAsync(out_hist, d_hist, (size_t)cells * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare read-back: ") + hipGetErrorString(e)); }
+    Fault fx = kFaultInit, fy = kFaultInit;
+    int rc = end_host_faults(tx, s, fx);
+    if (rc == ST_OK && ty != tx) rc = end_host_faults(ty, s, fy);
+    cleanup();
+    if (rc != ST_OK) return rc;
+    rc = report_fault(tx->n_nodes, fx, bad_id);      // (not expected: the ids were checked on the host)
+    if (rc == ST_OK) rc = report_fault(ty->n_nodes, fy, bad_id);
+    if (rc != ST_OK) return rc;
+    *out = st_pair_moments{count, shift[0], shift[1], fin.sx, fin.sy, fin.sxx, fin.syy, fin.sxy, fin.min_x, fin.max_x, fin.min_y, fin.max_y};
+    return ST_OK;
+}
+
+extern "C" {
+
+int st_compare_triangle_host(st_tree *tx, st_tree *ty, const int64_t *ids_x, const int64_t *ids_y, int64_t m, int64_t k_begin,
+                             int64_t k_count, const double *edges_x, int32_t bins_x, const double *edges_y, int32_t bins_y,
+                             st_pair_moments *out, int64_t *out_hist, int64_t *bad_id)
+try {
+    int rc = compare_hist_args(edges_x, bins_x, edges_y, bins_y, out_hist);
+    if (rc != ST_OK) return rc;
+    if (!out) return fail(ST_ERR_ARG, "out is NULL");
+    rc = compare_trees_args(tx, ty);
+    if (rc != ST_OK) return rc;
+    if (m < 0 || k_begin < 0 || k_count < 0) return fail(ST_ERR_ARG, "negative size");
+    if (m > 3000000000LL) return fail(ST_ERR_ARG, "m too large");
+    if (k_begin + k_count > m * (m - 1) / 2) return fail(ST_ERR_ARG, "pair range exceeds m(m-1)/2");
+    if (m > 0 && (!ids_x || !ids_y)) return fail(ST_ERR_ARG, "ids_x or ids_y is NULL");
+    if (k_count == 0) {
+        compare_empty(out, out_hist, bins_x, bins_y);
+        return ST_OK;
+    }
+    rc = compare_check_ids(ids_x, m, tx->n_nodes, bad_id);
+    if (rc == ST_OK) rc = compare_check_ids(ids_y, m, ty->n_nodes, bad_id);
+    if (rc != ST_OK) return rc;
+    auto setup = [&](char *d_extra, hipStream_t s) {
+        hipError_t e = hipMemcpyAsync(d_extra, ids_x, (size_t)m * 8, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_extra + (size_t)m * 8, ids_y, (size_t)m * 8, hipMemcpyHostToDevice, s);
+        return e;
+    };
+    auto prep = [](char *, hipStream_t, int64_t, int64_t) { return hipSuccess; };
+    auto src_x = [&](char *d_extra, int64_t off) {
+        return SrcTriangle{reinterpret_cast<const long long *>(d_extra), 1, (long long)(k_begin + off)};
+    };
+    auto src_y = [&](char *d_extra, int64_t off) {
+        return SrcTriangle{reinterpret_cast<const long long *>(d_extra) + m, 1, (long long)(k_begin + off)};
+    };
+    return compare_run(tx, ty, k_count, kCompareChunkTriangle, (size_t)m * 16, setup, prep, src_x, src_y, edges_x, bins_x, edges_y,
+                       bins_y, out, out_hist, bad_id);
+} ST_CATCH_ALL
+
+int st_compare_pairs_host(st_tree *tx, st_tree *ty, const int64_t *pairs_x, const int64_t *pairs_y, int64_t n, const double *edges_x,
+                          int32_t bins_x, const double *edges_y, int32_t bins_y, st_pair_moments *out, int64_t *out_hist,
+                          int64_t *bad_id)
+try {
+    int rc = compare_hist_args(edges_x, bins_x, edges_y, bins_y, out_hist);
+    if (rc != ST_OK) return rc;
+    if (!out) return fail(ST_ERR_ARG, "out is NULL");
+    rc = compare_trees_args(tx, ty);
+    if (rc != ST_OK) return rc;
+    if (n < 0) return fail(ST_ERR_ARG, "n < 0");
+    if (n > 0 && (!pairs_x || !pairs_y)) return fail(ST_ERR_ARG, "pairs_x or pairs_y is NULL");
+    if (n == 0) {
+        compare_empty(out, out_hist, bins_x, bins_y);
+        return ST_OK;
+    }
+    rc = compare_check_ids(pairs_x, 2 * n, tx->n_nodes, bad_id);
+    if (rc == ST_OK) rc = compare_check_ids(pairs_y, 2 * n, ty->n_nodes, bad_id);
+    if (rc != ST_OK) return rc;
+    const int64_t chunk = std::min(n, kCompareChunkPairs);
+    auto setup = [](char *, hipStream_t) { return hipSuccess; };
+    auto prep = [&](char *d_extra, hipStream_t s, int64_t off, int64_t c) {
+        hipError_t e = hipMemcpyAsync(d_extra, pairs_x + 2 * off, (size_t)c * 16, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_extra + (size_t)chunk * 16, pairs_y + 2 * off, (size_t)c * 16, hipMemcpyHostToDevice, s);
+        return e;
+    };
+    auto src_x = [](char *d_extra, int64_t) { return SrcContig{reinterpret_cast<const long long *>(d_extra)}; };
+    auto src_y = [&](char *d_extra, int64_t) { return SrcContig{reinterpret_cast<const long long *>(d_extra + (size_t)chunk * 16)}; };
+    return compare_run(tx, ty, n, chunk, (size_t)chunk * 32, setup, prep, src_x, src_y, edges_x, bins_x, edges_y, bins_y, out, out_hist,
+                       bad_id);
 } ST_CATCH_ALL
 
 int st_quartets_host(st_tree *t, const int64_t *quartets, int64_t n, int64_t stride0, int64_t stride1,

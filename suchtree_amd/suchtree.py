@@ -373,6 +373,74 @@ class SuchTree(TreeNavigation):
         pairs_array = np.array(node_pairs, dtype=np.int64)
         return self.distances_bulk(pairs_array).tolist()
 
+    def _name_ids(self, names) -> np.ndarray:
+        """Leaf ids of ``names`` (NodeNotFoundError for an unknown one, as distances_by_name raises)."""
+        leaves = self.leaves
+        out = np.empty(len(names), dtype=np.int64)
+        for i, name in enumerate(names):
+            if name not in leaves:
+                raise NodeNotFoundError(name)
+            out[i] = leaves[name]
+        return out
+
+    def shared_leaves(self, other: "SuchTree") -> Tuple[list, np.ndarray, np.ndarray]:
+        """(names, ids in self, ids in other) of every leaf name present in both trees, ordered by self's leaf id.
+        An extension: the reference has no counterpart."""
+        names = [name for name, _ in sorted(self.leaves.items(), key=lambda kv: kv[1]) if name in other.leaves]
+        return names, self._name_ids(names), other._name_ids(names)
+
+    def compare_distances(self, other: "SuchTree", leaves=None, pairs=None, bins=None, range=None):
+        """Compare this tree's distances with ``other``'s over the same pairs, reduced on the GPU.
+
+        An extension: the reference has no counterpart.  It stands in for the comparison workflow of its docs
+        (docs/examples/SuchTree_examples.md, "Comparing the topologies of two large trees": random name pairs,
+        ``distances_by_name`` on both trees, then Pearson's r and a joint histogram on the host), but evaluates every
+        pair on the GPU and returns only a :class:`~suchtree_amd.compare.DistanceComparison`: x = distances here,
+        y = distances in ``other``.  The per-pair values are those of ``distances_bulk``.
+
+        ``leaves`` (all pairs of a leaf list; exclusive with ``pairs``):
+          * None: every leaf name present in both trees, ordered by this tree's leaf id (:meth:`shared_leaves`);
+          * a list of leaf names, looked up in both trees;
+          * a tuple ``(ids_self, ids_other)`` of aligned node-id arrays.
+          Pair k = (leaf j, leaf i), k = i(i-1)/2 + j, j < i: the enumeration of ``linked_distances``.
+        ``pairs``: a list of ``(name, name)`` tuples, looked up in each tree (unknown names raise as in
+        ``distances_by_name``), or a tuple of two aligned (n, 2) node-id arrays.
+        ``bins`` / ``range`` follow ``numpy.histogram2d`` (an int, two ints, or two edge arrays); ``bins=None`` skips the
+        histogram.  ``range=None`` with integer bins takes numpy's default range, the data's (min, max) widened by 0.5
+        where it is empty: that costs a second pass over all pairs (the first finds min and max).
+        Both trees must be on the same GPU (ValueError otherwise); an id out of range raises InvalidNodeError.
+        """
+        from . import compare
+        if leaves is not None and pairs is not None:
+            raise ValueError("leaves and pairs are mutually exclusive")
+        # (names and ids are resolved before either tree is touched on the GPU)
+        if pairs is not None:
+            if isinstance(pairs, tuple) and len(pairs) == 2 and all(isinstance(p, np.ndarray) for p in pairs):
+                px, py = (np.ascontiguousarray(p, dtype=np.int64) for p in pairs)
+            else:
+                if not isinstance(pairs, list):
+                    raise TypeError("pairs must be a list of (name, name) tuples or a tuple of two (n, 2) id arrays")
+                for i, p in enumerate(pairs):
+                    if len(p) != 2 or not isinstance(p[0], str) or not isinstance(p[1], str):
+                        raise TypeError("Pair {i}: both elements must be strings".format(i=str(i)))
+                flat = [name for p in pairs for name in p]
+                px = self._name_ids(flat).reshape(-1, 2)
+                py = other._name_ids(flat).reshape(-1, 2)
+            dx, dy = self._device_tree(), other._device_tree()
+            return compare.run(lambda edges: dx.compare_pairs_host(dy, px, py, edges=edges), bins, range)
+        if leaves is None:
+            _, ids_x, ids_y = self.shared_leaves(other)
+        elif isinstance(leaves, tuple) and len(leaves) == 2:
+            ids_x, ids_y = (np.ascontiguousarray(v, dtype=np.int64) for v in leaves)
+        else:
+            names = list(leaves)
+            ids_x, ids_y = self._name_ids(names), other._name_ids(names)
+        if ids_x.ndim != 1 or ids_x.shape != ids_y.shape:
+            raise ValueError("the two id lists must be 1-D and of equal length")
+        dx, dy = self._device_tree(), other._device_tree()
+        return compare.run(lambda edges: dx.compare_triangle_host(dy, ids_x, ids_y, edges=edges), bins, range,
+                           n_leaves=int(len(ids_x)))
+
     def common_ancestor(self, a: Union[int, str], b: Union[int, str]) -> int:
         """Most recent common ancestor of two nodes (MuchTree.pyx:1128-1149)."""
         node_a, node_b = self._validate_node_pair(a, b)
