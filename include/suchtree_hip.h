@@ -37,7 +37,8 @@ extern "C" {
  * ABI version: bumped whenever an exported struct grows, or an export, option or constant goes away.  A caller built against
  * an older header must not be handed a larger st_tree_info: compare ST_API_VERSION with st_api_version() at load (the ctypes
  * binding does) and use st_tree_info_get_sized, which writes at most the bytes the caller says it has.
- *   7: st_compare_triangle_host, st_compare_pairs_host and struct st_pair_moments added.
+ *   7: st_compare_triangle_host, st_compare_pairs_host and struct st_pair_moments added; later, without a bump (additive):
+ *      st_clade_plan, st_compare_clades_host, struct st_clade_segment and the ST_CLADE_* constants.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -339,6 +340,53 @@ int st_compare_triangle_host(st_tree *tree_x, st_tree *tree_y, const int64_t *id
 int st_compare_pairs_host(st_tree *tree_x, st_tree *tree_y, const int64_t *pairs_x, const int64_t *pairs_y, int64_t n,
                           const double *edges_x, int32_t bins_x, const double *edges_y, int32_t bins_y,
                           st_pair_moments *out, int64_t *out_hist, int64_t *bad_id);
+
+/*
+ * Every clade at once: the moments of linked distances of every node of a clade tree (tree_y), in one pass over the pairs.
+ * Links j = 0 .. n_links-1 are given in rank order: link j is leaf ids_y[j] of the clade tree and node ids_x[j] of
+ * tree_x.  The pairs of node v are the pairs of links whose clade-side leaves both lie under v, each evaluated as
+ * (lower rank, higher rank) in both trees -- the orientation of st_compare_triangle_host over the links under v in rank
+ * order, so every node's per-pair values are bit-identical to that call's.
+ *
+ * The pairs are cut into segments (st_clade_plan): links are permuted so that every node's links are one contiguous
+ * range; a rectangle of node v holds the pairs between one child's links and the links of v's later children, a
+ * triangle of leaf l the pairs of the links that share l.  Every pair lies in exactly one segment; a node's pairs are
+ * the segments of its subtree.  With max_links >= 0 only nodes with at most max_links links get their segments.
+ *
+ * Parent arrays: int32, n_nodes entries, -1 at the one root; children of a node are taken in increasing id order.
+ * A parent array that is not one rooted tree is ST_ERR_TREE; a link leaf id outside [0, n_nodes) ST_ERR_BOUNDS with
+ * *bad_id; a link leaf id that is not a leaf ST_ERR_ARG.  No counterpart in the reference.
+ */
+#define ST_CLADE_RECT 0       /* segment kind: rows x cols */
+#define ST_CLADE_TRI  1       /* segment kind: all pairs within rows (cols unused) */
+#define ST_CLADE_TILE 8192    /* pairs per tile of the clade reduction; chunk_pairs must be a multiple of it */
+typedef struct st_clade_segment {
+    int64_t first_pair;            /* global index k of its first pair */
+    int64_t n_pairs;
+    int32_t kind;                  /* ST_CLADE_RECT / ST_CLADE_TRI */
+    int32_t node;                  /* the node (rectangle) or leaf (triangle) whose pairs these are */
+    int32_t row_begin, row_end;    /* positions in the permuted link order */
+    int32_t col_begin, col_end;
+} st_clade_segment;
+
+/* Host only.  out_perm[p] = rank of the link at position p (n_links entries); out_begin / out_count (n_nodes each):
+ * node v's links are positions [out_begin[v], out_begin[v] + out_count[v]); out_leaves (n_nodes, may be NULL): leaves
+ * under v.  out_segs (room for seg_capacity >= 2 n_nodes entries, may be NULL to count only) receives the non-empty
+ * segments in pair order, *out_n_segs their number and *out_total_pairs the pairs they hold. */
+int st_clade_plan(const int32_t *parent, int64_t n_nodes, const int64_t *link_leaf, int64_t n_links, int64_t max_links,
+                  int64_t *out_perm, int64_t *out_begin, int64_t *out_count, int64_t *out_leaves,
+                  st_clade_segment *out_segs, int64_t seg_capacity, int64_t *out_n_segs, int64_t *out_total_pairs,
+                  int64_t *bad_id);
+/* out (n_nodes entries): node v's moments; n = -1 and NaN elsewhere for a node with more than max_links links (not
+ * computed; max_links < 0: no cap), n = 0 with zero sums and NaN min / max for a node with fewer than two.  out_count
+ * (n_nodes, may be NULL): links under each node.  n_nodes must be tree_y's node count.  chunk_pairs: pairs per device
+ * chunk, 0 = the default, else a positive multiple of ST_CLADE_TILE.  Trees and ids as for st_compare_triangle_host.
+ * Each tile-sized piece of a segment is summed about its own first pair in one fixed order, pieces are merged into
+ * segments and segments into nodes (children first, in increasing id order, then the node's own segments) with the
+ * shifted pairwise update on the host: results do not depend on the device, the grid or chunk_pairs. */
+int st_compare_clades_host(st_tree *tree_x, st_tree *tree_y, const int32_t *parent, int64_t n_nodes, const int64_t *ids_x,
+                           const int64_t *ids_y, int64_t n_links, int64_t max_links, int64_t chunk_pairs,
+                           st_pair_moments *out, int64_t *out_count, int64_t *bad_id);
 
 /*
  * Quartet topologies: for each row (a,b,c,d) of the int64 (n,4) view the row re-ordered so

@@ -42,8 +42,15 @@ SYMBOLS = (
     "st_tree_set_option", "st_triangle_device", "st_triangle_host", "st_grid_host", "st_knn_host",
     "st_quartets_host", "st_graph_matrices_host", "st_newick_open", "st_newick_fill", "st_newick_close",
     "st_host_depths", "st_link_sample_pairs", "st_bucket_moments", "st_device_malloc", "st_device_free", "st_memcpy_h2d", "st_memcpy_d2h",
-    "st_device_synchronize", "st_compare_triangle_host", "st_compare_pairs_host",
+    "st_device_synchronize", "st_compare_triangle_host", "st_compare_pairs_host", "st_clade_plan", "st_compare_clades_host",
 )
+
+CLADE_RECT, CLADE_TRI = 0, 1     # include/suchtree_hip.h: ST_CLADE_RECT / ST_CLADE_TRI
+CLADE_TILE = 8192                # ST_CLADE_TILE: pairs per tile of the clade reduction
+
+# st_clade_segment as a numpy record
+CLADE_SEGMENT = np.dtype([("first_pair", np.int64), ("n_pairs", np.int64), ("kind", np.int32), ("node", np.int32),
+                          ("row_begin", np.int32), ("row_end", np.int32), ("col_begin", np.int32), ("col_end", np.int32)])
 
 
 class PairMoments(ctypes.Structure):
@@ -53,6 +60,12 @@ class PairMoments(ctypes.Structure):
 
     def as_dict(self):
         return {k: (int(getattr(self, k)) if k == "n" else float(getattr(self, k))) for k, _ in self._fields_}
+
+
+# st_pair_moments as a numpy record (arrays of them: st_compare_clades_host)
+PAIR_MOMENTS = np.dtype([("n", np.int64)] + [(k, np.float64) for k in
+                                            "shift_x shift_y sx sy sxx syy sxy min_x max_x min_y max_y".split()])
+assert PAIR_MOMENTS.itemsize == ctypes.sizeof(PairMoments)
 
 
 class TreeInfo(ctypes.Structure):
@@ -211,6 +224,9 @@ def load():
                                                ctypes.POINTER(PairMoments), vp, ctypes.POINTER(i64)]
         L.st_compare_pairs_host.argtypes = [vp, vp, vp, vp, i64, vp, ctypes.c_int32, vp, ctypes.c_int32,
                                             ctypes.POINTER(PairMoments), vp, ctypes.POINTER(i64)]
+        L.st_clade_plan.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64),
+                                    ctypes.POINTER(i64)]
+        L.st_compare_clades_host.argtypes = [vp, vp, vp, i64, vp, vp, i64, i64, i64, vp, vp, ctypes.POINTER(i64)]
         L.st_graph_matrices_host.argtypes = [i32, i64, i64, vp, vp, vp, vp, vp]
         L.st_newick_open.argtypes = [ctypes.c_char_p, i64, ctypes.POINTER(vp), ctypes.POINTER(i64),
                                      ctypes.POINTER(i64), ctypes.POINTER(i64),
@@ -441,6 +457,26 @@ def device_count():
 
 def _ptr(a):
     return None if a is None else ctypes.c_void_p(a.ctypes.data)
+
+
+def clade_plan(parent, link_leaf, max_links=None):
+    """st_clade_plan (host only): the clade-contiguous permutation of the links (given in rank order by their clade-tree
+    leaf id), each node's link range / count / leaf count, the segments (a CLADE_SEGMENT array in pair order) and the
+    pair count.  Returns a dict of numpy arrays and ints."""
+    L = load()
+    parent = np.ascontiguousarray(parent, dtype=np.int32)
+    link_leaf = np.ascontiguousarray(link_leaf, dtype=np.int64)
+    n, m = int(parent.shape[0]), int(link_leaf.shape[0])
+    perm = np.empty(m, dtype=np.int64)
+    begin, count, leaves = (np.empty(n, dtype=np.int64) for _ in range(3))
+    segs = np.empty(2 * max(n, 1), dtype=CLADE_SEGMENT)
+    n_segs, total, bad = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    rc = L.st_clade_plan(_ptr(parent), n, _ptr(link_leaf) if m else None, m, -1 if max_links is None else int(max_links),
+                         _ptr(perm) if m else None, _ptr(begin), _ptr(count), _ptr(leaves), _ptr(segs), len(segs),
+                         ctypes.byref(n_segs), ctypes.byref(total), ctypes.byref(bad))
+    check(rc, tree_size=n, bad_id=int(bad.value))
+    return {"perm": perm, "begin": begin, "count": count, "leaves": leaves, "segments": segs[: n_segs.value].copy(),
+            "total_pairs": int(total.value)}
 
 
 def host_table_plan(parent, distance, strategy="auto", table_mb=0):
@@ -697,6 +733,29 @@ class DeviceTree:
                                              _ptr(ex), bx, _ptr(ey), by, ctypes.byref(out), _ptr(hist), ctypes.byref(bad))
         self._compare_check(other, rc, bad)
         return out, hist
+
+    def compare_clades_host(self, other, parent, ids_x, ids_y, max_links=None, chunk_pairs=0):
+        """st_compare_clades_host: one PairMoments-shaped record per node of ``other`` (the clade tree, whose int32
+        ``parent`` array is given), x = this tree, y = ``other``, over the links ``ids_x`` / ``ids_y`` (rank order).
+        Returns (structured array of st_pair_moments fields, per-node link counts); n = -1 marks a node over
+        ``max_links``."""
+        parent = np.ascontiguousarray(parent, dtype=np.int32)
+        ids_x = np.ascontiguousarray(ids_x, dtype=np.int64)
+        ids_y = np.ascontiguousarray(ids_y, dtype=np.int64)
+        if ids_x.ndim != 1 or ids_x.shape != ids_y.shape:
+            raise ValueError("ids_x and ids_y must be 1-D arrays of equal length")
+        n, m = int(parent.shape[0]), int(ids_x.shape[0])
+        out = np.zeros(n, dtype=PAIR_MOMENTS)
+        count = np.zeros(n, dtype=np.int64)
+        bad = ctypes.c_int64(0)
+        rc = self._lib.st_compare_clades_host(self.handle, other.handle, _ptr(parent), n, _ptr(ids_x) if m else None,
+                                              _ptr(ids_y) if m else None, m, -1 if max_links is None else int(max_links),
+                                              int(chunk_pairs), _ptr(out), _ptr(count), ctypes.byref(bad))
+        bad = int(bad.value)
+        if rc == ST_ERR_BOUNDS and not (0 <= bad < self.size):
+            check(rc, tree_size=self.size, bad_id=bad)
+        check(rc, tree_size=other.size, bad_id=bad)
+        return out, count
 
     def triangle_device(self, d_ids, m, k_begin, k_count, d_out_dist=0, d_out_mrca=0, stream=0, id_stride=1):
         rc = self._lib.st_triangle_device(self.handle, ctypes.c_void_p(d_ids), int(m), int(id_stride),

@@ -12,7 +12,7 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["DistanceComparison"]
+__all__ = ["DistanceComparison", "CladeComparisons"]
 
 
 @dataclass(frozen=True)
@@ -146,3 +146,85 @@ def run(call, bins, range, n_leaves=None):
         xedges, yedges = histogram_edges(bins, range, None)
     m, hist = call((xedges, yedges))
     return DistanceComparison.from_moments(m, hist, xedges, yedges, n_leaves=n_leaves)
+
+
+def pearson_pvalue(r, n):
+    """Two-sided p of ``scipy.stats.pearsonr`` for correlation ``r`` over ``n`` pairs, vectorised: 2 * betaincc(a, a,
+    (|r| + 1) / 2) with a = n/2 - 1, 1.0 where n == 2 (NaN where r is), NaN where n < 2.  All NaN without scipy."""
+    r = np.asarray(r, dtype=np.float64)
+    n = np.asarray(n, dtype=np.float64)
+    p = np.full(np.broadcast(r, n).shape, np.nan)
+    try:
+        from scipy import special
+    except ImportError:
+        return p
+    big = (n > 2) & ~np.isnan(r)
+    if big.any():
+        ab = n[big] / 2 - 1
+        p[big] = 2 * special.betaincc(ab, ab, (np.abs(np.clip(r[big], -1.0, 1.0)) + 1) / 2)
+    p[(n == 2) & ~np.isnan(r)] = 1.0
+    return p
+
+
+_SUMS = ("shift_x", "shift_y", "sx", "sy", "sxx", "syy", "sxy")
+
+
+class CladeComparisons:
+    """One row per clade: the summary :meth:`SuchLinkedTrees.linked_distances_summary` gives after subsetting to that
+    clade (SuchLinkedTrees.linked_distances_by_clade), as numpy columns.
+
+    ``nodes`` are clade-tree node ids in ``get_internal_nodes()`` order; ``n_leaves`` the clade's leaf count
+    (``subset_b_size`` / ``subset_a_size``), ``n_links`` its ``subset_n_links``, ``n_pairs`` = n_links (n_links - 1) / 2.
+    x is always TreeA and y TreeB: ``mean_a`` / ``var_a`` / ``min_a`` / ``max_a`` describe the TreeA column,
+    ``*_b`` the TreeB column, ``cov`` their population covariance, ``pearson_r`` Pearson's r (NaN where a variance is 0)
+    and ``pvalue`` the two-sided p of ``scipy.stats.pearsonr`` (NaN when scipy is not installed).  The shifted raw sums
+    ``shift_x`` ... ``sxy`` (x = TreeA) are kept, so :meth:`comparison` rebuilds any row as a DistanceComparison.
+    """
+
+    def __init__(self, nodes, n_leaves, n_links, sums, min_a, max_a, min_b, max_b, tree="B"):
+        self.tree = tree
+        self.nodes = np.asarray(nodes, dtype=np.int64)
+        self.n_leaves = np.asarray(n_leaves, dtype=np.int64)
+        self.n_links = np.asarray(n_links, dtype=np.int64)
+        self.n_pairs = self.n_links * (self.n_links - 1) // 2
+        for k in _SUMS:
+            setattr(self, k, np.asarray(sums[k], dtype=np.float64))
+        self.min_a, self.max_a = np.asarray(min_a, dtype=np.float64), np.asarray(max_a, dtype=np.float64)
+        self.min_b, self.max_b = np.asarray(min_b, dtype=np.float64), np.asarray(max_b, dtype=np.float64)
+        # the formulas of DistanceComparison.from_sums, elementwise in the same order (the same bits as comparison())
+        n = self.n_pairs.astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            self.mean_a = self.shift_x + self.sx / n
+            self.mean_b = self.shift_y + self.sy / n
+            self.var_a = np.maximum((self.sxx - self.sx * self.sx / n) / n, 0.0)
+            self.var_b = np.maximum((self.syy - self.sy * self.sy / n) / n, 0.0)
+            self.cov = (self.sxy - self.sx * self.sy / n) / n
+            ok = (self.var_a > 0) & (self.var_b > 0)
+            self.pearson_r = np.where(ok, np.clip(self.cov / np.sqrt(self.var_a * self.var_b), -1.0, 1.0), np.nan)
+        self.pvalue = pearson_pvalue(self.pearson_r, self.n_pairs)
+        self._row = None
+
+    def __len__(self):
+        return len(self.nodes)
+
+    def comparison_at(self, i) -> DistanceComparison:
+        """Row i as a DistanceComparison (``n_leaves`` = the row's link count, as linked_distances_summary reports)."""
+        return DistanceComparison.from_sums(int(self.n_pairs[i]), *(float(getattr(self, k)[i]) for k in _SUMS),
+                                            self.min_a[i], self.max_a[i], self.min_b[i], self.max_b[i],
+                                            n_leaves=int(self.n_links[i]))
+
+    def comparison(self, node) -> DistanceComparison:
+        """The row of clade ``node`` as a DistanceComparison (KeyError for a node without a row)."""
+        if self._row is None:
+            self._row = {int(v): i for i, v in enumerate(self.nodes)}
+        return self.comparison_at(self._row[int(node)])
+
+    def to_dataframe(self):
+        """The table of the per-clade notebook loop: ``name`` = "clade_<id>", ``n_links``, ``n_leafs``, ``r``, ``p``,
+        then the other columns (pandas, imported here)."""
+        import pandas as pd
+        cols = {"name": ["clade_%d" % v for v in self.nodes], "n_links": self.n_links, "n_leafs": self.n_leaves,
+                "r": self.pearson_r, "p": self.pvalue, "node": self.nodes, "n_pairs": self.n_pairs}
+        for k in ("mean_a", "mean_b", "var_a", "var_b", "cov", "min_a", "max_a", "min_b", "max_b") + _SUMS:
+            cols[k] = getattr(self, k)
+        return pd.DataFrame(cols)

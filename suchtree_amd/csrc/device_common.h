@@ -86,6 +86,62 @@ struct SrcTriangle {
     }
 };
 
+// Clade segments (st_compare_clades_host): pair k lies in one segment of a clade plan -- a rectangle (rows x cols of
+// link positions) or a triangle (all pairs within rows) -- and is evaluated as (lower rank, higher rank).  `ids` is this
+// tree's node id per link position (links permuted so that every clade is one range), `rank` each position's rank.
+// The segment of k is found by a binary search over the segments that meet k's tile of 2^kCladeTileShift pairs only
+// (tile[t].seg = the segment of pair t * 2^kCladeTileShift): one or two steps inside a large segment, at most
+// kCladeTileShift + 1 among tiny ones -- never one over all segments.  seg[] ends with a sentinel whose first = the
+// pair count.  Within a segment consecutive lanes share a row and walk the columns, as in the triangle.
+constexpr int kCladeTileShift = 13;      // 8192 pairs per tile (ST_CLADE_TILE)
+struct CladeSeg {
+    long long first;       // k of the segment's first pair
+    int r0, r1;            // row positions [r0, r1)
+    int c0, c1;            // column positions [c0, c1); c0 < 0: the triangle over [r0, r1)
+};
+struct CladeTile {
+    int seg;               // the segment of the tile's first pair (the sentinel's index past the last tile)
+    int piece;             // index of the tile's first piece (kernels_clades.h)
+};
+struct SrcSegments {
+    const int *ids;
+    const int *rank;
+    const CladeSeg *seg;
+    const CladeTile *tile;
+    long long k0;          // first pair index of this launch
+    __device__ __forceinline__ void load(long long i, long long &a, long long &b) const
+    {
+        const long long k = k0 + i;
+        const long long t = k >> kCladeTileShift;
+        int lo = tile[t].seg, hi = tile[t + 1].seg;      // largest s in [lo, hi] with seg[s].first <= k
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (seg[mid].first <= k) lo = mid;
+            else hi = mid - 1;
+        }
+        const CladeSeg g = seg[lo];
+        const long long l = k - g.first;
+        int p, q;
+        if (g.c0 >= 0) {
+            const long long nc = g.c1 - g.c0;
+            long long r = (long long)((double)l / (double)nc);
+            if (r * nc > l) r--;
+            else if ((r + 1) * nc <= l) r++;
+            p = g.r0 + (int)r;
+            q = g.c0 + (int)(l - r * nc);
+        } else {      // (the enumeration of SrcTriangle)
+            long long row = (long long)((1.0 + sqrt(1.0 + 8.0 * (double)l)) * 0.5);
+            if (row * (row - 1) / 2 > l) row--;
+            if ((row + 1) * row / 2 <= l) row++;
+            p = g.r0 + (int)(l - row * (row - 1) / 2);
+            q = g.r0 + (int)row;
+        }
+        if (rank[p] > rank[q]) { const int s = p; p = q; q = s; }
+        a = ids[p];
+        b = ids[q];
+    }
+};
+
 // Grid generator: element e = e0 + i of an n_rows x n_cols grid (C order) is the pair
 // (rows[r], cols[c]), r = e / n_cols, c = e % n_cols.  `symmetric` (rows and cols are the same
 // id list): below the diagonal the pair is taken in the order of its mirror image above it,

@@ -131,6 +131,7 @@ private:
 #include "device_common.h"
 #include "kernels_misc.h"
 #include "kernels_compare.h"
+#include "kernels_clades.h"
 
 
 // --------------------------------------------------------------------------
@@ -964,12 +965,93 @@ static void compare_empty(st_pair_moments *out, int64_t *out_hist, int32_t bins_
     if (out_hist) std::memset(out_hist, 0, (size_t)bins_x * (size_t)bins_y * 8);
 }
 
+// The moments / 2-D histogram reduction of st_compare_triangle_host / st_compare_pairs_host (kernels_compare.h), as a
+// reducer of compare_run: bytes(chunk) device bytes of its own, start() once, chunk() per chunk of distances, finish()
+// enqueues the read-back, done() fills the result once the stream has drained.
+struct MomentsReduce {
+    const double *edges_x, *edges_y;
+    int32_t bins_x, bins_y;
+    st_pair_moments *out;
+    int64_t *out_hist;
+    int64_t count = 0;
+    bool want_hist = false;
+    int cells = 0, n_edges = 0;
+    size_t o_final = 0, o_shift = 0, o_edges = 0, o_hist = 0, lds = 0;
+    CmpPartial *d_part = nullptr, *d_final = nullptr;
+    double *d_shift = nullptr;
+    CmpHist H{};
+    CmpPartial fin{};
+    double shift[2] = {0.0, 0.0};
+
+    static size_t up(size_t b) { return (b + 255) & ~(size_t)255; }
+    size_t bytes(int64_t)
+    {
+        want_hist = out_hist != nullptr;
+        cells = want_hist ? bins_x * bins_y : 0;
+        n_edges = want_hist ? bins_x + bins_y + 2 : 0;
+        o_final = up(sizeof(CmpPartial) * kCmpBlocks);
+        o_shift = o_final + up(sizeof(CmpPartial));
+        o_edges = o_shift + up(16);
+        o_hist = o_edges + up((size_t)n_edges * 8);
+        return o_hist + up((size_t)cells * 8);
+    }
+    hipError_t start(char *d, int64_t total, hipStream_t s)
+    {
+        count = total;
+        d_part = reinterpret_cast<CmpPartial *>(d);
+        d_final = reinterpret_cast<CmpPartial *>(d + o_final);
+        d_shift = reinterpret_cast<double *>(d + o_shift);
+        double *d_edges = reinterpret_cast<double *>(d + o_edges);
+        H = CmpHist{d_edges, d_edges + (want_hist ? bins_x + 1 : 0), bins_x, bins_y, 0, reinterpret_cast<unsigned long long *>(d + o_hist)};
+        hipError_t e = hipSuccess;
+        if (want_hist) {
+            lds = (size_t)((cells + 1) & ~1) * 4;
+            if (lds + (size_t)n_edges * 8 <= 128 * 1024) {      // edges beside the counters; else the kernel reads them from HBM (L2)
+                lds += (size_t)n_edges * 8;
+                H.edges_in_lds = 1;
+            }
+            e = hipMemcpyAsync(d_edges, edges_x, (size_t)(bins_x + 1) * 8, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_edges + bins_x + 1, edges_y, (size_t)(bins_y + 1) * 8, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = hipMemsetAsync(H.out, 0, (size_t)cells * 8, s);
+            if (e == hipSuccess && lds > 64 * 1024 - 1024)
+                e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_pair_moments<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        }
+        return e;
+    }
+    hipError_t chunk(const float *d_x, const float *d_y, int64_t off, int64_t c, hipStream_t s)
+    {
+        if (off == 0)
+            hipLaunchKernelGGL(k_pair_shift, dim3(1), dim3(kCmpThreads), 0, s, d_x, d_y, (int)std::min<int64_t>(c, kCmpShiftPairs), d_shift);
+        if (want_hist)
+            hipLaunchKernelGGL(k_pair_moments<true>, dim3(kCmpBlocks), dim3(kCmpThreads), lds, s, d_x, d_y, (long long)c, d_shift,
+                               off == 0 ? 1 : 0, d_part, H);
+        else
+            hipLaunchKernelGGL(k_pair_moments<false>, dim3(kCmpBlocks), dim3(kCmpThreads), 0, s, d_x, d_y, (long long)c, d_shift,
+                               off == 0 ? 1 : 0, d_part, H);
+        return hipGetLastError();
+    }
+    hipError_t finish(hipStream_t s)
+    {
+        hipLaunchKernelGGL(k_pair_moments_final, dim3(1), dim3(64), 0, s, d_part, kCmpBlocks, d_final);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&fin, d_final, sizeof fin, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(shift, d_shift, sizeof shift, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && want_hist) e = hipMemcpyAsync(out_hist, H.out, (size_t)cells * 8, hipMemcpyDeviceToHost, s);
+        return e;
+    }
+    int done()
+    {
+        *out = st_pair_moments{count, shift[0], shift[1], fin.sx, fin.sy, fin.sxx, fin.syy, fin.sxy, fin.min_x, fin.max_x, fin.min_y, fin.max_y};
+        return ST_OK;
+    }
+};
+
 // count pairs in chunks of `chunk`: prep(stream, off, c) stages what chunk [off, off + c) needs, src_x(off) / src_y(off)
-// are its pair sources in tree X / Y.  `extra` device bytes are handed to `setup` once (the caller's ids or pairs).
-template <typename Setup, typename Prep, typename SrcX, typename SrcY>
+// are its pair sources in tree X / Y, `red` reduces the two chunks of distances (MomentsReduce, CladeReduce).  `extra`
+// device bytes are handed to `setup` once (the caller's ids or pairs).
+template <typename Setup, typename Prep, typename SrcX, typename SrcY, typename Reduce>
 static int compare_run(st_tree *tx, st_tree *ty, int64_t count, int64_t chunk, size_t extra, Setup setup, Prep prep, SrcX src_x,
-                       SrcY src_y, const double *edges_x, int32_t bins_x, const double *edges_y, int32_t bins_y,
-                       st_pair_moments *out, int64_t *out_hist, int64_t *bad_id)
+                       SrcY src_y, Reduce &red, int64_t *bad_id)
 {
     ST_DEVICE(tx->device);
     // both trees live on one device and so share its staging pipe and that pipe's mutex (host_tree.h): one lock,
@@ -979,16 +1061,11 @@ static int compare_run(st_tree *tx, st_tree *ty, int64_t count, int64_t chunk, s
     std::unique_lock<std::mutex> lock_a(*ma), lock_b;
     if (mb != ma) lock_b = std::unique_lock<std::mutex>(*mb);
 
-    const bool want_hist = out_hist != nullptr;
-    const int cells = want_hist ? bins_x * bins_y : 0;
-    const int n_edges = want_hist ? bins_x + bins_y + 2 : 0;
     chunk = std::min(chunk, count);
-    // one device block: x | y | partials | final | shift | edges | histogram | caller's data
+    // one device block: x | y | the reducer's | caller's data
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_y = up((size_t)chunk * 4), o_part = o_y + up((size_t)chunk * 4);
-    const size_t o_final = o_part + up(sizeof(CmpPartial) * kCmpBlocks), o_shift = o_final + up(sizeof(CmpPartial));
-    const size_t o_edges = o_shift + up(16), o_hist = o_edges + up((size_t)n_edges * 8);
-    const size_t o_extra = o_hist + up((size_t)cells * 8), total = o_extra + up(extra);
+    const size_t o_y = up((size_t)chunk * 4), o_red = o_y + up((size_t)chunk * 4);
+    const size_t o_extra = o_red + up(red.bytes(chunk)), total = o_extra + up(extra);
     char *d = nullptr;
     hipStream_t s = nullptr;
     auto cleanup = [&]() {
@@ -1000,24 +1077,8 @@ static int compare_run(st_tree *tx, st_tree *ty, int64_t count, int64_t chunk, s
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d), total);
     if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare setup: ") + hipGetErrorString(e)); }
     float *d_x = reinterpret_cast<float *>(d), *d_y = reinterpret_cast<float *>(d + o_y);
-    CmpPartial *d_part = reinterpret_cast<CmpPartial *>(d + o_part), *d_final = reinterpret_cast<CmpPartial *>(d + o_final);
-    double *d_shift = reinterpret_cast<double *>(d + o_shift), *d_edges = reinterpret_cast<double *>(d + o_edges);
-    unsigned long long *d_hist = reinterpret_cast<unsigned long long *>(d + o_hist);
     char *d_extra = d + o_extra;
-    CmpHist H{d_edges, d_edges + (want_hist ? bins_x + 1 : 0), bins_x, bins_y, 0, d_hist};
-    size_t lds = 0;
-    if (want_hist) {
-        lds = (size_t)((cells + 1) & ~1) * 4;
-        if (lds + (size_t)n_edges * 8 <= 128 * 1024) {      // edges beside the counters; else the kernel reads them from HBM (L2)
-            lds += (size_t)n_edges * 8;
-            H.edges_in_lds = 1;
-        }
-        e = hipMemcpyAsync(d_edges, edges_x, (size_t)(bins_x + 1) * 8, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_edges + bins_x + 1, edges_y, (size_t)(bins_y + 1) * 8, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemsetAsync(d_hist, 0, (size_t)cells * 8, s);
-        if (e == hipSuccess && lds > 64 * 1024 - 1024)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_pair_moments<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
+    e = red.start(d + o_red, count, s);
     if (e == hipSuccess) e = setup(d_extra, s);
     if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare setup: ") + hipGetErrorString(e)); }
     if (begin_host_faults(tx, s) != ST_OK || (ty != tx && begin_host_faults(ty, s) != ST_OK)) { cleanup(); return ST_ERR_HIP; }
@@ -1029,24 +1090,10 @@ static int compare_run(st_tree *tx, st_tree *ty, int64_t count, int64_t chunk, s
         if (rc == ST_OK)
             rc = enqueue_src(ty, src_y(d_extra, off), c, DistSink{nullptr, d_y}, MrcaSink{nullptr, nullptr}, ty->d_fault_host, s);
         if (rc != ST_OK) { const std::string msg = g_last_error; cleanup(); return fail(rc, msg); }
-        if (off == 0)
-            hipLaunchKernelGGL(k_pair_shift, dim3(1), dim3(kCmpThreads), 0, s, d_x, d_y, (int)std::min<int64_t>(c, kCmpShiftPairs), d_shift);
-        if (want_hist)
-            hipLaunchKernelGGL(k_pair_moments<true>, dim3(kCmpBlocks), dim3(kCmpThreads), lds, s, d_x, d_y, (long long)c, d_shift,
-                               off == 0 ? 1 : 0, d_part, H);
-        else
-            hipLaunchKernelGGL(k_pair_moments<false>, dim3(kCmpBlocks), dim3(kCmpThreads), 0, s, d_x, d_y, (long long)c, d_shift,
-                               off == 0 ? 1 : 0, d_part, H);
-        e = hipGetLastError();
+        e = red.chunk(d_x, d_y, off, c, s);
         if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare launch: ") + hipGetErrorString(e)); }
     }
-    hipLaunchKernelGGL(k_pair_moments_final, dim3(1), dim3(64), 0, s, d_part, kCmpBlocks, d_final);
-    CmpPartial fin;
-    double shift[2];
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&fin, d_final, sizeof fin, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(shift, d_shift, sizeof shift, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && want_hist) e = hipMemcpyAsync(out_hist, d_hist, (size_t)cells * 8, hipMemcpyDeviceToHost, s);
+    e = red.finish(s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare read-back: ") + hipGetErrorString(e)); }
     Fault fx = kFaultInit, fy = kFaultInit;
@@ -1057,9 +1104,228 @@ static int compare_run(st_tree *tx, st_tree *ty, int64_t count, int64_t chunk, s
     rc = report_fault(tx->n_nodes, fx, bad_id);      // (not expected: the ids were checked on the host)
     if (rc == ST_OK) rc = report_fault(ty->n_nodes, fy, bad_id);
     if (rc != ST_OK) return rc;
-    *out = st_pair_moments{count, shift[0], shift[1], fin.sx, fin.sy, fin.sxx, fin.syy, fin.sxy, fin.min_x, fin.max_x, fin.min_y, fin.max_y};
+    return red.done();
+}
+
+// ---- every clade at once (st_clade_plan / st_compare_clades_host) ------------------------------------------------
+static_assert((1 << kCladeTileShift) == ST_CLADE_TILE, "device_common.h: kCladeTileShift");
+constexpr int64_t kCladeChunkPairs = (int64_t)1 << 25;      // 2 x 128 MiB of float32 distances, as the triangle
+
+// The clade tree's children in increasing id order, its preorder, the permutation that makes every clade one range of
+// link positions, and the segments.  Iterative throughout (a caterpillar of 1e5 levels is fine).
+struct CladePlan {
+    std::vector<int64_t> child_off, child;       // CSR: children of v are child[child_off[v] .. child_off[v + 1])
+    std::vector<int64_t> pre;                    // preorder (children in order); reversed, every child precedes its parent
+    std::vector<int64_t> perm, begin, count, leaves;
+    std::vector<st_clade_segment> segs;          // in pair order: nodes by link count, each node's own segments together
+    std::vector<int64_t> node_seg;               // node v's segments: segs[node_seg[v] .. node_seg[v] + node_nseg[v])
+    std::vector<int32_t> node_nseg;
+    int64_t total = 0;
+};
+
+static int clade_plan(const int32_t *parent, int64_t n, const int64_t *link_leaf, int64_t L, int64_t cap, CladePlan &P,
+                      int64_t *bad_id)
+{
+    if (n < 1) return fail(ST_ERR_ARG, "n_nodes < 1");
+    if (n > INT32_MAX || L > INT32_MAX) return fail(ST_ERR_ARG, "more than 2^31 - 1 nodes or links");
+    if (L < 0) return fail(ST_ERR_ARG, "n_links < 0");
+    if (!parent || (L > 0 && !link_leaf)) return fail(ST_ERR_ARG, "parent or link_leaf is NULL");
+    int64_t root = -1;
+    P.child_off.assign(n + 1, 0);
+    for (int64_t v = 0; v < n; v++) {
+        const int64_t p = parent[v];
+        if (p == -1) {
+            if (root >= 0) return fail(ST_ERR_TREE, "parent array has more than one root");
+            root = v;
+        } else if (p < 0 || p >= n || p == v) {
+            return fail(ST_ERR_TREE, "parent[" + std::to_string(v) + "] = " + std::to_string(p) + " is not a node");
+        } else {
+            P.child_off[p + 1]++;
+        }
+    }
+    if (root < 0) return fail(ST_ERR_TREE, "parent array has no root");
+    for (int64_t v = 0; v < n; v++) P.child_off[v + 1] += P.child_off[v];
+    P.child.assign(n > 1 ? n - 1 : 0, 0);
+    {
+        std::vector<int64_t> fill(P.child_off.begin(), P.child_off.end() - 1);
+        for (int64_t v = 0; v < n; v++)
+            if (parent[v] >= 0) P.child[fill[parent[v]]++] = v;      // (increasing id order)
+    }
+    P.pre.clear();
+    P.pre.reserve(n);
+    std::vector<int64_t> stack{root};
+    while (!stack.empty()) {
+        const int64_t v = stack.back();
+        stack.pop_back();
+        P.pre.push_back(v);
+        for (int64_t i = P.child_off[v + 1] - 1; i >= P.child_off[v]; i--) stack.push_back(P.child[i]);
+        if ((int64_t)P.pre.size() > n) break;
+    }
+    if ((int64_t)P.pre.size() != n) return fail(ST_ERR_TREE, "parent array is not one rooted tree (a cycle or a detached node)");
+    auto is_leaf = [&](int64_t v) { return P.child_off[v + 1] == P.child_off[v]; };
+    // links: ids in range (as the compare calls report them), then leaves only
+    Fault f = kFaultInit;
+    for (int64_t j = 0; j < L; j++) {
+        const long long v = link_leaf[j];
+        if (v < 0 || v >= n) {
+            f.max_bad = std::max(f.max_bad, v);
+            f.min_bad = std::min(f.min_bad, v);
+        }
+    }
+    int rc = report_fault(n, f, bad_id);
+    if (rc != ST_OK) return rc;
+    P.count.assign(n, 0);
+    for (int64_t j = 0; j < L; j++) {
+        if (!is_leaf(link_leaf[j])) return fail(ST_ERR_ARG, "link " + std::to_string(j) + ": node " + std::to_string(link_leaf[j]) + " is not a leaf of the clade tree");
+        P.count[link_leaf[j]]++;
+    }
+    // leaves in preorder get consecutive position ranges; links keep rank order within a leaf
+    P.begin.assign(n, 0);
+    P.leaves.assign(n, 0);
+    int64_t pos = 0;
+    for (const int64_t v : P.pre)
+        if (is_leaf(v)) {
+            P.begin[v] = pos;
+            pos += P.count[v];
+            P.leaves[v] = 1;
+        }
+    {
+        std::vector<int64_t> cur(P.begin);
+        P.perm.assign(L, 0);
+        for (int64_t j = 0; j < L; j++) P.perm[cur[link_leaf[j]]++] = j;
+    }
+    for (int64_t i = n - 1; i >= 0; i--) {
+        const int64_t v = P.pre[i];
+        if (is_leaf(v)) continue;
+        int64_t c = 0, l = 0;
+        for (int64_t e = P.child_off[v]; e < P.child_off[v + 1]; e++) {
+            c += P.count[P.child[e]];
+            l += P.leaves[P.child[e]];
+        }
+        P.count[v] = c;
+        P.leaves[v] = l;
+        P.begin[v] = P.begin[P.child[P.child_off[v]]];
+    }
+    // segments
+    P.segs.clear();
+    P.node_seg.assign(n, 0);
+    P.node_nseg.assign(n, 0);
+    P.total = 0;
+    auto emit = [&](int32_t kind, int64_t v, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int64_t np) {
+        P.segs.push_back(st_clade_segment{P.total, np, kind, (int32_t)v, (int32_t)r0, (int32_t)r1, (int32_t)c0, (int32_t)c1});
+        P.total += np;
+        P.node_nseg[v]++;
+    };
+    // nodes by link count (ties: reverse preorder), so that the segments of the nodes within any cap are a prefix of the
+    // pair range and keep their pair indices -- hence their pieces and their bits -- whatever the cap
+    std::vector<int64_t> order(P.pre.rbegin(), P.pre.rend());
+    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return P.count[a] < P.count[b]; });
+    for (const int64_t v : order) {
+        P.node_seg[v] = (int64_t)P.segs.size();
+        if (cap >= 0 && P.count[v] > cap) continue;
+        const int64_t end = P.begin[v] + P.count[v];
+        if (is_leaf(v)) {
+            if (P.count[v] >= 2) emit(ST_CLADE_TRI, v, P.begin[v], end, 0, 0, P.count[v] * (P.count[v] - 1) / 2);
+            continue;
+        }
+        for (int64_t e = P.child_off[v]; e + 1 < P.child_off[v + 1]; e++) {
+            const int64_t c = P.child[e], rows = P.count[c], c0 = P.begin[c] + rows;
+            if (rows > 0 && end > c0) emit(ST_CLADE_RECT, v, P.begin[c], c0, c0, end, rows * (end - c0));
+        }
+    }
     return ST_OK;
 }
+
+// Chan's pairwise update on shifted sums, in the operation order of compare.DistanceComparison.merge: b moved to a's shift
+static void clade_merge(st_pair_moments &a, const st_pair_moments &b)
+{
+    if (b.n == 0) return;
+    if (a.n == 0) {
+        a = b;
+        return;
+    }
+    const double dx = b.shift_x - a.shift_x, dy = b.shift_y - a.shift_y, nb = (double)b.n;
+    a.sx = a.sx + b.sx + nb * dx;
+    a.sy = a.sy + b.sy + nb * dy;
+    a.sxx = a.sxx + b.sxx + 2.0 * dx * b.sx + nb * dx * dx;
+    a.syy = a.syy + b.syy + 2.0 * dy * b.sy + nb * dy * dy;
+    a.sxy = a.sxy + b.sxy + dx * b.sy + dy * b.sx + nb * dx * dy;
+    a.n += b.n;
+    a.min_x = std::fmin(a.min_x, b.min_x);
+    a.max_x = std::fmax(a.max_x, b.max_x);
+    a.min_y = std::fmin(a.min_y, b.min_y);
+    a.max_y = std::fmax(a.max_y, b.max_y);
+}
+
+// The reducer of st_compare_clades_host: k_clade_pieces per chunk into one device array of pieces, read back at the end;
+// done() merges pieces into segments (index order) and segments into nodes (children first, in id order, then the
+// node's own segments) on the host.
+struct CladeReduce {
+    const CladePlan &P;
+    const std::vector<CladeTile> &tiles;
+    const std::vector<int64_t> &seg_piece;       // segment s's pieces: [seg_piece[s], seg_piece[s + 1])
+    const CladeSeg *d_seg = nullptr;             // (set by the caller's setup)
+    const CladeTile *d_tile = nullptr;
+    st_pair_moments *out;
+    int64_t cap;
+    int64_t n_pieces = 0;
+    CladePiece *d_pieces = nullptr;
+    std::vector<CladePiece> pieces;
+
+    size_t bytes(int64_t) { return (size_t)n_pieces * sizeof(CladePiece); }
+    hipError_t start(char *d, int64_t, hipStream_t)
+    {
+        d_pieces = reinterpret_cast<CladePiece *>(d);
+        return hipSuccess;
+    }
+    hipError_t chunk(const float *d_x, const float *d_y, int64_t off, int64_t c, hipStream_t s)
+    {
+        const int64_t tiles_c = (c + ST_CLADE_TILE - 1) / ST_CLADE_TILE;
+        const int64_t blocks = (tiles_c + kCladeThreads / 64 - 1) / (kCladeThreads / 64);
+        hipLaunchKernelGGL(k_clade_pieces, dim3((unsigned)blocks), dim3(kCladeThreads), 0, s, d_x, d_y, (long long)off, (long long)c, d_seg,
+                           d_tile, d_pieces);
+        return hipGetLastError();
+    }
+    hipError_t finish(hipStream_t s)
+    {
+        pieces.resize(n_pieces);
+        return hipMemcpyAsync(pieces.data(), d_pieces, (size_t)n_pieces * sizeof(CladePiece), hipMemcpyDeviceToHost, s);
+    }
+    int done()
+    {
+        const int64_t n = (int64_t)P.pre.size();
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        const st_pair_moments empty{0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, nan, nan, nan, nan};
+        std::vector<st_pair_moments> seg_m(P.segs.size(), empty);
+        for (size_t si = 0; si < P.segs.size(); si++) {
+            const st_clade_segment &g = P.segs[si];
+            const int64_t seg_end = g.first_pair + g.n_pairs;
+            for (int64_t q = seg_piece[si]; q < seg_piece[si + 1]; q++) {
+                // piece q of segment si: its part of tile t
+                const int64_t t = (g.first_pair >> kCladeTileShift) + (q - seg_piece[si]);
+                const int64_t lo = std::max<int64_t>(g.first_pair, t << kCladeTileShift);
+                const int64_t hi = std::min<int64_t>(seg_end, (t + 1) << kCladeTileShift);
+                const CladePiece &c = pieces[q];
+                const st_pair_moments pm{hi - lo, (double)c.cx, (double)c.cy, c.sx, c.sy, c.sxx, c.syy, c.sxy,
+                                         (double)c.min_x, (double)c.max_x, (double)c.min_y, (double)c.max_y};
+                clade_merge(seg_m[si], pm);
+            }
+        }
+        const st_pair_moments skipped{-1, nan, nan, nan, nan, nan, nan, nan, nan, nan, nan, nan};
+        for (int64_t i = n - 1; i >= 0; i--) {      // (a node within the cap has every child within it)
+            const int64_t v = P.pre[i];
+            if (cap >= 0 && P.count[v] > cap) {
+                out[v] = skipped;
+                continue;
+            }
+            st_pair_moments acc = empty;
+            for (int64_t e = P.child_off[v]; e < P.child_off[v + 1]; e++) clade_merge(acc, out[P.child[e]]);
+            for (int64_t si = P.node_seg[v]; si < P.node_seg[v] + P.node_nseg[v]; si++) clade_merge(acc, seg_m[si]);
+            out[v] = acc;
+        }
+        return ST_OK;
+    }
+};
 
 extern "C" {
 
@@ -1095,8 +1361,8 @@ try {
     auto src_y = [&](char *d_extra, int64_t off) {
         return SrcTriangle{reinterpret_cast<const long long *>(d_extra) + m, 1, (long long)(k_begin + off)};
     };
-    return compare_run(tx, ty, k_count, kCompareChunkTriangle, (size_t)m * 16, setup, prep, src_x, src_y, edges_x, bins_x, edges_y,
-                       bins_y, out, out_hist, bad_id);
+    MomentsReduce red{edges_x, edges_y, bins_x, bins_y, out, out_hist};
+    return compare_run(tx, ty, k_count, kCompareChunkTriangle, (size_t)m * 16, setup, prep, src_x, src_y, red, bad_id);
 } ST_CATCH_ALL
 
 int st_compare_pairs_host(st_tree *tx, st_tree *ty, const int64_t *pairs_x, const int64_t *pairs_y, int64_t n, const double *edges_x,
@@ -1126,8 +1392,104 @@ try {
     };
     auto src_x = [](char *d_extra, int64_t) { return SrcContig{reinterpret_cast<const long long *>(d_extra)}; };
     auto src_y = [&](char *d_extra, int64_t) { return SrcContig{reinterpret_cast<const long long *>(d_extra + (size_t)chunk * 16)}; };
-    return compare_run(tx, ty, n, chunk, (size_t)chunk * 32, setup, prep, src_x, src_y, edges_x, bins_x, edges_y, bins_y, out, out_hist,
-                       bad_id);
+    MomentsReduce red{edges_x, edges_y, bins_x, bins_y, out, out_hist};
+    return compare_run(tx, ty, n, chunk, (size_t)chunk * 32, setup, prep, src_x, src_y, red, bad_id);
+} ST_CATCH_ALL
+
+int st_clade_plan(const int32_t *parent, int64_t n_nodes, const int64_t *link_leaf, int64_t n_links, int64_t max_links,
+                  int64_t *out_perm, int64_t *out_begin, int64_t *out_count, int64_t *out_leaves, st_clade_segment *out_segs,
+                  int64_t seg_capacity, int64_t *out_n_segs, int64_t *out_total_pairs, int64_t *bad_id)
+try {
+    CladePlan P;
+    int rc = clade_plan(parent, n_nodes, link_leaf, n_links, max_links, P, bad_id);
+    if (rc != ST_OK) return rc;
+    if (out_segs && seg_capacity < (int64_t)P.segs.size())
+        return fail(ST_ERR_ARG, "seg_capacity " + std::to_string(seg_capacity) + " < " + std::to_string(P.segs.size()) + " segments");
+    if (out_perm) std::copy(P.perm.begin(), P.perm.end(), out_perm);
+    if (out_begin) std::copy(P.begin.begin(), P.begin.end(), out_begin);
+    if (out_count) std::copy(P.count.begin(), P.count.end(), out_count);
+    if (out_leaves) std::copy(P.leaves.begin(), P.leaves.end(), out_leaves);
+    if (out_segs) std::copy(P.segs.begin(), P.segs.end(), out_segs);
+    if (out_n_segs) *out_n_segs = (int64_t)P.segs.size();
+    if (out_total_pairs) *out_total_pairs = P.total;
+    return ST_OK;
+} ST_CATCH_ALL
+
+int st_compare_clades_host(st_tree *tx, st_tree *ty, const int32_t *parent, int64_t n_nodes, const int64_t *ids_x,
+                           const int64_t *ids_y, int64_t n_links, int64_t max_links, int64_t chunk_pairs,
+                           st_pair_moments *out, int64_t *out_count, int64_t *bad_id)
+try {
+    if (!out) return fail(ST_ERR_ARG, "out is NULL");
+    int rc = compare_trees_args(tx, ty);
+    if (rc != ST_OK) return rc;
+    if (n_nodes != ty->n_nodes)
+        return fail(ST_ERR_ARG, "parent array of " + std::to_string(n_nodes) + " nodes: tree_y has " + std::to_string(ty->n_nodes));
+    if (n_links < 0) return fail(ST_ERR_ARG, "n_links < 0");
+    if (n_links > 0 && (!ids_x || !ids_y)) return fail(ST_ERR_ARG, "ids_x or ids_y is NULL");
+    if (chunk_pairs < 0 || chunk_pairs % ST_CLADE_TILE != 0)
+        return fail(ST_ERR_ARG, "chunk_pairs must be 0 or a positive multiple of " + std::to_string(ST_CLADE_TILE));
+    rc = compare_check_ids(ids_x, n_links, tx->n_nodes, bad_id);
+    if (rc == ST_OK) rc = compare_check_ids(ids_y, n_links, ty->n_nodes, bad_id);
+    if (rc != ST_OK) return rc;
+    CladePlan P;
+    rc = clade_plan(parent, n_nodes, ids_y, n_links, max_links, P, bad_id);
+    if (rc != ST_OK) return rc;
+    if (out_count) std::copy(P.count.begin(), P.count.end(), out_count);
+    // tiles and pieces: tile[t].seg = the segment of pair t * TILE, tile[t].piece = pieces before tile t; a sentinel
+    // segment (first = total) and a sentinel tile close the tables
+    const int64_t total = P.total, n_segs = (int64_t)P.segs.size();
+    const int64_t n_tiles = (total + ST_CLADE_TILE - 1) / ST_CLADE_TILE;
+    std::vector<CladeSeg> segs(n_segs + 1);
+    std::vector<CladeTile> tiles(n_tiles + 1);
+    std::vector<int64_t> seg_piece(n_segs + 1, 0);
+    int64_t n_pieces = 0;
+    for (int64_t s = 0; s < n_segs; s++) {
+        const st_clade_segment &g = P.segs[s];
+        segs[s] = CladeSeg{(long long)g.first_pair, g.row_begin, g.row_end, g.kind == ST_CLADE_TRI ? -1 : g.col_begin, g.col_end};
+        const int64_t tf = g.first_pair >> kCladeTileShift, tl = (g.first_pair + g.n_pairs - 1) >> kCladeTileShift;
+        seg_piece[s] = n_pieces;
+        for (int64_t t = (g.first_pair + ST_CLADE_TILE - 1) >> kCladeTileShift; t <= tl; t++)      // tiles that start in s
+            tiles[t] = CladeTile{(int)s, (int)(n_pieces + (t - tf))};
+        n_pieces += tl - tf + 1;
+    }
+    seg_piece[n_segs] = n_pieces;
+    segs[n_segs] = CladeSeg{(long long)total, 0, 0, 0, 0};
+    if (n_pieces > INT32_MAX) return fail(ST_ERR_ARG, "more than 2^31 - 1 pieces");
+    tiles[n_tiles] = CladeTile{(int)n_segs, (int)n_pieces};
+    CladeReduce red{P, tiles, seg_piece, nullptr, nullptr, out, max_links};
+    red.n_pieces = n_pieces;
+    if (total == 0) return red.done();      // (nothing to launch)
+    // device: permuted ids of X and Y and ranks (int32) | segments | tiles
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t L = (size_t)n_links;
+    const size_t o_y = up(L * 4), o_rank = o_y + up(L * 4), o_seg = o_rank + up(L * 4);
+    const size_t o_tile = o_seg + up(segs.size() * sizeof(CladeSeg)), extra = o_tile + up(tiles.size() * sizeof(CladeTile));
+    std::vector<int32_t> sx(L), sy(L), rk(L);
+    for (size_t p = 0; p < L; p++) {
+        const int64_t j = P.perm[p];
+        sx[p] = (int32_t)ids_x[j];
+        sy[p] = (int32_t)ids_y[j];
+        rk[p] = (int32_t)j;
+    }
+    auto setup = [&](char *d, hipStream_t s) {
+        red.d_seg = reinterpret_cast<const CladeSeg *>(d + o_seg);
+        red.d_tile = reinterpret_cast<const CladeTile *>(d + o_tile);
+        hipError_t e = hipMemcpyAsync(d, sx.data(), L * 4, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d + o_y, sy.data(), L * 4, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d + o_rank, rk.data(), L * 4, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d + o_seg, segs.data(), segs.size() * sizeof(CladeSeg), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d + o_tile, tiles.data(), tiles.size() * sizeof(CladeTile), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);      // (the host vectors are pageable and go out of scope with this call)
+        return e;
+    };
+    auto prep = [](char *, hipStream_t, int64_t, int64_t) { return hipSuccess; };
+    auto src = [&](size_t o_ids) {
+        return [&, o_ids](char *d, int64_t off) {
+            return SrcSegments{reinterpret_cast<const int *>(d + o_ids), reinterpret_cast<const int *>(d + o_rank),
+                               reinterpret_cast<const CladeSeg *>(d + o_seg), reinterpret_cast<const CladeTile *>(d + o_tile), (long long)off};
+        };
+    };
+    return compare_run(tx, ty, total, chunk_pairs > 0 ? chunk_pairs : kCladeChunkPairs, extra, setup, prep, src(0), src(o_y), red, bad_id);
 } ST_CATCH_ALL
 
 int st_quartets_host(st_tree *t, const int64_t *quartets, int64_t n, int64_t stride0, int64_t stride1,

@@ -214,6 +214,101 @@ class SuchLinkedTrees:
         return compare.run(lambda edges: dev_a.compare_triangle_host(dev_b, ids_a, ids_b, edges=edges), bins, range,
                            n_leaves=int(ll.shape[0]))
 
+    @staticmethod
+    def _breadth_first(tree: SuchTree, node_id: int, leaves: bool) -> np.ndarray:
+        """The leaves (:meth:`_leaves_below`) or the internal nodes (``get_internal_nodes``) below a node, breadth-first,
+        one numpy step per level."""
+        left, right = tree._flat.left, tree._flat.right
+        level, out = np.array([int(node_id)], dtype=np.int64), []
+        while level.size:
+            leaf = left[level] == -1
+            out.append(level[leaf] if leaves else level[~leaf])
+            inner = level[~leaf]
+            level = np.stack([left[inner], right[inner]], axis=1).ravel().astype(np.int64)
+        return np.concatenate(out)
+
+    @classmethod
+    def _leaf_order(cls, tree: SuchTree, node_id: int) -> np.ndarray:
+        return cls._breadth_first(tree, node_id, True)
+
+    def _flat_table(self):
+        """The link table as (TreeA leaf ids, column start offsets), built once."""
+        if getattr(self, "_table_flat", None) is None:
+            lens = np.array([len(c) for c in self._table], dtype=np.int64)
+            start = np.zeros(len(lens) + 1, dtype=np.int64)
+            np.cumsum(lens, out=start[1:])
+            ids = np.concatenate([np.asarray(c, dtype=np.int64) for c in self._table]) if self._n_links else np.empty(0, np.int64)
+            self._table_flat = (ids, start)
+        return self._table_flat
+
+    def _links_in_order(self, columns, a_leaves):
+        """(TreeA ids, TreeB ids) of the links of ``columns`` (in that order; table order within a column) whose TreeA
+        leaf is in ``a_leaves``: the link list _build_linklist would build, without touching the subset state."""
+        ids, start = self._flat_table()
+        columns = np.asarray(columns, dtype=np.int64)
+        lens = start[columns + 1] - start[columns]
+        total = int(lens.sum())
+        first = np.repeat(start[columns] - np.concatenate(([0], np.cumsum(lens)[:-1])), lens)
+        pos = first + np.arange(total, dtype=np.int64)
+        a = ids[pos]
+        b = np.repeat(self._col_ids[columns].astype(np.int64), lens)
+        keep = np.zeros(self._tree_a.size, dtype=bool)
+        keep[np.asarray(a_leaves, dtype=np.int64)] = True
+        k = keep[a]
+        return a[k], b[k]
+
+    def linked_distances_by_clade(self, tree="B", min_leaves=0, min_links=2, max_links=None, chunk_pairs=0):
+        """:meth:`linked_distances_summary` for every clade of one tree at once, in one pass over the pairs on the GPU.
+
+        ``tree="B"``: one row per internal node c of TreeB, equal to what ``subset_b(c); linked_distances_summary()``
+        gives under the current ``subset_a``; ``tree="A"``: the mirror, the clades of TreeA under the current
+        ``subset_b``.  x is TreeA and y TreeB in both cases.  Rows follow ``get_internal_nodes()`` (breadth-first from
+        the root) and are kept when ``n_leaves >= min_leaves``, ``n_links >= min_links`` and, unless ``max_links`` is
+        None, ``n_links <= max_links`` -- the per-clade loop of the reference's SuchLinkedTrees notebook with its filters
+        (``subset_b_size``, ``subset_n_links``).  A cap also saves work: only clades within it are evaluated.
+
+        Each clade's per-pair values are bit-identical to its ``linked_distances()``: pair (link j, link i) of the clade
+        is evaluated with the link of lower rank first, the rank being the position in the link list of the tree's
+        root.  The subset state and ``linklist`` are the same after the call as before it.  Returns a
+        :class:`~suchtree_amd.compare.CladeComparisons`; its ``pvalue`` column is NaN when scipy is not installed.
+        ``chunk_pairs`` (a multiple of 8192, 0 = default) only sets the device chunk; results do not depend on it.
+        An extension: the reference has no counterpart.
+        """
+        from . import compare
+        if tree not in ("A", "B"):
+            raise ValueError("tree must be 'A' or 'B'")
+        A, B = self._tree_a, self._tree_b
+        if tree == "B":
+            col_of = np.full(B.size, -1, dtype=np.int64)
+            col_of[self._col_ids.astype(np.int64)] = np.arange(len(self._col_ids))
+            cols = col_of[self._leaf_order(B, B.root_node)]
+            ids_a, ids_b = self._links_in_order(cols, self._subset_a_leafs)
+            clade, other, ids_clade, ids_other = B, A, ids_b, ids_a
+        else:
+            ids_a, ids_b = self._links_in_order(self._subset_columns, self._leaf_order(A, A.root_node))
+            clade, other, ids_clade, ids_other = A, B, ids_a, ids_b
+        parent = np.ascontiguousarray(clade._flat.parent, dtype=np.int32)
+        dev_o, dev_c = other._device_tree(), clade._device_tree()
+        m, count = dev_o.compare_clades_host(dev_c, parent, ids_other, ids_clade, max_links=max_links, chunk_pairs=chunk_pairs)
+        leaves = self._leaf_counts(clade)
+        nodes = self._breadth_first(clade, clade.root_node, False)      # (get_internal_nodes() order)
+        keep = (leaves[nodes] >= min_leaves) & (count[nodes] >= min_links) & (m["n"][nodes] >= 0)
+        if max_links is not None:
+            keep &= count[nodes] <= max_links
+        nodes = nodes[keep]
+        r = m[nodes]
+        # x = the other tree in the call: for tree="A" that is TreeB, so the columns swap back
+        sx, sy = ("x", "y") if tree == "B" else ("y", "x")
+        sums = {"shift_x": r["shift_" + sx], "shift_y": r["shift_" + sy], "sx": r["s" + sx], "sy": r["s" + sy],
+                "sxx": r["s" + sx + sx], "syy": r["s" + sy + sy], "sxy": r["sxy"]}
+        return compare.CladeComparisons(nodes, leaves[nodes], count[nodes], sums, r["min_" + sx], r["max_" + sx], r["min_" + sy],
+                                        r["max_" + sy], tree=tree)
+
+    @staticmethod
+    def _leaf_counts(tree: SuchTree) -> np.ndarray:
+        """Leaves under every node (st_clade_plan)."""
+        return _capi.clade_plan(tree._flat.parent, np.empty(0, dtype=np.int64))["leaves"]
+
     def sample_linked_distances(self, sigma=0.001, buckets=64, n=4096, maxcycles=100, seed=None):
         """Monte-Carlo form of :meth:`linked_distances` (pyx:2951-3079): cycles of ``buckets`` x ``n`` random link
         pairs, distances in both trees, until the spread of the per-bucket standard deviations falls below ``sigma``
