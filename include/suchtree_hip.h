@@ -38,7 +38,8 @@ extern "C" {
  * an older header must not be handed a larger st_tree_info: compare ST_API_VERSION with st_api_version() at load (the ctypes
  * binding does) and use st_tree_info_get_sized, which writes at most the bytes the caller says it has.
  *   7: st_compare_triangle_host, st_compare_pairs_host and struct st_pair_moments added; later, without a bump (additive):
- *      st_clade_plan, st_compare_clades_host, struct st_clade_segment and the ST_CLADE_* constants.
+ *      st_clade_plan, st_compare_clades_host, struct st_clade_segment and the ST_CLADE_* constants; then, also additive,
+ *      st_compare_rows_host.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -387,6 +388,25 @@ int st_clade_plan(const int32_t *parent, int64_t n_nodes, const int64_t *link_le
 int st_compare_clades_host(st_tree *tree_x, st_tree *tree_y, const int32_t *parent, int64_t n_nodes, const int64_t *ids_x,
                            const int64_t *ids_y, int64_t n_links, int64_t max_links, int64_t chunk_pairs,
                            st_pair_moments *out, int64_t *out_count, int64_t *bad_id);
+
+/*
+ * Many triangles in one pass: row r of the C-order int64 (n_rows, m) arrays ids_x / ids_y is one
+ * st_compare_triangle_host over all of its pairs -- pair k = (ids_x[r,j], ids_x[r,i]) in tree_x and (ids_y[r,j],
+ * ids_y[r,i]) in tree_y, k = i(i-1)/2 + j -- and out[r] (n_rows entries) receives that row's moments, summed about the
+ * row's first pair (0 where it is not finite).  A row with m < 2 gives n = 0, zero sums and NaN min / max.  The rows of
+ * a permutation test (SuchLinkedTrees.hommola_cospeciation: the links relabelled once per permutation) are such rows.
+ * Trees, ids and error codes as for st_compare_triangle_host; chunk_pairs: 0 (the default) or a positive multiple of
+ * ST_CLADE_TILE, else ST_ERR_ARG.  Device memory is bounded by one chunk of pairs, the ids of its rows and its blocks.
+ *
+ * Determinism: out[r] depends only on row r's ids and the two trees -- not on r, the other rows, n_rows, chunk_pairs
+ * or the device.  A row is cut into blocks of ST_CLADE_TILE pairs counted from its first pair; each block is summed
+ * about its own first pair in one fixed order that depends on its length alone, and the blocks are merged in block
+ * order with the shifted pairwise update (the operation order of DistanceComparison.merge).  Identical rows give
+ * identical bits wherever they stand.  No float atomics.  No counterpart in the reference.
+ */
+int st_compare_rows_host(st_tree *tree_x, st_tree *tree_y, const int64_t *ids_x, const int64_t *ids_y,
+                         int64_t n_rows, int64_t m, int64_t chunk_pairs,
+                         st_pair_moments *out, int64_t *bad_id);
 
 /*
  * Quartet topologies: for each row (a,b,c,d) of the int64 (n,4) view the row re-ordered so

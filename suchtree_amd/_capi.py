@@ -43,6 +43,7 @@ SYMBOLS = (
     "st_quartets_host", "st_graph_matrices_host", "st_newick_open", "st_newick_fill", "st_newick_close",
     "st_host_depths", "st_link_sample_pairs", "st_bucket_moments", "st_device_malloc", "st_device_free", "st_memcpy_h2d", "st_memcpy_d2h",
     "st_device_synchronize", "st_compare_triangle_host", "st_compare_pairs_host", "st_clade_plan", "st_compare_clades_host",
+    "st_compare_rows_host",
 )
 
 CLADE_RECT, CLADE_TRI = 0, 1     # include/suchtree_hip.h: ST_CLADE_RECT / ST_CLADE_TRI
@@ -62,7 +63,7 @@ class PairMoments(ctypes.Structure):
         return {k: (int(getattr(self, k)) if k == "n" else float(getattr(self, k))) for k, _ in self._fields_}
 
 
-# st_pair_moments as a numpy record (arrays of them: st_compare_clades_host)
+# st_pair_moments as a numpy record (arrays of them: st_compare_clades_host, st_compare_rows_host)
 PAIR_MOMENTS = np.dtype([("n", np.int64)] + [(k, np.float64) for k in
                                             "shift_x shift_y sx sy sxx syy sxy min_x max_x min_y max_y".split()])
 assert PAIR_MOMENTS.itemsize == ctypes.sizeof(PairMoments)
@@ -227,6 +228,7 @@ def load():
         L.st_clade_plan.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64),
                                     ctypes.POINTER(i64)]
         L.st_compare_clades_host.argtypes = [vp, vp, vp, i64, vp, vp, i64, i64, i64, vp, vp, ctypes.POINTER(i64)]
+        L.st_compare_rows_host.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, ctypes.POINTER(i64)]
         L.st_graph_matrices_host.argtypes = [i32, i64, i64, vp, vp, vp, vp, vp]
         L.st_newick_open.argtypes = [ctypes.c_char_p, i64, ctypes.POINTER(vp), ctypes.POINTER(i64),
                                      ctypes.POINTER(i64), ctypes.POINTER(i64),
@@ -756,6 +758,24 @@ class DeviceTree:
             check(rc, tree_size=self.size, bad_id=bad)
         check(rc, tree_size=other.size, bad_id=bad)
         return out, count
+
+    def compare_rows_host(self, other, ids_x, ids_y, chunk_pairs=0):
+        """st_compare_rows_host: one PairMoments-shaped record per row of the int64 (n_rows, m) ``ids_x`` (this tree) /
+        ``ids_y`` (``other``): the moments of the triangle over that row's ids (the enumeration of triangle_host).  A row's
+        record depends on its ids alone -- not on its index, the other rows or ``chunk_pairs`` (0 or a multiple of
+        CLADE_TILE)."""
+        ids_x = np.ascontiguousarray(ids_x, dtype=np.int64)
+        ids_y = np.ascontiguousarray(ids_y, dtype=np.int64)
+        if ids_x.ndim != 2 or ids_x.shape != ids_y.shape:
+            raise ValueError("ids_x and ids_y must be 2-D arrays of equal shape")
+        n_rows, m = (int(v) for v in ids_x.shape)
+        out = np.zeros(n_rows, dtype=PAIR_MOMENTS)
+        bad = ctypes.c_int64(0)
+        has = n_rows * m > 0
+        rc = self._lib.st_compare_rows_host(self.handle, other.handle, _ptr(ids_x) if has else None, _ptr(ids_y) if has else None,
+                                            n_rows, m, int(chunk_pairs), _ptr(out) if n_rows else None, ctypes.byref(bad))
+        self._compare_check(other, rc, bad)
+        return out
 
     def triangle_device(self, d_ids, m, k_begin, k_count, d_out_dist=0, d_out_mrca=0, stream=0, id_stride=1):
         rc = self._lib.st_triangle_device(self.handle, ctypes.c_void_p(d_ids), int(m), int(id_stride),

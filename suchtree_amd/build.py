@@ -21,7 +21,7 @@ HIP_SOURCES = [os.path.join(CSRC, f) for f in ("suchtree_hip.hip", "launch_walk.
 CPP_SOURCES = [os.path.join(CSRC, "tree_prep.cpp"), os.path.join(CSRC, "newick_parse.cpp")]
 SOURCES = HIP_SOURCES + CPP_SOURCES
 # (source, extra flags, object name): launch_canopy.hip holds the slowest instantiations (the scalar ladder kernel's two forms, the
-# predicated kernel's long-chain forms) and is compiled in four parts, two pair sources each (one in the last)
+# predicated kernel's long-chain forms) and is compiled in four parts, two pair sources each
 UNITS = [(src, [], os.path.basename(src) + ".o") for src in SOURCES if not src.endswith("launch_canopy.hip")]
 UNITS = [(os.path.join(CSRC, "launch_canopy.hip"), ["-DST_CANOPY_PART=%d" % k], "launch_canopy.%d.o" % k)
          for k in range(4)] + UNITS

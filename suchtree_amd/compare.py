@@ -12,7 +12,7 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["DistanceComparison", "CladeComparisons"]
+__all__ = ["DistanceComparison", "CladeComparisons", "HommolaResult"]
 
 
 @dataclass(frozen=True)
@@ -169,6 +169,21 @@ def pearson_pvalue(r, n):
 _SUMS = ("shift_x", "shift_y", "sx", "sy", "sxx", "syy", "sxy")
 
 
+def row_stats(n, shift_x, shift_y, sx, sy, sxx, syy, sxy):
+    """(mean_x, mean_y, var_x, var_y, cov, pearson_r) of rows of sums: the formulas of DistanceComparison.from_sums,
+    elementwise in the same order (the same bits as from_sums on each row)."""
+    n = np.asarray(n).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean_x = shift_x + sx / n
+        mean_y = shift_y + sy / n
+        var_x = np.maximum((sxx - sx * sx / n) / n, 0.0)
+        var_y = np.maximum((syy - sy * sy / n) / n, 0.0)
+        cov = (sxy - sx * sy / n) / n
+        ok = (var_x > 0) & (var_y > 0)
+        r = np.where(ok, np.clip(cov / np.sqrt(var_x * var_y), -1.0, 1.0), np.nan)
+    return mean_x, mean_y, var_x, var_y, cov, r
+
+
 class CladeComparisons:
     """One row per clade: the summary :meth:`SuchLinkedTrees.linked_distances_summary` gives after subsetting to that
     clade (SuchLinkedTrees.linked_distances_by_clade), as numpy columns.
@@ -191,16 +206,8 @@ class CladeComparisons:
             setattr(self, k, np.asarray(sums[k], dtype=np.float64))
         self.min_a, self.max_a = np.asarray(min_a, dtype=np.float64), np.asarray(max_a, dtype=np.float64)
         self.min_b, self.max_b = np.asarray(min_b, dtype=np.float64), np.asarray(max_b, dtype=np.float64)
-        # the formulas of DistanceComparison.from_sums, elementwise in the same order (the same bits as comparison())
-        n = self.n_pairs.astype(np.float64)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            self.mean_a = self.shift_x + self.sx / n
-            self.mean_b = self.shift_y + self.sy / n
-            self.var_a = np.maximum((self.sxx - self.sx * self.sx / n) / n, 0.0)
-            self.var_b = np.maximum((self.syy - self.sy * self.sy / n) / n, 0.0)
-            self.cov = (self.sxy - self.sx * self.sy / n) / n
-            ok = (self.var_a > 0) & (self.var_b > 0)
-            self.pearson_r = np.where(ok, np.clip(self.cov / np.sqrt(self.var_a * self.var_b), -1.0, 1.0), np.nan)
+        self.mean_a, self.mean_b, self.var_a, self.var_b, self.cov, self.pearson_r = row_stats(
+            self.n_pairs, *(getattr(self, k) for k in _SUMS))
         self.pvalue = pearson_pvalue(self.pearson_r, self.n_pairs)
         self._row = None
 
@@ -228,3 +235,60 @@ class CladeComparisons:
         for k in ("mean_a", "mean_b", "var_a", "var_b", "cov", "min_a", "max_a", "min_b", "max_b") + _SUMS:
             cols[k] = getattr(self, k)
         return pd.DataFrame(cols)
+
+
+@dataclass(frozen=True)
+class HommolaResult:
+    """Hommola et al.'s (2009) permutation test of cospeciation (SuchLinkedTrees.hommola_cospeciation).
+
+    ``corr_coeff`` is Pearson's r of the unpermuted links (x = TreeA, y = TreeB), ``observed`` their full summary,
+    ``perm_stats`` the r of each permutation in draw order (float64, ``permutations`` of them) and ``p_value`` scikit-bio's
+    (count(perm_stats >= corr_coeff) + 1) / (permutations + 1).  ``seed`` repeats the run.  Iterating gives
+    ``(corr_coeff, p_value, perm_stats)``, as scikit-bio's ``hommola_cospeciation`` returns them.
+    """
+
+    corr_coeff: float
+    p_value: float
+    perm_stats: np.ndarray
+    observed: DistanceComparison
+    n_links: int
+    permutations: int
+    seed: int
+
+    def __iter__(self):
+        return iter((self.corr_coeff, self.p_value, self.perm_stats))
+
+
+def hommola_pvalue(corr_coeff, perm_stats):
+    """scikit-bio's rule: (number of permuted r >= the observed r, NaN not counted, + 1) / (permutations + 1); NaN when
+    the observed r is NaN or there are no permutations."""
+    perm_stats = np.asarray(perm_stats, dtype=np.float64)
+    if math.isnan(corr_coeff) or perm_stats.size == 0:
+        return float("nan")
+    return (int(np.count_nonzero(perm_stats >= corr_coeff)) + 1) / (perm_stats.size + 1)
+
+
+def hommola_rows(u_a, u_b, pos_a, pos_b, permutations, seed, batch):
+    """The rows of Hommola's test as (ids_a, ids_b), C-order int64 (rows, n_links), in batches of at most ``batch`` rows.
+
+    Link j is leaf ``u_a[pos_a[j]]`` of TreeA and ``u_b[pos_b[j]]`` of TreeB (``u_a`` / ``u_b``: the universes).  The
+    first batch is row 0 alone, the links as they are.  Then permutation p = 1 .. ``permutations``, drawn in order from
+    ``numpy.random.default_rng(seed)`` as scikit-bio's hommola_cospeciation draws them -- mp = rng.permutation(len(u_b)),
+    then mh = rng.permutation(len(u_a)) -- relabels the links: ids_b = u_b[mp[pos_b]], ids_a = u_a[mh[pos_a]].  Draws
+    happen as batches are taken, so the first k permutations are the same for any ``permutations`` >= k and any batch.
+    Host memory is the batch's ids plus one permutation of each universe at a time."""
+    u_a, u_b = np.asarray(u_a, dtype=np.int64), np.asarray(u_b, dtype=np.int64)
+    pos_a, pos_b = np.asarray(pos_a, dtype=np.int64), np.asarray(pos_b, dtype=np.int64)
+    yield u_a[pos_a][None, :], u_b[pos_b][None, :]
+    rng = np.random.default_rng(seed)
+    na, nb = len(u_a), len(u_b)
+    done = 0
+    while done < permutations:
+        k = min(int(batch), permutations - done)
+        ids_a = np.empty((k, len(pos_a)), dtype=np.int64)
+        ids_b = np.empty((k, len(pos_b)), dtype=np.int64)
+        for i in range(k):      # (only each draw's image is kept: memory grows with the links, not the universes)
+            ids_b[i] = u_b[rng.permutation(nb)[pos_b]]
+            ids_a[i] = u_a[rng.permutation(na)[pos_a]]
+        done += k
+        yield ids_a, ids_b

@@ -142,6 +142,33 @@ struct SrcSegments {
     }
 };
 
+// Rows of id lists (st_compare_rows_host): row r's pairs are the triangle over its m ids, P = m(m-1)/2 of them, pair k of
+// row r at global index r * S + k (S = P, or P rounded up to a multiple of 2^kCladeTileShift; pairs [P, S) are padding
+// and evaluate the row's first pair).  `ids` holds the rows uploaded for this chunk, from row r_base on.  r = g / S by a
+// double reciprocal and a +-1 correction (global indices stay below 2^50), never a 64-bit divide per pair.
+struct SrcRows {
+    const int *ids;
+    long long m, P, S;
+    double inv_s;          // 1.0 / S
+    long long k0;          // first global pair index of this launch
+    long long r_base;      // the row at ids[0]
+    __device__ __forceinline__ void load(long long i, long long &a, long long &b) const
+    {
+        const long long g = k0 + i;
+        long long r = (long long)((double)g * inv_s);
+        if (r * S > g) r--;
+        else if ((r + 1) * S <= g) r++;
+        long long k = g - r * S;
+        if (k >= P) k = 0;
+        long long row = (long long)((1.0 + sqrt(1.0 + 8.0 * (double)k)) * 0.5);      // (the enumeration of SrcTriangle)
+        if (row * (row - 1) / 2 > k) row--;
+        if ((row + 1) * row / 2 <= k) row++;
+        const int *v = ids + (r - r_base) * m;
+        a = v[k - row * (row - 1) / 2];
+        b = v[row];
+    }
+};
+
 // Grid generator: element e = e0 + i of an n_rows x n_cols grid (C order) is the pair
 // (rows[r], cols[c]), r = e / n_cols, c = e % n_cols.  `symmetric` (rows and cols are the same
 // id list): below the diagonal the pair is taken in the order of its mirror image above it,

@@ -49,6 +49,24 @@ __device__ __forceinline__ void clade_store(CladePiece *out, const CladeAcc &a, 
     *out = CladePiece{a.sx, a.sy, a.sxx, a.syy, a.sxy, cx, cy, a.min_x, a.max_x, a.min_y, a.max_y};
 }
 
+// The wave's part of the order rule: lane l's sums combined by an xor butterfly over the 64 lanes (every lane ends with
+// the same result; lane 0's is stored).  Shared by k_clade_pieces and k_row_blocks (kernels_rows.h).
+__device__ __forceinline__ void clade_wave_reduce(CladeAcc &a)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a.sx += __shfl_xor(a.sx, o);
+        a.sy += __shfl_xor(a.sy, o);
+        a.sxx += __shfl_xor(a.sxx, o);
+        a.syy += __shfl_xor(a.syy, o);
+        a.sxy += __shfl_xor(a.sxy, o);
+        a.min_x = fminf(a.min_x, __shfl_xor(a.min_x, o));
+        a.max_x = fmaxf(a.max_x, __shfl_xor(a.max_x, o));
+        a.min_y = fminf(a.min_y, __shfl_xor(a.min_y, o));
+        a.max_y = fmaxf(a.max_y, __shfl_xor(a.max_y, o));
+    }
+}
+
 // One chunk: pairs [off, off + c) at x[0..c), y[0..c); off is a multiple of the tile.  Wave w of workgroup b takes tile
 // (off >> kCladeTileShift) + 4 b + w; its pieces are segments tile[t].seg, tile[t].seg + 1, ... (every segment holds
 // at least one pair), written to out[tile[t].piece + j].  Rounds of 64 pieces: lane j sums piece j if it is short, then
@@ -86,18 +104,7 @@ __global__ __launch_bounds__(kCladeThreads) void k_clade_pieces(const float *__r
             const float cx = clade_shift(x[wlo - off]), cy = clade_shift(y[wlo - off]);
             CladeAcc a;
             for (long long i = wlo + lane; i < whi; i += 64) a.add(x[i - off], y[i - off], (double)cx, (double)cy);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                a.sx += __shfl_xor(a.sx, o);
-                a.sy += __shfl_xor(a.sy, o);
-                a.sxx += __shfl_xor(a.sxx, o);
-                a.syy += __shfl_xor(a.syy, o);
-                a.sxy += __shfl_xor(a.sxy, o);
-                a.min_x = fminf(a.min_x, __shfl_xor(a.min_x, o));
-                a.max_x = fmaxf(a.max_x, __shfl_xor(a.max_x, o));
-                a.min_y = fminf(a.min_y, __shfl_xor(a.min_y, o));
-                a.max_y = fmaxf(a.max_y, __shfl_xor(a.max_y, o));
-            }
+            clade_wave_reduce(a);
             if (lane == 0) clade_store(out + t0.piece + r + b, a, cx, cy);
         }
     }

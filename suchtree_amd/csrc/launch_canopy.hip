@@ -173,7 +173,7 @@ hipError_t launch_canopy(const st_tree *t, const Src &src, int64_t n, DistSink o
 #define ST_INSTANTIATE_CANOPY(S) \
     template hipError_t launch_canopy<S>(const st_tree *, const S &, int64_t, DistSink, MrcaSink, Fault *, hipStream_t, int *);
 // The instantiations are the slowest part of the build since round 6 (the scalar ladder kernel has two forms): the file is compiled
-// four times, -DST_CANOPY_PART=0 / 1 / 2 / 3, each part with two of the seven pair sources, the last with one (build.py).
+// four times, -DST_CANOPY_PART=0 / 1 / 2 / 3, each part with two of the eight pair sources (build.py).
 #ifndef ST_CANOPY_PART
 ST_FOR_EACH_SRC(ST_INSTANTIATE_CANOPY)      // (one piece: a plain `hipcc -c` of this file still works)
 #elif ST_CANOPY_PART == 0
@@ -187,6 +187,7 @@ ST_INSTANTIATE_CANOPY(SrcGrid)
 ST_INSTANTIATE_CANOPY(SrcQuartet)
 #else
 ST_INSTANTIATE_CANOPY(SrcSegments)
+ST_INSTANTIATE_CANOPY(SrcRows)
 #endif
 
 }  // namespace st

@@ -23,7 +23,8 @@ template <typename Src>
 hipError_t launch_walk(const st_tree *t, const Src &src, int64_t n, DistSink out_d, MrcaSink out_m, Fault *fault,
                        hipStream_t stream, int *choice = nullptr);
 
-#define ST_FOR_EACH_SRC(X) X(SrcContig) X(SrcContig32) X(SrcStrided) X(SrcTriangle) X(SrcGrid) X(SrcQuartet) X(SrcSegments)
+#define ST_FOR_EACH_SRC(X) X(SrcContig) X(SrcContig32) X(SrcStrided) X(SrcTriangle) X(SrcGrid) X(SrcQuartet) X(SrcSegments) \
+                           X(SrcRows)
 #ifndef ST_LAUNCH_UNIT
 #define ST_EXTERN_LAUNCH(S)                                                                                              \
     extern template hipError_t launch_canopy<S>(const st_tree *, const S &, int64_t, DistSink, MrcaSink, Fault *, hipStream_t, int *); \

@@ -132,6 +132,7 @@ private:
 #include "kernels_misc.h"
 #include "kernels_compare.h"
 #include "kernels_clades.h"
+#include "kernels_rows.h"
 
 
 // --------------------------------------------------------------------------
@@ -1327,6 +1328,119 @@ struct CladeReduce {
     }
 };
 
+// ---- many triangles at once (st_compare_rows_host) ----------------------------------------------------------------
+// Row r's pairs sit at global index r * S + k (SrcRows).  Rows of at most half a chunk are dense (S = P; a chunk holds
+// whole rows, at most kRowsChunkBlocks blocks' worth so that tiny rows do not make huge piece buffers); larger rows are
+// padded to whole tiles (S = P rounded up) and a chunk is whole tiles.  Either way no block straddles a chunk.
+constexpr int64_t kRowsChunkBlocks = (int64_t)1 << 18;      // 16 MiB of pieces per buffer
+struct RowsLayout {
+    int64_t P = 0, S = 0, nb = 0, chunk = 0, max_rows = 0, max_blocks = 0;
+};
+
+static RowsLayout rows_layout(int64_t n_rows, int64_t m, int64_t chunk_pairs)
+{
+    RowsLayout L;
+    const int64_t C = chunk_pairs > 0 ? chunk_pairs : kCladeChunkPairs;
+    L.P = m * (m - 1) / 2;
+    L.nb = (L.P + ST_CLADE_TILE - 1) / ST_CLADE_TILE;
+    if (L.P == 0) return L;
+    if (L.P <= C / 2) {
+        L.S = L.P;
+        L.max_rows = std::max<int64_t>(1, std::min({n_rows, C / L.P, kRowsChunkBlocks / L.nb}));
+        L.chunk = L.max_rows * L.P;
+        L.max_blocks = L.max_rows * L.nb;
+    } else {
+        L.S = L.nb * ST_CLADE_TILE;
+        L.chunk = C;
+        L.max_rows = std::min(n_rows, (C - 1) / L.S + 2);
+        L.max_blocks = std::min(C / ST_CLADE_TILE, n_rows * L.nb);
+    }
+    return L;
+}
+
+// The reducer of st_compare_rows_host: k_row_blocks per chunk into one of two device piece buffers, each read back into
+// its pinned host twin; the host folds a chunk's pieces into their rows (block order, clade_merge) while the device works
+// on the next chunk.  Pieces of at most two chunks exist at any time.
+struct RowsReduce {
+    const RowsLayout &L;
+    st_pair_moments *out;
+    CladePiece *d_pieces[2] = {nullptr, nullptr}, *h_pieces[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int64_t first[2] = {0, 0}, count[2] = {0, 0};      // buffer i holds blocks [first, first + count); 0: nothing pending
+    int next = 0;
+
+    RowsReduce(const RowsLayout &l, st_pair_moments *o) : L(l), out(o) {}
+    ~RowsReduce()
+    {
+        for (int i = 0; i < 2; i++) {
+            if (h_pieces[i]) (void)hipHostFree(h_pieces[i]);
+            if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+    }
+    size_t piece_bytes() const { return ((size_t)L.max_blocks * sizeof(CladePiece) + 255) & ~(size_t)255; }
+    size_t bytes(int64_t) { return 2 * piece_bytes(); }
+    hipError_t start(char *d, int64_t, hipStream_t)
+    {
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < 2 && e == hipSuccess; i++) {
+            d_pieces[i] = reinterpret_cast<CladePiece *>(d + i * piece_bytes());
+            e = hipHostMalloc(reinterpret_cast<void **>(&h_pieces[i]), (size_t)L.max_blocks * sizeof(CladePiece), hipHostMallocDefault);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
+        }
+        return e;
+    }
+    int64_t block_of(int64_t g) const      // the block of global pair g (padding: its row's last block)
+    {
+        const int64_t r = g / L.S;
+        return r * L.nb + ((g - r * L.S) >> kCladeTileShift);
+    }
+    int64_t block_lo(int64_t t) const { return t / L.nb * L.S + t % L.nb * ST_CLADE_TILE; }
+    int64_t block_len(int64_t t) const { return std::min<int64_t>((t % L.nb + 1) * ST_CLADE_TILE, L.P) - t % L.nb * ST_CLADE_TILE; }
+    hipError_t drain(int i)
+    {
+        if (count[i] == 0) return hipSuccess;
+        const hipError_t e = hipEventSynchronize(ev[i]);
+        if (e != hipSuccess) return e;
+        for (int64_t j = 0; j < count[i]; j++) {
+            const int64_t t = first[i] + j;
+            const CladePiece &c = h_pieces[i][j];
+            clade_merge(out[t / L.nb], st_pair_moments{block_len(t), (double)c.cx, (double)c.cy, c.sx, c.sy, c.sxx, c.syy, c.sxy,
+                                                       (double)c.min_x, (double)c.max_x, (double)c.min_y, (double)c.max_y});
+        }
+        count[i] = 0;
+        return hipSuccess;
+    }
+    hipError_t chunk(const float *d_x, const float *d_y, int64_t off, int64_t c, hipStream_t s)
+    {
+        const int i = next;
+        next ^= 1;
+        hipError_t e = drain(i);      // (the pieces of two chunks ago)
+        if (e != hipSuccess) return e;
+        const int64_t t0 = block_of(off), n = block_of(off + c - 1) + 1 - t0, tl = t0 + n - 1;
+        if (n > L.max_blocks || block_lo(t0) != off || block_lo(tl) + block_len(tl) > off + c) return hipErrorInvalidValue;
+        const int64_t per = L.P <= kCladeLanePiece ? kCladeThreads : kCladeThreads / 64;      // blocks per workgroup
+        hipLaunchKernelGGL(k_row_blocks, dim3((unsigned)((n + per - 1) / per)), dim3(kCladeThreads), 0, s, d_x, d_y, (long long)off,
+                           (long long)L.S, (long long)L.P, (long long)L.nb, (long long)t0, (long long)n, d_pieces[i]);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(h_pieces[i], d_pieces[i], (size_t)n * sizeof(CladePiece), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipEventRecord(ev[i], s);
+        if (e == hipSuccess) {
+            first[i] = t0;
+            count[i] = n;
+        }
+        return e;
+    }
+    hipError_t finish(hipStream_t) { return hipSuccess; }
+    int done()
+    {
+        for (int k = 0; k < 2; k++, next ^= 1) {      // the older buffer first
+            const hipError_t e = drain(next);
+            if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("rows read-back: ") + hipGetErrorString(e));
+        }
+        return ST_OK;
+    }
+};
+
 extern "C" {
 
 int st_compare_triangle_host(st_tree *tx, st_tree *ty, const int64_t *ids_x, const int64_t *ids_y, int64_t m, int64_t k_begin,
@@ -1490,6 +1604,52 @@ try {
         };
     };
     return compare_run(tx, ty, total, chunk_pairs > 0 ? chunk_pairs : kCladeChunkPairs, extra, setup, prep, src(0), src(o_y), red, bad_id);
+} ST_CATCH_ALL
+
+int st_compare_rows_host(st_tree *tx, st_tree *ty, const int64_t *ids_x, const int64_t *ids_y, int64_t n_rows, int64_t m,
+                         int64_t chunk_pairs, st_pair_moments *out, int64_t *bad_id)
+try {
+    if (n_rows < 0 || m < 0) return fail(ST_ERR_ARG, "n_rows < 0 or m < 0");
+    if (chunk_pairs < 0 || chunk_pairs % ST_CLADE_TILE != 0)
+        return fail(ST_ERR_ARG, "chunk_pairs must be 0 or a positive multiple of " + std::to_string(ST_CLADE_TILE));
+    if (m > 3000000000LL) return fail(ST_ERR_ARG, "m too large");
+    if (n_rows > 0 && m > 0 && (!ids_x || !ids_y)) return fail(ST_ERR_ARG, "ids_x or ids_y is NULL");
+    if (n_rows > 0 && !out) return fail(ST_ERR_ARG, "out is NULL");
+    int rc = compare_trees_args(tx, ty);
+    if (rc != ST_OK) return rc;
+    const RowsLayout L = rows_layout(n_rows, m, chunk_pairs);
+    if (L.S > 0 && n_rows > ((int64_t)1 << 50) / L.S) return fail(ST_ERR_ARG, "more than 2^50 pairs in one call");
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int64_t r = 0; r < n_rows; r++) out[r] = st_pair_moments{0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, nan, nan, nan, nan};
+    if (n_rows == 0 || L.P == 0) return ST_OK;      // (nothing to launch)
+    const int64_t n_ids = n_rows * m;
+    rc = compare_check_ids(ids_x, n_ids, tx->n_nodes, bad_id);
+    if (rc == ST_OK) rc = compare_check_ids(ids_y, n_ids, ty->n_nodes, bad_id);
+    if (rc != ST_OK) return rc;
+    const std::vector<int32_t> hx(ids_x, ids_x + n_ids), hy(ids_y, ids_y + n_ids);      // (checked: below n_nodes)
+    // device: the int32 ids of up to max_rows rows from row `up_lo` on, X then Y; uploaded again when a chunk needs others
+    const size_t row_bytes = (size_t)m * 4, half = ((size_t)L.max_rows * row_bytes + 255) & ~(size_t)255;
+    int64_t up_lo = -1, up_hi = -1;
+    auto setup = [](char *, hipStream_t) { return hipSuccess; };
+    auto prep = [&](char *d, hipStream_t s, int64_t off, int64_t c) {
+        const int64_t r0 = off / L.S, r1 = (off + c - 1) / L.S + 1;
+        if (r1 - r0 > L.max_rows) return hipErrorInvalidValue;
+        if (r0 >= up_lo && r1 <= up_hi) return hipSuccess;
+        up_lo = r0;
+        up_hi = std::min(n_rows, r0 + L.max_rows);
+        const size_t b = (size_t)(up_hi - up_lo) * row_bytes;
+        hipError_t e = hipMemcpyAsync(d, hx.data() + up_lo * m, b, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d + half, hy.data() + up_lo * m, b, hipMemcpyHostToDevice, s);
+        return e;
+    };
+    auto src = [&](size_t o) {
+        return [&, o](char *d, int64_t off) {
+            return SrcRows{reinterpret_cast<const int *>(d + o), (long long)m, (long long)L.P, (long long)L.S, 1.0 / (double)L.S,
+                           (long long)off, (long long)up_lo};
+        };
+    };
+    RowsReduce red(L, out);
+    return compare_run(tx, ty, n_rows * L.S, L.chunk, 2 * half, setup, prep, src(0), src(half), red, bad_id);
 } ST_CATCH_ALL
 
 int st_quartets_host(st_tree *t, const int64_t *quartets, int64_t n, int64_t stride0, int64_t stride1,

@@ -304,6 +304,63 @@ class SuchLinkedTrees:
         return compare.CladeComparisons(nodes, leaves[nodes], count[nodes], sums, r["min_" + sx], r["max_" + sx], r["min_" + sy],
                                         r["max_" + sy], tree=tree)
 
+    _HOMMOLA_IDS = 1 << 23      # ids per tree per library call: bounds the host memory of the rows
+
+    def hommola_cospeciation(self, permutations=999, seed=None):
+        """Hommola et al.'s (2009) permutation test of cospeciation on the current subset, with the semantics of
+        scikit-bio's ``hommola_cospeciation`` (interaction matrix = ``linkmatrix``, distance matrices over
+        ``subset_a_leafs`` / ``subset_b_leafs``, leaves without links included).
+
+        Pearson's r over all pairs of links (x = TreeA, y = TreeB, the pairs of :meth:`linked_distances` in its
+        orientation), then the r of ``permutations`` relabellings: per permutation, drawn in order from
+        ``numpy.random.default_rng(seed)``, mp = a permutation of the TreeB leaves, then mh = one of the TreeA leaves,
+        and every link's leaves are replaced by their images.  ``p_value`` = (count(perm_stats >= r) + 1) /
+        (permutations + 1), NaN permuted r not counted; an observed r that is NaN (a constant column) gives a NaN p and
+        NaN ``perm_stats`` without evaluating a permutation.  ``seed=None`` draws a seed and reports it.
+
+        All rows are evaluated on the GPU in batched passes (st_compare_rows_host).  Each row's result depends on its
+        links alone, so ``perm_stats[:k]`` is the same for any ``permutations >= k`` and the same seed, bit for bit.
+        ValueError for fewer than 3 links or leaves, or a ``permutations`` that is not a non-negative integer.  The
+        subset state, ``linklist`` and the generator of :meth:`sample_linked_distances` are left as they were.
+        Returns a :class:`~suchtree_amd.compare.HommolaResult`; ``r, p, stats = result`` works as with scikit-bio.
+        An extension: the reference has no counterpart (its notebook samples instead).
+        """
+        import math
+        import numbers
+        from . import compare
+        if isinstance(permutations, bool) or not isinstance(permutations, numbers.Integral) or permutations < 0:
+            raise ValueError("permutations must be a non-negative integer, got %r" % (permutations,))
+        permutations = int(permutations)
+        ll = np.ascontiguousarray(self.linklist, dtype=np.int64)
+        L = int(ll.shape[0])
+        if L < 3:
+            raise ValueError("Hommola's test needs at least 3 links; the subset has %d" % L)
+        u_a = np.asarray(self._subset_a_leafs, dtype=np.int64)
+        u_b = np.asarray(self._subset_b_leafs, dtype=np.int64)
+        if len(u_a) < 3 or len(u_b) < 3:
+            raise ValueError("Hommola's test needs at least 3 leaves in each tree; the subset has %d and %d" % (len(u_a), len(u_b)))
+        if seed is None:
+            seed = np.random.SeedSequence().entropy
+        seed = int(seed)
+        where_a = np.full(self._tree_a.size, -1, dtype=np.int64)
+        where_a[u_a] = np.arange(len(u_a))
+        where_b = np.full(self._tree_b.size, -1, dtype=np.int64)
+        where_b[u_b] = np.arange(len(u_b))
+        rows = compare.hommola_rows(u_a, u_b, where_a[ll[:, 1]], where_b[ll[:, 0]], permutations, seed,
+                                    max(1, self._HOMMOLA_IDS // L))
+        dev_a, dev_b = self._tree_a._device_tree(), self._tree_b._device_tree()
+        m0 = dev_a.compare_rows_host(dev_b, *next(rows))[0]
+        observed = compare.DistanceComparison.from_sums(*(m0[k] for k in _capi.PAIR_MOMENTS.names), n_leaves=L)
+        perm_stats = np.full(permutations, np.nan)
+        if not math.isnan(observed.pearson_r):
+            done = 0
+            for ids_a, ids_b in rows:
+                m = dev_a.compare_rows_host(dev_b, ids_a, ids_b)
+                perm_stats[done:done + len(m)] = compare.row_stats(m["n"], *(m[k] for k in compare._SUMS))[5]
+                done += len(m)
+        return compare.HommolaResult(observed.pearson_r, compare.hommola_pvalue(observed.pearson_r, perm_stats), perm_stats,
+                                     observed, L, permutations, seed)
+
     @staticmethod
     def _leaf_counts(tree: SuchTree) -> np.ndarray:
         """Leaves under every node (st_clade_plan)."""
