@@ -83,8 +83,9 @@ class DistanceComparison:
     def merge(cls, a: "DistanceComparison", b: "DistanceComparison") -> "DistanceComparison":
         """Combine results over disjoint pair ranges (Chan et al.'s pairwise update, written on the shifted sums): b's
         sums are moved to a's shift, d = b.shift - a.shift, sum(x - a.shift) = b.sx + n_b d_x,
-        sum(x - a.shift)^2 = b.sxx + 2 d_x b.sx + n_b d_x^2, and so on, then added.  Histograms add when both have the
-        same edges (otherwise ValueError)."""
+        sum(x - a.shift)^2 = b.sxx + 2 d_x b.sx + n_b d_x^2 (b.sxx itself where that is infinite), and so on, then added.
+        The class of an infinite cross product depends on the shift it was summed about and is not recovered.
+        Histograms add when both have the same edges (otherwise ValueError)."""
         if b.n_pairs == 0:
             return a
         if a.n_pairs == 0:
@@ -97,8 +98,9 @@ class DistanceComparison:
         dx, dy, nb = b.shift_x - a.shift_x, b.shift_y - a.shift_y, b.n_pairs
         sx = a.sx + b.sx + nb * dx
         sy = a.sy + b.sy + nb * dy
-        sxx = a.sxx + b.sxx + 2.0 * dx * b.sx + nb * dx * dx
-        syy = a.syy + b.syy + 2.0 * dy * b.sy + nb * dy * dy
+        # (an infinite value makes b's squares +inf about any shift: moved, they would be inf - inf = NaN)
+        sxx = a.sxx + b.sxx if math.isinf(b.sxx) else a.sxx + b.sxx + 2.0 * dx * b.sx + nb * dx * dx
+        syy = a.syy + b.syy if math.isinf(b.syy) else a.syy + b.syy + 2.0 * dy * b.sy + nb * dy * dy
         sxy = a.sxy + b.sxy + dx * b.sy + dy * b.sx + nb * dx * dy
         return cls.from_sums(a.n_pairs + nb, a.shift_x, a.shift_y, sx, sy, sxx, syy, sxy,
                              np.fmin(a.min_x, b.min_x), np.fmax(a.max_x, b.max_x), np.fmin(a.min_y, b.min_y),

@@ -1248,8 +1248,9 @@ static void clade_merge(st_pair_moments &a, const st_pair_moments &b)
     const double dx = b.shift_x - a.shift_x, dy = b.shift_y - a.shift_y, nb = (double)b.n;
     a.sx = a.sx + b.sx + nb * dx;
     a.sy = a.sy + b.sy + nb * dy;
-    a.sxx = a.sxx + b.sxx + 2.0 * dx * b.sx + nb * dx * dx;
-    a.syy = a.syy + b.syy + 2.0 * dy * b.sy + nb * dy * dy;
+    // (an infinite value makes b's squares +inf about any shift: moved, they would be inf - inf = NaN where dx * b.sx < 0)
+    a.sxx = std::isinf(b.sxx) ? a.sxx + b.sxx : a.sxx + b.sxx + 2.0 * dx * b.sx + nb * dx * dx;
+    a.syy = std::isinf(b.syy) ? a.syy + b.syy : a.syy + b.syy + 2.0 * dy * b.sy + nb * dy * dy;
     a.sxy = a.sxy + b.sxy + dx * b.sy + dy * b.sx + nb * dx * dy;
     a.n += b.n;
     a.min_x = std::fmin(a.min_x, b.min_x);

@@ -407,7 +407,10 @@ class SuchTree(TreeNavigation):
         ``distances_by_name``), or a tuple of two aligned (n, 2) node-id arrays.
         ``bins`` / ``range`` follow ``numpy.histogram2d`` (an int, two ints, or two edge arrays); ``bins=None`` skips the
         histogram.  ``range=None`` with integer bins takes numpy's default range, the data's (min, max) widened by 0.5
-        where it is empty: that costs a second pass over all pairs (the first finds min and max).
+        where it is empty: that costs a second pass over all pairs (the first finds min and max).  That first pass
+        ignores NaN distances (NaN-ignoring min and max), so the range is that of the other values; numpy raises on
+        NaN data there instead.  An infinite distance makes the range infinite: ValueError, as in numpy.  The
+        histogram leaves NaN and infinite distances out, as numpy does with a given range.
         Both trees must be on the same GPU (ValueError otherwise); an id out of range raises InvalidNodeError.
         """
         from . import compare

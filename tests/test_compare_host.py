@@ -134,6 +134,17 @@ def test_merged_histograms_add_and_must_share_edges():
         DistanceComparison.merge(a, other)
 
 
+def test_merge_keeps_infinite_squares_infinite():
+    """b holds an infinite x: its squares are +inf about any shift, also moved to a's larger shift (inf - inf before)."""
+    a = DistanceComparison.from_sums(3, 5.0, 1.0, 0.5, 0.25, 2.0, 1.0, 0.5, 4.0, 6.0, 0.5, 1.5)
+    b = DistanceComparison.from_sums(2, 0.0, 1.0, np.inf, 0.5, np.inf, 0.5, np.inf, 1.0, np.inf, 1.0, 1.5)
+    m = DistanceComparison.merge(a, b)
+    assert m.n_pairs == 5 and m.sx == np.inf and m.sxx == np.inf and m.max_x == np.inf
+    assert (m.sy, m.syy) == (0.75, 1.5)
+    c = DistanceComparison.from_sums(2, 1.0, 1.0, np.nan, 0.5, np.nan, 0.5, np.nan, 1.0, 2.0, 1.0, 1.5)
+    assert np.isnan(DistanceComparison.merge(a, c).sxx)
+
+
 def test_histogram_edges_are_numpy_s():
     rng = np.random.default_rng(2)
     x, y = rng.random(500) * 3, rng.random(500) + 7
