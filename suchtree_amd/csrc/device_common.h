@@ -1,6 +1,7 @@
 // device_common.h -- included first by every translation unit of libsuchtree_hip.so.
 // Fault word, pair sources (where pair i of a launch comes from), result sinks.
 #pragma once
+#include "compare_plan.h"
 
 namespace st {
 
@@ -92,17 +93,8 @@ struct SrcTriangle {
 // The segment of k is found by a binary search over the segments that meet k's tile of 2^kCladeTileShift pairs only
 // (tile[t].seg = the segment of pair t * 2^kCladeTileShift): one or two steps inside a large segment, at most
 // kCladeTileShift + 1 among tiny ones -- never one over all segments.  seg[] ends with a sentinel whose first = the
-// pair count.  Within a segment consecutive lanes share a row and walk the columns, as in the triangle.
-constexpr int kCladeTileShift = 13;      // 8192 pairs per tile (ST_CLADE_TILE)
-struct CladeSeg {
-    long long first;       // k of the segment's first pair
-    int r0, r1;            // row positions [r0, r1)
-    int c0, c1;            // column positions [c0, c1); c0 < 0: the triangle over [r0, r1)
-};
-struct CladeTile {
-    int seg;               // the segment of the tile's first pair (the sentinel's index past the last tile)
-    int piece;             // index of the tile's first piece (kernels_clades.h)
-};
+// pair count.  Within a segment consecutive lanes share a row and walk the columns, as in the triangle.  (CladeSeg,
+// CladeTile and kCladeTileShift: compare_plan.h, where the host fills them.)
 struct SrcSegments {
     const int *ids;
     const int *rank;

@@ -1,0 +1,266 @@
+// host_compare.h -- part of suchtree_hip.hip (included after host_upload.h).  The device side of the compare paths
+// (st_compare_*_host): compare_run drives chunks of pairs through the unchanged distance kernels of tree X and then
+// tree Y into two float32 scratch buffers on the device, and a reducer -- MomentsReduce (kernels_compare.h), CladeReduce
+// (kernels_clades.h), RowsReduce (kernels_rows.h) -- reduces them.  Device scratch is bounded by the chunk, host memory
+// by the histogram or the pieces: nothing grows with the pair count.  What needs no GPU -- the clade plan and its
+// tables, the rows layout, the folding of pieces -- is compare_plan.cpp.
+#pragma once
+
+constexpr int64_t kCompareChunkTriangle = (int64_t)1 << 25;   // 2 x 128 MiB of float32 distances
+constexpr int64_t kCompareChunkPairs = (int64_t)1 << 22;      // + 2 x 64 MiB of uploaded int64 pairs
+
+// parts of one device block start on 256-byte boundaries
+static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// The moments / 2-D histogram reduction of st_compare_triangle_host / st_compare_pairs_host (kernels_compare.h), as a
+// reducer of compare_run: bytes(chunk) device bytes of its own, start() once, chunk() per chunk of distances, finish()
+// enqueues the read-back, done() fills the result once the stream has drained.
+struct MomentsReduce {
+    const double *edges_x, *edges_y;
+    int32_t bins_x, bins_y;
+    st_pair_moments *out;
+    int64_t *out_hist;
+    int64_t count = 0;
+    bool want_hist = false;
+    int cells = 0, n_edges = 0;
+    size_t o_final = 0, o_shift = 0, o_edges = 0, o_hist = 0, lds = 0;
+    CmpPartial *d_part = nullptr, *d_final = nullptr;
+    double *d_shift = nullptr;
+    CmpHist H{};
+    CmpPartial fin{};
+    double shift[2] = {0.0, 0.0};
+
+    size_t bytes(int64_t)
+    {
+        want_hist = out_hist != nullptr;
+        cells = want_hist ? bins_x * bins_y : 0;
+        n_edges = want_hist ? bins_x + bins_y + 2 : 0;
+        o_final = align256(sizeof(CmpPartial) * kCmpBlocks);
+        o_shift = o_final + align256(sizeof(CmpPartial));
+        o_edges = o_shift + align256(16);
+        o_hist = o_edges + align256((size_t)n_edges * 8);
+        return o_hist + align256((size_t)cells * 8);
+    }
+    hipError_t start(char *d, int64_t total, hipStream_t s)
+    {
+        count = total;
+        d_part = reinterpret_cast<CmpPartial *>(d);
+        d_final = reinterpret_cast<CmpPartial *>(d + o_final);
+        d_shift = reinterpret_cast<double *>(d + o_shift);
+        double *d_edges = reinterpret_cast<double *>(d + o_edges);
+        H = CmpHist{d_edges, d_edges + (want_hist ? bins_x + 1 : 0), bins_x, bins_y, 0, reinterpret_cast<unsigned long long *>(d + o_hist)};
+        hipError_t e = hipSuccess;
+        if (want_hist) {
+            lds = (size_t)((cells + 1) & ~1) * 4;
+            if (lds + (size_t)n_edges * 8 <= 128 * 1024) {      // edges beside the counters; else the kernel reads them from HBM (L2)
+                lds += (size_t)n_edges * 8;
+                H.edges_in_lds = 1;
+            }
+            e = hipMemcpyAsync(d_edges, edges_x, (size_t)(bins_x + 1) * 8, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_edges + bins_x + 1, edges_y, (size_t)(bins_y + 1) * 8, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = hipMemsetAsync(H.out, 0, (size_t)cells * 8, s);
+            if (e == hipSuccess && lds > 64 * 1024 - 1024)
+                e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_pair_moments<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        }
+        return e;
+    }
+    hipError_t chunk(const float *d_x, const float *d_y, int64_t off, int64_t c, hipStream_t s)
+    {
+        if (off == 0)
+            hipLaunchKernelGGL(k_pair_shift, dim3(1), dim3(kCmpThreads), 0, s, d_x, d_y, (int)std::min<int64_t>(c, kCmpShiftPairs), d_shift);
+        if (want_hist)
+            hipLaunchKernelGGL(k_pair_moments<true>, dim3(kCmpBlocks), dim3(kCmpThreads), lds, s, d_x, d_y, (long long)c, d_shift,
+                               off == 0 ? 1 : 0, d_part, H);
+        else
+            hipLaunchKernelGGL(k_pair_moments<false>, dim3(kCmpBlocks), dim3(kCmpThreads), 0, s, d_x, d_y, (long long)c, d_shift,
+                               off == 0 ? 1 : 0, d_part, H);
+        return hipGetLastError();
+    }
+    hipError_t finish(hipStream_t s)
+    {
+        hipLaunchKernelGGL(k_pair_moments_final, dim3(1), dim3(64), 0, s, d_part, kCmpBlocks, d_final);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&fin, d_final, sizeof fin, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(shift, d_shift, sizeof shift, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && want_hist) e = hipMemcpyAsync(out_hist, H.out, (size_t)cells * 8, hipMemcpyDeviceToHost, s);
+        return e;
+    }
+    int done()
+    {
+        *out = st_pair_moments{count, shift[0], shift[1], fin.sx, fin.sy, fin.sxx, fin.syy, fin.sxy, fin.min_x, fin.max_x, fin.min_y, fin.max_y};
+        return ST_OK;
+    }
+};
+
+// count pairs in chunks of `chunk`: prep(stream, off, c) stages what chunk [off, off + c) needs, src_x(off) / src_y(off)
+// are its pair sources in tree X / Y, `red` reduces the two chunks of distances (MomentsReduce, CladeReduce).  `extra`
+// device bytes are handed to `setup` once (the caller's ids or pairs).
+template <typename Setup, typename Prep, typename SrcX, typename SrcY, typename Reduce>
+static int compare_run(st_tree *tx, st_tree *ty, int64_t count, int64_t chunk, size_t extra, Setup setup, Prep prep, SrcX src_x,
+                       SrcY src_y, Reduce &red, int64_t *bad_id)
+{
+    ST_DEVICE(tx->device);
+    // both trees live on one device and so share its staging pipe and that pipe's mutex (host_tree.h): one lock,
+    // also when tree_x == tree_y; distinct mutexes (not possible today) would be taken in address order
+    std::mutex *ma = &tx->dp->m, *mb = &ty->dp->m;
+    if (mb < ma) std::swap(ma, mb);
+    std::unique_lock<std::mutex> lock_a(*ma), lock_b;
+    if (mb != ma) lock_b = std::unique_lock<std::mutex>(*mb);
+
+    chunk = std::min(chunk, count);
+    // one device block: x | y | the reducer's | caller's data
+    const size_t o_y = align256((size_t)chunk * 4), o_red = o_y + align256((size_t)chunk * 4);
+    const size_t o_extra = o_red + align256(red.bytes(chunk)), total = o_extra + align256(extra);
+    char *d = nullptr;
+    hipStream_t s = nullptr;
+    auto cleanup = [&]() {
+        if (s) (void)hipStreamSynchronize(s);
+        (void)hipFree(d);
+        if (s) (void)hipStreamDestroy(s);
+    };
+    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d), total);
+    if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare setup: ") + hipGetErrorString(e)); }
+    float *d_x = reinterpret_cast<float *>(d), *d_y = reinterpret_cast<float *>(d + o_y);
+    char *d_extra = d + o_extra;
+    e = red.start(d + o_red, count, s);
+    if (e == hipSuccess) e = setup(d_extra, s);
+    if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare setup: ") + hipGetErrorString(e)); }
+    if (begin_host_faults(tx, s) != ST_OK || (ty != tx && begin_host_faults(ty, s) != ST_OK)) { cleanup(); return ST_ERR_HIP; }
+    for (int64_t off = 0; off < count; off += chunk) {
+        const int64_t c = std::min(chunk, count - off);
+        e = prep(d_extra, s, off, c);
+        if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare upload: ") + hipGetErrorString(e)); }
+        int rc = enqueue_src(tx, src_x(d_extra, off), c, DistSink{nullptr, d_x}, MrcaSink{nullptr, nullptr}, tx->d_fault_host, s);
+        if (rc == ST_OK)
+            rc = enqueue_src(ty, src_y(d_extra, off), c, DistSink{nullptr, d_y}, MrcaSink{nullptr, nullptr}, ty->d_fault_host, s);
+        if (rc != ST_OK) { const std::string msg = g_last_error; cleanup(); return fail(rc, msg); }
+        e = red.chunk(d_x, d_y, off, c, s);
+        if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare launch: ") + hipGetErrorString(e)); }
+    }
+    e = red.finish(s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare read-back: ") + hipGetErrorString(e)); }
+    Fault fx = kFaultInit, fy = kFaultInit;
+    int rc = end_host_faults(tx, s, fx);
+    if (rc == ST_OK && ty != tx) rc = end_host_faults(ty, s, fy);
+    cleanup();
+    if (rc != ST_OK) return rc;
+    rc = report_fault(tx->n_nodes, fx, bad_id);      // (not expected: the ids were checked on the host)
+    if (rc == ST_OK) rc = report_fault(ty->n_nodes, fy, bad_id);
+    if (rc != ST_OK) return rc;
+    return red.done();
+}
+
+// The reducer of st_compare_clades_host: k_clade_pieces per chunk into one device array of pieces, read back at the end;
+// done() merges pieces into segments (index order) and segments into nodes (children first, in id order, then the
+// node's own segments) on the host.
+struct CladeReduce {
+    const CladePlan &P;
+    const CladeTables &T;
+    st_pair_moments *out;
+    int64_t cap;
+    const CladeSeg *d_seg = nullptr;             // (set by the caller's setup)
+    const CladeTile *d_tile = nullptr;
+    CladePiece *d_pieces = nullptr;
+    std::vector<CladePiece> pieces;
+
+    size_t bytes(int64_t) { return (size_t)T.n_pieces * sizeof(CladePiece); }
+    hipError_t start(char *d, int64_t, hipStream_t)
+    {
+        d_pieces = reinterpret_cast<CladePiece *>(d);
+        return hipSuccess;
+    }
+    hipError_t chunk(const float *d_x, const float *d_y, int64_t off, int64_t c, hipStream_t s)
+    {
+        const int64_t tiles_c = (c + ST_CLADE_TILE - 1) / ST_CLADE_TILE;
+        const int64_t blocks = (tiles_c + kCladeThreads / 64 - 1) / (kCladeThreads / 64);
+        hipLaunchKernelGGL(k_clade_pieces, dim3((unsigned)blocks), dim3(kCladeThreads), 0, s, d_x, d_y, (long long)off, (long long)c, d_seg,
+                           d_tile, d_pieces);
+        return hipGetLastError();
+    }
+    hipError_t finish(hipStream_t s)
+    {
+        pieces.resize(T.n_pieces);
+        return hipMemcpyAsync(pieces.data(), d_pieces, (size_t)T.n_pieces * sizeof(CladePiece), hipMemcpyDeviceToHost, s);
+    }
+    int done()
+    {
+        clade_fold(P, T, pieces.data(), cap, out);
+        return ST_OK;
+    }
+};
+
+// The reducer of st_compare_rows_host: k_row_blocks per chunk into one of two device piece buffers, each read back into
+// its pinned host twin; the host folds a chunk's pieces into their rows (block order, clade_merge) while the device works
+// on the next chunk.  Pieces of at most two chunks exist at any time.
+struct RowsReduce {
+    const RowsLayout &L;
+    st_pair_moments *out;
+    CladePiece *d_pieces[2] = {nullptr, nullptr}, *h_pieces[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int64_t first[2] = {0, 0}, count[2] = {0, 0};      // buffer i holds blocks [first, first + count); 0: nothing pending
+    int next = 0;
+
+    RowsReduce(const RowsLayout &l, st_pair_moments *o) : L(l), out(o) {}
+    ~RowsReduce()
+    {
+        for (int i = 0; i < 2; i++) {
+            if (h_pieces[i]) (void)hipHostFree(h_pieces[i]);
+            if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+    }
+    size_t piece_bytes() const { return align256((size_t)L.max_blocks * sizeof(CladePiece)); }
+    size_t bytes(int64_t) { return 2 * piece_bytes(); }
+    hipError_t start(char *d, int64_t, hipStream_t)
+    {
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < 2 && e == hipSuccess; i++) {
+            d_pieces[i] = reinterpret_cast<CladePiece *>(d + i * piece_bytes());
+            e = hipHostMalloc(reinterpret_cast<void **>(&h_pieces[i]), (size_t)L.max_blocks * sizeof(CladePiece), hipHostMallocDefault);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
+        }
+        return e;
+    }
+    hipError_t drain(int i)
+    {
+        if (count[i] == 0) return hipSuccess;
+        const hipError_t e = hipEventSynchronize(ev[i]);
+        if (e != hipSuccess) return e;
+        for (int64_t j = 0; j < count[i]; j++) {
+            const int64_t t = first[i] + j;
+            clade_merge(out[t / L.nb], piece_moments(h_pieces[i][j], L.block_len(t)));
+        }
+        count[i] = 0;
+        return hipSuccess;
+    }
+    hipError_t chunk(const float *d_x, const float *d_y, int64_t off, int64_t c, hipStream_t s)
+    {
+        const int i = next;
+        next ^= 1;
+        hipError_t e = drain(i);      // (the pieces of two chunks ago)
+        if (e != hipSuccess) return e;
+        const int64_t t0 = L.block_of(off), n = L.block_of(off + c - 1) + 1 - t0, tl = t0 + n - 1;
+        if (n > L.max_blocks || L.block_lo(t0) != off || L.block_lo(tl) + L.block_len(tl) > off + c) return hipErrorInvalidValue;
+        const int64_t per = L.P <= kCladeLanePiece ? kCladeThreads : kCladeThreads / 64;      // blocks per workgroup
+        hipLaunchKernelGGL(k_row_blocks, dim3((unsigned)((n + per - 1) / per)), dim3(kCladeThreads), 0, s, d_x, d_y, (long long)off,
+                           (long long)L.S, (long long)L.P, (long long)L.nb, (long long)t0, (long long)n, d_pieces[i]);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(h_pieces[i], d_pieces[i], (size_t)n * sizeof(CladePiece), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipEventRecord(ev[i], s);
+        if (e == hipSuccess) {
+            first[i] = t0;
+            count[i] = n;
+        }
+        return e;
+    }
+    hipError_t finish(hipStream_t) { return hipSuccess; }
+    int done()
+    {
+        for (int k = 0; k < 2; k++, next ^= 1) {      // the older buffer first
+            const hipError_t e = drain(next);
+            if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("rows read-back: ") + hipGetErrorString(e));
+        }
+        return ST_OK;
+    }
+};

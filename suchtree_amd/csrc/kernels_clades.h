@@ -2,8 +2,8 @@
 // The reduction of st_compare_clades_host: pair k has a float32 distance x[k] in tree X and y[k] in tree Y, written by
 // the unchanged distance kernels over SrcSegments into compare_run's two scratch chunks.  The pair range is cut into
 // tiles of 2^kCladeTileShift pairs aligned to global k (chunks are whole tiles); a piece is one segment's part of one
-// tile.  This kernel writes the shifted float64 sums and the min / max of every piece; the host merges pieces into
-// segments and segments into clades.
+// tile.  This kernel writes the shifted float64 sums and the min / max of every piece (CladePiece, compare_plan.h); the
+// host merges pieces into segments and segments into clades (compare_plan.cpp: clade_fold).
 //
 // Determinism: a piece is summed about its own first pair (cx, cy) = (x, y) of that pair, so it needs nothing from
 // another tile or chunk, and in one order that depends on its length alone -- up to kCladeLanePiece pairs by one lane
@@ -15,12 +15,6 @@ namespace st {
 
 constexpr int kCladeThreads = 256;        // four waves per workgroup, one tile per wave
 constexpr int kCladeLanePiece = 64;       // pieces of at most this many pairs are summed by a single lane
-
-struct CladePiece {
-    double sx, sy, sxx, syy, sxy;          // sums of (x - cx), (y - cy), squares and cross product
-    float cx, cy;                          // the shift: the piece's first pair (0 where that is not finite)
-    float min_x, max_x, min_y, max_y;      // NaN-ignoring; +inf / -inf when nothing was seen
-};
 
 struct CladeAcc {
     double sx = 0.0, sy = 0.0, sxx = 0.0, syy = 0.0, sxy = 0.0;

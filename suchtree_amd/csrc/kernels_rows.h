@@ -3,7 +3,7 @@
 // rounded up to whole tiles with pairs [P, S) as padding).  A block is the row's pairs [2^kCladeTileShift b,
 // min(2^kCladeTileShift (b + 1), P)), counted from the row's first pair; global block t is block t % nb of row t / nb
 // (nb blocks per row), and chunks hold whole blocks.  This kernel writes one CladePiece per block and skips the padding;
-// the host folds a row's blocks in block order (clade_merge).
+// the host folds a row's blocks in block order (RowsReduce::drain, host_compare.h; clade_merge, compare_plan.cpp).
 //
 // Determinism: a block is summed about its own first pair in the order rule of k_clade_pieces, which depends on its
 // length alone -- up to kCladeLanePiece pairs by one lane in index order, longer ones by one wave (lane l takes pairs l,

@@ -27,8 +27,10 @@
 // functions, exported through launch_decl.h -- and this file: error plumbing, the C ABI and the host side in
 // between: st_tree.h / host_tree.h (handle, pipe registry), launch_policy.h + host_launch.h (which family a
 // request gets, enqueueing, faults), host_path.h (host-buffer pipeline, mailbox, copy kernels), host_upload.h
-// (tables -> device), kernels_misc.h (k nearest, graph matrices), kernels_compare.h (moments / 2-D histogram of two
-// trees' distances over the same pairs: st_compare_*).
+// (tables -> device), kernels_misc.h (k nearest, graph matrices), and the compare paths (st_compare_*: two trees'
+// distances over the same pairs, reduced on the device): kernels_compare.h / kernels_clades.h / kernels_rows.h (moments
+// and 2-D histogram, clade pieces, row blocks), host_compare.h (the chunk driver compare_run and its reducers) and,
+// host-only C++ beside tree_prep.cpp, compare_plan.cpp (argument checks, clade plan and tables, rows layout, the fold).
 //
 // Host side of the C ABI: tree upload to one or several GPUs (tree_prep.cpp builds the tables, under a table budget
 // if one is given), the host path (host_pipe.h, host_copy.h: packed ids in through the copy engine, kernels write
@@ -145,6 +147,7 @@ using namespace st;
 #include "host_path.h"
 #include "host_tune.h"
 #include "host_upload.h"
+#include "host_compare.h"
 
 extern "C" {
 
@@ -741,14 +744,20 @@ try {
     return distances_host_impl(t, pairs, n, stride0, stride1, out_dist, out_mrca, bad_id);
 } ST_CATCH_ALL
 
+static int triangle_range_args(int64_t m, int64_t k_begin, int64_t k_count)
+{
+    if (m < 0 || k_begin < 0 || k_count < 0) return fail(ST_ERR_ARG, "negative size");
+    if (m > 3000000000LL) return fail(ST_ERR_ARG, "m too large");
+    if (k_begin + k_count > m * (m - 1) / 2) return fail(ST_ERR_ARG, "pair range exceeds m(m-1)/2");
+    return ST_OK;
+}
+
 static int triangle_args(st_tree *t, const int64_t *ids, int64_t m, int64_t k_begin, int64_t k_count,
                          const void *out_d, const void *out_m)
 {
     if (!t) return fail(ST_ERR_ARG, "tree is NULL");
-    if (m < 0 || k_begin < 0 || k_count < 0) return fail(ST_ERR_ARG, "negative size");
-    if (m > 3000000000LL) return fail(ST_ERR_ARG, "m too large");
-    const int64_t total = m * (m - 1) / 2;
-    if (k_begin + k_count > total) return fail(ST_ERR_ARG, "pair range exceeds m(m-1)/2");
+    const int rc = triangle_range_args(m, k_begin, k_count);
+    if (rc != ST_OK) return rc;
     if (k_count > 0 && !ids) return fail(ST_ERR_ARG, "ids is NULL");
     if (!out_d && !out_m) return fail(ST_ERR_ARG, "both outputs are NULL");
     return ST_OK;
@@ -909,44 +918,12 @@ try {
 
 }  // extern "C"
 
-// ---- compare path (st_compare_triangle_host / st_compare_pairs_host) --------------------------------------------
-// Chunks of pairs go through the unchanged distance kernels of tree X and then tree Y into two float32 scratch
-// buffers on the device; kernels_compare.h reduces them.  Device scratch is bounded by the chunk, host memory by the
-// histogram: nothing grows with the pair count.
-constexpr int64_t kCompareChunkTriangle = (int64_t)1 << 25;   // 2 x 128 MiB of float32 distances
-constexpr int64_t kCompareChunkPairs = (int64_t)1 << 22;      // + 2 x 64 MiB of uploaded int64 pairs
-
-static int compare_hist_args(const double *edges_x, int32_t bins_x, const double *edges_y, int32_t bins_y, const int64_t *out_hist)
-{
-    if (!edges_x && !edges_y && !out_hist) return ST_OK;
-    if (!edges_x || !edges_y || !out_hist) return fail(ST_ERR_ARG, "edges_x, edges_y and out_hist must all be given or all be NULL");
-    if (bins_x < 1 || bins_y < 1) return fail(ST_ERR_ARG, "bins_x and bins_y must be >= 1");
-    if ((int64_t)bins_x * bins_y > kCmpMaxCells)
-        return fail(ST_ERR_ARG, "histogram of " + std::to_string((int64_t)bins_x * bins_y) + " cells: at most " + std::to_string(kCmpMaxCells));
-    const double *edges[2] = {edges_x, edges_y};
-    const int32_t bins[2] = {bins_x, bins_y};
-    for (int a = 0; a < 2; a++) {
-        const double *e = edges[a];
-        for (int32_t i = 0; i <= bins[a]; i++) {
-            if (!std::isfinite(e[i])) return fail(ST_ERR_ARG, "histogram edges must be finite");
-            if (i > 0 && e[i] < e[i - 1]) return fail(ST_ERR_ARG, "histogram edges must be monotonically increasing");
-        }
-        if (!(e[0] < e[bins[a]])) return fail(ST_ERR_ARG, "the first histogram edge must be below the last");
-    }
-    return ST_OK;
-}
-
+// ---- compare paths (st_compare_*_host, st_clade_plan): validate, stage, call compare_run (host_compare.h) -----------
 // ids on the host, before anything is launched: ST_ERR_BOUNDS with the id the reference reports (MuchTree.pyx:897-903)
 static int compare_check_ids(const int64_t *ids, int64_t n, int64_t n_nodes, int64_t *bad_id)
 {
     Fault f = kFaultInit;
-    for (int64_t i = 0; i < n; i++) {
-        const long long v = ids[i];
-        if (v < 0 || v >= n_nodes) {
-            f.max_bad = std::max(f.max_bad, v);
-            f.min_bad = std::min(f.min_bad, v);
-        }
-    }
+    ids_in_range(ids, n, n_nodes, f.max_bad, f.min_bad);
     return report_fault(n_nodes, f, bad_id);
 }
 
@@ -959,488 +936,17 @@ static int compare_trees_args(st_tree *tx, st_tree *ty)
     return ST_OK;
 }
 
+static int chunk_pairs_arg(int64_t chunk_pairs)
+{
+    if (chunk_pairs >= 0 && chunk_pairs % ST_CLADE_TILE == 0) return ST_OK;
+    return fail(ST_ERR_ARG, "chunk_pairs must be 0 or a positive multiple of " + std::to_string(ST_CLADE_TILE));
+}
+
 static void compare_empty(st_pair_moments *out, int64_t *out_hist, int32_t bins_x, int32_t bins_y)
 {
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    *out = st_pair_moments{0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, nan, nan, nan, nan};
+    *out = moments_empty();
     if (out_hist) std::memset(out_hist, 0, (size_t)bins_x * (size_t)bins_y * 8);
 }
-
-// The moments / 2-D histogram reduction of st_compare_triangle_host / st_compare_pairs_host (kernels_compare.h), as a
-// reducer of compare_run: bytes(chunk) device bytes of its own, start() once, chunk() per chunk of distances, finish()
-// enqueues the read-back, done() fills the result once the stream has drained.
-struct MomentsReduce {
-    const double *edges_x, *edges_y;
-    int32_t bins_x, bins_y;
-    st_pair_moments *out;
-    int64_t *out_hist;
-    int64_t count = 0;
-    bool want_hist = false;
-    int cells = 0, n_edges = 0;
-    size_t o_final = 0, o_shift = 0, o_edges = 0, o_hist = 0, lds = 0;
-    CmpPartial *d_part = nullptr, *d_final = nullptr;
-    double *d_shift = nullptr;
-    CmpHist H{};
-    CmpPartial fin{};
-    double shift[2] = {0.0, 0.0};
-
-    static size_t up(size_t b) { return (b + 255) & ~(size_t)255; }
-    size_t bytes(int64_t)
-    {
-        want_hist = out_hist != nullptr;
-        cells = want_hist ? bins_x * bins_y : 0;
-        n_edges = want_hist ? bins_x + bins_y + 2 : 0;
-        o_final = up(sizeof(CmpPartial) * kCmpBlocks);
-        o_shift = o_final + up(sizeof(CmpPartial));
-        o_edges = o_shift + up(16);
-        o_hist = o_edges + up((size_t)n_edges * 8);
-        return o_hist + up((size_t)cells * 8);
-    }
-    hipError_t start(char *d, int64_t total, hipStream_t s)
-    {
-        count = total;
-        d_part = reinterpret_cast<CmpPartial *>(d);
-        d_final = reinterpret_cast<CmpPartial *>(d + o_final);
-        d_shift = reinterpret_cast<double *>(d + o_shift);
-        double *d_edges = reinterpret_cast<double *>(d + o_edges);
-        H = CmpHist{d_edges, d_edges + (want_hist ? bins_x + 1 : 0), bins_x, bins_y, 0, reinterpret_cast<unsigned long long *>(d + o_hist)};
-        hipError_t e = hipSuccess;
-        if (want_hist) {
-            lds = (size_t)((cells + 1) & ~1) * 4;
-            if (lds + (size_t)n_edges * 8 <= 128 * 1024) {      // edges beside the counters; else the kernel reads them from HBM (L2)
-                lds += (size_t)n_edges * 8;
-                H.edges_in_lds = 1;
-            }
-            e = hipMemcpyAsync(d_edges, edges_x, (size_t)(bins_x + 1) * 8, hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_edges + bins_x + 1, edges_y, (size_t)(bins_y + 1) * 8, hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) e = hipMemsetAsync(H.out, 0, (size_t)cells * 8, s);
-            if (e == hipSuccess && lds > 64 * 1024 - 1024)
-                e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_pair_moments<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        }
-        return e;
-    }
-    hipError_t chunk(const float *d_x, const float *d_y, int64_t off, int64_t c, hipStream_t s)
-    {
-        if (off == 0)
-            hipLaunchKernelGGL(k_pair_shift, dim3(1), dim3(kCmpThreads), 0, s, d_x, d_y, (int)std::min<int64_t>(c, kCmpShiftPairs), d_shift);
-        if (want_hist)
-            hipLaunchKernelGGL(k_pair_moments<true>, dim3(kCmpBlocks), dim3(kCmpThreads), lds, s, d_x, d_y, (long long)c, d_shift,
-                               off == 0 ? 1 : 0, d_part, H);
-        else
-            hipLaunchKernelGGL(k_pair_moments<false>, dim3(kCmpBlocks), dim3(kCmpThreads), 0, s, d_x, d_y, (long long)c, d_shift,
-                               off == 0 ? 1 : 0, d_part, H);
-        return hipGetLastError();
-    }
-    hipError_t finish(hipStream_t s)
-    {
-        hipLaunchKernelGGL(k_pair_moments_final, dim3(1), dim3(64), 0, s, d_part, kCmpBlocks, d_final);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(&fin, d_final, sizeof fin, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(shift, d_shift, sizeof shift, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && want_hist) e = hipMemcpyAsync(out_hist, H.out, (size_t)cells * 8, hipMemcpyDeviceToHost, s);
-        return e;
-    }
-    int done()
-    {
-        *out = st_pair_moments{count, shift[0], shift[1], fin.sx, fin.sy, fin.sxx, fin.syy, fin.sxy, fin.min_x, fin.max_x, fin.min_y, fin.max_y};
-        return ST_OK;
-    }
-};
-
-// count pairs in chunks of `chunk`: prep(stream, off, c) stages what chunk [off, off + c) needs, src_x(off) / src_y(off)
-// are its pair sources in tree X / Y, `red` reduces the two chunks of distances (MomentsReduce, CladeReduce).  `extra`
-// device bytes are handed to `setup` once (the caller's ids or pairs).
-template <typename Setup, typename Prep, typename SrcX, typename SrcY, typename Reduce>
-static int compare_run(st_tree *tx, st_tree *ty, int64_t count, int64_t chunk, size_t extra, Setup setup, Prep prep, SrcX src_x,
-                       SrcY src_y, Reduce &red, int64_t *bad_id)
-{
-    ST_DEVICE(tx->device);
-    // both trees live on one device and so share its staging pipe and that pipe's mutex (host_tree.h): one lock,
-    // also when tree_x == tree_y; distinct mutexes (not possible today) would be taken in address order
-    std::mutex *ma = &tx->dp->m, *mb = &ty->dp->m;
-    if (mb < ma) std::swap(ma, mb);
-    std::unique_lock<std::mutex> lock_a(*ma), lock_b;
-    if (mb != ma) lock_b = std::unique_lock<std::mutex>(*mb);
-
-    chunk = std::min(chunk, count);
-    // one device block: x | y | the reducer's | caller's data
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_y = up((size_t)chunk * 4), o_red = o_y + up((size_t)chunk * 4);
-    const size_t o_extra = o_red + up(red.bytes(chunk)), total = o_extra + up(extra);
-    char *d = nullptr;
-    hipStream_t s = nullptr;
-    auto cleanup = [&]() {
-        if (s) (void)hipStreamSynchronize(s);
-        (void)hipFree(d);
-        if (s) (void)hipStreamDestroy(s);
-    };
-    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d), total);
-    if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare setup: ") + hipGetErrorString(e)); }
-    float *d_x = reinterpret_cast<float *>(d), *d_y = reinterpret_cast<float *>(d + o_y);
-    char *d_extra = d + o_extra;
-    e = red.start(d + o_red, count, s);
-    if (e == hipSuccess) e = setup(d_extra, s);
-    if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare setup: ") + hipGetErrorString(e)); }
-    if (begin_host_faults(tx, s) != ST_OK || (ty != tx && begin_host_faults(ty, s) != ST_OK)) { cleanup(); return ST_ERR_HIP; }
-    for (int64_t off = 0; off < count; off += chunk) {
-        const int64_t c = std::min(chunk, count - off);
-        e = prep(d_extra, s, off, c);
-        if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare upload: ") + hipGetErrorString(e)); }
-        int rc = enqueue_src(tx, src_x(d_extra, off), c, DistSink{nullptr, d_x}, MrcaSink{nullptr, nullptr}, tx->d_fault_host, s);
-        if (rc == ST_OK)
-            rc = enqueue_src(ty, src_y(d_extra, off), c, DistSink{nullptr, d_y}, MrcaSink{nullptr, nullptr}, ty->d_fault_host, s);
-        if (rc != ST_OK) { const std::string msg = g_last_error; cleanup(); return fail(rc, msg); }
-        e = red.chunk(d_x, d_y, off, c, s);
-        if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare launch: ") + hipGetErrorString(e)); }
-    }
-    e = red.finish(s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare read-back: ") + hipGetErrorString(e)); }
-    Fault fx = kFaultInit, fy = kFaultInit;
-    int rc = end_host_faults(tx, s, fx);
-    if (rc == ST_OK && ty != tx) rc = end_host_faults(ty, s, fy);
-    cleanup();
-    if (rc != ST_OK) return rc;
-    rc = report_fault(tx->n_nodes, fx, bad_id);      // (not expected: the ids were checked on the host)
-    if (rc == ST_OK) rc = report_fault(ty->n_nodes, fy, bad_id);
-    if (rc != ST_OK) return rc;
-    return red.done();
-}
-
-// ---- every clade at once (st_clade_plan / st_compare_clades_host) ------------------------------------------------
-static_assert((1 << kCladeTileShift) == ST_CLADE_TILE, "device_common.h: kCladeTileShift");
-constexpr int64_t kCladeChunkPairs = (int64_t)1 << 25;      // 2 x 128 MiB of float32 distances, as the triangle
-
-// The clade tree's children in increasing id order, its preorder, the permutation that makes every clade one range of
-// link positions, and the segments.  Iterative throughout (a caterpillar of 1e5 levels is fine).
-struct CladePlan {
-    std::vector<int64_t> child_off, child;       // CSR: children of v are child[child_off[v] .. child_off[v + 1])
-    std::vector<int64_t> pre;                    // preorder (children in order); reversed, every child precedes its parent
-    std::vector<int64_t> perm, begin, count, leaves;
-    std::vector<st_clade_segment> segs;          // in pair order: nodes by link count, each node's own segments together
-    std::vector<int64_t> node_seg;               // node v's segments: segs[node_seg[v] .. node_seg[v] + node_nseg[v])
-    std::vector<int32_t> node_nseg;
-    int64_t total = 0;
-};
-
-static int clade_plan(const int32_t *parent, int64_t n, const int64_t *link_leaf, int64_t L, int64_t cap, CladePlan &P,
-                      int64_t *bad_id)
-{
-    if (n < 1) return fail(ST_ERR_ARG, "n_nodes < 1");
-    if (n > INT32_MAX || L > INT32_MAX) return fail(ST_ERR_ARG, "more than 2^31 - 1 nodes or links");
-    if (L < 0) return fail(ST_ERR_ARG, "n_links < 0");
-    if (!parent || (L > 0 && !link_leaf)) return fail(ST_ERR_ARG, "parent or link_leaf is NULL");
-    int64_t root = -1;
-    P.child_off.assign(n + 1, 0);
-    for (int64_t v = 0; v < n; v++) {
-        const int64_t p = parent[v];
-        if (p == -1) {
-            if (root >= 0) return fail(ST_ERR_TREE, "parent array has more than one root");
-            root = v;
-        } else if (p < 0 || p >= n || p == v) {
-            return fail(ST_ERR_TREE, "parent[" + std::to_string(v) + "] = " + std::to_string(p) + " is not a node");
-        } else {
-            P.child_off[p + 1]++;
-        }
-    }
-    if (root < 0) return fail(ST_ERR_TREE, "parent array has no root");
-    for (int64_t v = 0; v < n; v++) P.child_off[v + 1] += P.child_off[v];
-    P.child.assign(n > 1 ? n - 1 : 0, 0);
-    {
-        std::vector<int64_t> fill(P.child_off.begin(), P.child_off.end() - 1);
-        for (int64_t v = 0; v < n; v++)
-            if (parent[v] >= 0) P.child[fill[parent[v]]++] = v;      // (increasing id order)
-    }
-    P.pre.clear();
-    P.pre.reserve(n);
-    std::vector<int64_t> stack{root};
-    while (!stack.empty()) {
-        const int64_t v = stack.back();
-        stack.pop_back();
-        P.pre.push_back(v);
-        for (int64_t i = P.child_off[v + 1] - 1; i >= P.child_off[v]; i--) stack.push_back(P.child[i]);
-        if ((int64_t)P.pre.size() > n) break;
-    }
-    if ((int64_t)P.pre.size() != n) return fail(ST_ERR_TREE, "parent array is not one rooted tree (a cycle or a detached node)");
-    auto is_leaf = [&](int64_t v) { return P.child_off[v + 1] == P.child_off[v]; };
-    // links: ids in range (as the compare calls report them), then leaves only
-    Fault f = kFaultInit;
-    for (int64_t j = 0; j < L; j++) {
-        const long long v = link_leaf[j];
-        if (v < 0 || v >= n) {
-            f.max_bad = std::max(f.max_bad, v);
-            f.min_bad = std::min(f.min_bad, v);
-        }
-    }
-    int rc = report_fault(n, f, bad_id);
-    if (rc != ST_OK) return rc;
-    P.count.assign(n, 0);
-    for (int64_t j = 0; j < L; j++) {
-        if (!is_leaf(link_leaf[j])) return fail(ST_ERR_ARG, "link " + std::to_string(j) + ": node " + std::to_string(link_leaf[j]) + " is not a leaf of the clade tree");
-        P.count[link_leaf[j]]++;
-    }
-    // leaves in preorder get consecutive position ranges; links keep rank order within a leaf
-    P.begin.assign(n, 0);
-    P.leaves.assign(n, 0);
-    int64_t pos = 0;
-    for (const int64_t v : P.pre)
-        if (is_leaf(v)) {
-            P.begin[v] = pos;
-            pos += P.count[v];
-            P.leaves[v] = 1;
-        }
-    {
-        std::vector<int64_t> cur(P.begin);
-        P.perm.assign(L, 0);
-        for (int64_t j = 0; j < L; j++) P.perm[cur[link_leaf[j]]++] = j;
-    }
-    for (int64_t i = n - 1; i >= 0; i--) {
-        const int64_t v = P.pre[i];
-        if (is_leaf(v)) continue;
-        int64_t c = 0, l = 0;
-        for (int64_t e = P.child_off[v]; e < P.child_off[v + 1]; e++) {
-            c += P.count[P.child[e]];
-            l += P.leaves[P.child[e]];
-        }
-        P.count[v] = c;
-        P.leaves[v] = l;
-        P.begin[v] = P.begin[P.child[P.child_off[v]]];
-    }
-    // segments
-    P.segs.clear();
-    P.node_seg.assign(n, 0);
-    P.node_nseg.assign(n, 0);
-    P.total = 0;
-    auto emit = [&](int32_t kind, int64_t v, int64_t r0, int64_t r1, int64_t c0, int64_t c1, int64_t np) {
-        P.segs.push_back(st_clade_segment{P.total, np, kind, (int32_t)v, (int32_t)r0, (int32_t)r1, (int32_t)c0, (int32_t)c1});
-        P.total += np;
-        P.node_nseg[v]++;
-    };
-    // nodes by link count (ties: reverse preorder), so that the segments of the nodes within any cap are a prefix of the
-    // pair range and keep their pair indices -- hence their pieces and their bits -- whatever the cap
-    std::vector<int64_t> order(P.pre.rbegin(), P.pre.rend());
-    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return P.count[a] < P.count[b]; });
-    for (const int64_t v : order) {
-        P.node_seg[v] = (int64_t)P.segs.size();
-        if (cap >= 0 && P.count[v] > cap) continue;
-        const int64_t end = P.begin[v] + P.count[v];
-        if (is_leaf(v)) {
-            if (P.count[v] >= 2) emit(ST_CLADE_TRI, v, P.begin[v], end, 0, 0, P.count[v] * (P.count[v] - 1) / 2);
-            continue;
-        }
-        for (int64_t e = P.child_off[v]; e + 1 < P.child_off[v + 1]; e++) {
-            const int64_t c = P.child[e], rows = P.count[c], c0 = P.begin[c] + rows;
-            if (rows > 0 && end > c0) emit(ST_CLADE_RECT, v, P.begin[c], c0, c0, end, rows * (end - c0));
-        }
-    }
-    return ST_OK;
-}
-
-// Chan's pairwise update on shifted sums, in the operation order of compare.DistanceComparison.merge: b moved to a's shift
-static void clade_merge(st_pair_moments &a, const st_pair_moments &b)
-{
-    if (b.n == 0) return;
-    if (a.n == 0) {
-        a = b;
-        return;
-    }
-    const double dx = b.shift_x - a.shift_x, dy = b.shift_y - a.shift_y, nb = (double)b.n;
-    a.sx = a.sx + b.sx + nb * dx;
-    a.sy = a.sy + b.sy + nb * dy;
-    // (an infinite value makes b's squares +inf about any shift: moved, they would be inf - inf = NaN where dx * b.sx < 0)
-    a.sxx = std::isinf(b.sxx) ? a.sxx + b.sxx : a.sxx + b.sxx + 2.0 * dx * b.sx + nb * dx * dx;
-    a.syy = std::isinf(b.syy) ? a.syy + b.syy : a.syy + b.syy + 2.0 * dy * b.sy + nb * dy * dy;
-    a.sxy = a.sxy + b.sxy + dx * b.sy + dy * b.sx + nb * dx * dy;
-    a.n += b.n;
-    a.min_x = std::fmin(a.min_x, b.min_x);
-    a.max_x = std::fmax(a.max_x, b.max_x);
-    a.min_y = std::fmin(a.min_y, b.min_y);
-    a.max_y = std::fmax(a.max_y, b.max_y);
-}
-
-// The reducer of st_compare_clades_host: k_clade_pieces per chunk into one device array of pieces, read back at the end;
-// done() merges pieces into segments (index order) and segments into nodes (children first, in id order, then the
-// node's own segments) on the host.
-struct CladeReduce {
-    const CladePlan &P;
-    const std::vector<CladeTile> &tiles;
-    const std::vector<int64_t> &seg_piece;       // segment s's pieces: [seg_piece[s], seg_piece[s + 1])
-    const CladeSeg *d_seg = nullptr;             // (set by the caller's setup)
-    const CladeTile *d_tile = nullptr;
-    st_pair_moments *out;
-    int64_t cap;
-    int64_t n_pieces = 0;
-    CladePiece *d_pieces = nullptr;
-    std::vector<CladePiece> pieces;
-
-    size_t bytes(int64_t) { return (size_t)n_pieces * sizeof(CladePiece); }
-    hipError_t start(char *d, int64_t, hipStream_t)
-    {
-        d_pieces = reinterpret_cast<CladePiece *>(d);
-        return hipSuccess;
-    }
-    hipError_t chunk(const float *d_x, const float *d_y, int64_t off, int64_t c, hipStream_t s)
-    {
-        const int64_t tiles_c = (c + ST_CLADE_TILE - 1) / ST_CLADE_TILE;
-        const int64_t blocks = (tiles_c + kCladeThreads / 64 - 1) / (kCladeThreads / 64);
-        hipLaunchKernelGGL(k_clade_pieces, dim3((unsigned)blocks), dim3(kCladeThreads), 0, s, d_x, d_y, (long long)off, (long long)c, d_seg,
-                           d_tile, d_pieces);
-        return hipGetLastError();
-    }
-    hipError_t finish(hipStream_t s)
-    {
-        pieces.resize(n_pieces);
-        return hipMemcpyAsync(pieces.data(), d_pieces, (size_t)n_pieces * sizeof(CladePiece), hipMemcpyDeviceToHost, s);
-    }
-    int done()
-    {
-        const int64_t n = (int64_t)P.pre.size();
-        const double nan = std::numeric_limits<double>::quiet_NaN();
-        const st_pair_moments empty{0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, nan, nan, nan, nan};
-        std::vector<st_pair_moments> seg_m(P.segs.size(), empty);
-        for (size_t si = 0; si < P.segs.size(); si++) {
-            const st_clade_segment &g = P.segs[si];
-            const int64_t seg_end = g.first_pair + g.n_pairs;
-            for (int64_t q = seg_piece[si]; q < seg_piece[si + 1]; q++) {
-                // piece q of segment si: its part of tile t
-                const int64_t t = (g.first_pair >> kCladeTileShift) + (q - seg_piece[si]);
-                const int64_t lo = std::max<int64_t>(g.first_pair, t << kCladeTileShift);
-                const int64_t hi = std::min<int64_t>(seg_end, (t + 1) << kCladeTileShift);
-                const CladePiece &c = pieces[q];
-                const st_pair_moments pm{hi - lo, (double)c.cx, (double)c.cy, c.sx, c.sy, c.sxx, c.syy, c.sxy,
-                                         (double)c.min_x, (double)c.max_x, (double)c.min_y, (double)c.max_y};
-                clade_merge(seg_m[si], pm);
-            }
-        }
-        const st_pair_moments skipped{-1, nan, nan, nan, nan, nan, nan, nan, nan, nan, nan, nan};
-        for (int64_t i = n - 1; i >= 0; i--) {      // (a node within the cap has every child within it)
-            const int64_t v = P.pre[i];
-            if (cap >= 0 && P.count[v] > cap) {
-                out[v] = skipped;
-                continue;
-            }
-            st_pair_moments acc = empty;
-            for (int64_t e = P.child_off[v]; e < P.child_off[v + 1]; e++) clade_merge(acc, out[P.child[e]]);
-            for (int64_t si = P.node_seg[v]; si < P.node_seg[v] + P.node_nseg[v]; si++) clade_merge(acc, seg_m[si]);
-            out[v] = acc;
-        }
-        return ST_OK;
-    }
-};
-
-// ---- many triangles at once (st_compare_rows_host) ----------------------------------------------------------------
-// Row r's pairs sit at global index r * S + k (SrcRows).  Rows of at most half a chunk are dense (S = P; a chunk holds
-// whole rows, at most kRowsChunkBlocks blocks' worth so that tiny rows do not make huge piece buffers); larger rows are
-// padded to whole tiles (S = P rounded up) and a chunk is whole tiles.  Either way no block straddles a chunk.
-constexpr int64_t kRowsChunkBlocks = (int64_t)1 << 18;      // 16 MiB of pieces per buffer
-struct RowsLayout {
-    int64_t P = 0, S = 0, nb = 0, chunk = 0, max_rows = 0, max_blocks = 0;
-};
-
-static RowsLayout rows_layout(int64_t n_rows, int64_t m, int64_t chunk_pairs)
-{
-    RowsLayout L;
-    const int64_t C = chunk_pairs > 0 ? chunk_pairs : kCladeChunkPairs;
-    L.P = m * (m - 1) / 2;
-    L.nb = (L.P + ST_CLADE_TILE - 1) / ST_CLADE_TILE;
-    if (L.P == 0) return L;
-    if (L.P <= C / 2) {
-        L.S = L.P;
-        L.max_rows = std::max<int64_t>(1, std::min({n_rows, C / L.P, kRowsChunkBlocks / L.nb}));
-        L.chunk = L.max_rows * L.P;
-        L.max_blocks = L.max_rows * L.nb;
-    } else {
-        L.S = L.nb * ST_CLADE_TILE;
-        L.chunk = C;
-        L.max_rows = std::min(n_rows, (C - 1) / L.S + 2);
-        L.max_blocks = std::min(C / ST_CLADE_TILE, n_rows * L.nb);
-    }
-    return L;
-}
-
-// The reducer of st_compare_rows_host: k_row_blocks per chunk into one of two device piece buffers, each read back into
-// its pinned host twin; the host folds a chunk's pieces into their rows (block order, clade_merge) while the device works
-// on the next chunk.  Pieces of at most two chunks exist at any time.
-struct RowsReduce {
-    const RowsLayout &L;
-    st_pair_moments *out;
-    CladePiece *d_pieces[2] = {nullptr, nullptr}, *h_pieces[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    int64_t first[2] = {0, 0}, count[2] = {0, 0};      // buffer i holds blocks [first, first + count); 0: nothing pending
-    int next = 0;
-
-    RowsReduce(const RowsLayout &l, st_pair_moments *o) : L(l), out(o) {}
-    ~RowsReduce()
-    {
-        for (int i = 0; i < 2; i++) {
-            if (h_pieces[i]) (void)hipHostFree(h_pieces[i]);
-            if (ev[i]) (void)hipEventDestroy(ev[i]);
-        }
-    }
-    size_t piece_bytes() const { return ((size_t)L.max_blocks * sizeof(CladePiece) + 255) & ~(size_t)255; }
-    size_t bytes(int64_t) { return 2 * piece_bytes(); }
-    hipError_t start(char *d, int64_t, hipStream_t)
-    {
-        hipError_t e = hipSuccess;
-        for (int i = 0; i < 2 && e == hipSuccess; i++) {
-            d_pieces[i] = reinterpret_cast<CladePiece *>(d + i * piece_bytes());
-            e = hipHostMalloc(reinterpret_cast<void **>(&h_pieces[i]), (size_t)L.max_blocks * sizeof(CladePiece), hipHostMallocDefault);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
-        }
-        return e;
-    }
-    int64_t block_of(int64_t g) const      // the block of global pair g (padding: its row's last block)
-    {
-        const int64_t r = g / L.S;
-        return r * L.nb + ((g - r * L.S) >> kCladeTileShift);
-    }
-    int64_t block_lo(int64_t t) const { return t / L.nb * L.S + t % L.nb * ST_CLADE_TILE; }
-    int64_t block_len(int64_t t) const { return std::min<int64_t>((t % L.nb + 1) * ST_CLADE_TILE, L.P) - t % L.nb * ST_CLADE_TILE; }
-    hipError_t drain(int i)
-    {
-        if (count[i] == 0) return hipSuccess;
-        const hipError_t e = hipEventSynchronize(ev[i]);
-        if (e != hipSuccess) return e;
-        for (int64_t j = 0; j < count[i]; j++) {
-            const int64_t t = first[i] + j;
-            const CladePiece &c = h_pieces[i][j];
-            clade_merge(out[t / L.nb], st_pair_moments{block_len(t), (double)c.cx, (double)c.cy, c.sx, c.sy, c.sxx, c.syy, c.sxy,
-                                                       (double)c.min_x, (double)c.max_x, (double)c.min_y, (double)c.max_y});
-        }
-        count[i] = 0;
-        return hipSuccess;
-    }
-    hipError_t chunk(const float *d_x, const float *d_y, int64_t off, int64_t c, hipStream_t s)
-    {
-        const int i = next;
-        next ^= 1;
-        hipError_t e = drain(i);      // (the pieces of two chunks ago)
-        if (e != hipSuccess) return e;
-        const int64_t t0 = block_of(off), n = block_of(off + c - 1) + 1 - t0, tl = t0 + n - 1;
-        if (n > L.max_blocks || block_lo(t0) != off || block_lo(tl) + block_len(tl) > off + c) return hipErrorInvalidValue;
-        const int64_t per = L.P <= kCladeLanePiece ? kCladeThreads : kCladeThreads / 64;      // blocks per workgroup
-        hipLaunchKernelGGL(k_row_blocks, dim3((unsigned)((n + per - 1) / per)), dim3(kCladeThreads), 0, s, d_x, d_y, (long long)off,
-                           (long long)L.S, (long long)L.P, (long long)L.nb, (long long)t0, (long long)n, d_pieces[i]);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(h_pieces[i], d_pieces[i], (size_t)n * sizeof(CladePiece), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipEventRecord(ev[i], s);
-        if (e == hipSuccess) {
-            first[i] = t0;
-            count[i] = n;
-        }
-        return e;
-    }
-    hipError_t finish(hipStream_t) { return hipSuccess; }
-    int done()
-    {
-        for (int k = 0; k < 2; k++, next ^= 1) {      // the older buffer first
-            const hipError_t e = drain(next);
-            if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("rows read-back: ") + hipGetErrorString(e));
-        }
-        return ST_OK;
-    }
-};
 
 extern "C" {
 
@@ -1448,14 +954,14 @@ int st_compare_triangle_host(st_tree *tx, st_tree *ty, const int64_t *ids_x, con
                              int64_t k_count, const double *edges_x, int32_t bins_x, const double *edges_y, int32_t bins_y,
                              st_pair_moments *out, int64_t *out_hist, int64_t *bad_id)
 try {
-    int rc = compare_hist_args(edges_x, bins_x, edges_y, bins_y, out_hist);
-    if (rc != ST_OK) return rc;
+    std::string err;
+    int rc = compare_hist_args(edges_x, bins_x, edges_y, bins_y, out_hist, kCmpMaxCells, err);
+    if (rc != ST_OK) return fail(rc, err);
     if (!out) return fail(ST_ERR_ARG, "out is NULL");
     rc = compare_trees_args(tx, ty);
     if (rc != ST_OK) return rc;
-    if (m < 0 || k_begin < 0 || k_count < 0) return fail(ST_ERR_ARG, "negative size");
-    if (m > 3000000000LL) return fail(ST_ERR_ARG, "m too large");
-    if (k_begin + k_count > m * (m - 1) / 2) return fail(ST_ERR_ARG, "pair range exceeds m(m-1)/2");
+    rc = triangle_range_args(m, k_begin, k_count);
+    if (rc != ST_OK) return rc;
     if (m > 0 && (!ids_x || !ids_y)) return fail(ST_ERR_ARG, "ids_x or ids_y is NULL");
     if (k_count == 0) {
         compare_empty(out, out_hist, bins_x, bins_y);
@@ -1484,8 +990,9 @@ int st_compare_pairs_host(st_tree *tx, st_tree *ty, const int64_t *pairs_x, cons
                           int32_t bins_x, const double *edges_y, int32_t bins_y, st_pair_moments *out, int64_t *out_hist,
                           int64_t *bad_id)
 try {
-    int rc = compare_hist_args(edges_x, bins_x, edges_y, bins_y, out_hist);
-    if (rc != ST_OK) return rc;
+    std::string err;
+    int rc = compare_hist_args(edges_x, bins_x, edges_y, bins_y, out_hist, kCmpMaxCells, err);
+    if (rc != ST_OK) return fail(rc, err);
     if (!out) return fail(ST_ERR_ARG, "out is NULL");
     rc = compare_trees_args(tx, ty);
     if (rc != ST_OK) return rc;
@@ -1516,8 +1023,10 @@ int st_clade_plan(const int32_t *parent, int64_t n_nodes, const int64_t *link_le
                   int64_t seg_capacity, int64_t *out_n_segs, int64_t *out_total_pairs, int64_t *bad_id)
 try {
     CladePlan P;
-    int rc = clade_plan(parent, n_nodes, link_leaf, n_links, max_links, P, bad_id);
-    if (rc != ST_OK) return rc;
+    std::string err;
+    const int rc = clade_plan(parent, n_nodes, link_leaf, n_links, max_links, P, err);
+    if (rc == ST_ERR_BOUNDS) return compare_check_ids(link_leaf, n_links, n_nodes, bad_id);      // (a second scan, to word it)
+    if (rc != ST_OK) return fail(rc, err);
     if (out_segs && seg_capacity < (int64_t)P.segs.size())
         return fail(ST_ERR_ARG, "seg_capacity " + std::to_string(seg_capacity) + " < " + std::to_string(P.segs.size()) + " segments");
     if (out_perm) std::copy(P.perm.begin(), P.perm.end(), out_perm);
@@ -1541,44 +1050,24 @@ try {
         return fail(ST_ERR_ARG, "parent array of " + std::to_string(n_nodes) + " nodes: tree_y has " + std::to_string(ty->n_nodes));
     if (n_links < 0) return fail(ST_ERR_ARG, "n_links < 0");
     if (n_links > 0 && (!ids_x || !ids_y)) return fail(ST_ERR_ARG, "ids_x or ids_y is NULL");
-    if (chunk_pairs < 0 || chunk_pairs % ST_CLADE_TILE != 0)
-        return fail(ST_ERR_ARG, "chunk_pairs must be 0 or a positive multiple of " + std::to_string(ST_CLADE_TILE));
+    rc = chunk_pairs_arg(chunk_pairs);
+    if (rc != ST_OK) return rc;
     rc = compare_check_ids(ids_x, n_links, tx->n_nodes, bad_id);
     if (rc == ST_OK) rc = compare_check_ids(ids_y, n_links, ty->n_nodes, bad_id);
     if (rc != ST_OK) return rc;
     CladePlan P;
-    rc = clade_plan(parent, n_nodes, ids_y, n_links, max_links, P, bad_id);
-    if (rc != ST_OK) return rc;
+    std::string err;
+    rc = clade_plan(parent, n_nodes, ids_y, n_links, max_links, P, err);      // (not ST_ERR_BOUNDS: ids_y were checked above)
+    if (rc != ST_OK) return fail(rc, err);
     if (out_count) std::copy(P.count.begin(), P.count.end(), out_count);
-    // tiles and pieces: tile[t].seg = the segment of pair t * TILE, tile[t].piece = pieces before tile t; a sentinel
-    // segment (first = total) and a sentinel tile close the tables
-    const int64_t total = P.total, n_segs = (int64_t)P.segs.size();
-    const int64_t n_tiles = (total + ST_CLADE_TILE - 1) / ST_CLADE_TILE;
-    std::vector<CladeSeg> segs(n_segs + 1);
-    std::vector<CladeTile> tiles(n_tiles + 1);
-    std::vector<int64_t> seg_piece(n_segs + 1, 0);
-    int64_t n_pieces = 0;
-    for (int64_t s = 0; s < n_segs; s++) {
-        const st_clade_segment &g = P.segs[s];
-        segs[s] = CladeSeg{(long long)g.first_pair, g.row_begin, g.row_end, g.kind == ST_CLADE_TRI ? -1 : g.col_begin, g.col_end};
-        const int64_t tf = g.first_pair >> kCladeTileShift, tl = (g.first_pair + g.n_pairs - 1) >> kCladeTileShift;
-        seg_piece[s] = n_pieces;
-        for (int64_t t = (g.first_pair + ST_CLADE_TILE - 1) >> kCladeTileShift; t <= tl; t++)      // tiles that start in s
-            tiles[t] = CladeTile{(int)s, (int)(n_pieces + (t - tf))};
-        n_pieces += tl - tf + 1;
-    }
-    seg_piece[n_segs] = n_pieces;
-    segs[n_segs] = CladeSeg{(long long)total, 0, 0, 0, 0};
-    if (n_pieces > INT32_MAX) return fail(ST_ERR_ARG, "more than 2^31 - 1 pieces");
-    tiles[n_tiles] = CladeTile{(int)n_segs, (int)n_pieces};
-    CladeReduce red{P, tiles, seg_piece, nullptr, nullptr, out, max_links};
-    red.n_pieces = n_pieces;
-    if (total == 0) return red.done();      // (nothing to launch)
+    CladeTables T;
+    if (!clade_tables(P, T)) return fail(ST_ERR_ARG, "more than 2^31 - 1 pieces");
+    CladeReduce red{P, T, out, max_links};
+    if (P.total == 0) return red.done();      // (nothing to launch)
     // device: permuted ids of X and Y and ranks (int32) | segments | tiles
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t L = (size_t)n_links;
-    const size_t o_y = up(L * 4), o_rank = o_y + up(L * 4), o_seg = o_rank + up(L * 4);
-    const size_t o_tile = o_seg + up(segs.size() * sizeof(CladeSeg)), extra = o_tile + up(tiles.size() * sizeof(CladeTile));
+    const size_t o_y = align256(L * 4), o_rank = o_y + align256(L * 4), o_seg = o_rank + align256(L * 4);
+    const size_t o_tile = o_seg + align256(T.segs.size() * sizeof(CladeSeg)), extra = o_tile + align256(T.tiles.size() * sizeof(CladeTile));
     std::vector<int32_t> sx(L), sy(L), rk(L);
     for (size_t p = 0; p < L; p++) {
         const int64_t j = P.perm[p];
@@ -1592,8 +1081,8 @@ try {
         hipError_t e = hipMemcpyAsync(d, sx.data(), L * 4, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(d + o_y, sy.data(), L * 4, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(d + o_rank, rk.data(), L * 4, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d + o_seg, segs.data(), segs.size() * sizeof(CladeSeg), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d + o_tile, tiles.data(), tiles.size() * sizeof(CladeTile), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d + o_seg, T.segs.data(), T.segs.size() * sizeof(CladeSeg), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d + o_tile, T.tiles.data(), T.tiles.size() * sizeof(CladeTile), hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);      // (the host vectors are pageable and go out of scope with this call)
         return e;
     };
@@ -1604,24 +1093,23 @@ try {
                                reinterpret_cast<const CladeSeg *>(d + o_seg), reinterpret_cast<const CladeTile *>(d + o_tile), (long long)off};
         };
     };
-    return compare_run(tx, ty, total, chunk_pairs > 0 ? chunk_pairs : kCladeChunkPairs, extra, setup, prep, src(0), src(o_y), red, bad_id);
+    return compare_run(tx, ty, P.total, chunk_pairs > 0 ? chunk_pairs : kCladeChunkPairs, extra, setup, prep, src(0), src(o_y), red, bad_id);
 } ST_CATCH_ALL
 
 int st_compare_rows_host(st_tree *tx, st_tree *ty, const int64_t *ids_x, const int64_t *ids_y, int64_t n_rows, int64_t m,
                          int64_t chunk_pairs, st_pair_moments *out, int64_t *bad_id)
 try {
     if (n_rows < 0 || m < 0) return fail(ST_ERR_ARG, "n_rows < 0 or m < 0");
-    if (chunk_pairs < 0 || chunk_pairs % ST_CLADE_TILE != 0)
-        return fail(ST_ERR_ARG, "chunk_pairs must be 0 or a positive multiple of " + std::to_string(ST_CLADE_TILE));
+    int rc = chunk_pairs_arg(chunk_pairs);
+    if (rc != ST_OK) return rc;
     if (m > 3000000000LL) return fail(ST_ERR_ARG, "m too large");
     if (n_rows > 0 && m > 0 && (!ids_x || !ids_y)) return fail(ST_ERR_ARG, "ids_x or ids_y is NULL");
     if (n_rows > 0 && !out) return fail(ST_ERR_ARG, "out is NULL");
-    int rc = compare_trees_args(tx, ty);
+    rc = compare_trees_args(tx, ty);
     if (rc != ST_OK) return rc;
     const RowsLayout L = rows_layout(n_rows, m, chunk_pairs);
     if (L.S > 0 && n_rows > ((int64_t)1 << 50) / L.S) return fail(ST_ERR_ARG, "more than 2^50 pairs in one call");
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    for (int64_t r = 0; r < n_rows; r++) out[r] = st_pair_moments{0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, nan, nan, nan, nan};
+    std::fill_n(out, n_rows, moments_empty());
     if (n_rows == 0 || L.P == 0) return ST_OK;      // (nothing to launch)
     const int64_t n_ids = n_rows * m;
     rc = compare_check_ids(ids_x, n_ids, tx->n_nodes, bad_id);
@@ -1629,7 +1117,7 @@ try {
     if (rc != ST_OK) return rc;
     const std::vector<int32_t> hx(ids_x, ids_x + n_ids), hy(ids_y, ids_y + n_ids);      // (checked: below n_nodes)
     // device: the int32 ids of up to max_rows rows from row `up_lo` on, X then Y; uploaded again when a chunk needs others
-    const size_t row_bytes = (size_t)m * 4, half = ((size_t)L.max_rows * row_bytes + 255) & ~(size_t)255;
+    const size_t row_bytes = (size_t)m * 4, half = align256((size_t)L.max_rows * row_bytes);
     int64_t up_lo = -1, up_hi = -1;
     auto setup = [](char *, hipStream_t) { return hipSuccess; };
     auto prep = [&](char *d, hipStream_t s, int64_t off, int64_t c) {

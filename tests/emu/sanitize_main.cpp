@@ -1,16 +1,20 @@
 // sanitize_main.cpp -- TEST INFRASTRUCTURE ONLY.
 // Address/UB-sanitizer run of the product's host-side C++ (table construction, per-pair
-// functions compiled for the host, native Newick ingest) on generated trees.  Built and run
+// functions compiled for the host, native Newick ingest, the compare paths' planning and folding) on generated trees.  Built and run
 // by tests/test_sanitizers.py with g++ -fsanitize=address,undefined; exits non-zero on any
 // finding or on a mismatch between the walk and canopy families.
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <random>
 #include <string>
 #include <vector>
 
 #include "../../include/suchtree_hip.h"
+#include "../../suchtree_amd/csrc/compare_plan.h"
 #include "../../suchtree_amd/csrc/host_copy.h"
 #include "../../suchtree_amd/csrc/pair_math.h"
 #include "../../suchtree_amd/csrc/tree_prep.h"
@@ -283,6 +287,128 @@ static int check_host_copy(std::mt19937_64 &rng)
     return 0;
 }
 
+// ---- compare_plan.cpp: the clade plan, its tables and the fold; the rows layout; the merge -------------------------
+// Any rooted tree with 0-3 links per leaf in shuffled order, under no cap, 0, a small and a large one.  Exact
+// expectations throughout: the segments tile [0, total), the tile table points at the segment and the piece of every
+// tile's first pair, and the fold of zero-sum pieces leaves node v with n = C(count[v], 2) pairs, or -1 over the cap.
+static int check_clades(std::mt19937_64 &rng, const std::vector<int32_t> &parent)
+{
+    const int64_t n = (int64_t)parent.size();
+    std::vector<char> inner((size_t)n, 0);
+    for (const int32_t p : parent)
+        if (p >= 0) inner[(size_t)p] = 1;
+    std::vector<int64_t> links;
+    for (int64_t v = 0; v < n; v++)
+        if (!inner[(size_t)v])
+            for (int k = (int)(rng() % 4); k > 0; k--) links.push_back(v);
+    std::shuffle(links.begin(), links.end(), rng);
+    for (const int64_t cap : {(int64_t)-1, (int64_t)0, (int64_t)5, (int64_t)200}) {
+        CladePlan P;
+        std::string err;
+        if (clade_plan(parent.data(), n, links.data(), (int64_t)links.size(), cap, P, err) != ST_OK) return 70;
+        int64_t run = 0;
+        for (const st_clade_segment &g : P.segs) {
+            if (g.first_pair != run || g.n_pairs < 1) return 71;
+            run += g.n_pairs;
+        }
+        if (run != P.total) return 72;
+        CladeTables T;
+        if (!clade_tables(P, T)) return 73;
+        const int64_t n_segs = (int64_t)P.segs.size(), n_tiles = (P.total + ST_CLADE_TILE - 1) / ST_CLADE_TILE;
+        if ((int64_t)T.segs.size() != n_segs + 1 || (int64_t)T.tiles.size() != n_tiles + 1) return 74;
+        if (T.segs[(size_t)n_segs].first != P.total || T.tiles[(size_t)n_tiles].seg != n_segs || T.tiles[(size_t)n_tiles].piece != T.n_pieces) return 75;
+        for (int64_t t = 0; t < n_tiles; t++) {
+            const int64_t k = t * ST_CLADE_TILE, s = T.tiles[(size_t)t].seg;
+            if (s < 0 || s >= n_segs || T.segs[(size_t)s].first > k || T.segs[(size_t)s + 1].first <= k) return 76;
+            if (T.tiles[(size_t)t].piece != T.seg_piece[(size_t)s] + (t - T.segs[(size_t)s].first / ST_CLADE_TILE)) return 77;
+        }
+        const std::vector<CladePiece> pieces((size_t)T.n_pieces, CladePiece{});
+        std::vector<st_pair_moments> out((size_t)n);
+        clade_fold(P, T, pieces.data(), cap, out.data());
+        for (int64_t v = 0; v < n; v++) {
+            const int64_t c = P.count[(size_t)v];
+            if (out[(size_t)v].n != (cap >= 0 && c > cap ? -1 : c * (c - 1) / 2)) return 78;
+        }
+    }
+    return 0;
+}
+
+// The conditions RowsReduce::chunk and the id upload of st_compare_rows_host (host_compare.h, suchtree_hip.hip) reject
+// with hipErrorInvalidValue, walked chunk by chunk as compare_run does; every row's blocks hold its P pairs.
+static int check_rows_layout()
+{
+    for (const int64_t m : {2, 3, 11, 12, 13, 128, 129, 130, 5000})
+        for (const int64_t n_rows : {1, 2, 7, 1000, 300000})
+            for (const int64_t chunk_pairs : {0, ST_CLADE_TILE, 2 * ST_CLADE_TILE, 1 << 20}) {
+                const RowsLayout L = rows_layout(n_rows, m, chunk_pairs);
+                if (L.P != m * (m - 1) / 2 || L.S < L.P || L.chunk < 1) return 80;
+                const int64_t total = n_rows * L.S;
+                if (total > (int64_t)1 << 34) continue;
+                for (int64_t off = 0; off < total; off += L.chunk) {
+                    const int64_t c = std::min(L.chunk, total - off);
+                    const int64_t t0 = L.block_of(off), nblk = L.block_of(off + c - 1) + 1 - t0, tl = t0 + nblk - 1;
+                    if (nblk > L.max_blocks || L.block_lo(t0) != off || L.block_lo(tl) + L.block_len(tl) > off + c) return 81;
+                    if ((off + c - 1) / L.S + 1 - off / L.S > L.max_rows) return 82;
+                }
+                for (int64_t r = 0; r < n_rows; r++) {
+                    int64_t pairs = 0;
+                    for (int64_t b = 0; b < L.nb; b++) pairs += L.block_len(r * L.nb + b);
+                    if (pairs != L.P) return 83;
+                }
+            }
+    return 0;
+}
+
+// a piece as the kernels sum it (kernels_clades.h: CladeAcc): about its own first pair, 0 where that is not finite
+static CladePiece sum_piece(const float *x, const float *y, int64_t k)
+{
+    const float inf = std::numeric_limits<float>::infinity();
+    CladePiece c{0.0, 0.0, 0.0, 0.0, 0.0, std::isfinite(x[0]) ? x[0] : 0.0f, std::isfinite(y[0]) ? y[0] : 0.0f, inf, -inf, inf, -inf};
+    for (int64_t i = 0; i < k; i++) {
+        const double dx = (double)x[i] - (double)c.cx, dy = (double)y[i] - (double)c.cy;
+        c.sx += dx;
+        c.sy += dy;
+        c.sxx += dx * dx;
+        c.syy += dy * dy;
+        c.sxy += dx * dy;
+        c.min_x = std::fmin(c.min_x, x[i]);
+        c.max_x = std::fmax(c.max_x, x[i]);
+        c.min_y = std::fmin(c.min_y, y[i]);
+        c.max_y = std::fmax(c.max_y, y[i]);
+    }
+    return c;
+}
+
+// Small-integer data, so that every sum is exact in float64: pieces folded in order are the direct sums about the first
+// piece's shift, bit for bit.  Then one infinite value: its piece's squares stay +inf when moved to another shift.
+static int check_merge(std::mt19937_64 &rng)
+{
+    for (int round = 0; round < 200; round++) {
+        const int64_t total = 1 + (int64_t)(rng() % 3000);
+        std::vector<float> x((size_t)total), y((size_t)total);
+        for (int64_t i = 0; i < total; i++) {
+            x[(size_t)i] = (float)(rng() % 1000);
+            y[(size_t)i] = (float)(rng() % 1000) - 500.0f;
+        }
+        st_pair_moments acc = moments_empty();
+        for (int64_t lo = 0; lo < total;) {
+            const int64_t k = std::min<int64_t>(total - lo, 1 + (int64_t)(rng() % 400));
+            clade_merge(acc, piece_moments(sum_piece(x.data() + lo, y.data() + lo, k), k));
+            lo += k;
+        }
+        const CladePiece d = sum_piece(x.data(), y.data(), total);
+        if (acc.n != total || acc.shift_x != (double)x[0] || acc.shift_y != (double)y[0]) return 90;
+        if (acc.sx != d.sx || acc.sy != d.sy || acc.sxx != d.sxx || acc.syy != d.syy || acc.sxy != d.sxy) return 91;
+        if (acc.min_x != d.min_x || acc.max_x != d.max_x || acc.min_y != d.min_y || acc.max_y != d.max_y) return 92;
+    }
+    const float inf = std::numeric_limits<float>::infinity();
+    const float xa[2] = {5.0f, 6.0f}, xb[2] = {2.0f, inf}, xc[2] = {9.0f, 1.0f}, y2[2] = {1.0f, 2.0f};
+    st_pair_moments acc = moments_empty();
+    for (const float *px : {xa, xb, xc}) clade_merge(acc, piece_moments(sum_piece(px, y2, 2), 2));      // (b: dx * sx = -inf)
+    if (acc.n != 6 || !(acc.sxx == (double)inf) || acc.syy != 3.0 || acc.max_x != (double)inf || acc.min_x != 1.0) return 93;
+    return 0;
+}
+
 int main()
 {
     std::mt19937_64 rng(12345);
@@ -296,6 +422,21 @@ int main()
                 if (rc) { std::printf("FAILED rc=%d\n", rc); return rc; }
             }
     if (check_newick(rng)) return 9;
+    std::vector<int32_t> parent;
+    std::vector<float> dist;
+    for (int n : sizes)
+        for (double s : skews) {
+            random_tree(rng, n, s, parent, dist);
+            if (const int rc = check_clades(rng, parent)) { std::printf("FAILED clades leaves=%d skew=%g rc=%d\n", n, s, rc); return rc; }
+        }
+    random_tree(rng, 1000, 0.5, parent, dist);      // any rooted tree: one rectangle per child but the last
+    parent.push_back((int32_t)(std::find(parent.begin(), parent.end(), -1) - parent.begin()));      // a third child of the root
+    if (const int rc = check_clades(rng, parent)) { std::printf("FAILED clades three children rc=%d\n", rc); return rc; }
+    parent.assign(3001, 0);      // a star
+    parent[0] = -1;
+    if (const int rc = check_clades(rng, parent)) { std::printf("FAILED clades star rc=%d\n", rc); return rc; }
+    if (const int rc = check_rows_layout()) { std::printf("FAILED rows_layout rc=%d\n", rc); return rc; }
+    if (const int rc = check_merge(rng)) { std::printf("FAILED merge rc=%d\n", rc); return rc; }
     std::printf("sanitize ok\n");
     return 0;
 }

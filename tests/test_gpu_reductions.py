@@ -19,10 +19,10 @@ from suchtree_amd.linked import SuchLinkedTrees
 pytestmark = pytest.mark.gpu
 
 TILE = _capi.CLADE_TILE              # ST_CLADE_TILE
-CHUNK_TRIANGLE = 1 << 25             # suchtree_hip.hip: kCompareChunkTriangle
-CHUNK_PAIRS = 1 << 22                # suchtree_hip.hip: kCompareChunkPairs
-CHUNK_CLADES = 1 << 25               # suchtree_hip.hip: kCladeChunkPairs (also the rows' default chunk)
-ROWS_CHUNK_BLOCKS = 1 << 18          # suchtree_hip.hip: kRowsChunkBlocks
+CHUNK_TRIANGLE = 1 << 25             # host_compare.h: kCompareChunkTriangle
+CHUNK_PAIRS = 1 << 22                # host_compare.h: kCompareChunkPairs
+CHUNK_CLADES = 1 << 25               # compare_plan.h: kCladeChunkPairs (also the rows' default chunk)
+ROWS_CHUNK_BLOCKS = 1 << 18          # compare_plan.h: kRowsChunkBlocks
 SHIFT_PAIRS = 4096                   # kernels_compare.h: kCmpShiftPairs
 MAX_CELLS = 16384                    # kernels_compare.h: kCmpMaxCells
 LANE_PIECE = 64                      # kernels_clades.h: kCladeLanePiece
@@ -186,7 +186,7 @@ def test_explicit_pairs_across_chunk_boundaries(ml_nj):
 # ---- B. histogram layouts ----------------------------------------------------------------------------------------
 
 def _hist_layout(bins_x, bins_y):
-    """MomentsReduce::start (suchtree_hip.hip): uint32 counters ((cells + 1) & ~1) * 4 bytes, the edges beside them in LDS
+    """MomentsReduce::start (host_compare.h): uint32 counters ((cells + 1) & ~1) * 4 bytes, the edges beside them in LDS
     iff counters + edges <= 128 KiB (else k_pair_moments reads them from global memory), hipFuncSetAttribute iff the
     dynamic LDS exceeds 64 KiB - 1024.  Returns (edges_in_lds, attribute)."""
     cells = bins_x * bins_y
@@ -269,7 +269,7 @@ def test_histogram_through_compare_distances(ml_arrays, nj_arrays, sample3000):
 # ---- C. row blocks at their thresholds ---------------------------------------------------------------------------
 
 def _rows_layout(n_rows, m, chunk_pairs):
-    """suchtree_hip.hip: rows_layout -- (P, S, nb, chunk, dense)."""
+    """compare_plan.cpp: rows_layout -- (P, S, nb, chunk, dense)."""
     C = chunk_pairs if chunk_pairs > 0 else CHUNK_CLADES
     P = m * (m - 1) // 2
     nb = -(-P // TILE)
@@ -354,8 +354,8 @@ def test_many_tiny_rows_span_three_chunks(trees):
 # ---- D. clade pieces at their thresholds -------------------------------------------------------------------------
 
 def _pieces(segs):
-    """The pieces of a clade plan as st_compare_clades_host cuts them (suchtree_hip.hip, the tile loop before CladeReduce,
-    and CladeReduce::done): segment s's part of each tile it meets -- (tile, lo, hi, s)."""
+    """The pieces of a clade plan as st_compare_clades_host cuts them (compare_plan.cpp: clade_tables and
+    clade_fold): segment s's part of each tile it meets -- (tile, lo, hi, s)."""
     out = []
     for s, g in enumerate(segs):
         f, n = int(g["first_pair"]), int(g["n_pairs"])

@@ -15,7 +15,7 @@ def test_host_code_under_asan_ubsan(tmp_path):
     csrc = os.path.join(ROOT, "suchtree_amd", "csrc")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
            "-ffp-contract=off", "-o", exe, os.path.join(ROOT, "tests", "emu", "sanitize_main.cpp"),
-           os.path.join(csrc, "tree_prep.cpp"), os.path.join(csrc, "newick_parse.cpp")]
+           os.path.join(csrc, "tree_prep.cpp"), os.path.join(csrc, "newick_parse.cpp"), os.path.join(csrc, "compare_plan.cpp")]
     subprocess.check_call(cmd)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     out = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=600)
