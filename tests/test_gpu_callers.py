@@ -131,6 +131,12 @@ def test_grid_generator_pairwise_matrix_and_knn_on_a_real_tree(ml_arrays):
         dev.set_strategy(strategy)
         d2, _ = dev.grid_host(ids[:300], ids[:300], symmetric=True)
         assert_bits_equal(d2, D[:300, :300].reshape(-1), strategy)
+        # 90,000 elements are below ml.tree's canopy_min_pairs (131072, launch_policy.h:127): the walk kernel under either
+        # strategy.  810 x 810 = 656,100 elements are two host-path launches of 2^18 and one of 131,812
+        # (st_host_chunk_plan), none below it: canopy kernels under "canopy"
+        assert [m for _, _, m in _capi.host_chunk_map(810 * 810, 1)] == [262144, 262144, 131812]
+        d3, _ = dev.grid_host(ids[:810], ids[:810], symmetric=True)
+        assert_bits_equal(d3, D[:810, :810].reshape(-1), strategy + ", 810 x 810")
     dev.set_strategy("auto")
     with pytest.raises(ValueError):
         dev.grid_host(rows, cols, symmetric=True)

@@ -33,6 +33,30 @@ def test_triangle_rows():
     assert hi == 4_999_950_000 and hi - lo in (624_993_750, 624_993_749)
 
 
+def test_triangle_rows_against_isqrt_at_the_row_boundaries():
+    """triangle_row_of against math.isqrt on Python integers at k = T(r) - 2 ... T(r) + 1, T(r) = r (r - 1) / 2, for rows
+    near 2^12, 2^16, 10^5, 2^20, where 8 k + 1 passes 2^53, 1.5e8 and the ABI's cap m = 3e9; and what its two corrections
+    do there: the uncorrected float64 formula is one too large at T(r) - 1 for every row from about 9.5e7 on (the first
+    correction is load-bearing), and with numpy's correctly rounded sqrt never one too small at T(r) (the second one is a
+    guard against a sqrt that is an ulp low, under which EVERY T(r) would come out one row short)."""
+    import math
+    fired_first, fired_second = 0, 0
+    for top in (1 << 12, 1 << 16, 100_000, 1 << 20, 47_453_133, 94_906_266, 150_000_000, 1_000_000_000, 3_000_000_000):
+        r = np.arange(top - 3000, top, dtype=np.int64)
+        t = r * (r - 1) // 2
+        k = np.concatenate([t - 2, t - 1, t, t + 1, t + r // 2, t + r - 1])
+        want = np.array([(1 + math.isqrt(1 + 8 * int(x))) // 2 for x in k], dtype=np.int64)
+        assert np.array_equal(want[2 * len(r):3 * len(r)], r) and np.array_equal(want[len(r):2 * len(r)], r - 1)
+        assert np.array_equal(sharding.triangle_row_of(k), want), top
+        raw = np.floor((1.0 + np.sqrt(1.0 + 8.0 * k.astype(np.float64))) / 2.0).astype(np.int64)
+        assert np.all(np.abs(raw - want) <= 1)
+        fired_first += int((raw > want).sum())
+        fired_second += int((raw < want).sum())
+        if top >= 150_000_000:
+            assert np.all(raw[len(r):2 * len(r)] == r), top      # (every T(r) - 1 of these rows needs the first correction)
+    assert fired_first > 9000 and fired_second == 0
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
