@@ -39,7 +39,8 @@ extern "C" {
  * binding does) and use st_tree_info_get_sized, which writes at most the bytes the caller says it has.
  *   7: st_compare_triangle_host, st_compare_pairs_host and struct st_pair_moments added; later, without a bump (additive):
  *      st_clade_plan, st_compare_clades_host, struct st_clade_segment and the ST_CLADE_* constants; then, also additive,
- *      st_compare_rows_host.
+ *      st_compare_rows_host; then, also additive, struct st_rank_sums, st_compare_triangle_ranks_host,
+ *      st_compare_pairs_ranks_host and st_spearman_host.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -407,6 +408,41 @@ int st_compare_clades_host(st_tree *tree_x, st_tree *tree_y, const int32_t *pare
 int st_compare_rows_host(st_tree *tree_x, st_tree *tree_y, const int64_t *ids_x, const int64_t *ids_y,
                          int64_t n_rows, int64_t m, int64_t chunk_pairs,
                          st_pair_moments *out, int64_t *bad_id);
+
+/*
+ * Exact Spearman rank correlation of the same pairs.  rank_x is the midrank of x_k among the call's n float32 distances
+ * (scipy.stats.rankdata(x, "average"): equal values tie, -0.0 ties with +0.0), a_k = 2 rank_x(x_k) - (n + 1)
+ * = 2 (#values < x_k) + (#values == x_k) - n, an integer, and b_k likewise for y.  Then
+ *   Sxy = sum a_k b_k,   Sxx = sum a_k^2 = (n^3 - n - sum over x's tie groups of (t^3 - t)) / 3,   Syy likewise,
+ * and Spearman's rs = Sxy / (sqrt(Sxx) sqrt(Syy)): NaN when Sxx or Syy is 0, when n < 2 or when n_nan > 0 (scipy's
+ * "propagate").  The three sums are 128-bit two's-complement integers: they do not depend on reduction order, grid,
+ * chunk size or device, so two calls, or a call and st_spearman_host on the same values, agree exactly.
+ *
+ * No pair is kept.  Three passes recompute the distances chunk by chunk: the first is st_compare_*_host's own (out
+ * receives the same st_pair_moments, bit for bit, as that call without a histogram) and also marks which of the 4096
+ * top-12-bit buckets of the order-preserving key each tree's values fall in; the second counts every value in one
+ * uint32 counter per (occupied bucket, low 20 bits) and a scan in key order turns the counts into a_k in place; the
+ * third looks a_k and b_k up and sums their products.  Device memory: the chunk plus 4 MiB per occupied bucket and tree
+ * (ml.tree vs nj.tree, all pairs: 0.6 GB; at worst 2 x 4096 buckets, 32 GiB) -- it does not grow with the pair count.
+ * n is limited to 2^31 - 1 (|a| within int32, a b within int64): more is ST_ERR_ARG and launches nothing.
+ * chunk_pairs: pairs per device chunk of the second and third pass, 0 = the path's default, else a positive multiple
+ * of ST_CLADE_TILE (ST_ERR_ARG otherwise); the result does not depend on it.  Pairs, orientation, id checks and error
+ * codes are those of st_compare_triangle_host / st_compare_pairs_host.  No counterpart in the reference, whose docs
+ * rank a sample of the pairs on the host (scipy.stats.spearmanr).
+ */
+typedef struct st_rank_sums {
+    int64_t  n, n_nan;                 /* pairs ranked; pairs with a NaN on either side (then everything below is 0) */
+    int64_t  distinct_x, distinct_y;   /* distinct values after -0 -> +0 */
+    uint64_t sxy_lo; int64_t sxy_hi;   /* 128-bit two's complement */
+    uint64_t sxx_lo, sxx_hi, syy_lo, syy_hi;
+} st_rank_sums;
+int st_compare_triangle_ranks_host(st_tree *tree_x, st_tree *tree_y, const int64_t *ids_x, const int64_t *ids_y, int64_t m,
+                                   int64_t k_begin, int64_t k_count, int64_t chunk_pairs,
+                                   st_pair_moments *out, st_rank_sums *out_ranks, int64_t *bad_id);
+int st_compare_pairs_ranks_host(st_tree *tree_x, st_tree *tree_y, const int64_t *pairs_x, const int64_t *pairs_y, int64_t n,
+                                int64_t chunk_pairs, st_pair_moments *out, st_rank_sums *out_ranks, int64_t *bad_id);
+/* Host only, no GPU: the same keys, midranks and tie arithmetic over two plain arrays of n values. */
+int st_spearman_host(const float *x, const float *y, int64_t n, st_rank_sums *out);
 
 /*
  * Quartet topologies: for each row (a,b,c,d) of the int64 (n,4) view the row re-ordered so

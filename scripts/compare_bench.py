@@ -10,6 +10,17 @@
 
     python scripts/compare_bench.py [--reps 3] [--no-profile]
 
+With --spearman it measures the exact Spearman rank correlation of the same pairs instead
+(compare_distances(spearman=True): three passes over the pairs) and prints
+
+  spearman_r, rank sums, distinct_x / distinct_y    of the full population
+  moments_s                                         the moments-only call (one pass): the yardstick is three of it
+  spearman_s                                        the ranks call, wall
+  atomics_gadds_per_s                               scattered no-return uint32 atomic adds (libst_microbench.so) into
+                                                    4 MiB, 256 MiB and 1 GiB of counters: the rate that bounds the count pass
+  kernels                                           under rocprofv3: summed time of the distance kernels and of each
+                                                    rank kernel (occupancy, count, scan, dot) of one ranks call
+
 Reads the committed fixtures under tests/golden only.
 """
 import argparse
@@ -63,6 +74,77 @@ def run(reps):
             "hist64_s": best_h, "hist64_pairs_per_s": n / best_h, "reps": reps}
 
 
+def atomic_rates():
+    """G adds/s of scattered no-return uint32 atomic adds, by table size."""
+    import ctypes
+    from suchtree_amd import build
+    lib = ctypes.CDLL(build.build_microbench())
+    lib.stmb_scatter_atomic_u32.argtypes = [ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
+    out = {}
+    for mib in (4, 256, 1024):
+        rate = ctypes.c_double(0.0)
+        rc = lib.stmb_scatter_atomic_u32(0, mib << 20, 4096, 3, ctypes.byref(rate))
+        out["%d_MiB" % mib] = rate.value if rc == 0 else None
+    return out
+
+
+def run_spearman(reps):
+    from suchtree_amd.compare import rank_fields
+    dx, dy, ids_x, ids_y = load()
+    n = len(ids_x) * (len(ids_x) - 1) // 2
+    dx.compare_triangle_ranks_host(dy, ids_x[:3000], ids_y[:3000])      # warm-up (kernels loaded, pipes built)
+    best_m = best_s = ranks = None
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        dx.compare_triangle_host(dy, ids_x, ids_y)
+        t = time.perf_counter() - t0
+        best_m = t if best_m is None else min(best_m, t)
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        _, ranks = dx.compare_triangle_ranks_host(dy, ids_x, ids_y)
+        t = time.perf_counter() - t0
+        best_s = t if best_s is None else min(best_s, t)
+    f = rank_fields(ranks)
+    return {"pairs": n, "spearman_r": f["spearman_r"], "rank_sxy": str(f["rank_sxy"]), "rank_sxx": str(f["rank_sxx"]),
+            "rank_syy": str(f["rank_syy"]), "distinct_x": f["distinct_x"], "distinct_y": f["distinct_y"], "moments_s": best_m,
+            "three_moments_s": 3 * best_m, "spearman_s": best_s, "spearman_pairs_per_s": n / best_s, "reps": reps}
+
+
+def profile_spearman():
+    """One ranks call (and its small warm-up) under rocprofv3: kernel time by kind."""
+    rows = _trace(["--spearman", "--child"])
+    if isinstance(rows, dict):
+        return rows
+    kinds = {"distance_ns": 0, "moments_ns": 0, "occupancy_ns": 0, "count_ns": 0, "scan_ns": 0, "dot_ns": 0, "other_ns": 0}
+    for r in rows:
+        name, ns = r["Kernel_Name"], int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
+        kind = ("occupancy_ns" if "k_rank_occupancy" in name else "count_ns" if "k_rank_count" in name else
+                "scan_ns" if "k_rank_block_sums" in name or "k_rank_scan" in name else "dot_ns" if "k_rank_dot" in name else
+                "moments_ns" if "k_pair_" in name else "distance_ns" if "k_canopy" in name or "k_walk" in name else "other_ns")
+        kinds[kind] += ns
+    return kinds
+
+
+def _trace(child_args):
+    """The kernel-trace rows of this script run once more under rocprofv3 (a dict describing the failure otherwise)."""
+    exe = shutil.which("rocprofv3")
+    if exe is None:
+        return {"error": "rocprofv3 not found"}
+    out = tempfile.mkdtemp(prefix="compare_bench_")
+    try:
+        cmd = [exe, "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "cmp", "--", sys.executable,
+               os.path.abspath(__file__)] + child_args
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+        if p.returncode != 0:
+            return {"error": "rocprofv3 exit %d" % p.returncode, "stderr": p.stderr[-2000:]}
+        traces = glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True)
+        if not traces:
+            return {"error": "no kernel trace written"}
+        return list(csv.DictReader(open(traces[0])))
+    finally:
+        shutil.rmtree(out, ignore_errors=True)
+
+
 def profile():
     """Run this script once more (one rep) under rocprofv3 and sum the kernel time by kind."""
     exe = shutil.which("rocprofv3")
@@ -110,8 +192,20 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--spearman", action="store_true", help="measure the exact Spearman rank correlation instead")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.spearman:
+        if a.child:      # (under rocprofv3: the ranks call alone, after its small warm-up)
+            dx, dy, ids_x, ids_y = load()
+            dx.compare_triangle_ranks_host(dy, ids_x[:3000], ids_y[:3000])
+            dx.compare_triangle_ranks_host(dy, ids_x, ids_y)
+            return
+        res = run_spearman(a.reps)
+        res["atomics_gadds_per_s"] = atomic_rates()
+        res["kernels"] = None if a.no_profile else profile_spearman()
+        print(json.dumps(res))
+        return
     if a.child:       # (under rocprofv3: one rep of each phase, the warm-up's small triangle included)
         run(1)
         return

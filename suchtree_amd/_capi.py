@@ -43,7 +43,7 @@ SYMBOLS = (
     "st_quartets_host", "st_graph_matrices_host", "st_newick_open", "st_newick_fill", "st_newick_close",
     "st_host_depths", "st_link_sample_pairs", "st_bucket_moments", "st_device_malloc", "st_device_free", "st_memcpy_h2d", "st_memcpy_d2h",
     "st_device_synchronize", "st_compare_triangle_host", "st_compare_pairs_host", "st_clade_plan", "st_compare_clades_host",
-    "st_compare_rows_host",
+    "st_compare_rows_host", "st_compare_triangle_ranks_host", "st_compare_pairs_ranks_host", "st_spearman_host",
 )
 
 CLADE_RECT, CLADE_TRI = 0, 1     # include/suchtree_hip.h: ST_CLADE_RECT / ST_CLADE_TRI
@@ -67,6 +67,36 @@ class PairMoments(ctypes.Structure):
 PAIR_MOMENTS = np.dtype([("n", np.int64)] + [(k, np.float64) for k in
                                             "shift_x shift_y sx sy sxx syy sxy min_x max_x min_y max_y".split()])
 assert PAIR_MOMENTS.itemsize == ctypes.sizeof(PairMoments)
+
+
+class RankSums(ctypes.Structure):
+    """st_rank_sums (include/suchtree_hip.h): the exact integer sums of Spearman's rank correlation."""
+    _fields_ = [("n", ctypes.c_int64), ("n_nan", ctypes.c_int64), ("distinct_x", ctypes.c_int64), ("distinct_y", ctypes.c_int64),
+                ("sxy_lo", ctypes.c_uint64), ("sxy_hi", ctypes.c_int64), ("sxx_lo", ctypes.c_uint64), ("sxx_hi", ctypes.c_uint64),
+                ("syy_lo", ctypes.c_uint64), ("syy_hi", ctypes.c_uint64)]
+
+    @property
+    def sxy(self):
+        return (int(self.sxy_hi) << 64) + int(self.sxy_lo)
+
+    @property
+    def sxx(self):
+        return (int(self.sxx_hi) << 64) + int(self.sxx_lo)
+
+    @property
+    def syy(self):
+        return (int(self.syy_hi) << 64) + int(self.syy_lo)
+
+
+def spearman_host(x, y):
+    """st_spearman_host: the exact rank sums (``RankSums``) of two float32 arrays of equal length, on the host."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    if x.ndim != 1 or x.shape != y.shape:
+        raise ValueError("x and y must be 1-D arrays of equal length")
+    out = RankSums()
+    check(load().st_spearman_host(_ptr(x) if len(x) else None, _ptr(y) if len(y) else None, len(x), ctypes.byref(out)))
+    return out
 
 
 class TreeInfo(ctypes.Structure):
@@ -225,6 +255,11 @@ def load():
                                                ctypes.POINTER(PairMoments), vp, ctypes.POINTER(i64)]
         L.st_compare_pairs_host.argtypes = [vp, vp, vp, vp, i64, vp, ctypes.c_int32, vp, ctypes.c_int32,
                                             ctypes.POINTER(PairMoments), vp, ctypes.POINTER(i64)]
+        L.st_compare_triangle_ranks_host.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, ctypes.POINTER(PairMoments),
+                                                     ctypes.POINTER(RankSums), ctypes.POINTER(i64)]
+        L.st_compare_pairs_ranks_host.argtypes = [vp, vp, vp, vp, i64, i64, ctypes.POINTER(PairMoments), ctypes.POINTER(RankSums),
+                                                  ctypes.POINTER(i64)]
+        L.st_spearman_host.argtypes = [vp, vp, i64, ctypes.POINTER(RankSums)]
         L.st_clade_plan.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64),
                                     ctypes.POINTER(i64)]
         L.st_compare_clades_host.argtypes = [vp, vp, vp, i64, vp, vp, i64, i64, i64, vp, vp, ctypes.POINTER(i64)]
@@ -735,6 +770,36 @@ class DeviceTree:
                                              _ptr(ex), bx, _ptr(ey), by, ctypes.byref(out), _ptr(hist), ctypes.byref(bad))
         self._compare_check(other, rc, bad)
         return out, hist
+
+    def compare_triangle_ranks_host(self, other, ids_x, ids_y, k_begin=0, k_count=None, chunk_pairs=0):
+        """compare_triangle_host without a histogram plus the exact rank sums of the same pairs
+        (st_compare_triangle_ranks_host).  Returns (moments, ``RankSums``)."""
+        ids_x = np.ascontiguousarray(ids_x, dtype=np.int64)
+        ids_y = np.ascontiguousarray(ids_y, dtype=np.int64)
+        if ids_x.ndim != 1 or ids_x.shape != ids_y.shape:
+            raise ValueError("ids_x and ids_y must be 1-D arrays of equal length")
+        m = int(ids_x.shape[0])
+        if k_count is None:
+            k_count = m * (m - 1) // 2 - int(k_begin)
+        out, ranks, bad = PairMoments(), RankSums(), ctypes.c_int64(0)
+        rc = self._lib.st_compare_triangle_ranks_host(self.handle, other.handle, _ptr(ids_x) if m else None, _ptr(ids_y) if m else None,
+                                                      m, int(k_begin), int(k_count), int(chunk_pairs), ctypes.byref(out),
+                                                      ctypes.byref(ranks), ctypes.byref(bad))
+        self._compare_check(other, rc, bad)
+        return out, ranks
+
+    def compare_pairs_ranks_host(self, other, pairs_x, pairs_y, chunk_pairs=0):
+        """The same over explicit pairs (st_compare_pairs_ranks_host).  Returns (moments, ``RankSums``)."""
+        pairs_x = np.ascontiguousarray(pairs_x, dtype=np.int64)
+        pairs_y = np.ascontiguousarray(pairs_y, dtype=np.int64)
+        if pairs_x.ndim != 2 or pairs_x.shape[1:] != (2,) or pairs_x.shape != pairs_y.shape:
+            raise ValueError("pairs_x and pairs_y must be (n, 2) arrays of equal shape")
+        n = int(pairs_x.shape[0])
+        out, ranks, bad = PairMoments(), RankSums(), ctypes.c_int64(0)
+        rc = self._lib.st_compare_pairs_ranks_host(self.handle, other.handle, _ptr(pairs_x) if n else None, _ptr(pairs_y) if n else None,
+                                                   n, int(chunk_pairs), ctypes.byref(out), ctypes.byref(ranks), ctypes.byref(bad))
+        self._compare_check(other, rc, bad)
+        return out, ranks
 
     def compare_clades_host(self, other, parent, ids_x, ids_y, max_links=None, chunk_pairs=0):
         """st_compare_clades_host: one PairMoments-shaped record per node of ``other`` (the clade tree, whose int32

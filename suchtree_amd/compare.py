@@ -24,6 +24,13 @@ class DistanceComparison:
     ``xedges`` / ``yedges`` its edges.  ``n_leaves`` is the length of the id list whose pairs were compared (None for
     explicit pairs).  The raw sums -- ``sx`` = sum of (x - shift_x), ``sxx`` = sum of (x - shift_x)^2, ``sxy`` = sum of
     (x - shift_x)(y - shift_y), ... -- are kept so that results over disjoint pair ranges can be combined (:meth:`merge`).
+
+    With ``spearman=True`` the call also ranks every pair: ``spearman_r`` is Spearman's rs of all n pairs (midranks, as
+    ``scipy.stats.spearmanr``; NaN for a constant column, n < 2 or a NaN distance), computed from the exact integers
+    ``rank_sxy`` = sum a b, ``rank_sxx`` = sum a^2, ``rank_syy`` = sum b^2 with a = 2 rank(x) - (n + 1), b likewise for y
+    (Python ints: they do not depend on reduction order, chunking or device); ``distinct_x`` / ``distinct_y`` count the
+    distinct distances.  All six are None when ranks were not asked for, and after :meth:`merge`: ranks of disjoint
+    pair ranges do not combine.
     """
 
     n_pairs: int
@@ -48,11 +55,18 @@ class DistanceComparison:
     sxx: float = 0.0
     syy: float = 0.0
     sxy: float = 0.0
+    spearman_r: Optional[float] = None
+    rank_sxy: Optional[int] = None
+    rank_sxx: Optional[int] = None
+    rank_syy: Optional[int] = None
+    distinct_x: Optional[int] = None
+    distinct_y: Optional[int] = None
 
     @classmethod
     def from_sums(cls, n, shift_x, shift_y, sx, sy, sxx, syy, sxy, min_x, max_x, min_y, max_y, hist=None, xedges=None,
-                  yedges=None, n_leaves=None):
-        """Derive the statistics from sums about a shift (st_pair_moments)."""
+                  yedges=None, n_leaves=None, ranks=None):
+        """Derive the statistics from sums about a shift (st_pair_moments); ``ranks``: the library's ``_capi.RankSums`` of
+        the same pairs, or None."""
         n = int(n)
         nan = float("nan")
         if n == 0:
@@ -71,13 +85,13 @@ class DistanceComparison:
         return cls(n_pairs=n, n_leaves=n_leaves, mean_x=mean_x, mean_y=mean_y, var_x=var_x, var_y=var_y, cov=cov,
                    pearson_r=r, min_x=float(min_x), max_x=float(max_x), min_y=float(min_y), max_y=float(max_y), hist=hist,
                    xedges=xedges, yedges=yedges, shift_x=float(shift_x), shift_y=float(shift_y), sx=float(sx),
-                   sy=float(sy), sxx=float(sxx), syy=float(syy), sxy=float(sxy))
+                   sy=float(sy), sxx=float(sxx), syy=float(syy), sxy=float(sxy), **rank_fields(ranks))
 
     @classmethod
-    def from_moments(cls, m, hist=None, xedges=None, yedges=None, n_leaves=None):
-        """From the library's ``_capi.PairMoments``."""
+    def from_moments(cls, m, hist=None, xedges=None, yedges=None, n_leaves=None, ranks=None):
+        """From the library's ``_capi.PairMoments`` and, if given, its ``_capi.RankSums``."""
         return cls.from_sums(m.n, m.shift_x, m.shift_y, m.sx, m.sy, m.sxx, m.syy, m.sxy, m.min_x, m.max_x, m.min_y,
-                             m.max_y, hist, xedges, yedges, n_leaves)
+                             m.max_y, hist, xedges, yedges, n_leaves, ranks)
 
     @classmethod
     def merge(cls, a: "DistanceComparison", b: "DistanceComparison") -> "DistanceComparison":
@@ -85,11 +99,13 @@ class DistanceComparison:
         sums are moved to a's shift, d = b.shift - a.shift, sum(x - a.shift) = b.sx + n_b d_x,
         sum(x - a.shift)^2 = b.sxx + 2 d_x b.sx + n_b d_x^2 (b.sxx itself where that is infinite), and so on, then added.
         The class of an infinite cross product depends on the shift it was summed about and is not recovered.
-        Histograms add when both have the same edges (otherwise ValueError)."""
+        Histograms add when both have the same edges (otherwise ValueError).  The rank fields (``spearman_r``, ``rank_*``,
+        ``distinct_*``) of the result are None: a value's rank depends on every pair of its call, so ranks of disjoint
+        ranges do not combine."""
         if b.n_pairs == 0:
-            return a
+            return a if a.rank_sxy is None else replace(a, **rank_fields(None))
         if a.n_pairs == 0:
-            return replace(b, n_leaves=a.n_leaves if a.n_leaves == b.n_leaves else None)
+            return replace(b, n_leaves=a.n_leaves if a.n_leaves == b.n_leaves else None, **rank_fields(None))
         hist = None
         if a.hist is not None or b.hist is not None:
             if a.hist is None or b.hist is None or not (np.array_equal(a.xedges, b.xedges) and np.array_equal(a.yedges, b.yedges)):
@@ -106,6 +122,23 @@ class DistanceComparison:
                              np.fmin(a.min_x, b.min_x), np.fmax(a.max_x, b.max_x), np.fmin(a.min_y, b.min_y),
                              np.fmax(a.max_y, b.max_y), hist, a.xedges if hist is not None else None,
                              a.yedges if hist is not None else None, a.n_leaves if a.n_leaves == b.n_leaves else None)
+
+
+def spearman_from_sums(n, n_nan, sxy, sxx, syy):
+    """Spearman's rs from the exact sums: sxy / (sqrt(sxx) sqrt(syy)) clipped to [-1, 1]; NaN when a column is constant
+    (sxx or syy 0), n < 2, or a pair held a NaN (scipy's nan_policy="propagate")."""
+    if n < 2 or n_nan > 0 or sxx <= 0 or syy <= 0:
+        return float("nan")
+    return min(1.0, max(-1.0, float(sxy) / (math.sqrt(float(sxx)) * math.sqrt(float(syy)))))
+
+
+def rank_fields(ranks):
+    """The rank fields of a DistanceComparison from a ``_capi.RankSums`` (None: all None)."""
+    if ranks is None:
+        return dict(spearman_r=None, rank_sxy=None, rank_sxx=None, rank_syy=None, distinct_x=None, distinct_y=None)
+    sxy, sxx, syy = ranks.sxy, ranks.sxx, ranks.syy
+    return dict(spearman_r=spearman_from_sums(int(ranks.n), int(ranks.n_nan), sxy, sxx, syy), rank_sxy=sxy, rank_sxx=sxx,
+                rank_syy=syy, distinct_x=int(ranks.distinct_x), distinct_y=int(ranks.distinct_y))
 
 
 def histogram_edges(bins, range, min_max):
@@ -130,9 +163,16 @@ def _needs_data_range(bins, range):
     return np.ndim(bins) == 0   # one edge array for both axes
 
 
-def run(call, bins, range, n_leaves=None):
+def run(call, bins, range, n_leaves=None, rank_call=None):
     """call(edges) -> (PairMoments, hist): one pass of the library.  ``range=None`` with integer bins costs a second
-    pass: the first finds min and max, the second bins."""
+    pass: the first finds min and max, the second bins.  rank_call() -> (PairMoments, RankSums), if given, adds the
+    rank fields: alone it is the only call (its moments are call(None)'s); with ``bins`` the histogram calls run as
+    they do without it."""
+    if rank_call is not None:
+        m, ranks = rank_call()
+        if bins is None:
+            return DistanceComparison.from_moments(m, n_leaves=n_leaves, ranks=ranks)
+        return replace(run(call, bins, range, n_leaves), **rank_fields(ranks))
     if bins is None:
         m, _ = call(None)
         return DistanceComparison.from_moments(m, n_leaves=n_leaves)

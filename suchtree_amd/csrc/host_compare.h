@@ -3,7 +3,8 @@
 // tree Y into two float32 scratch buffers on the device, and a reducer -- MomentsReduce (kernels_compare.h), CladeReduce
 // (kernels_clades.h), RowsReduce (kernels_rows.h) -- reduces them.  Device scratch is bounded by the chunk, host memory
 // by the histogram or the pieces: nothing grows with the pair count.  What needs no GPU -- the clade plan and its
-// tables, the rows layout, the folding of pieces -- is compare_plan.cpp.
+// tables, the rows layout, the folding of pieces -- is compare_plan.cpp.  The exact Spearman rank sums (compare_ranks,
+// at the end) are three such runs around count tables that the entry point owns (kernels_ranks.h, rank_plan.cpp).
 #pragma once
 
 constexpr int64_t kCompareChunkTriangle = (int64_t)1 << 25;   // 2 x 128 MiB of float32 distances
@@ -264,3 +265,203 @@ struct RowsReduce {
         return ST_OK;
     }
 };
+
+// ---- exact Spearman rank sums (st_compare_*_ranks_host; kernels_ranks.h, rank_plan.h) ------------------------------
+// What the three passes share.  It outlives each pass's compare_run (which frees its own block), so the entry point
+// owns it: the destructor frees everything on every path out.
+struct RankState {
+    char *d_small = nullptr;                 // occupancy | slots | miss | scan shares | scan results | dot slots | dot result
+    unsigned *d_tab[2] = {nullptr, nullptr};      // tree X's and tree Y's counters, then their a
+    unsigned long long *d_block_sum = nullptr;
+    RankSlots slots[2];
+    int h_slots[2 * kRankBuckets];
+    RankOccupancy occ;
+    RankScanPart scan[2];
+    RankDotPart dot;
+    unsigned miss = 0;
+    int64_t n = 0;
+
+    static constexpr size_t o_slots = (sizeof(RankOccupancy) + 255) & ~(size_t)255;
+    static constexpr size_t o_miss = o_slots + sizeof(int) * 2 * kRankBuckets;
+    static constexpr size_t o_parts = o_miss + 256;
+    static constexpr size_t o_scan = o_parts + sizeof(RankScanPart) * kRankBlocks;
+    static constexpr size_t o_dot = o_scan + 256;
+    static constexpr size_t o_dot_final = o_dot + sizeof(RankDotPart) * kRankBlocks;
+    static constexpr size_t small_bytes = o_dot_final + 256;
+
+    RankOccupancy *d_occ() const { return reinterpret_cast<RankOccupancy *>(d_small); }
+    int *d_slots() const { return reinterpret_cast<int *>(d_small + o_slots); }
+    unsigned *d_miss() const { return reinterpret_cast<unsigned *>(d_small + o_miss); }
+    RankScanPart *d_parts() const { return reinterpret_cast<RankScanPart *>(d_small + o_parts); }
+    RankScanPart *d_scan() const { return reinterpret_cast<RankScanPart *>(d_small + o_scan); }
+    RankDotPart *d_dot() const { return reinterpret_cast<RankDotPart *>(d_small + o_dot); }
+    RankDotPart *d_dot_final() const { return reinterpret_cast<RankDotPart *>(d_small + o_dot_final); }
+    size_t tab_bytes(int t) const { return (size_t)slots[t].n_slots * (size_t)kRankBucketKeys * 4; }
+    int64_t scan_blocks(int t) const { return (int64_t)slots[t].n_slots * (kRankBucketKeys / kRankScanBlock); }
+
+    RankState() = default;
+    RankState(const RankState &) = delete;
+    RankState &operator=(const RankState &) = delete;
+    ~RankState()
+    {
+        (void)hipFree(d_small);
+        (void)hipFree(d_tab[0]);
+        (void)hipFree(d_tab[1]);
+        (void)hipFree(d_block_sum);
+    }
+
+    // between pass 0 and pass 1: the slots of the occupied buckets and the tables they need
+    int tables()
+    {
+        for (int t = 0; t < 2; t++) {
+            rank_slots(occ.occ + t * kRankBuckets, slots[t]);
+            std::copy(slots[t].slot, slots[t].slot + kRankBuckets, h_slots + t * kRankBuckets);
+            uint64_t seen = 0;
+            for (int b = 0; b < kRankBuckets; b++) seen += occ.occ[t * kRankBuckets + b];
+            if ((int64_t)seen != n) return fail(ST_ERR_HIP, "ranks: the occupancy pass saw " + std::to_string(seen) + " of " + std::to_string(n) + " values");
+        }
+        for (int t = 0; t < 2; t++) {
+            const hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_tab[t]), tab_bytes(t));
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(ST_ERR_NOMEM, "ranks: the distances occupy " + std::to_string(slots[0].n_slots) + " + " + std::to_string(slots[1].n_slots) +
+                                              " of " + std::to_string(kRankBuckets) + " key buckets, 4 MiB of counters each: " + hipGetErrorString(e));
+            }
+        }
+        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_block_sum), (size_t)std::max(scan_blocks(0), scan_blocks(1)) * 8);
+        if (e != hipSuccess) return fail(ST_ERR_NOMEM, std::string("ranks: ") + hipGetErrorString(e));
+        return ST_OK;
+    }
+    int missed(const char *pass) const
+    {
+        if (miss == 0) return ST_OK;
+        return fail(ST_ERR_HIP, std::string("ranks: ") + std::to_string(miss) + " values of the " + pass + " pass fell in buckets the first pass had not seen");
+    }
+};
+
+// pass 0: the moments of st_compare_*_host (the same kernels in the same order: the same bits) and the occupancy
+struct RankOccupancyReduce {
+    MomentsReduce mom;
+    RankState &R;
+
+    size_t bytes(int64_t c) { return mom.bytes(c); }
+    hipError_t start(char *d, int64_t total, hipStream_t s)
+    {
+        hipError_t e = mom.start(d, total, s);
+        if (e == hipSuccess) e = hipMemsetAsync(R.d_occ(), 0, sizeof(RankOccupancy), s);
+        return e;
+    }
+    hipError_t chunk(const float *d_x, const float *d_y, int64_t off, int64_t c, hipStream_t s)
+    {
+        hipError_t e = mom.chunk(d_x, d_y, off, c, s);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_rank_occupancy, dim3(kRankBlocks), dim3(kRankThreads), 0, s, d_x, d_y, (long long)c, R.d_occ());
+        return hipGetLastError();
+    }
+    hipError_t finish(hipStream_t s)
+    {
+        hipError_t e = mom.finish(s);
+        if (e == hipSuccess) e = hipMemcpyAsync(&R.occ, R.d_occ(), sizeof(RankOccupancy), hipMemcpyDeviceToHost, s);
+        return e;
+    }
+    int done() { return mom.done(); }
+};
+
+// pass 1: count every value, then the scan of each table in key order
+struct RankCountReduce {
+    RankState &R;
+
+    size_t bytes(int64_t) { return 0; }
+    hipError_t start(char *, int64_t, hipStream_t s)
+    {
+        hipError_t e = hipMemcpyAsync(R.d_slots(), R.h_slots, sizeof R.h_slots, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemsetAsync(R.d_miss(), 0, 4, s);
+        for (int t = 0; t < 2 && e == hipSuccess; t++) e = hipMemsetAsync(R.d_tab[t], 0, R.tab_bytes(t), s);
+        return e;
+    }
+    hipError_t chunk(const float *d_x, const float *d_y, int64_t, int64_t c, hipStream_t s)
+    {
+        hipLaunchKernelGGL(k_rank_count, dim3(kRankBlocks), dim3(kRankThreads), 0, s, d_x, d_y, (long long)c, R.d_slots(), R.d_tab[0],
+                           R.d_tab[1], R.d_miss());
+        return hipGetLastError();
+    }
+    hipError_t finish(hipStream_t s)
+    {
+        for (int t = 0; t < 2; t++) {
+            const int64_t nb = R.scan_blocks(t);
+            const int grid = (int)std::min<int64_t>(nb, kRankBlocks);
+            hipLaunchKernelGGL(k_rank_block_sums, dim3(grid), dim3(kRankThreads), 0, s, R.d_tab[t], (long long)nb, R.d_block_sum, R.d_parts());
+            hipLaunchKernelGGL(k_rank_scan_blocks, dim3(1), dim3(kRankThreads), 0, s, R.d_block_sum, (long long)nb, R.d_parts(), grid,
+                               R.d_scan() + t);
+            hipLaunchKernelGGL(k_rank_scan_apply, dim3((unsigned)nb), dim3(kRankThreads), 0, s, R.d_tab[t], R.d_block_sum, (long long)R.n);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+        hipError_t e = hipMemcpyAsync(R.scan, R.d_scan(), sizeof R.scan, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(&R.miss, R.d_miss(), 4, hipMemcpyDeviceToHost, s);
+        return e;
+    }
+    int done()
+    {
+        const int rc = R.missed("count");
+        if (rc != ST_OK) return rc;
+        for (int t = 0; t < 2; t++)
+            if ((int64_t)R.scan[t].total != R.n) return fail(ST_ERR_HIP, "ranks: the scan counted " + std::to_string(R.scan[t].total) + " of " + std::to_string(R.n) + " values");
+        return ST_OK;
+    }
+};
+
+// pass 2: sum of a_x * a_y
+struct RankDotReduce {
+    RankState &R;
+
+    size_t bytes(int64_t) { return 0; }
+    hipError_t start(char *, int64_t, hipStream_t s) { return hipMemsetAsync(R.d_miss(), 0, 4, s); }
+    hipError_t chunk(const float *d_x, const float *d_y, int64_t off, int64_t c, hipStream_t s)
+    {
+        hipLaunchKernelGGL(k_rank_dot, dim3(kRankBlocks), dim3(kRankThreads), 0, s, d_x, d_y, (long long)c, R.d_slots(),
+                           reinterpret_cast<const int *>(R.d_tab[0]), reinterpret_cast<const int *>(R.d_tab[1]), off == 0 ? 1 : 0, R.d_dot(),
+                           R.d_miss());
+        return hipGetLastError();
+    }
+    hipError_t finish(hipStream_t s)
+    {
+        hipLaunchKernelGGL(k_rank_dot_final, dim3(1), dim3(64), 0, s, R.d_dot(), kRankBlocks, R.d_dot_final());
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&R.dot, R.d_dot_final(), sizeof R.dot, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(&R.miss, R.d_miss(), 4, hipMemcpyDeviceToHost, s);
+        return e;
+    }
+    int done() { return R.missed("lookup"); }
+};
+
+// The three passes.  run(chunk_pairs, reducer) is one compare_run over the caller's pairs; chunk_pairs 0 = the path's
+// default, which pass 0 always takes so that its moments are those of st_compare_*_host.
+template <typename Run>
+static int compare_ranks(st_tree *tx, int64_t n, int64_t chunk_pairs, Run run, st_pair_moments *out, st_rank_sums *out_ranks)
+{
+    ST_DEVICE(tx->device);
+    auto R = std::make_unique<RankState>();
+    R->n = n;
+    const hipError_t e = hipMalloc(reinterpret_cast<void **>(&R->d_small), RankState::small_bytes);
+    if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("ranks setup: ") + hipGetErrorString(e));
+    RankOccupancyReduce occupancy{MomentsReduce{nullptr, nullptr, 0, 0, out, nullptr}, *R};
+    int rc = run((int64_t)0, occupancy);
+    if (rc != ST_OK) return rc;
+    if (R->occ.n_nan > 0) {
+        rank_finish(n, (int64_t)R->occ.n_nan, 0, 0, 0, 0, 0, out_ranks);
+        return ST_OK;
+    }
+    rc = R->tables();
+    if (rc != ST_OK) return rc;
+    RankCountReduce count{*R};
+    rc = run(chunk_pairs, count);
+    if (rc != ST_OK) return rc;
+    RankDotReduce dot{*R};
+    rc = run(chunk_pairs, dot);
+    if (rc != ST_OK) return rc;
+    const i128 sxy = (i128)(((u128)(uint64_t)R->dot.hi << 64) | R->dot.lo);
+    rank_finish(n, 0, (int64_t)R->scan[0].distinct, (int64_t)R->scan[1].distinct, sxy, ((u128)R->scan[0].tie_hi << 64) | R->scan[0].tie_lo,
+                ((u128)R->scan[1].tie_hi << 64) | R->scan[1].tie_lo, out_ranks);
+    return ST_OK;
+}

@@ -7,6 +7,11 @@
 //                              size (the access pattern of the canopy kernel's record fetches)
 //   stmb_stream_copy           a plain 16-byte-per-lane streaming copy (achievable HBM rate)
 //
+// and, for scripts/compare_bench.py --spearman, the rate its count pass is bound by:
+//
+//   stmb_scatter_atomic_u32    no-return uint32 atomic adds at uniformly random counters of a table of a given size
+//                              (the access pattern of k_rank_count, kernels_ranks.h)
+//
 // scripts/micro/gather_bench.hip wraps the same kernels in a main() that sweeps table sizes.
 // Built for gfx950 only.
 #include <hip/hip_runtime.h>
@@ -55,6 +60,21 @@ __global__ __launch_bounds__(1024) void k_gather(const uint8_t *__restrict__ tab
         }
     }
     if (acc == 0xdeadbeef) out[0] = acc;
+}
+
+// each lane does iters x UNROLL no-return atomic adds of 1 at random counters
+template <int UNROLL>
+__global__ __launch_bounds__(256) void k_scatter_atomic(uint32_t *__restrict__ table, uint32_t n_counters, int iters)
+{
+    uint32_t s = (blockIdx.x * blockDim.x + threadIdx.x) * 2654435761u + 12345u;
+    for (int it = 0; it < iters; it++) {
+        uint32_t off[UNROLL];
+#pragma unroll
+        for (int k = 0; k < UNROLL; k++) off[k] = __umulhi(rng(s), n_counters);
+#pragma unroll
+        for (int k = 0; k < UNROLL; k++)
+            (void)__hip_atomic_fetch_add(table + off[k], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 }
 
 __global__ __launch_bounds__(1024) void k_copy(const uint4 *__restrict__ src, uint4 *__restrict__ dst, long long n16)
@@ -262,6 +282,36 @@ int stmb_stream_copy_shape(int device, long long bytes, int reps, int unroll, in
     (void)hipFree(dst);
     if (rc == 0 && gbytes_per_s) *gbytes_per_s = 2.0 * (double)bytes / best / 1e6;
     return rc;
+}
+
+// `blocks` x 256 lanes x 256 no-return atomic adds of 1 at uniformly random uint32 counters of a `table_bytes` (a
+// multiple of 4) table.  Returns 0 and the best-of-`reps` rate in G adds/s.
+int stmb_scatter_atomic_u32(int device, long long table_bytes, int blocks, int reps, double *gadds_per_s)
+{
+    if (table_bytes < 4 || (table_bytes & 3) || table_bytes / 4 > 0xFFFFFFFFLL || blocks < 1 || reps < 1) return 2;
+    STMB_CK(hipSetDevice(device));
+    uint32_t *d_table = nullptr;
+    STMB_CK(hipMalloc(&d_table, (size_t)table_bytes));
+    STMB_CK(hipMemset(d_table, 0, (size_t)table_bytes));
+    const int iters = 64, unroll = 4, threads = 256;
+    hipEvent_t e0, e1;
+    STMB_CK(hipEventCreate(&e0));
+    STMB_CK(hipEventCreate(&e1));
+    float best = 1e30f;
+    for (int rep = 0; rep < reps + 1; rep++) {
+        STMB_CK(hipEventRecord(e0));
+        hipLaunchKernelGGL((stmb::k_scatter_atomic<4>), dim3(blocks), dim3(threads), 0, 0, d_table, (uint32_t)(table_bytes / 4), iters);
+        STMB_CK(hipEventRecord(e1));
+        STMB_CK(hipEventSynchronize(e1));
+        float ms;
+        STMB_CK(hipEventElapsedTime(&ms, e0, e1));
+        if (rep > 0 && ms < best) best = ms;
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    (void)hipFree(d_table);
+    if (gadds_per_s) *gadds_per_s = (double)blocks * threads * iters * unroll / best / 1e6;
+    return 0;
 }
 
 }  // extern "C"

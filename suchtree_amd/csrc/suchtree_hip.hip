@@ -31,6 +31,8 @@
 // distances over the same pairs, reduced on the device): kernels_compare.h / kernels_clades.h / kernels_rows.h (moments
 // and 2-D histogram, clade pieces, row blocks), host_compare.h (the chunk driver compare_run and its reducers) and,
 // host-only C++ beside tree_prep.cpp, compare_plan.cpp (argument checks, clade plan and tables, rows layout, the fold).
+// Exact Spearman rank sums of the same pairs (st_compare_*_ranks_host): kernels_ranks.h, the reducers at the end of
+// host_compare.h and, host-only, rank_plan.cpp (keys, bucket layout, tie arithmetic, st_spearman_host).
 //
 // Host side of the C ABI: tree upload to one or several GPUs (tree_prep.cpp builds the tables, under a table budget
 // if one is given), the host path (host_pipe.h, host_copy.h: packed ids in through the copy engine, kernels write
@@ -49,6 +51,7 @@
 #include <cstring>
 #include <limits>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -133,6 +136,7 @@ private:
 #include "device_common.h"
 #include "kernels_misc.h"
 #include "kernels_compare.h"
+#include "kernels_ranks.h"
 #include "kernels_clades.h"
 #include "kernels_rows.h"
 
@@ -948,6 +952,50 @@ static void compare_empty(st_pair_moments *out, int64_t *out_hist, int32_t bins_
     if (out_hist) std::memset(out_hist, 0, (size_t)bins_x * (size_t)bins_y * 8);
 }
 
+// one compare_run over pairs [k_begin, k_begin + k_count) of the triangle / over n explicit pairs (arguments checked by
+// the caller); chunk_pairs 0: the path's default chunk
+template <typename Reduce>
+static int compare_triangle_run(st_tree *tx, st_tree *ty, const int64_t *ids_x, const int64_t *ids_y, int64_t m, int64_t k_begin,
+                                int64_t k_count, int64_t chunk_pairs, Reduce &red, int64_t *bad_id)
+{
+    auto setup = [&](char *d_extra, hipStream_t s) {
+        hipError_t e = hipMemcpyAsync(d_extra, ids_x, (size_t)m * 8, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_extra + (size_t)m * 8, ids_y, (size_t)m * 8, hipMemcpyHostToDevice, s);
+        return e;
+    };
+    auto prep = [](char *, hipStream_t, int64_t, int64_t) { return hipSuccess; };
+    auto src_x = [&](char *d_extra, int64_t off) {
+        return SrcTriangle{reinterpret_cast<const long long *>(d_extra), 1, (long long)(k_begin + off)};
+    };
+    auto src_y = [&](char *d_extra, int64_t off) {
+        return SrcTriangle{reinterpret_cast<const long long *>(d_extra) + m, 1, (long long)(k_begin + off)};
+    };
+    return compare_run(tx, ty, k_count, chunk_pairs > 0 ? chunk_pairs : kCompareChunkTriangle, (size_t)m * 16, setup, prep, src_x, src_y, red,
+                       bad_id);
+}
+
+template <typename Reduce>
+static int compare_pairs_run(st_tree *tx, st_tree *ty, const int64_t *pairs_x, const int64_t *pairs_y, int64_t n, int64_t chunk_pairs,
+                             Reduce &red, int64_t *bad_id)
+{
+    const int64_t chunk = std::min(n, chunk_pairs > 0 ? chunk_pairs : kCompareChunkPairs);
+    auto setup = [](char *, hipStream_t) { return hipSuccess; };
+    auto prep = [&](char *d_extra, hipStream_t s, int64_t off, int64_t c) {
+        hipError_t e = hipMemcpyAsync(d_extra, pairs_x + 2 * off, (size_t)c * 16, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_extra + (size_t)chunk * 16, pairs_y + 2 * off, (size_t)c * 16, hipMemcpyHostToDevice, s);
+        return e;
+    };
+    auto src_x = [](char *d_extra, int64_t) { return SrcContig{reinterpret_cast<const long long *>(d_extra)}; };
+    auto src_y = [&](char *d_extra, int64_t) { return SrcContig{reinterpret_cast<const long long *>(d_extra + (size_t)chunk * 16)}; };
+    return compare_run(tx, ty, n, chunk, (size_t)chunk * 32, setup, prep, src_x, src_y, red, bad_id);
+}
+
+static int rank_count_arg(int64_t n)
+{
+    if (n <= kRankMaxPairs) return ST_OK;
+    return fail(ST_ERR_ARG, "ranks of " + std::to_string(n) + " pairs: at most " + std::to_string(kRankMaxPairs) + " (2^31 - 1)");
+}
+
 extern "C" {
 
 int st_compare_triangle_host(st_tree *tx, st_tree *ty, const int64_t *ids_x, const int64_t *ids_y, int64_t m, int64_t k_begin,
@@ -970,20 +1018,8 @@ try {
     rc = compare_check_ids(ids_x, m, tx->n_nodes, bad_id);
     if (rc == ST_OK) rc = compare_check_ids(ids_y, m, ty->n_nodes, bad_id);
     if (rc != ST_OK) return rc;
-    auto setup = [&](char *d_extra, hipStream_t s) {
-        hipError_t e = hipMemcpyAsync(d_extra, ids_x, (size_t)m * 8, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_extra + (size_t)m * 8, ids_y, (size_t)m * 8, hipMemcpyHostToDevice, s);
-        return e;
-    };
-    auto prep = [](char *, hipStream_t, int64_t, int64_t) { return hipSuccess; };
-    auto src_x = [&](char *d_extra, int64_t off) {
-        return SrcTriangle{reinterpret_cast<const long long *>(d_extra), 1, (long long)(k_begin + off)};
-    };
-    auto src_y = [&](char *d_extra, int64_t off) {
-        return SrcTriangle{reinterpret_cast<const long long *>(d_extra) + m, 1, (long long)(k_begin + off)};
-    };
     MomentsReduce red{edges_x, edges_y, bins_x, bins_y, out, out_hist};
-    return compare_run(tx, ty, k_count, kCompareChunkTriangle, (size_t)m * 16, setup, prep, src_x, src_y, red, bad_id);
+    return compare_triangle_run(tx, ty, ids_x, ids_y, m, k_begin, k_count, 0, red, bad_id);
 } ST_CATCH_ALL
 
 int st_compare_pairs_host(st_tree *tx, st_tree *ty, const int64_t *pairs_x, const int64_t *pairs_y, int64_t n, const double *edges_x,
@@ -1005,17 +1041,61 @@ try {
     rc = compare_check_ids(pairs_x, 2 * n, tx->n_nodes, bad_id);
     if (rc == ST_OK) rc = compare_check_ids(pairs_y, 2 * n, ty->n_nodes, bad_id);
     if (rc != ST_OK) return rc;
-    const int64_t chunk = std::min(n, kCompareChunkPairs);
-    auto setup = [](char *, hipStream_t) { return hipSuccess; };
-    auto prep = [&](char *d_extra, hipStream_t s, int64_t off, int64_t c) {
-        hipError_t e = hipMemcpyAsync(d_extra, pairs_x + 2 * off, (size_t)c * 16, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_extra + (size_t)chunk * 16, pairs_y + 2 * off, (size_t)c * 16, hipMemcpyHostToDevice, s);
-        return e;
-    };
-    auto src_x = [](char *d_extra, int64_t) { return SrcContig{reinterpret_cast<const long long *>(d_extra)}; };
-    auto src_y = [&](char *d_extra, int64_t) { return SrcContig{reinterpret_cast<const long long *>(d_extra + (size_t)chunk * 16)}; };
     MomentsReduce red{edges_x, edges_y, bins_x, bins_y, out, out_hist};
-    return compare_run(tx, ty, n, chunk, (size_t)chunk * 32, setup, prep, src_x, src_y, red, bad_id);
+    return compare_pairs_run(tx, ty, pairs_x, pairs_y, n, 0, red, bad_id);
+} ST_CATCH_ALL
+
+int st_compare_triangle_ranks_host(st_tree *tx, st_tree *ty, const int64_t *ids_x, const int64_t *ids_y, int64_t m, int64_t k_begin,
+                                   int64_t k_count, int64_t chunk_pairs, st_pair_moments *out, st_rank_sums *out_ranks, int64_t *bad_id)
+try {
+    if (!out || !out_ranks) return fail(ST_ERR_ARG, "out or out_ranks is NULL");
+    int rc = compare_trees_args(tx, ty);
+    if (rc != ST_OK) return rc;
+    rc = triangle_range_args(m, k_begin, k_count);
+    if (rc == ST_OK) rc = chunk_pairs_arg(chunk_pairs);
+    if (rc == ST_OK) rc = rank_count_arg(k_count);
+    if (rc != ST_OK) return rc;
+    if (m > 0 && (!ids_x || !ids_y)) return fail(ST_ERR_ARG, "ids_x or ids_y is NULL");
+    if (k_count == 0) {
+        compare_empty(out, nullptr, 0, 0);
+        rank_finish(0, 0, 0, 0, 0, 0, 0, out_ranks);
+        return ST_OK;
+    }
+    rc = compare_check_ids(ids_x, m, tx->n_nodes, bad_id);
+    if (rc == ST_OK) rc = compare_check_ids(ids_y, m, ty->n_nodes, bad_id);
+    if (rc != ST_OK) return rc;
+    auto run = [&](int64_t chunk, auto &red) { return compare_triangle_run(tx, ty, ids_x, ids_y, m, k_begin, k_count, chunk, red, bad_id); };
+    return compare_ranks(tx, k_count, chunk_pairs, run, out, out_ranks);
+} ST_CATCH_ALL
+
+int st_compare_pairs_ranks_host(st_tree *tx, st_tree *ty, const int64_t *pairs_x, const int64_t *pairs_y, int64_t n, int64_t chunk_pairs,
+                                st_pair_moments *out, st_rank_sums *out_ranks, int64_t *bad_id)
+try {
+    if (!out || !out_ranks) return fail(ST_ERR_ARG, "out or out_ranks is NULL");
+    int rc = compare_trees_args(tx, ty);
+    if (rc != ST_OK) return rc;
+    if (n < 0) return fail(ST_ERR_ARG, "n < 0");
+    rc = chunk_pairs_arg(chunk_pairs);
+    if (rc == ST_OK) rc = rank_count_arg(n);
+    if (rc != ST_OK) return rc;
+    if (n > 0 && (!pairs_x || !pairs_y)) return fail(ST_ERR_ARG, "pairs_x or pairs_y is NULL");
+    if (n == 0) {
+        compare_empty(out, nullptr, 0, 0);
+        rank_finish(0, 0, 0, 0, 0, 0, 0, out_ranks);
+        return ST_OK;
+    }
+    rc = compare_check_ids(pairs_x, 2 * n, tx->n_nodes, bad_id);
+    if (rc == ST_OK) rc = compare_check_ids(pairs_y, 2 * n, ty->n_nodes, bad_id);
+    if (rc != ST_OK) return rc;
+    auto run = [&](int64_t chunk, auto &red) { return compare_pairs_run(tx, ty, pairs_x, pairs_y, n, chunk, red, bad_id); };
+    return compare_ranks(tx, n, chunk_pairs, run, out, out_ranks);
+} ST_CATCH_ALL
+
+int st_spearman_host(const float *x, const float *y, int64_t n, st_rank_sums *out)
+try {
+    std::string err;
+    const int rc = spearman_host(x, y, n, out, err);
+    return rc == ST_OK ? ST_OK : fail(rc, err);
 } ST_CATCH_ALL
 
 int st_clade_plan(const int32_t *parent, int64_t n_nodes, const int64_t *link_leaf, int64_t n_links, int64_t max_links,

@@ -389,7 +389,7 @@ class SuchTree(TreeNavigation):
         names = [name for name, _ in sorted(self.leaves.items(), key=lambda kv: kv[1]) if name in other.leaves]
         return names, self._name_ids(names), other._name_ids(names)
 
-    def compare_distances(self, other: "SuchTree", leaves=None, pairs=None, bins=None, range=None):
+    def compare_distances(self, other: "SuchTree", leaves=None, pairs=None, bins=None, range=None, spearman=False):
         """Compare this tree's distances with ``other``'s over the same pairs, reduced on the GPU.
 
         An extension: the reference has no counterpart.  It stands in for the comparison workflow of its docs
@@ -411,6 +411,9 @@ class SuchTree(TreeNavigation):
         ignores NaN distances (NaN-ignoring min and max), so the range is that of the other values; numpy raises on
         NaN data there instead.  An infinite distance makes the range infinite: ValueError, as in numpy.  The
         histogram leaves NaN and infinite distances out, as numpy does with a given range.
+        ``spearman=True`` also ranks every pair on the GPU (two more passes over the pairs and 4 MiB of device counters
+        per occupied key bucket, see DistanceComparison): ``spearman_r``, the exact integer rank sums and the distinct
+        counts are filled in; at most 2^31 - 1 pairs (ValueError beyond).  Every other field is what it is without it.
         Both trees must be on the same GPU (ValueError otherwise); an id out of range raises InvalidNodeError.
         """
         from . import compare
@@ -430,7 +433,8 @@ class SuchTree(TreeNavigation):
                 px = self._name_ids(flat).reshape(-1, 2)
                 py = other._name_ids(flat).reshape(-1, 2)
             dx, dy = self._device_tree(), other._device_tree()
-            return compare.run(lambda edges: dx.compare_pairs_host(dy, px, py, edges=edges), bins, range)
+            return compare.run(lambda edges: dx.compare_pairs_host(dy, px, py, edges=edges), bins, range,
+                               rank_call=(lambda: dx.compare_pairs_ranks_host(dy, px, py)) if spearman else None)
         if leaves is None:
             _, ids_x, ids_y = self.shared_leaves(other)
         elif isinstance(leaves, tuple) and len(leaves) == 2:
@@ -442,7 +446,8 @@ class SuchTree(TreeNavigation):
             raise ValueError("the two id lists must be 1-D and of equal length")
         dx, dy = self._device_tree(), other._device_tree()
         return compare.run(lambda edges: dx.compare_triangle_host(dy, ids_x, ids_y, edges=edges), bins, range,
-                           n_leaves=int(len(ids_x)))
+                           n_leaves=int(len(ids_x)),
+                           rank_call=(lambda: dx.compare_triangle_ranks_host(dy, ids_x, ids_y)) if spearman else None)
 
     def common_ancestor(self, a: Union[int, str], b: Union[int, str]) -> int:
         """Most recent common ancestor of two nodes (MuchTree.pyx:1128-1149)."""
