@@ -123,6 +123,7 @@ class TreeInfo(ctypes.Structure):
         ("b_table_bytes_per_leaf", ctypes.c_int32),
         ("ladder_sums", ctypes.c_int32),
         ("ladder_sums_max_pairs", ctypes.c_int64),
+        ("heap_lines", ctypes.c_int64),
     ]
 
     def as_dict(self):

@@ -1,5 +1,5 @@
 // kernels_canopy.h -- canopy family: CanopyParams, the per-pair device helpers, k_canopy_ladder, k_canopy_ilp,
-// k_mrca_ranks (launch_canopy.hip); k_canopy_sorted lives in kernels_canopy_sorted.h
+// k_canopy_ilp_heap, k_mrca_ranks (launch_canopy.hip); k_canopy_sorted lives in kernels_canopy_sorted.h
 // (launch_canopy_sorted.hip).  Include after device_common.h and pair_math.h.
 #pragma once
 #include "launch_geometry.h"
@@ -525,6 +525,121 @@ __global__ __launch_bounds__(kCanopyBlock, ((CAP <= 7 && PPL == 1) ? 8 : 4)) voi
         for (int j = 0; j < PPL; j++)      // (converged: every lane of the workgroup is here, with consecutive pair numbers)
             store_result_wave(out_d, out_m, base + (long long)j * blockDim.x + threadIdx.x, valid[j] ? s[j] : __builtin_nanf(""),
                               valid[j] ? m[j] : -1, live[j]);
+    }
+}
+
+// The predicated kernel on heap lines (tree_prep.h: prepare_heap_lines; perfect trees with in-order ids, the headline tree
+// among them).  Ids are arithmetic there: leaf slots sa = a >> 1 and sb = b >> 1 part ways k = bit length of (sa ^ sb)
+// edges below their MRCA, whose id is ((((sa >> k) << 1) | 1) << k) - 1; either side adds the six lowest edges of its
+// lineage from ONE 128-byte line (the line of 16 leaf slots) and the rest from the heap image in LDS, entry
+// (2^(D-6) + (slot >> 6)) >> q for its q-th edge above the line.  No portal, no block table, no depth cut, no shared-portal
+// case: one formula for every leaf pair, and a gather footprint of 8 MiB for 2^20 leaves where rec_a4 and the cherry
+// records take 20.  None of the addresses depends on a load but the pair's own, so a lane issues its four line loads
+// (two 16-byte windows per node: HeapSide) and all its LDS reads at once.  Four, because with eight narrower loads on a
+// line per 16 leaves in level order the kernel ran at the old 2.80 ms per 1e8 pairs: L1-miss latency per pair fell by 19 %
+// but the vector-memory address pipeline stayed busy 93 % of the launch (LAB_NOTES.md 9).  Sums start at +0.0f and every
+// add is predicated with -0.0f (kChainPad) as in k_canopy_ilp: the reference's adds in the reference's order, the same
+// bits.  A pair with an internal node (odd id) is walked on the tree itself (rare: a wave-level branch).
+struct HeapParams {
+    const float *lines;            // [2^(D-4) * 32] heap lines
+    const float *dist;             // [heap_image_bytes(D) / 4] heap image, staged to LDS
+    const Node8 *nodes;            // the walk family's tables (pairs with an internal node)
+    const int32_t *depth;
+    const Stride3 *stride;
+    long long n_nodes;
+    int32_t levels;                // D: edges between a leaf and the root
+};
+constexpr int kHeapLineEdges = 6;                                   // edges of a lineage that its line holds
+constexpr int kHeapClimbMax = kHeapMaxLevels - kHeapLineEdges;      // ... and the most that are left for the heap image
+
+typedef float __attribute__((ext_vector_type(4), aligned(4))) float4_align4;      // a 16-byte load at any dword
+
+// The six line values of one leaf slot (tree_prep.h: the layout of a heap line): two 16-byte loads, the window of the
+// slot's group of four leaves and the line's last four floats.
+struct HeapSide {
+    float4_align4 w;
+    float4 top;
+    uint32_t t;
+    __device__ __forceinline__ void load(const float *lines, uint32_t sl)
+    {
+        const float *line = lines + (size_t)(sl >> 4) * 32;
+        t = sl & 15u;
+        w = *reinterpret_cast<const float4_align4 *>(line + 7 * (t >> 2) + ((t & 2u) ? 3 : 0));
+        top = *reinterpret_cast<const float4 *>(line + 28);
+    }
+    // s += the first k (at most six) of the leaf's edges, in order; every add predicated (kChainPad)
+    __device__ __forceinline__ float add(float s, int k) const
+    {
+        const float pad = __uint_as_float(kChainPad);
+        // (selects between pairs of components only: a select chain over all four components of one vector can become an
+        // extract at a variable index, which the compiler keeps in scratch memory -- tests/test_heap_kernel_resources.py)
+        const float w0 = w.x, w1 = w.y, w2 = w.z, w3 = w.w, t0 = top.x, t3 = top.w;
+        const bool hi = (t & 2u) != 0, odd = (t & 1u) != 0;
+        const float own_lo = odd ? w1 : w0, own_hi = odd ? w3 : w2;
+        s += 0 < k ? (hi ? own_hi : own_lo) : pad;
+        s += 1 < k ? (hi ? w1 : w2) : pad;
+        s += 2 < k ? (hi ? w0 : w3) : pad;
+        s += 3 < k ? ((t & 8u) ? t3 : t0) : pad;
+        s += 4 < k ? top.y : pad;
+        s += 5 < k ? top.z : pad;
+        return s;
+    }
+};
+
+template <typename Src>
+__global__ __launch_bounds__(kCanopyBlock, 4) void k_canopy_ilp_heap(HeapParams P, Src src, long long n, DistSink out_d,
+                                                                     MrcaSink out_m, Fault *fault)
+{
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const float *H = reinterpret_cast<const float *>(lds_raw);
+    {      // stage the heap image: 16 bytes per lane per step, coalesced
+        const int n16 = (int)(heap_image_bytes(P.levels) / 16);
+        const uint4 *src16 = reinterpret_cast<const uint4 *>(P.dist);
+        uint4 *dst16 = reinterpret_cast<uint4 *>(lds_raw);
+        for (int k = threadIdx.x; k < n16; k += blockDim.x) dst16[k] = src16[k];
+        __syncthreads();
+    }
+    const uint32_t first = 1u << (P.levels - kHeapLineEdges);      // heap index of slot block 0 at the lowest level of the image
+    const float pad = __uint_as_float(kChainPad);
+    for (long long base = (long long)blockIdx.x * blockDim.x; base < n; base += (long long)gridDim.x * blockDim.x) {
+        const long long i = base + threadIdx.x;
+        const bool live = i < n;
+        long long ida, idb;
+        src.load(live ? i : n - 1, ida, idb);
+        const bool valid = (unsigned long long)ida < (unsigned long long)P.n_nodes && (unsigned long long)idb < (unsigned long long)P.n_nodes;
+        if (!valid && live) record_fault(fault, ida, idb, P.n_nodes);
+        const bool leaves = valid && !((ida | idb) & 1);
+        const uint32_t sa = leaves ? (uint32_t)ida >> 1 : 0u, sb = leaves ? (uint32_t)idb >> 1 : 0u;
+        // every load of both lines before anything uses them
+        HeapSide A, B;
+        A.load(P.lines, sa);
+        B.load(P.lines, sb);
+        // ... and the heap entries of both lineages: index (first + (slot >> 6)) >> q for the q-th edge above the line (a
+        // climb that is over, or a level the tree does not have, reads an entry that is never added: entry 1 at the least)
+        const uint32_t ua = first + (sa >> kHeapLineEdges), ub = first + (sb >> kHeapLineEdges);
+        float ha[kHeapClimbMax], hb[kHeapClimbMax];
+#pragma unroll
+        for (int q = 0; q < kHeapClimbMax; q++) {
+            const uint32_t xa = ua >> q, xb = ub >> q;
+            ha[q] = H[xa ? xa : 1u];
+            hb[q] = H[xb ? xb : 1u];
+        }
+        const uint32_t x = sa ^ sb;
+        const int k = x ? 32 - __clz((int)x) : 0;      // edges either side climbs
+        float s = A.add(0.0f, k);
+#pragma unroll
+        for (int q = 0; q < kHeapClimbMax; q++) s += kHeapLineEdges + q < k ? ha[q] : pad;
+        s = B.add(s, k);
+#pragma unroll
+        for (int q = 0; q < kHeapClimbMax; q++) s += kHeapLineEdges + q < k ? hb[q] : pad;
+        int m = k ? (int)((((((sa >> k) << 1) | 1u) << k)) - 1u) : (int)ida;
+        if (valid && !leaves) {      // an internal node (rare)
+            const PairResult r = pair_walk(P.nodes, P.depth, P.stride, (int32_t)ida, (int32_t)idb);
+            s = r.dist;
+            m = r.mrca;
+        }
+        // (converged: every lane of the workgroup is here, with consecutive pair numbers)
+        store_result_wave(out_d, out_m, i, valid ? s : __builtin_nanf(""), valid ? m : -1, live);
     }
 }
 

@@ -28,6 +28,13 @@ __host__ __device__ constexpr size_t ladder_kernel_lds_bytes(int canopy_nodes) {
 // block table of the four-byte a side (k_canopy_ilp<..., true>), padded to the 16-byte staging granule
 __host__ __device__ inline size_t leaf_block_image_bytes(int count) { return ((size_t)count * 2 + 15) & ~(size_t)15; }
 
+// heap image of the heap-line form (k_canopy_ilp_heap; tree_prep.h: heap_dist of a perfect tree with D levels of edges):
+// 2^(D-5) floats, padded to the 16-byte staging granule
+__host__ __device__ constexpr size_t heap_image_bytes(int levels)
+{
+    return ((size_t)4 << (levels - 5)) < 16 ? (size_t)16 : ((size_t)4 << (levels - 5));
+}
+
 // LDS scratch of a k_canopy_sorted tile of Q * 1024 pairs: per pair one uint16 (the sorted order), with the
 // sparse table one uint32 (the pair's meeting node; b's edge count in lineage-sum mode), with
 // lineage sums two more words (a's side, later the distance; b's record slot), then the bucket

@@ -132,6 +132,17 @@ static inline int64_t canopy_min_pairs(const st_tree *t)
     return walk_is_quick && (sorted || ladder || deep) ? kSortedMinPairs : kCanopyMinPairs;
 }
 
+// The heap-line form of the predicated kernel (kernels_canopy.h: k_canopy_ilp_heap; perfect trees): explicit pair batches
+// with distances take it where the handle has both tables and option "heap_lines" admits it -- 1 (default): trees of
+// 2^18 leaves and more (below, rec_a4 and the cherry records gather from under 5 MiB and there is nothing to win), 2:
+// wherever it was built.
+constexpr int kHeapDefaultMinLevels = 18;
+static inline bool heap_lines_applies(const st_tree *t)
+{
+    return t->strategy == ST_STRATEGY_CANOPY && t->d_heap_lines && t->d_heap_dist &&
+           (t->heap_lines == 2 || (t->heap_lines == 1 && t->heap_levels >= kHeapDefaultMinLevels));
+}
+
 static inline bool mrca_ranks_ready(const st_tree *t)
 {
     return t->strategy == ST_STRATEGY_CANOPY && t->mrca_ranks && t->d_rec_r && t->d_rmq64;

@@ -42,6 +42,10 @@ struct st_tree {
     uint8_t *d_rec_c = nullptr;           // cherry records (one per pair of sibling leaves; tree_prep.h), else NULL
     int cherries = 1;         // tuning: 0 = the predicated kernel reads every b record from rec_b even where cherry records exist
     int32_t leaf_block_shift = 0, leaf_block_count = 0;
+    float *d_heap_lines = nullptr;        // heap lines and heap image of a perfect tree (tree_prep.h: prepare_heap_lines), else NULL
+    float *d_heap_dist = nullptr;
+    int32_t heap_levels = 0;  // D of that tree, else 0
+    int heap_lines = 1;       // tuning: 0 = never the heap-line form, 1 = on trees of 2^18 leaves and more, 2 = wherever the tables exist
     int rec_a4 = 1;           // tuning: 0 = the predicated canopy kernel reads the 8-byte rec_a entries even when the four-byte form exists
     uint8_t *d_rec_p = nullptr;       // lineage sums (deep canopies with a sparse table), else NULL
     uint64_t *d_rmq64 = nullptr;

@@ -353,6 +353,8 @@ void st_tree_destroy(st_tree *t)
         (void)hipFree(t->d_rec_a4);
         (void)hipFree(t->d_leaf_blocks);
         (void)hipFree(t->d_rec_c);
+        (void)hipFree(t->d_heap_lines);
+        (void)hipFree(t->d_heap_dist);
         (void)hipFree(t->d_rec_b);
         (void)hipFree(t->d_rec_i);
         (void)hipFree(t->d_rec_p);
@@ -383,8 +385,10 @@ try {
     *info = t->info;
     info->strategy = t->strategy;
     info->big_batch_kernel = big_batch_kernel_of(t);      // (follows the handle's current options)
-    info->a_side_bytes = t->has_canopy ? ((t->rec_a4 && t->d_rec_a4 && t->d_leaf_blocks) ? 4 : 8) : 0;
-    info->b_table_bytes_per_leaf = t->has_canopy ? ((t->rec_a4 && t->cherries && t->d_rec_c && t->d_leaf_blocks) ? t->rec_bytes / 4 : t->rec_bytes / 2) : 0;
+    info->heap_lines = heap_lines_applies(t) ? 1 : 0;
+    info->a_side_bytes = t->has_canopy ? ((info->heap_lines || (t->rec_a4 && t->d_rec_a4 && t->d_leaf_blocks)) ? 4 : 8) : 0;
+    // (heap lines: both nodes of a pair gather from the one table of 8 bytes per leaf -- 4 + 4)
+    info->b_table_bytes_per_leaf = info->heap_lines ? 4 : t->has_canopy ? ((t->rec_a4 && t->cherries && t->d_rec_c && t->d_leaf_blocks) ? t->rec_bytes / 4 : t->rec_bytes / 2) : 0;
     info->ladder_sums = (t->ladder_sums && ladder_sums_ready(t)) ? 1 : 0;      // (for batches of up to ladder_sums_max_pairs, if that is set)
     info->ladder_sums_max_pairs = info->ladder_sums ? t->ladder_sums_max_pairs : 0;
     info->host_wire_bytes_in = t->wire48 && t->n_nodes <= 0xFFFFFF ? 6 : 8;
@@ -455,6 +459,11 @@ static int set_option_one(st_tree *t, const char *name, int64_t value)
     if (std::strcmp(name, "cherries") == 0) {
         if (value != 0 && value != 1) return fail(ST_ERR_ARG, "cherries must be 0 or 1");
         t->cherries = (int)value;
+        return ST_OK;
+    }
+    if (std::strcmp(name, "heap_lines") == 0) {
+        if (value < 0 || value > 2) return fail(ST_ERR_ARG, "heap_lines must be 0, 1 or 2");
+        t->heap_lines = (int)value;
         return ST_OK;
     }
     if (std::strcmp(name, "batch_probe") == 0) {

@@ -458,6 +458,54 @@ bool prepare_cherries(TreeTables &T)
     return true;
 }
 
+bool prepare_heap_lines(TreeTables &T)
+{
+    T.heap_lines.clear();
+    T.heap_dist.clear();
+    T.heap_levels = 0;
+    if (!T.parity_layout || !T.inorder_ids || (int64_t)T.nodes.size() != T.n) return false;
+    int D = -1;
+    for (int d = kHeapMinLevels; d <= kHeapMaxLevels; d++)
+        if (T.n == ((int64_t)2 << d) - 1) D = d;
+    if (D < 0 || T.n_leaves != (int64_t)1 << D) return false;
+    // the shape, node by node: (h, k) -> id (2k+1) * 2^h - 1 is a bijection onto [0, n), so this visits every node once
+    auto id_of = [](int h, int64_t k) { return ((2 * k + 1) << h) - 1; };
+    for (int h = 0; h <= D; h++) {
+        const int64_t count = (int64_t)1 << (D - h);
+        for (int64_t k = 0; k < count; k++) {
+            const int64_t x = id_of(h, k);
+            if (h == D ? x != (int64_t)T.root : (int64_t)T.nodes[(size_t)x].parent != id_of(h + 1, k >> 1)) return false;
+        }
+    }
+    auto e = [&](int h, int64_t k) { return T.nodes[(size_t)id_of(h, k)].dist; };
+    const int64_t lines = (int64_t)1 << (D - 4);
+    std::vector<float> L((size_t)lines * 32);
+    for (int64_t q = 0; q < lines; q++) {
+        float *line = L.data() + (size_t)q * 32;
+        for (int g = 0; g < 4; g++) {      // four leaves, the two edges above their cherries and the one above those
+            float *G = line + 7 * g;
+            G[0] = e(0, 16 * q + 4 * g);
+            G[1] = e(0, 16 * q + 4 * g + 1);
+            G[2] = e(1, 8 * q + 2 * g);
+            G[3] = e(2, 4 * q + g);
+            G[4] = e(1, 8 * q + 2 * g + 1);
+            G[5] = e(0, 16 * q + 4 * g + 2);
+            G[6] = e(0, 16 * q + 4 * g + 3);
+        }
+        line[28] = e(3, 2 * q);
+        line[29] = e(4, q);
+        line[30] = e(5, q >> 1);
+        line[31] = e(3, 2 * q + 1);
+    }
+    std::vector<float> H((size_t)1 << (D - 5), 0.0f);
+    for (int d = 1; d <= D - 6; d++)
+        for (int64_t j = 0; j < (int64_t)1 << d; j++) H[(size_t)(((int64_t)1 << d) + j)] = e(D - d, j);
+    T.heap_lines = std::move(L);
+    T.heap_dist = std::move(H);
+    T.heap_levels = D;
+    return true;
+}
+
 static void build_rmq64(TreeTables &T)
 {
     T.canopy_rmq64.resize(T.canopy_rmq.size());

@@ -148,6 +148,23 @@ struct TreeTables {
     // (kLeafBlockCherries) set beside its portal; other leaves, internal nodes and the shared-portal case read rec_b.
     // Built when at least 99 % of the leaves sit in marked blocks (balanced and near-balanced trees).
     std::vector<uint8_t> rec_c;                // [ceil(n_leaves / 2) * record_bytes/2] or empty
+    // Heap lines (prepare_heap_lines; perfect trees with in-order ids, 6 <= D <= 20 levels of edges): node ids are arithmetic
+    // there -- the node of height h (leaf = 0) and index k in its level has id (2k+1) * 2^h - 1 --, so no table has to name a
+    // parent, a portal or a depth, and every edge is stored ONCE.  e(h, k) = length of the edge above that node.
+    //   heap_lines: one 128-byte line (32 floats) per 16 leaf slots 16q .. 16q+15: the 31 edges of their subtree and the
+    //     one above it, laid out so that a leaf finds its six lowest edges in TWO 16-byte windows (k_canopy_ilp_heap issues
+    //     two loads per node; the vector-memory address pipeline, not the miss path, limits that kernel):
+    //       floats 7g .. 7g+6 (g = 0..3: leaves 4g .. 4g+3 of the line)
+    //           e(0, 16q+4g) e(0, 16q+4g+1) e(1, 8q+2g) e(2, 4q+g) e(1, 8q+2g+1) e(0, 16q+4g+2) e(0, 16q+4g+3)
+    //         -- the first two leaves of the group read floats 7g .. 7g+3, the last two 7g+3 .. 7g+6 (4-byte aligned windows)
+    //       floats 28 .. 31   e(3, 2q) e(4, q) e(5, q >> 1) e(3, 2q+1)
+    //   heap_dist:  the levels above, as a heap: entry 2^d + j = e(D - d, j) for depth 1 <= d <= D - 6 (entries 0 and 1 are
+    //     never read): 2^(D-5) floats, at most 128 KiB -- staged into LDS.
+    // Both nodes of a leaf pair read their six lowest edges from one line each and climb the rest in LDS: 8 MiB of gather
+    // footprint for 2^20 leaves where rec_a4 + the cherry records take 20.
+    std::vector<float> heap_lines;      // [32 * 2^(D-4)] or empty
+    std::vector<float> heap_dist;       // [2^(D-5)] or empty
+    int32_t heap_levels = 0;            // D, or 0
     std::vector<uint8_t> rec_b;         // [n * record_bytes/2]
     std::vector<uint8_t> rec_i;         // [n * record_bytes/2], or empty: left out under a table budget (pairs that share a
                                         // portal are then walked on the tree itself: kernels_canopy.h::same_portal_by_walk)
@@ -239,6 +256,11 @@ constexpr uint16_t kLeafBlockCherries = 0x8000u, kLeafBlockPortalMask = 0x3FFFu,
 static_assert(kMaxCanopyNodes <= (int)kLeafBlockPortalMask + 1,
               "a block-table entry keeps its portal in 14 bits (k_canopy_ilp masks every entry with kLeafBlockPortalMask)");
 bool prepare_cherries(TreeTables &T);
+
+// heap_lines, heap_dist and heap_levels (see TreeTables); false (tables left empty) unless the parent array IS the perfect
+// in-order tree of 6 <= D <= 20 levels (verified node by node).  Needs prepare_basic only.
+constexpr int kHeapMinLevels = 6, kHeapMaxLevels = 20;
+bool prepare_heap_lines(TreeTables &T);
 
 // rec_r and canopy_rmq64 (see TreeTables) for trees with a canopy and in-order ids; false otherwise.
 bool prepare_rank_table(TreeTables &T);
