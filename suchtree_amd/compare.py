@@ -125,11 +125,13 @@ class DistanceComparison:
 
 
 def spearman_from_sums(n, n_nan, sxy, sxx, syy):
-    """Spearman's rs from the exact sums: sxy / (sqrt(sxx) sqrt(syy)) clipped to [-1, 1]; NaN when a column is constant
-    (sxx or syy 0), n < 2, or a pair held a NaN (scipy's nan_policy="propagate")."""
+    """Spearman's rs from the exact sums: sxy / sqrt(sxx syy) clipped to [-1, 1]; NaN when a column is constant
+    (sxx or syy 0), n < 2, or a pair held a NaN (scipy's nan_policy="propagate").  One square root of the product
+    (below 2^186 for n <= 2^31 - 1), not the product of two: sqrt(s * s) == s in binary floating point, so sxy == sxx == syy
+    gives 1.0 and sxy == -sxx -1.0 exactly, which sqrt(s) * sqrt(s) misses by an ulp for some s."""
     if n < 2 or n_nan > 0 or sxx <= 0 or syy <= 0:
         return float("nan")
-    return min(1.0, max(-1.0, float(sxy) / (math.sqrt(float(sxx)) * math.sqrt(float(syy)))))
+    return min(1.0, max(-1.0, float(sxy) / math.sqrt(float(sxx) * float(syy))))
 
 
 def rank_fields(ranks):

@@ -10,53 +10,14 @@ import subprocess
 
 import numpy as np
 import pytest
-from scipy.stats import rankdata, spearmanr
+from scipy.stats import spearmanr
 
 from conftest import ROOT
+from rank_reference import host_columns as _columns, perfect_tree_sums, scipy_midrank_sums as _want, tie_identity as _tie_identity
 from suchtree_amd import _capi
 from suchtree_amd.compare import DistanceComparison, rank_fields, spearman_from_sums
 
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-
-
-def _want(x, y):
-    """(Sxy, Sxx, Syy) as Python ints from scipy's midranks: a = 2 rank - (n + 1) is an integer."""
-    n = len(x)
-    a2 = 2 * rankdata(x.astype(np.float64), "average") - (n + 1)
-    b2 = 2 * rankdata(y.astype(np.float64), "average") - (n + 1)
-    assert np.array_equal(a2, np.rint(a2)) and np.array_equal(b2, np.rint(b2))
-    a, b = [int(v) for v in a2], [int(v) for v in b2]
-    return sum(p * q for p, q in zip(a, b)), sum(p * p for p in a), sum(q * q for q in b)
-
-
-def _tie_identity(v):
-    n = len(v)
-    _, t = np.unique(v, return_counts=True)      # (-0.0 == +0.0: one group)
-    ties = sum(int(c) ** 3 - int(c) for c in t)
-    assert (n ** 3 - n - ties) % 3 == 0
-    return (n ** 3 - n - ties) // 3
-
-
-def _columns():
-    rng = np.random.default_rng(31)
-    n = 200_000
-    heavy = rng.integers(-40, 40, n).astype(np.float32) * np.float32(0.125)
-    zeros = np.where(rng.random(n) < 0.5, np.float32(-0.0), np.float32(0.0)).astype(np.float32)
-    mixed = np.where(rng.random(n) < 0.3, zeros, heavy).astype(np.float32)
-    spread = (rng.standard_normal(n) * 10.0 ** rng.integers(-30, 30, n)).astype(np.float32)
-    spread[rng.random(n) < 0.01] = np.inf
-    sub = (rng.integers(-1000, 1000, n).astype(np.float64) * 1.4e-45).astype(np.float32)      # subnormals, both signs
-    distinct = rng.permutation(n).astype(np.float32)
-    assert len(np.unique(distinct)) == n and (np.abs(sub[sub != 0]) < 1.2e-38).all() and np.signbit(mixed[mixed == 0]).any()
-    return {
-        "heavy ties vs mixed zeros": (heavy, mixed),
-        "wide range with inf vs heavy ties": (spread, heavy),
-        "subnormals vs wide range": (sub, spread),
-        "all distinct vs all distinct": (distinct, rng.permutation(n).astype(np.float32)),
-        "all distinct vs heavy ties": (distinct, heavy),
-        "small": (heavy[:37], spread[:37]),
-        "two": (np.float32([1, 2]), np.float32([5, -5])),
-    }
 
 
 @pytest.mark.parametrize("case", list(_columns()))
@@ -84,6 +45,19 @@ def test_identical_and_negated_columns():
     # -0.0 ties with +0.0 on either side
     z = _capi.spearman_host(np.float32([0.0, -0.0, 1.0, -1.0]), np.float32([-0.0, 0.0, 2.0, -2.0]))
     assert z.distinct_x == z.distinct_y == 3 and z.sxy == z.sxx == z.syy == (4 ** 3 - 4 - 6) // 3
+
+
+def test_spearman_r_is_exactly_one_when_the_sums_are_equal():
+    """sqrt(s) * sqrt(s) misses s by an ulp for some s (the triangle of a perfect tree of 1024 leaves against itself gave
+    0.9999999999999998): spearman_from_sums takes one root of the product."""
+    for L in range(2, 17):
+        s = perfect_tree_sums(L, "identity")
+        assert s.sxy == s.sxx == s.syy
+        assert spearman_from_sums(s.n, 0, s.sxy, s.sxx, s.syy) == 1.0 and spearman_from_sums(s.n, 0, -s.sxy, s.sxx, s.syy) == -1.0
+    rng = np.random.default_rng(34)
+    for s in rng.integers(1, 2 ** 62, 2000):
+        s = int(s) * int(rng.integers(1, 2 ** 31))
+        assert spearman_from_sums(5, 0, s, s, s) == 1.0 and spearman_from_sums(5, 0, -s, s, s) == -1.0
 
 
 def test_nan_empty_single_and_constant_columns_give_nan():
