@@ -41,7 +41,8 @@ extern "C" {
  *      st_clade_plan, st_compare_clades_host, struct st_clade_segment and the ST_CLADE_* constants; then, also additive,
  *      st_compare_rows_host; then, also additive, struct st_rank_sums, st_compare_triangle_ranks_host,
  *      st_compare_pairs_ranks_host and st_spearman_host; then st_tree_info.heap_lines appended (8 bytes) with option
- *      "heap_lines" -- callers built against the shorter struct keep using st_tree_info_get_sized.
+ *      "heap_lines" -- callers built against the shorter struct keep using st_tree_info_get_sized; then, in the same way,
+ *      st_tree_info.stream_hint appended (8 bytes) with option "stream_hint".
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -95,6 +96,8 @@ typedef struct st_tree_info {
     int64_t heap_lines;       /* 1 = explicit pair batches with distances currently take the heap-line form of the predicated kernel
                                  (perfect trees; option "heap_lines"): both nodes of a pair gather from one table of 8 bytes per
                                  leaf, so a_side_bytes and b_table_bytes_per_leaf are 4 and 4 while it is set; else 0 */
+    int64_t stream_hint;      /* 1 = large explicit pair batches with distances from and to device buffers (st_distances_device*) currently
+                                 read their pairs and write their results with the non-temporal hint (option "stream_hint"); else 0 */
 } st_tree_info;
 
 /* st_tree_info.dropped_tables, in the order in which a table budget (st_tree_options.table_budget_bytes, else
@@ -533,9 +536,15 @@ int st_tree_set_strategy(st_tree *tree, int strategy);
  * "heap_lines": perfect trees with in-order ids and 6 to 20 levels of edges also get heap lines -- one 128-byte line per 16
  * leaves that holds the 31 edges of their subtree and the one above it, and the levels above as a heap kept in LDS: every
  * edge once, 8 bytes per leaf.  Explicit pair batches with distances then read both nodes of a pair from that table, with
- * ids, MRCAs and meeting depths by arithmetic (the same bits).  1 (default) = on trees of 2^18 leaves and more (below, the
- * tables above already gather from under 5 MiB); 2 = wherever the tables exist; 0 = never.  st_tree_info.heap_lines
+ * ids, MRCAs and meeting depths by arithmetic (the same bits).  1 (default) = on trees of 2^17 leaves and more (at 2^16 the
+ * tables above are still ahead); 2 = wherever the tables exist; 0 = never.  st_tree_info.heap_lines
  * follows.  Under a table budget these tables are the first to go.
+ * "stream_hint": the pair array and the result arrays of a launch are read once and written once; with the hint the kernel
+ * reads and writes them non-temporally, so that they do not push the tables it gathers from out of L2 (the same bytes either
+ * way).  1 (default) = explicit pair batches from and to device buffers (st_distances_device, _f32, _wire) that the
+ * heap-line kernel takes: pair loads and result stores; 2 = also the pair loads of the predicated kernel on general tables, for
+ * such batches and for the host entry points' int32 pairs (the other kernels have no hinted form); 0 = never.  Paths whose next kernel reads the results
+ * back (the st_compare_* family) never use it.  st_tree_info.stream_hint follows.
  * "wire48": 1 (default) = on trees of fewer than 2^24 nodes the host entry points ship ids over the link as 24 bits
  * each (6 bytes per pair instead of 8; the packing step then checks the range and keeps the id to report); 0 = int32.
  * "wire24": 1 (default) = on such trees MRCA ids come back over the link as 24 bits each (7 bytes per pair with the

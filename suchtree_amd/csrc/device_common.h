@@ -19,15 +19,55 @@ __device__ __forceinline__ void record_fault(Fault *f, long long a, long long b,
     if (b < 0 || b >= n_nodes) { atomicMax(&f->max_bad, b); atomicMin(&f->min_bad, b); }
 }
 
+// ---- the streaming hint ----------------------------------------------------
+// A pair array is read once and a result array written once, yet their lines allocate in L2 and push out the table lines
+// a kernel gathers from: on the 8 MiB of heap lines behind a 4 MiB L2 the 28 bytes per pair of the headline launch cost
+// one fabric read in ten (scripts/l2_lru_model.py; LAB_NOTES.md 9).  `nt` of an explicit pair source marks the launch's
+// pair array and result arrays as such streams: the loads of the pairs then carry the non-temporal modifier
+// (global_load_dwordx4 ... nt) and, in k_canopy_ilp_heap, so do the stores of the results (global_store_dword ... nt).
+// A run-time, wave-uniform field like SrcContig32::packed48, so that no kernel is compiled twice; the host sets it
+// (launch_policy.h: stream_hint_applies) and aggregate initialisation without it leaves it 0.  The same bytes at the
+// same addresses either way.  The sinks carry no field of their own: k_canopy_ilp_heap sits at its limit of scalar
+// registers (tests/test_heap_kernel_resources.py allows no spill), and one more word among its arguments, or one more
+// loop-invariant condition in its loop, makes it spill -- so that kernel tests the source's field once and runs one of two
+// copies of its loop (kernels_canopy.h: heap_pairs), and the other kernels' stores stay plain.  load() stays the plain load:
+// only k_canopy_ilp, measured with it, asks for load_stream(); every other kernel compiles to what it was.
+// A hinted access and its plain twin sit in the two arms of a branch, same address, same value: the optimiser hoists or sinks them
+// into ONE access and, the hint being advice, drops it on the way (seen on the pair load and on both id stores of
+// k_canopy_ilp_heap; a compiler fence between them does not stop it).  It merges only accesses that are the same operation, and
+// the declared alignment is part of that: the hinted ones go through types that claim HALF their natural alignment (claiming
+// less than holds is always allowed, and global memory takes a dword or a 16-byte access at any such address in one instruction:
+// HeapSide's float4_align4).  tests/test_stream_hint_codegen.py notices if the hint gets lost again.
+typedef long long __attribute__((ext_vector_type(2), aligned(8))) StreamI64x2;
+typedef int __attribute__((ext_vector_type(2), aligned(4))) StreamI32x2;
+typedef int __attribute__((aligned(2))) StreamI32;
+typedef unsigned __attribute__((aligned(2))) StreamU32;
+typedef float __attribute__((aligned(2))) StreamF32;
+typedef double __attribute__((aligned(4))) StreamF64;
+
 // ---- pair sources: where pair number i of a launch comes from ----------------
 // C-order int64 (n,2): one 16-byte load per lane, fully coalesced.
 struct SrcContig {
     const long long *pairs;
-    __device__ __forceinline__ void load(long long i, long long &a, long long &b) const
+    int nt;      // the streaming hint (above)
+    template <bool NT> __device__ __forceinline__ void load_as(long long i, long long &a, long long &b) const
     {
-        const longlong2 v = reinterpret_cast<const longlong2 *>(pairs)[i];
-        a = v.x;
-        b = v.y;
+        if constexpr (NT) {
+            const StreamI64x2 v = __builtin_nontemporal_load(reinterpret_cast<const StreamI64x2 *>(pairs) + i);
+            a = v.x;
+            b = v.y;
+        } else {
+            const longlong2 v = reinterpret_cast<const longlong2 *>(pairs)[i];
+            a = v.x;
+            b = v.y;
+        }
+    }
+    __device__ __forceinline__ void load(long long i, long long &a, long long &b) const { load_as<false>(i, a, b); }
+    // with the hint where the field says so: the kernels that were measured with it (k_canopy_ilp; kernels_canopy.h: load_pair)
+    __device__ __forceinline__ void load_stream(long long i, long long &a, long long &b) const
+    {
+        if (nt) load_as<true>(i, a, b);
+        else load_as<false>(i, a, b);
     }
 };
 
@@ -36,13 +76,19 @@ struct SrcContig {
 // packed48: the narrower wire format of trees with fewer than 2^24 nodes -- 24 bits per id, 6 bytes per pair, three
 // 2-byte loads per lane (consecutive lanes read consecutive bytes; 0xFFFFFF stands for an id out of range, which the
 // host has already judged: host_copy.h::pack_pairs48).  One type for both formats (a wave-uniform branch), so that
-// no kernel is compiled twice for it.
+// no kernel is compiled twice for it.  (nt: the 8-byte form only; the packed form keeps its plain 2-byte loads.)
 struct SrcContig32 {
     const int *pairs;
     int packed48;
-    __device__ __forceinline__ void load(long long i, long long &a, long long &b) const
+    int nt;      // the streaming hint (above); sits in what was padding
+    // NT: the hinted load of the 8-byte form (the caller has checked that the source is not packed)
+    template <bool NT> __device__ __forceinline__ void load_as(long long i, long long &a, long long &b) const
     {
-        if (packed48) {
+        if constexpr (NT) {
+            const StreamI32x2 v = __builtin_nontemporal_load(reinterpret_cast<const StreamI32x2 *>(pairs) + i);
+            a = v.x;
+            b = v.y;
+        } else if (packed48) {
             const unsigned short *q = reinterpret_cast<const unsigned short *>(pairs) + 3 * i;
             const unsigned w0 = q[0], w1 = q[1], w2 = q[2];
             a = (long long)(w0 | ((w1 & 0xFFu) << 16));
@@ -52,6 +98,12 @@ struct SrcContig32 {
             a = v.x;
             b = v.y;
         }
+    }
+    __device__ __forceinline__ void load(long long i, long long &a, long long &b) const { load_as<false>(i, a, b); }
+    __device__ __forceinline__ void load_stream(long long i, long long &a, long long &b) const      // (see SrcContig)
+    {
+        if (nt && !packed48) load_as<true>(i, a, b);
+        else load_as<false>(i, a, b);
     }
 };
 
@@ -217,17 +269,43 @@ struct MrcaSink {
     __host__ __device__ bool any() const { return m32 != nullptr || m24 != nullptr; }
 };
 
+// Plain (NT = false) or hinted stores of one value (the under-aligned types: see the streaming hint above)
+template <bool NT> __device__ __forceinline__ void stream_store(int *p, int v)
+{
+    if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<StreamI32 *>(p));
+    else *p = v;
+}
+template <bool NT> __device__ __forceinline__ void stream_store(unsigned *p, unsigned v)
+{
+    if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<StreamU32 *>(p));
+    else *p = v;
+}
+template <bool NT> __device__ __forceinline__ void stream_store(float *p, float v)
+{
+    if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<StreamF32 *>(p));
+    else *p = v;
+}
+template <bool NT> __device__ __forceinline__ void stream_store(double *p, double v)
+{
+    if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<StreamF64 *>(p));
+    else *p = v;
+}
+
 // One id, from any lane in any control flow (scattered form): three byte stores in the packed format.
-__device__ __forceinline__ void store_mrca(const MrcaSink &out, long long i, int m)
+template <bool NT> __device__ __forceinline__ void store_mrca_as(const MrcaSink &out, long long i, int m)
 {
     if (out.m32) {
-        out.m32[i] = m;
+        stream_store<NT>(out.m32 + i, m);
     } else if (out.m24) {
         unsigned char *p = out.m24 + 3 * i;
         p[0] = (unsigned char)m;
         p[1] = (unsigned char)(m >> 8);
         p[2] = (unsigned char)(m >> 16);
     }
+}
+__device__ __forceinline__ void store_mrca(const MrcaSink &out, long long i, int m)
+{
+    store_mrca_as<false>(out, i, m);
 }
 
 // The ids of 64 consecutive pairs, one per lane: EVERY lane of the wave calls this in converged control flow with
@@ -236,25 +314,33 @@ __device__ __forceinline__ void store_mrca(const MrcaSink &out, long long i, int
 // quad's first three lanes -- a wave writes 192 consecutive bytes in aligned dwords, no byte stores (byte-masked
 // partial writes are what a link to host memory handles worst).  A dword's upper bytes belong to the next pair: if
 // that one is not live (the tail of a batch) or its id is not known yet (it follows by store_mrca) they are zero.
-__device__ __forceinline__ void store_mrca_wave(const MrcaSink &out, long long i, int m, bool live)
+template <bool NT> __device__ __forceinline__ void store_mrca_wave_as(const MrcaSink &out, long long i, int m, bool live)
 {
     if (out.m32) {
-        if (live) out.m32[i] = m;
+        if (live) stream_store<NT>(out.m32 + i, m);
     } else if (out.m24) {
         const unsigned v = live ? ((unsigned)m & 0xFFFFFFu) : 0u;
         const unsigned next = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xF9 /* quad_perm:[1,2,3,3] */, 0xF, 0xF, true);
         const unsigned p = (unsigned)i & 3u;
         if (live && p != 3u) {
             const unsigned w = (v >> (8u * p)) | (next << (24u - 8u * p));
-            reinterpret_cast<unsigned *>(out.m24)[(i >> 2) * 3 + p] = w;
+            stream_store<NT>(reinterpret_cast<unsigned *>(out.m24) + (i >> 2) * 3 + p, w);
         }
     }
 }
+__device__ __forceinline__ void store_mrca_wave(const MrcaSink &out, long long i, int m, bool live)
+{
+    store_mrca_wave_as<false>(out, i, m, live);
+}
 
+template <bool NT> __device__ __forceinline__ void store_dist_as(const DistSink &out_d, long long i, float d)
+{
+    if (out_d.d64) stream_store<NT>(out_d.d64 + i, (double)d);
+    else if (out_d.f32) stream_store<NT>(out_d.f32 + i, d);
+}
 __device__ __forceinline__ void store_dist(const DistSink &out_d, long long i, float d)
 {
-    if (out_d.d64) out_d.d64[i] = (double)d;
-    else if (out_d.f32) out_d.f32[i] = d;
+    store_dist_as<false>(out_d, i, d);
 }
 
 // scattered form (any lane, any control flow)
@@ -264,11 +350,16 @@ __device__ __forceinline__ void store_result(const DistSink &out_d, const MrcaSi
     store_mrca(out_m, i, m);
 }
 
-// converged form (see store_mrca_wave)
+// converged form (see store_mrca_wave); NT: with the streaming hint (k_canopy_ilp_heap)
+template <bool NT>
+__device__ __forceinline__ void store_result_wave_as(const DistSink &out_d, const MrcaSink &out_m, long long i, float d, int m, bool live)
+{
+    if (live) store_dist_as<NT>(out_d, i, d);
+    store_mrca_wave_as<NT>(out_m, i, m, live);
+}
 __device__ __forceinline__ void store_result_wave(const DistSink &out_d, const MrcaSink &out_m, long long i, float d, int m, bool live)
 {
-    if (live) store_dist(out_d, i, d);
-    store_mrca_wave(out_m, i, m, live);
+    store_result_wave_as<false>(out_d, out_m, i, d, m, live);
 }
 
 }  // namespace st

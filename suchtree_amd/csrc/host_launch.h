@@ -23,9 +23,8 @@ static int enqueue_src(st_tree *t, const Src &src, int64_t n, DistSink d_out, Mr
     // pair once and stores coalesced, so it may also work on pinned host memory)
     const bool ranks_only = !d_out.any() && d_mrca.any() && mrca_ranks_ready(t) && n >= kCanopyMinPairs;
     const bool canopy = ranks_only ||
-                        (t->strategy == ST_STRATEGY_CANOPY && n >= canopy_min_pairs(t) &&
-                         (allow_sorted || !(t->tile_sort && sorted_q(t) > 0) || sorted_zero_copy(t)) &&
-                         !prefers_walk_sorted(t, n, d_out.any()));
+                        (canopy_takes(t, n, d_out.any()) &&
+                         (allow_sorted || !(t->tile_sort && sorted_q(t) > 0) || sorted_zero_copy(t)));
     // Large batches of explicit pairs that the scalar ladder kernel would take, on a tree whose tile-sorted walk kernel is
     // ready as well: the batch itself decides (pair_math.h: probe_says_walk) -- both kernels are enqueued, every workgroup
     // of either samples the batch, the kernel the sample does not choose returns at once.  From kProbeMinPairs pairs: the empty
@@ -54,8 +53,10 @@ static int enqueue(st_tree *t, const int64_t *d_pairs, int64_t n, int64_t s0, in
                    DistSink d_out, MrcaSink d_mrca, hipStream_t stream)
 {
     const long long *p = reinterpret_cast<const long long *>(d_pairs);
+    // the caller's buffers: read once, written once (launch_policy.h: stream_hint_applies; a strided view has no hinted form)
+    const int nt = stream_hint_applies(t, n, d_out.any()) ? 1 : 0;
     if (s0 == 2 && s1 == 1 && (reinterpret_cast<uintptr_t>(d_pairs) & 15) == 0)
-        return enqueue_src(t, SrcContig{p}, n, d_out, d_mrca, t->d_fault, stream);
+        return enqueue_src(t, SrcContig{p, nt}, n, d_out, d_mrca, t->d_fault, stream);
     return enqueue_src(t, SrcStrided{p, (long long)s0, (long long)s1}, n, d_out, d_mrca, t->d_fault, stream);
 }
 

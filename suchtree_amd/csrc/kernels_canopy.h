@@ -340,6 +340,15 @@ __global__ __launch_bounds__(kCanopyBlock, (CAP == 15 ? 8 : 4)) void k_canopy_la
     }
 }
 
+
+// Pair i of an explicit source with the streaming hint where its field says so (device_common.h), of any other source as it comes
+template <typename Src>
+__device__ __forceinline__ void load_pair(const Src &src, long long i, long long &a, long long &b)
+{
+    if constexpr (std::is_same<Src, SrcContig>::value || std::is_same<Src, SrcContig32>::value) src.load_stream(i, a, b);
+    else src.load(i, a, b);
+}
+
 // The predicated kernel (shallow canopies; the headline): one pair per lane, ds_read_b64 per canopy entry (low word = dist
 // bits, high word = parent index).  All updates are predicated selects (a finished climb keeps re-reading its meeting
 // node), so nothing serialises behind a branch.  (PPL: pairs per lane, 1 -- two measured equal and were dropped in round 5,
@@ -378,7 +387,7 @@ __global__ __launch_bounds__(kCanopyBlock, ((CAP <= 7 && PPL == 1) ? 8 : 4)) voi
             const long long i = base + (long long)j * blockDim.x + threadIdx.x;
             live[j] = i < n;
             idx[j] = live[j] ? i : n - 1;
-            src.load(idx[j], ida[j], idb[j]);
+            load_pair(src, idx[j], ida[j], idb[j]);
         }
         bool any_bad = false;
 #pragma unroll
@@ -586,26 +595,20 @@ struct HeapSide {
     }
 };
 
-template <typename Src>
-__global__ __launch_bounds__(kCanopyBlock, 4) void k_canopy_ilp_heap(HeapParams P, Src src, long long n, DistSink out_d,
-                                                                     MrcaSink out_m, Fault *fault)
+// The kernel's loop over its pairs, NT: with the streaming hint on the pair load and the result stores (device_common.h).  The hint
+// is a run-time field, but this loop has no scalar register to spare for one more loop-invariant condition (the plain form sits at
+// the limit; tests/test_heap_kernel_resources.py), so the kernel tests it once and runs one of two copies of the loop.
+template <bool NT, typename Src>
+__device__ __forceinline__ void heap_pairs(const HeapParams &P, const Src &src, long long n, const DistSink &out_d, const MrcaSink &out_m,
+                                           Fault *fault, const float *H)
 {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    const float *H = reinterpret_cast<const float *>(lds_raw);
-    {      // stage the heap image: 16 bytes per lane per step, coalesced
-        const int n16 = (int)(heap_image_bytes(P.levels) / 16);
-        const uint4 *src16 = reinterpret_cast<const uint4 *>(P.dist);
-        uint4 *dst16 = reinterpret_cast<uint4 *>(lds_raw);
-        for (int k = threadIdx.x; k < n16; k += blockDim.x) dst16[k] = src16[k];
-        __syncthreads();
-    }
     const uint32_t first = 1u << (P.levels - kHeapLineEdges);      // heap index of slot block 0 at the lowest level of the image
     const float pad = __uint_as_float(kChainPad);
     for (long long base = (long long)blockIdx.x * blockDim.x; base < n; base += (long long)gridDim.x * blockDim.x) {
         const long long i = base + threadIdx.x;
         const bool live = i < n;
         long long ida, idb;
-        src.load(live ? i : n - 1, ida, idb);
+        src.template load_as<NT>(live ? i : n - 1, ida, idb);
         const bool valid = (unsigned long long)ida < (unsigned long long)P.n_nodes && (unsigned long long)idb < (unsigned long long)P.n_nodes;
         if (!valid && live) record_fault(fault, ida, idb, P.n_nodes);
         const bool leaves = valid && !((ida | idb) & 1);
@@ -639,7 +642,32 @@ __global__ __launch_bounds__(kCanopyBlock, 4) void k_canopy_ilp_heap(HeapParams 
             m = r.mrca;
         }
         // (converged: every lane of the workgroup is here, with consecutive pair numbers)
-        store_result_wave(out_d, out_m, i, valid ? s : __builtin_nanf(""), valid ? m : -1, live);
+        store_result_wave_as<NT>(out_d, out_m, i, valid ? s : __builtin_nanf(""), valid ? m : -1, live);
+    }
+}
+
+template <typename Src>
+__global__ __launch_bounds__(kCanopyBlock, 4) void k_canopy_ilp_heap(HeapParams P, Src src, long long n, DistSink out_d,
+                                                                     MrcaSink out_m, Fault *fault)
+{
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const float *H = reinterpret_cast<const float *>(lds_raw);
+    {      // stage the heap image: 16 bytes per lane per step, coalesced
+        const int n16 = (int)(heap_image_bytes(P.levels) / 16);
+        const uint4 *src16 = reinterpret_cast<const uint4 *>(P.dist);
+        uint4 *dst16 = reinterpret_cast<uint4 *>(lds_raw);
+        for (int k = threadIdx.x; k < n16; k += blockDim.x) dst16[k] = src16[k];
+        __syncthreads();
+    }
+    if constexpr (std::is_same<Src, SrcContig>::value) {
+        // the loop's entry test in front of the choice: neither copy then keeps the other's
+        if ((long long)blockIdx.x * blockDim.x >= n) return;
+        if (src.nt) heap_pairs<true>(P, src, n, out_d, out_m, fault, H);
+        else heap_pairs<false>(P, src, n, out_d, out_m, fault, H);
+    } else {
+        // the int32 source (the host path, never hinted by default) keeps the plain loop alone: with its format test in the loop a
+        // second copy does not fit the scalar registers
+        heap_pairs<false>(P, src, n, out_d, out_m, fault, H);
     }
 }
 

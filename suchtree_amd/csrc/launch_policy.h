@@ -134,14 +134,28 @@ static inline int64_t canopy_min_pairs(const st_tree *t)
 
 // The heap-line form of the predicated kernel (kernels_canopy.h: k_canopy_ilp_heap; perfect trees): explicit pair batches
 // with distances take it where the handle has both tables and option "heap_lines" admits it -- 1 (default): trees of
-// 2^18 leaves and more (below, rec_a4 and the cherry records gather from under 5 MiB and there is nothing to win), 2:
-// wherever it was built.
-constexpr int kHeapDefaultMinLevels = 18;
+// 2^17 leaves and more, 2: wherever it was built.  1e8 random leaf pairs, ms per launch, rec_a4 + cherry records / heap lines with
+// the streaming hint (profiles/stream_hint_r08.log): 2^16 leaves 1.50 / 1.60, 2^17 1.79 / 1.61, 2^18 1.97 / 1.62, 2^19 2.29 / 1.82.
+constexpr int kHeapDefaultMinLevels = 17;
 static inline bool heap_lines_applies(const st_tree *t)
 {
     return t->strategy == ST_STRATEGY_CANOPY && t->d_heap_lines && t->d_heap_dist &&
            (t->heap_lines == 2 || (t->heap_lines == 1 && t->heap_levels >= kHeapDefaultMinLevels));
 }
+
+// The streaming hint (device_common.h) of a batch of n explicit pairs that goes from and to the caller's device buffers
+// (st_distances_device*), option "stream_hint" -- 1 (default): the batches the heap-line kernel takes, whose 8 MiB of lines (2^20
+// leaves) share a 4 MiB L2 with the streams: pair loads and result stores; 2: also the pair loads of k_canopy_ilp on such batches and
+// on the host path's int32 pairs (8-byte form) -- the other kernels have no hinted form --; 0: never.  Never set where the next kernel on
+// the stream reads what this one wrote (host_compare.h: the compare, clade, row and rank paths build their own sources).  What the
+// default covers is what was measured to gain (LAB_NOTES.md, 2026-10-17; profiles/stream_hint_r08.log).
+static inline bool canopy_takes(const st_tree *t, int64_t n, bool want_dist);
+static inline bool stream_hint_applies(const st_tree *t, int64_t n, bool want_dist)
+{
+    if (t->stream_hint != 1) return t->stream_hint == 2;
+    return want_dist && heap_lines_applies(t) && canopy_takes(t, n, want_dist);
+}
+static inline bool stream_hint_host(const st_tree *t) { return t->stream_hint == 2; }
 
 static inline bool mrca_ranks_ready(const st_tree *t)
 {
@@ -164,6 +178,11 @@ static inline bool prefers_walk_sorted(const st_tree *t, int64_t n, bool want_di
     if (want_dist && ladder_applies(t, n)) return false;      // (large batches of a handle that measured the ladder kernel fastest)
     if (t->strategy != ST_STRATEGY_CANOPY || !t->prefer_walk_sorted || !want_dist || n < std::max<int64_t>(walk_sorted_min_pairs(t), 524288)) return false;
     return t->walk_ladder && t->d_crown_ladder && t->walk_crown && walk_sorted_ready(t);
+}
+// A batch in device memory goes to the canopy family (host_launch.h: enqueue_src)
+static inline bool canopy_takes(const st_tree *t, int64_t n, bool want_dist)
+{
+    return t->strategy == ST_STRATEGY_CANOPY && n >= canopy_min_pairs(t) && !prefers_walk_sorted(t, n, want_dist);
 }
 
 // The rule used when the candidates are not timed (SUCHTREE_AMD_AUTOTUNE=0): deep-canopy trees whose canopy image

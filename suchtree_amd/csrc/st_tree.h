@@ -45,7 +45,8 @@ struct st_tree {
     float *d_heap_lines = nullptr;        // heap lines and heap image of a perfect tree (tree_prep.h: prepare_heap_lines), else NULL
     float *d_heap_dist = nullptr;
     int32_t heap_levels = 0;  // D of that tree, else 0
-    int heap_lines = 1;       // tuning: 0 = never the heap-line form, 1 = on trees of 2^18 leaves and more, 2 = wherever the tables exist
+    int heap_lines = 1;       // tuning: 0 = never the heap-line form, 1 = on trees of 2^17 leaves and more, 2 = wherever the tables exist
+    int stream_hint = 1;      // tuning: pair and result streams carry the non-temporal hint (device_common.h) 0 = never, 1 = where launch_policy.h::stream_hint_applies says, 2 = wherever source and sinks support it
     int rec_a4 = 1;           // tuning: 0 = the predicated canopy kernel reads the 8-byte rec_a entries even when the four-byte form exists
     uint8_t *d_rec_p = nullptr;       // lineage sums (deep canopies with a sparse table), else NULL
     uint64_t *d_rmq64 = nullptr;

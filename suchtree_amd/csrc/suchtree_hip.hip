@@ -386,6 +386,7 @@ try {
     info->strategy = t->strategy;
     info->big_batch_kernel = big_batch_kernel_of(t);      // (follows the handle's current options)
     info->heap_lines = heap_lines_applies(t) ? 1 : 0;
+    info->stream_hint = stream_hint_applies(t, (int64_t)1 << 40, true) ? 1 : 0;      // (large explicit batches with distances)
     info->a_side_bytes = t->has_canopy ? ((info->heap_lines || (t->rec_a4 && t->d_rec_a4 && t->d_leaf_blocks)) ? 4 : 8) : 0;
     // (heap lines: both nodes of a pair gather from the one table of 8 bytes per leaf -- 4 + 4)
     info->b_table_bytes_per_leaf = info->heap_lines ? 4 : t->has_canopy ? ((t->rec_a4 && t->cherries && t->d_rec_c && t->d_leaf_blocks) ? t->rec_bytes / 4 : t->rec_bytes / 2) : 0;
@@ -464,6 +465,11 @@ static int set_option_one(st_tree *t, const char *name, int64_t value)
     if (std::strcmp(name, "heap_lines") == 0) {
         if (value < 0 || value > 2) return fail(ST_ERR_ARG, "heap_lines must be 0, 1 or 2");
         t->heap_lines = (int)value;
+        return ST_OK;
+    }
+    if (std::strcmp(name, "stream_hint") == 0) {
+        if (value < 0 || value > 2) return fail(ST_ERR_ARG, "stream_hint must be 0, 1 or 2");
+        t->stream_hint = (int)value;
         return ST_OK;
     }
     if (std::strcmp(name, "batch_probe") == 0) {
@@ -721,7 +727,7 @@ static int distances_host_impl(st_tree *t, const Id *pairs, int64_t n, int64_t s
         };
         auto launch = [&](PipeSlot &s, int64_t off, int64_t m) {
             return launch_chunk(r, s, off, m, wire48 ? 6 : 8, out,
-                                [wire48](const void *in) { return SrcContig32{static_cast<const int *>(in), wire48 ? 1 : 0}; });
+                                [wire48, r](const void *in) { return SrcContig32{static_cast<const int *>(in), wire48 ? 1 : 0, stream_hint_host(r) ? 1 : 0}; });
         };
         {   // (the pipe may not exist yet: ensure() inside run_pipe creates the streams)
             const hipError_t e = r->dp->pipe.ensure(std::max<int64_t>(seq.chunk, 1024));
