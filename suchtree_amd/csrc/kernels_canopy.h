@@ -563,18 +563,41 @@ constexpr int kHeapClimbMax = kHeapMaxLevels - kHeapLineEdges;      // ... and t
 
 typedef float __attribute__((ext_vector_type(4), aligned(4))) float4_align4;      // a 16-byte load at any dword
 
-// The six line values of one leaf slot (tree_prep.h: the layout of a heap line): two 16-byte loads, the window of the
-// slot's group of four leaves and the line's last four floats.
+// The six line values of one leaf slot (tree_prep.h: the layout of a heap line) out of two 16-byte loads, the window of the
+// slot's group of four leaves and the line's last four floats -- shared between lanes l and l ^ 1 (tree_prep.h:
+// heap_pair_offset): either gather instruction reads the window of one of the two slots on its own lane and the top of the same
+// slot on the lane beside it, so the L1 looks every line up once (a lane that read both had its second lookup behind those of
+// the 63 other lanes, and 0.18 requests per pair went out again for a tag replaced in between).  The loading lane picks the
+// neighbour's e3 and hands the three top values over by quad permutes: no LDS, and every lane of the wave must be active.
+__device__ __forceinline__ uint32_t heap_lane_swap(uint32_t v)      // lane l reads lane l ^ 1 (quad_perm:[1,0,3,2])
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);
+}
 struct HeapSide {
-    float4_align4 w;
-    float4 top;
-    uint32_t t;
-    __device__ __forceinline__ void load(const float *lines, uint32_t sl)
+    float4_align4 w;       // issue(): the loads of step 0 and 1; settle(): the slot's own window
+    float4_align4 top;     // issue(): ...; settle(): x, y, z = the slot's e3, e4, e5
+    uint32_t t, nb;
+    // odd: all ones on an odd lane, 0 on an even one
+    __device__ __forceinline__ void issue(const float *lines, uint32_t sl, uint32_t odd)
     {
-        const float *line = lines + (size_t)(sl >> 4) * 32;
         t = sl & 15u;
-        w = *reinterpret_cast<const float4_align4 *>(line + 7 * (t >> 2) + ((t & 2u) ? 3 : 0));
-        top = *reinterpret_cast<const float4 *>(line + 28);
+        nb = heap_lane_swap(sl);
+        w = *reinterpret_cast<const float4_align4 *>(lines + heap_pair_offset(0, odd, sl, nb));
+        top = *reinterpret_cast<const float4_align4 *>(lines + heap_pair_offset(1, odd, sl, nb));
+    }
+    __device__ __forceinline__ void settle(uint32_t odd)
+    {
+        const uint32_t m = heap_pair_window_mask(1, odd);      // set: step 1 read the own window and step 0 the neighbour's top
+        const uint32_t a0 = __float_as_uint(w.x), a1 = __float_as_uint(w.y), a2 = __float_as_uint(w.z), a3 = __float_as_uint(w.w);
+        const uint32_t b0 = __float_as_uint(top.x), b1 = __float_as_uint(top.y), b2 = __float_as_uint(top.z), b3 = __float_as_uint(top.w);
+        w.x = __uint_as_float(heap_pair_select(m, b0, a0));
+        w.y = __uint_as_float(heap_pair_select(m, b1, a1));
+        w.z = __uint_as_float(heap_pair_select(m, b2, a2));
+        w.w = __uint_as_float(heap_pair_select(m, b3, a3));
+        const uint32_t n0 = heap_pair_select(m, a0, b0), n3 = heap_pair_select(m, a3, b3);      // the neighbour's top
+        top.x = __uint_as_float(heap_lane_swap((nb & 8u) ? n3 : n0));
+        top.y = __uint_as_float(heap_lane_swap(heap_pair_select(m, a1, b1)));
+        top.z = __uint_as_float(heap_lane_swap(heap_pair_select(m, a2, b2)));
     }
     // s += the first k (at most six) of the leaf's edges, in order; every add predicated (kChainPad)
     __device__ __forceinline__ float add(float s, int k) const
@@ -582,13 +605,13 @@ struct HeapSide {
         const float pad = __uint_as_float(kChainPad);
         // (selects between pairs of components only: a select chain over all four components of one vector can become an
         // extract at a variable index, which the compiler keeps in scratch memory -- tests/test_heap_kernel_resources.py)
-        const float w0 = w.x, w1 = w.y, w2 = w.z, w3 = w.w, t0 = top.x, t3 = top.w;
+        const float w0 = w.x, w1 = w.y, w2 = w.z, w3 = w.w;
         const bool hi = (t & 2u) != 0, odd = (t & 1u) != 0;
         const float own_lo = odd ? w1 : w0, own_hi = odd ? w3 : w2;
         s += 0 < k ? (hi ? own_hi : own_lo) : pad;
         s += 1 < k ? (hi ? w1 : w2) : pad;
         s += 2 < k ? (hi ? w0 : w3) : pad;
-        s += 3 < k ? ((t & 8u) ? t3 : t0) : pad;
+        s += 3 < k ? top.x : pad;
         s += 4 < k ? top.y : pad;
         s += 5 < k ? top.z : pad;
         return s;
@@ -604,6 +627,7 @@ __device__ __forceinline__ void heap_pairs(const HeapParams &P, const Src &src, 
 {
     const uint32_t first = 1u << (P.levels - kHeapLineEdges);      // heap index of slot block 0 at the lowest level of the image
     const float pad = __uint_as_float(kChainPad);
+    const uint32_t odd = 0u - (threadIdx.x & 1u);      // the lane's parity as a mask (tree_prep.h: heap_pair_offset)
     for (long long base = (long long)blockIdx.x * blockDim.x; base < n; base += (long long)gridDim.x * blockDim.x) {
         const long long i = base + threadIdx.x;
         const bool live = i < n;
@@ -613,10 +637,10 @@ __device__ __forceinline__ void heap_pairs(const HeapParams &P, const Src &src, 
         if (!valid && live) record_fault(fault, ida, idb, P.n_nodes);
         const bool leaves = valid && !((ida | idb) & 1);
         const uint32_t sa = leaves ? (uint32_t)ida >> 1 : 0u, sb = leaves ? (uint32_t)idb >> 1 : 0u;
-        // every load of both lines before anything uses them
+        // every load of both lines before anything uses them (converged: the lane pairs exchange slots here ...)
         HeapSide A, B;
-        A.load(P.lines, sa);
-        B.load(P.lines, sb);
+        A.issue(P.lines, sa, odd);
+        B.issue(P.lines, sb, odd);
         // ... and the heap entries of both lineages: index (first + (slot >> 6)) >> q for the q-th edge above the line (a
         // climb that is over, or a level the tree does not have, reads an entry that is never added: entry 1 at the least)
         const uint32_t ua = first + (sa >> kHeapLineEdges), ub = first + (sb >> kHeapLineEdges);
@@ -629,6 +653,8 @@ __device__ __forceinline__ void heap_pairs(const HeapParams &P, const Src &src, 
         }
         const uint32_t x = sa ^ sb;
         const int k = x ? 32 - __clz((int)x) : 0;      // edges either side climbs
+        A.settle(odd);                                 // (... and top values here: before the branch of the internal nodes)
+        B.settle(odd);
         float s = A.add(0.0f, k);
 #pragma unroll
         for (int q = 0; q < kHeapClimbMax; q++) s += kHeapLineEdges + q < k ? ha[q] : pad;

@@ -135,7 +135,10 @@ static inline int64_t canopy_min_pairs(const st_tree *t)
 // The heap-line form of the predicated kernel (kernels_canopy.h: k_canopy_ilp_heap; perfect trees): explicit pair batches
 // with distances take it where the handle has both tables and option "heap_lines" admits it -- 1 (default): trees of
 // 2^17 leaves and more, 2: wherever it was built.  1e8 random leaf pairs, ms per launch, rec_a4 + cherry records / heap lines with
-// the streaming hint (profiles/stream_hint_r08.log): 2^16 leaves 1.50 / 1.60, 2^17 1.79 / 1.61, 2^18 1.97 / 1.62, 2^19 2.29 / 1.82.
+// the streaming hint (profiles/lane_pairs_r09.log): 2^16 leaves 1.50 / 1.39, 2^17 1.79 / 1.39, 2^18 1.96 / 1.40, 2^19 2.29 / 1.52
+// (before lanes l and l ^ 1 shared their line loads: 1.61 / 1.62 / 1.62 / 1.82).  2^16 is ahead with heap lines now; the default
+// stays at 17 until the tests that reach the general tables through a default 2^16-leaf handle (tests/test_gpu_parity.py,
+// tests/test_gpu_heap_lines.py) are moved with it (LAB_NOTES.md, 2026-10-17, lane pairs).
 constexpr int kHeapDefaultMinLevels = 17;
 static inline bool heap_lines_applies(const st_tree *t)
 {

@@ -262,6 +262,23 @@ bool prepare_cherries(TreeTables &T);
 constexpr int kHeapMinLevels = 6, kHeapMaxLevels = 20;
 bool prepare_heap_lines(TreeTables &T);
 
+// Where a leaf slot finds its six lowest edges in heap_lines, as float offsets from the table's base: the 16-byte window of
+// the slot's group of four leaves, and the last four floats of its line.
+ST_HD uint32_t heap_window_offset(uint32_t slot) { return (slot >> 4) * 32u + 7u * ((slot & 15u) >> 2) + ((slot & 2u) ? 3u : 0u); }
+ST_HD uint32_t heap_top_offset(uint32_t slot) { return (slot >> 4) * 32u + 28u; }
+// Lanes l and l ^ 1 of k_canopy_ilp_heap share their line loads: each of a side's two gather instructions (step 0, 1) reads
+// the window of one lane's slot and, on the lane beside it, the top of the SAME slot, so an instruction touches 32 lines,
+// each from two adjacent lanes, and no lane looks a line up twice.  Step 0 serves the even lane's slot, step 1 the odd
+// lane's.  odd: all ones on an odd lane, 0 on an even one (a mask, not a condition: the kernel has no scalar register pair
+// to spare for a loop-invariant one).  heap_pair_window_mask: all ones where the lane reads the window of its own slot in
+// that step, 0 where it reads the top of its neighbour's slot; heap_pair_select(m, x, y): x where m is set, else y.
+ST_HD uint32_t heap_pair_window_mask(int step, uint32_t odd) { return step ? odd : ~odd; }
+ST_HD uint32_t heap_pair_select(uint32_t m, uint32_t x, uint32_t y) { return (m & x) | (~m & y); }
+ST_HD uint32_t heap_pair_offset(int step, uint32_t odd, uint32_t own, uint32_t neighbour)
+{
+    return heap_pair_select(heap_pair_window_mask(step, odd), heap_window_offset(own), heap_top_offset(neighbour));
+}
+
 // rec_r and canopy_rmq64 (see TreeTables) for trees with a canopy and in-order ids; false otherwise.
 bool prepare_rank_table(TreeTables &T);
 
