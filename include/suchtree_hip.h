@@ -42,7 +42,8 @@ extern "C" {
  *      st_compare_rows_host; then, also additive, struct st_rank_sums, st_compare_triangle_ranks_host,
  *      st_compare_pairs_ranks_host and st_spearman_host; then st_tree_info.heap_lines appended (8 bytes) with option
  *      "heap_lines" -- callers built against the shorter struct keep using st_tree_info_get_sized; then, in the same way,
- *      st_tree_info.stream_hint appended (8 bytes) with option "stream_hint".
+ *      st_tree_info.stream_hint appended (8 bytes) with option "stream_hint"; then, also additive, struct st_quartet_table,
+ *      the ST_QUARTET_* constants, st_quartet_positions, st_compare_quartets_leaves_host and st_compare_quartets_host.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -460,6 +461,62 @@ int st_spearman_host(const float *x, const float *y, int64_t n, st_rank_sums *ou
 int st_quartets_host(st_tree *tree, const int64_t *quartets, int64_t n,
                      int64_t stride0, int64_t stride1,
                      int64_t *out_topologies, int64_t *bad_id);
+
+/*
+ * Compare two trees by quartet topology, counted on the GPU.  The quartets are generated on the device (or uploaded),
+ * classified in both trees by the MRCA kernels behind st_quartets_host, and counted: only the table leaves the device.
+ * Replaces, for the question "how many quartets do two trees resolve alike", two quartet_topologies_bulk calls
+ * (SuchTree/MuchTree.pyx:1271-1329) and a host-side comparison of their (n,4) results.  No counterpart in the reference.
+ *
+ * Class of a quartet (a,b,c,d) in one tree.  Take the six MRCA ids in the reference's order ab ac ad bc bd cd
+ * (MuchTree.pyx:1357-1362) and let `pick` be the first index whose id occurs exactly once among the six (the rule of
+ * _quartet_topologies, :1364-1372).  Class 0 is ab|cd (pick 0 or 5), class 1 ac|bd (pick 1 or 4), class 2 ad|bc (pick 2
+ * or 3); class 3 is "none unique", where the reference leaves j = 5 and reports ab|cd -- counted apart here.  Four
+ * distinct leaves never give class 3; repeated ids and internal nodes may.
+ *
+ * Result.  cell[i][j] counts the quartets of class i in tree_x and class j in tree_y; n is the sum of the cells.  The
+ * counts are integers accumulated with integer atomics: they do not depend on grid, chunking, device or order, and two
+ * calls over disjoint index ranges add cell by cell to the call over their union.
+ *
+ * ST_QUARTET_ALL: all quartets of m leaves.  Quartet k, 0 <= k < C(m,4), is the k-th 4-subset of positions
+ * p0 < p1 < p2 < p3 in colexicographic order: p3 is the largest p with C(p,4) <= k, then k -= C(p3,4); p2 the largest p
+ * with C(p,3) <= k, and so on down to p0.  The quartet is (ids[p0], ids[p1], ids[p2], ids[p3]).  4 <= m <= 65536, so
+ * that C(m,4) < 2^60; m < 4 is valid only with a count of 0.
+ *
+ * ST_QUARTET_SAMPLE: sampled quartets.  Quartet k depends on (seed, k, m) alone, so the first k quartets are the same
+ * for any sample size.  For j = 0..3, u_j = mix(seed + (4k + j + 1) * 0x9E3779B97F4A7C15 mod 2^64), mix the splitmix64
+ * finalizer (z ^= z>>30; z *= 0xBF58476D1CE4E5B9; z ^= z>>27; z *= 0x94D049BB133111EB; z ^= z>>31), and r_j = the high
+ * 64 bits of u_j * (m - j).  p_j starts as r_j; going through the positions already chosen in increasing order,
+ * p_j++ whenever p_j >= q.  The quartet is (ids[p_0], ..., ids[p_3]) in draw order: an ordered 4-tuple of distinct
+ * positions, uniform up to m * 2^-64.  4 <= m < 2^31 and k_begin + k_count <= 2^62; m < 4 only with a count of 0.
+ */
+#define ST_QUARTET_ALL     0
+#define ST_QUARTET_SAMPLE  1
+typedef struct st_quartet_table {
+    int64_t n;             /* quartets counted: the sum of the cells */
+    int64_t cell[4][4];    /* [class in tree_x][class in tree_y] */
+} st_quartet_table;
+
+/* The (k_count,4) int32 positions of quartets [k_begin, k_begin + k_count) of `mode`.  device = -1 computes them on the
+ * host (no GPU, no tree); device >= 0 runs the generator kernel of the compare path and copies its output back: the same
+ * values.  It states which quartets a sample held.  A bad mode, m or range is ST_ERR_ARG, as is a NULL out_pos with
+ * k_count > 0. */
+int st_quartet_positions(int device, int mode, uint64_t seed, int64_t m, int64_t k_begin, int64_t k_count, int32_t *out_pos);
+
+/* Generated quartets [k_begin, k_begin + k_count) over two aligned id lists: quartet positions (p0..p3) are evaluated as
+ * (ids_x[p0..p3]) in tree_x and (ids_y[p0..p3]) in tree_y.  The ids need not be leaves.  Conventions as for
+ * st_compare_triangle_host: both trees on one device (tree_x == tree_y allowed); every id is checked on the host before
+ * anything is launched (ST_ERR_BOUNDS with *bad_id, tree_x's ids first); an empty range gives a zero table and launches
+ * nothing.  chunk_quartets: quartets per device chunk, 0 = the default, else a positive value below 2^31 / 6; the result
+ * does not depend on it.  A bad mode, m, range or chunk is ST_ERR_ARG.  Device memory is bounded by the chunk -- two
+ * (c,4) int64 id arrays, two 6c int32 MRCA arrays, the table -- plus the two id lists. */
+int st_compare_quartets_leaves_host(st_tree *tree_x, st_tree *tree_y, const int64_t *ids_x, const int64_t *ids_y, int64_t m,
+                                    int mode, uint64_t seed, int64_t k_begin, int64_t k_count, int64_t chunk_quartets,
+                                    st_quartet_table *out, int64_t *bad_id);
+/* Explicit quartets: row i of the C-order int64 (n,4) array quartets_x in tree_x against row i of quartets_y in tree_y,
+ * uploaded chunk by chunk.  Otherwise as above. */
+int st_compare_quartets_host(st_tree *tree_x, st_tree *tree_y, const int64_t *quartets_x, const int64_t *quartets_y, int64_t n,
+                             int64_t chunk_quartets, st_quartet_table *out, int64_t *bad_id);
 
 /*
  * Dense graph matrices of SuchLinkedTrees: adjacency A (A[u][v] = A[v][u] = w per edge) and

@@ -44,6 +44,7 @@ SYMBOLS = (
     "st_host_depths", "st_link_sample_pairs", "st_bucket_moments", "st_device_malloc", "st_device_free", "st_memcpy_h2d", "st_memcpy_d2h",
     "st_device_synchronize", "st_compare_triangle_host", "st_compare_pairs_host", "st_clade_plan", "st_compare_clades_host",
     "st_compare_rows_host", "st_compare_triangle_ranks_host", "st_compare_pairs_ranks_host", "st_spearman_host",
+    "st_quartet_positions", "st_compare_quartets_leaves_host", "st_compare_quartets_host",
 )
 
 CLADE_RECT, CLADE_TRI = 0, 1     # include/suchtree_hip.h: ST_CLADE_RECT / ST_CLADE_TRI
@@ -86,6 +87,31 @@ class RankSums(ctypes.Structure):
     @property
     def syy(self):
         return (int(self.syy_hi) << 64) + int(self.syy_lo)
+
+
+QUARTET_MODE = {"all": 0, "sample": 1}      # include/suchtree_hip.h: ST_QUARTET_ALL / ST_QUARTET_SAMPLE
+QUARTET_MAX_LEAVES_ALL = 65536
+
+
+class QuartetTable(ctypes.Structure):
+    """st_quartet_table (include/suchtree_hip.h): cell[i][j] = quartets of class i in tree x and class j in tree y."""
+    _fields_ = [("n", ctypes.c_int64), ("cell", (ctypes.c_int64 * 4) * 4)]
+
+    def as_array(self):
+        return np.array([[int(v) for v in row] for row in self.cell], dtype=np.int64)
+
+
+def quartet_positions(mode, seed, m, k_begin, k_count, device=-1):
+    """st_quartet_positions: the int32 (k_count, 4) positions of quartets [k_begin, k_begin + k_count) of ``mode``
+    ("all" / "sample") among m leaves; ``device`` -1 = computed on the host (no GPU), else by the generator kernel."""
+    if mode not in QUARTET_MODE:
+        raise ValueError("mode must be 'all' or 'sample'")
+    if int(k_count) < 0:
+        raise ValueError("negative count")
+    out = np.empty((int(k_count), 4), dtype=np.int32)
+    check(load().st_quartet_positions(int(device), QUARTET_MODE[mode], int(seed) & 0xFFFFFFFFFFFFFFFF, int(m), int(k_begin),
+                                      int(k_count), _ptr(out) if len(out) else None))
+    return out
 
 
 def spearman_host(x, y):
@@ -262,6 +288,10 @@ def load():
         L.st_compare_pairs_ranks_host.argtypes = [vp, vp, vp, vp, i64, i64, ctypes.POINTER(PairMoments), ctypes.POINTER(RankSums),
                                                   ctypes.POINTER(i64)]
         L.st_spearman_host.argtypes = [vp, vp, i64, ctypes.POINTER(RankSums)]
+        L.st_quartet_positions.argtypes = [i32, i32, ctypes.c_uint64, i64, i64, i64, vp]
+        L.st_compare_quartets_leaves_host.argtypes = [vp, vp, vp, vp, i64, i32, ctypes.c_uint64, i64, i64, i64,
+                                                      ctypes.POINTER(QuartetTable), ctypes.POINTER(i64)]
+        L.st_compare_quartets_host.argtypes = [vp, vp, vp, vp, i64, i64, ctypes.POINTER(QuartetTable), ctypes.POINTER(i64)]
         L.st_clade_plan.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64),
                                     ctypes.POINTER(i64)]
         L.st_compare_clades_host.argtypes = [vp, vp, vp, i64, vp, vp, i64, i64, i64, vp, vp, ctypes.POINTER(i64)]
@@ -802,6 +832,46 @@ class DeviceTree:
                                                    n, int(chunk_pairs), ctypes.byref(out), ctypes.byref(ranks), ctypes.byref(bad))
         self._compare_check(other, rc, bad)
         return out, ranks
+
+    def compare_quartets_leaves_host(self, other, ids_x, ids_y, mode="all", seed=0, k_begin=0, k_count=None, chunk_quartets=0):
+        """The int64 (4, 4) table of quartet classes -- [class here][class in ``other``] -- of quartets
+        [k_begin, k_begin + k_count) generated on the GPU over the aligned id lists ``ids_x`` (this tree) and ``ids_y``
+        (``other``): ``mode`` "all" = the C(m,4) subsets in colexicographic order (k_count None: up to the last),
+        "sample" = quartet k drawn from (seed, k, m) (st_compare_quartets_leaves_host)."""
+        ids_x = np.ascontiguousarray(ids_x, dtype=np.int64)
+        ids_y = np.ascontiguousarray(ids_y, dtype=np.int64)
+        if ids_x.ndim != 1 or ids_x.shape != ids_y.shape:
+            raise ValueError("ids_x and ids_y must be 1-D arrays of equal length")
+        if mode not in QUARTET_MODE:
+            raise ValueError("mode must be 'all' or 'sample'")
+        m = int(ids_x.shape[0])
+        if k_count is None:
+            if mode != "all":
+                raise ValueError("a sample needs k_count")
+            if m > QUARTET_MAX_LEAVES_ALL:
+                raise ValueError("all quartets of %d leaves: at most %d leaves" % (m, QUARTET_MAX_LEAVES_ALL))
+            k_count = (m * (m - 1) * (m - 2) * (m - 3) // 24 if m >= 4 else 0) - int(k_begin)
+        out, bad = QuartetTable(), ctypes.c_int64(0)
+        rc = self._lib.st_compare_quartets_leaves_host(self.handle, other.handle, _ptr(ids_x) if m else None, _ptr(ids_y) if m else None,
+                                                       m, QUARTET_MODE[mode], int(seed) & 0xFFFFFFFFFFFFFFFF, int(k_begin), int(k_count),
+                                                       int(chunk_quartets), ctypes.byref(out), ctypes.byref(bad))
+        self._compare_check(other, rc, bad)
+        return out.as_array()
+
+    def compare_quartets_host(self, other, quartets_x, quartets_y, chunk_quartets=0):
+        """The same table over explicit quartets: row i of ``quartets_x`` (int64 (n,4)) in this tree against row i of
+        ``quartets_y`` in ``other`` (st_compare_quartets_host)."""
+        quartets_x = np.ascontiguousarray(quartets_x, dtype=np.int64)
+        quartets_y = np.ascontiguousarray(quartets_y, dtype=np.int64)
+        if quartets_x.ndim != 2 or quartets_x.shape[1:] != (4,) or quartets_x.shape != quartets_y.shape:
+            raise ValueError("quartets_x and quartets_y must be (n, 4) arrays of equal shape")
+        n = int(quartets_x.shape[0])
+        out, bad = QuartetTable(), ctypes.c_int64(0)
+        rc = self._lib.st_compare_quartets_host(self.handle, other.handle, _ptr(quartets_x) if n else None,
+                                                _ptr(quartets_y) if n else None, n, int(chunk_quartets), ctypes.byref(out),
+                                                ctypes.byref(bad))
+        self._compare_check(other, rc, bad)
+        return out.as_array()
 
     def compare_clades_host(self, other, parent, ids_x, ids_y, max_links=None, chunk_pairs=0):
         """st_compare_clades_host: one PairMoments-shaped record per node of ``other`` (the clade tree, whose int32

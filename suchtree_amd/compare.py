@@ -1,5 +1,6 @@
 """Comparing two trees' distances over the same pairs, reduced on the GPU (SuchTree.compare_distances,
-SuchLinkedTrees.linked_distances_summary; C ABI st_compare_triangle_host / st_compare_pairs_host).
+SuchLinkedTrees.linked_distances_summary; C ABI st_compare_triangle_host / st_compare_pairs_host), and their
+topologies over the same quartets, counted on the GPU (SuchTree.compare_quartets; st_compare_quartets_*_host).
 
 No counterpart in the reference: its comparison workflows (docs/examples/SuchTree_examples.md, "Comparing the
 topologies of two large trees"; SuchLinkedTrees.linked_distances, MuchTree.pyx:2900-2934) bring every distance back
@@ -12,7 +13,7 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["DistanceComparison", "CladeComparisons", "HommolaResult"]
+__all__ = ["DistanceComparison", "CladeComparisons", "HommolaResult", "QuartetComparison", "quartet_positions"]
 
 
 @dataclass(frozen=True)
@@ -336,3 +337,98 @@ def hommola_rows(u_a, u_b, pos_a, pos_b, permutations, seed, batch):
             ids_a[i] = u_a[rng.permutation(na)[pos_a]]
         done += k
         yield ids_a, ids_b
+
+
+QUARTET_MAX_ALL = 1 << 36      # SuchTree.compare_quartets(samples=None) enumerates at most this many quartets
+
+
+@dataclass(frozen=True)
+class QuartetComparison:
+    """How two trees resolve the same n quartets (SuchTree.compare_quartets).
+
+    ``table[i, j]`` (int64, 4 x 4) counts the quartets of class i in the first tree and class j in the second: class 0
+    is ab|cd, 1 ac|bd, 2 ad|bc of the quartet (a, b, c, d) and 3 "unresolved" -- no MRCA of its six pairs is unique,
+    which four distinct leaves never give (repeated ids and internal nodes may).  ``agree`` is the trace over classes
+    0..2, ``unresolved`` the sum of row and column 3, ``similarity`` = agree / n and ``distance`` = 1 - similarity: over
+    all quartets of a leaf set (``mode`` "all") the normalised quartet distance.  ``stderr`` = sqrt(s (1 - s) / n), the
+    binomial standard error of ``similarity`` for a sample (``mode`` "sample"), 0.0 for all quartets; for explicit
+    quartets (``mode`` "given") it is that of a sample, should the rows be one.  ``n_leaves`` is the length of the leaf
+    list (None for explicit quartets), ``seed`` the seed of a sample (None otherwise): quartet k of it is
+    ``quartet_positions(n_leaves, samples, seed)[k]``.  The counts are exact integers.
+    """
+
+    n: int
+    table: np.ndarray
+    n_leaves: Optional[int] = None
+    mode: str = "given"
+    seed: Optional[int] = None
+
+    def __post_init__(self):
+        t = np.asarray(self.table, dtype=np.int64)
+        if t.shape != (4, 4):
+            raise ValueError("table must be 4 x 4")
+        if int(t.sum()) != int(self.n):
+            raise ValueError("n must be the sum of the table")
+        if self.mode not in ("all", "sample", "given"):
+            raise ValueError("mode must be 'all', 'sample' or 'given'")
+        object.__setattr__(self, "table", t)
+        object.__setattr__(self, "n", int(self.n))
+
+    @classmethod
+    def from_table(cls, table, n_leaves=None, mode="given", seed=None):
+        table = np.asarray(table, dtype=np.int64)
+        return cls(n=int(table.sum()), table=table, n_leaves=n_leaves, mode=mode, seed=seed)
+
+    @property
+    def agree(self) -> int:
+        return int(self.table[0, 0] + self.table[1, 1] + self.table[2, 2])
+
+    @property
+    def unresolved(self) -> int:
+        return int(self.table[3, :].sum() + self.table[:3, 3].sum())
+
+    @property
+    def similarity(self) -> float:
+        return self.agree / self.n if self.n else float("nan")
+
+    @property
+    def distance(self) -> float:
+        return 1.0 - self.similarity
+
+    @property
+    def stderr(self) -> float:
+        if self.n == 0:
+            return float("nan")
+        if self.mode == "all":
+            return 0.0
+        s = self.similarity
+        return math.sqrt(s * (1.0 - s) / self.n)
+
+    @classmethod
+    def merge(cls, a: "QuartetComparison", b: "QuartetComparison") -> "QuartetComparison":
+        """Add the tables of two results over disjoint quartet ranges of the same question: the counts are integers, so
+        the sum is the table of the union whatever the split.  ``n_leaves``, ``mode`` and ``seed`` are kept where both
+        parts agree (else None, and mode "given")."""
+        return cls(n=a.n + b.n, table=a.table + b.table, n_leaves=a.n_leaves if a.n_leaves == b.n_leaves else None,
+                   mode=a.mode if a.mode == b.mode else "given", seed=a.seed if a.seed == b.seed else None)
+
+
+def quartet_positions(m, samples=None, seed=0, begin=0, count=None, device=None):
+    """The int32 (count, 4) leaf positions of the quartets SuchTree.compare_quartets compares over a list of ``m``
+    leaves: with ``samples=None`` quartets [begin, begin + count) of all C(m,4) in colexicographic order (count None: up
+    to the last), else quartets [begin, begin + count) of the sample drawn from ``seed`` (count None: up to ``samples``;
+    quartet k depends on (seed, k, m) alone).  ``device=None`` computes them on the host, without a GPU; a device index
+    runs the generator kernel there -- the same values."""
+    from . import _capi
+    m, begin = int(m), int(begin)
+    if samples is None:
+        mode = "all"
+        if count is None:
+            if m > _capi.QUARTET_MAX_LEAVES_ALL:
+                raise ValueError("all quartets of %d leaves: at most %d leaves; give samples=" % (m, _capi.QUARTET_MAX_LEAVES_ALL))
+            count = (math.comb(m, 4) if m >= 4 else 0) - begin
+    else:
+        mode = "sample"
+        if count is None:
+            count = int(samples) - begin
+    return _capi.quartet_positions(mode, 0 if samples is None else seed, m, begin, count, -1 if device is None else int(device))

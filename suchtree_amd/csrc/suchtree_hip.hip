@@ -33,6 +33,9 @@
 // host-only C++ beside tree_prep.cpp, compare_plan.cpp (argument checks, clade plan and tables, rows layout, the fold).
 // Exact Spearman rank sums of the same pairs (st_compare_*_ranks_host): kernels_ranks.h, the reducers at the end of
 // host_compare.h and, host-only, rank_plan.cpp (keys, bucket layout, tie arithmetic, st_spearman_host).
+// Two trees' quartet topologies, counted on the device (st_compare_quartets_*_host, st_quartet_positions):
+// kernels_quartets.h (generator, classify-and-count), host_quartets.h (the chunk driver) and, host-only,
+// quartet_plan.cpp (unranking, the draw, the class rule, argument checks).
 //
 // Host side of the C ABI: tree upload to one or several GPUs (tree_prep.cpp builds the tables, under a table budget
 // if one is given), the host path (host_pipe.h, host_copy.h: packed ids in through the copy engine, kernels write
@@ -139,6 +142,7 @@ private:
 #include "kernels_ranks.h"
 #include "kernels_clades.h"
 #include "kernels_rows.h"
+#include "kernels_quartets.h"
 
 
 // --------------------------------------------------------------------------
@@ -152,6 +156,7 @@ using namespace st;
 #include "host_tune.h"
 #include "host_upload.h"
 #include "host_compare.h"
+#include "host_quartets.h"
 
 extern "C" {
 
@@ -1324,6 +1329,61 @@ try {
     const int rc = end_host_faults(t, pipe.slot[0].stream, f);
     if (rc != ST_OK) return rc;
     return report_fault(t->n_nodes, f, bad_id);
+} ST_CATCH_ALL
+
+int st_quartet_positions(int device, int mode, uint64_t seed, int64_t m, int64_t k_begin, int64_t k_count, int32_t *out_pos)
+try {
+    std::string err;
+    const int rc = quartet_range_args(mode, m, k_begin, k_count, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (device < -1) return fail(ST_ERR_ARG, "device must be -1 (host) or a device index");
+    if (k_count > 0 && !out_pos) return fail(ST_ERR_ARG, "out_pos is NULL");
+    if (k_count == 0) return ST_OK;
+    if (device < 0) {
+        quartet_positions_host(mode, seed, m, k_begin, k_count, out_pos);
+        return ST_OK;
+    }
+    return quartet_positions_device(device, mode, seed, m, k_begin, k_count, out_pos);
+} ST_CATCH_ALL
+
+int st_compare_quartets_leaves_host(st_tree *tx, st_tree *ty, const int64_t *ids_x, const int64_t *ids_y, int64_t m, int mode,
+                                    uint64_t seed, int64_t k_begin, int64_t k_count, int64_t chunk_quartets, st_quartet_table *out,
+                                    int64_t *bad_id)
+try {
+    if (!out) return fail(ST_ERR_ARG, "out is NULL");
+    int rc = compare_trees_args(tx, ty);
+    if (rc != ST_OK) return rc;
+    std::string err;
+    rc = quartet_range_args(mode, m, k_begin, k_count, err);
+    if (rc == ST_OK) rc = quartet_chunk_arg(chunk_quartets, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (m > 0 && (!ids_x || !ids_y)) return fail(ST_ERR_ARG, "ids_x or ids_y is NULL");
+    *out = st_quartet_table{};
+    if (k_count == 0) return ST_OK;
+    rc = compare_check_ids(ids_x, m, tx->n_nodes, bad_id);
+    if (rc == ST_OK) rc = compare_check_ids(ids_y, m, ty->n_nodes, bad_id);
+    if (rc != ST_OK) return rc;
+    return quartet_leaves_run(tx, ty, ids_x, ids_y, m, mode, seed, k_begin, k_count, chunk_quartets > 0 ? chunk_quartets : kQuartetChunk, out,
+                              bad_id);
+} ST_CATCH_ALL
+
+int st_compare_quartets_host(st_tree *tx, st_tree *ty, const int64_t *quartets_x, const int64_t *quartets_y, int64_t n,
+                             int64_t chunk_quartets, st_quartet_table *out, int64_t *bad_id)
+try {
+    if (!out) return fail(ST_ERR_ARG, "out is NULL");
+    int rc = compare_trees_args(tx, ty);
+    if (rc != ST_OK) return rc;
+    if (n < 0) return fail(ST_ERR_ARG, "n < 0");
+    std::string err;
+    rc = quartet_chunk_arg(chunk_quartets, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (n > 0 && (!quartets_x || !quartets_y)) return fail(ST_ERR_ARG, "quartets_x or quartets_y is NULL");
+    *out = st_quartet_table{};
+    if (n == 0) return ST_OK;
+    rc = compare_check_ids(quartets_x, 4 * n, tx->n_nodes, bad_id);
+    if (rc == ST_OK) rc = compare_check_ids(quartets_y, 4 * n, ty->n_nodes, bad_id);
+    if (rc != ST_OK) return rc;
+    return quartet_given_run(tx, ty, quartets_x, quartets_y, n, chunk_quartets > 0 ? chunk_quartets : kQuartetChunk, out, bad_id);
 } ST_CATCH_ALL
 
 int st_graph_matrices_host(int device, int64_t n, int64_t n_edges, const int32_t *u, const int32_t *v,

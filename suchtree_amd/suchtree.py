@@ -9,6 +9,7 @@ bipartitions, RED) come from navigate.py.  All arithmetic happens in
 libsuchtree_hip.so on the GPU; nothing here computes a distance or an MRCA on
 the CPU, and a missing library or GPU raises ``HipBackendError``.
 """
+import math
 import os
 from itertools import chain
 from numbers import Integral
@@ -448,6 +449,72 @@ class SuchTree(TreeNavigation):
         return compare.run(lambda edges: dx.compare_triangle_host(dy, ids_x, ids_y, edges=edges), bins, range,
                            n_leaves=int(len(ids_x)),
                            rank_call=(lambda: dx.compare_triangle_ranks_host(dy, ids_x, ids_y)) if spearman else None)
+
+    def compare_quartets(self, other: "SuchTree", leaves=None, quartets=None, samples=None, seed=None):
+        """Compare this tree's topology with ``other``'s over the same quartets, counted on the GPU.
+
+        An extension: the reference has no counterpart.  It stands in for two ``quartet_topologies_bulk`` calls
+        (MuchTree.pyx:1271-1329) and a host-side comparison of their results: the quartets are generated on the GPU,
+        classified in both trees and counted there, and only a :class:`~suchtree_amd.compare.QuartetComparison` -- a
+        4 x 4 table of counts -- comes back.  A quartet's class in a tree is what ``quartet_topologies_bulk`` reports
+        for it: which of b, c, d ends up beside a.
+
+        ``leaves`` (as in :meth:`compare_distances`; exclusive with ``quartets``): None = every leaf name present in both
+        trees, a list of leaf names, or a tuple ``(ids_self, ids_other)`` of aligned node-id arrays.
+        ``samples=None`` compares all C(m,4) quartets of the m leaves (``distance`` is then the normalised quartet
+        distance): at most 2^36 of them and at most 65536 leaves, ValueError beyond -- give ``samples=``.
+        ``samples=n`` draws n quartets of distinct leaves, uniformly; quartet k depends on (seed, k, m) alone
+        (:func:`~suchtree_amd.compare.quartet_positions` returns them).  ``seed=None`` takes a seed from
+        ``numpy.random.default_rng()``; the result reports it.  Fewer than four leaves with ``samples > 0``: ValueError.
+        ``quartets``: a list of 4-tuples of leaf names, looked up in each tree, or a tuple of two aligned (n, 4)
+        node-id arrays (repeated ids and internal nodes are allowed: such rows may fall in class 3).
+        Both trees must be on the same GPU (ValueError otherwise); an id out of range raises InvalidNodeError.
+        """
+        from . import compare
+        if quartets is not None and (leaves is not None or samples is not None):
+            raise ValueError("quartets is exclusive with leaves and samples")
+        # (names and ids are resolved before either tree is touched on the GPU)
+        if quartets is not None:
+            if isinstance(quartets, tuple) and len(quartets) == 2 and all(isinstance(q, np.ndarray) for q in quartets):
+                qx, qy = (np.ascontiguousarray(q, dtype=np.int64) for q in quartets)
+            else:
+                if not isinstance(quartets, list):
+                    raise TypeError("quartets must be a list of 4-tuples of names or a tuple of two (n, 4) id arrays")
+                for i, q in enumerate(quartets):
+                    if len(q) != 4 or not all(isinstance(name, str) for name in q):
+                        raise TypeError("Quartet {i}: all four elements must be strings".format(i=str(i)))
+                flat = [name for q in quartets for name in q]
+                qx = self._name_ids(flat).reshape(-1, 4)
+                qy = other._name_ids(flat).reshape(-1, 4)
+            table = self._device_tree().compare_quartets_host(other._device_tree(), qx, qy)
+            return compare.QuartetComparison.from_table(table, mode="given")
+        if leaves is None:
+            _, ids_x, ids_y = self.shared_leaves(other)
+        elif isinstance(leaves, tuple) and len(leaves) == 2:
+            ids_x, ids_y = (np.ascontiguousarray(v, dtype=np.int64) for v in leaves)
+        else:
+            names = list(leaves)
+            ids_x, ids_y = self._name_ids(names), other._name_ids(names)
+        if ids_x.ndim != 1 or ids_x.shape != ids_y.shape:
+            raise ValueError("the two id lists must be 1-D and of equal length")
+        m = int(len(ids_x))
+        if samples is None:
+            total = math.comb(m, 4)
+            if m > _capi.QUARTET_MAX_LEAVES_ALL or total > compare.QUARTET_MAX_ALL:
+                raise ValueError("all quartets of %d leaves are %d, more than 2^36: draw a sample with samples=" % (m, total))
+            mode, count, seed = "all", total, None
+        else:
+            count = int(samples)
+            if count < 0:
+                raise ValueError("samples must not be negative")
+            if m < 4 and count > 0:
+                raise ValueError("a quartet needs four leaves, the list has %d" % m)
+            if seed is None:
+                seed = int(np.random.default_rng().integers(0, 1 << 63))
+            mode, seed = "sample", int(seed)
+        table = self._device_tree().compare_quartets_leaves_host(other._device_tree(), ids_x, ids_y, mode=mode, seed=seed or 0,
+                                                                 k_count=count)
+        return compare.QuartetComparison.from_table(table, n_leaves=m, mode=mode, seed=seed)
 
     def common_ancestor(self, a: Union[int, str], b: Union[int, str]) -> int:
         """Most recent common ancestor of two nodes (MuchTree.pyx:1128-1149)."""
