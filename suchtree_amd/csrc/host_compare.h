@@ -93,6 +93,53 @@ struct MomentsReduce {
     }
 };
 
+// What the two chunk drivers -- compare_run below, quartet_run in host_quartets.h -- share: both trees' pipe mutexes, one
+// stream, one device block, the two host fault words.  Declared after ST_DEVICE(...).  Both trees live on one device and
+// so share its staging pipe and that pipe's mutex (host_tree.h): one lock, also when tree_x == tree_y; distinct mutexes
+// (not possible today) are taken in address order.  `what` words the messages ("compare", "quartet compare").
+struct TwoTreeSession {
+    st_tree *tx, *ty;
+    const char *what;
+    std::unique_lock<std::mutex> lock_a, lock_b;
+    Stream s;
+    DevBuf<char> d;
+
+    TwoTreeSession(st_tree *x, st_tree *y, const char *w) : tx(x), ty(y), what(w)
+    {
+        std::mutex *ma = &tx->dp->m, *mb = &ty->dp->m;
+        if (mb < ma) std::swap(ma, mb);
+        lock_a = std::unique_lock<std::mutex>(*ma);
+        if (mb != ma) lock_b = std::unique_lock<std::mutex>(*mb);
+    }
+    // the block dies only once the stream has drained, the stream after the block, the locks last
+    ~TwoTreeSession()
+    {
+        if (s) (void)hipStreamSynchronize(s);
+        d.reset();
+        s.reset();
+    }
+    int hip_fail(const char *step, hipError_t e) const { return fail(ST_ERR_HIP, std::string(what) + step + hipGetErrorString(e)); }
+    // the stream and the block of `total` bytes
+    int open(size_t total)
+    {
+        hipError_t e = s.create();
+        if (e == hipSuccess) e = d.alloc(total);
+        return e == hipSuccess ? ST_OK : hip_fail(" setup: ", e);
+    }
+    // arms both fault words (behind what the caller has staged on the stream) ...
+    int arm() { return begin_host_faults(tx, s) != ST_OK || (ty != tx && begin_host_faults(ty, s) != ST_OK) ? ST_ERR_HIP : ST_OK; }
+    // ... and reads them back once the stream has drained: tree X's fault is reported first
+    int close(int64_t *bad_id)
+    {
+        Fault fx = kFaultInit, fy = kFaultInit;
+        int rc = end_host_faults(tx, s, fx);
+        if (rc == ST_OK && ty != tx) rc = end_host_faults(ty, s, fy);
+        if (rc == ST_OK) rc = report_fault(tx->n_nodes, fx, bad_id);      // (not expected: the ids were checked on the host)
+        if (rc == ST_OK) rc = report_fault(ty->n_nodes, fy, bad_id);
+        return rc;
+    }
+};
+
 // count pairs in chunks of `chunk`: prep(stream, off, c) stages what chunk [off, off + c) needs, src_x(off) / src_y(off)
 // are its pair sources in tree X / Y, `red` reduces the two chunks of distances (MomentsReduce, CladeReduce).  `extra`
 // device bytes are handed to `setup` once (the caller's ids or pairs).
@@ -101,54 +148,37 @@ static int compare_run(st_tree *tx, st_tree *ty, int64_t count, int64_t chunk, s
                        SrcY src_y, Reduce &red, int64_t *bad_id)
 {
     ST_DEVICE(tx->device);
-    // both trees live on one device and so share its staging pipe and that pipe's mutex (host_tree.h): one lock,
-    // also when tree_x == tree_y; distinct mutexes (not possible today) would be taken in address order
-    std::mutex *ma = &tx->dp->m, *mb = &ty->dp->m;
-    if (mb < ma) std::swap(ma, mb);
-    std::unique_lock<std::mutex> lock_a(*ma), lock_b;
-    if (mb != ma) lock_b = std::unique_lock<std::mutex>(*mb);
-
+    TwoTreeSession ses(tx, ty, "compare");
     chunk = std::min(chunk, count);
     // one device block: x | y | the reducer's | caller's data
     const size_t o_y = align256((size_t)chunk * 4), o_red = o_y + align256((size_t)chunk * 4);
     const size_t o_extra = o_red + align256(red.bytes(chunk)), total = o_extra + align256(extra);
-    char *d = nullptr;
-    hipStream_t s = nullptr;
-    auto cleanup = [&]() {
-        if (s) (void)hipStreamSynchronize(s);
-        (void)hipFree(d);
-        if (s) (void)hipStreamDestroy(s);
-    };
-    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d), total);
-    if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare setup: ") + hipGetErrorString(e)); }
+    int rc = ses.open(total);
+    if (rc != ST_OK) return rc;
+    char *const d = ses.d;
+    const hipStream_t s = ses.s;
     float *d_x = reinterpret_cast<float *>(d), *d_y = reinterpret_cast<float *>(d + o_y);
     char *d_extra = d + o_extra;
-    e = red.start(d + o_red, count, s);
+    hipError_t e = red.start(d + o_red, count, s);
     if (e == hipSuccess) e = setup(d_extra, s);
-    if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare setup: ") + hipGetErrorString(e)); }
-    if (begin_host_faults(tx, s) != ST_OK || (ty != tx && begin_host_faults(ty, s) != ST_OK)) { cleanup(); return ST_ERR_HIP; }
+    if (e != hipSuccess) return ses.hip_fail(" setup: ", e);
+    rc = ses.arm();
+    if (rc != ST_OK) return rc;
     for (int64_t off = 0; off < count; off += chunk) {
         const int64_t c = std::min(chunk, count - off);
         e = prep(d_extra, s, off, c);
-        if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare upload: ") + hipGetErrorString(e)); }
-        int rc = enqueue_src(tx, src_x(d_extra, off), c, DistSink{nullptr, d_x}, MrcaSink{nullptr, nullptr}, tx->d_fault_host, s);
+        if (e != hipSuccess) return ses.hip_fail(" upload: ", e);
+        rc = enqueue_src(tx, src_x(d_extra, off), c, DistSink{nullptr, d_x}, MrcaSink{nullptr, nullptr}, tx->d_fault_host, s);
         if (rc == ST_OK)
             rc = enqueue_src(ty, src_y(d_extra, off), c, DistSink{nullptr, d_y}, MrcaSink{nullptr, nullptr}, ty->d_fault_host, s);
-        if (rc != ST_OK) { const std::string msg = g_last_error; cleanup(); return fail(rc, msg); }
+        if (rc != ST_OK) return rc;
         e = red.chunk(d_x, d_y, off, c, s);
-        if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare launch: ") + hipGetErrorString(e)); }
+        if (e != hipSuccess) return ses.hip_fail(" launch: ", e);
     }
     e = red.finish(s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("compare read-back: ") + hipGetErrorString(e)); }
-    Fault fx = kFaultInit, fy = kFaultInit;
-    int rc = end_host_faults(tx, s, fx);
-    if (rc == ST_OK && ty != tx) rc = end_host_faults(ty, s, fy);
-    cleanup();
-    if (rc != ST_OK) return rc;
-    rc = report_fault(tx->n_nodes, fx, bad_id);      // (not expected: the ids were checked on the host)
-    if (rc == ST_OK) rc = report_fault(ty->n_nodes, fy, bad_id);
+    if (e != hipSuccess) return ses.hip_fail(" read-back: ", e);
+    rc = ses.close(bad_id);
     if (rc != ST_OK) return rc;
     return red.done();
 }
@@ -198,19 +228,13 @@ struct CladeReduce {
 struct RowsReduce {
     const RowsLayout &L;
     st_pair_moments *out;
-    CladePiece *d_pieces[2] = {nullptr, nullptr}, *h_pieces[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    CladePiece *d_pieces[2] = {nullptr, nullptr};      // (parts of compare_run's block)
+    PinnedBuf<CladePiece> h_pieces[2];
+    Event ev[2];
     int64_t first[2] = {0, 0}, count[2] = {0, 0};      // buffer i holds blocks [first, first + count); 0: nothing pending
     int next = 0;
 
     RowsReduce(const RowsLayout &l, st_pair_moments *o) : L(l), out(o) {}
-    ~RowsReduce()
-    {
-        for (int i = 0; i < 2; i++) {
-            if (h_pieces[i]) (void)hipHostFree(h_pieces[i]);
-            if (ev[i]) (void)hipEventDestroy(ev[i]);
-        }
-    }
     size_t piece_bytes() const { return align256((size_t)L.max_blocks * sizeof(CladePiece)); }
     size_t bytes(int64_t) { return 2 * piece_bytes(); }
     hipError_t start(char *d, int64_t, hipStream_t)
@@ -218,8 +242,8 @@ struct RowsReduce {
         hipError_t e = hipSuccess;
         for (int i = 0; i < 2 && e == hipSuccess; i++) {
             d_pieces[i] = reinterpret_cast<CladePiece *>(d + i * piece_bytes());
-            e = hipHostMalloc(reinterpret_cast<void **>(&h_pieces[i]), (size_t)L.max_blocks * sizeof(CladePiece), hipHostMallocDefault);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
+            e = h_pieces[i].alloc((size_t)L.max_blocks, hipHostMallocDefault);
+            if (e == hipSuccess) e = ev[i].create(hipEventDisableTiming);
         }
         return e;
     }
@@ -268,11 +292,11 @@ struct RowsReduce {
 
 // ---- exact Spearman rank sums (st_compare_*_ranks_host; kernels_ranks.h, rank_plan.h) ------------------------------
 // What the three passes share.  It outlives each pass's compare_run (which frees its own block), so the entry point
-// owns it: the destructor frees everything on every path out.
+// owns it: its members free everything on every path out.
 struct RankState {
-    char *d_small = nullptr;                 // occupancy | slots | miss | scan shares | scan results | dot slots | dot result
-    unsigned *d_tab[2] = {nullptr, nullptr};      // tree X's and tree Y's counters, then their a
-    unsigned long long *d_block_sum = nullptr;
+    DevBuf<char> d_small;                    // occupancy | slots | miss | scan shares | scan results | dot slots | dot result
+    DevBuf<unsigned> d_tab[2];                    // tree X's and tree Y's counters, then their a
+    DevBuf<unsigned long long> d_block_sum;
     RankSlots slots[2];
     int h_slots[2 * kRankBuckets];
     RankOccupancy occ;
@@ -289,7 +313,7 @@ struct RankState {
     static constexpr size_t o_dot_final = o_dot + sizeof(RankDotPart) * kRankBlocks;
     static constexpr size_t small_bytes = o_dot_final + 256;
 
-    RankOccupancy *d_occ() const { return reinterpret_cast<RankOccupancy *>(d_small); }
+    RankOccupancy *d_occ() const { return reinterpret_cast<RankOccupancy *>(d_small.get()); }
     int *d_slots() const { return reinterpret_cast<int *>(d_small + o_slots); }
     unsigned *d_miss() const { return reinterpret_cast<unsigned *>(d_small + o_miss); }
     RankScanPart *d_parts() const { return reinterpret_cast<RankScanPart *>(d_small + o_parts); }
@@ -298,17 +322,6 @@ struct RankState {
     RankDotPart *d_dot_final() const { return reinterpret_cast<RankDotPart *>(d_small + o_dot_final); }
     size_t tab_bytes(int t) const { return (size_t)slots[t].n_slots * (size_t)kRankBucketKeys * 4; }
     int64_t scan_blocks(int t) const { return (int64_t)slots[t].n_slots * (kRankBucketKeys / kRankScanBlock); }
-
-    RankState() = default;
-    RankState(const RankState &) = delete;
-    RankState &operator=(const RankState &) = delete;
-    ~RankState()
-    {
-        (void)hipFree(d_small);
-        (void)hipFree(d_tab[0]);
-        (void)hipFree(d_tab[1]);
-        (void)hipFree(d_block_sum);
-    }
 
     // between pass 0 and pass 1: the slots of the occupied buckets and the tables they need
     int tables()
@@ -321,14 +334,14 @@ struct RankState {
             if ((int64_t)seen != n) return fail(ST_ERR_HIP, "ranks: the occupancy pass saw " + std::to_string(seen) + " of " + std::to_string(n) + " values");
         }
         for (int t = 0; t < 2; t++) {
-            const hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_tab[t]), tab_bytes(t));
+            const hipError_t e = d_tab[t].alloc(tab_bytes(t) / 4);
             if (e != hipSuccess) {
                 (void)hipGetLastError();
                 return fail(ST_ERR_NOMEM, "ranks: the distances occupy " + std::to_string(slots[0].n_slots) + " + " + std::to_string(slots[1].n_slots) +
                                               " of " + std::to_string(kRankBuckets) + " key buckets, 4 MiB of counters each: " + hipGetErrorString(e));
             }
         }
-        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_block_sum), (size_t)std::max(scan_blocks(0), scan_blocks(1)) * 8);
+        const hipError_t e = d_block_sum.alloc((size_t)std::max(scan_blocks(0), scan_blocks(1)));
         if (e != hipSuccess) return fail(ST_ERR_NOMEM, std::string("ranks: ") + hipGetErrorString(e));
         return ST_OK;
     }
@@ -420,7 +433,7 @@ struct RankDotReduce {
     hipError_t chunk(const float *d_x, const float *d_y, int64_t off, int64_t c, hipStream_t s)
     {
         hipLaunchKernelGGL(k_rank_dot, dim3(kRankBlocks), dim3(kRankThreads), 0, s, d_x, d_y, (long long)c, R.d_slots(),
-                           reinterpret_cast<const int *>(R.d_tab[0]), reinterpret_cast<const int *>(R.d_tab[1]), off == 0 ? 1 : 0, R.d_dot(),
+                           reinterpret_cast<const int *>(R.d_tab[0].get()), reinterpret_cast<const int *>(R.d_tab[1].get()), off == 0 ? 1 : 0, R.d_dot(),
                            R.d_miss());
         return hipGetLastError();
     }
@@ -443,7 +456,7 @@ static int compare_ranks(st_tree *tx, int64_t n, int64_t chunk_pairs, Run run, s
     ST_DEVICE(tx->device);
     auto R = std::make_unique<RankState>();
     R->n = n;
-    const hipError_t e = hipMalloc(reinterpret_cast<void **>(&R->d_small), RankState::small_bytes);
+    const hipError_t e = R->d_small.alloc(RankState::small_bytes);
     if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("ranks setup: ") + hipGetErrorString(e));
     RankOccupancyReduce occupancy{MomentsReduce{nullptr, nullptr, 0, 0, out, nullptr}, *R};
     int rc = run((int64_t)0, occupancy);

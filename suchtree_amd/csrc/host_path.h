@@ -4,11 +4,11 @@
 #pragma once
 
 template <typename T>
-static int upload(T **dst, const std::vector<T> &src, int64_t *bytes)
+static int upload(DevBuf<T> &dst, const std::vector<T> &src, int64_t *bytes)
 {
     const size_t sz = std::max<size_t>(src.size() * sizeof(T), 16);
-    ST_HIP(hipMalloc(reinterpret_cast<void **>(dst), sz));
-    if (!src.empty()) ST_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    ST_HIP(dst.alloc((sz + sizeof(T) - 1) / sizeof(T)));      // (whole elements: sz itself wherever sizeof(T) divides 16)
+    if (!src.empty()) ST_HIP(hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
     *bytes += (int64_t)sz;
     return ST_OK;
 }
@@ -54,29 +54,25 @@ static int small_batch(st_tree *t, const Id *pairs, int64_t n, int64_t stride0, 
         // set up in locals and committed to the handle only when every step has succeeded: a partly
         // initialised mailbox (memory but no stream, no block counter) must never be launched on
         const size_t bytes = (size_t)kMailboxPairs * (16 + 8 + 4) + 64;     // + the completion word
-        void *host = nullptr, *dev = nullptr;
-        Fault *counter = nullptr;
-        hipStream_t stream = nullptr;
-        hipError_t e = hipHostMalloc(&host, bytes, hipHostMallocMapped);
+        PinnedBuf<char> host;
+        void *dev = nullptr;
+        DevBuf<Fault> counter;
+        Stream stream;
+        hipError_t e = host.alloc(bytes, hipHostMallocMapped);
         if (e == hipSuccess) e = hipHostGetDevicePointer(&dev, host, 0);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&counter), sizeof(Fault));      // [0]: block counter of the mailbox kernel
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+        if (e == hipSuccess) e = counter.alloc(1);      // [0]: block counter of the mailbox kernel
+        if (e == hipSuccess) e = stream.create();
         // cleared ON the mailbox stream: a hipMemset on the null stream is not ordered before
         // kernels of a non-blocking stream, and recycled device memory is not zero
         if (e == hipSuccess) e = hipMemsetAsync(counter, 0, sizeof(Fault), stream);
-        if (e != hipSuccess) {
-            if (stream) (void)hipStreamDestroy(stream);
-            if (counter) (void)hipFree(counter);
-            if (host) (void)hipHostFree(host);
-            return fail(ST_ERR_HIP, std::string("mailbox setup: ") + hipGetErrorString(e));
-        }
-        *reinterpret_cast<volatile unsigned *>(static_cast<char *>(host) + (size_t)kMailboxPairs * 28) = 0;
+        if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("mailbox setup: ") + hipGetErrorString(e));
+        *reinterpret_cast<volatile unsigned *>(host + (size_t)kMailboxPairs * 28) = 0;
         t->mb_dev = dev;
-        t->d_fault_mb = counter;
-        t->mb_stream = stream;
-        t->mb_host = host;
+        t->d_fault_mb = std::move(counter);
+        t->mb_stream = std::move(stream);
+        t->mb_host = std::move(host);
     }
-    int64_t *h_pairs = static_cast<int64_t *>(t->mb_host);
+    int64_t *h_pairs = reinterpret_cast<int64_t *>(t->mb_host.get());
     double *h_dist = reinterpret_cast<double *>(h_pairs + 2 * kMailboxPairs);
     int32_t *h_mrca = reinterpret_cast<int32_t *>(h_dist + kMailboxPairs);
     long long max_id = std::numeric_limits<long long>::min(), min_id = std::numeric_limits<long long>::max();
@@ -97,11 +93,11 @@ static int small_batch(st_tree *t, const Id *pairs, int64_t n, int64_t stride0, 
     double *d_dist = reinterpret_cast<double *>(d_base + (size_t)kMailboxPairs * 16);
     int32_t *d_mrca = reinterpret_cast<int32_t *>(d_base + (size_t)kMailboxPairs * 24);
     unsigned *d_done = reinterpret_cast<unsigned *>(d_base + (size_t)kMailboxPairs * 28);
-    volatile unsigned *h_done = reinterpret_cast<volatile unsigned *>(static_cast<char *>(t->mb_host) + (size_t)kMailboxPairs * 28);
+    volatile unsigned *h_done = reinterpret_cast<volatile unsigned *>(t->mb_host + (size_t)kMailboxPairs * 28);
     unsigned seq = ++t->mb_seq;
     if (seq == 0) seq = ++t->mb_seq;     // (0 is the word's initial value)
     ST_HIP(launch_walk_mailbox(t, reinterpret_cast<const long long *>(d_base), (int)n, out_dist ? d_dist : nullptr,
-                               out_mrca ? d_mrca : nullptr, reinterpret_cast<unsigned *>(t->d_fault_mb), d_done, seq, t->mb_stream));
+                               out_mrca ? d_mrca : nullptr, reinterpret_cast<unsigned *>(t->d_fault_mb.get()), d_done, seq, t->mb_stream));
     // poll the completion word (pinned host memory); if it does not show up within a few
     // milliseconds something is wrong: let the runtime report it
     {

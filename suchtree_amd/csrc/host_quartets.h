@@ -13,63 +13,47 @@ static int quartet_grid(int64_t n) { return (int)std::min<int64_t>((n + kQuartet
 
 // `count` quartets in chunks of `chunk`: setup(d_extra, stream) stages what every chunk needs in `extra` device bytes
 // (the id lists), prep(d_extra, d_qx, d_qy, stream, off, c) fills the two (c,4) id arrays of chunk [off, off + c).
-// Mirrors compare_run: one stream, one device block, both trees' pipe mutexes in address order, both fault words,
-// cleanup on every way out.
+// The locks, the stream, the device block and the fault words are compare_run's: TwoTreeSession (host_compare.h).
 template <typename Setup, typename Prep>
 static int quartet_run(st_tree *tx, st_tree *ty, int64_t count, int64_t chunk, size_t extra, Setup setup, Prep prep, st_quartet_table *out,
                        int64_t *bad_id)
 {
     ST_DEVICE(tx->device);
-    std::mutex *ma = &tx->dp->m, *mb = &ty->dp->m;
-    if (mb < ma) std::swap(ma, mb);
-    std::unique_lock<std::mutex> lock_a(*ma), lock_b;
-    if (mb != ma) lock_b = std::unique_lock<std::mutex>(*mb);
-
+    TwoTreeSession ses(tx, ty, "quartet compare");
     chunk = std::min(chunk, count);
     // one device block: quartets x | quartets y | MRCA ids x | MRCA ids y | table | caller's data
     const size_t q_bytes = align256((size_t)chunk * 32), m_bytes = align256((size_t)chunk * 24);
     const size_t o_qy = q_bytes, o_mx = 2 * q_bytes, o_my = o_mx + m_bytes, o_table = o_my + m_bytes, o_extra = o_table + 256;
     const size_t total = o_extra + align256(extra);
-    char *d = nullptr;
-    hipStream_t s = nullptr;
-    auto cleanup = [&]() {
-        if (s) (void)hipStreamSynchronize(s);
-        (void)hipFree(d);
-        if (s) (void)hipStreamDestroy(s);
-    };
-    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d), total);
-    if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("quartet compare setup: ") + hipGetErrorString(e)); }
+    int rc = ses.open(total);
+    if (rc != ST_OK) return rc;
+    char *const d = ses.d;
+    const hipStream_t s = ses.s;
     long long *d_qx = reinterpret_cast<long long *>(d), *d_qy = reinterpret_cast<long long *>(d + o_qy);
     int *d_mx = reinterpret_cast<int *>(d + o_mx), *d_my = reinterpret_cast<int *>(d + o_my);
     unsigned long long *d_table = reinterpret_cast<unsigned long long *>(d + o_table);
     char *d_extra = d + o_extra;
-    e = hipMemsetAsync(d_table, 0, 16 * sizeof(unsigned long long), s);
+    hipError_t e = hipMemsetAsync(d_table, 0, 16 * sizeof(unsigned long long), s);
     if (e == hipSuccess) e = setup(d_extra, s);
-    if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("quartet compare setup: ") + hipGetErrorString(e)); }
-    if (begin_host_faults(tx, s) != ST_OK || (ty != tx && begin_host_faults(ty, s) != ST_OK)) { cleanup(); return ST_ERR_HIP; }
+    if (e != hipSuccess) return ses.hip_fail(" setup: ", e);
+    rc = ses.arm();
+    if (rc != ST_OK) return rc;
     for (int64_t off = 0; off < count; off += chunk) {
         const int64_t c = std::min(chunk, count - off);
         e = prep(d_extra, d_qx, d_qy, s, off, c);
-        if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("quartet compare staging: ") + hipGetErrorString(e)); }
-        int rc = enqueue_src(tx, SrcQuartet{d_qx}, 6 * c, DistSink{nullptr, nullptr}, MrcaSink{d_mx, nullptr}, tx->d_fault_host, s);
+        if (e != hipSuccess) return ses.hip_fail(" staging: ", e);
+        rc = enqueue_src(tx, SrcQuartet{d_qx}, 6 * c, DistSink{nullptr, nullptr}, MrcaSink{d_mx, nullptr}, tx->d_fault_host, s);
         if (rc == ST_OK) rc = enqueue_src(ty, SrcQuartet{d_qy}, 6 * c, DistSink{nullptr, nullptr}, MrcaSink{d_my, nullptr}, ty->d_fault_host, s);
-        if (rc != ST_OK) { const std::string msg = g_last_error; cleanup(); return fail(rc, msg); }
+        if (rc != ST_OK) return rc;
         hipLaunchKernelGGL(k_quartet_agree, dim3(quartet_grid(c)), dim3(kQuartetThreads), 0, s, d_mx, d_my, (long long)c, d_table);
         e = hipGetLastError();
-        if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("quartet compare launch: ") + hipGetErrorString(e)); }
+        if (e != hipSuccess) return ses.hip_fail(" launch: ", e);
     }
     unsigned long long cells[16];
     e = hipMemcpyAsync(cells, d_table, sizeof cells, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("quartet compare read-back: ") + hipGetErrorString(e)); }
-    Fault fx = kFaultInit, fy = kFaultInit;
-    int rc = end_host_faults(tx, s, fx);
-    if (rc == ST_OK && ty != tx) rc = end_host_faults(ty, s, fy);
-    cleanup();
-    if (rc != ST_OK) return rc;
-    rc = report_fault(tx->n_nodes, fx, bad_id);      // (not expected: the ids were checked on the host)
-    if (rc == ST_OK) rc = report_fault(ty->n_nodes, fy, bad_id);
+    if (e != hipSuccess) return ses.hip_fail(" read-back: ", e);
+    rc = ses.close(bad_id);
     if (rc != ST_OK) return rc;
     out->n = 0;
     for (int i = 0; i < 16; i++) {
@@ -134,22 +118,17 @@ static int quartet_positions_device(int device, int mode, uint64_t seed, int64_t
     if (device >= n_dev) return fail(ST_ERR_ARG, "device " + std::to_string(device) + " of " + std::to_string(n_dev));
     ST_DEVICE(device);
     const int64_t chunk = std::min(k_count, kQuartetChunk);
-    int *d_pos = nullptr;
-    hipStream_t s = nullptr;
-    auto cleanup = [&]() {
-        if (s) (void)hipStreamSynchronize(s);
-        (void)hipFree(d_pos);
-        if (s) (void)hipStreamDestroy(s);
-    };
-    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_pos), (size_t)chunk * 16);
+    Stream s;      // (dies after the buffer)
+    DevBuf<int> d_pos;
+    hipError_t e = s.create();
+    if (e == hipSuccess) e = d_pos.alloc((size_t)chunk * 4);
     for (int64_t off = 0; off < k_count && e == hipSuccess; off += chunk) {
         const int64_t c = std::min(chunk, k_count - off);
         e = quartet_draw_any(mode, nullptr, nullptr, seed, m, k_begin + off, c, nullptr, nullptr, d_pos, s);
         if (e == hipSuccess) e = hipMemcpyAsync(out_pos + 4 * off, d_pos, (size_t)c * 16, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);      // (the buffer is reused by the next chunk)
     }
-    cleanup();
+    if (s) (void)hipStreamSynchronize(s);      // (an error may have left the draw kernel running: the buffer dies behind it)
     if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("quartet positions: ") + hipGetErrorString(e));
     return ST_OK;
 }

@@ -156,19 +156,15 @@ static void tune_deep_tree(st_tree *t, const TreeTables &T, const char *device_n
         if ((size_t)n * 28 > free_b / 8) n >>= 2;
         if ((size_t)n * 28 + leaves.size() * 4 > free_b / 2) return;
     }
-    int32_t *d_leaves = nullptr;
-    long long *d_pairs = nullptr;
-    double *d_dist = nullptr;
-    int32_t *d_mrca = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    DevBuf<int32_t> d_leaves, d_mrca;
+    DevBuf<long long> d_pairs;
+    DevBuf<double> d_dist;
+    Stream stream;
+    Event e0, e1;
     const std::string keep = g_last_error;
-    bool ok = hipMalloc(reinterpret_cast<void **>(&d_leaves), leaves.size() * 4) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void **>(&d_pairs), (size_t)n * 16) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void **>(&d_dist), (size_t)n * 8) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void **>(&d_mrca), (size_t)n * 4) == hipSuccess &&
-              hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess &&
-              hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess &&
+    bool ok = d_leaves.alloc(leaves.size()) == hipSuccess && d_pairs.alloc((size_t)n * 2) == hipSuccess &&
+              d_dist.alloc((size_t)n) == hipSuccess && d_mrca.alloc((size_t)n) == hipSuccess && stream.create() == hipSuccess &&
+              e0.create() == hipSuccess && e1.create() == hipSuccess &&
               hipMemcpyAsync(d_leaves, leaves.data(), leaves.size() * 4, hipMemcpyHostToDevice, stream) == hipSuccess;
     if (ok) {      // the sample is drawn on the device (k_sample_leaf_pairs, kernels_misc.h)
         hipLaunchKernelGGL(k_sample_leaf_pairs, dim3(1024), dim3(256), 0, stream, d_leaves, (unsigned)leaves.size(), d_pairs, (long long)n);
@@ -280,12 +276,5 @@ static void tune_deep_tree(st_tree *t, const TreeTables &T, const char *device_n
     }
     t->batch_probe = keep_probe;
     (void)hipGetLastError();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (stream) (void)hipStreamDestroy(stream);
-    (void)hipFree(d_leaves);
-    (void)hipFree(d_pairs);
-    (void)hipFree(d_dist);
-    (void)hipFree(d_mrca);
     g_last_error = keep;
 }

@@ -236,9 +236,9 @@ static int build_tables(const int32_t *parent, const float *distance, int64_t n_
 // free right now), left out -- pointer NULL, kernels use the form without it -- otherwise, and also
 // when its allocation or copy fails.  Never an error.
 template <typename P, typename V>
-static bool upload_optional(P **dst, const V &v, int64_t *bytes)
+static bool upload_optional(DevBuf<P> &dst, const V &v, int64_t *bytes)
 {
-    *dst = nullptr;
+    dst.reset();
     if (v.empty()) return false;
     size_t free_b = 0, total_b = 0;
     const size_t need = v.size() * sizeof(v[0]);
@@ -248,8 +248,7 @@ static bool upload_optional(P **dst, const V &v, int64_t *bytes)
     }
     const std::string keep = g_last_error;
     if (upload(dst, v, bytes) != ST_OK) {
-        if (*dst) (void)hipFree(*dst);
-        *dst = nullptr;
+        dst.reset();
         (void)hipGetLastError();
         g_last_error = keep;
         return false;
@@ -294,23 +293,22 @@ static int upload_tree(BuiltTables &B, int device, st_tree **out, bool tune = tr
     t->n_nodes = T.n;
     t->n_leaves = T.n_leaves;
     int64_t bytes = 0;
-    int rc = upload(&t->d_nodes, T.nodes, &bytes);
-    if (rc == ST_OK) rc = upload(&t->d_depth, T.depth, &bytes);
-    if (rc == ST_OK) rc = upload(&t->d_stride, T.stride, &bytes);
-    if (rc == ST_OK) (void)upload_optional(&t->d_tree_rmq, T.tree_rmq, &bytes);
+    int rc = upload(t->d_nodes, T.nodes, &bytes);
+    if (rc == ST_OK) rc = upload(t->d_depth, T.depth, &bytes);
+    if (rc == ST_OK) rc = upload(t->d_stride, T.stride, &bytes);
+    if (rc == ST_OK) (void)upload_optional(t->d_tree_rmq, T.tree_rmq, &bytes);
     // lineage tables of the walk family: {node_rec, sums} or nothing; lengths and the crown's table are further options
     auto upload_walk_lineage = [&]() {
         if (T.lineage_node_rec.empty() || T.lineage_sum.empty()) return;
-        if (!upload_optional(&t->d_lineage_node_rec, T.lineage_node_rec, &bytes)) return;
-        if (!t->d_lineage && !upload_optional(&t->d_lineage, T.lineage_sum, &bytes)) {
-            (void)hipFree(t->d_lineage_node_rec);
-            t->d_lineage_node_rec = nullptr;
+        if (!upload_optional(t->d_lineage_node_rec, T.lineage_node_rec, &bytes)) return;
+        if (!t->d_lineage && !upload_optional(t->d_lineage, T.lineage_sum, &bytes)) {
+            t->d_lineage_node_rec.reset();
             return;
         }
-        (void)upload_optional(&t->d_lineage_len, T.lineage_len, &bytes);
-        if (upload_optional(&t->d_crown_rmq, T.crown_rmq, &bytes)) {
+        (void)upload_optional(t->d_lineage_len, T.lineage_len, &bytes);
+        if (upload_optional(t->d_crown_rmq, T.crown_rmq, &bytes)) {
             t->crown_nodes = T.crown_nodes;
-            (void)upload_optional(&t->d_crown_ladder, T.crown_ladder, &bytes);
+            (void)upload_optional(t->d_crown_ladder, T.crown_ladder, &bytes);
         }
     };
     if (rc == ST_OK && !B.canopy_ok) upload_walk_lineage();
@@ -323,68 +321,65 @@ static int upload_tree(BuiltTables &B, int device, st_tree **out, bool tune = tr
         for (const CanopyEntry &e : T.canopy) t->canopy_depth = std::max<int>(t->canopy_depth, (int)(e.link >> 16));
         std::vector<CanopyEntry> image = T.canopy;
         if (image.size() & 1) image.push_back(CanopyEntry{0.0f, 0u});   // 16-byte staging granule
-        rc = upload(&t->d_canopy, image, &bytes);
-        if (rc == ST_OK) rc = upload(&t->d_canopy_id, T.canopy_id, &bytes);
-        if (rc == ST_OK) rc = upload(&t->d_ladder, T.ladder, &bytes);
+        rc = upload(t->d_canopy, image, &bytes);
+        if (rc == ST_OK) rc = upload(t->d_canopy_id, T.canopy_id, &bytes);
+        if (rc == ST_OK) rc = upload(t->d_ladder, T.ladder, &bytes);
         if (rc == ST_OK) {
             std::vector<uint16_t> cd = T.canopy_depth;
             cd.resize((cd.size() + 7) / 8 * 8, 0);     // 16-byte staging granule
-            rc = upload(&t->d_cdepth, cd, &bytes);
+            rc = upload(t->d_cdepth, cd, &bytes);
         }
         if (rc == ST_OK && B.deep && T.inorder_ids && !T.canopy_rmq.empty()) {
-            rc = upload(&t->d_cpos, T.canopy_pos, &bytes);
-            if (rc == ST_OK) rc = upload(&t->d_rmq, T.canopy_rmq, &bytes);
+            rc = upload(t->d_cpos, T.canopy_pos, &bytes);
+            if (rc == ST_OK) rc = upload(t->d_rmq, T.canopy_rmq, &bytes);
         }
-        if (rc == ST_OK) rc = upload(&t->d_rec_a, T.rec_a, &bytes);
+        if (rc == ST_OK) rc = upload(t->d_rec_a, T.rec_a, &bytes);
         if (rc == ST_OK && !T.rec_a4.empty() &&
             canopy_lds_bytes(t) + leaf_block_image_bytes((int)T.leaf_block_portal.size()) <= 160 * 1024) {
             std::vector<uint16_t> blocks = T.leaf_block_portal;
             blocks.resize(leaf_block_image_bytes((int)blocks.size()) / 2, 0xFFFFu);     // 16-byte staging granule
-            if (upload_optional(&t->d_rec_a4, T.rec_a4, &bytes)) {
-                if (upload_optional(&t->d_leaf_blocks, blocks, &bytes)) {
+            if (upload_optional(t->d_rec_a4, T.rec_a4, &bytes)) {
+                if (upload_optional(t->d_leaf_blocks, blocks, &bytes)) {
                     t->leaf_block_shift = T.leaf_block_shift;
                     t->leaf_block_count = (int32_t)T.leaf_block_portal.size();
                     // cherry records: the block table carries their bits, so without the table on the device they must go too
-                    if (!T.rec_c.empty() && !upload_optional(&t->d_rec_c, T.rec_c, &bytes)) {
+                    if (!T.rec_c.empty() && !upload_optional(t->d_rec_c, T.rec_c, &bytes)) {
                         for (uint16_t &e : blocks)
                             if (e != kLeafBlockMixed) e &= (uint16_t)~kLeafBlockCherries;
                         (void)hipMemcpy(t->d_leaf_blocks, blocks.data(), blocks.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
                     }
                 } else {
-                    (void)hipFree(t->d_rec_a4);
-                    t->d_rec_a4 = nullptr;
+                    t->d_rec_a4.reset();
                 }
             }
         }
         if (rc == ST_OK && !T.heap_lines.empty()) {      // (optional: without either table the form is not used)
             std::vector<float> image = T.heap_dist;
             image.resize(heap_image_bytes(T.heap_levels) / 4, 0.0f);      // 16-byte staging granule
-            if (upload_optional(&t->d_heap_lines, T.heap_lines, &bytes)) {
-                if (upload_optional(&t->d_heap_dist, image, &bytes)) {
+            if (upload_optional(t->d_heap_lines, T.heap_lines, &bytes)) {
+                if (upload_optional(t->d_heap_dist, image, &bytes)) {
                     t->heap_levels = T.heap_levels;
                 } else {
-                    (void)hipFree(t->d_heap_lines);
-                    t->d_heap_lines = nullptr;
+                    t->d_heap_lines.reset();
                 }
             }
         }
-        if (rc == ST_OK) rc = upload(&t->d_rec_b, T.rec_b, &bytes);
-        if (rc == ST_OK && !T.rec_i.empty()) rc = upload(&t->d_rec_i, T.rec_i, &bytes);      // (empty: left out under a table budget)
+        if (rc == ST_OK) rc = upload(t->d_rec_b, T.rec_b, &bytes);
+        if (rc == ST_OK && !T.rec_i.empty()) rc = upload(t->d_rec_i, T.rec_i, &bytes);      // (empty: left out under a table budget)
         if (rc == ST_OK && !T.rec_r.empty()) {
             // the MRCA-only kernel needs the rank alone: 2 bytes per node, so that the leaves' half of the
             // table (2 MB for 2^20 leaves) stays in an XCD's L2 (4-byte entries: 4.4e10 ids/s)
             std::vector<uint16_t> ranks(T.rec_r.size());
             for (size_t k = 0; k < ranks.size(); k++) ranks[k] = (uint16_t)(T.rec_r[k] & 0xFFFFu);
-            rc = upload(&t->d_rec_r, ranks, &bytes);
-            if (rc == ST_OK) rc = upload(&t->d_rmq64, T.canopy_rmq64, &bytes);
+            rc = upload(t->d_rec_r, ranks, &bytes);
+            if (rc == ST_OK) rc = upload(t->d_rmq64, T.canopy_rmq64, &bytes);
         }
         if (rc == ST_OK && T.rec_p.empty() && !T.lineage_sum.empty()) {
             upload_walk_lineage();      // (lineage tables in the walk family's own form only: build_walk_only_tables)
         } else if (rc == ST_OK && t->d_rmq && t->d_rmq64 && !T.lineage_sum.empty()) {
-            if (upload_optional(&t->d_rec_p, T.rec_p, &bytes)) {
-                if (!upload_optional(&t->d_lineage, T.lineage_sum, &bytes)) {
-                    (void)hipFree(t->d_rec_p);
-                    t->d_rec_p = nullptr;
+            if (upload_optional(t->d_rec_p, T.rec_p, &bytes)) {
+                if (!upload_optional(t->d_lineage, T.lineage_sum, &bytes)) {
+                    t->d_rec_p.reset();
                 } else {
                     upload_walk_lineage();      // (the walk family's view of the same sums)
                 }
@@ -392,32 +387,23 @@ static int upload_tree(BuiltTables &B, int device, st_tree **out, bool tune = tr
         }
     }
     if (rc == ST_OK) {
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&t->d_fault), 2 * sizeof(Fault));
+        hipError_t e = t->d_fault.alloc(2);
         const Fault init2[2] = {kFaultInit, kFaultInit};
         if (e == hipSuccess) e = hipMemcpy(t->d_fault, init2, sizeof(init2), hipMemcpyHostToDevice);
         if (e != hipSuccess) rc = fail(ST_ERR_HIP, std::string("tree setup: ") + hipGetErrorString(e));
         else t->d_fault_host = t->d_fault + 1;
     }
     if (rc == ST_OK && B.canopy_ok && !T.ladder.empty()) {      // work counters of the scalar ladder kernel (optional: static deal without)
-        if (hipMalloc(reinterpret_cast<void **>(&t->d_work), (size_t)kWorkSlots * 64 * sizeof(unsigned long long)) != hipSuccess) {
+        if (t->d_work.alloc((size_t)kWorkSlots * 64) != hipSuccess) {
             (void)hipGetLastError();
-            t->d_work = nullptr;
         } else {
             bytes += (int64_t)kWorkSlots * 64 * 8;
             for (unsigned k = 0; k < kWorkSlots; k++) {      // (an event that cannot be created leaves the static deal: launch_canopy.hip)
-                if (hipEventCreateWithFlags(&t->work_done[k], hipEventDisableTiming) != hipSuccess) {
-                    (void)hipGetLastError();
-                    t->work_done[k] = nullptr;
-                }
+                if (t->work_done[k].create(hipEventDisableTiming) != hipSuccess) (void)hipGetLastError();
             }
             // words of the batch probe (host_launch.h::enqueue_src): optional as well
-            const bool ok = t->d_rec_r && hipMalloc(reinterpret_cast<void **>(&t->d_choice), kWorkSlots * sizeof(int)) == hipSuccess;
-            if (!ok) {
-                (void)hipGetLastError();
-                t->d_choice = nullptr;
-            } else {
-                bytes += (int64_t)kWorkSlots * 4;
-            }
+            if (t->d_rec_r && t->d_choice.alloc(kWorkSlots) == hipSuccess) bytes += (int64_t)kWorkSlots * 4;
+            else (void)hipGetLastError();
         }
     }
     if (rc != ST_OK) return rc;      // (owner destroys t and keeps the message)

@@ -25,11 +25,12 @@
 // Four translation units (compiled in parallel, build.py): launch_walk.hip (kernels_walk.h), launch_canopy.hip
 // (kernels_canopy.h), launch_canopy_sorted.hip (kernels_canopy_sorted.h) -- each a kernel family with its launch
 // functions, exported through launch_decl.h -- and this file: error plumbing, the C ABI and the host side in
-// between: st_tree.h / host_tree.h (handle, pipe registry), launch_policy.h + host_launch.h (which family a
-// request gets, enqueueing, faults), host_path.h (host-buffer pipeline, mailbox, copy kernels), host_upload.h
-// (tables -> device), kernels_misc.h (k nearest, graph matrices), and the compare paths (st_compare_*: two trees'
-// distances over the same pairs, reduced on the device): kernels_compare.h / kernels_clades.h / kernels_rows.h (moments
-// and 2-D histogram, clade pieces, row blocks), host_compare.h (the chunk driver compare_run and its reducers) and,
+// between: st_tree.h / host_tree.h (handle, pipe registry), device_res.h (the owners of device and pinned memory, streams
+// and events that the handle and the host calls hold), launch_policy.h + host_launch.h (which family a request gets,
+// enqueueing, faults), host_path.h (host-buffer pipeline, mailbox, copy kernels), host_upload.h (tables -> device),
+// kernels_misc.h (k nearest, graph matrices), and the compare paths (st_compare_*: two trees' distances over the same
+// pairs, reduced on the device): kernels_compare.h / kernels_clades.h / kernels_rows.h (moments and 2-D histogram, clade
+// pieces, row blocks), host_compare.h (TwoTreeSession, the chunk driver compare_run and its reducers) and,
 // host-only C++ beside tree_prep.cpp, compare_plan.cpp (argument checks, clade plan and tables, rows layout, the fold).
 // Exact Spearman rank sums of the same pairs (st_compare_*_ranks_host): kernels_ranks.h, the reducers at the end of
 // host_compare.h and, host-only, rank_plan.cpp (keys, bucket layout, tie arithmetic, st_spearman_host).
@@ -342,46 +343,13 @@ void st_tree_destroy(st_tree *t)
     if (!t) return;
     for (st_tree *p : t->peers) st_tree_destroy(p);
     t->peers.clear();
+    const int device = t->device;
+    const bool has_pipe = t->dp != nullptr;
     {
-        DeviceScope scope(t->device);
-        (void)hipFree(t->d_nodes);
-        (void)hipFree(t->d_depth);
-        (void)hipFree(t->d_stride);
-        (void)hipFree(t->d_tree_rmq);
-        (void)hipFree(t->d_canopy);
-        (void)hipFree(t->d_canopy_id);
-        (void)hipFree(t->d_ladder);
-        (void)hipFree(t->d_cdepth);
-        (void)hipFree(t->d_cpos);
-        (void)hipFree(t->d_rmq);
-        (void)hipFree(t->d_rec_a);
-        (void)hipFree(t->d_rec_a4);
-        (void)hipFree(t->d_leaf_blocks);
-        (void)hipFree(t->d_rec_c);
-        (void)hipFree(t->d_heap_lines);
-        (void)hipFree(t->d_heap_dist);
-        (void)hipFree(t->d_rec_b);
-        (void)hipFree(t->d_rec_i);
-        (void)hipFree(t->d_rec_p);
-        (void)hipFree(t->d_rmq64);
-        (void)hipFree(t->d_rec_r);
-        (void)hipFree(t->d_lineage);
-        (void)hipFree(t->d_lineage_len);
-        (void)hipFree(t->d_lineage_node_rec);
-        (void)hipFree(t->d_crown_rmq);
-        (void)hipFree(t->d_crown_ladder);
-        (void)hipFree(t->d_fault);
-        (void)hipFree(t->d_work);
-        for (hipEvent_t ev : t->work_done)
-            if (ev) (void)hipEventDestroy(ev);
-        (void)hipFree(t->d_choice);
-        (void)hipFree(t->q_tmp);
-        if (t->mb_host) (void)hipHostFree(t->mb_host);
-        (void)hipFree(t->d_fault_mb);
-        if (t->mb_stream) (void)hipStreamDestroy(t->mb_stream);
+        DeviceScope scope(device);      // (the handle's owners release their memory, events and stream on its device)
+        delete t;
     }
-    if (t->dp) pipe_release(t->device);
-    delete t;
+    if (has_pipe) pipe_release(device);
 }
 
 int st_tree_info_get(const st_tree *t, st_tree_info *info)
@@ -903,39 +871,36 @@ try {
     std::lock_guard<std::mutex> lock(t->dp->m);
     // rows per launch: the distance block (float32, device only) stays under 256 MiB
     const int64_t rows_per_block = std::max<int64_t>(1, std::min<int64_t>(n_queries, ((int64_t)1 << 26) / n_cands));
-    long long *d_q = nullptr, *d_c = nullptr, *d_oi = nullptr;
-    float *d_tmp = nullptr;
-    double *d_od = nullptr;
-    hipStream_t stream = nullptr;
-    auto cleanup = [&]() {
-        (void)hipFree(d_q); (void)hipFree(d_c); (void)hipFree(d_oi); (void)hipFree(d_tmp); (void)hipFree(d_od);
-        if (stream) (void)hipStreamDestroy(stream);
-    };
-    hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_q), (size_t)n_queries * 8);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_c), (size_t)n_cands * 8);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_tmp), (size_t)rows_per_block * (size_t)n_cands * 4);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_oi), (size_t)n_queries * k * 8);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_od), (size_t)n_queries * k * 8);
+    // (the buffers die before the stream; a way out that may leave kernels on it drains it first)
+    Stream stream;
+    DevBuf<long long> d_q, d_c, d_oi;
+    DevBuf<float> d_tmp;
+    DevBuf<double> d_od;
+    hipError_t e = stream.create();
+    if (e == hipSuccess) e = d_q.alloc((size_t)n_queries);
+    if (e == hipSuccess) e = d_c.alloc((size_t)n_cands);
+    if (e == hipSuccess) e = d_tmp.alloc((size_t)rows_per_block * (size_t)n_cands);
+    if (e == hipSuccess) e = d_oi.alloc((size_t)n_queries * k);
+    if (e == hipSuccess) e = d_od.alloc((size_t)n_queries * k);
     if (e == hipSuccess) e = hipMemcpyAsync(d_q, queries, (size_t)n_queries * 8, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_c, cands, (size_t)n_cands * 8, hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) { cleanup(); return fail(ST_ERR_HIP, std::string("knn setup: ") + hipGetErrorString(e)); }
-    if (begin_host_faults(t, stream) != ST_OK) { cleanup(); return ST_ERR_HIP; }
+    if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("knn setup: ") + hipGetErrorString(e));
+    if (begin_host_faults(t, stream) != ST_OK) return ST_ERR_HIP;
     for (int64_t r0 = 0; r0 < n_queries; r0 += rows_per_block) {
         const int64_t rows = std::min(rows_per_block, n_queries - r0);
         const SrcGrid src{d_q + r0, d_c, (long long)n_cands, 0, 0};
         const int rc = enqueue_src(t, src, rows * n_cands, DistSink{nullptr, d_tmp}, MrcaSink{nullptr, nullptr}, t->d_fault_host, stream);
-        if (rc != ST_OK) { (void)hipStreamSynchronize(stream); cleanup(); return rc; }
+        if (rc != ST_OK) { (void)hipStreamSynchronize(stream); return rc; }
         hipLaunchKernelGGL(k_knn_select, dim3((unsigned)rows), dim3(256), 0, stream, d_tmp, (long long)n_cands,
                            d_q + r0, d_c, skip_self, k, d_oi + r0 * k, d_od + r0 * k);
         e = hipGetLastError();
-        if (e != hipSuccess) { (void)hipStreamSynchronize(stream); cleanup(); return fail(ST_ERR_HIP, std::string("knn launch: ") + hipGetErrorString(e)); }
+        if (e != hipSuccess) { (void)hipStreamSynchronize(stream); return fail(ST_ERR_HIP, std::string("knn launch: ") + hipGetErrorString(e)); }
     }
     e = hipMemcpyAsync(out_index, d_oi, (size_t)n_queries * k * 8, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out_dist, d_od, (size_t)n_queries * k * 8, hipMemcpyDeviceToHost, stream);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(stream); return fail(ST_ERR_HIP, std::string("knn D2H: ") + hipGetErrorString(e)); }
     Fault f = kFaultInit;
-    int rc = e == hipSuccess ? end_host_faults(t, stream, f) : fail(ST_ERR_HIP, std::string("knn D2H: ") + hipGetErrorString(e));
-    cleanup();
+    const int rc = end_host_faults(t, stream, f);
     if (rc != ST_OK) return rc;
     return report_fault(t->n_nodes, f, bad_id);
 } ST_CATCH_ALL
@@ -1264,10 +1229,8 @@ try {
     if (begin_host_faults(t, pipe.slot[0].stream) != ST_OK) return ST_ERR_HIP;
     const bool canopy = t->strategy == ST_STRATEGY_CANOPY && 6 * chunk >= canopy_min_pairs(t);
     if (canopy && t->q_tmp_cap < kPipeSlots * chunk) {      // six MRCA ids per quartet, per slot
-        (void)hipFree(t->q_tmp);
-        t->q_tmp = nullptr;
         t->q_tmp_cap = 0;
-        ST_HIP(hipMalloc(&t->q_tmp, (size_t)kPipeSlots * (size_t)chunk * 24));
+        ST_HIP(t->q_tmp.alloc((size_t)kPipeSlots * (size_t)chunk * 6));
         t->q_tmp_cap = kPipeSlots * chunk;
     }
     auto out_of = [&](PipeSlot &s) { return reinterpret_cast<int64_t *>(static_cast<char *>(s.h_in) + (size_t)chunk * 32); };
@@ -1303,7 +1266,7 @@ try {
         if (e != hipSuccess) return bail(ST_ERR_HIP, std::string("quartet pipeline: ") + hipGetErrorString(e));
         if (canopy && 6 * m >= canopy_min_pairs(t)) {
             // six MRCA ids per quartet out of the canopy / rank-table kernels, then the pick
-            int32_t *tmp = static_cast<int32_t *>(t->q_tmp) + (size_t)slot_index * (size_t)chunk * 6;
+            int32_t *tmp = t->q_tmp + (size_t)slot_index * (size_t)chunk * 6;
             const int rc = enqueue_src(t, SrcQuartet{static_cast<const long long *>(s.d_in)}, 6 * m,
                                        DistSink{nullptr, nullptr}, MrcaSink{tmp, nullptr}, t->d_fault_host, s.stream);
             if (rc != ST_OK) return bail(rc, g_last_error);
@@ -1409,7 +1372,7 @@ try {
                                       std::to_string(need >> 20) + " MiB of device memory, " + std::to_string(free_b >> 20) + " MiB free");
     // one grow-only workspace per device, kept between calls (a 422 x 422 Laplacian is all
     // allocation time otherwise); calls on one device take turns
-    struct Workspace { std::mutex m; char *p = nullptr; size_t cap = 0; };
+    struct Workspace { std::mutex m; DevBuf<char> p; size_t cap = 0; };      // (never deleted: no HIP call from a static destructor)
     static std::mutex ws_map_mutex;
     static std::map<int, Workspace *> ws_map;
     Workspace *W;
@@ -1421,10 +1384,8 @@ try {
     }
     std::lock_guard<std::mutex> ws_lock(W->m);
     if (W->cap < need) {
-        (void)hipFree(W->p);
-        W->p = nullptr;
         W->cap = 0;
-        ST_HIP(hipMalloc(reinterpret_cast<void **>(&W->p), need));
+        ST_HIP(W->p.alloc(need));
         W->cap = need;
     }
     char *ws = W->p;
@@ -1454,8 +1415,7 @@ try {
     if (e == hipSuccess && out_adjacency) e = hipMemcpy(out_adjacency, d_A, mat, hipMemcpyDeviceToHost);
     if (e == hipSuccess && out_laplacian) e = hipMemcpy(out_laplacian, d_L, mat, hipMemcpyDeviceToHost);
     if (W->cap > ((size_t)256 << 20)) {     // do not sit on a multi-GB workspace
-        (void)hipFree(W->p);
-        W->p = nullptr;
+        W->p.reset();
         W->cap = 0;
     }
     if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("graph matrices: ") + hipGetErrorString(e));
