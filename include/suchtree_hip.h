@@ -43,7 +43,9 @@ extern "C" {
  *      st_compare_pairs_ranks_host and st_spearman_host; then st_tree_info.heap_lines appended (8 bytes) with option
  *      "heap_lines" -- callers built against the shorter struct keep using st_tree_info_get_sized; then, in the same way,
  *      st_tree_info.stream_hint appended (8 bytes) with option "stream_hint"; then, also additive, struct st_quartet_table,
- *      the ST_QUARTET_* constants, st_quartet_positions, st_compare_quartets_leaves_host and st_compare_quartets_host.
+ *      the ST_QUARTET_* constants, st_quartet_positions, st_compare_quartets_leaves_host and st_compare_quartets_host; then, also
+ *      additive, struct st_kendall_counts, ST_KENDALL_TILE, st_compare_triangle_kendall_host, st_compare_pairs_kendall_host,
+ *      st_kendall_arrays_host and st_kendall_host.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -451,6 +453,43 @@ int st_compare_pairs_ranks_host(st_tree *tree_x, st_tree *tree_y, const int64_t 
                                 int64_t chunk_pairs, st_pair_moments *out, st_rank_sums *out_ranks, int64_t *bad_id);
 /* Host only, no GPU: the same keys, midranks and tie arithmetic over two plain arrays of n values. */
 int st_spearman_host(const float *x, const float *y, int64_t n, st_rank_sums *out);
+
+/*
+ * Exact Kendall's tau-b of the same pairs (scipy.stats.kendalltau(x, y), variant "b", nan_policy "propagate"), from
+ * integer counts over the call's n pairs of float32 distances.  With n0 = n (n - 1) / 2:
+ *   ties_x     = sum over the tie groups of x of t (t - 1) / 2 (equal values tie, -0.0 ties with +0.0; infinities are
+ *                ordinary values), ties_y likewise, ties_xy over the groups equal in both x and y,
+ *   discordant = the number of {i, j} with (x_i - x_j)(y_i - y_j) < 0,
+ *   concordant = n0 - ties_x - ties_y + ties_xy - discordant,
+ *   tau        = (concordant - discordant) / sqrt((n0 - ties_x)(n0 - ties_y)): NaN when a factor is 0, when n < 2 or when
+ *                n_nan > 0 -- then every count is 0, as in st_rank_sums.
+ * Every count is an integer below 2^61 (n <= 2^31 - 1: more is ST_ERR_ARG and launches nothing): none depends on
+ * reduction order, grid, chunk size or device, so two calls, or a call and st_kendall_host on the same values, agree
+ * exactly.
+ *
+ * The pairs are kept and sorted on the device: one pass of the distance kernels writes each pair's 64-bit key (the
+ * order-preserving key of x above that of y) -- out receives the same st_pair_moments, bit for bit, as
+ * st_compare_*_host without a histogram -- then a merge sort by (x, y) (tiles of ST_KENDALL_TILE keys in LDS, then
+ * merge-path levels), the x and joint tie sums from runs of the sorted keys, a second merge sort of the low words that
+ * counts inversions (= discordant), and ties_y from its result.  Device memory: 16 bytes per pair beside the chunk (ml.tree
+ * vs nj.tree, all 1,475,684,301 pairs: 24 GB; at the limit 34 GB); an allocation that fails is ST_ERR_NOMEM and says how
+ * many bytes were asked for.  chunk_pairs, pairs, orientation, id checks and error codes: as for st_compare_*_ranks_host.
+ * No counterpart in the reference, whose docs call scipy.stats.kendalltau on a host-side sample of the pairs.
+ */
+#define ST_KENDALL_TILE 2048   /* keys a workgroup sorts in LDS and a merge level's workgroup writes */
+typedef struct st_kendall_counts {
+    int64_t  n, n_nan;                 /* pairs counted; pairs with a NaN on either side (then everything below is 0) */
+    uint64_t discordant, ties_x, ties_y, ties_xy;
+} st_kendall_counts;
+int st_compare_triangle_kendall_host(st_tree *tree_x, st_tree *tree_y, const int64_t *ids_x, const int64_t *ids_y, int64_t m,
+                                     int64_t k_begin, int64_t k_count, int64_t chunk_pairs,
+                                     st_pair_moments *out, st_kendall_counts *out_counts, int64_t *bad_id);
+int st_compare_pairs_kendall_host(st_tree *tree_x, st_tree *tree_y, const int64_t *pairs_x, const int64_t *pairs_y, int64_t n,
+                                  int64_t chunk_pairs, st_pair_moments *out, st_kendall_counts *out_counts, int64_t *bad_id);
+/* The counts of two plain float32 arrays of n values: both are uploaded to `device` and go through the same kernels. */
+int st_kendall_arrays_host(int device, const float *x, const float *y, int64_t n, st_kendall_counts *out);
+/* Host only, no GPU: the same keys, tie rule and counts. */
+int st_kendall_host(const float *x, const float *y, int64_t n, st_kendall_counts *out);
 
 /*
  * Quartet topologies: for each row (a,b,c,d) of the int64 (n,4) view the row re-ordered so

@@ -21,6 +21,17 @@ With --spearman it measures the exact Spearman rank correlation of the same pair
   kernels                                           under rocprofv3: summed time of the distance kernels and of each
                                                     rank kernel (occupancy, count, scan, dot) of one ranks call
 
+With --kendall it measures exact Kendall's tau-b (compare_distances(kendall=True): one pass over the pairs that keeps
+every pair's 64-bit key, then two merge sorts and three tie scans on the device) at 1e7 pairs, 1e8 pairs and all pairs,
+and writes the result, one JSON line and a readable table, to --log (default profiles/kendall_tau_r12.log):
+
+  kendall_s                     the Kendall call, wall (best of --reps), with tau and the exact counts
+  moments_s                     yardstick 1: one moments-only call over the same pairs -- the distance pass it contains
+  spearman_s                    yardstick 2: a spearman=True call over the same pairs
+  scipy_fetch_s / scipy_tau_s   yardstick 3, at 1e7 pairs: both distance columns fetched to the host (triangle_host), then
+                                scipy.stats.kendalltau on them
+  kernels                       under rocprofv3: the summed time of each kernel kind of one Kendall call per size
+
 Reads the committed fixtures under tests/golden only.
 """
 import argparse
@@ -125,6 +136,89 @@ def profile_spearman():
     return kinds
 
 
+KENDALL_SIZES = (10 ** 7, 10 ** 8, None)      # pairs of the triangle over all shared leaves, from pair 0; None: all of them
+KENDALL_KINDS = (("k_kendall_keys", "keys_ns"), ("k_kendall_tile_sortIy", "tile_sort64_ns"), ("k_kendall_mergeIy", "merge64_ns"),
+                 ("k_kendall_tile_sortIj", "tile_sort32_ns"), ("k_kendall_mergeIj", "merge32_ns"), ("k_kendall_low_words", "low_words_ns"),
+                 ("k_kendall_tie", "ties_ns"), ("k_kendall_final", "final_ns"), ("k_pair_", "moments_ns"), ("k_canopy", "distance_ns"),
+                 ("k_walk", "distance_ns"))
+KENDALL_DEMANGLED = (("k_kendall_tile_sort<unsigned long", "tile_sort64_ns"), ("k_kendall_merge<unsigned long", "merge64_ns"),
+                     ("k_kendall_tile_sort<unsigned int", "tile_sort32_ns"), ("k_kendall_merge<unsigned int", "merge32_ns"))
+
+
+def _best(reps, call):
+    best = out = None
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        out = call()
+        t = time.perf_counter() - t0
+        best = t if best is None else min(best, t)
+    return best, out
+
+
+def run_kendall(reps):
+    from scipy.stats import kendalltau
+    from suchtree_amd.compare import kendall_fields, rank_fields
+    dx, dy, ids_x, ids_y = load()
+    total = len(ids_x) * (len(ids_x) - 1) // 2
+    dx.compare_triangle_kendall_host(dy, ids_x[:3000], ids_y[:3000])      # warm-up (kernels loaded, pipes built)
+    dx.compare_triangle_ranks_host(dy, ids_x[:3000], ids_y[:3000])
+    sizes = []
+    for size in KENDALL_SIZES:
+        n = total if size is None else size
+        moments_s, _ = _best(reps, lambda: dx.compare_triangle_host(dy, ids_x, ids_y, 0, n))
+        spearman_s, (_, ranks) = _best(reps, lambda: dx.compare_triangle_ranks_host(dy, ids_x, ids_y, 0, n))
+        kendall_s, (_, counts) = _best(reps, lambda: dx.compare_triangle_kendall_host(dy, ids_x, ids_y, 0, n))
+        f = kendall_fields(counts)
+        row = {"pairs": n, "moments_s": moments_s, "spearman_s": spearman_s, "kendall_s": kendall_s, "kendall_pairs_per_s": n / kendall_s,
+               "device_bytes": 16 * n, "kendall_tau": f["kendall_tau"], "spearman_r": rank_fields(ranks)["spearman_r"],
+               "concordant": f["concordant"], "discordant": f["discordant"], "ties_x": f["ties_x"], "ties_y": f["ties_y"], "ties_xy": f["ties_xy"]}
+        if size == KENDALL_SIZES[0]:      # the host route, once, at the smallest size
+            t0 = time.perf_counter()
+            x = dx.triangle_host(ids_x, 0, n)[0].astype(np.float32)
+            y = dy.triangle_host(ids_y, 0, n)[0].astype(np.float32)
+            row["scipy_fetch_s"] = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            row["scipy_tau"] = float(kendalltau(x, y)[0])
+            row["scipy_tau_s"] = time.perf_counter() - t0
+        sizes.append(row)
+    return {"reps": reps, "sizes": sizes}
+
+
+def profile_kendall():
+    """One Kendall call per size (after a small warm-up) under rocprofv3: kernel time by kind, per call."""
+    rows = _trace(["--kendall", "--child"])
+    if isinstance(rows, dict):
+        return rows
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    calls, cur = [], {}
+    for r in rows:
+        name, ns = r["Kernel_Name"], int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
+        kind = next((k for frag, k in KENDALL_DEMANGLED + KENDALL_KINDS if frag in name), "other_ns")
+        cur[kind] = cur.get(kind, 0) + ns
+        cur["launches"] = cur.get("launches", 0) + 1
+        if kind == "final_ns":      # (the last kernel of a call)
+            calls.append(cur)
+            cur = {}
+    return calls[1:]                # (without the warm-up)
+
+
+def kendall_report(res):
+    lines = ["exact Kendall tau-b over the triangle of ml.tree vs nj.tree (scripts/compare_bench.py --kendall), wall seconds, best of %d"
+             % res["reps"], "%14s %10s %10s %10s %12s %22s" % ("pairs", "moments", "spearman", "kendall", "pairs/s", "tau")]
+    for r in res["sizes"]:
+        lines.append("%14d %10.4f %10.4f %10.4f %12.3e %22.17g" % (r["pairs"], r["moments_s"], r["spearman_s"], r["kendall_s"],
+                                                                  r["kendall_pairs_per_s"], r["kendall_tau"]))
+    r = res["sizes"][0]
+    lines.append("host route at %d pairs: both columns fetched in %.3f s, scipy.stats.kendalltau %.3f s (tau %.17g)"
+                 % (r["pairs"], r["scipy_fetch_s"], r["scipy_tau_s"], r["scipy_tau"]))
+    if isinstance(res.get("kernels"), list):
+        for r, k in zip(res["sizes"], res["kernels"]):
+            tot = sum(v for name, v in k.items() if name.endswith("_ns"))
+            lines.append("kernels at %d pairs (%d launches, %.4f s summed): " % (r["pairs"], k.get("launches", 0), tot * 1e-9) +
+                         ", ".join("%s %.4f" % (name[:-3], v * 1e-9) for name, v in sorted(k.items(), key=lambda kv: -kv[1]) if name.endswith("_ns")))
+    return lines
+
+
 def _trace(child_args):
     """The kernel-trace rows of this script run once more under rocprofv3 (a dict describing the failure otherwise)."""
     exe = shutil.which("rocprofv3")
@@ -193,8 +287,32 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--spearman", action="store_true", help="measure the exact Spearman rank correlation instead")
+    ap.add_argument("--kendall", action="store_true", help="measure exact Kendall's tau-b instead")
+    ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "kendall_tau_r12.log"), help="where --kendall writes its report")
+    ap.add_argument("--kendall-measure", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.kendall_measure:
+        print(json.dumps(run_kendall(a.reps)))
+        return
+    if a.kendall:
+        if a.child:      # (under rocprofv3: one Kendall call per size, after its small warm-up)
+            dx, dy, ids_x, ids_y = load()
+            dx.compare_triangle_kendall_host(dy, ids_x[:3000], ids_y[:3000])
+            for size in KENDALL_SIZES:
+                dx.compare_triangle_kendall_host(dy, ids_x, ids_y, 0, size)
+            return
+        # (the measurement in a child process of its own: its 24 GB of device memory are gone before the profiled run)
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--kendall-measure", "--reps", str(a.reps)], capture_output=True, text=True)
+        if p.returncode != 0:
+            sys.exit("the measuring child failed (%d): %s" % (p.returncode, p.stderr[-2000:]))
+        res = json.loads(p.stdout.strip().splitlines()[-1])
+        res["kernels"] = None if a.no_profile else profile_kendall()
+        text = "\n".join(kendall_report(res) + [json.dumps(res)]) + "\n"
+        with open(a.log, "w") as f:
+            f.write(text)
+        sys.stdout.write(text)
+        return
     if a.spearman:
         if a.child:      # (under rocprofv3: the ranks call alone, after its small warm-up)
             dx, dy, ids_x, ids_y = load()

@@ -45,10 +45,12 @@ SYMBOLS = (
     "st_device_synchronize", "st_compare_triangle_host", "st_compare_pairs_host", "st_clade_plan", "st_compare_clades_host",
     "st_compare_rows_host", "st_compare_triangle_ranks_host", "st_compare_pairs_ranks_host", "st_spearman_host",
     "st_quartet_positions", "st_compare_quartets_leaves_host", "st_compare_quartets_host",
+    "st_compare_triangle_kendall_host", "st_compare_pairs_kendall_host", "st_kendall_arrays_host", "st_kendall_host",
 )
 
 CLADE_RECT, CLADE_TRI = 0, 1     # include/suchtree_hip.h: ST_CLADE_RECT / ST_CLADE_TRI
 CLADE_TILE = 8192                # ST_CLADE_TILE: pairs per tile of the clade reduction
+KENDALL_TILE = 2048              # ST_KENDALL_TILE: keys per tile of the Kendall sort (a workgroup's share of a merge level)
 
 # st_clade_segment as a numpy record
 CLADE_SEGMENT = np.dtype([("first_pair", np.int64), ("n_pairs", np.int64), ("kind", np.int32), ("node", np.int32),
@@ -89,6 +91,23 @@ class RankSums(ctypes.Structure):
         return (int(self.syy_hi) << 64) + int(self.syy_lo)
 
 
+class KendallCounts(ctypes.Structure):
+    """st_kendall_counts (include/suchtree_hip.h): the exact integer counts of Kendall's tau-b."""
+    _fields_ = [("n", ctypes.c_int64), ("n_nan", ctypes.c_int64), ("discordant", ctypes.c_uint64), ("ties_x", ctypes.c_uint64),
+                ("ties_y", ctypes.c_uint64), ("ties_xy", ctypes.c_uint64)]
+
+    @property
+    def concordant(self):
+        """n0 - ties_x - ties_y + ties_xy - discordant, n0 = n (n - 1) / 2; 0 when a pair held a NaN."""
+        n = int(self.n)
+        if self.n_nan > 0 or n < 2:
+            return 0
+        return n * (n - 1) // 2 - int(self.ties_x) - int(self.ties_y) + int(self.ties_xy) - int(self.discordant)
+
+    def as_tuple(self):
+        return tuple(int(getattr(self, k)) for k, _ in self._fields_)
+
+
 QUARTET_MODE = {"all": 0, "sample": 1}      # include/suchtree_hip.h: ST_QUARTET_ALL / ST_QUARTET_SAMPLE
 QUARTET_MAX_LEAVES_ALL = 65536
 
@@ -122,6 +141,31 @@ def spearman_host(x, y):
         raise ValueError("x and y must be 1-D arrays of equal length")
     out = RankSums()
     check(load().st_spearman_host(_ptr(x) if len(x) else None, _ptr(y) if len(y) else None, len(x), ctypes.byref(out)))
+    return out
+
+
+def _float_columns(x, y):
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    if x.ndim != 1 or x.shape != y.shape:
+        raise ValueError("x and y must be 1-D arrays of equal length")
+    return x, y
+
+
+def kendall_host(x, y):
+    """st_kendall_host: the exact Kendall counts (``KendallCounts``) of two float32 arrays of equal length, on the host."""
+    x, y = _float_columns(x, y)
+    out = KendallCounts()
+    check(load().st_kendall_host(_ptr(x) if len(x) else None, _ptr(y) if len(y) else None, len(x), ctypes.byref(out)))
+    return out
+
+
+def kendall_arrays_host(x, y, device=0):
+    """st_kendall_arrays_host: the same counts by the GPU path -- both arrays are uploaded to ``device`` and go through the
+    sort and count kernels of the compare path."""
+    x, y = _float_columns(x, y)
+    out = KendallCounts()
+    check(load().st_kendall_arrays_host(int(device), _ptr(x) if len(x) else None, _ptr(y) if len(y) else None, len(x), ctypes.byref(out)))
     return out
 
 
@@ -288,6 +332,12 @@ def load():
         L.st_compare_pairs_ranks_host.argtypes = [vp, vp, vp, vp, i64, i64, ctypes.POINTER(PairMoments), ctypes.POINTER(RankSums),
                                                   ctypes.POINTER(i64)]
         L.st_spearman_host.argtypes = [vp, vp, i64, ctypes.POINTER(RankSums)]
+        L.st_compare_triangle_kendall_host.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, ctypes.POINTER(PairMoments),
+                                                       ctypes.POINTER(KendallCounts), ctypes.POINTER(i64)]
+        L.st_compare_pairs_kendall_host.argtypes = [vp, vp, vp, vp, i64, i64, ctypes.POINTER(PairMoments), ctypes.POINTER(KendallCounts),
+                                                    ctypes.POINTER(i64)]
+        L.st_kendall_arrays_host.argtypes = [i32, vp, vp, i64, ctypes.POINTER(KendallCounts)]
+        L.st_kendall_host.argtypes = [vp, vp, i64, ctypes.POINTER(KendallCounts)]
         L.st_quartet_positions.argtypes = [i32, i32, ctypes.c_uint64, i64, i64, i64, vp]
         L.st_compare_quartets_leaves_host.argtypes = [vp, vp, vp, vp, i64, i32, ctypes.c_uint64, i64, i64, i64,
                                                       ctypes.POINTER(QuartetTable), ctypes.POINTER(i64)]
@@ -832,6 +882,36 @@ class DeviceTree:
                                                    n, int(chunk_pairs), ctypes.byref(out), ctypes.byref(ranks), ctypes.byref(bad))
         self._compare_check(other, rc, bad)
         return out, ranks
+
+    def compare_triangle_kendall_host(self, other, ids_x, ids_y, k_begin=0, k_count=None, chunk_pairs=0):
+        """compare_triangle_host without a histogram plus the exact Kendall counts of the same pairs
+        (st_compare_triangle_kendall_host).  Returns (moments, ``KendallCounts``)."""
+        ids_x = np.ascontiguousarray(ids_x, dtype=np.int64)
+        ids_y = np.ascontiguousarray(ids_y, dtype=np.int64)
+        if ids_x.ndim != 1 or ids_x.shape != ids_y.shape:
+            raise ValueError("ids_x and ids_y must be 1-D arrays of equal length")
+        m = int(ids_x.shape[0])
+        if k_count is None:
+            k_count = m * (m - 1) // 2 - int(k_begin)
+        out, counts, bad = PairMoments(), KendallCounts(), ctypes.c_int64(0)
+        rc = self._lib.st_compare_triangle_kendall_host(self.handle, other.handle, _ptr(ids_x) if m else None, _ptr(ids_y) if m else None,
+                                                        m, int(k_begin), int(k_count), int(chunk_pairs), ctypes.byref(out),
+                                                        ctypes.byref(counts), ctypes.byref(bad))
+        self._compare_check(other, rc, bad)
+        return out, counts
+
+    def compare_pairs_kendall_host(self, other, pairs_x, pairs_y, chunk_pairs=0):
+        """The same over explicit pairs (st_compare_pairs_kendall_host).  Returns (moments, ``KendallCounts``)."""
+        pairs_x = np.ascontiguousarray(pairs_x, dtype=np.int64)
+        pairs_y = np.ascontiguousarray(pairs_y, dtype=np.int64)
+        if pairs_x.ndim != 2 or pairs_x.shape[1:] != (2,) or pairs_x.shape != pairs_y.shape:
+            raise ValueError("pairs_x and pairs_y must be (n, 2) arrays of equal shape")
+        n = int(pairs_x.shape[0])
+        out, counts, bad = PairMoments(), KendallCounts(), ctypes.c_int64(0)
+        rc = self._lib.st_compare_pairs_kendall_host(self.handle, other.handle, _ptr(pairs_x) if n else None, _ptr(pairs_y) if n else None,
+                                                     n, int(chunk_pairs), ctypes.byref(out), ctypes.byref(counts), ctypes.byref(bad))
+        self._compare_check(other, rc, bad)
+        return out, counts
 
     def compare_quartets_leaves_host(self, other, ids_x, ids_y, mode="all", seed=0, k_begin=0, k_count=None, chunk_quartets=0):
         """The int64 (4, 4) table of quartet classes -- [class here][class in ``other``] -- of quartets

@@ -32,6 +32,13 @@ class DistanceComparison:
     (Python ints: they do not depend on reduction order, chunking or device); ``distinct_x`` / ``distinct_y`` count the
     distinct distances.  All six are None when ranks were not asked for, and after :meth:`merge`: ranks of disjoint
     pair ranges do not combine.
+
+    With ``kendall=True`` the call also keeps and sorts every pair on the GPU: ``kendall_tau`` is Kendall's tau-b of all
+    n pairs (``scipy.stats.kendalltau``; NaN for a constant column, n < 2 or a NaN distance), computed from the exact
+    integers ``concordant``, ``discordant``, ``ties_x``, ``ties_y`` and ``ties_xy`` (Python ints: sums of t (t - 1) / 2
+    over the tie groups of x, of y and of both; concordant + discordant + ties_x + ties_y - ties_xy = n (n - 1) / 2), from
+    which gamma, Somers' D or tau-a follow as well.  No p-value: pairs that share a leaf are not independent.  All six
+    are None when Kendall's tau was not asked for, and after :meth:`merge`.
     """
 
     n_pairs: int
@@ -62,12 +69,18 @@ class DistanceComparison:
     rank_syy: Optional[int] = None
     distinct_x: Optional[int] = None
     distinct_y: Optional[int] = None
+    kendall_tau: Optional[float] = None
+    concordant: Optional[int] = None
+    discordant: Optional[int] = None
+    ties_x: Optional[int] = None
+    ties_y: Optional[int] = None
+    ties_xy: Optional[int] = None
 
     @classmethod
     def from_sums(cls, n, shift_x, shift_y, sx, sy, sxx, syy, sxy, min_x, max_x, min_y, max_y, hist=None, xedges=None,
-                  yedges=None, n_leaves=None, ranks=None):
+                  yedges=None, n_leaves=None, ranks=None, kendall=None):
         """Derive the statistics from sums about a shift (st_pair_moments); ``ranks``: the library's ``_capi.RankSums`` of
-        the same pairs, or None."""
+        the same pairs, or None; ``kendall``: its ``_capi.KendallCounts``, or None."""
         n = int(n)
         nan = float("nan")
         if n == 0:
@@ -86,13 +99,13 @@ class DistanceComparison:
         return cls(n_pairs=n, n_leaves=n_leaves, mean_x=mean_x, mean_y=mean_y, var_x=var_x, var_y=var_y, cov=cov,
                    pearson_r=r, min_x=float(min_x), max_x=float(max_x), min_y=float(min_y), max_y=float(max_y), hist=hist,
                    xedges=xedges, yedges=yedges, shift_x=float(shift_x), shift_y=float(shift_y), sx=float(sx),
-                   sy=float(sy), sxx=float(sxx), syy=float(syy), sxy=float(sxy), **rank_fields(ranks))
+                   sy=float(sy), sxx=float(sxx), syy=float(syy), sxy=float(sxy), **rank_fields(ranks), **kendall_fields(kendall))
 
     @classmethod
-    def from_moments(cls, m, hist=None, xedges=None, yedges=None, n_leaves=None, ranks=None):
-        """From the library's ``_capi.PairMoments`` and, if given, its ``_capi.RankSums``."""
+    def from_moments(cls, m, hist=None, xedges=None, yedges=None, n_leaves=None, ranks=None, kendall=None):
+        """From the library's ``_capi.PairMoments`` and, if given, its ``_capi.RankSums`` and ``_capi.KendallCounts``."""
         return cls.from_sums(m.n, m.shift_x, m.shift_y, m.sx, m.sy, m.sxx, m.syy, m.sxy, m.min_x, m.max_x, m.min_y,
-                             m.max_y, hist, xedges, yedges, n_leaves, ranks)
+                             m.max_y, hist, xedges, yedges, n_leaves, ranks, kendall)
 
     @classmethod
     def merge(cls, a: "DistanceComparison", b: "DistanceComparison") -> "DistanceComparison":
@@ -102,11 +115,11 @@ class DistanceComparison:
         The class of an infinite cross product depends on the shift it was summed about and is not recovered.
         Histograms add when both have the same edges (otherwise ValueError).  The rank fields (``spearman_r``, ``rank_*``,
         ``distinct_*``) of the result are None: a value's rank depends on every pair of its call, so ranks of disjoint
-        ranges do not combine."""
+        ranges do not combine.  The Kendall fields are None for the same reason."""
         if b.n_pairs == 0:
-            return a if a.rank_sxy is None else replace(a, **rank_fields(None))
+            return a if a.rank_sxy is None and a.discordant is None else replace(a, **rank_fields(None), **kendall_fields(None))
         if a.n_pairs == 0:
-            return replace(b, n_leaves=a.n_leaves if a.n_leaves == b.n_leaves else None, **rank_fields(None))
+            return replace(b, n_leaves=a.n_leaves if a.n_leaves == b.n_leaves else None, **rank_fields(None), **kendall_fields(None))
         hist = None
         if a.hist is not None or b.hist is not None:
             if a.hist is None or b.hist is None or not (np.array_equal(a.xedges, b.xedges) and np.array_equal(a.yedges, b.yedges)):
@@ -144,6 +157,28 @@ def rank_fields(ranks):
                 rank_syy=syy, distinct_x=int(ranks.distinct_x), distinct_y=int(ranks.distinct_y))
 
 
+def kendall_from_counts(n, n_nan, concordant, discordant, ties_x, ties_y):
+    """Kendall's tau-b from the exact counts: (concordant - discordant) / sqrt((n0 - ties_x)(n0 - ties_y)), n0 =
+    n (n - 1) / 2, clipped to [-1, 1]; NaN when a factor is 0, n < 2, or a pair held a NaN (scipy's
+    nan_policy="propagate").  The integer numerator and the two integer factors are converted to float, then one square
+    root of the product is taken, as in spearman_from_sums: identical columns (numerator == both factors) give 1.0 and
+    negated ones -1.0 exactly."""
+    n0 = int(n) * (int(n) - 1) // 2
+    fx, fy = n0 - int(ties_x), n0 - int(ties_y)
+    if n < 2 or n_nan > 0 or fx <= 0 or fy <= 0:
+        return float("nan")
+    return min(1.0, max(-1.0, float(int(concordant) - int(discordant)) / math.sqrt(float(fx) * float(fy))))
+
+
+def kendall_fields(counts):
+    """The Kendall fields of a DistanceComparison from a ``_capi.KendallCounts`` (None: all None)."""
+    if counts is None:
+        return dict(kendall_tau=None, concordant=None, discordant=None, ties_x=None, ties_y=None, ties_xy=None)
+    con, dis, tx, ty, txy = int(counts.concordant), int(counts.discordant), int(counts.ties_x), int(counts.ties_y), int(counts.ties_xy)
+    return dict(kendall_tau=kendall_from_counts(int(counts.n), int(counts.n_nan), con, dis, tx, ty), concordant=con,
+                discordant=dis, ties_x=tx, ties_y=ty, ties_xy=txy)
+
+
 def histogram_edges(bins, range, min_max):
     """(xedges, yedges) exactly as numpy.histogram2d builds them for ``bins`` / ``range``.  With ``range=None`` the range of
     integer bins is the data's (min_x, max_x), (min_y, max_y), given as ``min_max`` (numpy widens an empty range by 0.5 on
@@ -166,11 +201,17 @@ def _needs_data_range(bins, range):
     return np.ndim(bins) == 0   # one edge array for both axes
 
 
-def run(call, bins, range, n_leaves=None, rank_call=None):
+def run(call, bins, range, n_leaves=None, rank_call=None, kendall_call=None):
     """call(edges) -> (PairMoments, hist): one pass of the library.  ``range=None`` with integer bins costs a second
     pass: the first finds min and max, the second bins.  rank_call() -> (PairMoments, RankSums), if given, adds the
     rank fields: alone it is the only call (its moments are call(None)'s); with ``bins`` the histogram calls run as
-    they do without it."""
+    they do without it.  kendall_call() -> (PairMoments, KendallCounts), if given, adds the Kendall fields in the same
+    way: alone it is the only call; with ``bins`` or rank_call those run as they do without it, beside it."""
+    if kendall_call is not None:
+        m, counts = kendall_call()
+        if bins is None and rank_call is None:
+            return DistanceComparison.from_moments(m, n_leaves=n_leaves, kendall=counts)
+        return replace(run(call, bins, range, n_leaves, rank_call), **kendall_fields(counts))
     if rank_call is not None:
         m, ranks = rank_call()
         if bins is None:

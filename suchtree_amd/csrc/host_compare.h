@@ -3,8 +3,10 @@
 // tree Y into two float32 scratch buffers on the device, and a reducer -- MomentsReduce (kernels_compare.h), CladeReduce
 // (kernels_clades.h), RowsReduce (kernels_rows.h) -- reduces them.  Device scratch is bounded by the chunk, host memory
 // by the histogram or the pieces: nothing grows with the pair count.  What needs no GPU -- the clade plan and its
-// tables, the rows layout, the folding of pieces -- is compare_plan.cpp.  The exact Spearman rank sums (compare_ranks,
-// at the end) are three such runs around count tables that the entry point owns (kernels_ranks.h, rank_plan.cpp).
+// tables, the rows layout, the folding of pieces -- is compare_plan.cpp.  The exact Spearman rank sums (compare_ranks)
+// are three such runs around count tables that the entry point owns (kernels_ranks.h, rank_plan.cpp); the exact Kendall
+// counts (compare_kendall, at the end) are one run that keeps every pair's key, then a sort (kernels_kendall.h,
+// kendall_plan.cpp).
 #pragma once
 
 constexpr int64_t kCompareChunkTriangle = (int64_t)1 << 25;   // 2 x 128 MiB of float32 distances
@@ -476,5 +478,167 @@ static int compare_ranks(st_tree *tx, int64_t n, int64_t chunk_pairs, Run run, s
     const i128 sxy = (i128)(((u128)(uint64_t)R->dot.hi << 64) | R->dot.lo);
     rank_finish(n, 0, (int64_t)R->scan[0].distinct, (int64_t)R->scan[1].distinct, sxy, ((u128)R->scan[0].tie_hi << 64) | R->scan[0].tie_lo,
                 ((u128)R->scan[1].tie_hi << 64) | R->scan[1].tie_lo, out_ranks);
+    return ST_OK;
+}
+
+// ---- exact Kendall tau-b counts (st_compare_*_kendall_host, st_kendall_arrays_host; kernels_kendall.h, kendall_plan.h) ----
+// The pairs' keys and the sort's second buffer: 16 bytes per pair, which outlive the compare_run that fills them, so the
+// entry point owns them.  The 32-bit stage lives inside the two buffers: after the 64-bit sort one holds the sorted keys
+// and the other is spare -- it takes the block records of the two tie scans, then the low words in its first 4 n bytes
+// with their sort's second buffer in the last 4 n; the buffer of the sorted keys is spare for the last tie scan.
+struct KendallState {
+    DevBuf<unsigned long long> d_keys[2];
+    DevBuf<char> d_small;                    // NaN pairs | slots of the four counts | the four counts
+    int64_t n = 0;
+    unsigned long long counts[kKendallCounts] = {0, 0, 0, 0}, n_nan = 0;
+
+    static constexpr size_t o_part = 256;
+    static constexpr size_t o_final = o_part + sizeof(unsigned long long) * kKendallCounts * kKendallBlocks;
+    static constexpr size_t small_bytes = o_final + 256;
+
+    unsigned long long *d_nan() const { return reinterpret_cast<unsigned long long *>(d_small.get()); }
+    unsigned long long *d_part(int count) const { return reinterpret_cast<unsigned long long *>(d_small + o_part) + (size_t)count * kKendallBlocks; }
+    unsigned long long *d_final() const { return reinterpret_cast<unsigned long long *>(d_small + o_final); }
+
+    // everything the call needs beside compare_run's block, or nothing
+    int alloc(int64_t pairs)
+    {
+        n = pairs;
+        const size_t bytes = (size_t)n * 8;
+        hipError_t e = d_small.alloc(small_bytes);
+        for (int i = 0; i < 2 && e == hipSuccess; i++) e = d_keys[i].alloc((size_t)n);
+        if (e == hipSuccess) return ST_OK;
+        (void)hipGetLastError();
+        d_small.reset();
+        d_keys[0].reset();
+        d_keys[1].reset();
+        return fail(ST_ERR_NOMEM, "Kendall counts of " + std::to_string(n) + " pairs need two device buffers of " + std::to_string(bytes) +
+                                      " bytes each (16 bytes per pair) and " + std::to_string(small_bytes) + " more: " + hipGetErrorString(e));
+    }
+    hipError_t start(hipStream_t s) { return hipMemsetAsync(d_small, 0, small_bytes, s); }
+    int grid() const { return (int)std::min<int64_t>((n + kKendallTile - 1) / kKendallTile, kKendallBlocks); }
+
+    // src (n keys) sorted, ping-ponging with `other`; returns the buffer that holds the result
+    template <typename Key, bool Count>
+    Key *sort(Key *src, Key *other, hipStream_t s)
+    {
+        hipLaunchKernelGGL((k_kendall_tile_sort<Key, Count>), dim3(grid()), dim3(kKendallThreads), 0, s, src, src, (long long)n, d_part(kKendallDiscordant));
+        for (int64_t run = kKendallTile; run < n; run <<= 1) {
+            hipLaunchKernelGGL((k_kendall_merge<Key, Count>), dim3(grid()), dim3(kKendallThreads), 0, s, src, other, (long long)n, (long long)run,
+                               d_part(kKendallDiscordant));
+            std::swap(src, other);
+        }
+        return src;
+    }
+    // the tie sum of sorted[0, n) by (key >> shift) into the slots of `count`; `blocks`: room for one int per tile
+    template <typename Key>
+    void ties(const Key *sorted, int shift, int count, int *blocks, hipStream_t s)
+    {
+        const int64_t n_blocks = (n + kKendallTile - 1) / kKendallTile;
+        hipLaunchKernelGGL(k_kendall_tie_blocks<Key>, dim3(grid()), dim3(kKendallThreads), 0, s, sorted, (long long)n, shift, blocks);
+        hipLaunchKernelGGL(k_kendall_tie_carry, dim3(1), dim3(kKendallThreads), 0, s, blocks, (long long)n_blocks);
+        hipLaunchKernelGGL(k_kendall_tie_sums<Key>, dim3(grid()), dim3(kKendallThreads), 0, s, sorted, (long long)n, shift, blocks, d_part(count));
+    }
+    // everything after the keys (in d_keys[0]), and the read-back; n >= 1
+    hipError_t enqueue(hipStream_t s)
+    {
+        unsigned long long *sorted = sort<unsigned long long, false>(d_keys[0].get(), d_keys[1].get(), s);
+        unsigned long long *spare = sorted == d_keys[0].get() ? d_keys[1].get() : d_keys[0].get();
+        ties(sorted, 32, kKendallTiesX, reinterpret_cast<int *>(spare), s);
+        ties(sorted, 0, kKendallTiesXY, reinterpret_cast<int *>(spare), s);
+        uint32_t *low = reinterpret_cast<uint32_t *>(spare);
+        hipLaunchKernelGGL(k_kendall_low_words, dim3(grid()), dim3(kKendallThreads), 0, s, sorted, (long long)n, low);
+        const uint32_t *low_sorted = sort<uint32_t, true>(low, low + n, s);
+        ties(low_sorted, 0, kKendallTiesY, reinterpret_cast<int *>(sorted), s);
+        hipLaunchKernelGGL(k_kendall_final, dim3(kKendallCounts), dim3(64), 0, s, d_part(0), d_final());
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(counts, d_final(), sizeof counts, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(&n_nan, d_nan(), sizeof n_nan, hipMemcpyDeviceToHost, s);
+        return e;
+    }
+    void done(st_kendall_counts *out) const
+    {
+        kendall_finish(n, (int64_t)n_nan, counts[kKendallDiscordant], counts[kKendallTiesX], counts[kKendallTiesY], counts[kKendallTiesXY], out);
+    }
+};
+
+// The reducer of the Kendall path: every chunk's keys at the chunk's offset, the sort and the counts in finish().  With
+// `moments` it also is the MomentsReduce of st_compare_*_host (the same kernels in the same order: the same bits).
+struct KendallKeysReduce {
+    MomentsReduce mom;
+    KendallState &K;
+    bool moments;
+
+    size_t bytes(int64_t c) { return moments ? mom.bytes(c) : 0; }
+    hipError_t start(char *d, int64_t total, hipStream_t s)
+    {
+        hipError_t e = moments ? mom.start(d, total, s) : hipSuccess;
+        if (e == hipSuccess) e = K.start(s);
+        return e;
+    }
+    hipError_t chunk(const float *d_x, const float *d_y, int64_t off, int64_t c, hipStream_t s)
+    {
+        hipError_t e = moments ? mom.chunk(d_x, d_y, off, c, s) : hipSuccess;
+        if (e != hipSuccess) return e;
+        const int grid = (int)std::min<int64_t>((c + kKendallThreads - 1) / kKendallThreads, kKendallBlocks);
+        hipLaunchKernelGGL(k_kendall_keys, dim3(grid), dim3(kKendallThreads), 0, s, d_x, d_y, (long long)c, K.d_keys[0] + off, K.d_nan());
+        return hipGetLastError();
+    }
+    hipError_t finish(hipStream_t s)
+    {
+        hipError_t e = moments ? mom.finish(s) : hipSuccess;
+        if (e == hipSuccess) e = K.enqueue(s);
+        return e;
+    }
+    int done() { return moments ? mom.done() : ST_OK; }
+};
+
+// run(chunk_pairs, reducer) is one compare_run over the caller's pairs.  chunk_pairs 0: one pass gives the moments and
+// the keys.  Another chunk would change the order of the moments' float sums, so then the moments take a pass of their
+// own at the path's default chunk and the keys a second one at chunk_pairs: out is always st_compare_*_host's.
+template <typename Run>
+static int compare_kendall(st_tree *tx, int64_t n, int64_t chunk_pairs, Run run, st_pair_moments *out, st_kendall_counts *out_counts)
+{
+    ST_DEVICE(tx->device);
+    KendallState K;
+    int rc = K.alloc(n);
+    if (rc != ST_OK) return rc;
+    if (chunk_pairs != 0) {
+        MomentsReduce mom{nullptr, nullptr, 0, 0, out, nullptr};
+        rc = run((int64_t)0, mom);
+        if (rc != ST_OK) return rc;
+    }
+    KendallKeysReduce keys{MomentsReduce{nullptr, nullptr, 0, 0, out, nullptr}, K, chunk_pairs == 0};
+    rc = run(chunk_pairs, keys);
+    if (rc != ST_OK) return rc;
+    K.done(out_counts);
+    return ST_OK;
+}
+
+// st_kendall_arrays_host: the two columns are staged in the sort's second buffer (x in its first 4 n bytes, y in the
+// last), their keys written to the first, then KendallState::enqueue as above.
+static int kendall_arrays(int device, const float *x, const float *y, int64_t n, st_kendall_counts *out)
+{
+    ST_DEVICE(device);
+    KendallState K;
+    int rc = K.alloc(n);
+    if (rc != ST_OK) return rc;
+    struct Drained {      // (declared after K: the stream drains before the buffers go)
+        Stream s;
+        ~Drained() { if (s) (void)hipStreamSynchronize(s); }
+    } q;
+    float *d_x = reinterpret_cast<float *>(K.d_keys[1].get()), *d_y = d_x + n;
+    hipError_t e = q.s.create();
+    if (e == hipSuccess) e = K.start(q.s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_x, x, (size_t)n * 4, hipMemcpyHostToDevice, q.s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_y, y, (size_t)n * 4, hipMemcpyHostToDevice, q.s);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_kendall_keys, dim3(K.grid()), dim3(kKendallThreads), 0, q.s, d_x, d_y, (long long)n, K.d_keys[0].get(), K.d_nan());
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = K.enqueue(q.s);
+    if (e == hipSuccess) e = hipStreamSynchronize(q.s);
+    if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("Kendall counts: ") + hipGetErrorString(e));
+    K.done(out);
     return ST_OK;
 }

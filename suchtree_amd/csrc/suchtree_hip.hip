@@ -34,6 +34,9 @@
 // host-only C++ beside tree_prep.cpp, compare_plan.cpp (argument checks, clade plan and tables, rows layout, the fold).
 // Exact Spearman rank sums of the same pairs (st_compare_*_ranks_host): kernels_ranks.h, the reducers at the end of
 // host_compare.h and, host-only, rank_plan.cpp (keys, bucket layout, tie arithmetic, st_spearman_host).
+// Exact Kendall tau-b counts of the same pairs (st_compare_*_kendall_host, st_kendall_arrays_host): kernels_kendall.h (keys,
+// tile sort, merge levels, tie scans), KendallState and its reducer at the end of host_compare.h and, host-only,
+// kendall_plan.cpp (the merge arithmetic both sides share, st_kendall_host).
 // Two trees' quartet topologies, counted on the device (st_compare_quartets_*_host, st_quartet_positions):
 // kernels_quartets.h (generator, classify-and-count), host_quartets.h (the chunk driver) and, host-only,
 // quartet_plan.cpp (unranking, the draw, the class rule, argument checks).
@@ -141,6 +144,7 @@ private:
 #include "kernels_misc.h"
 #include "kernels_compare.h"
 #include "kernels_ranks.h"
+#include "kernels_kendall.h"
 #include "kernels_clades.h"
 #include "kernels_rows.h"
 #include "kernels_quartets.h"
@@ -975,10 +979,10 @@ static int compare_pairs_run(st_tree *tx, st_tree *ty, const int64_t *pairs_x, c
     return compare_run(tx, ty, n, chunk, (size_t)chunk * 32, setup, prep, src_x, src_y, red, bad_id);
 }
 
-static int rank_count_arg(int64_t n)
+static int rank_count_arg(int64_t n, const char *what = "ranks")
 {
     if (n <= kRankMaxPairs) return ST_OK;
-    return fail(ST_ERR_ARG, "ranks of " + std::to_string(n) + " pairs: at most " + std::to_string(kRankMaxPairs) + " (2^31 - 1)");
+    return fail(ST_ERR_ARG, std::string(what) + " of " + std::to_string(n) + " pairs: at most " + std::to_string(kRankMaxPairs) + " (2^31 - 1)");
 }
 
 extern "C" {
@@ -1080,6 +1084,71 @@ int st_spearman_host(const float *x, const float *y, int64_t n, st_rank_sums *ou
 try {
     std::string err;
     const int rc = spearman_host(x, y, n, out, err);
+    return rc == ST_OK ? ST_OK : fail(rc, err);
+} ST_CATCH_ALL
+
+int st_compare_triangle_kendall_host(st_tree *tx, st_tree *ty, const int64_t *ids_x, const int64_t *ids_y, int64_t m, int64_t k_begin,
+                                     int64_t k_count, int64_t chunk_pairs, st_pair_moments *out, st_kendall_counts *out_counts, int64_t *bad_id)
+try {
+    if (!out || !out_counts) return fail(ST_ERR_ARG, "out or out_counts is NULL");
+    int rc = compare_trees_args(tx, ty);
+    if (rc != ST_OK) return rc;
+    rc = triangle_range_args(m, k_begin, k_count);
+    if (rc == ST_OK) rc = chunk_pairs_arg(chunk_pairs);
+    if (rc == ST_OK) rc = rank_count_arg(k_count, "Kendall counts");
+    if (rc != ST_OK) return rc;
+    if (m > 0 && (!ids_x || !ids_y)) return fail(ST_ERR_ARG, "ids_x or ids_y is NULL");
+    if (k_count == 0) {
+        compare_empty(out, nullptr, 0, 0);
+        kendall_finish(0, 0, 0, 0, 0, 0, out_counts);
+        return ST_OK;
+    }
+    rc = compare_check_ids(ids_x, m, tx->n_nodes, bad_id);
+    if (rc == ST_OK) rc = compare_check_ids(ids_y, m, ty->n_nodes, bad_id);
+    if (rc != ST_OK) return rc;
+    auto run = [&](int64_t chunk, auto &red) { return compare_triangle_run(tx, ty, ids_x, ids_y, m, k_begin, k_count, chunk, red, bad_id); };
+    return compare_kendall(tx, k_count, chunk_pairs, run, out, out_counts);
+} ST_CATCH_ALL
+
+int st_compare_pairs_kendall_host(st_tree *tx, st_tree *ty, const int64_t *pairs_x, const int64_t *pairs_y, int64_t n, int64_t chunk_pairs,
+                                  st_pair_moments *out, st_kendall_counts *out_counts, int64_t *bad_id)
+try {
+    if (!out || !out_counts) return fail(ST_ERR_ARG, "out or out_counts is NULL");
+    int rc = compare_trees_args(tx, ty);
+    if (rc != ST_OK) return rc;
+    if (n < 0) return fail(ST_ERR_ARG, "n < 0");
+    rc = chunk_pairs_arg(chunk_pairs);
+    if (rc == ST_OK) rc = rank_count_arg(n, "Kendall counts");
+    if (rc != ST_OK) return rc;
+    if (n > 0 && (!pairs_x || !pairs_y)) return fail(ST_ERR_ARG, "pairs_x or pairs_y is NULL");
+    if (n == 0) {
+        compare_empty(out, nullptr, 0, 0);
+        kendall_finish(0, 0, 0, 0, 0, 0, out_counts);
+        return ST_OK;
+    }
+    rc = compare_check_ids(pairs_x, 2 * n, tx->n_nodes, bad_id);
+    if (rc == ST_OK) rc = compare_check_ids(pairs_y, 2 * n, ty->n_nodes, bad_id);
+    if (rc != ST_OK) return rc;
+    auto run = [&](int64_t chunk, auto &red) { return compare_pairs_run(tx, ty, pairs_x, pairs_y, n, chunk, red, bad_id); };
+    return compare_kendall(tx, n, chunk_pairs, run, out, out_counts);
+} ST_CATCH_ALL
+
+int st_kendall_arrays_host(int device, const float *x, const float *y, int64_t n, st_kendall_counts *out)
+try {
+    std::string err;
+    const int rc = kendall_args(x, y, n, out, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (n == 0) {
+        kendall_finish(0, 0, 0, 0, 0, 0, out);
+        return ST_OK;
+    }
+    return kendall_arrays(device, x, y, n, out);
+} ST_CATCH_ALL
+
+int st_kendall_host(const float *x, const float *y, int64_t n, st_kendall_counts *out)
+try {
+    std::string err;
+    const int rc = kendall_host(x, y, n, out, err);
     return rc == ST_OK ? ST_OK : fail(rc, err);
 } ST_CATCH_ALL
 

@@ -201,12 +201,13 @@ class SuchLinkedTrees:
         return {"TreeA": d_a, "TreeB": d_b, "ids_A": ids_a, "ids_B": ids_b,
                 "n_pairs": size, "n_samples": size, "deviation_a": None, "deviation_b": None}
 
-    def linked_distances_summary(self, bins=None, range=None, spearman=False):
+    def linked_distances_summary(self, bins=None, range=None, spearman=False, kendall=False):
         """:meth:`linked_distances` reduced on the GPU: a :class:`~suchtree_amd.compare.DistanceComparison` of the same
         pairs with x = the TreeA column, y = the TreeB column (ids from ``linklist[:,1]`` / ``linklist[:,0]``), under the
         current ``subset_a`` / ``subset_b``.  No distance vector is materialised.  ``bins`` / ``range`` as in
         ``numpy.histogram2d`` (``range=None`` with integer bins costs a second pass).  ``spearman=True`` adds Spearman's rs
-        of all pairs and its exact rank sums, as in :meth:`SuchTree.compare_distances`.  An extension: the reference
+        of all pairs and its exact rank sums, ``kendall=True`` Kendall's tau-b and its exact counts (16 bytes of device
+        memory per pair), as in :meth:`SuchTree.compare_distances`.  An extension: the reference
         has no counterpart (its notebooks correlate the two columns of linked_distances on the host)."""
         from . import compare
         ll = np.ascontiguousarray(self.linklist, dtype=np.int64)
@@ -214,7 +215,8 @@ class SuchLinkedTrees:
         dev_a, dev_b = self._tree_a._device_tree(), self._tree_b._device_tree()
         return compare.run(lambda edges: dev_a.compare_triangle_host(dev_b, ids_a, ids_b, edges=edges), bins, range,
                            n_leaves=int(ll.shape[0]),
-                           rank_call=(lambda: dev_a.compare_triangle_ranks_host(dev_b, ids_a, ids_b)) if spearman else None)
+                           rank_call=(lambda: dev_a.compare_triangle_ranks_host(dev_b, ids_a, ids_b)) if spearman else None,
+                           kendall_call=(lambda: dev_a.compare_triangle_kendall_host(dev_b, ids_a, ids_b)) if kendall else None)
 
     @staticmethod
     def _breadth_first(tree: SuchTree, node_id: int, leaves: bool) -> np.ndarray:

@@ -390,7 +390,8 @@ class SuchTree(TreeNavigation):
         names = [name for name, _ in sorted(self.leaves.items(), key=lambda kv: kv[1]) if name in other.leaves]
         return names, self._name_ids(names), other._name_ids(names)
 
-    def compare_distances(self, other: "SuchTree", leaves=None, pairs=None, bins=None, range=None, spearman=False):
+    def compare_distances(self, other: "SuchTree", leaves=None, pairs=None, bins=None, range=None, spearman=False,
+                          kendall=False):
         """Compare this tree's distances with ``other``'s over the same pairs, reduced on the GPU.
 
         An extension: the reference has no counterpart.  It stands in for the comparison workflow of its docs
@@ -415,6 +416,12 @@ class SuchTree(TreeNavigation):
         ``spearman=True`` also ranks every pair on the GPU (two more passes over the pairs and 4 MiB of device counters
         per occupied key bucket, see DistanceComparison): ``spearman_r``, the exact integer rank sums and the distinct
         counts are filled in; at most 2^31 - 1 pairs (ValueError beyond).  Every other field is what it is without it.
+        ``kendall=True`` also keeps every pair on the GPU as a 64-bit key, sorts them there and counts: ``kendall_tau``
+        (tau-b, as ``scipy.stats.kendalltau``) and the exact integers ``concordant``, ``discordant``, ``ties_x``,
+        ``ties_y``, ``ties_xy`` are filled in.  One pass over the pairs and 16 bytes of device memory per pair (all
+        1.48e9 pairs of 54,327 leaves: 24 GB; MemoryError when the device cannot give them); at most 2^31 - 1 pairs.
+        With ``bins`` or ``spearman=True`` those calls run as they do without it.  Every other field is what it is
+        without it.
         Both trees must be on the same GPU (ValueError otherwise); an id out of range raises InvalidNodeError.
         """
         from . import compare
@@ -435,7 +442,8 @@ class SuchTree(TreeNavigation):
                 py = other._name_ids(flat).reshape(-1, 2)
             dx, dy = self._device_tree(), other._device_tree()
             return compare.run(lambda edges: dx.compare_pairs_host(dy, px, py, edges=edges), bins, range,
-                               rank_call=(lambda: dx.compare_pairs_ranks_host(dy, px, py)) if spearman else None)
+                               rank_call=(lambda: dx.compare_pairs_ranks_host(dy, px, py)) if spearman else None,
+                               kendall_call=(lambda: dx.compare_pairs_kendall_host(dy, px, py)) if kendall else None)
         if leaves is None:
             _, ids_x, ids_y = self.shared_leaves(other)
         elif isinstance(leaves, tuple) and len(leaves) == 2:
@@ -448,7 +456,8 @@ class SuchTree(TreeNavigation):
         dx, dy = self._device_tree(), other._device_tree()
         return compare.run(lambda edges: dx.compare_triangle_host(dy, ids_x, ids_y, edges=edges), bins, range,
                            n_leaves=int(len(ids_x)),
-                           rank_call=(lambda: dx.compare_triangle_ranks_host(dy, ids_x, ids_y)) if spearman else None)
+                           rank_call=(lambda: dx.compare_triangle_ranks_host(dy, ids_x, ids_y)) if spearman else None,
+                           kendall_call=(lambda: dx.compare_triangle_kendall_host(dy, ids_x, ids_y)) if kendall else None)
 
     def compare_quartets(self, other: "SuchTree", leaves=None, quartets=None, samples=None, seed=None):
         """Compare this tree's topology with ``other``'s over the same quartets, counted on the GPU.
