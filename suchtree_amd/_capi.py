@@ -819,98 +819,90 @@ class DeviceTree:
             raise ValueError("histogram of %d cells: at most 16384" % (bx * by))
         return ex, bx, ey, by, np.zeros((bx, by), dtype=np.int64)
 
-    def compare_triangle_host(self, other, ids_x, ids_y, k_begin=0, k_count=None, edges=None):
-        """Moments (``PairMoments``) and, with ``edges = (xedges, yedges)``, the int64 2-D histogram of the distances of
-        pairs k in [k_begin, k_begin + k_count) of the triangle over ``ids_x`` in this tree and ``ids_y`` in ``other``
-        (st_compare_triangle_host; the pair enumeration of triangle_host).  Returns (moments, hist or None)."""
+    @staticmethod
+    def _id_lists(ids_x, ids_y):
+        """(ids_x, ids_y, m): two aligned id lists as contiguous 1-D int64 arrays, and their length."""
         ids_x = np.ascontiguousarray(ids_x, dtype=np.int64)
         ids_y = np.ascontiguousarray(ids_y, dtype=np.int64)
         if ids_x.ndim != 1 or ids_x.shape != ids_y.shape:
             raise ValueError("ids_x and ids_y must be 1-D arrays of equal length")
-        m = int(ids_x.shape[0])
-        if k_count is None:
-            k_count = m * (m - 1) // 2 - int(k_begin)
+        return ids_x, ids_y, int(ids_x.shape[0])
+
+    @staticmethod
+    def _id_rows(rows_x, rows_y, k, what):
+        """(rows_x, rows_y, n): two aligned (n, k) id arrays -- ``what`` "pairs" (k = 2) or "quartets" (k = 4) -- as
+        contiguous int64 arrays, and their row count."""
+        rows_x = np.ascontiguousarray(rows_x, dtype=np.int64)
+        rows_y = np.ascontiguousarray(rows_y, dtype=np.int64)
+        if rows_x.ndim != 2 or rows_x.shape[1:] != (k,) or rows_x.shape != rows_y.shape:
+            raise ValueError("%s_x and %s_y must be (n, %d) arrays of equal shape" % (what, what, k))
+        return rows_x, rows_y, int(rows_x.shape[0])
+
+    @staticmethod
+    def _triangle_count(m, k_begin, k_count):
+        """k_count, by default up to the last pair of the triangle over m ids."""
+        return int(m * (m - 1) // 2 - int(k_begin) if k_count is None else k_count)
+
+    def _compare_call(self, fn, other, args, *outs):
+        """fn(self, other, *args, *outs, &bad_id) of a two-tree entry point: an array goes as its pointer (NULL when it is
+        empty or None), a result structure by reference.  Raises as _compare_check does."""
+        def c(a):
+            if isinstance(a, np.ndarray):
+                return _ptr(a) if a.size else None
+            return ctypes.byref(a) if isinstance(a, ctypes.Structure) else a
+        bad = ctypes.c_int64(0)
+        self._compare_check(other, fn(self.handle, other.handle, *(c(a) for a in args + outs), ctypes.byref(bad)), bad)
+
+    def compare_triangle_host(self, other, ids_x, ids_y, k_begin=0, k_count=None, edges=None):
+        """Moments (``PairMoments``) and, with ``edges = (xedges, yedges)``, the int64 2-D histogram of the distances of
+        pairs k in [k_begin, k_begin + k_count) of the triangle over ``ids_x`` in this tree and ``ids_y`` in ``other``
+        (st_compare_triangle_host; the pair enumeration of triangle_host).  Returns (moments, hist or None)."""
+        ids_x, ids_y, m = self._id_lists(ids_x, ids_y)
+        k_count = self._triangle_count(m, k_begin, k_count)
         ex, bx, ey, by, hist = self._compare_hist(edges)
-        out, bad = PairMoments(), ctypes.c_int64(0)
-        rc = self._lib.st_compare_triangle_host(self.handle, other.handle, _ptr(ids_x) if m else None, _ptr(ids_y) if m else None, m,
-                                                int(k_begin), int(k_count), _ptr(ex), bx, _ptr(ey), by, ctypes.byref(out), _ptr(hist),
-                                                ctypes.byref(bad))
-        self._compare_check(other, rc, bad)
+        out = PairMoments()
+        self._compare_call(self._lib.st_compare_triangle_host, other, (ids_x, ids_y, m, int(k_begin), k_count, ex, bx, ey, by), out, hist)
         return out, hist
 
     def compare_pairs_host(self, other, pairs_x, pairs_y, edges=None):
         """The same over explicit pairs: row i of ``pairs_x`` (int64 (n,2)) in this tree, row i of ``pairs_y`` in ``other``
         (st_compare_pairs_host).  Returns (moments, hist or None)."""
-        pairs_x = np.ascontiguousarray(pairs_x, dtype=np.int64)
-        pairs_y = np.ascontiguousarray(pairs_y, dtype=np.int64)
-        if pairs_x.ndim != 2 or pairs_x.shape[1:] != (2,) or pairs_x.shape != pairs_y.shape:
-            raise ValueError("pairs_x and pairs_y must be (n, 2) arrays of equal shape")
-        n = int(pairs_x.shape[0])
+        pairs_x, pairs_y, n = self._id_rows(pairs_x, pairs_y, 2, "pairs")
         ex, bx, ey, by, hist = self._compare_hist(edges)
-        out, bad = PairMoments(), ctypes.c_int64(0)
-        rc = self._lib.st_compare_pairs_host(self.handle, other.handle, _ptr(pairs_x) if n else None, _ptr(pairs_y) if n else None, n,
-                                             _ptr(ex), bx, _ptr(ey), by, ctypes.byref(out), _ptr(hist), ctypes.byref(bad))
-        self._compare_check(other, rc, bad)
+        out = PairMoments()
+        self._compare_call(self._lib.st_compare_pairs_host, other, (pairs_x, pairs_y, n, ex, bx, ey, by), out, hist)
         return out, hist
 
     def compare_triangle_ranks_host(self, other, ids_x, ids_y, k_begin=0, k_count=None, chunk_pairs=0):
         """compare_triangle_host without a histogram plus the exact rank sums of the same pairs
         (st_compare_triangle_ranks_host).  Returns (moments, ``RankSums``)."""
-        ids_x = np.ascontiguousarray(ids_x, dtype=np.int64)
-        ids_y = np.ascontiguousarray(ids_y, dtype=np.int64)
-        if ids_x.ndim != 1 or ids_x.shape != ids_y.shape:
-            raise ValueError("ids_x and ids_y must be 1-D arrays of equal length")
-        m = int(ids_x.shape[0])
-        if k_count is None:
-            k_count = m * (m - 1) // 2 - int(k_begin)
-        out, ranks, bad = PairMoments(), RankSums(), ctypes.c_int64(0)
-        rc = self._lib.st_compare_triangle_ranks_host(self.handle, other.handle, _ptr(ids_x) if m else None, _ptr(ids_y) if m else None,
-                                                      m, int(k_begin), int(k_count), int(chunk_pairs), ctypes.byref(out),
-                                                      ctypes.byref(ranks), ctypes.byref(bad))
-        self._compare_check(other, rc, bad)
+        ids_x, ids_y, m = self._id_lists(ids_x, ids_y)
+        out, ranks = PairMoments(), RankSums()
+        self._compare_call(self._lib.st_compare_triangle_ranks_host, other,
+                           (ids_x, ids_y, m, int(k_begin), self._triangle_count(m, k_begin, k_count), int(chunk_pairs)), out, ranks)
         return out, ranks
 
     def compare_pairs_ranks_host(self, other, pairs_x, pairs_y, chunk_pairs=0):
         """The same over explicit pairs (st_compare_pairs_ranks_host).  Returns (moments, ``RankSums``)."""
-        pairs_x = np.ascontiguousarray(pairs_x, dtype=np.int64)
-        pairs_y = np.ascontiguousarray(pairs_y, dtype=np.int64)
-        if pairs_x.ndim != 2 or pairs_x.shape[1:] != (2,) or pairs_x.shape != pairs_y.shape:
-            raise ValueError("pairs_x and pairs_y must be (n, 2) arrays of equal shape")
-        n = int(pairs_x.shape[0])
-        out, ranks, bad = PairMoments(), RankSums(), ctypes.c_int64(0)
-        rc = self._lib.st_compare_pairs_ranks_host(self.handle, other.handle, _ptr(pairs_x) if n else None, _ptr(pairs_y) if n else None,
-                                                   n, int(chunk_pairs), ctypes.byref(out), ctypes.byref(ranks), ctypes.byref(bad))
-        self._compare_check(other, rc, bad)
+        pairs_x, pairs_y, n = self._id_rows(pairs_x, pairs_y, 2, "pairs")
+        out, ranks = PairMoments(), RankSums()
+        self._compare_call(self._lib.st_compare_pairs_ranks_host, other, (pairs_x, pairs_y, n, int(chunk_pairs)), out, ranks)
         return out, ranks
 
     def compare_triangle_kendall_host(self, other, ids_x, ids_y, k_begin=0, k_count=None, chunk_pairs=0):
         """compare_triangle_host without a histogram plus the exact Kendall counts of the same pairs
         (st_compare_triangle_kendall_host).  Returns (moments, ``KendallCounts``)."""
-        ids_x = np.ascontiguousarray(ids_x, dtype=np.int64)
-        ids_y = np.ascontiguousarray(ids_y, dtype=np.int64)
-        if ids_x.ndim != 1 or ids_x.shape != ids_y.shape:
-            raise ValueError("ids_x and ids_y must be 1-D arrays of equal length")
-        m = int(ids_x.shape[0])
-        if k_count is None:
-            k_count = m * (m - 1) // 2 - int(k_begin)
-        out, counts, bad = PairMoments(), KendallCounts(), ctypes.c_int64(0)
-        rc = self._lib.st_compare_triangle_kendall_host(self.handle, other.handle, _ptr(ids_x) if m else None, _ptr(ids_y) if m else None,
-                                                        m, int(k_begin), int(k_count), int(chunk_pairs), ctypes.byref(out),
-                                                        ctypes.byref(counts), ctypes.byref(bad))
-        self._compare_check(other, rc, bad)
+        ids_x, ids_y, m = self._id_lists(ids_x, ids_y)
+        out, counts = PairMoments(), KendallCounts()
+        self._compare_call(self._lib.st_compare_triangle_kendall_host, other,
+                           (ids_x, ids_y, m, int(k_begin), self._triangle_count(m, k_begin, k_count), int(chunk_pairs)), out, counts)
         return out, counts
 
     def compare_pairs_kendall_host(self, other, pairs_x, pairs_y, chunk_pairs=0):
         """The same over explicit pairs (st_compare_pairs_kendall_host).  Returns (moments, ``KendallCounts``)."""
-        pairs_x = np.ascontiguousarray(pairs_x, dtype=np.int64)
-        pairs_y = np.ascontiguousarray(pairs_y, dtype=np.int64)
-        if pairs_x.ndim != 2 or pairs_x.shape[1:] != (2,) or pairs_x.shape != pairs_y.shape:
-            raise ValueError("pairs_x and pairs_y must be (n, 2) arrays of equal shape")
-        n = int(pairs_x.shape[0])
-        out, counts, bad = PairMoments(), KendallCounts(), ctypes.c_int64(0)
-        rc = self._lib.st_compare_pairs_kendall_host(self.handle, other.handle, _ptr(pairs_x) if n else None, _ptr(pairs_y) if n else None,
-                                                     n, int(chunk_pairs), ctypes.byref(out), ctypes.byref(counts), ctypes.byref(bad))
-        self._compare_check(other, rc, bad)
+        pairs_x, pairs_y, n = self._id_rows(pairs_x, pairs_y, 2, "pairs")
+        out, counts = PairMoments(), KendallCounts()
+        self._compare_call(self._lib.st_compare_pairs_kendall_host, other, (pairs_x, pairs_y, n, int(chunk_pairs)), out, counts)
         return out, counts
 
     def compare_quartets_leaves_host(self, other, ids_x, ids_y, mode="all", seed=0, k_begin=0, k_count=None, chunk_quartets=0):
@@ -918,39 +910,27 @@ class DeviceTree:
         [k_begin, k_begin + k_count) generated on the GPU over the aligned id lists ``ids_x`` (this tree) and ``ids_y``
         (``other``): ``mode`` "all" = the C(m,4) subsets in colexicographic order (k_count None: up to the last),
         "sample" = quartet k drawn from (seed, k, m) (st_compare_quartets_leaves_host)."""
-        ids_x = np.ascontiguousarray(ids_x, dtype=np.int64)
-        ids_y = np.ascontiguousarray(ids_y, dtype=np.int64)
-        if ids_x.ndim != 1 or ids_x.shape != ids_y.shape:
-            raise ValueError("ids_x and ids_y must be 1-D arrays of equal length")
+        ids_x, ids_y, m = self._id_lists(ids_x, ids_y)
         if mode not in QUARTET_MODE:
             raise ValueError("mode must be 'all' or 'sample'")
-        m = int(ids_x.shape[0])
         if k_count is None:
             if mode != "all":
                 raise ValueError("a sample needs k_count")
             if m > QUARTET_MAX_LEAVES_ALL:
                 raise ValueError("all quartets of %d leaves: at most %d leaves" % (m, QUARTET_MAX_LEAVES_ALL))
             k_count = (m * (m - 1) * (m - 2) * (m - 3) // 24 if m >= 4 else 0) - int(k_begin)
-        out, bad = QuartetTable(), ctypes.c_int64(0)
-        rc = self._lib.st_compare_quartets_leaves_host(self.handle, other.handle, _ptr(ids_x) if m else None, _ptr(ids_y) if m else None,
-                                                       m, QUARTET_MODE[mode], int(seed) & 0xFFFFFFFFFFFFFFFF, int(k_begin), int(k_count),
-                                                       int(chunk_quartets), ctypes.byref(out), ctypes.byref(bad))
-        self._compare_check(other, rc, bad)
+        out = QuartetTable()
+        self._compare_call(self._lib.st_compare_quartets_leaves_host, other,
+                           (ids_x, ids_y, m, QUARTET_MODE[mode], int(seed) & 0xFFFFFFFFFFFFFFFF, int(k_begin), int(k_count), int(chunk_quartets)),
+                           out)
         return out.as_array()
 
     def compare_quartets_host(self, other, quartets_x, quartets_y, chunk_quartets=0):
         """The same table over explicit quartets: row i of ``quartets_x`` (int64 (n,4)) in this tree against row i of
         ``quartets_y`` in ``other`` (st_compare_quartets_host)."""
-        quartets_x = np.ascontiguousarray(quartets_x, dtype=np.int64)
-        quartets_y = np.ascontiguousarray(quartets_y, dtype=np.int64)
-        if quartets_x.ndim != 2 or quartets_x.shape[1:] != (4,) or quartets_x.shape != quartets_y.shape:
-            raise ValueError("quartets_x and quartets_y must be (n, 4) arrays of equal shape")
-        n = int(quartets_x.shape[0])
-        out, bad = QuartetTable(), ctypes.c_int64(0)
-        rc = self._lib.st_compare_quartets_host(self.handle, other.handle, _ptr(quartets_x) if n else None,
-                                                _ptr(quartets_y) if n else None, n, int(chunk_quartets), ctypes.byref(out),
-                                                ctypes.byref(bad))
-        self._compare_check(other, rc, bad)
+        quartets_x, quartets_y, n = self._id_rows(quartets_x, quartets_y, 4, "quartets")
+        out = QuartetTable()
+        self._compare_call(self._lib.st_compare_quartets_host, other, (quartets_x, quartets_y, n, int(chunk_quartets)), out)
         return out.as_array()
 
     def compare_clades_host(self, other, parent, ids_x, ids_y, max_links=None, chunk_pairs=0):
@@ -959,11 +939,8 @@ class DeviceTree:
         Returns (structured array of st_pair_moments fields, per-node link counts); n = -1 marks a node over
         ``max_links``."""
         parent = np.ascontiguousarray(parent, dtype=np.int32)
-        ids_x = np.ascontiguousarray(ids_x, dtype=np.int64)
-        ids_y = np.ascontiguousarray(ids_y, dtype=np.int64)
-        if ids_x.ndim != 1 or ids_x.shape != ids_y.shape:
-            raise ValueError("ids_x and ids_y must be 1-D arrays of equal length")
-        n, m = int(parent.shape[0]), int(ids_x.shape[0])
+        ids_x, ids_y, m = self._id_lists(ids_x, ids_y)
+        n = int(parent.shape[0])
         out = np.zeros(n, dtype=PAIR_MOMENTS)
         count = np.zeros(n, dtype=np.int64)
         bad = ctypes.c_int64(0)
@@ -987,11 +964,7 @@ class DeviceTree:
             raise ValueError("ids_x and ids_y must be 2-D arrays of equal shape")
         n_rows, m = (int(v) for v in ids_x.shape)
         out = np.zeros(n_rows, dtype=PAIR_MOMENTS)
-        bad = ctypes.c_int64(0)
-        has = n_rows * m > 0
-        rc = self._lib.st_compare_rows_host(self.handle, other.handle, _ptr(ids_x) if has else None, _ptr(ids_y) if has else None,
-                                            n_rows, m, int(chunk_pairs), _ptr(out) if n_rows else None, ctypes.byref(bad))
-        self._compare_check(other, rc, bad)
+        self._compare_call(self._lib.st_compare_rows_host, other, (ids_x, ids_y, n_rows, m, int(chunk_pairs)), out)
         return out
 
     def triangle_device(self, d_ids, m, k_begin, k_count, d_out_dist=0, d_out_mrca=0, stream=0, id_stride=1):

@@ -201,37 +201,36 @@ def _needs_data_range(bins, range):
     return np.ndim(bins) == 0   # one edge array for both axes
 
 
-def run(call, bins, range, n_leaves=None, rank_call=None, kendall_call=None):
-    """call(edges) -> (PairMoments, hist): one pass of the library.  ``range=None`` with integer bins costs a second
-    pass: the first finds min and max, the second bins.  rank_call() -> (PairMoments, RankSums), if given, adds the
-    rank fields: alone it is the only call (its moments are call(None)'s); with ``bins`` the histogram calls run as
-    they do without it.  kendall_call() -> (PairMoments, KendallCounts), if given, adds the Kendall fields in the same
-    way: alone it is the only call; with ``bins`` or rank_call those run as they do without it, beside it."""
-    if kendall_call is not None:
-        m, counts = kendall_call()
-        if bins is None and rank_call is None:
-            return DistanceComparison.from_moments(m, n_leaves=n_leaves, kendall=counts)
-        return replace(run(call, bins, range, n_leaves, rank_call), **kendall_fields(counts))
-    if rank_call is not None:
-        m, ranks = rank_call()
-        if bins is None:
-            return DistanceComparison.from_moments(m, n_leaves=n_leaves, ranks=ranks)
-        return replace(run(call, bins, range, n_leaves), **rank_fields(ranks))
-    if bins is None:
-        m, _ = call(None)
-        return DistanceComparison.from_moments(m, n_leaves=n_leaves)
-    if _needs_data_range(bins, range):
-        m, _ = call(None)
-        if m.n == 0:
-            raise ValueError("autodetected range of an empty set of pairs: give range=")
-        mm = (m.min_x, m.max_x, m.min_y, m.max_y)
-        if not all(np.isfinite(mm)):
-            raise ValueError("autodetected range of [%r, %r] x [%r, %r] is not finite" % mm)
-        xedges, yedges = histogram_edges(bins, None, mm)
-    else:
-        xedges, yedges = histogram_edges(bins, range, None)
-    m, hist = call((xedges, yedges))
-    return DistanceComparison.from_moments(m, hist, xedges, yedges, n_leaves=n_leaves)
+def run(dx, dy, kind, arrays, bins, range, n_leaves=None, spearman=False, kendall=False):
+    """The library calls behind compare_distances and linked_distances_summary, over one pair input of the
+    ``_capi.DeviceTree`` s ``dx`` (x) and ``dy`` (y): ``kind`` "triangle" with ``arrays`` = two aligned id lists, or "pairs"
+    with two (n, 2) id arrays.  ``kendall`` and ``spearman`` each cost their own call, in that order, which also returns
+    the moments: without ``bins`` no other call is made.  With ``bins`` the moments call follows with the edges, after
+    one without when ``range=None`` leaves numpy's range to the data (the first pass finds min and max, the second
+    bins), and the moments are its.  With none of the three there is one moments call."""
+    def call(stat, **kw):
+        return getattr(dx, "compare_%s%s_host" % (kind, stat))(dy, *arrays, **kw)
+
+    ranks = counts = hist = xedges = yedges = None
+    if kendall:
+        m, counts = call("_kendall")
+    if spearman:
+        m, ranks = call("_ranks")
+    if bins is not None:
+        if _needs_data_range(bins, range):
+            m, _ = call("", edges=None)
+            if m.n == 0:
+                raise ValueError("autodetected range of an empty set of pairs: give range=")
+            mm = (m.min_x, m.max_x, m.min_y, m.max_y)
+            if not all(np.isfinite(mm)):
+                raise ValueError("autodetected range of [%r, %r] x [%r, %r] is not finite" % mm)
+            xedges, yedges = histogram_edges(bins, None, mm)
+        else:
+            xedges, yedges = histogram_edges(bins, range, None)
+        m, hist = call("", edges=(xedges, yedges))
+    elif not (spearman or kendall):
+        m, _ = call("", edges=None)
+    return DistanceComparison.from_moments(m, hist, xedges, yedges, n_leaves=n_leaves, ranks=ranks, kendall=counts)
 
 
 def pearson_pvalue(r, n):

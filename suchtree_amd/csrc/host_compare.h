@@ -5,8 +5,9 @@
 // by the histogram or the pieces: nothing grows with the pair count.  What needs no GPU -- the clade plan and its
 // tables, the rows layout, the folding of pieces -- is compare_plan.cpp.  The exact Spearman rank sums (compare_ranks)
 // are three such runs around count tables that the entry point owns (kernels_ranks.h, rank_plan.cpp); the exact Kendall
-// counts (compare_kendall, at the end) are one run that keeps every pair's key, then a sort (kernels_kendall.h,
-// kendall_plan.cpp).
+// counts (compare_kendall) are one run that keeps every pair's key, then a sort (kernels_kendall.h, kendall_plan.cpp).
+// The entry points st_compare_{triangle,pairs}[_ranks|_kendall]_host are one skeleton, compare_entry (at the end), over
+// a pair input (TriangleInput, PairsInput, after compare_run) and a statistic (MomentsStat, RanksStat, KendallStat).
 #pragma once
 
 constexpr int64_t kCompareChunkTriangle = (int64_t)1 << 25;   // 2 x 128 MiB of float32 distances
@@ -184,6 +185,85 @@ static int compare_run(st_tree *tx, st_tree *ty, int64_t count, int64_t chunk, s
     if (rc != ST_OK) return rc;
     return red.done();
 }
+
+// ---- the two pair inputs of compare_entry (at the end): what the caller's pairs are, how they are checked and how one
+// compare_run goes over them.  A new pair source is one more such struct.
+static int triangle_range_args(int64_t m, int64_t k_begin, int64_t k_count)      // (st_triangle_* check their range with it too)
+{
+    if (m < 0 || k_begin < 0 || k_count < 0) return fail(ST_ERR_ARG, "negative size");
+    if (m > 3000000000LL) return fail(ST_ERR_ARG, "m too large");
+    if (k_begin + k_count > m * (m - 1) / 2) return fail(ST_ERR_ARG, "pair range exceeds m(m-1)/2");
+    return ST_OK;
+}
+
+// ids on the host, before anything is launched: ST_ERR_BOUNDS with the id the reference reports (MuchTree.pyx:897-903)
+static int compare_check_ids(const int64_t *ids, int64_t n, int64_t n_nodes, int64_t *bad_id)
+{
+    Fault f = kFaultInit;
+    ids_in_range(ids, n, n_nodes, f.max_bad, f.min_bad);
+    return report_fault(n_nodes, f, bad_id);
+}
+
+// n ids of tree X, then n of tree Y
+static int compare_check_ids(st_tree *tx, st_tree *ty, const int64_t *ids_x, const int64_t *ids_y, int64_t n, int64_t *bad_id)
+{
+    const int rc = compare_check_ids(ids_x, n, tx->n_nodes, bad_id);
+    return rc != ST_OK ? rc : compare_check_ids(ids_y, n, ty->n_nodes, bad_id);
+}
+
+// pairs [k_begin, k_begin + k_count) of the triangle over two aligned id lists; chunk_pairs 0: the path's default chunk
+struct TriangleInput {
+    const int64_t *ids_x, *ids_y;
+    int64_t m, k_begin, k_count;
+
+    int64_t count() const { return k_count; }
+    int range_args() const { return triangle_range_args(m, k_begin, k_count); }
+    int null_args() const { return m > 0 && (!ids_x || !ids_y) ? fail(ST_ERR_ARG, "ids_x or ids_y is NULL") : ST_OK; }
+    int check_ids(st_tree *tx, st_tree *ty, int64_t *bad_id) const { return compare_check_ids(tx, ty, ids_x, ids_y, m, bad_id); }
+    template <typename Reduce>
+    int run(st_tree *tx, st_tree *ty, int64_t chunk_pairs, Reduce &red, int64_t *bad_id) const
+    {
+        auto setup = [&](char *d_extra, hipStream_t s) {
+            hipError_t e = hipMemcpyAsync(d_extra, ids_x, (size_t)m * 8, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_extra + (size_t)m * 8, ids_y, (size_t)m * 8, hipMemcpyHostToDevice, s);
+            return e;
+        };
+        auto prep = [](char *, hipStream_t, int64_t, int64_t) { return hipSuccess; };
+        auto src_x = [&](char *d_extra, int64_t off) {
+            return SrcTriangle{reinterpret_cast<const long long *>(d_extra), 1, (long long)(k_begin + off)};
+        };
+        auto src_y = [&](char *d_extra, int64_t off) {
+            return SrcTriangle{reinterpret_cast<const long long *>(d_extra) + m, 1, (long long)(k_begin + off)};
+        };
+        return compare_run(tx, ty, k_count, chunk_pairs > 0 ? chunk_pairs : kCompareChunkTriangle, (size_t)m * 16, setup, prep, src_x, src_y,
+                           red, bad_id);
+    }
+};
+
+// n explicit pairs, row i of pairs_x in tree X against row i of pairs_y in tree Y, uploaded chunk by chunk
+struct PairsInput {
+    const int64_t *pairs_x, *pairs_y;
+    int64_t n;
+
+    int64_t count() const { return n; }
+    int range_args() const { return n < 0 ? fail(ST_ERR_ARG, "n < 0") : ST_OK; }
+    int null_args() const { return n > 0 && (!pairs_x || !pairs_y) ? fail(ST_ERR_ARG, "pairs_x or pairs_y is NULL") : ST_OK; }
+    int check_ids(st_tree *tx, st_tree *ty, int64_t *bad_id) const { return compare_check_ids(tx, ty, pairs_x, pairs_y, 2 * n, bad_id); }
+    template <typename Reduce>
+    int run(st_tree *tx, st_tree *ty, int64_t chunk_pairs, Reduce &red, int64_t *bad_id) const
+    {
+        const int64_t chunk = std::min(n, chunk_pairs > 0 ? chunk_pairs : kCompareChunkPairs);
+        auto setup = [](char *, hipStream_t) { return hipSuccess; };
+        auto prep = [&](char *d_extra, hipStream_t s, int64_t off, int64_t c) {
+            hipError_t e = hipMemcpyAsync(d_extra, pairs_x + 2 * off, (size_t)c * 16, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_extra + (size_t)chunk * 16, pairs_y + 2 * off, (size_t)c * 16, hipMemcpyHostToDevice, s);
+            return e;
+        };
+        auto src_x = [](char *d_extra, int64_t) { return SrcContig{reinterpret_cast<const long long *>(d_extra)}; };
+        auto src_y = [&](char *d_extra, int64_t) { return SrcContig{reinterpret_cast<const long long *>(d_extra + (size_t)chunk * 16)}; };
+        return compare_run(tx, ty, n, chunk, (size_t)chunk * 32, setup, prep, src_x, src_y, red, bad_id);
+    }
+};
 
 // The reducer of st_compare_clades_host: k_clade_pieces per chunk into one device array of pieces, read back at the end;
 // done() merges pieces into segments (index order) and segments into nodes (children first, in id order, then the
@@ -641,4 +721,99 @@ static int kendall_arrays(int device, const float *x, const float *y, int64_t n,
     if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("Kendall counts: ") + hipGetErrorString(e));
     K.done(out);
     return ST_OK;
+}
+
+// ---- the entry points: pair input x statistic (st_compare_{triangle,pairs}[_ranks|_kendall]_host) ----------------------
+static int compare_trees_args(st_tree *tx, st_tree *ty)
+{
+    if (!tx || !ty) return fail(ST_ERR_ARG, "tree_x or tree_y is NULL");
+    if (tx->device != ty->device)
+        return fail(ST_ERR_ARG, "tree_x is on device " + std::to_string(tx->device) + ", tree_y on device " + std::to_string(ty->device) +
+                                    ": both trees must live on the same device");
+    return ST_OK;
+}
+
+static int chunk_pairs_arg(int64_t chunk_pairs)
+{
+    if (chunk_pairs >= 0 && chunk_pairs % ST_CLADE_TILE == 0) return ST_OK;
+    return fail(ST_ERR_ARG, "chunk_pairs must be 0 or a positive multiple of " + std::to_string(ST_CLADE_TILE));
+}
+
+// the chunk, then the count (ranks and Kendall counts: at most 2^31 - 1 pairs)
+static int rank_count_args(int64_t chunk_pairs, int64_t n, const char *what)
+{
+    const int rc = chunk_pairs_arg(chunk_pairs);
+    if (rc != ST_OK || n <= kRankMaxPairs) return rc;
+    return fail(ST_ERR_ARG, std::string(what) + " of " + std::to_string(n) + " pairs: at most " + std::to_string(kRankMaxPairs) + " (2^31 - 1)");
+}
+
+static int compare_empty(st_pair_moments *out, int64_t *out_hist, int32_t bins_x, int32_t bins_y)
+{
+    *out = moments_empty();
+    if (out_hist) std::memset(out_hist, 0, (size_t)bins_x * (size_t)bins_y * 8);
+    return ST_OK;
+}
+
+// A statistic holds its output pointers (and its chunk): out_args() checks them, count_args(n) what it asks of the pair
+// count, empty() is the result of no pairs, go(tx, n, run) computes it -- run(chunk_pairs, reducer) is one compare_run
+// over the caller's pairs.  A new statistic is one more such struct.
+struct MomentsStat {
+    const double *edges_x, *edges_y;
+    int32_t bins_x, bins_y;
+    st_pair_moments *out;
+    int64_t *out_hist;
+
+    int out_args() const
+    {
+        std::string err;
+        const int rc = compare_hist_args(edges_x, bins_x, edges_y, bins_y, out_hist, kCmpMaxCells, err);
+        if (rc != ST_OK) return fail(rc, err);
+        return out ? ST_OK : fail(ST_ERR_ARG, "out is NULL");
+    }
+    int count_args(int64_t) const { return ST_OK; }
+    int empty() const { return compare_empty(out, out_hist, bins_x, bins_y); }
+    template <typename Run>
+    int go(st_tree *, int64_t, Run run) const { MomentsReduce red{edges_x, edges_y, bins_x, bins_y, out, out_hist}; return run((int64_t)0, red); }
+};
+
+struct RanksStat {
+    int64_t chunk_pairs;
+    st_pair_moments *out;
+    st_rank_sums *out_ranks;
+
+    int out_args() const { return out && out_ranks ? ST_OK : fail(ST_ERR_ARG, "out or out_ranks is NULL"); }
+    int count_args(int64_t n) const { return rank_count_args(chunk_pairs, n, "ranks"); }
+    int empty() const { rank_finish(0, 0, 0, 0, 0, 0, 0, out_ranks); return compare_empty(out, nullptr, 0, 0); }
+    template <typename Run>
+    int go(st_tree *tx, int64_t n, Run run) const { return compare_ranks(tx, n, chunk_pairs, run, out, out_ranks); }
+};
+
+struct KendallStat {
+    int64_t chunk_pairs;
+    st_pair_moments *out;
+    st_kendall_counts *out_counts;
+
+    int out_args() const { return out && out_counts ? ST_OK : fail(ST_ERR_ARG, "out or out_counts is NULL"); }
+    int count_args(int64_t n) const { return rank_count_args(chunk_pairs, n, "Kendall counts"); }
+    int empty() const { kendall_finish(0, 0, 0, 0, 0, 0, out_counts); return compare_empty(out, nullptr, 0, 0); }
+    template <typename Run>
+    int go(st_tree *tx, int64_t n, Run run) const { return compare_kendall(tx, n, chunk_pairs, run, out, out_counts); }
+};
+
+// What every such entry point does, in the order in which its errors are reported: the statistic's outputs, the trees,
+// the input's range, the chunk and the count, the NULL id arrays; then the empty result, or the ids (tree X's first) and
+// the run.
+template <typename In, typename Stat>
+static int compare_entry(st_tree *tx, st_tree *ty, const In &in, Stat &&stat, int64_t *bad_id)
+{
+    int rc = stat.out_args();
+    if (rc == ST_OK) rc = compare_trees_args(tx, ty);
+    if (rc == ST_OK) rc = in.range_args();
+    if (rc == ST_OK) rc = stat.count_args(in.count());
+    if (rc == ST_OK) rc = in.null_args();
+    if (rc != ST_OK) return rc;
+    if (in.count() == 0) return stat.empty();
+    rc = in.check_ids(tx, ty, bad_id);
+    if (rc != ST_OK) return rc;
+    return stat.go(tx, in.count(), [&](int64_t chunk, auto &red) { return in.run(tx, ty, chunk, red, bad_id); });
 }

@@ -30,7 +30,8 @@
 // enqueueing, faults), host_path.h (host-buffer pipeline, mailbox, copy kernels), host_upload.h (tables -> device),
 // kernels_misc.h (k nearest, graph matrices), and the compare paths (st_compare_*: two trees' distances over the same
 // pairs, reduced on the device): kernels_compare.h / kernels_clades.h / kernels_rows.h (moments and 2-D histogram, clade
-// pieces, row blocks), host_compare.h (TwoTreeSession, the chunk driver compare_run and its reducers) and,
+// pieces, row blocks), host_compare.h (TwoTreeSession, the chunk driver compare_run and its reducers, the pair inputs,
+// statistics and the one skeleton, compare_entry, of the triangle / pairs entry points) and,
 // host-only C++ beside tree_prep.cpp, compare_plan.cpp (argument checks, clade plan and tables, rows layout, the fold).
 // Exact Spearman rank sums of the same pairs (st_compare_*_ranks_host): kernels_ranks.h, the reducers at the end of
 // host_compare.h and, host-only, rank_plan.cpp (keys, bucket layout, tie arithmetic, st_spearman_host).
@@ -740,14 +741,6 @@ try {
     return distances_host_impl(t, pairs, n, stride0, stride1, out_dist, out_mrca, bad_id);
 } ST_CATCH_ALL
 
-static int triangle_range_args(int64_t m, int64_t k_begin, int64_t k_count)
-{
-    if (m < 0 || k_begin < 0 || k_count < 0) return fail(ST_ERR_ARG, "negative size");
-    if (m > 3000000000LL) return fail(ST_ERR_ARG, "m too large");
-    if (k_begin + k_count > m * (m - 1) / 2) return fail(ST_ERR_ARG, "pair range exceeds m(m-1)/2");
-    return ST_OK;
-}
-
 static int triangle_args(st_tree *t, const int64_t *ids, int64_t m, int64_t k_begin, int64_t k_count,
                          const void *out_d, const void *out_m)
 {
@@ -911,173 +904,38 @@ try {
 
 }  // extern "C"
 
-// ---- compare paths (st_compare_*_host, st_clade_plan): validate, stage, call compare_run (host_compare.h) -----------
-// ids on the host, before anything is launched: ST_ERR_BOUNDS with the id the reference reports (MuchTree.pyx:897-903)
-static int compare_check_ids(const int64_t *ids, int64_t n, int64_t n_nodes, int64_t *bad_id)
-{
-    Fault f = kFaultInit;
-    ids_in_range(ids, n, n_nodes, f.max_bad, f.min_bad);
-    return report_fault(n_nodes, f, bad_id);
-}
-
-static int compare_trees_args(st_tree *tx, st_tree *ty)
-{
-    if (!tx || !ty) return fail(ST_ERR_ARG, "tree_x or tree_y is NULL");
-    if (tx->device != ty->device)
-        return fail(ST_ERR_ARG, "tree_x is on device " + std::to_string(tx->device) + ", tree_y on device " + std::to_string(ty->device) +
-                                    ": both trees must live on the same device");
-    return ST_OK;
-}
-
-static int chunk_pairs_arg(int64_t chunk_pairs)
-{
-    if (chunk_pairs >= 0 && chunk_pairs % ST_CLADE_TILE == 0) return ST_OK;
-    return fail(ST_ERR_ARG, "chunk_pairs must be 0 or a positive multiple of " + std::to_string(ST_CLADE_TILE));
-}
-
-static void compare_empty(st_pair_moments *out, int64_t *out_hist, int32_t bins_x, int32_t bins_y)
-{
-    *out = moments_empty();
-    if (out_hist) std::memset(out_hist, 0, (size_t)bins_x * (size_t)bins_y * 8);
-}
-
-// one compare_run over pairs [k_begin, k_begin + k_count) of the triangle / over n explicit pairs (arguments checked by
-// the caller); chunk_pairs 0: the path's default chunk
-template <typename Reduce>
-static int compare_triangle_run(st_tree *tx, st_tree *ty, const int64_t *ids_x, const int64_t *ids_y, int64_t m, int64_t k_begin,
-                                int64_t k_count, int64_t chunk_pairs, Reduce &red, int64_t *bad_id)
-{
-    auto setup = [&](char *d_extra, hipStream_t s) {
-        hipError_t e = hipMemcpyAsync(d_extra, ids_x, (size_t)m * 8, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_extra + (size_t)m * 8, ids_y, (size_t)m * 8, hipMemcpyHostToDevice, s);
-        return e;
-    };
-    auto prep = [](char *, hipStream_t, int64_t, int64_t) { return hipSuccess; };
-    auto src_x = [&](char *d_extra, int64_t off) {
-        return SrcTriangle{reinterpret_cast<const long long *>(d_extra), 1, (long long)(k_begin + off)};
-    };
-    auto src_y = [&](char *d_extra, int64_t off) {
-        return SrcTriangle{reinterpret_cast<const long long *>(d_extra) + m, 1, (long long)(k_begin + off)};
-    };
-    return compare_run(tx, ty, k_count, chunk_pairs > 0 ? chunk_pairs : kCompareChunkTriangle, (size_t)m * 16, setup, prep, src_x, src_y, red,
-                       bad_id);
-}
-
-template <typename Reduce>
-static int compare_pairs_run(st_tree *tx, st_tree *ty, const int64_t *pairs_x, const int64_t *pairs_y, int64_t n, int64_t chunk_pairs,
-                             Reduce &red, int64_t *bad_id)
-{
-    const int64_t chunk = std::min(n, chunk_pairs > 0 ? chunk_pairs : kCompareChunkPairs);
-    auto setup = [](char *, hipStream_t) { return hipSuccess; };
-    auto prep = [&](char *d_extra, hipStream_t s, int64_t off, int64_t c) {
-        hipError_t e = hipMemcpyAsync(d_extra, pairs_x + 2 * off, (size_t)c * 16, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_extra + (size_t)chunk * 16, pairs_y + 2 * off, (size_t)c * 16, hipMemcpyHostToDevice, s);
-        return e;
-    };
-    auto src_x = [](char *d_extra, int64_t) { return SrcContig{reinterpret_cast<const long long *>(d_extra)}; };
-    auto src_y = [&](char *d_extra, int64_t) { return SrcContig{reinterpret_cast<const long long *>(d_extra + (size_t)chunk * 16)}; };
-    return compare_run(tx, ty, n, chunk, (size_t)chunk * 32, setup, prep, src_x, src_y, red, bad_id);
-}
-
-static int rank_count_arg(int64_t n, const char *what = "ranks")
-{
-    if (n <= kRankMaxPairs) return ST_OK;
-    return fail(ST_ERR_ARG, std::string(what) + " of " + std::to_string(n) + " pairs: at most " + std::to_string(kRankMaxPairs) + " (2^31 - 1)");
-}
-
+// ---- compare paths (st_compare_*_host, st_clade_plan) ---------------------------------------------------------------
+// st_compare_{triangle,pairs}[_ranks|_kendall]_host are compare_entry (host_compare.h) over a pair input -- TriangleInput,
+// PairsInput -- and a statistic -- MomentsStat, RanksStat, KendallStat: a new input or statistic is a struct there and one
+// line here per entry point.  st_compare_clades_host and st_compare_rows_host stage their own pairs and call compare_run
+// themselves; st_compare_quartets[_leaves]_host (further down) spell the same ladder out around quartet_run.
 extern "C" {
 
 int st_compare_triangle_host(st_tree *tx, st_tree *ty, const int64_t *ids_x, const int64_t *ids_y, int64_t m, int64_t k_begin,
                              int64_t k_count, const double *edges_x, int32_t bins_x, const double *edges_y, int32_t bins_y,
                              st_pair_moments *out, int64_t *out_hist, int64_t *bad_id)
 try {
-    std::string err;
-    int rc = compare_hist_args(edges_x, bins_x, edges_y, bins_y, out_hist, kCmpMaxCells, err);
-    if (rc != ST_OK) return fail(rc, err);
-    if (!out) return fail(ST_ERR_ARG, "out is NULL");
-    rc = compare_trees_args(tx, ty);
-    if (rc != ST_OK) return rc;
-    rc = triangle_range_args(m, k_begin, k_count);
-    if (rc != ST_OK) return rc;
-    if (m > 0 && (!ids_x || !ids_y)) return fail(ST_ERR_ARG, "ids_x or ids_y is NULL");
-    if (k_count == 0) {
-        compare_empty(out, out_hist, bins_x, bins_y);
-        return ST_OK;
-    }
-    rc = compare_check_ids(ids_x, m, tx->n_nodes, bad_id);
-    if (rc == ST_OK) rc = compare_check_ids(ids_y, m, ty->n_nodes, bad_id);
-    if (rc != ST_OK) return rc;
-    MomentsReduce red{edges_x, edges_y, bins_x, bins_y, out, out_hist};
-    return compare_triangle_run(tx, ty, ids_x, ids_y, m, k_begin, k_count, 0, red, bad_id);
+    return compare_entry(tx, ty, TriangleInput{ids_x, ids_y, m, k_begin, k_count}, MomentsStat{edges_x, edges_y, bins_x, bins_y, out, out_hist},
+                         bad_id);
 } ST_CATCH_ALL
 
 int st_compare_pairs_host(st_tree *tx, st_tree *ty, const int64_t *pairs_x, const int64_t *pairs_y, int64_t n, const double *edges_x,
                           int32_t bins_x, const double *edges_y, int32_t bins_y, st_pair_moments *out, int64_t *out_hist,
                           int64_t *bad_id)
 try {
-    std::string err;
-    int rc = compare_hist_args(edges_x, bins_x, edges_y, bins_y, out_hist, kCmpMaxCells, err);
-    if (rc != ST_OK) return fail(rc, err);
-    if (!out) return fail(ST_ERR_ARG, "out is NULL");
-    rc = compare_trees_args(tx, ty);
-    if (rc != ST_OK) return rc;
-    if (n < 0) return fail(ST_ERR_ARG, "n < 0");
-    if (n > 0 && (!pairs_x || !pairs_y)) return fail(ST_ERR_ARG, "pairs_x or pairs_y is NULL");
-    if (n == 0) {
-        compare_empty(out, out_hist, bins_x, bins_y);
-        return ST_OK;
-    }
-    rc = compare_check_ids(pairs_x, 2 * n, tx->n_nodes, bad_id);
-    if (rc == ST_OK) rc = compare_check_ids(pairs_y, 2 * n, ty->n_nodes, bad_id);
-    if (rc != ST_OK) return rc;
-    MomentsReduce red{edges_x, edges_y, bins_x, bins_y, out, out_hist};
-    return compare_pairs_run(tx, ty, pairs_x, pairs_y, n, 0, red, bad_id);
+    return compare_entry(tx, ty, PairsInput{pairs_x, pairs_y, n}, MomentsStat{edges_x, edges_y, bins_x, bins_y, out, out_hist}, bad_id);
 } ST_CATCH_ALL
 
 int st_compare_triangle_ranks_host(st_tree *tx, st_tree *ty, const int64_t *ids_x, const int64_t *ids_y, int64_t m, int64_t k_begin,
                                    int64_t k_count, int64_t chunk_pairs, st_pair_moments *out, st_rank_sums *out_ranks, int64_t *bad_id)
 try {
-    if (!out || !out_ranks) return fail(ST_ERR_ARG, "out or out_ranks is NULL");
-    int rc = compare_trees_args(tx, ty);
-    if (rc != ST_OK) return rc;
-    rc = triangle_range_args(m, k_begin, k_count);
-    if (rc == ST_OK) rc = chunk_pairs_arg(chunk_pairs);
-    if (rc == ST_OK) rc = rank_count_arg(k_count);
-    if (rc != ST_OK) return rc;
-    if (m > 0 && (!ids_x || !ids_y)) return fail(ST_ERR_ARG, "ids_x or ids_y is NULL");
-    if (k_count == 0) {
-        compare_empty(out, nullptr, 0, 0);
-        rank_finish(0, 0, 0, 0, 0, 0, 0, out_ranks);
-        return ST_OK;
-    }
-    rc = compare_check_ids(ids_x, m, tx->n_nodes, bad_id);
-    if (rc == ST_OK) rc = compare_check_ids(ids_y, m, ty->n_nodes, bad_id);
-    if (rc != ST_OK) return rc;
-    auto run = [&](int64_t chunk, auto &red) { return compare_triangle_run(tx, ty, ids_x, ids_y, m, k_begin, k_count, chunk, red, bad_id); };
-    return compare_ranks(tx, k_count, chunk_pairs, run, out, out_ranks);
+    return compare_entry(tx, ty, TriangleInput{ids_x, ids_y, m, k_begin, k_count}, RanksStat{chunk_pairs, out, out_ranks}, bad_id);
 } ST_CATCH_ALL
 
 int st_compare_pairs_ranks_host(st_tree *tx, st_tree *ty, const int64_t *pairs_x, const int64_t *pairs_y, int64_t n, int64_t chunk_pairs,
                                 st_pair_moments *out, st_rank_sums *out_ranks, int64_t *bad_id)
 try {
-    if (!out || !out_ranks) return fail(ST_ERR_ARG, "out or out_ranks is NULL");
-    int rc = compare_trees_args(tx, ty);
-    if (rc != ST_OK) return rc;
-    if (n < 0) return fail(ST_ERR_ARG, "n < 0");
-    rc = chunk_pairs_arg(chunk_pairs);
-    if (rc == ST_OK) rc = rank_count_arg(n);
-    if (rc != ST_OK) return rc;
-    if (n > 0 && (!pairs_x || !pairs_y)) return fail(ST_ERR_ARG, "pairs_x or pairs_y is NULL");
-    if (n == 0) {
-        compare_empty(out, nullptr, 0, 0);
-        rank_finish(0, 0, 0, 0, 0, 0, 0, out_ranks);
-        return ST_OK;
-    }
-    rc = compare_check_ids(pairs_x, 2 * n, tx->n_nodes, bad_id);
-    if (rc == ST_OK) rc = compare_check_ids(pairs_y, 2 * n, ty->n_nodes, bad_id);
-    if (rc != ST_OK) return rc;
-    auto run = [&](int64_t chunk, auto &red) { return compare_pairs_run(tx, ty, pairs_x, pairs_y, n, chunk, red, bad_id); };
-    return compare_ranks(tx, n, chunk_pairs, run, out, out_ranks);
+    return compare_entry(tx, ty, PairsInput{pairs_x, pairs_y, n}, RanksStat{chunk_pairs, out, out_ranks}, bad_id);
 } ST_CATCH_ALL
 
 int st_spearman_host(const float *x, const float *y, int64_t n, st_rank_sums *out)
@@ -1090,47 +948,13 @@ try {
 int st_compare_triangle_kendall_host(st_tree *tx, st_tree *ty, const int64_t *ids_x, const int64_t *ids_y, int64_t m, int64_t k_begin,
                                      int64_t k_count, int64_t chunk_pairs, st_pair_moments *out, st_kendall_counts *out_counts, int64_t *bad_id)
 try {
-    if (!out || !out_counts) return fail(ST_ERR_ARG, "out or out_counts is NULL");
-    int rc = compare_trees_args(tx, ty);
-    if (rc != ST_OK) return rc;
-    rc = triangle_range_args(m, k_begin, k_count);
-    if (rc == ST_OK) rc = chunk_pairs_arg(chunk_pairs);
-    if (rc == ST_OK) rc = rank_count_arg(k_count, "Kendall counts");
-    if (rc != ST_OK) return rc;
-    if (m > 0 && (!ids_x || !ids_y)) return fail(ST_ERR_ARG, "ids_x or ids_y is NULL");
-    if (k_count == 0) {
-        compare_empty(out, nullptr, 0, 0);
-        kendall_finish(0, 0, 0, 0, 0, 0, out_counts);
-        return ST_OK;
-    }
-    rc = compare_check_ids(ids_x, m, tx->n_nodes, bad_id);
-    if (rc == ST_OK) rc = compare_check_ids(ids_y, m, ty->n_nodes, bad_id);
-    if (rc != ST_OK) return rc;
-    auto run = [&](int64_t chunk, auto &red) { return compare_triangle_run(tx, ty, ids_x, ids_y, m, k_begin, k_count, chunk, red, bad_id); };
-    return compare_kendall(tx, k_count, chunk_pairs, run, out, out_counts);
+    return compare_entry(tx, ty, TriangleInput{ids_x, ids_y, m, k_begin, k_count}, KendallStat{chunk_pairs, out, out_counts}, bad_id);
 } ST_CATCH_ALL
 
 int st_compare_pairs_kendall_host(st_tree *tx, st_tree *ty, const int64_t *pairs_x, const int64_t *pairs_y, int64_t n, int64_t chunk_pairs,
                                   st_pair_moments *out, st_kendall_counts *out_counts, int64_t *bad_id)
 try {
-    if (!out || !out_counts) return fail(ST_ERR_ARG, "out or out_counts is NULL");
-    int rc = compare_trees_args(tx, ty);
-    if (rc != ST_OK) return rc;
-    if (n < 0) return fail(ST_ERR_ARG, "n < 0");
-    rc = chunk_pairs_arg(chunk_pairs);
-    if (rc == ST_OK) rc = rank_count_arg(n, "Kendall counts");
-    if (rc != ST_OK) return rc;
-    if (n > 0 && (!pairs_x || !pairs_y)) return fail(ST_ERR_ARG, "pairs_x or pairs_y is NULL");
-    if (n == 0) {
-        compare_empty(out, nullptr, 0, 0);
-        kendall_finish(0, 0, 0, 0, 0, 0, out_counts);
-        return ST_OK;
-    }
-    rc = compare_check_ids(pairs_x, 2 * n, tx->n_nodes, bad_id);
-    if (rc == ST_OK) rc = compare_check_ids(pairs_y, 2 * n, ty->n_nodes, bad_id);
-    if (rc != ST_OK) return rc;
-    auto run = [&](int64_t chunk, auto &red) { return compare_pairs_run(tx, ty, pairs_x, pairs_y, n, chunk, red, bad_id); };
-    return compare_kendall(tx, n, chunk_pairs, run, out, out_counts);
+    return compare_entry(tx, ty, PairsInput{pairs_x, pairs_y, n}, KendallStat{chunk_pairs, out, out_counts}, bad_id);
 } ST_CATCH_ALL
 
 int st_kendall_arrays_host(int device, const float *x, const float *y, int64_t n, st_kendall_counts *out)
@@ -1186,8 +1010,7 @@ try {
     if (n_links > 0 && (!ids_x || !ids_y)) return fail(ST_ERR_ARG, "ids_x or ids_y is NULL");
     rc = chunk_pairs_arg(chunk_pairs);
     if (rc != ST_OK) return rc;
-    rc = compare_check_ids(ids_x, n_links, tx->n_nodes, bad_id);
-    if (rc == ST_OK) rc = compare_check_ids(ids_y, n_links, ty->n_nodes, bad_id);
+    rc = compare_check_ids(tx, ty, ids_x, ids_y, n_links, bad_id);
     if (rc != ST_OK) return rc;
     CladePlan P;
     std::string err;
@@ -1246,8 +1069,7 @@ try {
     std::fill_n(out, n_rows, moments_empty());
     if (n_rows == 0 || L.P == 0) return ST_OK;      // (nothing to launch)
     const int64_t n_ids = n_rows * m;
-    rc = compare_check_ids(ids_x, n_ids, tx->n_nodes, bad_id);
-    if (rc == ST_OK) rc = compare_check_ids(ids_y, n_ids, ty->n_nodes, bad_id);
+    rc = compare_check_ids(tx, ty, ids_x, ids_y, n_ids, bad_id);
     if (rc != ST_OK) return rc;
     const std::vector<int32_t> hx(ids_x, ids_x + n_ids), hy(ids_y, ids_y + n_ids);      // (checked: below n_nodes)
     // device: the int32 ids of up to max_rows rows from row `up_lo` on, X then Y; uploaded again when a chunk needs others
@@ -1392,8 +1214,7 @@ try {
     if (m > 0 && (!ids_x || !ids_y)) return fail(ST_ERR_ARG, "ids_x or ids_y is NULL");
     *out = st_quartet_table{};
     if (k_count == 0) return ST_OK;
-    rc = compare_check_ids(ids_x, m, tx->n_nodes, bad_id);
-    if (rc == ST_OK) rc = compare_check_ids(ids_y, m, ty->n_nodes, bad_id);
+    rc = compare_check_ids(tx, ty, ids_x, ids_y, m, bad_id);
     if (rc != ST_OK) return rc;
     return quartet_leaves_run(tx, ty, ids_x, ids_y, m, mode, seed, k_begin, k_count, chunk_quartets > 0 ? chunk_quartets : kQuartetChunk, out,
                               bad_id);
@@ -1412,8 +1233,7 @@ try {
     if (n > 0 && (!quartets_x || !quartets_y)) return fail(ST_ERR_ARG, "quartets_x or quartets_y is NULL");
     *out = st_quartet_table{};
     if (n == 0) return ST_OK;
-    rc = compare_check_ids(quartets_x, 4 * n, tx->n_nodes, bad_id);
-    if (rc == ST_OK) rc = compare_check_ids(quartets_y, 4 * n, ty->n_nodes, bad_id);
+    rc = compare_check_ids(tx, ty, quartets_x, quartets_y, 4 * n, bad_id);
     if (rc != ST_OK) return rc;
     return quartet_given_run(tx, ty, quartets_x, quartets_y, n, chunk_quartets > 0 ? chunk_quartets : kQuartetChunk, out, bad_id);
 } ST_CATCH_ALL

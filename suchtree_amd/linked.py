@@ -213,10 +213,7 @@ class SuchLinkedTrees:
         ll = np.ascontiguousarray(self.linklist, dtype=np.int64)
         ids_a, ids_b = np.ascontiguousarray(ll[:, 1]), np.ascontiguousarray(ll[:, 0])
         dev_a, dev_b = self._tree_a._device_tree(), self._tree_b._device_tree()
-        return compare.run(lambda edges: dev_a.compare_triangle_host(dev_b, ids_a, ids_b, edges=edges), bins, range,
-                           n_leaves=int(ll.shape[0]),
-                           rank_call=(lambda: dev_a.compare_triangle_ranks_host(dev_b, ids_a, ids_b)) if spearman else None,
-                           kendall_call=(lambda: dev_a.compare_triangle_kendall_host(dev_b, ids_a, ids_b)) if kendall else None)
+        return compare.run(dev_a, dev_b, "triangle", (ids_a, ids_b), bins, range, int(ll.shape[0]), spearman, kendall)
 
     @staticmethod
     def _breadth_first(tree: SuchTree, node_id: int, leaves: bool) -> np.ndarray:

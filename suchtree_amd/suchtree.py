@@ -441,9 +441,7 @@ class SuchTree(TreeNavigation):
                 px = self._name_ids(flat).reshape(-1, 2)
                 py = other._name_ids(flat).reshape(-1, 2)
             dx, dy = self._device_tree(), other._device_tree()
-            return compare.run(lambda edges: dx.compare_pairs_host(dy, px, py, edges=edges), bins, range,
-                               rank_call=(lambda: dx.compare_pairs_ranks_host(dy, px, py)) if spearman else None,
-                               kendall_call=(lambda: dx.compare_pairs_kendall_host(dy, px, py)) if kendall else None)
+            return compare.run(dx, dy, "pairs", (px, py), bins, range, spearman=spearman, kendall=kendall)
         if leaves is None:
             _, ids_x, ids_y = self.shared_leaves(other)
         elif isinstance(leaves, tuple) and len(leaves) == 2:
@@ -454,10 +452,7 @@ class SuchTree(TreeNavigation):
         if ids_x.ndim != 1 or ids_x.shape != ids_y.shape:
             raise ValueError("the two id lists must be 1-D and of equal length")
         dx, dy = self._device_tree(), other._device_tree()
-        return compare.run(lambda edges: dx.compare_triangle_host(dy, ids_x, ids_y, edges=edges), bins, range,
-                           n_leaves=int(len(ids_x)),
-                           rank_call=(lambda: dx.compare_triangle_ranks_host(dy, ids_x, ids_y)) if spearman else None,
-                           kendall_call=(lambda: dx.compare_triangle_kendall_host(dy, ids_x, ids_y)) if kendall else None)
+        return compare.run(dx, dy, "triangle", (ids_x, ids_y), bins, range, int(len(ids_x)), spearman, kendall)
 
     def compare_quartets(self, other: "SuchTree", leaves=None, quartets=None, samples=None, seed=None):
         """Compare this tree's topology with ``other``'s over the same quartets, counted on the GPU.
