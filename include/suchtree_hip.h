@@ -45,7 +45,8 @@ extern "C" {
  *      st_tree_info.stream_hint appended (8 bytes) with option "stream_hint"; then, also additive, struct st_quartet_table,
  *      the ST_QUARTET_* constants, st_quartet_positions, st_compare_quartets_leaves_host and st_compare_quartets_host; then, also
  *      additive, struct st_kendall_counts, ST_KENDALL_TILE, st_compare_triangle_kendall_host, st_compare_pairs_kendall_host,
- *      st_kendall_arrays_host and st_kendall_host.
+ *      st_kendall_arrays_host and st_kendall_host; then, also additive, struct st_hommola_clade, ST_HOMMOLA_MAX_UNIVERSE,
+ *      st_hommola_permutation and st_hommola_clades_host.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -418,6 +419,64 @@ int st_compare_clades_host(st_tree *tree_x, st_tree *tree_y, const int32_t *pare
 int st_compare_rows_host(st_tree *tree_x, st_tree *tree_y, const int64_t *ids_x, const int64_t *ids_y,
                          int64_t n_rows, int64_t m, int64_t chunk_pairs,
                          st_pair_moments *out, int64_t *bad_id);
+
+/*
+ * Hommola's permutation test of cospeciation for many clades of one tree in one pass (SuchLinkedTrees.hommola_by_clade).
+ * tree_c is the clade tree, tree_o the other tree; x = tree_o, y = tree_c.
+ *
+ * Orders.  univ_c (n_univ_c ids) are the clade tree's leaves in an order in which every clade is one range
+ * [leaf_begin, leaf_begin + leaf_count) -- depth-first, children in increasing id order -- and univ_o (n_univ_o ids) the
+ * other tree's leaves.  Link l (0 <= l < n_links) joins position pos_o[l] of univ_o and pos_c[l] of univ_c; the links are
+ * laid out so that pos_c is non-decreasing (the order of st_clade_plan's out_perm), hence every clade's links are one
+ * range [link_begin, link_begin + link_count).  Pair t = i(i-1)/2 + j (j < i) of a clade of L links is (link j, link i)
+ * of its range, with x = D_o[q_o(j)][q_o(i)] and y = D_c[q_c(j)][q_c(i)], D[p][q] = dist(u[p], u[q]) with the arguments in
+ * that order (both triangles are kept: the float32 sums are not symmetric in the last bit) and q the link's position,
+ * relabelled.
+ *
+ * Permutations.  Row p = 0 of a clade is the identity; row p >= 1 relabels a link at position i to sigma[i], on the
+ * clade side over the clade's own range (offset by leaf_begin) with side s = 0, on the other side over all of univ_o
+ * with s = 1.  For (seed, clade node id c, p, s, universe size n), with mix the splitmix64 finalizer of
+ * ST_QUARTET_SAMPLE, G = 0x9E3779B97F4A7C15 and all arithmetic mod 2^64:
+ *     h0 = mix(seed + (c + 1) G),  h1 = mix(h0 + (2p + s) G),
+ *     w_i = (mix(h1 + (i + 1) G) & 0xFFFFFFFFFFFF0000) | i  for i = 0 .. n-1,
+ *     sigma[j] = the low 16 bits of the j-th smallest w.
+ * The w are distinct, so sigma does not depend on the sorting method; universes therefore hold at most
+ * ST_HOMMOLA_MAX_UNIVERSE positions.  A clade's rows depend on (seed, c, its links, the two universes) alone -- not on the
+ * other clades, on chunk_blocks or on the device -- and row p is the same whatever `permutations` >= p.
+ *
+ * Sums.  out holds n_clades x (permutations + 1) records, row p of clade k at out[k * (permutations + 1) + p].  A row is
+ * cut into blocks of ST_CLADE_TILE pairs from its first pair, each block is summed about its own first pair by the order
+ * rule of st_compare_rows_host and the blocks are merged in block order: every record is bit-identical to
+ * st_compare_rows_host on the relabelled ids u_o[q_o], u_c[q_c].  A clade of fewer than two links gives n = 0, zero sums
+ * and NaN min / max.  No float atomics.
+ *
+ * Conventions and error order as for st_compare_rows_host: both trees on one device; the universe ids are checked on the
+ * host before anything is launched (ST_ERR_BOUNDS with *bad_id, tree_o's ids first).  ST_ERR_ARG: pos_c not
+ * non-decreasing, a position outside its universe, a clade whose link range is not exactly the links inside its leaf
+ * range, clade ranges that are not laminar (nested or disjoint), a universe above the limit, a negative permutations
+ * or chunk_blocks.  chunk_blocks: blocks per device chunk, 0 = the default; the result does not depend on it.  Zero
+ * clades or zero links launch nothing.  Device memory: 4 (n_univ_o^2 + the sum over the maximal clade ranges of
+ * leaf_count^2) bytes of matrices, the ids and positions, and one chunk of positions and pieces; an allocation that
+ * fails is ST_ERR_NOMEM with the bytes asked for.  No counterpart in the reference, whose SuchLinkedTrees notebook loops
+ * subset_b over the clades and takes the parametric p of scipy.stats.pearsonr.
+ */
+#define ST_HOMMOLA_MAX_UNIVERSE 16384
+typedef struct st_hommola_clade {
+    int32_t node;                      /* the clade's node id: seeds its permutations */
+    int32_t leaf_begin, leaf_count;    /* its leaves: positions of univ_c */
+    int32_t link_begin, link_count;    /* its links */
+    int32_t reserved;
+} st_hommola_clade;
+
+/* The permutation sigma of (seed, node, p, side) over n positions as int32, 1 <= n <= ST_HOMMOLA_MAX_UNIVERSE (p = 0: the
+ * identity).  device = -1 computes it on the host (no GPU); device >= 0 runs the sort of the relabelling kernel there and
+ * copies its output back: the same values.  A bad n, p, side or node is ST_ERR_ARG.  No counterpart in the reference. */
+int st_hommola_permutation(int device, uint64_t seed, int32_t node, int64_t p, int side, int32_t n, int32_t *out);
+
+int st_hommola_clades_host(st_tree *tree_o, st_tree *tree_c, const int64_t *univ_o, int32_t n_univ_o, const int64_t *univ_c,
+                           int32_t n_univ_c, const int32_t *pos_o, const int32_t *pos_c, int64_t n_links,
+                           const st_hommola_clade *clades, int64_t n_clades, int64_t permutations, uint64_t seed,
+                           int64_t chunk_blocks, st_pair_moments *out, int64_t *bad_id);
 
 /*
  * Exact Spearman rank correlation of the same pairs.  rank_x is the midrank of x_k among the call's n float32 distances

@@ -46,6 +46,7 @@ SYMBOLS = (
     "st_compare_rows_host", "st_compare_triangle_ranks_host", "st_compare_pairs_ranks_host", "st_spearman_host",
     "st_quartet_positions", "st_compare_quartets_leaves_host", "st_compare_quartets_host",
     "st_compare_triangle_kendall_host", "st_compare_pairs_kendall_host", "st_kendall_arrays_host", "st_kendall_host",
+    "st_hommola_permutation", "st_hommola_clades_host",
 )
 
 CLADE_RECT, CLADE_TRI = 0, 1     # include/suchtree_hip.h: ST_CLADE_RECT / ST_CLADE_TRI
@@ -106,6 +107,21 @@ class KendallCounts(ctypes.Structure):
 
     def as_tuple(self):
         return tuple(int(getattr(self, k)) for k, _ in self._fields_)
+
+
+HOMMOLA_MAX_UNIVERSE = 16384     # ST_HOMMOLA_MAX_UNIVERSE: leaves per universe of st_hommola_clades_host
+# st_hommola_clade as a numpy record
+HOMMOLA_CLADE = np.dtype([("node", np.int32), ("leaf_begin", np.int32), ("leaf_count", np.int32), ("link_begin", np.int32),
+                          ("link_count", np.int32), ("reserved", np.int32)])
+
+
+def hommola_permutation(seed, node, p, side, n, device=-1):
+    """st_hommola_permutation: the int32 permutation of (seed, clade node, permutation index p, side, universe size n) that
+    st_hommola_clades_host applies; ``device`` -1 = computed on the host (no GPU), else by the sort of the relabelling kernel."""
+    n = int(n)
+    out = np.empty(max(n, 0), dtype=np.int32)
+    check(load().st_hommola_permutation(int(device), int(seed) & 0xFFFFFFFFFFFFFFFF, int(node), int(p), int(side), n, _ptr(out) if n > 0 else None))
+    return out
 
 
 QUARTET_MODE = {"all": 0, "sample": 1}      # include/suchtree_hip.h: ST_QUARTET_ALL / ST_QUARTET_SAMPLE
@@ -342,6 +358,9 @@ def load():
         L.st_compare_quartets_leaves_host.argtypes = [vp, vp, vp, vp, i64, i32, ctypes.c_uint64, i64, i64, i64,
                                                       ctypes.POINTER(QuartetTable), ctypes.POINTER(i64)]
         L.st_compare_quartets_host.argtypes = [vp, vp, vp, vp, i64, i64, ctypes.POINTER(QuartetTable), ctypes.POINTER(i64)]
+        L.st_hommola_permutation.argtypes = [i32, ctypes.c_uint64, ctypes.c_int32, i64, i32, ctypes.c_int32, vp]
+        L.st_hommola_clades_host.argtypes = [vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, i64, vp, i64, i64, ctypes.c_uint64, i64, vp,
+                                             ctypes.POINTER(i64)]
         L.st_clade_plan.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64),
                                     ctypes.POINTER(i64)]
         L.st_compare_clades_host.argtypes = [vp, vp, vp, i64, vp, vp, i64, i64, i64, vp, vp, ctypes.POINTER(i64)]
@@ -965,6 +984,23 @@ class DeviceTree:
         n_rows, m = (int(v) for v in ids_x.shape)
         out = np.zeros(n_rows, dtype=PAIR_MOMENTS)
         self._compare_call(self._lib.st_compare_rows_host, other, (ids_x, ids_y, n_rows, m, int(chunk_pairs)), out)
+        return out
+
+    def hommola_clades_host(self, clade_tree, univ_o, univ_c, pos_o, pos_c, clades, permutations, seed, chunk_blocks=0):
+        """st_hommola_clades_host: x = this tree (the other tree of the test), y = ``clade_tree``.  ``clades`` is a
+        HOMMOLA_CLADE array; returns the (len(clades), permutations + 1) array of st_pair_moments records, row p of every
+        clade (p = 0: the links as they are)."""
+        univ_o = np.ascontiguousarray(univ_o, dtype=np.int64)
+        univ_c = np.ascontiguousarray(univ_c, dtype=np.int64)
+        pos_o = np.ascontiguousarray(pos_o, dtype=np.int32)
+        pos_c = np.ascontiguousarray(pos_c, dtype=np.int32)
+        clades = np.ascontiguousarray(clades, dtype=HOMMOLA_CLADE)
+        if univ_o.ndim != 1 or univ_c.ndim != 1 or pos_o.ndim != 1 or pos_o.shape != pos_c.shape or clades.ndim != 1:
+            raise ValueError("universes, positions and clades must be 1-D, pos_o and pos_c of equal length")
+        out = np.zeros((len(clades), int(permutations) + 1 if int(permutations) >= 0 else 0), dtype=PAIR_MOMENTS)
+        self._compare_call(self._lib.st_hommola_clades_host, clade_tree,
+                           (univ_o, len(univ_o), univ_c, len(univ_c), pos_o, pos_c, len(pos_o), clades, len(clades), int(permutations),
+                            int(seed) & 0xFFFFFFFFFFFFFFFF, int(chunk_blocks)), out)
         return out
 
     def triangle_device(self, d_ids, m, k_begin, k_count, d_out_dist=0, d_out_mrca=0, stream=0, id_stride=1):

@@ -379,6 +379,69 @@ def hommola_rows(u_a, u_b, pos_a, pos_b, permutations, seed, batch):
         yield ids_a, ids_b
 
 
+class CladeHommola:
+    """Hommola's permutation test for every clade of one tree (SuchLinkedTrees.hommola_by_clade), as numpy columns.
+
+    ``nodes`` are clade-tree node ids in ``get_internal_nodes()`` order; ``n_leaves`` the clade's leaf count, ``n_links``
+    its links, ``n_pairs`` = n_links (n_links - 1) / 2.  ``corr_coeff`` is Pearson's r of the unpermuted links (x = TreeA,
+    y = TreeB; the clade's ``pearson_r`` of linked_distances_by_clade), ``n_ge`` the number of permuted r >= it (NaN not
+    counted), ``n_nan`` the permuted rows whose r is NaN and ``p_value`` = (n_ge + 1) / (permutations + 1), NaN where
+    ``corr_coeff`` is.  ``perm_stats`` is the (rows,
+    permutations) float64 array of permuted r with ``keep_stats=True``, else None.  ``permutations``, ``seed`` and
+    ``tree`` repeat the call; ``skipped_nodes`` lists the clades of more than ``max_leaves`` leaves, which were not
+    evaluated.
+    """
+
+    def __init__(self, nodes, n_leaves, n_links, observed, n_ge, n_nan, perm_stats, permutations, seed, tree, skipped_nodes):
+        self.tree, self.permutations, self.seed = tree, int(permutations), int(seed)
+        self.nodes = np.asarray(nodes, dtype=np.int64)
+        self.n_leaves = np.asarray(n_leaves, dtype=np.int64)
+        self.n_links = np.asarray(n_links, dtype=np.int64)
+        self.n_pairs = self.n_links * (self.n_links - 1) // 2
+        self._observed = observed      # st_pair_moments records of the unpermuted links, x = TreeA
+        self.corr_coeff = row_stats(observed["n"], *(observed[k] for k in _SUMS))[5] if len(observed) else np.empty(0)
+        self.n_ge = np.asarray(n_ge, dtype=np.int64)
+        self.n_nan = np.asarray(n_nan, dtype=np.int64)
+        self.p_value = np.where(np.isnan(self.corr_coeff), np.nan, (self.n_ge + 1) / (self.permutations + 1))
+        self.perm_stats = perm_stats
+        self.skipped_nodes = np.asarray(skipped_nodes, dtype=np.int64)
+        self._row = None
+
+    def __len__(self):
+        return len(self.nodes)
+
+    def result(self, node) -> "HommolaResult":
+        """The row of clade ``node`` as a HommolaResult (KeyError for a node without a row): ``observed`` from the row's
+        sums, ``perm_stats`` empty unless the call kept them."""
+        if self._row is None:
+            self._row = {int(v): i for i, v in enumerate(self.nodes)}
+        i = self._row[int(node)]
+        o = self._observed[i]
+        observed = DistanceComparison.from_sums(int(o["n"]), *(float(o[k]) for k in _SUMS), float(o["min_x"]), float(o["max_x"]),
+                                                float(o["min_y"]), float(o["max_y"]), n_leaves=int(self.n_links[i]))
+        stats = self.perm_stats[i].copy() if self.perm_stats is not None else np.empty(0)
+        return HommolaResult(float(self.corr_coeff[i]), float(self.p_value[i]), stats, observed, int(self.n_links[i]),
+                             self.permutations, self.seed)
+
+    def to_dataframe(self):
+        """The table of the per-clade notebook loop: ``name`` = "clade_<id>", ``n_links``, ``n_leafs``, ``r``, ``p`` (the
+        permutation p), then the other columns (pandas, imported here)."""
+        import pandas as pd
+        return pd.DataFrame({"name": ["clade_%d" % v for v in self.nodes], "n_links": self.n_links, "n_leafs": self.n_leaves,
+                             "r": self.corr_coeff, "p": self.p_value, "node": self.nodes, "n_pairs": self.n_pairs,
+                             "n_ge": self.n_ge, "n_nan": self.n_nan})
+
+
+def hommola_permutation(seed, node, p, side, n, device=None):
+    """The int32 permutation that SuchLinkedTrees.hommola_by_clade applies for (``seed``, clade ``node``, permutation
+    index ``p`` >= 1, ``side``: 0 = the clade tree over the clade's own leaves, 1 = the other tree) over a universe of
+    ``n`` leaves in depth-first order: a link at position i moves to position ``result[i]``; p = 0 is the identity.
+    ``device=None`` computes it on the host, without a GPU; a device index runs the kernel's sort there -- the same
+    values."""
+    from . import _capi
+    return _capi.hommola_permutation(seed, node, p, side, n, -1 if device is None else int(device))
+
+
 QUARTET_MAX_ALL = 1 << 36      # SuchTree.compare_quartets(samples=None) enumerates at most this many quartets
 
 

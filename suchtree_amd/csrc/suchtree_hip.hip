@@ -41,6 +41,9 @@
 // Two trees' quartet topologies, counted on the device (st_compare_quartets_*_host, st_quartet_positions):
 // kernels_quartets.h (generator, classify-and-count), host_quartets.h (the chunk driver) and, host-only,
 // quartet_plan.cpp (unranking, the draw, the class rule, argument checks).
+// Hommola's permutation test for many clades at once (st_hommola_clades_host, st_hommola_permutation): kernels_hommola.h
+// (the sorts that relabel the links, the blocks over two distance matrices), host_hommola.h (the chunk driver) and,
+// host-only, hommola_plan.cpp (argument checks, maximal ranges, block and chunk tables, the fold, the host permutation).
 //
 // Host side of the C ABI: tree upload to one or several GPUs (tree_prep.cpp builds the tables, under a table budget
 // if one is given), the host path (host_pipe.h, host_copy.h: packed ids in through the copy engine, kernels write
@@ -149,6 +152,7 @@ private:
 #include "kernels_clades.h"
 #include "kernels_rows.h"
 #include "kernels_quartets.h"
+#include "kernels_hommola.h"
 
 
 // --------------------------------------------------------------------------
@@ -163,6 +167,7 @@ using namespace st;
 #include "host_upload.h"
 #include "host_compare.h"
 #include "host_quartets.h"
+#include "host_hommola.h"
 
 extern "C" {
 
@@ -1236,6 +1241,40 @@ try {
     rc = compare_check_ids(tx, ty, quartets_x, quartets_y, 4 * n, bad_id);
     if (rc != ST_OK) return rc;
     return quartet_given_run(tx, ty, quartets_x, quartets_y, n, chunk_quartets > 0 ? chunk_quartets : kQuartetChunk, out, bad_id);
+} ST_CATCH_ALL
+
+int st_hommola_permutation(int device, uint64_t seed, int32_t node, int64_t p, int side, int32_t n, int32_t *out)
+try {
+    std::string err;
+    const int rc = hommola_permutation_args(node, p, side, n, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (device < -1) return fail(ST_ERR_ARG, "device must be -1 (host) or a device index");
+    if (!out) return fail(ST_ERR_ARG, "out is NULL");
+    if (device < 0) {
+        hommola_permutation_host(seed, node, p, side, n, out);
+        return ST_OK;
+    }
+    return hommola_permutation_device(device, seed, node, p, side, n, out);
+} ST_CATCH_ALL
+
+int st_hommola_clades_host(st_tree *to, st_tree *tc, const int64_t *univ_o, int32_t n_univ_o, const int64_t *univ_c, int32_t n_univ_c,
+                           const int32_t *pos_o, const int32_t *pos_c, int64_t n_links, const st_hommola_clade *clades, int64_t n_clades,
+                           int64_t permutations, uint64_t seed, int64_t chunk_blocks, st_pair_moments *out, int64_t *bad_id)
+try {
+    HommolaPlan P;
+    std::string err;
+    int rc = hommola_plan(n_univ_o, n_univ_c, pos_o, pos_c, n_links, clades, n_clades, permutations, chunk_blocks, P, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if ((n_univ_o > 0 && !univ_o) || (n_univ_c > 0 && !univ_c)) return fail(ST_ERR_ARG, "univ_o or univ_c is NULL");
+    if (P.n_rows > 0 && !out) return fail(ST_ERR_ARG, "out is NULL");
+    rc = compare_trees_args(to, tc);
+    if (rc != ST_OK) return rc;
+    rc = compare_check_ids(univ_o, n_univ_o, to->n_nodes, bad_id);
+    if (rc == ST_OK) rc = compare_check_ids(univ_c, n_univ_c, tc->n_nodes, bad_id);
+    if (rc != ST_OK) return rc;
+    std::fill_n(out, P.n_rows, moments_empty());
+    if (P.n_blocks == 0) return ST_OK;      // (no clades, no links, or no clade with two links: nothing to launch)
+    return hommola_clades_run(to, tc, univ_o, univ_c, pos_o, pos_c, n_links, P, seed, out, bad_id);
 } ST_CATCH_ALL
 
 int st_graph_matrices_host(int device, int64_t n, int64_t n_edges, const int32_t *u, const int32_t *v,

@@ -362,6 +362,157 @@ class SuchLinkedTrees:
         return compare.HommolaResult(observed.pearson_r, compare.hommola_pvalue(observed.pearson_r, perm_stats), perm_stats,
                                      observed, L, permutations, seed)
 
+    _HOMMOLA_GROUP_ROWS = 1 << 21      # rows of st_pair_moments per library call of hommola_by_clade: bounds its host memory
+
+    @staticmethod
+    def _depth_first_leaves(tree: SuchTree):
+        """(leaves, begin, count): the tree's leaves in depth-first order, children in increasing id order, and every
+        node's range [begin, begin + count) of that order (st_clade_plan over one link per leaf)."""
+        left = np.asarray(tree._flat.left)
+        leaf_ids = np.flatnonzero(left == -1).astype(np.int64)
+        plan = _capi.clade_plan(tree._flat.parent, leaf_ids)
+        return leaf_ids[plan["perm"]], plan["begin"], plan["count"]
+
+    def hommola_by_clade(self, tree="B", permutations=999, seed=None, nodes=None, min_leaves=3, min_links=3, max_links=None,
+                         max_leaves=4096, keep_stats=False, chunk_blocks=0):
+        """:meth:`hommola_cospeciation` for every clade of one tree at once, in one pass on the GPU.
+
+        ``tree="B"``: one row per internal node c of TreeB under the current ``subset_a``, Hommola's test with scikit-bio's
+        semantics on what ``subset_b(c)`` would select -- the links under c, the clade's leaves (linked or not) on the
+        clade side, the current subset leaves of the other tree on the other side; ``tree="A"`` is the mirror.  x is TreeA
+        and y TreeB in both cases.  Rows follow ``get_internal_nodes()`` order and are kept as in
+        :meth:`linked_distances_by_clade` (``min_leaves``, ``min_links``, ``max_links``; fewer than 3 leaves or links never
+        make a row); ``nodes=`` restricts them to the listed clade ids.  Clades of more than ``max_leaves`` leaves (at
+        most 16384) are not evaluated and are listed in ``skipped_nodes``: the whole-tree test stays with
+        :meth:`hommola_cospeciation`.
+
+        ``corr_coeff`` is the r that :meth:`linked_distances_by_clade` reports for the clade, from a pass of its own.
+        Each clade's distances are then computed once, as a matrix, and every permutation only relabels the links'
+        positions in it.  Permutation p >= 1 of clade c on side s is ``compare.hommola_permutation(seed, c, p, s, n)`` over the
+        side's leaves in depth-first order (children in increasing id order); it is generated on the GPU, and differs
+        from the numpy draws of :meth:`hommola_cospeciation` with the same seed.  A clade's rows depend on (seed, c, its
+        links, the two leaf sets) alone -- not on the other clades, ``nodes``, the filters or ``chunk_blocks`` -- and
+        ``perm_stats[:, :k]`` is the same for any ``permutations >= k``.  ``seed=None`` draws a seed and reports it.
+        The subset state, ``linklist`` and the generator of :meth:`sample_linked_distances` are left as they were.
+        Returns a :class:`~suchtree_amd.compare.CladeHommola`.  An extension: the reference has no counterpart (its
+        notebook loops ``subset_b`` over the clades and keeps ``pearsonr``'s parametric p).
+        """
+        import numbers
+        from . import compare
+        if tree not in ("A", "B"):
+            raise ValueError("tree must be 'A' or 'B'")
+        if isinstance(permutations, bool) or not isinstance(permutations, numbers.Integral) or permutations < 0:
+            raise ValueError("permutations must be a non-negative integer, got %r" % (permutations,))
+        permutations = int(permutations)
+        limit = _capi.HOMMOLA_MAX_UNIVERSE
+        if isinstance(max_leaves, bool) or not isinstance(max_leaves, numbers.Integral) or max_leaves < 0 or max_leaves > limit:
+            raise ValueError("max_leaves must be an integer from 0 to %d, got %r" % (limit, max_leaves))
+        if seed is None:
+            seed = int(np.random.SeedSequence().generate_state(1, np.uint64)[0])
+        if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or not 0 <= seed < 1 << 64:
+            raise ValueError("seed must be an integer from 0 to 2^64 - 1, got %r" % (seed,))
+        seed = int(seed)
+        A, B = self._tree_a, self._tree_b
+        if tree == "B":
+            col_of = np.full(B.size, -1, dtype=np.int64)
+            col_of[self._col_ids.astype(np.int64)] = np.arange(len(self._col_ids))
+            ids_a, ids_b = self._links_in_order(col_of[self._leaf_order(B, B.root_node)], self._subset_a_leafs)
+            clade, other, ids_clade, ids_other, other_root = B, A, ids_b, ids_a, self._subset_a_root
+        else:
+            ids_a, ids_b = self._links_in_order(self._subset_columns, self._leaf_order(A, A.root_node))
+            clade, other, ids_clade, ids_other, other_root = A, B, ids_a, ids_b, self._subset_b_root
+        univ_c, leaf_begin, leaves = self._depth_first_leaves(clade)
+        o_leaves, o_begin, o_count = self._depth_first_leaves(other)
+        univ_o = o_leaves[o_begin[other_root]: o_begin[other_root] + o_count[other_root]]
+        if len(univ_o) < 3:
+            raise ValueError("Hommola's test needs at least 3 leaves in each tree; the other tree's subset has %d" % len(univ_o))
+        if len(univ_o) > limit:
+            raise ValueError("the other tree's subset has %d leaves: at most %d (subset it first)" % (len(univ_o), limit))
+        # the links laid out so that every clade's are one range; their positions in the two universes
+        plan = _capi.clade_plan(clade._flat.parent, ids_clade)
+        where_c = np.full(clade.size, -1, dtype=np.int64)
+        where_c[univ_c] = np.arange(len(univ_c))
+        where_o = np.full(other.size, -1, dtype=np.int64)
+        where_o[univ_o] = np.arange(len(univ_o))
+        pos_c = where_c[ids_clade[plan["perm"]]].astype(np.int32)
+        pos_o = where_o[ids_other[plan["perm"]]].astype(np.int32)
+        link_begin, count = plan["begin"], plan["count"]
+        # rows
+        rows = self._breadth_first(clade, clade.root_node, False)      # (get_internal_nodes() order)
+        if nodes is not None:
+            wanted = np.atleast_1d(np.asarray(nodes, dtype=np.int64))
+            left = np.asarray(clade._flat.left)
+            for v in wanted:
+                if v < 0 or v >= clade.size or left[v] == -1:
+                    raise ValueError("node %d is not an internal node of Tree%s" % (v, tree))
+            rows = rows[np.isin(rows, wanted)]
+        keep = (leaves[rows] >= max(int(min_leaves), 3)) & (count[rows] >= max(int(min_links), 3))
+        if max_links is not None:
+            keep &= count[rows] <= max_links
+        rows = rows[keep]
+        skipped = rows[leaves[rows] > max_leaves]
+        rows = rows[leaves[rows] <= max_leaves]
+        n = len(rows)
+        # Groups of whole maximal clades -- within max_leaves, the parent not -- of about _HOMMOLA_GROUP_ROWS rows and at most
+        # 16384 leaves: a call's clade-side universe is the leaf ranges of its maximal clades, one behind the other, and its
+        # links are theirs.  (A clade's permutations run over its own leaf range, so the cut changes no result.)
+        parent = np.asarray(clade._flat.parent)
+        fits = leaves <= max_leaves
+        top = np.flatnonzero(fits & ((parent < 0) | ~fits[np.maximum(parent, 0)]))
+        top = top[np.argsort(leaf_begin[top])]
+        owner = np.searchsorted(leaf_begin[top], leaf_begin[rows], side="right") - 1
+        order = np.argsort(owner, kind="stable")
+        n_ge, n_nan = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        stats = np.full((n, permutations), np.nan) if keep_stats else None
+        dev_o, dev_c = other._device_tree(), clade._device_tree()
+        # The observed r is the clade's r of linked_distances_by_clade: every pair with the link of lower rank first, as
+        # subset_b(c) orders it.  (The permuted rows take a pair's links in layout order, and float32 distances are not
+        # symmetric in their last bit: row 0 of the library call differs from this r at about 1e-8.)
+        observed = np.zeros(n, dtype=_capi.PAIR_MOMENTS)
+        if n:
+            parent32 = np.ascontiguousarray(clade._flat.parent, dtype=np.int32)
+            observed = dev_o.compare_clades_host(dev_c, parent32, ids_other, ids_clade, max_links=int(count[rows].max()))[0][rows]
+        corr = compare.row_stats(observed["n"], *(observed[k] for k in compare._SUMS))[5]
+        per_group = max(1, self._HOMMOLA_GROUP_ROWS // (permutations + 1))
+        at = 0
+        while at < n:
+            end, span = at, 0
+            while end < n:      # one more maximal clade with all its rows, while it fits
+                o = owner[order[end]]
+                stop = end
+                while stop < n and owner[order[stop]] == o:
+                    stop += 1
+                if end > at and (stop - at > per_group or span + leaves[top[o]] > limit):
+                    break
+                end, span = stop, span + int(leaves[top[o]])
+            idx = order[at:end]
+            at = end
+            v = rows[idx]
+            tops = top[np.unique(owner[idx])]      # (by leaf_begin)
+            leaf_off = np.concatenate(([0], np.cumsum(leaves[tops])[:-1])) - leaf_begin[tops]      # new position - old, per maximal clade
+            link_off = np.concatenate(([0], np.cumsum(count[tops])[:-1])) - link_begin[tops]
+            of = np.searchsorted(leaf_begin[tops], leaf_begin[v], side="right") - 1
+            clades = np.zeros(len(v), dtype=_capi.HOMMOLA_CLADE)
+            clades["node"], clades["leaf_begin"], clades["leaf_count"] = v, leaf_begin[v] + leaf_off[of], leaves[v]
+            clades["link_begin"], clades["link_count"] = link_begin[v] + link_off[of], count[v]
+            leaf_at = np.concatenate([np.arange(leaf_begin[t], leaf_begin[t] + leaves[t]) for t in tops])
+            link_at = np.concatenate([np.arange(link_begin[t], link_begin[t] + count[t]) for t in tops])
+            shift = np.repeat(leaf_off, count[tops]).astype(np.int32)
+            m = dev_o.hommola_clades_host(dev_c, univ_o, univ_c[leaf_at], pos_o[link_at], pos_c[link_at] + shift, clades, permutations, seed,
+                                          chunk_blocks)
+            r = compare.row_stats(m["n"][:, 1:], *(m[k][:, 1:] for k in compare._SUMS))[5]
+            with np.errstate(invalid="ignore"):
+                n_ge[idx] = np.count_nonzero(r >= corr[idx, None], axis=1)
+            n_nan[idx] = np.count_nonzero(np.isnan(r), axis=1)
+            if keep_stats:
+                stats[idx] = r
+        if tree == "A":      # x = the other tree in the call: for tree="A" that is TreeB, so the columns swap back
+            swapped = observed.copy()
+            for a, b in (("shift_x", "shift_y"), ("sx", "sy"), ("sxx", "syy"), ("min_x", "min_y"), ("max_x", "max_y")):
+                swapped[a], swapped[b] = observed[b], observed[a]
+            observed = swapped
+        return compare.CladeHommola(rows, leaves[rows], count[rows], observed, n_ge, n_nan, stats, permutations, seed, tree, skipped)
+
     @staticmethod
     def _leaf_counts(tree: SuchTree) -> np.ndarray:
         """Leaves under every node (st_clade_plan)."""
