@@ -46,7 +46,8 @@ extern "C" {
  *      the ST_QUARTET_* constants, st_quartet_positions, st_compare_quartets_leaves_host and st_compare_quartets_host; then, also
  *      additive, struct st_kendall_counts, ST_KENDALL_TILE, st_compare_triangle_kendall_host, st_compare_pairs_kendall_host,
  *      st_kendall_arrays_host and st_kendall_host; then, also additive, struct st_hommola_clade, ST_HOMMOLA_MAX_UNIVERSE,
- *      st_hommola_permutation and st_hommola_clades_host.
+ *      st_hommola_permutation and st_hommola_clades_host; then, also additive, struct st_dispersion_record,
+ *      st_partner_dispersion_host and st_dispersion_matrix.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -477,6 +478,65 @@ int st_hommola_clades_host(st_tree *tree_o, st_tree *tree_c, const int64_t *univ
                            int32_t n_univ_c, const int32_t *pos_o, const int32_t *pos_c, int64_t n_links,
                            const st_hommola_clade *clades, int64_t n_clades, int64_t permutations, uint64_t seed,
                            int64_t chunk_blocks, st_pair_moments *out, int64_t *bad_id);
+
+/*
+ * How closely related are the members of a set of leaves: the sums behind MPD (mean pairwise distance) and MNTD (mean
+ * distance to the nearest other member) of many sets over one universe, each with the null that shuffles the universe's
+ * labels (picante's ses.mpd / ses.mntd with null.model = "taxa.labels").  SuchLinkedTrees.partner_dispersion asks it of
+ * every leaf's partners in the other tree; SuchTree.dispersion of any sets of leaves.
+ *
+ * Universe and matrix.  univ (n_univ ids, 3 <= n_univ <= ST_HOMMOLA_MAX_UNIVERSE) are leaves of the tree in depth-first
+ * order, children in increasing id order (the order of st_hommola_clades_host).  D[a][b] = dist(u[a], u[b]) as float32,
+ * the arguments in that order; both triangles are kept (the float32 sums are not symmetric in the last bit).  It is
+ * written once by the distance kernels.
+ *
+ * Sets.  Set r (0 <= r < n_sets) is the k_r = sets[r + 1] - sets[r] positions set_pos[sets[r] .. sets[r + 1]) of the
+ * universe, strictly increasing: s_0 < s_1 < ... < s_{k-1}.  sets holds n_sets + 1 offsets, 0 <= sets[r] <= sets[r + 1]
+ * <= n_pos (sets may share positions of set_pos).
+ *
+ * Relabelling.  Under permutation p the set is relabelled to q_i = sigma_p[s_i], sigma_p = st_hommola_permutation(seed,
+ * node = stream, p, side = 0, n_univ): p = 0 is the identity, `stream` any non-negative int32 (the facade passes the
+ * universe's subset root).  One sigma_p serves every set of the call, as the taxa-labels null is defined: a set's null
+ * draws are uniform k-subsets of the universe, and the sets of a call share the shuffles.
+ *
+ * Record.  out holds n_sets x (permutations + 1) records, (r, p) at out[r * (permutations + 1) + p]:
+ *     rowsum_i = sum over j != i of (double) D[q_i][q_j], added one by one with j ascending, from 0.0;
+ *     rowmin_i = m after: m = +inf; for j != i ascending: v = D[q_i][q_j]; m = v < m ? v : m
+ *                (a NaN entry is never taken; of equal values, -0.0 and +0.0 among them, the first stays);
+ *     pair_sum = sum over i of rowsum_i,  nearest_sum = sum over i of (double) rowmin_i.
+ * The caller forms MPD = pair_sum / (k (k - 1)) and MNTD = nearest_sum / k.  k < 2 gives a record of zeros.
+ * The order over i depends on k alone:
+ *     k <= 64: element i sits in lane i of K' lanes, K' = max(2, the next power of two >= k), the other lanes hold +0.0,
+ *              and `a += a of lane (l xor o)` runs over o = K'/2, K'/4 .. 1; every lane ends with the total.
+ *     k > 64:  256 lanes; lane t adds its elements i = t, t + 256, ... in ascending order from 0.0; each of the four
+ *              waves of 64 lanes runs the butterfly o = 32 .. 1; then total = ((w0 + w1) + w2) + w3.
+ * Record (r, p) depends on (seed, stream, p, D, set r) alone -- not on r, the other sets, permutations, chunk_tasks, the
+ * grid or the device; identical sets give identical bits wherever they stand; column p is the same for any permutations
+ * >= p.  No float atomics.
+ *
+ * st_partner_dispersion_host builds D on the tree's device (4 n_univ^2 bytes) and runs the kernels.  The universe ids are
+ * checked on the host before anything is launched (ST_ERR_BOUNDS with *bad_id).  ST_ERR_ARG: a universe size outside
+ * 3 .. ST_HOMMOLA_MAX_UNIVERSE, bad offsets, a position outside the universe, a set that is not strictly increasing,
+ * negative permutations, chunk_tasks or stream.  chunk_tasks: (set, permutation) tasks per device chunk, and the most
+ * permutations whose sigma the device holds at once; 0 = the default; the result does not depend on it.  An allocation
+ * that fails is ST_ERR_NOMEM with the bytes asked for, before out is written.  Zero sets, or none of two positions,
+ * launch nothing.
+ *
+ * st_dispersion_matrix is the same reduction over the caller's C-order float32 n x n matrix D: device = -1 computes it on
+ * the host, operation for operation (no GPU); device >= 0 uploads D and runs the same kernels: the same bits.
+ * No counterpart in the reference.
+ */
+typedef struct st_dispersion_record {
+    double pair_sum, nearest_sum;
+} st_dispersion_record;
+
+int st_partner_dispersion_host(st_tree *tree, const int64_t *univ, int32_t n_univ, const int32_t *set_pos, int64_t n_pos,
+                               const int64_t *sets, int64_t n_sets, int64_t permutations, uint64_t seed, int32_t stream,
+                               int64_t chunk_tasks, st_dispersion_record *out, int64_t *bad_id);
+
+int st_dispersion_matrix(int device, const float *D, int32_t n, const int32_t *set_pos, int64_t n_pos, const int64_t *sets,
+                         int64_t n_sets, int64_t permutations, uint64_t seed, int32_t stream, int64_t chunk_tasks,
+                         st_dispersion_record *out);
 
 /*
  * Exact Spearman rank correlation of the same pairs.  rank_x is the midrank of x_k among the call's n float32 distances

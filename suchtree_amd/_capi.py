@@ -46,7 +46,7 @@ SYMBOLS = (
     "st_compare_rows_host", "st_compare_triangle_ranks_host", "st_compare_pairs_ranks_host", "st_spearman_host",
     "st_quartet_positions", "st_compare_quartets_leaves_host", "st_compare_quartets_host",
     "st_compare_triangle_kendall_host", "st_compare_pairs_kendall_host", "st_kendall_arrays_host", "st_kendall_host",
-    "st_hommola_permutation", "st_hommola_clades_host",
+    "st_hommola_permutation", "st_hommola_clades_host", "st_partner_dispersion_host", "st_dispersion_matrix",
 )
 
 CLADE_RECT, CLADE_TRI = 0, 1     # include/suchtree_hip.h: ST_CLADE_RECT / ST_CLADE_TRI
@@ -121,6 +121,55 @@ def hommola_permutation(seed, node, p, side, n, device=-1):
     n = int(n)
     out = np.empty(max(n, 0), dtype=np.int32)
     check(load().st_hommola_permutation(int(device), int(seed) & 0xFFFFFFFFFFFFFFFF, int(node), int(p), int(side), n, _ptr(out) if n > 0 else None))
+    return out
+
+
+# st_dispersion_record as a numpy record
+DISPERSION_RECORD = np.dtype([("pair_sum", np.float64), ("nearest_sum", np.float64)])
+
+
+def _dispersion_sets(sets, n_univ):
+    """(set_pos int32, offsets int64, n_sets) of an iterable of position collections, or of a (set_pos, offsets) tuple of
+    arrays; ValueError for a position outside the universe or a set that is not strictly increasing (the library checks
+    again)."""
+    if isinstance(sets, tuple) and len(sets) == 2 and all(isinstance(a, np.ndarray) for a in sets):
+        pos = np.ascontiguousarray(sets[0], dtype=np.int32)
+        off = np.ascontiguousarray(sets[1], dtype=np.int64)
+        if pos.ndim != 1 or off.ndim != 1 or len(off) < 1:
+            raise ValueError("set_pos must be 1-D and offsets hold n_sets + 1 entries")
+        return pos, off, len(off) - 1
+    rows = [np.asarray(r, dtype=np.int64).ravel() for r in sets]
+    off = np.zeros(len(rows) + 1, dtype=np.int64)
+    if rows:
+        np.cumsum([len(r) for r in rows], out=off[1:])
+    pos = np.concatenate(rows) if rows else np.empty(0, dtype=np.int64)
+    if len(pos) and (pos.min() < 0 or pos.max() >= n_univ):
+        raise ValueError("a position outside the universe of %d" % n_univ)
+    return pos.astype(np.int32), off, len(rows)
+
+
+def _dispersion_args(permutations, stream, chunk_tasks):
+    if int(permutations) < 0:
+        raise ValueError("permutations < 0")
+    if int(stream) < 0 or int(stream) > 0x7FFFFFFF:
+        raise ValueError("stream must be a non-negative int32")
+    if int(chunk_tasks) < 0:
+        raise ValueError("chunk_tasks < 0")
+
+
+def dispersion_matrix(D, sets, permutations, seed, stream=0, device=-1, chunk_tasks=0):
+    """st_dispersion_matrix: the (n_sets, permutations + 1) array of DISPERSION_RECORD of the position sets ``sets`` (an
+    iterable of strictly increasing position collections, or a (set_pos, offsets) tuple of arrays) over the C-order
+    float32 (n, n) matrix ``D``; ``device`` -1 = the host restatement (no GPU), else the kernels on that device."""
+    D = np.ascontiguousarray(D, dtype=np.float32)
+    if D.ndim != 2 or D.shape[0] != D.shape[1]:
+        raise ValueError("D must be a square matrix")
+    n = int(D.shape[0])
+    _dispersion_args(permutations, stream, chunk_tasks)
+    pos, off, n_sets = _dispersion_sets(sets, n)
+    out = np.zeros((n_sets, int(permutations) + 1), dtype=DISPERSION_RECORD)
+    check(load().st_dispersion_matrix(int(device), _ptr(D), n, _ptr(pos) if len(pos) else None, len(pos), _ptr(off), n_sets, int(permutations),
+                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(chunk_tasks), _ptr(out) if out.size else None))
     return out
 
 
@@ -361,6 +410,9 @@ def load():
         L.st_hommola_permutation.argtypes = [i32, ctypes.c_uint64, ctypes.c_int32, i64, i32, ctypes.c_int32, vp]
         L.st_hommola_clades_host.argtypes = [vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, i64, vp, i64, i64, ctypes.c_uint64, i64, vp,
                                              ctypes.POINTER(i64)]
+        L.st_partner_dispersion_host.argtypes = [vp, vp, ctypes.c_int32, vp, i64, vp, i64, i64, ctypes.c_uint64, ctypes.c_int32, i64, vp,
+                                                 ctypes.POINTER(i64)]
+        L.st_dispersion_matrix.argtypes = [i32, vp, ctypes.c_int32, vp, i64, vp, i64, i64, ctypes.c_uint64, ctypes.c_int32, i64, vp]
         L.st_clade_plan.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64),
                                     ctypes.POINTER(i64)]
         L.st_compare_clades_host.argtypes = [vp, vp, vp, i64, vp, vp, i64, i64, i64, vp, vp, ctypes.POINTER(i64)]
@@ -1001,6 +1053,22 @@ class DeviceTree:
         self._compare_call(self._lib.st_hommola_clades_host, clade_tree,
                            (univ_o, len(univ_o), univ_c, len(univ_c), pos_o, pos_c, len(pos_o), clades, len(clades), int(permutations),
                             int(seed) & 0xFFFFFFFFFFFFFFFF, int(chunk_blocks)), out)
+        return out
+
+    def partner_dispersion_host(self, univ, sets, permutations, seed, stream=0, chunk_tasks=0):
+        """st_partner_dispersion_host: the (n_sets, permutations + 1) array of DISPERSION_RECORD of the position sets
+        ``sets`` (as in ``dispersion_matrix``) over the universe ``univ`` (node ids of this tree, depth-first)."""
+        univ = np.ascontiguousarray(univ, dtype=np.int64)
+        if univ.ndim != 1:
+            raise ValueError("the universe must be 1-D")
+        _dispersion_args(permutations, stream, chunk_tasks)
+        pos, off, n_sets = _dispersion_sets(sets, len(univ))
+        out = np.zeros((n_sets, int(permutations) + 1), dtype=DISPERSION_RECORD)
+        bad = ctypes.c_int64(0)
+        rc = self._lib.st_partner_dispersion_host(self.handle, _ptr(univ) if len(univ) else None, len(univ), _ptr(pos) if len(pos) else None,
+                                                  len(pos), _ptr(off), n_sets, int(permutations), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream),
+                                                  int(chunk_tasks), _ptr(out) if out.size else None, ctypes.byref(bad))
+        check(rc, tree_size=self.size, bad_id=int(bad.value))
         return out
 
     def triangle_device(self, d_ids, m, k_begin, k_count, d_out_dist=0, d_out_mrca=0, stream=0, id_stride=1):

@@ -13,7 +13,7 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["DistanceComparison", "CladeComparisons", "HommolaResult", "QuartetComparison", "quartet_positions"]
+__all__ = ["DistanceComparison", "CladeComparisons", "HommolaResult", "QuartetComparison", "SetDispersion", "quartet_positions"]
 
 
 @dataclass(frozen=True)
@@ -440,6 +440,104 @@ def hommola_permutation(seed, node, p, side, n, device=None):
     values."""
     from . import _capi
     return _capi.hommola_permutation(seed, node, p, side, n, -1 if device is None else int(device))
+
+
+class SetDispersion:
+    """How closely related the members of each of many leaf sets are (SuchTree.dispersion,
+    SuchLinkedTrees.partner_dispersion), as numpy columns, one entry per set.
+
+    ``n`` is the set's size k, ``mpd`` the mean of the k (k - 1) ordered pairwise distances among its members and ``mntd``
+    the mean over the members of the distance to the nearest other member (NaN for k < 2).  The null shuffles the labels
+    of the universe (picante's ``null.model = "taxa.labels"``): under permutation p every set is relabelled by the same
+    shuffle, so a set's null draws are uniform k-subsets of the universe, and the sets of a call share the shuffles.
+    For ``x`` in (``mpd``, ``mntd``): ``x_null_mean`` and ``x_null_sd`` (the sample standard deviation, ddof = 1, as
+    picante's ``sd``) over the null draws that are not NaN, ``x_ses`` = (x - mean) / sd -- NaN where the sd is 0 or
+    undefined; NRI = -mpd_ses, NTI = -mntd_ses -- ``x_n_le`` the number of null draws <= x and ``x_p`` =
+    (n_le + 1) / (permutations + 1), the lower tail: small when the members are clustered.  A null whose draws are all
+    equal has sd 0 exactly; a set that is the whole universe has that null by definition (every draw is the set itself)
+    and is reported so: mean = x, sd = 0, SES NaN, p = 1.  ``n_nan`` counts the null draws with a NaN in either statistic.
+    ``null_mpd`` / ``null_mntd`` are the (sets, permutations) arrays of the draws with ``keep_null=True``, else None.
+    ``permutations``, ``seed`` and ``n_universe`` repeat the call.  ``leaves`` / ``names`` are filled in by
+    ``partner_dispersion``: the leaf whose partners a row describes.
+    """
+
+    COLUMNS = ("n", "mpd", "mntd", "mpd_null_mean", "mpd_null_sd", "mpd_ses", "mpd_n_le", "mpd_p", "mntd_null_mean", "mntd_null_sd",
+               "mntd_ses", "mntd_n_le", "mntd_p", "n_nan")
+
+    def __init__(self, n_sets, permutations, seed, n_universe, keep_null=False):
+        self.permutations, self.seed, self.n_universe = int(permutations), int(seed), int(n_universe)
+        self.n = np.zeros(n_sets, dtype=np.int64)
+        for k in self.COLUMNS[1:]:
+            setattr(self, k, np.zeros(n_sets, dtype=np.int64) if k.endswith("n_le") or k == "n_nan" else np.full(n_sets, np.nan))
+        self.null_mpd = np.full((n_sets, self.permutations), np.nan) if keep_null else None
+        self.null_mntd = np.full((n_sets, self.permutations), np.nan) if keep_null else None
+        self.leaves = self.names = None
+
+    def __len__(self):
+        return len(self.n)
+
+    def fill(self, at, k, records):
+        """Reduce the (rows, permutations + 1) DISPERSION_RECORD array of sets [at, at + rows) of sizes ``k``."""
+        k = np.asarray(k, dtype=np.int64)
+        rows = slice(at, at + len(k))
+        self.n[rows] = k
+        kk = np.maximum(k, 2).astype(np.float64)[:, None]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mpd = np.where(k[:, None] >= 2, records["pair_sum"] / (kk * (kk - 1)), np.nan)
+            mntd = np.where(k[:, None] >= 2, records["nearest_sum"] / kk, np.nan)
+        whole = k == self.n_universe
+        self.n_nan[rows] = np.count_nonzero(np.isnan(mpd[:, 1:]) | np.isnan(mntd[:, 1:]), axis=1)
+        for name, x in (("mpd", mpd), ("mntd", mntd)):
+            mean, sd, ses, n_le = null_summary(x[:, 0], x[:, 1:], whole)
+            getattr(self, name)[rows] = x[:, 0]
+            getattr(self, name + "_null_mean")[rows] = mean
+            getattr(self, name + "_null_sd")[rows] = sd
+            getattr(self, name + "_ses")[rows] = ses
+            getattr(self, name + "_n_le")[rows] = n_le
+            getattr(self, name + "_p")[rows] = np.where(np.isnan(x[:, 0]), np.nan, (n_le + 1) / (self.permutations + 1))
+            if self.null_mpd is not None:
+                getattr(self, "null_" + name)[rows] = x[:, 1:]
+
+    def row(self, i) -> dict:
+        """Row i as a dict of Python scalars (plus ``leaf`` / ``name`` where the call knows them)."""
+        out = {k: getattr(self, k)[i].item() for k in self.COLUMNS}
+        if self.leaves is not None:
+            out["leaf"], out["name"] = int(self.leaves[i]), self.names[i]
+        return out
+
+    def to_dataframe(self):
+        """The columns as a pandas DataFrame (pandas imported here), ``leaf`` / ``name`` first where the call knows them."""
+        import pandas as pd
+        cols = {} if self.leaves is None else {"name": self.names, "leaf": self.leaves}
+        cols.update({k: getattr(self, k) for k in self.COLUMNS})
+        return pd.DataFrame(cols)
+
+
+def null_summary(observed, null, degenerate=None):
+    """(mean, sd, ses, n_le) per row of ``null`` (rows, draws) against ``observed`` (rows): NaN draws left out, sd with
+    ddof = 1, exactly 0 where all draws are equal; rows marked ``degenerate`` have the observation as their null."""
+    import warnings
+    rows, draws = null.shape
+    mean, sd = np.full(rows, np.nan), np.full(rows, np.nan)
+    n_le = np.zeros(rows, dtype=np.int64)
+    if draws:
+        with np.errstate(invalid="ignore", divide="ignore"):
+            with warnings.catch_warnings():      # (a row of NaN draws only: numpy warns and gives NaN, which is the answer)
+                warnings.simplefilter("ignore", RuntimeWarning)
+                mean = np.nanmean(null, axis=1)
+                sd = np.nanstd(null, axis=1, ddof=1)
+                top = np.nanmax(null, axis=1)
+                flat = top == np.nanmin(null, axis=1)
+            mean = np.where(flat, top, mean)
+            sd = np.where(flat & (np.count_nonzero(~np.isnan(null), axis=1) >= 2), 0.0, sd)
+            n_le = np.count_nonzero(null <= observed[:, None], axis=1)
+    if degenerate is not None and draws:
+        mean = np.where(degenerate, observed, mean)
+        sd = np.where(degenerate, 0.0, sd)
+        n_le = np.where(degenerate & ~np.isnan(observed), draws, n_le)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ses = np.where(sd > 0, (observed - mean) / sd, np.nan)
+    return mean, sd, ses, n_le
 
 
 QUARTET_MAX_ALL = 1 << 36      # SuchTree.compare_quartets(samples=None) enumerates at most this many quartets

@@ -1,0 +1,158 @@
+// dispersion_plan.cpp -- see dispersion_plan.h.  Argument checks and index arithmetic driven by caller-supplied positions,
+// and the restatement of the device reduction operation for operation: no GPU calls.
+#include "dispersion_plan.h"
+
+#include <algorithm>
+#include <limits>
+#include <numeric>
+
+namespace st {
+
+static int fail(int code, std::string &err, const std::string &msg)
+{
+    err = msg;
+    return code;
+}
+
+int dispersion_plan(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets, int64_t permutations,
+                    int32_t stream, int64_t chunk_tasks, DispersionPlan &P, std::string &err)
+{
+    if (n_univ < 3 || n_univ > kHommolaMaxUniverse)
+        return fail(ST_ERR_ARG, err, "a universe of " + std::to_string(n_univ) + " positions: 3 to " + std::to_string(kHommolaMaxUniverse));
+    if (permutations < 0) return fail(ST_ERR_ARG, err, "permutations < 0");
+    if (chunk_tasks < 0) return fail(ST_ERR_ARG, err, "chunk_tasks < 0");
+    if (stream < 0) return fail(ST_ERR_ARG, err, "stream < 0");
+    if (n_pos < 0 || n_sets < 0) return fail(ST_ERR_ARG, err, "negative size");
+    if (n_pos > INT32_MAX) return fail(ST_ERR_ARG, err, "more than 2^31 - 1 positions");
+    if ((n_sets > 0 && !sets) || (n_pos > 0 && !set_pos)) return fail(ST_ERR_ARG, err, "set_pos or sets is NULL");
+    const int64_t R = permutations + 1;
+    if (n_sets > 0 && R > ((int64_t)1 << 40) / n_sets) return fail(ST_ERR_ARG, err, "more than 2^40 records in one call");
+    for (int64_t r = 0; r < n_sets; r++) {
+        const int64_t b = sets[r], e = sets[r + 1];
+        if (b < 0 || e < b || e > n_pos)
+            return fail(ST_ERR_ARG, err, "set " + std::to_string(r) + ": offsets [" + std::to_string(b) + ", " + std::to_string(e) + ") of " +
+                                             std::to_string(n_pos) + " positions");
+        for (int64_t i = b; i < e; i++) {
+            if (set_pos[i] < 0 || set_pos[i] >= n_univ) return fail(ST_ERR_ARG, err, "set " + std::to_string(r) + ": a position outside the universe");
+            if (i > b && set_pos[i] <= set_pos[i - 1])
+                return fail(ST_ERR_ARG, err, "set " + std::to_string(r) + ": positions must be strictly increasing");
+        }
+    }
+    P = DispersionPlan{};
+    P.n_univ = n_univ;
+    P.n_sets = n_sets;
+    P.rows = R;
+    for (int64_t r = 0; r < n_sets; r++)
+        if (sets[r + 1] - sets[r] >= 2) P.order.push_back(r);
+    auto cls = [&](int64_t r) { return dispersion_class((int)(sets[r + 1] - sets[r])); };
+    std::stable_sort(P.order.begin(), P.order.end(), [&](int64_t a, int64_t b) { return cls(a) < cls(b); });
+    const int64_t live = (int64_t)P.order.size();
+    P.sets.resize((size_t)live);
+    int64_t c = 0;
+    for (int k = 0; k < kDispersionClasses; k++) {
+        P.class_begin[k] = c;
+        while (c < live && cls(P.order[(size_t)c]) == k) c++;
+    }
+    P.class_begin[kDispersionClasses] = live;
+    for (c = 0; c < live; c++) {
+        const int64_t r = P.order[(size_t)c];
+        P.sets[(size_t)c] = DispersionSetDev{(int)sets[r], (int)(sets[r + 1] - sets[r])};
+        P.max_count = std::max(P.max_count, P.sets[(size_t)c].count);
+    }
+    int64_t block = std::max<int64_t>(1, kDispersionSigmaBytes / (2 * (int64_t)n_univ));
+    int64_t cap = kDispersionChunkTasks;
+    if (chunk_tasks > 0) {
+        block = std::min(block, chunk_tasks);
+        cap = std::min(chunk_tasks, kDispersionMaxChunkTasks);
+    }
+    P.perm_block = std::min(block, R);
+    if (live == 0) return ST_OK;
+    for (int64_t p0 = 0; p0 < R; p0 += P.perm_block) {
+        const int64_t np = std::min(P.perm_block, R - p0), tasks = live * np;
+        for (int64_t t = 0; t < tasks; t += cap) {
+            P.chunks.push_back(DispersionChunk{p0, np, t, std::min(cap, tasks - t)});
+            P.max_chunk_tasks = std::max(P.max_chunk_tasks, P.chunks.back().n_tasks);
+        }
+    }
+    return ST_OK;
+}
+
+// what a wave does with `a += shfl_xor(a, o)` over offsets width / 2 .. 1: v[0 .. width) in, every lane's total out
+static void butterfly(double *v, int width)
+{
+    double w[64];
+    for (int o = width >> 1; o > 0; o >>= 1) {
+        for (int l = 0; l < width; l++) w[l] = v[l] + v[l ^ o];
+        std::copy(w, w + width, v);
+    }
+}
+
+st_dispersion_record dispersion_record(const float *D, int32_t n, const int32_t *q, int32_t k)
+{
+    st_dispersion_record out{0.0, 0.0};
+    if (k < 2) return out;
+    const int lanes = k <= kDispersionWaveMax ? dispersion_lanes(k) : kDispersionThreads;
+    double a[kDispersionThreads], b[kDispersionThreads];
+    std::fill(a, a + lanes, 0.0);
+    std::fill(b, b + lanes, 0.0);
+    for (int32_t i = 0; i < k; i++) {
+        const float *row = D + (size_t)q[i] * (size_t)n;
+        double sum = 0.0;
+        float m = std::numeric_limits<float>::infinity();
+        for (int32_t j = 0; j < k; j++) {
+            if (j == i) continue;
+            const float v = row[q[j]];
+            sum += (double)v;
+            m = v < m ? v : m;
+        }
+        if (k <= kDispersionWaveMax) {      // element i sits in lane i
+            a[i] = sum;
+            b[i] = (double)m;
+        } else {                            // lane i % 256 adds its elements in ascending order from 0.0
+            a[i % kDispersionThreads] += sum;
+            b[i % kDispersionThreads] += (double)m;
+        }
+    }
+    if (k <= kDispersionWaveMax) {
+        butterfly(a, lanes);
+        butterfly(b, lanes);
+        out.pair_sum = a[0];
+        out.nearest_sum = b[0];
+        return out;
+    }
+    for (int w = 0; w < kDispersionThreads / 64; w++) {      // every wave's butterfly, the wave totals in wave order
+        butterfly(a + 64 * w, 64);
+        butterfly(b + 64 * w, 64);
+    }
+    out.pair_sum = a[0];
+    out.nearest_sum = b[0];
+    for (int w = 1; w < kDispersionThreads / 64; w++) {
+        out.pair_sum += a[64 * w];
+        out.nearest_sum += b[64 * w];
+    }
+    return out;
+}
+
+void dispersion_host(const float *D, const DispersionPlan &P, const int32_t *set_pos, const int64_t *sets, uint64_t seed, int32_t stream,
+                     st_dispersion_record *out)
+{
+    std::vector<int32_t> sigma((size_t)P.n_univ), q((size_t)std::max(P.max_count, 1));
+    for (int64_t p = 0; p < P.rows; p++) {
+        hommola_permutation_host(seed, stream, p, 0, P.n_univ, sigma.data());      // (one sigma serves every set)
+        for (int64_t r = 0; r < P.n_sets; r++) {
+            const int64_t b = sets[r], k = sets[r + 1] - b;
+            for (int64_t i = 0; i < k && k >= 2; i++) q[(size_t)i] = sigma[(size_t)set_pos[b + i]];
+            out[r * P.rows + p] = dispersion_record(D, P.n_univ, q.data(), (int32_t)k);
+        }
+    }
+}
+
+void dispersion_scatter(const DispersionPlan &P, const DispersionChunk &c, const st_dispersion_record *records, st_dispersion_record *out)
+{
+    for (int64_t j = 0; j < c.n_tasks; j++) {
+        const int64_t t = c.task_begin + j, s = t / c.n_perms, p = c.p_begin + (t - s * c.n_perms);
+        out[P.order[(size_t)s] * P.rows + p] = records[j];
+    }
+}
+
+}  // namespace st

@@ -1,0 +1,84 @@
+// dispersion_plan.h -- the host-only side of the partner-dispersion reduction (st_partner_dispersion_host,
+// st_dispersion_matrix), plain C++17, and what the device shares with it (kernels_dispersion.h): the size classes and the
+// record.  No GPU calls in here (dispersion_plan.cpp): the "not gpu" tests run it under the address /
+// undefined-behaviour sanitizers (tests/emu/sanitize_dispersion.cpp).  The definitions are the contract of
+// include/suchtree_hip.h (st_partner_dispersion_host).
+//
+// Layout.  A task is (set, permutation p).  Sets of fewer than two positions make no task: their records are zeros.
+// The others are ordered by size class -- K' = 2, 4, 8, 16, 32 (packed: 64 / K' tasks per wave), 64 (one task per wave),
+// then the sets of more than 64 positions (one task per workgroup) -- and by their index within a class.  The
+// permutations are cut into blocks of up to `perm_block` consecutive p, whose sigma rows the device holds at once; within
+// a block of n_perms permutations from p0, task t = c * n_perms + (p - p0) is set order[c] under permutation p, so a
+// class is one range of t, and a chunk is a range of t of one block.
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "hommola_plan.h"
+
+namespace st {
+
+constexpr int kDispersionWaveMax = 64;            // sets of up to 64 positions: element i in lane i
+constexpr int kDispersionPackedMax = 32;          // K' up to 32: several tasks per wave
+constexpr int kDispersionThreads = 256;           // the workgroup of every task kernel
+constexpr int kDispersionClasses = 7;             // K' = 2 .. 64 (classes 0 .. 5), then the workgroup class (6)
+constexpr int64_t kDispersionChunkTasks = 1 << 20;            // default tasks per chunk: 16 MiB of records
+constexpr int64_t kDispersionMaxChunkTasks = 1 << 30;          // a launch's task index stays within 32 bits
+constexpr int64_t kDispersionSigmaBytes = 64 << 20;           // default bound of a block's sigma rows
+
+// K' of a set of k >= 2 positions, k <= 64: max(2, the next power of two >= k)
+ST_QUARTET_HD int dispersion_lanes(int k)
+{
+    int kp = 2;
+    while (kp < k) kp <<= 1;
+    return kp;
+}
+ST_QUARTET_HD int dispersion_class(int k)      // k >= 2
+{
+    if (k > kDispersionWaveMax) return 6;
+    int c = 0;
+    for (int kp = 2; kp < k; kp <<= 1) c++;
+    return c;
+}
+
+struct DispersionSetDev {
+    int begin, count;      // the set's positions: set_pos[begin, begin + count)
+};
+
+struct DispersionChunk {
+    int64_t p_begin, n_perms;          // the block of permutations it belongs to
+    int64_t task_begin, n_tasks;       // tasks [task_begin, task_begin + n_tasks) of that block
+};
+
+struct DispersionPlan {
+    int32_t n_univ = 0;
+    int64_t n_sets = 0, rows = 0;                 // rows = permutations + 1 records per set
+    std::vector<int64_t> order;                   // the live sets (k >= 2) by (class, index)
+    std::vector<DispersionSetDev> sets;           // order[c]'s range
+    int64_t class_begin[kDispersionClasses + 1] = {};      // sets [class_begin[k], class_begin[k + 1]) of `order` are of class k
+    int64_t perm_block = 0;
+    int max_count = 0;                            // the largest set
+    std::vector<DispersionChunk> chunks;
+    int64_t max_chunk_tasks = 0;
+};
+
+// ST_OK, or ST_ERR_ARG with `err`.  Checks, in this order: the universe size (3 .. kHommolaMaxUniverse), nothing negative
+// (permutations, chunk_tasks, stream, the counts), the offsets (sets[0 .. n_sets]: 0 <= sets[r] <= sets[r + 1] <= n_pos),
+// every set (positions inside the universe, strictly increasing).  Then the layout above: chunk_tasks 0 = blocks of up
+// to kDispersionSigmaBytes of sigma rows and chunks of kDispersionChunkTasks tasks; chunk_tasks > 0 = at most that many
+// tasks per chunk and permutations per block.
+int dispersion_plan(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets, int64_t permutations,
+                    int32_t stream, int64_t chunk_tasks, DispersionPlan &P, std::string &err);
+
+// the record of the relabelled positions q[0 .. k) over the n x n matrix D, by the order rule of the contract
+st_dispersion_record dispersion_record(const float *D, int32_t n, const int32_t *q, int32_t k);
+
+// every record of the call on the host: out[r * rows + p]
+void dispersion_host(const float *D, const DispersionPlan &P, const int32_t *set_pos, const int64_t *sets, uint64_t seed, int32_t stream,
+                     st_dispersion_record *out);
+
+// records[n] of tasks [task_begin, task_begin + n) of the block at p_begin into out
+void dispersion_scatter(const DispersionPlan &P, const DispersionChunk &c, const st_dispersion_record *records, st_dispersion_record *out);
+
+}  // namespace st

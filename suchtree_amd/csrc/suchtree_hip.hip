@@ -44,6 +44,9 @@
 // Hommola's permutation test for many clades at once (st_hommola_clades_host, st_hommola_permutation): kernels_hommola.h
 // (the sorts that relabel the links, the blocks over two distance matrices), host_hommola.h (the chunk driver) and,
 // host-only, hommola_plan.cpp (argument checks, maximal ranges, block and chunk tables, the fold, the host permutation).
+// MPD / MNTD sums of many leaf sets under the taxa-labels null (st_partner_dispersion_host, st_dispersion_matrix):
+// kernels_dispersion.h (one sort per permutation, the k x k reducer in three size classes), host_dispersion.h (the chunk
+// driver) and, host-only, dispersion_plan.cpp (argument checks, size classes, chunks, the restatement of the reduction).
 //
 // Host side of the C ABI: tree upload to one or several GPUs (tree_prep.cpp builds the tables, under a table budget
 // if one is given), the host path (host_pipe.h, host_copy.h: packed ids in through the copy engine, kernels write
@@ -153,6 +156,7 @@ private:
 #include "kernels_rows.h"
 #include "kernels_quartets.h"
 #include "kernels_hommola.h"
+#include "kernels_dispersion.h"
 
 
 // --------------------------------------------------------------------------
@@ -168,6 +172,7 @@ using namespace st;
 #include "host_compare.h"
 #include "host_quartets.h"
 #include "host_hommola.h"
+#include "host_dispersion.h"
 
 extern "C" {
 
@@ -1275,6 +1280,43 @@ try {
     std::fill_n(out, P.n_rows, moments_empty());
     if (P.n_blocks == 0) return ST_OK;      // (no clades, no links, or no clade with two links: nothing to launch)
     return hommola_clades_run(to, tc, univ_o, univ_c, pos_o, pos_c, n_links, P, seed, out, bad_id);
+} ST_CATCH_ALL
+
+int st_partner_dispersion_host(st_tree *t, const int64_t *univ, int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets,
+                               int64_t n_sets, int64_t permutations, uint64_t seed, int32_t stream, int64_t chunk_tasks,
+                               st_dispersion_record *out, int64_t *bad_id)
+try {
+    DispersionPlan P;
+    std::string err;
+    int rc = dispersion_plan(n_univ, set_pos, n_pos, sets, n_sets, permutations, stream, chunk_tasks, P, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (!univ) return fail(ST_ERR_ARG, "univ is NULL");
+    if (n_sets > 0 && !out) return fail(ST_ERR_ARG, "out is NULL");
+    if (!t) return fail(ST_ERR_ARG, "tree is NULL");
+    rc = compare_check_ids(univ, n_univ, t->n_nodes, bad_id);
+    if (rc != ST_OK) return rc;
+    if (P.chunks.empty()) {      // (no set of two positions: nothing to launch)
+        std::fill_n(out, P.n_sets * P.rows, st_dispersion_record{0.0, 0.0});
+        return ST_OK;
+    }
+    return partner_dispersion_run(t, univ, P, set_pos, n_pos, seed, stream, out, bad_id);
+} ST_CATCH_ALL
+
+int st_dispersion_matrix(int device, const float *D, int32_t n, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets,
+                         int64_t permutations, uint64_t seed, int32_t stream, int64_t chunk_tasks, st_dispersion_record *out)
+try {
+    DispersionPlan P;
+    std::string err;
+    const int rc = dispersion_plan(n, set_pos, n_pos, sets, n_sets, permutations, stream, chunk_tasks, P, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (device < -1) return fail(ST_ERR_ARG, "device must be -1 (host) or a device index");
+    if (!D) return fail(ST_ERR_ARG, "D is NULL");
+    if (n_sets > 0 && !out) return fail(ST_ERR_ARG, "out is NULL");
+    if (device < 0 || P.chunks.empty()) {
+        dispersion_host(D, P, set_pos, sets, seed, stream, out);
+        return ST_OK;
+    }
+    return dispersion_matrix_device(device, D, P, set_pos, n_pos, seed, stream, out);
 } ST_CATCH_ALL
 
 int st_graph_matrices_host(int device, int64_t n, int64_t n_edges, const int32_t *u, const int32_t *v,

@@ -513,6 +513,62 @@ class SuchLinkedTrees:
             observed = swapped
         return compare.CladeHommola(rows, leaves[rows], count[rows], observed, n_ge, n_nan, stats, permutations, seed, tree, skipped)
 
+    def partner_dispersion(self, of="A", permutations=999, seed=None, pool="subset", min_partners=2, max_partners=None, keep_null=False):
+        """Phylogenetic specificity: for each leaf, are its partners in the other tree close relatives of one another?
+
+        ``of="A"``: one row per TreeA leaf of the current ``subset_a`` (in ``subset_a_leafs`` order) with at least
+        ``min_partners`` -- and, unless ``max_partners`` is None, at most that many -- linked TreeB leaves inside the
+        current ``subset_b``; the distances are TreeB's.  ``of="B"`` is the mirror.  Each row holds the MPD and MNTD of
+        the leaf's partners and their standardised effect sizes against the null that shuffles the partner tree's leaf
+        labels (:meth:`SuchTree.dispersion`, picante's ``ses.mpd`` / ``ses.mntd`` with ``null.model = "taxa.labels"``;
+        NRI = -``mpd_ses``, NTI = -``mntd_ses``, ``mpd_p`` / ``mntd_p`` small for clustered partners).  ``pool`` is the
+        universe whose labels are shuffled: ``"subset"`` = every leaf of the partner tree's current subset, ``"linked"`` =
+        only those with a link in the current subset.  One shuffle serves every row: a row's null draws are uniform
+        k-subsets of the universe, and the rows share the shuffles.  The shuffles are those of ``SuchTree.dispersion``
+        with ``stream`` = the partner tree's subset root.  A universe of more than 16384 leaves is a ValueError: subset it
+        first.  No row, nothing launched.
+
+        The subset state, ``linklist`` and the generator of :meth:`sample_linked_distances` are left as they were.
+        Returns a :class:`~suchtree_amd.compare.SetDispersion` with ``leaves`` (the rows' leaf ids) and ``names``.
+        An extension: the reference has no counterpart.
+        """
+        import numbers
+        if of not in ("A", "B"):
+            raise ValueError("of must be 'A' or 'B'")
+        if pool not in ("subset", "linked"):
+            raise ValueError("pool must be 'subset' or 'linked'")
+        for name, v in (("min_partners", min_partners), ("max_partners", max_partners)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 0):
+                raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
+        ll = np.ascontiguousarray(self.linklist, dtype=np.int64)
+        if of == "A":
+            own, partner, own_ids, partner_ids = self._tree_a, self._tree_b, ll[:, 1], ll[:, 0]
+            own_leaves, partner_leaves, root = self._subset_a_leafs, self._subset_b_leafs, self._subset_b_root
+        else:
+            own, partner, own_ids, partner_ids = self._tree_b, self._tree_a, ll[:, 0], ll[:, 1]
+            own_leaves, partner_leaves, root = self._subset_b_leafs, self._subset_a_leafs, self._subset_a_root
+        universe = np.asarray(partner_leaves, dtype=np.int64) if pool == "subset" else np.unique(partner_ids)
+        if len(universe) > _capi.HOMMOLA_MAX_UNIVERSE:
+            raise ValueError("the partner tree's %s has %d leaves: at most %d (subset it first)"
+                             % ("subset" if pool == "subset" else "linked leaves", len(universe), _capi.HOMMOLA_MAX_UNIVERSE))
+        by_leaf = {}      # leaf -> its partners' ids
+        if len(ll):
+            order = np.argsort(own_ids, kind="stable")
+            ids, first, count = np.unique(own_ids[order], return_index=True, return_counts=True)
+            by_leaf = {int(v): partner_ids[order[b:b + c]] for v, b, c in zip(ids, first, count)}
+        leaves, sets = [], []
+        for leaf in np.asarray(own_leaves, dtype=np.int64).tolist():
+            partners = by_leaf.get(leaf)
+            k = 0 if partners is None else len(partners)
+            if k >= max(int(min_partners), 1) and (max_partners is None or k <= max_partners):
+                leaves.append(leaf)
+                sets.append(partners)
+        out = partner.dispersion(sets, universe=universe, permutations=permutations, seed=seed, stream=int(root), keep_null=keep_null)
+        out.leaves = np.asarray(leaves, dtype=np.int64)
+        names = own.leaf_nodes
+        out.names = [names[int(v)] for v in leaves]
+        return out
+
     @staticmethod
     def _leaf_counts(tree: SuchTree) -> np.ndarray:
         """Leaves under every node (st_clade_plan)."""

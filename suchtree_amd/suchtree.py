@@ -520,6 +520,99 @@ class SuchTree(TreeNavigation):
                                                                  k_count=count)
         return compare.QuartetComparison.from_table(table, n_leaves=m, mode=mode, seed=seed)
 
+    _DISPERSION_GROUP_ROWS = 1 << 22      # records per library call of dispersion: bounds its host memory (16 bytes each)
+
+    def _depth_first_leaves(self) -> np.ndarray:
+        """The leaf ids in depth-first order, children in increasing id order (st_clade_plan over one link per leaf)."""
+        leaf_ids = np.flatnonzero(np.asarray(self._flat.left) == -1).astype(np.int64)
+        return leaf_ids[_capi.clade_plan(self._flat.parent, leaf_ids)["perm"]]
+
+    def _leaf_ids(self, leaves, what) -> np.ndarray:
+        """Leaf ids of a collection of leaf names or leaf ids (ValueError for an id that is no leaf)."""
+        left = self._flat.left
+        if isinstance(leaves, np.ndarray) and leaves.dtype.kind in "iu":      # an id array: checked at once
+            ids = leaves.astype(np.int64).ravel()
+            ok = (ids >= 0) & (ids < self.size)
+            ok[ok] = np.asarray(left)[ids[ok]] == -1
+            if not ok.all():
+                raise ValueError("%s: %r is not a leaf of this tree" % (what, int(ids[~ok][0])))
+            return ids
+        leaves = list(leaves)
+        out = np.empty(len(leaves), dtype=np.int64)
+        for i, v in enumerate(leaves):
+            if isinstance(v, str):
+                if v not in self.leaves:
+                    raise NodeNotFoundError(v)
+                out[i] = self.leaves[v]
+            else:
+                if isinstance(v, bool) or not isinstance(v, Integral) or not 0 <= v < self.size or left[int(v)] != -1:
+                    raise ValueError("%s: %r is not a leaf of this tree" % (what, v))
+                out[i] = int(v)
+        return out
+
+    def dispersion(self, sets, universe=None, permutations=999, seed=None, stream=0, keep_null=False, chunk_tasks=0):
+        """How closely related are the members of each set of leaves: MPD and MNTD with a permutation null, on the GPU.
+
+        ``sets`` is an iterable of collections of leaf names or leaf ids.  For each, ``mpd`` is the mean pairwise distance
+        among its members and ``mntd`` the mean distance from a member to its nearest other member, in float64 over the
+        float32 distances of ``distances_bulk``.  Both are standardised against the null that shuffles the leaf labels of
+        ``universe`` (a collection of leaves; None = all leaves of the tree; 3 to 16384 leaves), picante's ``ses.mpd`` /
+        ``ses.mntd`` with ``null.model = "taxa.labels"``: NRI = -``mpd_ses``, NTI = -``mntd_ses``.  One shuffle serves
+        every set of the call: a set's null draws are uniform k-subsets of the universe, and the sets share the
+        shuffles.  Every member must be in the universe; a repeated member is a ValueError.
+
+        The universe's distances are computed once, as a matrix on the GPU, and every (set, permutation) is reduced
+        there.  Shuffle p >= 1 is ``compare.hommola_permutation(seed, stream, p, 0, n)`` over the universe in depth-first
+        order (children in increasing id order); a set's columns depend on (seed, ``stream``, the universe, the set)
+        alone -- not on the other sets or ``chunk_tasks`` -- and null column p is the same for any ``permutations`` >= p.
+        ``seed=None`` draws a seed and reports it.  ``keep_null=True`` keeps the (sets, permutations) null draws.
+        Returns a :class:`~suchtree_amd.compare.SetDispersion`.  An extension: the reference has no counterpart.
+        """
+        from . import compare
+        if isinstance(permutations, bool) or not isinstance(permutations, Integral) or permutations < 0:
+            raise ValueError("permutations must be a non-negative integer, got %r" % (permutations,))
+        if seed is None:
+            seed = int(np.random.SeedSequence().generate_state(1, np.uint64)[0])
+        if isinstance(seed, bool) or not isinstance(seed, Integral) or not 0 <= seed < 1 << 64:
+            raise ValueError("seed must be an integer from 0 to 2^64 - 1, got %r" % (seed,))
+        if isinstance(stream, bool) or not isinstance(stream, Integral) or not 0 <= stream < 1 << 31:
+            raise ValueError("stream must be an integer from 0 to 2^31 - 1, got %r" % (stream,))
+        if isinstance(chunk_tasks, bool) or not isinstance(chunk_tasks, Integral) or chunk_tasks < 0:
+            raise ValueError("chunk_tasks must be a non-negative integer, got %r" % (chunk_tasks,))
+        permutations, seed = int(permutations), int(seed)
+        univ = self._depth_first_leaves()
+        if universe is not None:
+            inside = np.zeros(self.size, dtype=bool)
+            inside[self._leaf_ids(universe, "universe")] = True
+            univ = univ[inside[univ]]
+        limit = _capi.HOMMOLA_MAX_UNIVERSE
+        if len(univ) < 3:
+            raise ValueError("the universe has %d leaves: at least 3" % len(univ))
+        if len(univ) > limit:
+            raise ValueError("the universe has %d leaves: at most %d (subset it first)" % (len(univ), limit))
+        where = np.full(self.size, -1, dtype=np.int64)
+        where[univ] = np.arange(len(univ))
+        rows = []
+        for r, members in enumerate(sets):
+            pos = np.sort(where[self._leaf_ids(members, "set %d" % r)])
+            if len(pos) and pos[0] < 0:
+                raise ValueError("set %d: a member outside the universe" % r)
+            if np.any(pos[1:] == pos[:-1]):
+                raise ValueError("set %d: a repeated member" % r)
+            rows.append(pos.astype(np.int32))
+        k = np.array([len(p) for p in rows], dtype=np.int64)
+        offsets = np.zeros(len(rows) + 1, dtype=np.int64)
+        np.cumsum(k, out=offsets[1:])
+        set_pos = np.concatenate(rows) if rows else np.empty(0, dtype=np.int32)
+        out = compare.SetDispersion(len(rows), permutations, seed, len(univ), keep_null)
+        per_group = max(1, self._DISPERSION_GROUP_ROWS // (permutations + 1))
+        for at in range(0, len(rows), per_group):      # (no sets: nothing is launched, and the tree stays where it is)
+            end = min(at + per_group, len(rows))
+            part = (set_pos[offsets[at]:offsets[end]], offsets[at:end + 1] - offsets[at])
+            rec = self._device_tree().partner_dispersion_host(univ, part, permutations, seed, int(stream), int(chunk_tasks))
+            out.fill(at, k[at:end], rec)      # (each group is reduced before the next)
+        return out
+
     def common_ancestor(self, a: Union[int, str], b: Union[int, str]) -> int:
         """Most recent common ancestor of two nodes (MuchTree.pyx:1128-1149)."""
         node_a, node_b = self._validate_node_pair(a, b)
