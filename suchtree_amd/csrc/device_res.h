@@ -1,12 +1,14 @@
 // device_res.h -- host-only owners of HIP resources: device memory (DevBuf), pinned host memory (PinnedBuf), a stream
-// (Stream), an event (Event).  Move-only (a declared move constructor deletes copying).  Each reads as the raw pointer or
-// handle it owns, so kernel arguments, null tests and pointer arithmetic are written as on a raw field.  What the code
-// around them relies on:
+// (Stream, DrainedStream), an event (Event).  Move-only (a declared move constructor deletes copying).  Each reads as the
+// raw pointer or handle it owns, so kernel arguments, null tests and pointer arithmetic are written as on a raw field.
+// What the code around them relies on:
 //   * a destructor only releases: it reports nothing and leaves the thread's error message alone;
 //   * a destructor runs with the owning device current: call-scoped owners are declared after ST_DEVICE(...), owners
 //     inside a heap object die in a `delete` under a DeviceScope;
 //   * no owner has static storage duration (the runtime may be gone before a static destructor runs);
-//   * Stream's destructor does not synchronise: whoever owns memory that the stream's work touches drains it first.
+//   * Stream's destructor does not synchronise: whoever owns memory that the stream's work touches drains it first.  A
+//     call's own stream is a DrainedStream, whose destructor does: memory that the stream's work touches is declared
+//     before the DrainedStream; reverse destruction order does the rest.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -84,6 +86,10 @@ public:
 
 private:
     hipStream_t s_ = nullptr;
+};
+
+struct DrainedStream : Stream {      // the stream of one call, not moved: drained, then destroyed
+    ~DrainedStream() { if (*this) (void)hipStreamSynchronize(*this); }
 };
 
 class Event {

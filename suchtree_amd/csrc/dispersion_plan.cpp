@@ -17,8 +17,8 @@ static int fail(int code, std::string &err, const std::string &msg)
 int dispersion_plan(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets, int64_t permutations,
                     int32_t stream, int64_t chunk_tasks, DispersionPlan &P, std::string &err)
 {
-    if (n_univ < 3 || n_univ > kHommolaMaxUniverse)
-        return fail(ST_ERR_ARG, err, "a universe of " + std::to_string(n_univ) + " positions: 3 to " + std::to_string(kHommolaMaxUniverse));
+    if (n_univ < 3 || n_univ > kPermMaxUniverse)
+        return fail(ST_ERR_ARG, err, "a universe of " + std::to_string(n_univ) + " positions: 3 to " + std::to_string(kPermMaxUniverse));
     if (permutations < 0) return fail(ST_ERR_ARG, err, "permutations < 0");
     if (chunk_tasks < 0) return fail(ST_ERR_ARG, err, "chunk_tasks < 0");
     if (stream < 0) return fail(ST_ERR_ARG, err, "stream < 0");
@@ -138,7 +138,7 @@ void dispersion_host(const float *D, const DispersionPlan &P, const int32_t *set
 {
     std::vector<int32_t> sigma((size_t)P.n_univ), q((size_t)std::max(P.max_count, 1));
     for (int64_t p = 0; p < P.rows; p++) {
-        hommola_permutation_host(seed, stream, p, 0, P.n_univ, sigma.data());      // (one sigma serves every set)
+        perm_host(seed, stream, p, 0, P.n_univ, sigma.data());      // (one sigma serves every set)
         for (int64_t r = 0; r < P.n_sets; r++) {
             const int64_t b = sets[r], k = sets[r + 1] - b;
             for (int64_t i = 0; i < k && k >= 2; i++) q[(size_t)i] = sigma[(size_t)set_pos[b + i]];

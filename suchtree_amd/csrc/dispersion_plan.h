@@ -15,7 +15,7 @@
 #include <string>
 #include <vector>
 
-#include "hommola_plan.h"
+#include "keyed_perm.h"
 
 namespace st {
 
@@ -63,7 +63,7 @@ struct DispersionPlan {
     int64_t max_chunk_tasks = 0;
 };
 
-// ST_OK, or ST_ERR_ARG with `err`.  Checks, in this order: the universe size (3 .. kHommolaMaxUniverse), nothing negative
+// ST_OK, or ST_ERR_ARG with `err`.  Checks, in this order: the universe size (3 .. kPermMaxUniverse), nothing negative
 // (permutations, chunk_tasks, stream, the counts), the offsets (sets[0 .. n_sets]: 0 <= sets[r] <= sets[r + 1] <= n_pos),
 // every set (positions inside the universe, strictly increasing).  Then the layout above: chunk_tasks 0 = blocks of up
 // to kDispersionSigmaBytes of sigma rows and chunks of kDispersionChunkTasks tasks; chunk_tasks > 0 = at most that many

@@ -1,5 +1,5 @@
-// hommola_plan.cpp -- see hommola_plan.h.  Index arithmetic driven by caller-supplied positions and clade ranges, the
-// host form of the permutation and the float64 folding of pieces: no GPU calls.
+// hommola_plan.cpp -- see hommola_plan.h.  Index arithmetic driven by caller-supplied positions and clade ranges and the
+// float64 folding of pieces: no GPU calls.
 #include "hommola_plan.h"
 
 #include <algorithm>
@@ -13,37 +13,14 @@ static int fail(int code, std::string &err, const std::string &msg)
     return code;
 }
 
-int hommola_permutation_args(int32_t node, int64_t p, int side, int32_t n, std::string &err)
-{
-    if (n < 1 || n > kHommolaMaxUniverse)
-        return fail(ST_ERR_ARG, err, "a universe of " + std::to_string(n) + " positions: 1 to " + std::to_string(kHommolaMaxUniverse));
-    if (p < 0) return fail(ST_ERR_ARG, err, "permutation index < 0");
-    if (side != 0 && side != 1) return fail(ST_ERR_ARG, err, "side must be 0 (the clade tree) or 1 (the other tree)");
-    if (node < 0) return fail(ST_ERR_ARG, err, "node < 0");
-    return ST_OK;
-}
-
-void hommola_permutation_host(uint64_t seed, int32_t node, int64_t p, int side, int32_t n, int32_t *out)
-{
-    if (p == 0) {
-        std::iota(out, out + n, 0);
-        return;
-    }
-    const uint64_t h1 = hommola_stream(seed, node, p, side);
-    std::vector<uint64_t> w((size_t)n);
-    for (int32_t i = 0; i < n; i++) w[(size_t)i] = hommola_key(h1, (uint32_t)i);
-    std::sort(w.begin(), w.end());
-    for (int32_t j = 0; j < n; j++) out[j] = (int32_t)(w[(size_t)j] & 0xFFFF);
-}
-
 int hommola_plan(int32_t n_univ_o, int32_t n_univ_c, const int32_t *pos_o, const int32_t *pos_c, int64_t n_links,
                  const st_hommola_clade *clades, int64_t n_clades, int64_t permutations, int64_t chunk_blocks, HommolaPlan &P,
                  std::string &err)
 {
     if (n_univ_o < 0 || n_univ_c < 0 || n_links < 0 || n_clades < 0) return fail(ST_ERR_ARG, err, "negative size");
-    if (n_univ_o > kHommolaMaxUniverse || n_univ_c > kHommolaMaxUniverse)
+    if (n_univ_o > kPermMaxUniverse || n_univ_c > kPermMaxUniverse)
         return fail(ST_ERR_ARG, err, "universes of " + std::to_string(n_univ_o) + " and " + std::to_string(n_univ_c) + " leaves: at most " +
-                                         std::to_string(kHommolaMaxUniverse) + " each");
+                                         std::to_string(kPermMaxUniverse) + " each");
     if (permutations < 0) return fail(ST_ERR_ARG, err, "permutations < 0");
     if (chunk_blocks < 0) return fail(ST_ERR_ARG, err, "chunk_blocks < 0");
     if (n_links > INT32_MAX) return fail(ST_ERR_ARG, err, "more than 2^31 - 1 links");
@@ -148,7 +125,7 @@ int hommola_plan(int32_t n_univ_o, int32_t n_univ_c, const int32_t *pos_o, const
         k.rel_begin = P.row_rel(first.row);
         k.n_rel = P.row_rel(last.row) + P.clades[(size_t)last.clade].link_count - k.rel_begin;
         for (int64_t q = first.clade; q <= last.clade; q++)
-            if (P.clades[(size_t)q].link_count >= 2) k.side0_classes |= 1u << hommola_sort_class(P.clades[(size_t)q].leaf_count);
+            if (P.clades[(size_t)q].link_count >= 2) k.side0_classes |= 1u << perm_sort_class(P.clades[(size_t)q].leaf_count);
         P.chunks.push_back(k);
         P.max_chunk_blocks = std::max(P.max_chunk_blocks, n);
         P.max_chunk_rel = std::max(P.max_chunk_rel, k.n_rel);

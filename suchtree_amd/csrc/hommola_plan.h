@@ -1,6 +1,6 @@
-// hommola_plan.h -- the host-only side of Hommola's permutation test for many clades at once (st_hommola_clades_host,
-// st_hommola_permutation), plain C++17, and the inline functions the device shares with it (kernels_hommola.h): the key
-// whose sort defines a permutation.  No GPU calls in here (hommola_plan.cpp): the "not gpu" tests run it under the
+// hommola_plan.h -- the host-only side of Hommola's permutation test for many clades at once (st_hommola_clades_host),
+// plain C++17, and the clade table the device shares with it (kernels_hommola.h); the permutation of a row is
+// keyed_perm.h's.  No GPU calls in here (hommola_plan.cpp): the "not gpu" tests run it under the
 // address / undefined-behaviour sanitizers (tests/emu/sanitize_hommola.cpp).  The definitions are the contract of
 // include/suchtree_hip.h (st_hommola_clades_host).
 //
@@ -15,24 +15,9 @@
 #include <vector>
 
 #include "compare_plan.h"
-#include "quartet_plan.h"
+#include "keyed_perm.h"
 
 namespace st {
-
-constexpr int32_t kHommolaMaxUniverse = ST_HOMMOLA_MAX_UNIVERSE;      // positions travel as 16 bits, keys carry 16 bits of index
-constexpr uint64_t kHommolaGolden = 0x9E3779B97F4A7C15ull;
-
-// the key of (seed, clade node, permutation p >= 1, side): h1, then w_i of universe position i.  Sorting the w of a
-// universe gives the permutation: sigma[j] = low 16 bits of the j-th smallest w (the w are distinct).
-ST_QUARTET_HD uint64_t hommola_stream(uint64_t seed, int32_t node, int64_t p, int side)
-{
-    const uint64_t h0 = quartet_mix(seed + ((uint64_t)(int64_t)node + 1) * kHommolaGolden);
-    return quartet_mix(h0 + (2 * (uint64_t)p + (uint64_t)side) * kHommolaGolden);
-}
-ST_QUARTET_HD uint64_t hommola_key(uint64_t h1, uint32_t i)
-{
-    return (quartet_mix(h1 + ((uint64_t)i + 1) * kHommolaGolden) & 0xFFFFFFFFFFFF0000ull) | (uint64_t)i;
-}
 
 // what the device reads of one clade (and the host of its rows and blocks); a sentinel closes the table
 struct HommolaCladeDev {
@@ -54,13 +39,8 @@ struct HommolaChunk {
     int64_t block_begin, n_blocks;      // global blocks [block_begin, block_begin + n_blocks)
     int64_t row_begin, n_rows;          // the rows they belong to
     int64_t rel_begin, n_rel;           // the relabelled positions of those rows
-    unsigned side0_classes;             // bit k: a clade-side sort of size class k is needed (HommolaSortClass)
+    unsigned side0_classes;             // bit k: a clade-side sort of size class k is needed (PermSortClass)
 };
-
-enum HommolaSortClass { kHommolaSortWave = 0, kHommolaSortSmall = 1, kHommolaSortLarge = 2 };
-constexpr int kHommolaWaveMax = 64;           // universes of up to 64 positions: one wave, keys in registers
-constexpr int kHommolaSmallMax = 2048;        // up to 2048: 256 lanes and 16 KiB of LDS; beyond: 1024 lanes, up to 128 KiB
-ST_QUARTET_HD int hommola_sort_class(int n) { return n <= kHommolaWaveMax ? kHommolaSortWave : n <= kHommolaSmallMax ? kHommolaSortSmall : kHommolaSortLarge; }
 
 struct HommolaRange {
     int32_t leaf_begin, leaf_count;
@@ -88,10 +68,6 @@ struct HommolaPlan {
 int hommola_plan(int32_t n_univ_o, int32_t n_univ_c, const int32_t *pos_o, const int32_t *pos_c, int64_t n_links,
                  const st_hommola_clade *clades, int64_t n_clades, int64_t permutations, int64_t chunk_blocks, HommolaPlan &P,
                  std::string &err);
-
-// the permutation of (seed, node, p, side) over n positions, 1 <= n <= kHommolaMaxUniverse; p = 0: the identity
-void hommola_permutation_host(uint64_t seed, int32_t node, int64_t p, int side, int32_t n, int32_t *out);
-int hommola_permutation_args(int32_t node, int64_t p, int side, int32_t n, std::string &err);
 
 // pieces[n] of global blocks [block_begin, block_begin + n) into out[row] (n_rows entries, moments_empty() before the
 // first block of a row): clade_merge in block order

@@ -16,6 +16,13 @@ constexpr int64_t kCompareChunkPairs = (int64_t)1 << 22;      // + 2 x 64 MiB of
 // parts of one device block start on 256-byte boundaries
 static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
+// a kernel that sorts with perm_sort_lds is about to get `lds` bytes (perm_lds_bytes): above 32 KiB they are asked for
+template <typename Kernel>
+static hipError_t perm_lds_opt_in(Kernel *kernel, size_t lds)
+{
+    return lds <= 32 * 1024 ? hipSuccess : hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
 // The moments / 2-D histogram reduction of st_compare_triangle_host / st_compare_pairs_host (kernels_compare.h), as a
 // reducer of compare_run: bytes(chunk) device bytes of its own, start() once, chunk() per chunk of distances, finish()
 // enqueues the read-back, done() fills the result once the stream has drained.
@@ -96,16 +103,17 @@ struct MomentsReduce {
     }
 };
 
-// What the two chunk drivers -- compare_run below, quartet_run in host_quartets.h -- share: both trees' pipe mutexes, one
-// stream, one device block, the two host fault words.  Declared after ST_DEVICE(...).  Both trees live on one device and
-// so share its staging pipe and that pipe's mutex (host_tree.h): one lock, also when tree_x == tree_y; distinct mutexes
-// (not possible today) are taken in address order.  `what` words the messages ("compare", "quartet compare").
+// What the chunk drivers (compare_run below, quartet_run, hommola_clades_run, partner_dispersion_run) share: both trees'
+// pipe mutexes, one device block, one stream, the two host fault words.  Declared after ST_DEVICE(...) and after whatever
+// else its stream's work touches (device_res.h).  Both trees live on one device and so share its staging pipe and that
+// pipe's mutex (host_tree.h): one lock, also when tree_x == tree_y; distinct mutexes (not possible today) are taken in
+// address order.  `what` words the messages ("compare", "quartet compare").
 struct TwoTreeSession {
     st_tree *tx, *ty;
     const char *what;
     std::unique_lock<std::mutex> lock_a, lock_b;
-    Stream s;
     DevBuf<char> d;
+    DrainedStream s;
 
     TwoTreeSession(st_tree *x, st_tree *y, const char *w) : tx(x), ty(y), what(w)
     {
@@ -113,13 +121,6 @@ struct TwoTreeSession {
         if (mb < ma) std::swap(ma, mb);
         lock_a = std::unique_lock<std::mutex>(*ma);
         if (mb != ma) lock_b = std::unique_lock<std::mutex>(*mb);
-    }
-    // the block dies only once the stream has drained, the stream after the block, the locks last
-    ~TwoTreeSession()
-    {
-        if (s) (void)hipStreamSynchronize(s);
-        d.reset();
-        s.reset();
     }
     int hip_fail(const char *step, hipError_t e) const { return fail(ST_ERR_HIP, std::string(what) + step + hipGetErrorString(e)); }
     // the stream and the block of `total` bytes
@@ -141,6 +142,60 @@ struct TwoTreeSession {
         if (rc == ST_OK) rc = report_fault(ty->n_nodes, fy, bad_id);
         return rc;
     }
+};
+
+// The two-slot read-back of a chunk driver whose host folds one chunk's results while the device works on the next: two
+// pinned buffers of T, an event each, and what the caller has to know about a fill (Tag).  Per chunk: acquire() before
+// the chunk's launches hands the fill of two chunks ago to `use`, the launches write the device twin of slot `next` (a
+// part of the caller's block), post() copies it out.  flush() at the end hands over what is left, the older fill first:
+// where results are merged, that order is part of their bits.  Declared before the session or stream that fills it.
+template <typename T, typename Tag>
+struct ReadbackRing {
+    PinnedBuf<T> h[2];
+    Event ev[2];
+    Tag tag[2] = {};
+    bool full[2] = {false, false};
+    int next = 0;
+
+    // both buffers (`count` elements each), then both events: after a failure, a null buffer tells which it was
+    hipError_t alloc(size_t count)
+    {
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < 2 && e == hipSuccess; i++) e = h[i].alloc(count, hipHostMallocDefault);
+        for (int i = 0; i < 2 && e == hipSuccess; i++) e = ev[i].create(hipEventDisableTiming);
+        return e;
+    }
+    template <typename Use>
+    hipError_t acquire(Use use)
+    {
+        if (!full[next]) return hipSuccess;
+        const hipError_t e = hipEventSynchronize(ev[next]);
+        if (e != hipSuccess) return e;
+        use(h[next].get(), tag[next]);
+        full[next] = false;
+        return hipSuccess;
+    }
+    hipError_t post(const T *d_src, size_t n, const Tag &t, hipStream_t s)
+    {
+        hipError_t e = hipMemcpyAsync(h[next], d_src, n * sizeof(T), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipEventRecord(ev[next], s);
+        if (e != hipSuccess) return e;
+        tag[next] = t;
+        full[next] = true;
+        next ^= 1;
+        return hipSuccess;
+    }
+    template <typename Use>
+    hipError_t flush(Use use)
+    {
+        const hipError_t e = acquire(use);      // (`next` is the older slot)
+        next ^= 1;
+        return e == hipSuccess ? acquire(use) : e;
+    }
+};
+
+struct BlockSpan {      // the tag of a slot of pieces: global blocks [first, first + count)
+    int64_t first, count;
 };
 
 // count pairs in chunks of `chunk`: prep(stream, off, c) stages what chunk [off, off + c) needs, src_x(off) / src_y(off)
@@ -305,70 +360,48 @@ struct CladeReduce {
 };
 
 // The reducer of st_compare_rows_host: k_row_blocks per chunk into one of two device piece buffers, each read back into
-// its pinned host twin; the host folds a chunk's pieces into their rows (block order, clade_merge) while the device works
-// on the next chunk.  Pieces of at most two chunks exist at any time.
+// its pinned host twin (ReadbackRing); the host folds a chunk's pieces into their rows (block order, clade_merge) while
+// the device works on the next chunk.  Pieces of at most two chunks exist at any time.
 struct RowsReduce {
     const RowsLayout &L;
     st_pair_moments *out;
     CladePiece *d_pieces[2] = {nullptr, nullptr};      // (parts of compare_run's block)
-    PinnedBuf<CladePiece> h_pieces[2];
-    Event ev[2];
-    int64_t first[2] = {0, 0}, count[2] = {0, 0};      // buffer i holds blocks [first, first + count); 0: nothing pending
-    int next = 0;
+    ReadbackRing<CladePiece, BlockSpan> ring;
 
     RowsReduce(const RowsLayout &l, st_pair_moments *o) : L(l), out(o) {}
     size_t piece_bytes() const { return align256((size_t)L.max_blocks * sizeof(CladePiece)); }
     size_t bytes(int64_t) { return 2 * piece_bytes(); }
     hipError_t start(char *d, int64_t, hipStream_t)
     {
-        hipError_t e = hipSuccess;
-        for (int i = 0; i < 2 && e == hipSuccess; i++) {
-            d_pieces[i] = reinterpret_cast<CladePiece *>(d + i * piece_bytes());
-            e = h_pieces[i].alloc((size_t)L.max_blocks, hipHostMallocDefault);
-            if (e == hipSuccess) e = ev[i].create(hipEventDisableTiming);
-        }
-        return e;
+        for (int i = 0; i < 2; i++) d_pieces[i] = reinterpret_cast<CladePiece *>(d + i * piece_bytes());
+        return ring.alloc((size_t)L.max_blocks);
     }
-    hipError_t drain(int i)
+    void fold(const CladePiece *pieces, const BlockSpan &b)
     {
-        if (count[i] == 0) return hipSuccess;
-        const hipError_t e = hipEventSynchronize(ev[i]);
-        if (e != hipSuccess) return e;
-        for (int64_t j = 0; j < count[i]; j++) {
-            const int64_t t = first[i] + j;
-            clade_merge(out[t / L.nb], piece_moments(h_pieces[i][j], L.block_len(t)));
+        for (int64_t j = 0; j < b.count; j++) {
+            const int64_t t = b.first + j;
+            clade_merge(out[t / L.nb], piece_moments(pieces[j], L.block_len(t)));
         }
-        count[i] = 0;
-        return hipSuccess;
     }
     hipError_t chunk(const float *d_x, const float *d_y, int64_t off, int64_t c, hipStream_t s)
     {
-        const int i = next;
-        next ^= 1;
-        hipError_t e = drain(i);      // (the pieces of two chunks ago)
+        hipError_t e = ring.acquire([&](const CladePiece *p, const BlockSpan &b) { fold(p, b); });      // (the pieces of two chunks ago)
         if (e != hipSuccess) return e;
         const int64_t t0 = L.block_of(off), n = L.block_of(off + c - 1) + 1 - t0, tl = t0 + n - 1;
         if (n > L.max_blocks || L.block_lo(t0) != off || L.block_lo(tl) + L.block_len(tl) > off + c) return hipErrorInvalidValue;
         const int64_t per = L.P <= kCladeLanePiece ? kCladeThreads : kCladeThreads / 64;      // blocks per workgroup
+        CladePiece *const d_out = d_pieces[ring.next];
         hipLaunchKernelGGL(k_row_blocks, dim3((unsigned)((n + per - 1) / per)), dim3(kCladeThreads), 0, s, d_x, d_y, (long long)off,
-                           (long long)L.S, (long long)L.P, (long long)L.nb, (long long)t0, (long long)n, d_pieces[i]);
+                           (long long)L.S, (long long)L.P, (long long)L.nb, (long long)t0, (long long)n, d_out);
         e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(h_pieces[i], d_pieces[i], (size_t)n * sizeof(CladePiece), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipEventRecord(ev[i], s);
-        if (e == hipSuccess) {
-            first[i] = t0;
-            count[i] = n;
-        }
+        if (e == hipSuccess) e = ring.post(d_out, (size_t)n, BlockSpan{t0, n}, s);
         return e;
     }
     hipError_t finish(hipStream_t) { return hipSuccess; }
     int done()
     {
-        for (int k = 0; k < 2; k++, next ^= 1) {      // the older buffer first
-            const hipError_t e = drain(next);
-            if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("rows read-back: ") + hipGetErrorString(e));
-        }
-        return ST_OK;
+        const hipError_t e = ring.flush([&](const CladePiece *p, const BlockSpan &b) { fold(p, b); });
+        return e == hipSuccess ? ST_OK : fail(ST_ERR_HIP, std::string("rows read-back: ") + hipGetErrorString(e));
     }
 };
 
@@ -703,21 +736,18 @@ static int kendall_arrays(int device, const float *x, const float *y, int64_t n,
     KendallState K;
     int rc = K.alloc(n);
     if (rc != ST_OK) return rc;
-    struct Drained {      // (declared after K: the stream drains before the buffers go)
-        Stream s;
-        ~Drained() { if (s) (void)hipStreamSynchronize(s); }
-    } q;
+    DrainedStream s;
     float *d_x = reinterpret_cast<float *>(K.d_keys[1].get()), *d_y = d_x + n;
-    hipError_t e = q.s.create();
-    if (e == hipSuccess) e = K.start(q.s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_x, x, (size_t)n * 4, hipMemcpyHostToDevice, q.s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_y, y, (size_t)n * 4, hipMemcpyHostToDevice, q.s);
+    hipError_t e = s.create();
+    if (e == hipSuccess) e = K.start(s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_x, x, (size_t)n * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_y, y, (size_t)n * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_kendall_keys, dim3(K.grid()), dim3(kKendallThreads), 0, q.s, d_x, d_y, (long long)n, K.d_keys[0].get(), K.d_nan());
+        hipLaunchKernelGGL(k_kendall_keys, dim3(K.grid()), dim3(kKendallThreads), 0, s, d_x, d_y, (long long)n, K.d_keys[0].get(), K.d_nan());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = K.enqueue(q.s);
-    if (e == hipSuccess) e = hipStreamSynchronize(q.s);
+    if (e == hipSuccess) e = K.enqueue(s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("Kendall counts: ") + hipGetErrorString(e));
     K.done(out);
     return ST_OK;

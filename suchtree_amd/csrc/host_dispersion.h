@@ -3,25 +3,20 @@
 // scatter: dispersion_plan.cpp).  The float32 matrix D is the caller's, uploaded, or written once by the unchanged
 // distance kernels over a SrcGrid.  One work block beside it: the positions, the set table, one block of sigma rows and
 // two chunks of records.  Per block of permutations: its sorts (k_dispersion_sigma); per chunk of whole tasks: one launch
-// per size class it meets (k_dispersion_tasks_*), its records copied to one of two pinned buffers and scattered to the
-// caller's rows while the device works on the next chunk.
+// per size class it meets (k_dispersion_tasks_*), its records copied to one of two pinned buffers (ReadbackRing,
+// host_compare.h) and scattered to the caller's rows while the device works on the next chunk.
 #pragma once
 
-// what a call holds besides D and the stream; declared before the stream's owner, so that it dies after the stream has drained
-struct DispersionWork {
-    DevBuf<char> d;
-    PinnedBuf<st_dispersion_record> h[2];
-    Event ev[2];
-};
+using DispersionRing = ReadbackRing<st_dispersion_record, const DispersionChunk *>;
 
 static hipError_t dispersion_launch_sigma(const DispersionSigmaArgs &a, int64_t n_perms, hipStream_t s)
 {
-    const int cls = hommola_sort_class(a.n);
-    if (cls == kHommolaSortLarge) {
-        hipLaunchKernelGGL(k_dispersion_sigma<kHommolaLargeThreads>, dim3((unsigned)n_perms), dim3(kHommolaLargeThreads), hommola_lds_bytes(a.n), s, a);
+    const int cls = perm_sort_class(a.n);
+    if (cls == kPermSortLarge) {
+        hipLaunchKernelGGL(k_dispersion_sigma<kPermLargeThreads>, dim3((unsigned)n_perms), dim3(kPermLargeThreads), perm_lds_bytes(a.n), s, a);
     } else {
-        hipLaunchKernelGGL(k_dispersion_sigma<kHommolaSmallThreads>, dim3((unsigned)n_perms), dim3(kHommolaSmallThreads),
-                           cls == kHommolaSortWave ? 0 : hommola_lds_bytes(a.n), s, a);
+        hipLaunchKernelGGL(k_dispersion_sigma<kPermSmallThreads>, dim3((unsigned)n_perms), dim3(kPermSmallThreads),
+                           cls == kPermSortWave ? 0 : perm_lds_bytes(a.n), s, a);
     }
     return hipGetLastError();
 }
@@ -55,9 +50,10 @@ static hipError_t dispersion_launch_tasks(const DispersionPlan &P, const Dispers
     return hipSuccess;
 }
 
-// every chunk of the plan on stream s over the device matrix d_D; `what` names the call in messages.  Returns ST_OK,
+// every chunk of the plan on stream s over the device matrix d_D, with the caller's work block and ring (declared before
+// the stream's owner); `what` names the call in messages.  Returns ST_OK,
 // ST_ERR_NOMEM or ST_ERR_HIP; on return nothing of this call is pending on s unless a HIP call failed.
-static int dispersion_chunks(DispersionWork &W, const char *what, hipStream_t s, const float *d_D, const DispersionPlan &P,
+static int dispersion_chunks(DevBuf<char> &d_work, DispersionRing &ring, const char *what, hipStream_t s, const float *d_D, const DispersionPlan &P,
                              const int32_t *set_pos, int64_t n_pos, uint64_t seed, int32_t stream, st_dispersion_record *out)
 {
     const size_t n = (size_t)P.n_univ, live = P.sets.size();
@@ -65,47 +61,31 @@ static int dispersion_chunks(DispersionWork &W, const char *what, hipStream_t s,
     const size_t rec_bytes = align256((size_t)P.max_chunk_tasks * sizeof(st_dispersion_record));
     const size_t o_rec = o_sigma + align256((size_t)P.perm_block * n * 2), total = o_rec + 2 * rec_bytes;
     auto hip_fail = [&](const char *step, hipError_t e) { return fail(ST_ERR_HIP, std::string(what) + step + hipGetErrorString(e)); };
-    hipError_t e = W.d.alloc(total);
+    hipError_t e = d_work.alloc(total);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return fail(ST_ERR_NOMEM, std::string(what) + ": a work block of " + std::to_string(total) + " bytes: " + hipGetErrorString(e));
     }
-    for (int i = 0; i < 2; i++) {
-        e = W.h[i].alloc((size_t)P.max_chunk_tasks, hipHostMallocDefault);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ST_ERR_NOMEM, std::string(what) + ": a pinned buffer of " + std::to_string((size_t)P.max_chunk_tasks * sizeof(st_dispersion_record)) +
-                                          " bytes: " + hipGetErrorString(e));
-        }
-        e = W.ev[i].create(hipEventDisableTiming);
-        if (e != hipSuccess) return hip_fail(" setup: ", e);
+    e = ring.alloc((size_t)P.max_chunk_tasks);
+    if (e != hipSuccess && !(ring.h[0] && ring.h[1])) {
+        (void)hipGetLastError();
+        return fail(ST_ERR_NOMEM, std::string(what) + ": a pinned buffer of " + std::to_string((size_t)P.max_chunk_tasks * sizeof(st_dispersion_record)) +
+                                      " bytes: " + hipGetErrorString(e));
     }
+    if (e != hipSuccess) return hip_fail(" setup: ", e);
     std::fill_n(out, P.n_sets * P.rows, st_dispersion_record{0.0, 0.0});      // (every allocation has succeeded: from here on out is written)
-    char *const d = W.d;
+    char *const d = d_work;
     st_dispersion_record *d_rec[2] = {reinterpret_cast<st_dispersion_record *>(d + o_rec), reinterpret_cast<st_dispersion_record *>(d + o_rec + rec_bytes)};
     e = hipMemcpyAsync(d, set_pos, (size_t)n_pos * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d + o_sets, P.sets.data(), live * sizeof(DispersionSetDev), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = perm_lds_opt_in(k_dispersion_sigma<kPermLargeThreads>, perm_lds_bytes((int)n));      // (above 32 KiB: the large class)
     if (e != hipSuccess) return hip_fail(" setup: ", e);
-    if (hommola_lds_bytes((int)n) > 32 * 1024 && hommola_sort_class((int)n) == kHommolaSortLarge) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dispersion_sigma<kHommolaLargeThreads>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)hommola_lds_bytes((int)n));
-        if (e != hipSuccess) return hip_fail(" setup: ", e);
-    }
-    const DispersionChunk *pending[2] = {nullptr, nullptr};
-    auto drain = [&](int i) {
-        if (!pending[i]) return hipSuccess;
-        const hipError_t de = hipEventSynchronize(W.ev[i]);
-        if (de != hipSuccess) return de;
-        dispersion_scatter(P, *pending[i], W.h[i], out);
-        pending[i] = nullptr;
-        return hipSuccess;
-    };
+    auto scatter = [&](const st_dispersion_record *records, const DispersionChunk *c) { dispersion_scatter(P, *c, records, out); };
     int64_t sigma_p = -1;      // the block whose rows the device holds
-    for (size_t k = 0; k < P.chunks.size(); k++) {
-        const DispersionChunk &c = P.chunks[k];
-        const int i = (int)(k & 1);
-        e = drain(i);      // (the records of two chunks ago)
+    for (const DispersionChunk &c : P.chunks) {
+        e = ring.acquire(scatter);      // (the records of two chunks ago)
         if (e != hipSuccess) return hip_fail(" read-back: ", e);
+        st_dispersion_record *const d_out = d_rec[ring.next];
         if (c.p_begin != sigma_p) {      // (stream order: the tasks of the block before have read their rows)
             e = dispersion_launch_sigma(DispersionSigmaArgs{reinterpret_cast<unsigned short *>(d + o_sigma), (long long)c.p_begin, (unsigned long long)seed,
                                                             (int)stream, (int)n},
@@ -114,18 +94,13 @@ static int dispersion_chunks(DispersionWork &W, const char *what, hipStream_t s,
             sigma_p = c.p_begin;
         }
         const DispersionTaskArgs ta{d_D, reinterpret_cast<const unsigned short *>(d + o_sigma), reinterpret_cast<const int *>(d),
-                                    reinterpret_cast<const DispersionSetDev *>(d + o_sets), d_rec[i], 0, 0, 0, (unsigned)c.n_perms, (int)n, 0};
+                                    reinterpret_cast<const DispersionSetDev *>(d + o_sets), d_out, 0, 0, 0, (unsigned)c.n_perms, (int)n, 0};
         e = dispersion_launch_tasks(P, c, ta, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(W.h[i], d_rec[i], (size_t)c.n_tasks * sizeof(st_dispersion_record), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipEventRecord(W.ev[i], s);
+        if (e == hipSuccess) e = ring.post(d_out, (size_t)c.n_tasks, &c, s);
         if (e != hipSuccess) return hip_fail(" launch: ", e);
-        pending[i] = &c;
     }
-    for (size_t k = P.chunks.size(); k < P.chunks.size() + 2; k++) {      // the older buffer first
-        e = drain((int)(k & 1));
-        if (e != hipSuccess) return hip_fail(" read-back: ", e);
-    }
-    e = hipStreamSynchronize(s);
+    e = ring.flush(scatter);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return hip_fail(" read-back: ", e);
     return ST_OK;
 }
@@ -134,7 +109,8 @@ static int partner_dispersion_run(st_tree *t, const int64_t *univ, const Dispers
                                   int32_t stream, st_dispersion_record *out, int64_t *bad_id)
 {
     ST_DEVICE(t->device);
-    DispersionWork W;      // (declared before the session: it dies after the session's stream has drained)
+    DevBuf<char> d_work;
+    DispersionRing ring;
     TwoTreeSession ses(t, t, "partner dispersion");
     const size_t n = (size_t)P.n_univ, o_univ = align256(n * n * 4), total = o_univ + align256(n * 8);
     hipError_t e = ses.s.create();
@@ -156,41 +132,29 @@ static int partner_dispersion_run(st_tree *t, const int64_t *univ, const Dispers
     rc = enqueue_src(t, SrcGrid{d_univ, d_univ, (long long)n, 0, 0}, (int64_t)(n * n), DistSink{nullptr, d_D}, MrcaSink{nullptr, nullptr},
                      t->d_fault_host, s);
     if (rc != ST_OK) return rc;
-    rc = dispersion_chunks(W, "partner dispersion", s, d_D, P, set_pos, n_pos, seed, stream, out);
+    rc = dispersion_chunks(d_work, ring, "partner dispersion", s, d_D, P, set_pos, n_pos, seed, stream, out);
     if (rc != ST_OK) return rc;
     return ses.close(bad_id);
 }
 
-// owns the stream and the matrix of st_dispersion_matrix: the matrix dies only once the stream has drained
-struct DispersionMatrixSession {
-    Stream s;
-    DevBuf<float> d;
-    ~DispersionMatrixSession()
-    {
-        if (s) (void)hipStreamSynchronize(s);
-        d.reset();
-        s.reset();
-    }
-};
-
 static int dispersion_matrix_device(int device, const float *D, const DispersionPlan &P, const int32_t *set_pos, int64_t n_pos, uint64_t seed,
                                     int32_t stream, st_dispersion_record *out)
 {
-    int n_dev = 0;
-    ST_HIP(hipGetDeviceCount(&n_dev));
-    if (device >= n_dev) return fail(ST_ERR_ARG, "device " + std::to_string(device) + " of " + std::to_string(n_dev));
+    if (const int rc = device_index_arg(device); rc != ST_OK) return rc;
     ST_DEVICE(device);
-    DispersionWork W;
-    DispersionMatrixSession ses;
+    DevBuf<char> d_work;
+    DispersionRing ring;
+    DevBuf<float> d_D;
+    DrainedStream s;
     const size_t n = (size_t)P.n_univ;
-    hipError_t e = ses.s.create();
+    hipError_t e = s.create();
     if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("dispersion matrix setup: ") + hipGetErrorString(e));
-    e = ses.d.alloc(n * n);
+    e = d_D.alloc(n * n);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return fail(ST_ERR_NOMEM, "dispersion matrix: a matrix of " + std::to_string(n * n * 4) + " bytes: " + hipGetErrorString(e));
     }
-    e = hipMemcpyAsync(ses.d, D, n * n * 4, hipMemcpyHostToDevice, ses.s);
+    e = hipMemcpyAsync(d_D, D, n * n * 4, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("dispersion matrix upload: ") + hipGetErrorString(e));
-    return dispersion_chunks(W, "dispersion matrix", ses.s, ses.d, P, set_pos, n_pos, seed, stream, out);
+    return dispersion_chunks(d_work, ring, "dispersion matrix", s, d_D, P, set_pos, n_pos, seed, stream, out);
 }

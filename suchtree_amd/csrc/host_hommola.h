@@ -1,29 +1,22 @@
 // host_hommola.h -- part of suchtree_hip.hip (included after host_compare.h).  The device side of
-// st_hommola_clades_host and st_hommola_permutation (kernels_hommola.h; the plan, the host form of the permutation and
-// the fold: hommola_plan.cpp).  One device block: the float32 matrices -- the other tree's n_o x n_o, then one square per
-// maximal clade range, each written once by the unchanged distance kernels over a SrcGrid -- the universes' ids, the
-// links' positions, the clade table, one chunk of relabelled positions and two chunks of pieces.  Per chunk of whole
-// blocks: the sorts of its rows (k_hommola_relabel*), its blocks (k_hommola_blocks), its pieces copied to one of two
-// pinned buffers, folded into their rows while the device works on the next chunk.
+// st_hommola_clades_host and st_hommola_permutation (kernels_hommola.h, kernels_perm.h; the plan and the fold:
+// hommola_plan.cpp).  One device block: the float32 matrices -- the other tree's n_o x n_o, then one square per maximal
+// clade range, each written once by the unchanged distance kernels over a SrcGrid -- the universes' ids, the links'
+// positions, the clade table, one chunk of relabelled positions and two chunks of pieces.  Per chunk of whole blocks:
+// the sorts of its rows (k_hommola_relabel*), its blocks (k_hommola_blocks), its pieces copied to one of two pinned
+// buffers (ReadbackRing, host_compare.h), folded into their rows while the device works on the next chunk.
 #pragma once
-
-static size_t hommola_lds_bytes(int n)
-{
-    size_t N = 128;
-    while (N < (size_t)n) N <<= 1;
-    return N * 8;
-}
 
 // the sorts of one side and size class over a chunk's rows; max_n: the largest universe the class meets in this call
 static hipError_t hommola_launch_relabel(const HommolaRelabelArgs &a, int max_n, hipStream_t s)
 {
-    if (a.cls == kHommolaSortWave) {
+    if (a.cls == kPermSortWave) {
         hipLaunchKernelGGL(k_hommola_relabel_wave, dim3((unsigned)((a.n_rows + 3) / 4)), dim3(256), 0, s, a);
-    } else if (a.cls == kHommolaSortSmall) {
-        hipLaunchKernelGGL(k_hommola_relabel<kHommolaSmallThreads>, dim3((unsigned)a.n_rows), dim3(kHommolaSmallThreads),
-                           hommola_lds_bytes(std::min(max_n, kHommolaSmallMax)), s, a);
+    } else if (a.cls == kPermSortSmall) {
+        hipLaunchKernelGGL(k_hommola_relabel<kPermSmallThreads>, dim3((unsigned)a.n_rows), dim3(kPermSmallThreads),
+                           perm_lds_bytes(std::min(max_n, kPermSmallMax)), s, a);
     } else {
-        hipLaunchKernelGGL(k_hommola_relabel<kHommolaLargeThreads>, dim3((unsigned)a.n_rows), dim3(kHommolaLargeThreads), hommola_lds_bytes(max_n),
+        hipLaunchKernelGGL(k_hommola_relabel<kPermLargeThreads>, dim3((unsigned)a.n_rows), dim3(kPermLargeThreads), perm_lds_bytes(max_n),
                            s, a);
     }
     return hipGetLastError();
@@ -33,8 +26,7 @@ static int hommola_clades_run(st_tree *to, st_tree *tc, const int64_t *univ_o, c
                               const int32_t *pos_c, int64_t n_links, const HommolaPlan &P, uint64_t seed, st_pair_moments *out, int64_t *bad_id)
 {
     ST_DEVICE(to->device);
-    PinnedBuf<CladePiece> h_pieces[2];      // (declared before the session: they die after its stream has drained)
-    Event ev[2];
+    ReadbackRing<CladePiece, BlockSpan> ring;
     TwoTreeSession ses(to, tc, "hommola clades");
     const size_t n_o = (size_t)P.n_univ_o, n_c = (size_t)P.n_univ_c, L = (size_t)n_links;
     const size_t o_uo = align256((size_t)P.mat_floats * 4), o_uc = o_uo + align256(n_o * 8), o_po = o_uc + align256(n_c * 8);
@@ -56,10 +48,7 @@ static int hommola_clades_run(st_tree *to, st_tree *tc, const int64_t *univ_o, c
     long long *d_uo = reinterpret_cast<long long *>(d + o_uo), *d_uc = reinterpret_cast<long long *>(d + o_uc);
     const HommolaCladeDev *d_clade = reinterpret_cast<const HommolaCladeDev *>(d + o_clade);
     CladePiece *d_pieces[2] = {reinterpret_cast<CladePiece *>(d + o_piece), reinterpret_cast<CladePiece *>(d + o_piece + piece_bytes)};
-    for (int i = 0; i < 2 && e == hipSuccess; i++) {
-        e = h_pieces[i].alloc((size_t)P.max_chunk_blocks, hipHostMallocDefault);
-        if (e == hipSuccess) e = ev[i].create(hipEventDisableTiming);
-    }
+    e = ring.alloc((size_t)P.max_chunk_blocks);
     if (e == hipSuccess) e = hipMemcpyAsync(d_uo, univ_o, n_o * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_uc, univ_c, n_c * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d + o_po, pos_o, L * 4, hipMemcpyHostToDevice, s);
@@ -80,29 +69,17 @@ static int hommola_clades_run(st_tree *to, st_tree *tc, const int64_t *univ_o, c
     int max_leaves = 1;
     for (int64_t c = 0; c < P.n_clades; c++)
         if (P.clades[(size_t)c].link_count >= 2) max_leaves = std::max(max_leaves, P.clades[(size_t)c].leaf_count);
-    const size_t lds_large = std::max(hommola_lds_bytes(max_leaves), hommola_lds_bytes((int)n_o));
-    if (lds_large > 32 * 1024) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_hommola_relabel<kHommolaLargeThreads>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds_large);
-        if (e != hipSuccess) return ses.hip_fail(" setup: ", e);
-    }
-    int64_t first[2] = {0, 0}, count[2] = {0, 0};
-    auto drain = [&](int i) {
-        if (count[i] == 0) return hipSuccess;
-        const hipError_t de = hipEventSynchronize(ev[i]);
-        if (de != hipSuccess) return de;
-        hommola_fold(P, first[i], count[i], h_pieces[i], out);
-        count[i] = 0;
-        return hipSuccess;
-    };
-    for (size_t k = 0; k < P.chunks.size(); k++) {
-        const HommolaChunk &ch = P.chunks[k];
-        const int i = (int)(k & 1);
-        e = drain(i);      // (the pieces of two chunks ago)
+    const size_t lds_large = std::max(perm_lds_bytes(max_leaves), perm_lds_bytes((int)n_o));
+    e = perm_lds_opt_in(k_hommola_relabel<kPermLargeThreads>, lds_large);
+    if (e != hipSuccess) return ses.hip_fail(" setup: ", e);
+    auto fold = [&](const CladePiece *pieces, const BlockSpan &b) { hommola_fold(P, b.first, b.count, pieces, out); };
+    for (const HommolaChunk &ch : P.chunks) {
+        e = ring.acquire(fold);      // (the pieces of two chunks ago)
         if (e != hipSuccess) return ses.hip_fail(" read-back: ", e);
+        CladePiece *const d_out = d_pieces[ring.next];
         HommolaRelabelArgs ra{d_clade, reinterpret_cast<const int *>(d + o_po), reinterpret_cast<unsigned short *>(d + o_rel), (long long)ch.row_begin,
                               (long long)ch.n_rows, (long long)P.rows_per_clade, (long long)ch.rel_begin, (unsigned long long)seed, 1, (int)n_o,
-                              hommola_sort_class((int)n_o)};
+                              perm_sort_class((int)n_o)};
         e = hommola_launch_relabel(ra, (int)n_o, s);
         ra.pos = reinterpret_cast<const int *>(d + o_pc);
         ra.side = 0;
@@ -115,57 +92,43 @@ static int hommola_clades_run(st_tree *to, st_tree *tc, const int64_t *univ_o, c
             const HommolaBlockArgs ba{d_clade, d_mat, reinterpret_cast<const unsigned *>(d + o_rel), (long long)ch.block_begin, (long long)ch.n_blocks,
                                       (long long)P.rows_per_clade, (long long)ch.rel_begin, (int)P.n_clades, (int)n_o};
             const int64_t waves = (ch.n_blocks + 63) / 64, per = kHommolaBlockThreads / 64;
-            hipLaunchKernelGGL(k_hommola_blocks, dim3((unsigned)((waves + per - 1) / per)), dim3(kHommolaBlockThreads), 0, s, ba, d_pieces[i]);
+            hipLaunchKernelGGL(k_hommola_blocks, dim3((unsigned)((waves + per - 1) / per)), dim3(kHommolaBlockThreads), 0, s, ba, d_out);
             e = hipGetLastError();
         }
-        if (e == hipSuccess) e = hipMemcpyAsync(h_pieces[i], d_pieces[i], (size_t)ch.n_blocks * sizeof(CladePiece), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipEventRecord(ev[i], s);
+        if (e == hipSuccess) e = ring.post(d_out, (size_t)ch.n_blocks, BlockSpan{ch.block_begin, ch.n_blocks}, s);
         if (e != hipSuccess) return ses.hip_fail(" launch: ", e);
-        first[i] = ch.block_begin;
-        count[i] = ch.n_blocks;
     }
-    for (size_t k = P.chunks.size(); k < P.chunks.size() + 2; k++) {      // the older buffer first
-        e = drain((int)(k & 1));
-        if (e != hipSuccess) return ses.hip_fail(" read-back: ", e);
-    }
-    e = hipStreamSynchronize(s);
+    e = ring.flush(fold);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return ses.hip_fail(" read-back: ", e);
     return ses.close(bad_id);
 }
 
 static int hommola_permutation_device(int device, uint64_t seed, int32_t node, int64_t p, int side, int32_t n, int32_t *out)
 {
-    int n_dev = 0;
-    ST_HIP(hipGetDeviceCount(&n_dev));
-    if (device >= n_dev) return fail(ST_ERR_ARG, "device " + std::to_string(device) + " of " + std::to_string(n_dev));
+    if (const int rc = device_index_arg(device); rc != ST_OK) return rc;
     ST_DEVICE(device);
-    Stream s;      // (dies after the buffer)
     DevBuf<int> d_out;
+    DrainedStream s;      // (also on an error: the buffer dies behind the kernel)
     hipError_t e = s.create();
     if (e == hipSuccess) e = d_out.alloc((size_t)n);
+    const size_t lds = perm_lds_bytes(n);
+    if (e == hipSuccess) e = perm_lds_opt_in(k_hommola_permutation<kPermLargeThreads>, lds);      // (above 32 KiB: the large class)
     if (e == hipSuccess) {
-        const size_t lds = hommola_lds_bytes(n);
-        const int cls = hommola_sort_class(n);
-        if (cls == kHommolaSortWave) {
+        const int cls = perm_sort_class(n);
+        if (cls == kPermSortWave) {
             hipLaunchKernelGGL(k_hommola_permutation_wave, dim3(1), dim3(64), 0, s, (unsigned long long)seed, (int)node, (long long)p, side, (int)n, d_out.get());
-        } else if (cls == kHommolaSortSmall) {
-            hipLaunchKernelGGL(k_hommola_permutation<kHommolaSmallThreads>, dim3(1), dim3(kHommolaSmallThreads), lds, s, (unsigned long long)seed, (int)node,
+        } else if (cls == kPermSortSmall) {
+            hipLaunchKernelGGL(k_hommola_permutation<kPermSmallThreads>, dim3(1), dim3(kPermSmallThreads), lds, s, (unsigned long long)seed, (int)node,
                                (long long)p, side, (int)n, d_out.get());
         } else {
-            if (lds > 32 * 1024)
-                e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_hommola_permutation<kHommolaLargeThreads>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)lds);
-            if (e == hipSuccess)
-                hipLaunchKernelGGL(k_hommola_permutation<kHommolaLargeThreads>, dim3(1), dim3(kHommolaLargeThreads), lds, s, (unsigned long long)seed,
-                                   (int)node, (long long)p, side, (int)n, d_out.get());
+            hipLaunchKernelGGL(k_hommola_permutation<kPermLargeThreads>, dim3(1), dim3(kPermLargeThreads), lds, s, (unsigned long long)seed,
+                               (int)node, (long long)p, side, (int)n, d_out.get());
         }
-        if (e == hipSuccess) e = hipGetLastError();
+        e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, s);
-    if (s) {      // (also on an error: the buffer dies behind the kernel)
-        const hipError_t es = hipStreamSynchronize(s);
-        if (e == hipSuccess) e = es;
-    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("hommola permutation: ") + hipGetErrorString(e));
     return ST_OK;
 }

@@ -113,13 +113,11 @@ static int quartet_given_run(st_tree *tx, st_tree *ty, const int64_t *quartets_x
 // st_quartet_positions on a device: the generator kernel alone, chunk by chunk into one device buffer
 static int quartet_positions_device(int device, int mode, uint64_t seed, int64_t m, int64_t k_begin, int64_t k_count, int32_t *out_pos)
 {
-    int n_dev = 0;
-    ST_HIP(hipGetDeviceCount(&n_dev));
-    if (device >= n_dev) return fail(ST_ERR_ARG, "device " + std::to_string(device) + " of " + std::to_string(n_dev));
+    if (const int rc = device_index_arg(device); rc != ST_OK) return rc;
     ST_DEVICE(device);
     const int64_t chunk = std::min(k_count, kQuartetChunk);
-    Stream s;      // (dies after the buffer)
     DevBuf<int> d_pos;
+    DrainedStream s;      // (an error may leave the draw kernel running: the buffer dies behind it)
     hipError_t e = s.create();
     if (e == hipSuccess) e = d_pos.alloc((size_t)chunk * 4);
     for (int64_t off = 0; off < k_count && e == hipSuccess; off += chunk) {
@@ -128,7 +126,6 @@ static int quartet_positions_device(int device, int mode, uint64_t seed, int64_t
         if (e == hipSuccess) e = hipMemcpyAsync(out_pos + 4 * off, d_pos, (size_t)c * 16, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);      // (the buffer is reused by the next chunk)
     }
-    if (s) (void)hipStreamSynchronize(s);      // (an error may have left the draw kernel running: the buffer dies behind it)
     if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("quartet positions: ") + hipGetErrorString(e));
     return ST_OK;
 }

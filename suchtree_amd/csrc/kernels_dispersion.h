@@ -1,10 +1,10 @@
-// kernels_dispersion.h -- included by suchtree_hip.hip (after kernels_hommola.h, whose sorts it reuses).
+// kernels_dispersion.h -- included by suchtree_hip.hip (after kernels_perm.h, whose sorts it uses).
 // The device side of st_partner_dispersion_host and st_dispersion_matrix (layout and order rule: dispersion_plan.h; the
 // contract: include/suchtree_hip.h).  Task (set, p) relabels the set's positions through sigma_p and reduces the k x k
 // sub-matrix D[q_i][q_j] of the float32 matrix D: every row's sum over j != i and its minimum, then both over i.
 //
-//   k_dispersion_sigma   one sort per permutation p of the chunk's block (not per task): the keys of hommola_stream(seed,
-//                        stream, p, 0) over the universe, sorted by hommola_sort_wave / hommola_sort_lds, the low 16 bits
+//   k_dispersion_sigma   one sort per permutation p of the chunk's block (not per task): the keys of perm_stream(seed,
+//                        stream, p, 0) over the universe, sorted by perm_sort_wave / perm_sort_lds, the low 16 bits
 //                        as one uint16 row of sigma.  p = 0 writes the identity.
 //   k_dispersion_tasks   three forms, one per size class; element i of a task is a lane's, the lane walks j:
 //       packed     K' <= 32: 64 / K' tasks per wave, q_j from lane j of the task's K'-lane group, the butterfly inside it;
@@ -35,7 +35,7 @@ struct DispersionSigmaArgs {
 template <int T>
 __global__ __launch_bounds__(T) void k_dispersion_sigma(DispersionSigmaArgs a)
 {
-    extern __shared__ unsigned long long hommola_keys[];
+    extern __shared__ unsigned long long perm_keys[];
     const unsigned tid = threadIdx.x;
     const long long p = a.p0 + blockIdx.x;
     unsigned short *row = a.sigma + (size_t)blockIdx.x * (size_t)a.n;
@@ -43,15 +43,15 @@ __global__ __launch_bounds__(T) void k_dispersion_sigma(DispersionSigmaArgs a)
         for (unsigned i = tid; i < (unsigned)a.n; i += T) row[i] = (unsigned short)i;
         return;
     }
-    const unsigned long long h1 = hommola_stream(a.seed, a.stream, p, 0);
-    if (a.n <= kHommolaWaveMax) {      // (workgroup-uniform: no barrier on this path)
+    const unsigned long long h1 = perm_stream(a.seed, a.stream, p, 0);
+    if (a.n <= kPermWaveMax) {      // (workgroup-uniform: no barrier on this path)
         if (tid >= 64) return;
-        const unsigned long long key = hommola_sort_wave(h1, a.n, (int)tid);
+        const unsigned long long key = perm_sort_wave(h1, a.n, (int)tid);
         if ((int)tid < a.n) row[tid] = (unsigned short)(key & 0xFFFF);
         return;
     }
-    hommola_sort_lds<T>(hommola_keys, h1, (unsigned)a.n, tid);
-    for (unsigned i = tid; i < (unsigned)a.n; i += T) row[i] = (unsigned short)(hommola_keys[i] & 0xFFFF);
+    perm_sort_lds<T>(perm_keys, h1, (unsigned)a.n, tid);
+    for (unsigned i = tid; i < (unsigned)a.n; i += T) row[i] = (unsigned short)(perm_keys[i] & 0xFFFF);
 }
 
 struct DispersionTaskArgs {

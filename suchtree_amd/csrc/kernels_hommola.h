@@ -1,20 +1,13 @@
-// kernels_hommola.h -- included by suchtree_hip.hip (after kernels_rows.h and kernels_quartets.h).
+// kernels_hommola.h -- included by suchtree_hip.hip (after kernels_rows.h, kernels_quartets.h and kernels_perm.h).
 // The device side of st_hommola_clades_host (layout: hommola_plan.h).  Row (clade, p) is the clade's links relabelled by
 // permutation p of each tree's universe; its pair (link j, link i) has x = D_o[q_o(j)][q_o(i)] and y = D_c[q_c(j)][q_c(i)],
 // D the float32 distance matrices that the unchanged distance kernels wrote once (SrcGrid), q the relabelled positions.
 //
-//   k_hommola_relabel*  one sort per (row, side): the keys w_i (hommola_key) of the side's universe -- the clade's own
-//                       leaf range, or the other tree's leaves -- sorted, sigma[j] = low 16 bits of the j-th smallest,
-//                       then every link's position through sigma into the chunk's buffer of 16-bit position pairs.
-//                       Universes of up to 64 positions: one wave, keys in registers, a bitonic network of lane
-//                       exchanges; larger ones: one workgroup, keys in LDS.  p = 0 writes the identity.
+//   k_hommola_relabel*  one sort per (row, side) of the side's universe -- the clade's own leaf range, or the other
+//                       tree's leaves -- by the form its size class takes (kernels_perm.h), then every link's position
+//                       through sigma into the chunk's buffer of 16-bit position pairs.  p = 0 writes the identity.
 //   k_hommola_blocks    one CladePiece per block of ST_CLADE_TILE pairs of a row: two 4-byte gathers for the positions
 //                       of links j and i, two for x and y, five multiply-adds (CladeAcc).
-//
-// The LDS sort: stages whose partner distance j is 64 or more exchange through LDS -- consecutive lanes read
-// consecutive 8-byte keys, so a 32-lane group covers one 256-byte bank row without a conflict; stages with j <= 32 would
-// read 8-byte keys 16 .. 512 bytes apart (2- to 32-way conflicts), so each lane takes one key into a register instead and
-// the wave runs those stages as lane exchanges, as the one-wave form does.
 //
 // Determinism: a block is summed about its own first pair by the order rule of k_row_blocks (kernels_rows.h) -- up to
 // kCladeLanePiece pairs by one lane in index order, longer ones by one wave, lane-strided, then the xor butterfly -- so
@@ -25,8 +18,6 @@
 
 namespace st {
 
-constexpr int kHommolaSmallThreads = 256;
-constexpr int kHommolaLargeThreads = 1024;
 constexpr int kHommolaBlockThreads = 256;      // four waves, 64 consecutive blocks each
 
 struct HommolaRelabelArgs {
@@ -38,7 +29,7 @@ struct HommolaRelabelArgs {
     unsigned long long seed;
     int side;                        // 0: the clade tree, over the clade's own leaf range; 1: the other tree
     int n_other;                     // the other tree's universe
-    int cls;                         // the size class this launch sorts (HommolaSortClass); the others return at once
+    int cls;                         // the size class this launch sorts (PermSortClass); the others return at once
 };
 
 struct HommolaTask {
@@ -60,54 +51,9 @@ __device__ __forceinline__ HommolaTask hommola_task(const HommolaRelabelArgs &a,
     t.link_begin = d.link_begin;
     t.links = d.link_count;
     t.slot = d.rel_begin + t.p * d.link_count - a.rel0;
-    t.h1 = hommola_stream(a.seed, d.node, t.p, a.side);
-    t.live = d.link_count >= 2 && hommola_sort_class(t.n) == a.cls;
+    t.h1 = perm_stream(a.seed, d.node, t.p, a.side);
+    t.live = d.link_count >= 2 && perm_sort_class(t.n) == a.cls;
     return t;
-}
-
-// stages j0, j0 / 2, ... 1 (j0 <= 32) of merge level k of a bitonic sort, on the key of element i held by lane i % 64
-__device__ __forceinline__ unsigned long long hommola_lane_stages(unsigned long long v, unsigned i, unsigned k, unsigned j0)
-{
-    for (unsigned j = j0; j > 0; j >>= 1) {
-        const unsigned long long o = __shfl_xor(v, (int)j);
-        const bool up = (i & k) == 0, lower = (i & j) == 0;
-        v = (lower == up) ? (v < o ? v : o) : (v < o ? o : v);
-    }
-    return v;
-}
-
-// the keys of h1 over n positions sorted in LDS (keys: room for n rounded up to a power of two, at least 128); every
-// lane of the workgroup of T calls it, and a barrier closes it
-template <int T>
-__device__ __forceinline__ void hommola_sort_lds(unsigned long long *keys, unsigned long long h1, unsigned n, unsigned tid)
-{
-    unsigned N = 128;      // a power of two, whole waves
-    while (N < n) N <<= 1;
-    for (unsigned i = tid; i < N; i += T) keys[i] = i < n ? hommola_key(h1, i) : ~0ull;
-    __syncthreads();
-    for (unsigned k = 2; k <= N; k <<= 1) {
-        for (unsigned j = k >> 1; j >= 64; j >>= 1) {
-            for (unsigned q = tid; q < N / 2; q += T) {
-                const unsigned lo = 2 * q - (q & (j - 1)), hi = lo + j;
-                const unsigned long long u = keys[lo], v = keys[hi];
-                if ((u > v) == ((lo & k) == 0)) {
-                    keys[lo] = v;
-                    keys[hi] = u;
-                }
-            }
-            __syncthreads();
-        }
-        for (unsigned i = tid; i < N; i += T) keys[i] = hommola_lane_stages(keys[i], i, k, k >> 1 < 32 ? k >> 1 : 32);
-        __syncthreads();
-    }
-}
-
-// the same for up to 64 positions: lane i's key in, the i-th smallest out
-__device__ __forceinline__ unsigned long long hommola_sort_wave(unsigned long long h1, int n, int lane)
-{
-    unsigned long long key = lane < n ? hommola_key(h1, (unsigned)lane) : ~0ull;
-    for (unsigned k = 2; k <= 64; k <<= 1) key = hommola_lane_stages(key, (unsigned)lane, k, k >> 1);
-    return key;
 }
 
 __global__ __launch_bounds__(256) void k_hommola_relabel_wave(HommolaRelabelArgs a)
@@ -115,7 +61,7 @@ __global__ __launch_bounds__(256) void k_hommola_relabel_wave(HommolaRelabelArgs
     const int lane = threadIdx.x & 63;
     const HommolaTask t = hommola_task(a, (long long)blockIdx.x * 4 + (threadIdx.x >> 6));      // (wave-uniform)
     if (!t.live) return;
-    const unsigned long long key = t.p != 0 ? hommola_sort_wave(t.h1, t.n, lane) : 0;
+    const unsigned long long key = t.p != 0 ? perm_sort_wave(t.h1, t.n, lane) : 0;
     for (int l0 = 0; l0 < t.links; l0 += 64) {      // (every lane takes part in the exchange)
         const int l = l0 + lane;
         const int at = l < t.links ? a.pos[t.link_begin + l] - t.base : 0;
@@ -127,33 +73,16 @@ __global__ __launch_bounds__(256) void k_hommola_relabel_wave(HommolaRelabelArgs
 template <int T>
 __global__ __launch_bounds__(T) void k_hommola_relabel(HommolaRelabelArgs a)
 {
-    extern __shared__ unsigned long long hommola_keys[];
+    extern __shared__ unsigned long long perm_keys[];
     const HommolaTask t = hommola_task(a, (long long)blockIdx.x);      // (workgroup-uniform)
     if (!t.live) return;
     const unsigned tid = threadIdx.x;
-    if (t.p != 0) hommola_sort_lds<T>(hommola_keys, t.h1, (unsigned)t.n, tid);
+    if (t.p != 0) perm_sort_lds<T>(perm_keys, t.h1, (unsigned)t.n, tid);
     for (int l = (int)tid; l < t.links; l += T) {
         const int at = a.pos[t.link_begin + l] - t.base;
-        const int to = t.p == 0 ? at : (int)(hommola_keys[at] & 0xFFFF);
+        const int to = t.p == 0 ? at : (int)(perm_keys[at] & 0xFFFF);
         a.rel[2 * (t.slot + l) + a.side] = (unsigned short)(t.base + to);
     }
-}
-
-// st_hommola_permutation on the device: one sort of n positions by the form its size class takes, sigma as int32
-template <int T>
-__global__ __launch_bounds__(T) void k_hommola_permutation(unsigned long long seed, int node, long long p, int side, int n, int *out)
-{
-    extern __shared__ unsigned long long hommola_keys[];
-    const unsigned tid = threadIdx.x;
-    if (p != 0) hommola_sort_lds<T>(hommola_keys, hommola_stream(seed, node, p, side), (unsigned)n, tid);
-    for (unsigned i = tid; i < (unsigned)n; i += T) out[i] = p == 0 ? (int)i : (int)(hommola_keys[i] & 0xFFFF);
-}
-
-__global__ __launch_bounds__(64) void k_hommola_permutation_wave(unsigned long long seed, int node, long long p, int side, int n, int *out)
-{
-    const int lane = threadIdx.x;
-    const unsigned long long key = p != 0 ? hommola_sort_wave(hommola_stream(seed, node, p, side), n, lane) : (unsigned long long)lane;
-    if (lane < n) out[lane] = (int)(key & 0xFFFF);
 }
 
 // pair k of a triangle as (col, row), col < row: k = row (row - 1) / 2 + col (the enumeration of SrcTriangle)

@@ -30,8 +30,8 @@
 // enqueueing, faults), host_path.h (host-buffer pipeline, mailbox, copy kernels), host_upload.h (tables -> device),
 // kernels_misc.h (k nearest, graph matrices), and the compare paths (st_compare_*: two trees' distances over the same
 // pairs, reduced on the device): kernels_compare.h / kernels_clades.h / kernels_rows.h (moments and 2-D histogram, clade
-// pieces, row blocks), host_compare.h (TwoTreeSession, the chunk driver compare_run and its reducers, the pair inputs,
-// statistics and the one skeleton, compare_entry, of the triangle / pairs entry points) and,
+// pieces, row blocks), host_compare.h (TwoTreeSession, ReadbackRing, the chunk driver compare_run and its reducers, the pair
+// inputs, statistics and the one skeleton, compare_entry, of the triangle / pairs entry points) and,
 // host-only C++ beside tree_prep.cpp, compare_plan.cpp (argument checks, clade plan and tables, rows layout, the fold).
 // Exact Spearman rank sums of the same pairs (st_compare_*_ranks_host): kernels_ranks.h, the reducers at the end of
 // host_compare.h and, host-only, rank_plan.cpp (keys, bucket layout, tie arithmetic, st_spearman_host).
@@ -41,9 +41,10 @@
 // Two trees' quartet topologies, counted on the device (st_compare_quartets_*_host, st_quartet_positions):
 // kernels_quartets.h (generator, classify-and-count), host_quartets.h (the chunk driver) and, host-only,
 // quartet_plan.cpp (unranking, the draw, the class rule, argument checks).
-// Hommola's permutation test for many clades at once (st_hommola_clades_host, st_hommola_permutation): kernels_hommola.h
-// (the sorts that relabel the links, the blocks over two distance matrices), host_hommola.h (the chunk driver) and,
-// host-only, hommola_plan.cpp (argument checks, maximal ranges, block and chunk tables, the fold, the host permutation).
+// The keyed permutation behind every null (st_hommola_permutation): keyed_perm.h (key, size classes, the host form; host
+// and device) and kernels_perm.h (the device sort).  Hommola's permutation test for many clades at once
+// (st_hommola_clades_host): kernels_hommola.h (the sorts that relabel the links, the blocks over two distance matrices),
+// host_hommola.h (the chunk driver) and, host-only, hommola_plan.cpp (argument checks, ranges, block and chunk tables, the fold).
 // MPD / MNTD sums of many leaf sets under the taxa-labels null (st_partner_dispersion_host, st_dispersion_matrix):
 // kernels_dispersion.h (one sort per permutation, the k x k reducer in three size classes), host_dispersion.h (the chunk
 // driver) and, host-only, dispersion_plan.cpp (argument checks, size classes, chunks, the restatement of the reduction).
@@ -145,6 +146,14 @@ private:
     if (device_scope_.error() != hipSuccess)                                               \
         return fail(ST_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(device_scope_.error()))
 
+static int device_index_arg(int device)
+{
+    int n_dev = 0;
+    ST_HIP(hipGetDeviceCount(&n_dev));
+    if (device >= n_dev) return fail(ST_ERR_ARG, "device " + std::to_string(device) + " of " + std::to_string(n_dev));
+    return ST_OK;
+}
+
 }  // namespace st
 
 #include "device_common.h"
@@ -155,6 +164,7 @@ private:
 #include "kernels_clades.h"
 #include "kernels_rows.h"
 #include "kernels_quartets.h"
+#include "kernels_perm.h"
 #include "kernels_hommola.h"
 #include "kernels_dispersion.h"
 
@@ -878,11 +888,10 @@ try {
     std::lock_guard<std::mutex> lock(t->dp->m);
     // rows per launch: the distance block (float32, device only) stays under 256 MiB
     const int64_t rows_per_block = std::max<int64_t>(1, std::min<int64_t>(n_queries, ((int64_t)1 << 26) / n_cands));
-    // (the buffers die before the stream; a way out that may leave kernels on it drains it first)
-    Stream stream;
     DevBuf<long long> d_q, d_c, d_oi;
     DevBuf<float> d_tmp;
     DevBuf<double> d_od;
+    DrainedStream stream;      // (every way out drains it before the buffers go)
     hipError_t e = stream.create();
     if (e == hipSuccess) e = d_q.alloc((size_t)n_queries);
     if (e == hipSuccess) e = d_c.alloc((size_t)n_cands);
@@ -897,15 +906,15 @@ try {
         const int64_t rows = std::min(rows_per_block, n_queries - r0);
         const SrcGrid src{d_q + r0, d_c, (long long)n_cands, 0, 0};
         const int rc = enqueue_src(t, src, rows * n_cands, DistSink{nullptr, d_tmp}, MrcaSink{nullptr, nullptr}, t->d_fault_host, stream);
-        if (rc != ST_OK) { (void)hipStreamSynchronize(stream); return rc; }
+        if (rc != ST_OK) return rc;
         hipLaunchKernelGGL(k_knn_select, dim3((unsigned)rows), dim3(256), 0, stream, d_tmp, (long long)n_cands,
                            d_q + r0, d_c, skip_self, k, d_oi + r0 * k, d_od + r0 * k);
         e = hipGetLastError();
-        if (e != hipSuccess) { (void)hipStreamSynchronize(stream); return fail(ST_ERR_HIP, std::string("knn launch: ") + hipGetErrorString(e)); }
+        if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("knn launch: ") + hipGetErrorString(e));
     }
     e = hipMemcpyAsync(out_index, d_oi, (size_t)n_queries * k * 8, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out_dist, d_od, (size_t)n_queries * k * 8, hipMemcpyDeviceToHost, stream);
-    if (e != hipSuccess) { (void)hipStreamSynchronize(stream); return fail(ST_ERR_HIP, std::string("knn D2H: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("knn D2H: ") + hipGetErrorString(e));
     Fault f = kFaultInit;
     const int rc = end_host_faults(t, stream, f);
     if (rc != ST_OK) return rc;
@@ -1251,12 +1260,12 @@ try {
 int st_hommola_permutation(int device, uint64_t seed, int32_t node, int64_t p, int side, int32_t n, int32_t *out)
 try {
     std::string err;
-    const int rc = hommola_permutation_args(node, p, side, n, err);
+    const int rc = perm_args(node, p, side, n, err);
     if (rc != ST_OK) return fail(rc, err);
     if (device < -1) return fail(ST_ERR_ARG, "device must be -1 (host) or a device index");
     if (!out) return fail(ST_ERR_ARG, "out is NULL");
     if (device < 0) {
-        hommola_permutation_host(seed, node, p, side, n, out);
+        perm_host(seed, node, p, side, n, out);
         return ST_OK;
     }
     return hommola_permutation_device(device, seed, node, p, side, n, out);

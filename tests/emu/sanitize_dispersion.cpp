@@ -105,7 +105,7 @@ static int check_case(const Case &C, int64_t perms)
     // the restatement against a plain loop: long double sums, the minimum by std::min
     std::vector<int32_t> sigma((size_t)C.n);
     for (int64_t p = 0; p < R; p++) {
-        hommola_permutation_host(99, 5, p, 0, C.n, sigma.data());
+        perm_host(99, 5, p, 0, C.n, sigma.data());
         for (int64_t r = 0; r < n_sets; r++) {
             const int64_t b = C.off[(size_t)r], k = C.off[(size_t)r + 1] - b;
             long double pair = 0, nearest = 0;
@@ -176,9 +176,9 @@ int main()
         Case c = good;
         c.n = 2;
         CHECK(plan_of(c, 5, 0, P, err) == ST_ERR_ARG);                          // a universe below 3 ...
-        c.n = kHommolaMaxUniverse + 1;
+        c.n = kPermMaxUniverse + 1;
         CHECK(plan_of(c, 5, 0, P, err) == ST_ERR_ARG);                          // ... and above the limit
-        c.n = kHommolaMaxUniverse;
+        c.n = kPermMaxUniverse;
         CHECK(plan_of(c, 5, 0, P, err) == ST_OK);
         c = good;
         c.pos[1] = 40;

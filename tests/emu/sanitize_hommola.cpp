@@ -1,4 +1,4 @@
-// The host side of the per-clade Hommola test (suchtree_amd/csrc/hommola_plan.cpp) under AddressSanitizer + UBSan
+// The host side of the per-clade Hommola test (suchtree_amd/csrc/hommola_plan.cpp, keyed_perm.h) under AddressSanitizer + UBSan
 // (tests/test_hommola_clades_host.py builds this with -fsanitize=address,undefined): the plan on caterpillar and random
 // trees -- laminar check, maximal ranges under several caps, blocks that tile every row once, chunk cuts -- the fold
 // against clade_merge in block order, every argument error, and the host form of the permutation.
@@ -215,6 +215,30 @@ int main()
         const Tree rt = random_tree(40);
         if (check_case(rt, make_case(rt, 700, 10, 40), 40, 1)) return 1;
     }
+    {      // the cuts that tests/test_gpu_hommola_clades.py (the drain order of the last two chunks) relies on: one clade of
+           // `links` links, one per leaf -> the sizes of its chunks
+        auto cuts = [](int links, int64_t perms, int64_t chunk_blocks, std::vector<int64_t> &sizes) {
+            Case C;
+            C.n_o = 35;
+            C.n_c = links;
+            for (int l = 0; l < links; l++) {
+                C.pos_c.push_back(l);
+                C.pos_o.push_back(l % 35);
+            }
+            C.clades = {st_hommola_clade{0, 0, links, 0, links, 0}};
+            std::string err;
+            HommolaPlan P;
+            if (plan_of(C, perms, chunk_blocks, P, err) != ST_OK) return false;
+            sizes.clear();
+            for (const HommolaChunk &k : P.chunks) sizes.push_back(k.n_blocks);
+            return P.clades[0].nb == (links == 182 ? 3 : 2);
+        };
+        std::vector<int64_t> n;
+        CHECK(cuts(182, 0, 1, n) && n == std::vector<int64_t>({1, 1, 1}));               // 16471 pairs: three blocks, an odd count
+        CHECK(cuts(182, 1, 1, n) && n == std::vector<int64_t>({1, 1, 1, 1, 1, 1}));      // an even count
+        CHECK(cuts(182, 0, 2, n) && n == std::vector<int64_t>({2, 1}));                  // the last row split 2 + 1
+        CHECK(cuts(130, 1, 3, n) && n == std::vector<int64_t>({3, 1}));                  // two blocks per row: row 1 crosses the cut
+    }
     // arguments
     {
         const Tree rt = random_tree(50);
@@ -258,13 +282,13 @@ int main()
             CHECK(plan_of(o, 5, 0, P, err) == ST_OK && P.ranges.size() == 1);
         }
         c = good;
-        c.n_o = kHommolaMaxUniverse + 1;
+        c.n_o = kPermMaxUniverse + 1;
         CHECK(plan_of(c, 5, 0, P, err) == ST_ERR_ARG);                                   // a universe above the limit
         c = good;
-        c.n_c = kHommolaMaxUniverse + 1;
+        c.n_c = kPermMaxUniverse + 1;
         CHECK(plan_of(c, 5, 0, P, err) == ST_ERR_ARG);
         c = good;
-        c.n_o = kHommolaMaxUniverse;
+        c.n_o = kPermMaxUniverse;
         CHECK(plan_of(c, 5, 0, P, err) == ST_OK);
         // nothing to do: no clades, no links
         CHECK(hommola_plan(3, 3, nullptr, nullptr, 0, nullptr, 0, 5, 0, P, err) == ST_OK && P.n_blocks == 0 && P.chunks.empty() && P.n_rows == 0);
@@ -275,22 +299,22 @@ int main()
     for (int32_t n : {1, 2, 3, 63, 64, 65, 2047, 2048, 2049, 16383, 16384}) {
         for (uint64_t seed : {0ull, 2024ull, ~0ull}) {
             std::vector<int32_t> s((size_t)n), seen((size_t)n, 0);
-            hommola_permutation_host(seed, 7, 3, 1, n, s.data());
-            const uint64_t h1 = hommola_stream(seed, 7, 3, 1);
+            perm_host(seed, 7, 3, 1, n, s.data());
+            const uint64_t h1 = perm_stream(seed, 7, 3, 1);
             for (int32_t j = 0; j < n; j++) {
                 CHECK(s[(size_t)j] >= 0 && s[(size_t)j] < n && seen[(size_t)s[(size_t)j]]++ == 0);
-                CHECK(j == 0 || hommola_key(h1, (uint32_t)s[(size_t)j - 1]) < hommola_key(h1, (uint32_t)s[(size_t)j]));
+                CHECK(j == 0 || perm_key(h1, (uint32_t)s[(size_t)j - 1]) < perm_key(h1, (uint32_t)s[(size_t)j]));
             }
-            hommola_permutation_host(seed, 7, 0, 1, n, s.data());
+            perm_host(seed, 7, 0, 1, n, s.data());
             for (int32_t j = 0; j < n; j++) CHECK(s[(size_t)j] == j);
         }
     }
     {
         std::string err;
-        CHECK(hommola_permutation_args(0, 1, 0, 1, err) == ST_OK && hommola_permutation_args(0, 1, 1, kHommolaMaxUniverse, err) == ST_OK);
-        CHECK(hommola_permutation_args(0, 1, 0, 0, err) == ST_ERR_ARG && hommola_permutation_args(0, 1, 0, kHommolaMaxUniverse + 1, err) == ST_ERR_ARG);
-        CHECK(hommola_permutation_args(0, -1, 0, 4, err) == ST_ERR_ARG && hommola_permutation_args(0, 1, 2, 4, err) == ST_ERR_ARG);
-        CHECK(hommola_permutation_args(-1, 1, 0, 4, err) == ST_ERR_ARG);
+        CHECK(perm_args(0, 1, 0, 1, err) == ST_OK && perm_args(0, 1, 1, kPermMaxUniverse, err) == ST_OK);
+        CHECK(perm_args(0, 1, 0, 0, err) == ST_ERR_ARG && perm_args(0, 1, 0, kPermMaxUniverse + 1, err) == ST_ERR_ARG);
+        CHECK(perm_args(0, -1, 0, 4, err) == ST_ERR_ARG && perm_args(0, 1, 2, 4, err) == ST_ERR_ARG);
+        CHECK(perm_args(-1, 1, 0, 4, err) == ST_ERR_ARG);
     }
     std::printf("sanitize hommola ok\n");
     return 0;

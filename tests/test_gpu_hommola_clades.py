@@ -118,6 +118,20 @@ def test_edges_of_the_order_rule(caterpillar):
     assert list(df.columns[:5]) == ["name", "n_links", "n_leafs", "r", "p"] and len(df) == len(res)
 
 
+@pytest.mark.parametrize("links, chunk_blocks, permutations", [(182, 1, 0), (182, 1, 1), (182, 2, 0), (130, 3, 1)])
+def test_drain_order_of_the_last_chunks(caterpillar, links, chunk_blocks, permutations):
+    """A row's pieces are merged in block order also when its blocks straddle the last chunks, whose two read-back slots
+    are drained after the loop, the older one first -- at both parities of the chunk count.  182 links are 16471 pairs,
+    three blocks per row: chunks of 1 + 1 + 1 blocks (odd), of 1 x 6 with one permutation (even), of 2 + 1; 130 links
+    are two blocks per row: with one permutation chunks of 3 + 1, row 1 across the cut (tests/emu/sanitize_hommola.cpp
+    checks these cuts on the host).  The yardstick reads every row's pieces back in one chunk: no drain order in it."""
+    S, layout = caterpillar
+    node = next(v for v in _inner_nodes(S.TreeB, layout) if layout.links(v)[1] == links)
+    got = _low_level(S, layout, [node], permutations, 2024, chunk_blocks)
+    assert got.shape == (1, permutations + 1) and np.all(got["n"] == links * (links - 1) // 2)
+    _check_rows(S, layout, [node], got, permutations, 2024)
+
+
 @pytest.fixture(scope="module")
 def nested():
     """TreeB = a random tree of 300 leaves, 400 random links: several links share a leaf, some leaves have none."""
