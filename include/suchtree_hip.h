@@ -47,7 +47,8 @@ extern "C" {
  *      additive, struct st_kendall_counts, ST_KENDALL_TILE, st_compare_triangle_kendall_host, st_compare_pairs_kendall_host,
  *      st_kendall_arrays_host and st_kendall_host; then, also additive, struct st_hommola_clade, ST_HOMMOLA_MAX_UNIVERSE,
  *      st_hommola_permutation and st_hommola_clades_host; then, also additive, struct st_dispersion_record,
- *      st_partner_dispersion_host and st_dispersion_matrix.
+ *      st_partner_dispersion_host and st_dispersion_matrix; then, also additive, ST_UNIFRAC_MAX_UNIVERSE,
+ *      ST_UNIFRAC_LANE_MAX, st_unifrac_host, st_unifrac_depths and st_unifrac_quantise.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -537,6 +538,78 @@ int st_partner_dispersion_host(st_tree *tree, const int64_t *univ, int32_t n_uni
 int st_dispersion_matrix(int device, const float *D, int32_t n, const int32_t *set_pos, int64_t n_pos, const int64_t *sets,
                          int64_t n_sets, int64_t permutations, uint64_t seed, int32_t stream, int64_t chunk_tasks,
                          st_dispersion_record *out);
+
+/*
+ * How different are two sets of leaves, measured on the tree: Faith's PD of many sets over one universe and, for pairs of
+ * them, the branch length of their union, from which unweighted UniFrac and PhyloSor follow.
+ * SuchLinkedTrees.partner_unifrac asks it of every two leaves' partners in the other tree; SuchTree.unifrac of any sets.
+ *
+ * Universe.  univ (n ids, 1 <= n <= ST_UNIFRAC_MAX_UNIVERSE = 2^20) are leaves of the tree under the node `root`, in
+ * depth-first order, children in increasing id order (the order of st_hommola_clades_host).  No n x n matrix is built:
+ * the 16384-leaf limit of the Hommola and dispersion calls does not apply.
+ *
+ * Depths.  d[k] = float32 dist(root, univ[k]); h[k] = float32 dist(root, mrca(univ[k], univ[k + 1])) for k < n - 1.  Both
+ * are written by the distance and MRCA kernels of the other calls, the arguments in that order: d[k] has the bits of
+ * st_distances_host for the pair (root, univ[k]).  A depth that is not finite is ST_ERR_ARG.
+ *
+ * Fixed point.  q(v) = llrint(ldexp((double) v, shift)).  shift = -1 is automatic: 39 - ilogb(max |v|) over all of d and
+ * h, and 0 when that maximum is 0, so the largest value lands in [2^39, 2^40) (for depths of 2^40 and more the shift used
+ * is negative).  A caller's shift, 0 .. 256, that would put a |q| at 2^40 or more is ST_ERR_ARG.  A caller cannot pass
+ * a negative shift (-1 is taken, any other negative value is ST_ERR_ARG): on a tree with a depth of 2^40 or more only
+ * the automatic shift works, and range calls share one scale there only because the automatic shift of one universe
+ * and root is the same in every call.  Every sum below is an
+ * exact int64, |sum| < 2^61 for n <= 2^20: the results do not depend on reduction order, on which kernel form took a
+ * pair, on chunk_pairs, the grid or the device.  Quantising costs at most 2^-40 of the largest depth per term, far below
+ * the float32 rounding already in d.  st_unifrac_quantise is this rule on the host (out_dq[n], out_hq[n - 1], the shift
+ * used; each may be NULL).
+ *
+ * Sets.  As for st_partner_dispersion_host: set r is the positions set_pos[sets[r] .. sets[r + 1]) of the universe,
+ * strictly increasing; sets holds n_sets + 1 offsets (n_sets <= 2^30).
+ *
+ * Union sum of two sets A and B.  Over the distinct merged positions s_1 < ... < s_t:
+ *     U(A, B) = sum over k of q(d[s_k])  -  sum over k < t of min q(h[s_k .. s_{k+1} - 1]),
+ * the branch length (in units of 2^-shift) of the subtree that joins root to every member; 0 for an empty union.
+ * PD(A) = U(A, A).  The caller derives the rest: shared = PD_A + PD_B - U, UniFrac = (2 U - PD_A - PD_B) / U, PhyloSor
+ * = 2 shared / (PD_A + PD_B), NaN where the denominator is 0.
+ *
+ * Pairs.  Pair k of the sets is (j, i) with k = i (i - 1) / 2 + j, 0 <= j < i < n_sets, the order of st_triangle_host; a
+ * call takes pairs [k_begin, k_begin + k_count).  out_pd holds n_sets values (every set, whatever the range), out_union
+ * k_count values.  Any output may be NULL, and what is not asked for is not computed.
+ *
+ * st_unifrac_host checks that root and the universe ids are node ids of the tree, on the host, before anything is
+ * launched (ST_ERR_BOUNDS with *bad_id).  It does not verify the rest of the precondition: a universe that is not in
+ * depth-first order, an id that is not a leaf or a leaf that does not lie under root gives sums that mean nothing, with
+ * no error (SuchTree.unifrac builds the universe itself and checks the members).  It then has d and h computed on the tree's device, quantises them on the host (at most 2 n values), builds the
+ * range-minimum table on the device and runs the pair kernels.  out_shift is the shift used, out_d[n] and out_h[n - 1]
+ * the float32 depths.  ST_ERR_ARG: n outside 1 .. ST_UNIFRAC_MAX_UNIVERSE, offsets that do not increase, a position
+ * outside the universe, a set that is not strictly increasing, a range outside the triangle of n_sets (n_sets - 1) / 2
+ * pairs, a negative chunk_pairs, a bad shift.  chunk_pairs: pairs per device chunk, 0 = 2^22; the result does not depend
+ * on it.  Pairs of |A| + |B| <= ST_UNIFRAC_LANE_MAX positions are merged by one lane each, larger ones by one wave each;
+ * the environment variable SUCHTREE_AMD_UNIFRAC_LANE_MAX (0 .. 2^22, read at every call) replaces the threshold for a
+ * measurement, and no result depends on it.
+ * Device memory: 8 (1 + L) n bytes of depths and table, L = floor(log2(n - 1)) + 1 levels (at most 176 MB at 2^20
+ * leaves), the positions (4 bytes each) and offsets (8 bytes per set), 12 bytes per pair of a chunk for the heavy list
+ * and one of the two chunks of int64 results, 8 more for the other, and 28 n bytes while the depths are computed.  An
+ * allocation that fails is ST_ERR_NOMEM with the bytes asked for, before any output is written.  Zero sets launch
+ * nothing (out_shift is then the caller's shift, or 0); an empty range launches no pair kernel.
+ *
+ * st_unifrac_depths is the same reduction over the caller's int64 arrays d_q[n] and h_q[n - 1] (a |value| of 2^40 or
+ * more is ST_ERR_ARG): device = -1 is the host restatement (no GPU); device >= 0 uploads the arrays and runs the same
+ * kernels: the same integers.  No counterpart in the reference.
+ */
+#define ST_UNIFRAC_MAX_UNIVERSE 1048576
+#define ST_UNIFRAC_LANE_MAX 512
+
+int st_unifrac_host(st_tree *tree, int64_t root, const int64_t *univ, int32_t n_univ, const int32_t *set_pos, int64_t n_pos,
+                    const int64_t *sets, int64_t n_sets, int64_t k_begin, int64_t k_count, int32_t shift, int64_t chunk_pairs,
+                    int64_t *out_pd, int64_t *out_union, int32_t *out_shift, float *out_d, float *out_h, int64_t *bad_id);
+
+int st_unifrac_depths(int device, const int64_t *d_q, const int64_t *h_q, int32_t n, const int32_t *set_pos, int64_t n_pos,
+                      const int64_t *sets, int64_t n_sets, int64_t k_begin, int64_t k_count, int64_t chunk_pairs,
+                      int64_t *out_pd, int64_t *out_union);
+
+int st_unifrac_quantise(const float *d, const float *h, int32_t n, int32_t shift, int64_t *out_dq, int64_t *out_hq,
+                        int32_t *out_shift);
 
 /*
  * Exact Spearman rank correlation of the same pairs.  rank_x is the midrank of x_k among the call's n float32 distances

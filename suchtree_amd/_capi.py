@@ -47,6 +47,7 @@ SYMBOLS = (
     "st_quartet_positions", "st_compare_quartets_leaves_host", "st_compare_quartets_host",
     "st_compare_triangle_kendall_host", "st_compare_pairs_kendall_host", "st_kendall_arrays_host", "st_kendall_host",
     "st_hommola_permutation", "st_hommola_clades_host", "st_partner_dispersion_host", "st_dispersion_matrix",
+    "st_unifrac_host", "st_unifrac_depths", "st_unifrac_quantise",
 )
 
 CLADE_RECT, CLADE_TRI = 0, 1     # include/suchtree_hip.h: ST_CLADE_RECT / ST_CLADE_TRI
@@ -171,6 +172,54 @@ def dispersion_matrix(D, sets, permutations, seed, stream=0, device=-1, chunk_ta
     check(load().st_dispersion_matrix(int(device), _ptr(D), n, _ptr(pos) if len(pos) else None, len(pos), _ptr(off), n_sets, int(permutations),
                                       int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(chunk_tasks), _ptr(out) if out.size else None))
     return out
+
+
+UNIFRAC_MAX_UNIVERSE = 1 << 20     # ST_UNIFRAC_MAX_UNIVERSE: leaves per universe of st_unifrac_host
+UNIFRAC_LANE_MAX = 512             # ST_UNIFRAC_LANE_MAX: pairs of |A| + |B| up to this are merged by one lane, larger ones by one wave
+
+
+def _unifrac_range(n_sets, begin, count, chunk_pairs):
+    """(begin, count) of a triangle range over ``n_sets`` sets, ``count`` None = up to the last pair."""
+    total = n_sets * (n_sets - 1) // 2
+    begin = int(begin)
+    count = total - begin if count is None else int(count)
+    if begin < 0 or count < 0 or begin + count > total:
+        raise ValueError("pairs [%d, +%d) of a triangle of %d" % (begin, count, total))
+    if int(chunk_pairs) < 0:
+        raise ValueError("chunk_pairs < 0")
+    return begin, count
+
+
+def unifrac_quantise(d, h, shift=None):
+    """st_unifrac_quantise: (d_q int64, h_q int64, shift used) of the float32 depths ``d`` (n) and ``h`` (n - 1) under the
+    fixed-point rule of st_unifrac_host; ``shift`` None = automatic.  ValueError for a depth that is not finite or a shift
+    that puts a value at 2^40 or more."""
+    d = np.ascontiguousarray(d, dtype=np.float32)
+    h = np.ascontiguousarray(h, dtype=np.float32)
+    if d.ndim != 1 or h.ndim != 1 or len(h) != max(len(d) - 1, 0):
+        raise ValueError("d must hold n depths and h n - 1")
+    d_q, h_q = np.zeros(len(d), dtype=np.int64), np.zeros(len(h), dtype=np.int64)
+    used = ctypes.c_int32(0)
+    check(load().st_unifrac_quantise(_ptr(d) if len(d) else None, _ptr(h) if len(h) else None, len(d), -1 if shift is None else int(shift),
+                                     _ptr(d_q) if len(d) else None, _ptr(h_q) if len(h) else None, ctypes.byref(used)))
+    return d_q, h_q, int(used.value)
+
+
+def unifrac_depths(d_q, h_q, sets, begin=0, count=None, device=-1, chunk_pairs=0):
+    """st_unifrac_depths: (pd_q, union_q), the int64 PD of every set and union sum of pairs [begin, begin + count) of the
+    triangle over the position sets ``sets`` (as in ``dispersion_matrix``), from the quantised depths ``d_q`` (n) and
+    ``h_q`` (n - 1); ``device`` -1 = the host restatement (no GPU), else the kernels on that device."""
+    d_q = np.ascontiguousarray(d_q, dtype=np.int64)
+    h_q = np.ascontiguousarray(h_q, dtype=np.int64)
+    if d_q.ndim != 1 or h_q.ndim != 1 or len(h_q) != max(len(d_q) - 1, 0):
+        raise ValueError("d_q must hold n depths and h_q n - 1")
+    pos, off, n_sets = _dispersion_sets(sets, len(d_q))
+    begin, count = _unifrac_range(n_sets, begin, count, chunk_pairs)
+    pd_q, union_q = np.zeros(n_sets, dtype=np.int64), np.zeros(count, dtype=np.int64)
+    check(load().st_unifrac_depths(int(device), _ptr(d_q) if len(d_q) else None, _ptr(h_q) if len(h_q) else None, len(d_q),
+                                   _ptr(pos) if len(pos) else None, len(pos), _ptr(off), n_sets, begin, count, int(chunk_pairs),
+                                   _ptr(pd_q) if n_sets else None, _ptr(union_q) if count else None))
+    return pd_q, union_q
 
 
 QUARTET_MODE = {"all": 0, "sample": 1}      # include/suchtree_hip.h: ST_QUARTET_ALL / ST_QUARTET_SAMPLE
@@ -413,6 +462,10 @@ def load():
         L.st_partner_dispersion_host.argtypes = [vp, vp, ctypes.c_int32, vp, i64, vp, i64, i64, ctypes.c_uint64, ctypes.c_int32, i64, vp,
                                                  ctypes.POINTER(i64)]
         L.st_dispersion_matrix.argtypes = [i32, vp, ctypes.c_int32, vp, i64, vp, i64, i64, ctypes.c_uint64, ctypes.c_int32, i64, vp]
+        L.st_unifrac_host.argtypes = [vp, i64, vp, ctypes.c_int32, vp, i64, vp, i64, i64, i64, ctypes.c_int32, i64, vp, vp,
+                                      ctypes.POINTER(ctypes.c_int32), vp, vp, ctypes.POINTER(i64)]
+        L.st_unifrac_depths.argtypes = [i32, vp, vp, ctypes.c_int32, vp, i64, vp, i64, i64, i64, i64, vp, vp]
+        L.st_unifrac_quantise.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, ctypes.POINTER(ctypes.c_int32)]
         L.st_clade_plan.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64),
                                     ctypes.POINTER(i64)]
         L.st_compare_clades_host.argtypes = [vp, vp, vp, i64, vp, vp, i64, i64, i64, vp, vp, ctypes.POINTER(i64)]
@@ -1070,6 +1123,26 @@ class DeviceTree:
                                                   int(chunk_tasks), _ptr(out) if out.size else None, ctypes.byref(bad))
         check(rc, tree_size=self.size, bad_id=int(bad.value))
         return out
+
+    def unifrac_host(self, root, univ, sets, begin=0, count=None, shift=None, chunk_pairs=0):
+        """st_unifrac_host: (pd_q, union_q, shift, d, h) of the position sets ``sets`` (as in ``dispersion_matrix``) over the
+        universe ``univ`` (leaf ids of this tree under ``root``, depth-first): the int64 PD of every set, the union sums of
+        pairs [begin, begin + count) of the triangle, the shift used and the float32 depths."""
+        univ = np.ascontiguousarray(univ, dtype=np.int64)
+        if univ.ndim != 1:
+            raise ValueError("the universe must be 1-D")
+        n = len(univ)
+        pos, off, n_sets = _dispersion_sets(sets, n)
+        begin, count = _unifrac_range(n_sets, begin, count, chunk_pairs)
+        pd_q, union_q = np.zeros(n_sets, dtype=np.int64), np.zeros(count, dtype=np.int64)
+        d, h = np.zeros(n, dtype=np.float32), np.zeros(max(n - 1, 0), dtype=np.float32)
+        used, bad = ctypes.c_int32(0), ctypes.c_int64(0)
+        rc = self._lib.st_unifrac_host(self.handle, int(root), _ptr(univ) if n else None, n, _ptr(pos) if len(pos) else None, len(pos), _ptr(off),
+                                       n_sets, begin, count, -1 if shift is None else int(shift), int(chunk_pairs),
+                                       _ptr(pd_q) if n_sets else None, _ptr(union_q) if count else None, ctypes.byref(used),
+                                       _ptr(d) if n else None, _ptr(h) if n > 1 else None, ctypes.byref(bad))
+        check(rc, tree_size=self.size, bad_id=int(bad.value))
+        return pd_q, union_q, int(used.value), d, h
 
     def triangle_device(self, d_ids, m, k_begin, k_count, d_out_dist=0, d_out_mrca=0, stream=0, id_stride=1):
         rc = self._lib.st_triangle_device(self.handle, ctypes.c_void_p(d_ids), int(m), int(id_stride),

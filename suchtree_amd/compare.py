@@ -13,7 +13,8 @@ from typing import Optional
 
 import numpy as np
 
-__all__ = ["DistanceComparison", "CladeComparisons", "HommolaResult", "QuartetComparison", "SetDispersion", "quartet_positions"]
+__all__ = ["DistanceComparison", "CladeComparisons", "HommolaResult", "QuartetComparison", "SetDispersion", "SetUniFrac", "quartet_positions",
+           "unifrac_from_depths"]
 
 
 @dataclass(frozen=True)
@@ -511,6 +512,104 @@ class SetDispersion:
         cols = {} if self.leaves is None else {"name": self.names, "leaf": self.leaves}
         cols.update({k: getattr(self, k) for k in self.COLUMNS})
         return pd.DataFrame(cols)
+
+
+class SetUniFrac:
+    """How different the members of every two of many leaf sets are, measured on the tree (SuchTree.unifrac,
+    SuchLinkedTrees.partner_unifrac, unifrac_from_depths).
+
+    ``n_sets`` sets; the pairs are ``[begin, begin + count)`` of the triangle k = i (i - 1) / 2 + j, 0 <= j < i < n_sets
+    (:meth:`pair`).  ``pd_q`` (n_sets) and ``union_q`` (count) are exact int64 sums of depths in units of ``quantum`` =
+    2^-``shift``: Faith's PD of every set -- the branch length that joins the root to its members -- and the same for
+    the union of a pair's two sets.  They depend on (root, the sets, shift) alone, not on the range, the chunking or the
+    device.  ``pd`` = ``pd_q`` * quantum (float64).  Condensed float64 arrays over the pairs: ``shared`` = PD_i + PD_j - U,
+    the branch length both sets use; ``unifrac`` = (2 U - PD_i - PD_j) / U, the unweighted UniFrac distance (the share of
+    the union's branch length that only one set uses); ``phylosor`` = 2 shared / (PD_i + PD_j); NaN where a denominator
+    is 0.  ``leaves`` / ``names`` are filled in by ``partner_unifrac`` (the leaf whose partners a row describes), ``root``
+    by the tree calls.
+    """
+
+    def __init__(self, n_sets, begin, shift, pd_q, union_q, root=None):
+        self.n_sets, self.begin, self.shift = int(n_sets), int(begin), int(shift)
+        self.pd_q = np.asarray(pd_q, dtype=np.int64)
+        self.union_q = np.asarray(union_q, dtype=np.int64)
+        self.count = len(self.union_q)
+        self.quantum = math.ldexp(1.0, -self.shift)
+        self.pd = self.pd_q.astype(np.float64) * self.quantum
+        self.root = root
+        self.leaves = self.names = None
+
+    def __len__(self):
+        return self.n_sets
+
+    def pair(self, k):
+        """(i, j), j < i, of pair ``k`` of this result (triangle index ``begin + k``)."""
+        if not 0 <= k < self.count:
+            raise IndexError("pair %d of %d" % (k, self.count))
+        i, j = self._rows(np.array([self.begin + int(k)], dtype=np.int64))
+        return int(i[0]), int(j[0])
+
+    @staticmethod
+    def _rows(k):
+        i = ((1 + np.sqrt(1.0 + 8.0 * k.astype(np.float64))) // 2).astype(np.int64)
+        i -= i * (i - 1) // 2 > k
+        i += (i + 1) * i // 2 <= k
+        return i, k - i * (i - 1) // 2
+
+    def _sums(self):
+        i, j = self._rows(self.begin + np.arange(self.count, dtype=np.int64))
+        return self.pd_q[i] + self.pd_q[j]      # (exact: below 2^62)
+
+    @property
+    def shared(self):
+        return (self._sums() - self.union_q).astype(np.float64) * self.quantum
+
+    @property
+    def unifrac(self):
+        both = self._sums()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.union_q != 0, (2 * self.union_q - both) / self.union_q.astype(np.float64), np.nan)
+
+    @property
+    def phylosor(self):
+        both = self._sums()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(both != 0, 2 * (both - self.union_q) / both.astype(np.float64), np.nan)
+
+    def matrix(self, which="unifrac"):
+        """The square symmetric (n_sets, n_sets) form of ``which`` ("unifrac", "phylosor" or "shared") with a zero
+        diagonal; only where the result holds the whole triangle."""
+        if which not in ("unifrac", "phylosor", "shared"):
+            raise ValueError("which must be 'unifrac', 'phylosor' or 'shared'")
+        if self.begin != 0 or self.count != self.n_sets * (self.n_sets - 1) // 2:
+            raise ValueError("matrix() needs the whole triangle, this result holds pairs [%d, +%d)" % (self.begin, self.count))
+        out = np.zeros((self.n_sets, self.n_sets))
+        i, j = self._rows(np.arange(self.count, dtype=np.int64))
+        out[i, j] = out[j, i] = getattr(self, which)
+        return out
+
+    def to_dataframe(self):
+        """One row per pair as a pandas DataFrame (pandas imported here): i, j (and the two names where the call knows them),
+        union, shared, unifrac, phylosor."""
+        import pandas as pd
+        i, j = self._rows(self.begin + np.arange(self.count, dtype=np.int64))
+        cols = {"i": i, "j": j}
+        if self.names is not None:
+            cols["name_i"], cols["name_j"] = [self.names[v] for v in i], [self.names[v] for v in j]
+        cols.update({"union": self.union_q.astype(np.float64) * self.quantum, "shared": self.shared, "unifrac": self.unifrac,
+                     "phylosor": self.phylosor})
+        return pd.DataFrame(cols)
+
+
+def unifrac_from_depths(d, h, sets, begin=0, count=None, shift=None, device=None, chunk_pairs=0):
+    """:class:`SetUniFrac` of the position sets ``sets`` over a universe given by its float32 depths: ``d[k]`` the root
+    distance of leaf k (leaves in depth-first order), ``h[k]`` that of the MRCA of leaves k and k + 1.  The depths are
+    quantised by the rule of ``SuchTree.unifrac`` (``shift`` None = automatic).  ``device=None`` computes on the host,
+    without a GPU; a device index runs the kernels there -- the same integers."""
+    from . import _capi
+    d_q, h_q, used = _capi.unifrac_quantise(d, h, shift)
+    pd_q, union_q = _capi.unifrac_depths(d_q, h_q, sets, begin, count, -1 if device is None else int(device), chunk_pairs)
+    return SetUniFrac(len(pd_q), begin, used, pd_q, union_q)
 
 
 def null_summary(observed, null, degenerate=None):

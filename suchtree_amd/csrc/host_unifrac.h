@@ -1,0 +1,183 @@
+// host_unifrac.h -- part of suchtree_hip.hip (included after host_dispersion.h).  The device side of st_unifrac_host and
+// st_unifrac_depths (kernels_unifrac.h; the plan, the quantiser and the host restatement: unifrac_plan.cpp).  One work
+// block: the heavy counter, the quantised depths, the range-minimum table (level 0 is h_q, one launch per further level),
+// the positions and offsets, one heavy list and two chunks of int64 results.  Per chunk: the counter zeroed, the lane
+// kernel, the wave kernel over what the lane kernel listed (skipped where no two sets reach the threshold), the results
+// copied to one of two pinned buffers (ReadbackRing, host_compare.h) and moved to the caller's arrays while the device
+// works on the next chunk.  st_unifrac_host first has the tree's distance and MRCA kernels write d and h, reads them back
+// and quantises them on the host (at most 2 n values).
+#pragma once
+
+// the lane / wave threshold: ST_UNIFRAC_LANE_MAX, or SUCHTREE_AMD_UNIFRAC_LANE_MAX for a measurement (scripts/unifrac_bench.py
+// sweeps it); no result depends on it
+static int unifrac_lane_max()
+{
+    const char *e = std::getenv("SUCHTREE_AMD_UNIFRAC_LANE_MAX");
+    if (e && *e) {
+        char *end = nullptr;
+        const long v = std::strtol(e, &end, 10);
+        if (end && *end == 0 && v >= 0 && v <= (1 << 22)) return (int)v;
+    }
+    return kUnifracLaneMax;
+}
+
+using UnifracRing = ReadbackRing<int64_t, const UnifracChunk *>;
+
+struct UnifracWork {      // declared before the stream's owner
+    DevBuf<char> d;
+    UnifracRing ring;
+    size_t o_dq = 0, o_table = 0, o_pos = 0, o_sets = 0, o_heavy = 0, o_out = 0, out_bytes = 0, total = 0;
+
+    // ST_OK, or ST_ERR_NOMEM with the bytes asked for
+    int alloc(const UnifracPlan &P, int64_t n_pos, const char *what)
+    {
+        o_dq = 256;      // (the counter has the block's first bytes)
+        o_table = o_dq + align256((size_t)P.n * 8);
+        o_pos = o_table + align256((size_t)P.levels * (size_t)P.m * 8);
+        o_sets = o_pos + align256((size_t)n_pos * 4);
+        o_heavy = o_sets + align256((size_t)(P.n_sets + 1) * 8);
+        o_out = o_heavy + align256((size_t)P.max_chunk * 4);
+        out_bytes = align256((size_t)P.max_chunk * 8);
+        total = o_out + 2 * out_bytes;
+        hipError_t e = d.alloc(total);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ST_ERR_NOMEM, std::string(what) + ": a work block of " + std::to_string(total) + " bytes: " + hipGetErrorString(e));
+        }
+        e = ring.alloc((size_t)P.max_chunk);
+        if (e != hipSuccess && !(ring.h[0] && ring.h[1])) {
+            (void)hipGetLastError();
+            return fail(ST_ERR_NOMEM, std::string(what) + ": a pinned buffer of " + std::to_string((size_t)P.max_chunk * 8) + " bytes: " + hipGetErrorString(e));
+        }
+        if (e != hipSuccess) return fail(ST_ERR_HIP, std::string(what) + " setup: " + hipGetErrorString(e));
+        return ST_OK;
+    }
+};
+
+// every chunk of the plan on stream s over the quantised depths (host arrays that outlive the call's stream work).
+// Returns ST_OK or ST_ERR_HIP; on return nothing of this call is pending on s unless a HIP call failed.
+static int unifrac_chunks(UnifracWork &W, const char *what, hipStream_t s, const UnifracPlan &P, const int64_t *d_q, const int64_t *h_q,
+                          const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t *out_pd, int64_t *out_union)
+{
+    auto hip_fail = [&](const char *step, hipError_t e) { return fail(ST_ERR_HIP, std::string(what) + step + hipGetErrorString(e)); };
+    char *const d = W.d;
+    int64_t *const d_table = reinterpret_cast<int64_t *>(d + W.o_table);
+    hipError_t e = hipMemcpyAsync(d + W.o_dq, d_q, (size_t)P.n * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && P.m > 0) e = hipMemcpyAsync(d_table, h_q, (size_t)P.m * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && n_pos > 0) e = hipMemcpyAsync(d + W.o_pos, set_pos, (size_t)n_pos * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + W.o_sets, sets, (size_t)(P.n_sets + 1) * 8, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return hip_fail(" setup: ", e);
+    for (int l = 1; l < P.levels; l++) {      // (2^l <= m: every level has an entry)
+        const int64_t half = (int64_t)1 << (l - 1), count = P.m - 2 * half + 1;
+        hipLaunchKernelGGL(k_unifrac_table, dim3((unsigned)((count + kUnifracThreads - 1) / kUnifracThreads)), dim3(kUnifracThreads), 0, s,
+                           d_table + (int64_t)(l - 1) * P.m, d_table + (int64_t)l * P.m, (long long)half, (long long)count);
+        e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(" launch: ", e);
+    }
+    int64_t largest = 0;
+    for (int64_t r = 0; r < P.n_sets; r++) largest = std::max(largest, sets[r + 1] - sets[r]);
+    const int lane_max = unifrac_lane_max();
+    const bool heavy = 2 * largest > lane_max;      // (else no task reaches the wave form: its launch is left out)
+    int64_t *d_out[2] = {reinterpret_cast<int64_t *>(d + W.o_out), reinterpret_cast<int64_t *>(d + W.o_out + W.out_bytes)};
+    auto deliver = [&](const int64_t *got, const UnifracChunk *c) {
+        std::memcpy((c->kind == kUnifracPD ? out_pd : out_union) + c->out_at, got, (size_t)c->count * 8);
+    };
+    for (const UnifracChunk &c : P.chunks) {
+        e = W.ring.acquire(deliver);      // (the results of two chunks ago)
+        if (e != hipSuccess) return hip_fail(" read-back: ", e);
+        int64_t *const out = d_out[W.ring.next];
+        const UnifracArgs a{reinterpret_cast<const int64_t *>(d + W.o_dq), d_table, reinterpret_cast<const int *>(d + W.o_pos),
+                            reinterpret_cast<const int64_t *>(d + W.o_sets), out, reinterpret_cast<unsigned *>(d + W.o_heavy),
+                            reinterpret_cast<unsigned *>(d), (long long)P.m, (long long)c.begin, (unsigned)c.count, c.kind, lane_max};
+        if (heavy) e = hipMemsetAsync(d, 0, 16, s);      // (stream order: the wave kernel of the chunk before has read it)
+        if (e != hipSuccess) return hip_fail(" launch: ", e);
+        hipLaunchKernelGGL(k_unifrac_lane, dim3((unsigned)((c.count + kUnifracThreads - 1) / kUnifracThreads)), dim3(kUnifracThreads), 0, s, a);
+        e = hipGetLastError();
+        if (e == hipSuccess && heavy) {
+            hipLaunchKernelGGL(k_unifrac_wave, dim3(kUnifracWaveBlocks), dim3(kUnifracThreads), 0, s, a);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = W.ring.post(out, (size_t)c.count, &c, s);
+        if (e != hipSuccess) return hip_fail(" launch: ", e);
+    }
+    e = W.ring.flush(deliver);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(" read-back: ", e);
+    return ST_OK;
+}
+
+static int unifrac_depths_device(int device, const UnifracPlan &P, const int64_t *d_q, const int64_t *h_q, const int32_t *set_pos, int64_t n_pos,
+                                 const int64_t *sets, int64_t *out_pd, int64_t *out_union)
+{
+    if (const int rc = device_index_arg(device); rc != ST_OK) return rc;
+    ST_DEVICE(device);
+    UnifracWork W;
+    DrainedStream s;
+    const hipError_t e = s.create();
+    if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("unifrac depths setup: ") + hipGetErrorString(e));
+    if (const int rc = W.alloc(P, n_pos, "unifrac depths"); rc != ST_OK) return rc;
+    return unifrac_chunks(W, "unifrac depths", s, P, d_q, h_q, set_pos, n_pos, sets, out_pd, out_union);
+}
+
+static int unifrac_tree_run(st_tree *t, int64_t root, const int64_t *univ, const UnifracPlan &P, const int32_t *set_pos, int64_t n_pos,
+                            const int64_t *sets, int32_t shift, int64_t *out_pd, int64_t *out_union, int32_t *out_shift, float *out_d, float *out_h,
+                            int64_t *bad_id)
+{
+    ST_DEVICE(t->device);
+    const size_t n = (size_t)P.n, m = (size_t)P.m;
+    std::vector<float> h_d(n), h_h(m);      // (read-back targets: declared before the stream's owner)
+    UnifracWork W;
+    TwoTreeSession ses(t, t, "unifrac");
+    // the depth block: root | universe | d | MRCA ids of adjacent leaves, as int32 and as int64 | h
+    const size_t o_univ = 256, o_d = o_univ + align256(n * 8), o_m32 = o_d + align256(n * 4), o_m64 = o_m32 + align256(m * 4);
+    const size_t o_h = o_m64 + align256(m * 8), total = o_h + align256(m * 4);
+    hipError_t e = ses.s.create();
+    if (e != hipSuccess) return ses.hip_fail(" setup: ", e);
+    e = ses.d.alloc(total);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ST_ERR_NOMEM, "unifrac: a depth block of " + std::to_string(total) + " bytes: " + hipGetErrorString(e));
+    }
+    if (!P.chunks.empty())
+        if (const int rc = W.alloc(P, n_pos, "unifrac"); rc != ST_OK) return rc;
+    char *const d = ses.d;
+    const hipStream_t s = ses.s;
+    long long *d_root = reinterpret_cast<long long *>(d), *d_univ = reinterpret_cast<long long *>(d + o_univ);
+    long long *d_m64 = reinterpret_cast<long long *>(d + o_m64);
+    int *d_m32 = reinterpret_cast<int *>(d + o_m32);
+    float *d_d = reinterpret_cast<float *>(d + o_d), *d_h = reinterpret_cast<float *>(d + o_h);
+    const long long root_id = root;
+    e = hipMemcpyAsync(d_root, &root_id, 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_univ, univ, n * 8, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return ses.hip_fail(" setup: ", e);
+    int rc = ses.arm();
+    if (rc != ST_OK) return rc;
+    // d[k] = dist(root, u[k]), the arguments in that order: a 1 x n grid
+    rc = enqueue_src(t, SrcGrid{d_root, d_univ, (long long)n, 0, 0}, (int64_t)n, DistSink{nullptr, d_d}, MrcaSink{nullptr, nullptr}, t->d_fault_host, s);
+    if (rc != ST_OK) return rc;
+    if (m > 0) {      // h[k] = dist(root, mrca(u[k], u[k + 1])): the pairs are the universe read with stride one
+        rc = enqueue_src(t, SrcStrided{d_univ, 1, 1}, (int64_t)m, DistSink{nullptr, nullptr}, MrcaSink{d_m32, nullptr}, t->d_fault_host, s);
+        if (rc != ST_OK) return rc;
+        hipLaunchKernelGGL(k_unifrac_widen, dim3((unsigned)((m + kUnifracThreads - 1) / kUnifracThreads)), dim3(kUnifracThreads), 0, s, d_m32, d_m64,
+                           (long long)m);
+        e = hipGetLastError();
+        if (e != hipSuccess) return ses.hip_fail(" launch: ", e);
+        rc = enqueue_src(t, SrcGrid{d_root, d_m64, (long long)m, 0, 0}, (int64_t)m, DistSink{nullptr, d_h}, MrcaSink{nullptr, nullptr}, t->d_fault_host, s);
+        if (rc != ST_OK) return rc;
+        e = hipMemcpyAsync(h_h.data(), d_h, m * 4, hipMemcpyDeviceToHost, s);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h_d.data(), d_d, n * 4, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return ses.hip_fail(" read-back: ", e);
+    rc = ses.close(bad_id);      // (drains the stream)
+    if (rc != ST_OK) return rc;
+    std::vector<int64_t> d_q(n), h_q(m);
+    std::string err;
+    int32_t used = 0;
+    rc = unifrac_quantise(h_d.data(), h_h.data(), P.n, shift, d_q.data(), h_q.data(), &used, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (out_shift) *out_shift = used;
+    if (out_d) std::copy(h_d.begin(), h_d.end(), out_d);
+    if (out_h) std::copy(h_h.begin(), h_h.end(), out_h);
+    if (P.chunks.empty()) return ST_OK;
+    return unifrac_chunks(W, "unifrac", s, P, d_q.data(), h_q.data(), set_pos, n_pos, sets, out_pd, out_union);
+}

@@ -48,6 +48,9 @@
 // MPD / MNTD sums of many leaf sets under the taxa-labels null (st_partner_dispersion_host, st_dispersion_matrix):
 // kernels_dispersion.h (one sort per permutation, the k x k reducer in three size classes), host_dispersion.h (the chunk
 // driver) and, host-only, dispersion_plan.cpp (argument checks, size classes, chunks, the restatement of the reduction).
+// Faith's PD of many leaf sets and the union sums of their pairs behind UniFrac (st_unifrac_host, st_unifrac_depths):
+// kernels_unifrac.h (the range-minimum table, the set merge in a lane form and a wave form), host_unifrac.h (the depths, the
+// chunk driver) and, host-only, unifrac_plan.cpp (argument checks, the quantiser, chunks, the restatement of the merge).
 //
 // Host side of the C ABI: tree upload to one or several GPUs (tree_prep.cpp builds the tables, under a table budget
 // if one is given), the host path (host_pipe.h, host_copy.h: packed ids in through the copy engine, kernels write
@@ -167,6 +170,7 @@ static int device_index_arg(int device)
 #include "kernels_perm.h"
 #include "kernels_hommola.h"
 #include "kernels_dispersion.h"
+#include "kernels_unifrac.h"
 
 
 // --------------------------------------------------------------------------
@@ -183,6 +187,7 @@ using namespace st;
 #include "host_quartets.h"
 #include "host_hommola.h"
 #include "host_dispersion.h"
+#include "host_unifrac.h"
 
 extern "C" {
 
@@ -1326,6 +1331,51 @@ try {
         return ST_OK;
     }
     return dispersion_matrix_device(device, D, P, set_pos, n_pos, seed, stream, out);
+} ST_CATCH_ALL
+
+int st_unifrac_quantise(const float *d, const float *h, int32_t n, int32_t shift, int64_t *out_dq, int64_t *out_hq, int32_t *out_shift)
+try {
+    std::string err;
+    const int rc = unifrac_quantise(d, h, n, shift, out_dq, out_hq, out_shift, err);
+    return rc == ST_OK ? ST_OK : fail(rc, err);
+} ST_CATCH_ALL
+
+int st_unifrac_depths(int device, const int64_t *d_q, const int64_t *h_q, int32_t n, const int32_t *set_pos, int64_t n_pos, const int64_t *sets,
+                      int64_t n_sets, int64_t k_begin, int64_t k_count, int64_t chunk_pairs, int64_t *out_pd, int64_t *out_union)
+try {
+    UnifracPlan P;
+    std::string err;
+    int rc = unifrac_plan(n, set_pos, n_pos, sets, n_sets, k_begin, k_count, chunk_pairs, out_pd != nullptr, out_union != nullptr, P, err);
+    if (rc == ST_OK) rc = unifrac_depth_args(d_q, h_q, n, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (device < -1) return fail(ST_ERR_ARG, "device must be -1 (host) or a device index");
+    if (P.chunks.empty()) return ST_OK;      // (no sets, an empty range or no output: nothing to launch)
+    if (device < 0) {
+        unifrac_host(d_q, h_q, P, set_pos, sets, out_pd, out_union);
+        return ST_OK;
+    }
+    return unifrac_depths_device(device, P, d_q, h_q, set_pos, n_pos, sets, out_pd, out_union);
+} ST_CATCH_ALL
+
+int st_unifrac_host(st_tree *t, int64_t root, const int64_t *univ, int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets,
+                    int64_t n_sets, int64_t k_begin, int64_t k_count, int32_t shift, int64_t chunk_pairs, int64_t *out_pd, int64_t *out_union,
+                    int32_t *out_shift, float *out_d, float *out_h, int64_t *bad_id)
+try {
+    UnifracPlan P;
+    std::string err;
+    int rc = unifrac_plan(n_univ, set_pos, n_pos, sets, n_sets, k_begin, k_count, chunk_pairs, out_pd != nullptr, out_union != nullptr, P, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (shift < -1 || shift > kUnifracMaxShift) return fail(ST_ERR_ARG, "shift must be -1 (automatic) or 0 to " + std::to_string(kUnifracMaxShift));
+    if (!univ) return fail(ST_ERR_ARG, "univ is NULL");
+    if (!t) return fail(ST_ERR_ARG, "tree is NULL");
+    rc = compare_check_ids(&root, 1, t->n_nodes, bad_id);
+    if (rc == ST_OK) rc = compare_check_ids(univ, n_univ, t->n_nodes, bad_id);
+    if (rc != ST_OK) return rc;
+    if (n_sets == 0) {      // (no sets: nothing to launch, and no depth is asked for)
+        if (out_shift) *out_shift = std::max(shift, 0);
+        return ST_OK;
+    }
+    return unifrac_tree_run(t, root, univ, P, set_pos, n_pos, sets, shift, out_pd, out_union, out_shift, out_d, out_h, bad_id);
 } ST_CATCH_ALL
 
 int st_graph_matrices_host(int device, int64_t n, int64_t n_edges, const int32_t *u, const int32_t *v,

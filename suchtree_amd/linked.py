@@ -541,16 +541,32 @@ class SuchLinkedTrees:
             if v is not None and (isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 0):
                 raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
         ll = np.ascontiguousarray(self.linklist, dtype=np.int64)
-        if of == "A":
-            own, partner, own_ids, partner_ids = self._tree_a, self._tree_b, ll[:, 1], ll[:, 0]
-            own_leaves, partner_leaves, root = self._subset_a_leafs, self._subset_b_leafs, self._subset_b_root
+        if pool == "subset":
+            universe = np.asarray(self._subset_b_leafs if of == "A" else self._subset_a_leafs, dtype=np.int64)
         else:
-            own, partner, own_ids, partner_ids = self._tree_b, self._tree_a, ll[:, 0], ll[:, 1]
-            own_leaves, partner_leaves, root = self._subset_b_leafs, self._subset_a_leafs, self._subset_a_root
-        universe = np.asarray(partner_leaves, dtype=np.int64) if pool == "subset" else np.unique(partner_ids)
-        if len(universe) > _capi.HOMMOLA_MAX_UNIVERSE:
+            universe = np.unique(ll[:, 0 if of == "A" else 1])
+        if len(universe) > _capi.HOMMOLA_MAX_UNIVERSE:      # (before the rows are built)
             raise ValueError("the partner tree's %s has %d leaves: at most %d (subset it first)"
                              % ("subset" if pool == "subset" else "linked leaves", len(universe), _capi.HOMMOLA_MAX_UNIVERSE))
+        own, partner, root, leaves, sets = self._partner_rows(of, min_partners, max_partners, ll)
+        out = partner.dispersion(sets, universe=universe, permutations=permutations, seed=seed, stream=int(root), keep_null=keep_null)
+        out.leaves = np.asarray(leaves, dtype=np.int64)
+        names = own.leaf_nodes
+        out.names = [names[int(v)] for v in leaves]
+        return out
+
+    def _partner_rows(self, of, min_partners, max_partners, ll=None):
+        """(own tree, partner tree, partner subset root, rows' leaf ids, rows' partner ids): the leaves of the current
+        subset of tree ``of``, in subset order, with min_partners .. max_partners links inside the other subset.  ``ll``:
+        the int64 ``linklist`` where the caller has read it already."""
+        if ll is None:
+            ll = np.ascontiguousarray(self.linklist, dtype=np.int64)
+        if of == "A":
+            own, partner, own_ids, partner_ids = self._tree_a, self._tree_b, ll[:, 1], ll[:, 0]
+            own_leaves, root = self._subset_a_leafs, self._subset_b_root
+        else:
+            own, partner, own_ids, partner_ids = self._tree_b, self._tree_a, ll[:, 0], ll[:, 1]
+            own_leaves, root = self._subset_b_leafs, self._subset_a_root
         by_leaf = {}      # leaf -> its partners' ids
         if len(ll):
             order = np.argsort(own_ids, kind="stable")
@@ -563,7 +579,31 @@ class SuchLinkedTrees:
             if k >= max(int(min_partners), 1) and (max_partners is None or k <= max_partners):
                 leaves.append(leaf)
                 sets.append(partners)
-        out = partner.dispersion(sets, universe=universe, permutations=permutations, seed=seed, stream=int(root), keep_null=keep_null)
+        return own, partner, int(root), leaves, sets
+
+    def partner_unifrac(self, of="A", min_partners=1, max_partners=None, begin=0, count=None, shift=None):
+        """How different are two leaves' partners: Faith's PD of every leaf's partner set and unweighted UniFrac between
+        every two of them, measured on the partner tree.
+
+        ``of="A"``: one row per TreeA leaf of the current ``subset_a`` (in ``subset_a_leafs`` order) with at least
+        ``min_partners`` -- and, unless ``max_partners`` is None, at most that many -- linked TreeB leaves inside the
+        current ``subset_b``, the row choice of :meth:`partner_dispersion`; the branch lengths are TreeB's, from its
+        current subset root.  ``of="B"`` is the mirror.  ``begin`` / ``count`` / ``shift`` as in :meth:`SuchTree.unifrac`,
+        which does the work: a sparse set merge over all row pairs on the GPU, no distance matrix, up to 2^20 partner
+        leaves.  Two leaves with the same partners are at distance 0, two with partners in disjoint clades near 1.
+
+        The subset state, ``linklist`` and the generator of :meth:`sample_linked_distances` are left as they were.
+        Returns a :class:`~suchtree_amd.compare.SetUniFrac` with ``leaves`` (the rows' leaf ids), ``names`` and ``root``.
+        An extension: the reference has no counterpart.
+        """
+        import numbers
+        if of not in ("A", "B"):
+            raise ValueError("of must be 'A' or 'B'")
+        for name, v in (("min_partners", min_partners), ("max_partners", max_partners)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 0):
+                raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
+        own, partner, root, leaves, sets = self._partner_rows(of, min_partners, max_partners)
+        out = partner.unifrac(sets, root=root, begin=begin, count=count, shift=shift)
         out.leaves = np.asarray(leaves, dtype=np.int64)
         names = own.leaf_nodes
         out.names = [names[int(v)] for v in leaves]

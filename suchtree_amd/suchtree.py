@@ -613,6 +613,66 @@ class SuchTree(TreeNavigation):
             out.fill(at, k[at:end], rec)      # (each group is reduced before the next)
         return out
 
+    def unifrac(self, sets, root=None, begin=0, count=None, shift=None, chunk_pairs=0):
+        """How different are every two sets of leaves, measured on this tree: Faith's PD and unweighted UniFrac, on the GPU.
+
+        ``sets`` is an iterable of collections of leaf names or leaf ids; a repeated member is a ValueError, and every
+        member must lie under ``root`` (a node id; None = the tree's root).  PD of a set is the branch length that joins
+        ``root`` to its members; for a pair of sets the call also sums the branch length of their union, from which
+        ``shared``, ``unifrac`` and ``phylosor`` follow (:class:`~suchtree_amd.compare.SetUniFrac`).  The universe is the
+        union of all members in depth-first order (up to 2^20 leaves): no distance matrix is built.
+
+        The pairs are ``[begin, begin + count)`` of the triangle k = i (i - 1) / 2 + j, j < i; ``count=None`` means the
+        whole triangle, which above 2^31 pairs is a ValueError: ask for ranges.  The sums are exact integers over depths
+        quantised to 2^-``shift`` (None = chosen from the largest depth): a row's ``pd_q`` and a pair's ``union_q`` depend
+        on (root, the sets, shift) alone, so pass ``shift=`` to keep several calls on one scale.  ``shift=`` takes 0 to
+        256: on a tree with a depth of 2^40 or more the automatic shift is negative and cannot be passed back; calls over
+        the same sets and root choose the same automatic shift there.  An extension: the
+        reference has no counterpart.
+        """
+        from . import compare
+        for name, v in (("begin", begin), ("count", count), ("shift", shift), ("chunk_pairs", chunk_pairs)):
+            if (v is not None or name in ("begin", "chunk_pairs")) and (isinstance(v, bool) or not isinstance(v, Integral) or v < 0):
+                raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
+        root = self.root_node if root is None else self._validate_node(root)
+        leaf_ids = np.flatnonzero(np.asarray(self._flat.left) == -1).astype(np.int64)
+        plan = _capi.clade_plan(self._flat.parent, leaf_ids)      # (one link per leaf: _depth_first_leaves, and every node's range of it)
+        order = leaf_ids[plan["perm"]]
+        rows, member = [], np.zeros(self.size, dtype=bool)
+        for r, members in enumerate(sets):
+            ids = self._leaf_ids(members, "set %d" % r)
+            if len(np.unique(ids)) != len(ids):
+                raise ValueError("set %d: a repeated member" % r)
+            rows.append(ids)
+            member[ids] = True
+        univ = order[member[order]]
+        inside = np.zeros(self.size, dtype=bool)      # the leaves under root are one range of the depth-first order
+        inside[order[int(plan["begin"][root]):int(plan["begin"][root]) + int(plan["count"][root])]] = True
+        if not inside[univ].all():
+            raise ValueError("leaf %d does not lie under node %d" % (int(univ[~inside[univ]][0]), root))
+        if len(univ) > _capi.UNIFRAC_MAX_UNIVERSE:
+            raise ValueError("the sets hold %d distinct leaves: at most %d" % (len(univ), _capi.UNIFRAC_MAX_UNIVERSE))
+        total = len(rows) * (len(rows) - 1) // 2
+        if count is None:
+            count = total - int(begin)
+            if count > 1 << 31:
+                raise ValueError("the whole triangle of %d sets is %d pairs, more than 2^31: ask for ranges with begin= and count=" % (len(rows), total))
+        if begin + count > total or count < 0:
+            raise ValueError("pairs [%d, +%d) of a triangle of %d" % (begin, count, total))
+        where = np.full(self.size, -1, dtype=np.int64)
+        where[univ] = np.arange(len(univ))
+        pos = [np.sort(where[ids]).astype(np.int32) for ids in rows]
+        offsets = np.zeros(len(rows) + 1, dtype=np.int64)
+        np.cumsum([len(p) for p in pos], out=offsets[1:])
+        set_pos = np.concatenate(pos) if pos else np.empty(0, dtype=np.int32)
+        if not len(univ):      # (no member at all: nothing is launched, and the tree stays where it is)
+            out = compare.SetUniFrac(len(rows), begin, shift or 0, np.zeros(len(rows), dtype=np.int64), np.zeros(count, dtype=np.int64), root)
+        else:
+            pd_q, union_q, used, _, _ = self._device_tree().unifrac_host(root, univ, (set_pos.astype(np.int32), offsets), begin, count, shift,
+                                                                         chunk_pairs)
+            out = compare.SetUniFrac(len(rows), begin, used, pd_q, union_q, root)
+        return out
+
     def common_ancestor(self, a: Union[int, str], b: Union[int, str]) -> int:
         """Most recent common ancestor of two nodes (MuchTree.pyx:1128-1149)."""
         node_a, node_b = self._validate_node_pair(a, b)
