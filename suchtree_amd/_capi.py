@@ -169,8 +169,8 @@ def dispersion_matrix(D, sets, permutations, seed, stream=0, device=-1, chunk_ta
     _dispersion_args(permutations, stream, chunk_tasks)
     pos, off, n_sets = _dispersion_sets(sets, n)
     out = np.zeros((n_sets, int(permutations) + 1), dtype=DISPERSION_RECORD)
-    check(load().st_dispersion_matrix(int(device), _ptr(D), n, _ptr(pos) if len(pos) else None, len(pos), _ptr(off), n_sets, int(permutations),
-                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(chunk_tasks), _ptr(out) if out.size else None))
+    check(load().st_dispersion_matrix(int(device), _ptr(D), n, _arg(pos), len(pos), _ptr(off), n_sets, int(permutations),
+                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(chunk_tasks), _arg(out)))
     return out
 
 
@@ -200,8 +200,7 @@ def unifrac_quantise(d, h, shift=None):
         raise ValueError("d must hold n depths and h n - 1")
     d_q, h_q = np.zeros(len(d), dtype=np.int64), np.zeros(len(h), dtype=np.int64)
     used = ctypes.c_int32(0)
-    check(load().st_unifrac_quantise(_ptr(d) if len(d) else None, _ptr(h) if len(h) else None, len(d), -1 if shift is None else int(shift),
-                                     _ptr(d_q) if len(d) else None, _ptr(h_q) if len(h) else None, ctypes.byref(used)))
+    check(load().st_unifrac_quantise(_arg(d), _arg(h), len(d), -1 if shift is None else int(shift), _arg(d_q), _arg(h_q), ctypes.byref(used)))
     return d_q, h_q, int(used.value)
 
 
@@ -216,9 +215,8 @@ def unifrac_depths(d_q, h_q, sets, begin=0, count=None, device=-1, chunk_pairs=0
     pos, off, n_sets = _dispersion_sets(sets, len(d_q))
     begin, count = _unifrac_range(n_sets, begin, count, chunk_pairs)
     pd_q, union_q = np.zeros(n_sets, dtype=np.int64), np.zeros(count, dtype=np.int64)
-    check(load().st_unifrac_depths(int(device), _ptr(d_q) if len(d_q) else None, _ptr(h_q) if len(h_q) else None, len(d_q),
-                                   _ptr(pos) if len(pos) else None, len(pos), _ptr(off), n_sets, begin, count, int(chunk_pairs),
-                                   _ptr(pd_q) if n_sets else None, _ptr(union_q) if count else None))
+    check(load().st_unifrac_depths(int(device), _arg(d_q), _arg(h_q), len(d_q), _arg(pos), len(pos), _ptr(off), n_sets, begin, count,
+                                   int(chunk_pairs), _arg(pd_q), _arg(union_q)))
     return pd_q, union_q
 
 
@@ -702,6 +700,14 @@ def _ptr(a):
     return None if a is None else ctypes.c_void_p(a.ctypes.data)
 
 
+def _arg(a):
+    """A call's argument: an array goes as its pointer (NULL when it is empty or None), a result structure by reference,
+    anything else as it is."""
+    if isinstance(a, np.ndarray):
+        return _ptr(a) if a.size else None
+    return ctypes.byref(a) if isinstance(a, ctypes.Structure) else a
+
+
 def clade_plan(parent, link_leaf, max_links=None):
     """st_clade_plan (host only): the clade-contiguous permutation of the links (given in rank order by their clade-tree
     leaf id), each node's link range / count / leaf count, the segments (a CLADE_SEGMENT array in pair order) and the
@@ -968,14 +974,10 @@ class DeviceTree:
         return int(m * (m - 1) // 2 - int(k_begin) if k_count is None else k_count)
 
     def _compare_call(self, fn, other, args, *outs):
-        """fn(self, other, *args, *outs, &bad_id) of a two-tree entry point: an array goes as its pointer (NULL when it is
-        empty or None), a result structure by reference.  Raises as _compare_check does."""
-        def c(a):
-            if isinstance(a, np.ndarray):
-                return _ptr(a) if a.size else None
-            return ctypes.byref(a) if isinstance(a, ctypes.Structure) else a
+        """fn(self, other, *args, *outs, &bad_id) of a two-tree entry point, every argument as _arg passes it.  Raises as
+        _compare_check does."""
         bad = ctypes.c_int64(0)
-        self._compare_check(other, fn(self.handle, other.handle, *(c(a) for a in args + outs), ctypes.byref(bad)), bad)
+        self._compare_check(other, fn(self.handle, other.handle, *(_arg(a) for a in args + outs), ctypes.byref(bad)), bad)
 
     def compare_triangle_host(self, other, ids_x, ids_y, k_begin=0, k_count=None, edges=None):
         """Moments (``PairMoments``) and, with ``edges = (xedges, yedges)``, the int64 2-D histogram of the distances of
@@ -1118,9 +1120,8 @@ class DeviceTree:
         pos, off, n_sets = _dispersion_sets(sets, len(univ))
         out = np.zeros((n_sets, int(permutations) + 1), dtype=DISPERSION_RECORD)
         bad = ctypes.c_int64(0)
-        rc = self._lib.st_partner_dispersion_host(self.handle, _ptr(univ) if len(univ) else None, len(univ), _ptr(pos) if len(pos) else None,
-                                                  len(pos), _ptr(off), n_sets, int(permutations), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream),
-                                                  int(chunk_tasks), _ptr(out) if out.size else None, ctypes.byref(bad))
+        rc = self._lib.st_partner_dispersion_host(self.handle, _arg(univ), len(univ), _arg(pos), len(pos), _ptr(off), n_sets, int(permutations),
+                                                  int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(chunk_tasks), _arg(out), ctypes.byref(bad))
         check(rc, tree_size=self.size, bad_id=int(bad.value))
         return out
 
@@ -1137,10 +1138,9 @@ class DeviceTree:
         pd_q, union_q = np.zeros(n_sets, dtype=np.int64), np.zeros(count, dtype=np.int64)
         d, h = np.zeros(n, dtype=np.float32), np.zeros(max(n - 1, 0), dtype=np.float32)
         used, bad = ctypes.c_int32(0), ctypes.c_int64(0)
-        rc = self._lib.st_unifrac_host(self.handle, int(root), _ptr(univ) if n else None, n, _ptr(pos) if len(pos) else None, len(pos), _ptr(off),
-                                       n_sets, begin, count, -1 if shift is None else int(shift), int(chunk_pairs),
-                                       _ptr(pd_q) if n_sets else None, _ptr(union_q) if count else None, ctypes.byref(used),
-                                       _ptr(d) if n else None, _ptr(h) if n > 1 else None, ctypes.byref(bad))
+        rc = self._lib.st_unifrac_host(self.handle, int(root), _arg(univ), n, _arg(pos), len(pos), _ptr(off), n_sets, begin, count,
+                                       -1 if shift is None else int(shift), int(chunk_pairs), _arg(pd_q), _arg(union_q), ctypes.byref(used),
+                                       _arg(d), _arg(h), ctypes.byref(bad))
         check(rc, tree_size=self.size, bad_id=int(bad.value))
         return pd_q, union_q, int(used.value), d, h
 

@@ -1,6 +1,7 @@
 // compare_plan.cpp -- see compare_plan.h.  Index arithmetic driven by caller-supplied parent arrays and link lists,
 // and the float64 folding of pieces: no GPU calls.
 #include "compare_plan.h"
+#include "plan_checks.h"
 
 #include <algorithm>
 #include <cmath>
@@ -39,12 +40,6 @@ void clade_merge(st_pair_moments &a, const st_pair_moments &b)
     a.max_x = std::fmax(a.max_x, b.max_x);
     a.min_y = std::fmin(a.min_y, b.min_y);
     a.max_y = std::fmax(a.max_y, b.max_y);
-}
-
-static int fail(int code, std::string &err, const std::string &msg)
-{
-    err = msg;
-    return code;
 }
 
 int compare_hist_args(const double *edges_x, int32_t bins_x, const double *edges_y, int32_t bins_y, const int64_t *out_hist,

@@ -1,18 +1,13 @@
 // dispersion_plan.cpp -- see dispersion_plan.h.  Argument checks and index arithmetic driven by caller-supplied positions,
 // and the restatement of the device reduction operation for operation: no GPU calls.
 #include "dispersion_plan.h"
+#include "plan_checks.h"
 
 #include <algorithm>
 #include <limits>
 #include <numeric>
 
 namespace st {
-
-static int fail(int code, std::string &err, const std::string &msg)
-{
-    err = msg;
-    return code;
-}
 
 int dispersion_plan(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets, int64_t permutations,
                     int32_t stream, int64_t chunk_tasks, DispersionPlan &P, std::string &err)
@@ -22,22 +17,9 @@ int dispersion_plan(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const
     if (permutations < 0) return fail(ST_ERR_ARG, err, "permutations < 0");
     if (chunk_tasks < 0) return fail(ST_ERR_ARG, err, "chunk_tasks < 0");
     if (stream < 0) return fail(ST_ERR_ARG, err, "stream < 0");
-    if (n_pos < 0 || n_sets < 0) return fail(ST_ERR_ARG, err, "negative size");
-    if (n_pos > INT32_MAX) return fail(ST_ERR_ARG, err, "more than 2^31 - 1 positions");
-    if ((n_sets > 0 && !sets) || (n_pos > 0 && !set_pos)) return fail(ST_ERR_ARG, err, "set_pos or sets is NULL");
     const int64_t R = permutations + 1;
     if (n_sets > 0 && R > ((int64_t)1 << 40) / n_sets) return fail(ST_ERR_ARG, err, "more than 2^40 records in one call");
-    for (int64_t r = 0; r < n_sets; r++) {
-        const int64_t b = sets[r], e = sets[r + 1];
-        if (b < 0 || e < b || e > n_pos)
-            return fail(ST_ERR_ARG, err, "set " + std::to_string(r) + ": offsets [" + std::to_string(b) + ", " + std::to_string(e) + ") of " +
-                                             std::to_string(n_pos) + " positions");
-        for (int64_t i = b; i < e; i++) {
-            if (set_pos[i] < 0 || set_pos[i] >= n_univ) return fail(ST_ERR_ARG, err, "set " + std::to_string(r) + ": a position outside the universe");
-            if (i > b && set_pos[i] <= set_pos[i - 1])
-                return fail(ST_ERR_ARG, err, "set " + std::to_string(r) + ": positions must be strictly increasing");
-        }
-    }
+    if (const int rc = position_sets_args(n_univ, set_pos, n_pos, sets, n_sets, err); rc != ST_OK) return rc;
     P = DispersionPlan{};
     P.n_univ = n_univ;
     P.n_sets = n_sets;

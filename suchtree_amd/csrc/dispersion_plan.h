@@ -64,8 +64,8 @@ struct DispersionPlan {
 };
 
 // ST_OK, or ST_ERR_ARG with `err`.  Checks, in this order: the universe size (3 .. kPermMaxUniverse), nothing negative
-// (permutations, chunk_tasks, stream, the counts), the offsets (sets[0 .. n_sets]: 0 <= sets[r] <= sets[r + 1] <= n_pos),
-// every set (positions inside the universe, strictly increasing).  Then the layout above: chunk_tasks 0 = blocks of up
+// (permutations, chunk_tasks, stream), at most 2^40 records, then the set table (position_sets_args, plan_checks.h: the
+// counts, NULL arrays, set by set its offsets and its positions).  Then the layout above: chunk_tasks 0 = blocks of up
 // to kDispersionSigmaBytes of sigma rows and chunks of kDispersionChunkTasks tasks; chunk_tasks > 0 = at most that many
 // tasks per chunk and permutations per block.
 int dispersion_plan(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets, int64_t permutations,

@@ -1,17 +1,12 @@
 // hommola_plan.cpp -- see hommola_plan.h.  Index arithmetic driven by caller-supplied positions and clade ranges and the
 // float64 folding of pieces: no GPU calls.
 #include "hommola_plan.h"
+#include "plan_checks.h"
 
 #include <algorithm>
 #include <numeric>
 
 namespace st {
-
-static int fail(int code, std::string &err, const std::string &msg)
-{
-    err = msg;
-    return code;
-}
 
 int hommola_plan(int32_t n_univ_o, int32_t n_univ_c, const int32_t *pos_o, const int32_t *pos_c, int64_t n_links,
                  const st_hommola_clade *clades, int64_t n_clades, int64_t permutations, int64_t chunk_blocks, HommolaPlan &P,

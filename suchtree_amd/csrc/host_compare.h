@@ -103,7 +103,7 @@ struct MomentsReduce {
     }
 };
 
-// What the chunk drivers (compare_run below, quartet_run, hommola_clades_run, partner_dispersion_run) share: both trees'
+// What the chunk drivers (compare_run below, quartet_run, hommola_clades_run, partner_dispersion_run, unifrac_tree_run) share: both trees'
 // pipe mutexes, one device block, one stream, the two host fault words.  Declared after ST_DEVICE(...) and after whatever
 // else its stream's work touches (device_res.h).  Both trees live on one device and so share its staging pipe and that
 // pipe's mutex (host_tree.h): one lock, also when tree_x == tree_y; distinct mutexes (not possible today) are taken in
@@ -129,6 +129,16 @@ struct TwoTreeSession {
         hipError_t e = s.create();
         if (e == hipSuccess) e = d.alloc(total);
         return e == hipSuccess ? ST_OK : hip_fail(" setup: ", e);
+    }
+    // the same where the block is what a call may fail to get: ST_ERR_NOMEM, "<what>: <noun> of <total> bytes<detail>: ..."
+    int open_or_nomem(size_t total, const char *noun, const std::string &detail = "")
+    {
+        hipError_t e = s.create();
+        if (e != hipSuccess) return hip_fail(" setup: ", e);
+        e = d.alloc(total);
+        if (e == hipSuccess) return ST_OK;
+        (void)hipGetLastError();
+        return fail(ST_ERR_NOMEM, std::string(what) + ": " + noun + " of " + std::to_string(total) + " bytes" + detail + ": " + hipGetErrorString(e));
     }
     // arms both fault words (behind what the caller has staged on the stream) ...
     int arm() { return begin_host_faults(tx, s) != ST_OK || (ty != tx && begin_host_faults(ty, s) != ST_OK) ? ST_ERR_HIP : ST_OK; }
@@ -165,6 +175,15 @@ struct ReadbackRing {
         for (int i = 0; i < 2 && e == hipSuccess; i++) e = ev[i].create(hipEventDisableTiming);
         return e;
     }
+    // the same as the status of the call `what`: a failed pinned buffer is ST_ERR_NOMEM with the bytes asked for, an event ST_ERR_HIP
+    int alloc(size_t count, const char *what)
+    {
+        const hipError_t e = alloc(count);
+        if (e == hipSuccess) return ST_OK;
+        if (h[0] && h[1]) return fail(ST_ERR_HIP, std::string(what) + " setup: " + hipGetErrorString(e));
+        (void)hipGetLastError();
+        return fail(ST_ERR_NOMEM, std::string(what) + ": a pinned buffer of " + std::to_string(count * sizeof(T)) + " bytes: " + hipGetErrorString(e));
+    }
     template <typename Use>
     hipError_t acquire(Use use)
     {
@@ -192,7 +211,21 @@ struct ReadbackRing {
         next ^= 1;
         return e == hipSuccess ? acquire(use) : e;
     }
+    // the tail of a chunk loop: flush(), then the stream drained
+    template <typename Use>
+    hipError_t drain(Use use, hipStream_t s) { const hipError_t e = flush(use); return e == hipSuccess ? hipStreamSynchronize(s) : e; }
 };
+
+// A work block of `total` bytes and the ring, of `count` elements a slot, that reads its results back, for the call `what`:
+// ST_OK, ST_ERR_NOMEM with the bytes asked for (the block, a pinned buffer) or ST_ERR_HIP (an event).
+template <typename T, typename Tag>
+static int alloc_work(DevBuf<char> &d, size_t total, ReadbackRing<T, Tag> &ring, size_t count, const char *what)
+{
+    const hipError_t e = d.alloc(total);
+    if (e == hipSuccess) return ring.alloc(count, what);
+    (void)hipGetLastError();
+    return fail(ST_ERR_NOMEM, std::string(what) + ": a work block of " + std::to_string(total) + " bytes: " + hipGetErrorString(e));
+}
 
 struct BlockSpan {      // the tag of a slot of pieces: global blocks [first, first + count)
     int64_t first, count;

@@ -61,22 +61,11 @@ static int dispersion_chunks(DevBuf<char> &d_work, DispersionRing &ring, const c
     const size_t rec_bytes = align256((size_t)P.max_chunk_tasks * sizeof(st_dispersion_record));
     const size_t o_rec = o_sigma + align256((size_t)P.perm_block * n * 2), total = o_rec + 2 * rec_bytes;
     auto hip_fail = [&](const char *step, hipError_t e) { return fail(ST_ERR_HIP, std::string(what) + step + hipGetErrorString(e)); };
-    hipError_t e = d_work.alloc(total);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ST_ERR_NOMEM, std::string(what) + ": a work block of " + std::to_string(total) + " bytes: " + hipGetErrorString(e));
-    }
-    e = ring.alloc((size_t)P.max_chunk_tasks);
-    if (e != hipSuccess && !(ring.h[0] && ring.h[1])) {
-        (void)hipGetLastError();
-        return fail(ST_ERR_NOMEM, std::string(what) + ": a pinned buffer of " + std::to_string((size_t)P.max_chunk_tasks * sizeof(st_dispersion_record)) +
-                                      " bytes: " + hipGetErrorString(e));
-    }
-    if (e != hipSuccess) return hip_fail(" setup: ", e);
+    if (const int rc = alloc_work(d_work, total, ring, (size_t)P.max_chunk_tasks, what); rc != ST_OK) return rc;
     std::fill_n(out, P.n_sets * P.rows, st_dispersion_record{0.0, 0.0});      // (every allocation has succeeded: from here on out is written)
     char *const d = d_work;
     st_dispersion_record *d_rec[2] = {reinterpret_cast<st_dispersion_record *>(d + o_rec), reinterpret_cast<st_dispersion_record *>(d + o_rec + rec_bytes)};
-    e = hipMemcpyAsync(d, set_pos, (size_t)n_pos * 4, hipMemcpyHostToDevice, s);
+    hipError_t e = hipMemcpyAsync(d, set_pos, (size_t)n_pos * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d + o_sets, P.sets.data(), live * sizeof(DispersionSetDev), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = perm_lds_opt_in(k_dispersion_sigma<kPermLargeThreads>, perm_lds_bytes((int)n));      // (above 32 KiB: the large class)
     if (e != hipSuccess) return hip_fail(" setup: ", e);
@@ -99,8 +88,7 @@ static int dispersion_chunks(DevBuf<char> &d_work, DispersionRing &ring, const c
         if (e == hipSuccess) e = ring.post(d_out, (size_t)c.n_tasks, &c, s);
         if (e != hipSuccess) return hip_fail(" launch: ", e);
     }
-    e = ring.flush(scatter);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    e = ring.drain(scatter, s);
     if (e != hipSuccess) return hip_fail(" read-back: ", e);
     return ST_OK;
 }
@@ -113,24 +101,18 @@ static int partner_dispersion_run(st_tree *t, const int64_t *univ, const Dispers
     DispersionRing ring;
     TwoTreeSession ses(t, t, "partner dispersion");
     const size_t n = (size_t)P.n_univ, o_univ = align256(n * n * 4), total = o_univ + align256(n * 8);
-    hipError_t e = ses.s.create();
-    if (e != hipSuccess) return ses.hip_fail(" setup: ", e);
-    e = ses.d.alloc(total);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ST_ERR_NOMEM, "partner dispersion: a distance matrix of " + std::to_string(total) + " bytes: " + hipGetErrorString(e));
-    }
+    int rc = ses.open_or_nomem(total, "a distance matrix");
+    if (rc != ST_OK) return rc;
     char *const d = ses.d;
     const hipStream_t s = ses.s;
     float *d_D = reinterpret_cast<float *>(d);
     long long *d_univ = reinterpret_cast<long long *>(d + o_univ);
-    e = hipMemcpyAsync(d_univ, univ, n * 8, hipMemcpyHostToDevice, s);
+    const hipError_t e = hipMemcpyAsync(d_univ, univ, n * 8, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return ses.hip_fail(" setup: ", e);
-    int rc = ses.arm();
+    rc = ses.arm();
     if (rc != ST_OK) return rc;
     // D[a][b] = dist(u[a], u[b]), the arguments in that order (not symmetric in the last bit)
-    rc = enqueue_src(t, SrcGrid{d_univ, d_univ, (long long)n, 0, 0}, (int64_t)(n * n), DistSink{nullptr, d_D}, MrcaSink{nullptr, nullptr},
-                     t->d_fault_host, s);
+    rc = enqueue_grid_dist(t, d_univ, d_univ, n, n * n, d_D, s);
     if (rc != ST_OK) return rc;
     rc = dispersion_chunks(d_work, ring, "partner dispersion", s, d_D, P, set_pos, n_pos, seed, stream, out);
     if (rc != ST_OK) return rc;

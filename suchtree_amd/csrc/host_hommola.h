@@ -34,36 +34,30 @@ static int hommola_clades_run(st_tree *to, st_tree *tc, const int64_t *univ_o, c
     const size_t o_rel = o_clade + align256(P.clades.size() * sizeof(HommolaCladeDev));
     const size_t piece_bytes = align256((size_t)P.max_chunk_blocks * sizeof(CladePiece));
     const size_t o_piece = o_rel + align256((size_t)P.max_chunk_rel * 4), total = o_piece + 2 * piece_bytes;
-    hipError_t e = ses.s.create();
-    if (e != hipSuccess) return ses.hip_fail(" setup: ", e);
-    e = ses.d.alloc(total);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ST_ERR_NOMEM, "hommola clades: one device block of " + std::to_string(total) + " bytes (" + std::to_string((size_t)P.mat_floats * 4) +
-                                      " of distance matrices): " + hipGetErrorString(e));
-    }
+    int rc = ses.open_or_nomem(total, "one device block", " (" + std::to_string((size_t)P.mat_floats * 4) + " of distance matrices)");
+    if (rc != ST_OK) return rc;
     char *const d = ses.d;
     const hipStream_t s = ses.s;
     float *d_mat = reinterpret_cast<float *>(d);
     long long *d_uo = reinterpret_cast<long long *>(d + o_uo), *d_uc = reinterpret_cast<long long *>(d + o_uc);
     const HommolaCladeDev *d_clade = reinterpret_cast<const HommolaCladeDev *>(d + o_clade);
     CladePiece *d_pieces[2] = {reinterpret_cast<CladePiece *>(d + o_piece), reinterpret_cast<CladePiece *>(d + o_piece + piece_bytes)};
-    e = ring.alloc((size_t)P.max_chunk_blocks);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_uo, univ_o, n_o * 8, hipMemcpyHostToDevice, s);
+    rc = ring.alloc((size_t)P.max_chunk_blocks, ses.what);
+    if (rc != ST_OK) return rc;
+    hipError_t e = hipMemcpyAsync(d_uo, univ_o, n_o * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_uc, univ_c, n_c * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d + o_po, pos_o, L * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d + o_pc, pos_c, L * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d + o_clade, P.clades.data(), P.clades.size() * sizeof(HommolaCladeDev), hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return ses.hip_fail(" setup: ", e);
-    int rc = ses.arm();
+    rc = ses.arm();
     if (rc != ST_OK) return rc;
     // the matrices: D[p][q] = dist(u[p], u[q]), the arguments in that order (not symmetric in the last bit)
-    rc = enqueue_src(to, SrcGrid{d_uo, d_uo, (long long)n_o, 0, 0}, (int64_t)(n_o * n_o), DistSink{nullptr, d_mat}, MrcaSink{nullptr, nullptr},
-                     to->d_fault_host, s);
+    rc = enqueue_grid_dist(to, d_uo, d_uo, n_o, n_o * n_o, d_mat, s);
     for (size_t r = 0; r < P.ranges.size() && rc == ST_OK; r++) {
         const HommolaRange &g = P.ranges[r];
-        rc = enqueue_src(tc, SrcGrid{d_uc + g.leaf_begin, d_uc + g.leaf_begin, (long long)g.leaf_count, 0, 0}, (int64_t)g.leaf_count * g.leaf_count,
-                         DistSink{nullptr, d_mat + g.mat_off}, MrcaSink{nullptr, nullptr}, tc->d_fault_host, s);
+        rc = enqueue_grid_dist(tc, d_uc + g.leaf_begin, d_uc + g.leaf_begin, (size_t)g.leaf_count, (size_t)g.leaf_count * g.leaf_count,
+                               d_mat + g.mat_off, s);
     }
     if (rc != ST_OK) return rc;
     int max_leaves = 1;
@@ -98,8 +92,7 @@ static int hommola_clades_run(st_tree *to, st_tree *tc, const int64_t *univ_o, c
         if (e == hipSuccess) e = ring.post(d_out, (size_t)ch.n_blocks, BlockSpan{ch.block_begin, ch.n_blocks}, s);
         if (e != hipSuccess) return ses.hip_fail(" launch: ", e);
     }
-    e = ring.flush(fold);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    e = ring.drain(fold, s);
     if (e != hipSuccess) return ses.hip_fail(" read-back: ", e);
     return ses.close(bad_id);
 }

@@ -60,6 +60,13 @@ static int enqueue(st_tree *t, const int64_t *d_pairs, int64_t n, int64_t s0, in
     return enqueue_src(t, SrcStrided{p, (long long)s0, (long long)s1}, n, d_out, d_mrca, t->d_fault, stream);
 }
 
+// float32 distances of a grid of ids into the device array `out`: entry k is dist(rows[k / n_cols], cols[k % n_cols]), the
+// arguments in that order (not symmetric in the last bit).  Faults go to the tree's host-path word.
+static int enqueue_grid_dist(st_tree *t, const long long *rows, const long long *cols, size_t n_cols, size_t count, float *out, hipStream_t s)
+{
+    return enqueue_src(t, SrcGrid{rows, cols, (long long)n_cols, 0, 0}, (int64_t)count, DistSink{nullptr, out}, MrcaSink{nullptr, nullptr}, t->d_fault_host, s);
+}
+
 // Copy a fault word back (synchronises `stream`) and re-arm it if it had fired.
 static int fetch_fault(Fault *d_word, hipStream_t stream, Fault &f)
 {

@@ -28,7 +28,7 @@ struct UnifracWork {      // declared before the stream's owner
     UnifracRing ring;
     size_t o_dq = 0, o_table = 0, o_pos = 0, o_sets = 0, o_heavy = 0, o_out = 0, out_bytes = 0, total = 0;
 
-    // ST_OK, or ST_ERR_NOMEM with the bytes asked for
+    // the status of alloc_work (host_compare.h): ST_ERR_NOMEM with the bytes asked for
     int alloc(const UnifracPlan &P, int64_t n_pos, const char *what)
     {
         o_dq = 256;      // (the counter has the block's first bytes)
@@ -39,18 +39,7 @@ struct UnifracWork {      // declared before the stream's owner
         o_out = o_heavy + align256((size_t)P.max_chunk * 4);
         out_bytes = align256((size_t)P.max_chunk * 8);
         total = o_out + 2 * out_bytes;
-        hipError_t e = d.alloc(total);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ST_ERR_NOMEM, std::string(what) + ": a work block of " + std::to_string(total) + " bytes: " + hipGetErrorString(e));
-        }
-        e = ring.alloc((size_t)P.max_chunk);
-        if (e != hipSuccess && !(ring.h[0] && ring.h[1])) {
-            (void)hipGetLastError();
-            return fail(ST_ERR_NOMEM, std::string(what) + ": a pinned buffer of " + std::to_string((size_t)P.max_chunk * 8) + " bytes: " + hipGetErrorString(e));
-        }
-        if (e != hipSuccess) return fail(ST_ERR_HIP, std::string(what) + " setup: " + hipGetErrorString(e));
-        return ST_OK;
+        return alloc_work(d, total, ring, (size_t)P.max_chunk, what);
     }
 };
 
@@ -100,8 +89,7 @@ static int unifrac_chunks(UnifracWork &W, const char *what, hipStream_t s, const
         if (e == hipSuccess) e = W.ring.post(out, (size_t)c.count, &c, s);
         if (e != hipSuccess) return hip_fail(" launch: ", e);
     }
-    e = W.ring.flush(deliver);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    e = W.ring.drain(deliver, s);
     if (e != hipSuccess) return hip_fail(" read-back: ", e);
     return ST_OK;
 }
@@ -131,15 +119,10 @@ static int unifrac_tree_run(st_tree *t, int64_t root, const int64_t *univ, const
     // the depth block: root | universe | d | MRCA ids of adjacent leaves, as int32 and as int64 | h
     const size_t o_univ = 256, o_d = o_univ + align256(n * 8), o_m32 = o_d + align256(n * 4), o_m64 = o_m32 + align256(m * 4);
     const size_t o_h = o_m64 + align256(m * 8), total = o_h + align256(m * 4);
-    hipError_t e = ses.s.create();
-    if (e != hipSuccess) return ses.hip_fail(" setup: ", e);
-    e = ses.d.alloc(total);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ST_ERR_NOMEM, "unifrac: a depth block of " + std::to_string(total) + " bytes: " + hipGetErrorString(e));
-    }
-    if (!P.chunks.empty())
-        if (const int rc = W.alloc(P, n_pos, "unifrac"); rc != ST_OK) return rc;
+    int rc = ses.open_or_nomem(total, "a depth block");
+    if (rc != ST_OK) return rc;
+    if (!P.chunks.empty()) rc = W.alloc(P, n_pos, "unifrac");
+    if (rc != ST_OK) return rc;
     char *const d = ses.d;
     const hipStream_t s = ses.s;
     long long *d_root = reinterpret_cast<long long *>(d), *d_univ = reinterpret_cast<long long *>(d + o_univ);
@@ -147,13 +130,13 @@ static int unifrac_tree_run(st_tree *t, int64_t root, const int64_t *univ, const
     int *d_m32 = reinterpret_cast<int *>(d + o_m32);
     float *d_d = reinterpret_cast<float *>(d + o_d), *d_h = reinterpret_cast<float *>(d + o_h);
     const long long root_id = root;
-    e = hipMemcpyAsync(d_root, &root_id, 8, hipMemcpyHostToDevice, s);
+    hipError_t e = hipMemcpyAsync(d_root, &root_id, 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_univ, univ, n * 8, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return ses.hip_fail(" setup: ", e);
-    int rc = ses.arm();
+    rc = ses.arm();
     if (rc != ST_OK) return rc;
     // d[k] = dist(root, u[k]), the arguments in that order: a 1 x n grid
-    rc = enqueue_src(t, SrcGrid{d_root, d_univ, (long long)n, 0, 0}, (int64_t)n, DistSink{nullptr, d_d}, MrcaSink{nullptr, nullptr}, t->d_fault_host, s);
+    rc = enqueue_grid_dist(t, d_root, d_univ, n, n, d_d, s);
     if (rc != ST_OK) return rc;
     if (m > 0) {      // h[k] = dist(root, mrca(u[k], u[k + 1])): the pairs are the universe read with stride one
         rc = enqueue_src(t, SrcStrided{d_univ, 1, 1}, (int64_t)m, DistSink{nullptr, nullptr}, MrcaSink{d_m32, nullptr}, t->d_fault_host, s);
@@ -162,7 +145,7 @@ static int unifrac_tree_run(st_tree *t, int64_t root, const int64_t *univ, const
                            (long long)m);
         e = hipGetLastError();
         if (e != hipSuccess) return ses.hip_fail(" launch: ", e);
-        rc = enqueue_src(t, SrcGrid{d_root, d_m64, (long long)m, 0, 0}, (int64_t)m, DistSink{nullptr, d_h}, MrcaSink{nullptr, nullptr}, t->d_fault_host, s);
+        rc = enqueue_grid_dist(t, d_root, d_m64, m, m, d_h, s);
         if (rc != ST_OK) return rc;
         e = hipMemcpyAsync(h_h.data(), d_h, m * 4, hipMemcpyDeviceToHost, s);
     }

@@ -32,7 +32,8 @@
 // pairs, reduced on the device): kernels_compare.h / kernels_clades.h / kernels_rows.h (moments and 2-D histogram, clade
 // pieces, row blocks), host_compare.h (TwoTreeSession, ReadbackRing, the chunk driver compare_run and its reducers, the pair
 // inputs, statistics and the one skeleton, compare_entry, of the triangle / pairs entry points) and,
-// host-only C++ beside tree_prep.cpp, compare_plan.cpp (argument checks, clade plan and tables, rows layout, the fold).
+// host-only C++ beside tree_prep.cpp, compare_plan.cpp (argument checks, clade plan and tables, rows layout, the fold);
+// plan_checks.h is what the plan units share in their checks (how one fails, a table of position sets).
 // Exact Spearman rank sums of the same pairs (st_compare_*_ranks_host): kernels_ranks.h, the reducers at the end of
 // host_compare.h and, host-only, rank_plan.cpp (keys, bucket layout, tie arithmetic, st_spearman_host).
 // Exact Kendall tau-b counts of the same pairs (st_compare_*_kendall_host, st_kendall_arrays_host): kernels_kendall.h (keys,
@@ -148,6 +149,9 @@ private:
     DeviceScope device_scope_(dev);                                                        \
     if (device_scope_.error() != hipSuccess)                                               \
         return fail(ST_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(device_scope_.error()))
+
+// the `device` of a call that also has a host form
+static int device_or_host_arg(int device) { return device < -1 ? fail(ST_ERR_ARG, "device must be -1 (host) or a device index") : ST_OK; }
 
 static int device_index_arg(int device)
 {
@@ -1214,7 +1218,7 @@ try {
     std::string err;
     const int rc = quartet_range_args(mode, m, k_begin, k_count, err);
     if (rc != ST_OK) return fail(rc, err);
-    if (device < -1) return fail(ST_ERR_ARG, "device must be -1 (host) or a device index");
+    if (device_or_host_arg(device) != ST_OK) return ST_ERR_ARG;
     if (k_count > 0 && !out_pos) return fail(ST_ERR_ARG, "out_pos is NULL");
     if (k_count == 0) return ST_OK;
     if (device < 0) {
@@ -1267,7 +1271,7 @@ try {
     std::string err;
     const int rc = perm_args(node, p, side, n, err);
     if (rc != ST_OK) return fail(rc, err);
-    if (device < -1) return fail(ST_ERR_ARG, "device must be -1 (host) or a device index");
+    if (device_or_host_arg(device) != ST_OK) return ST_ERR_ARG;
     if (!out) return fail(ST_ERR_ARG, "out is NULL");
     if (device < 0) {
         perm_host(seed, node, p, side, n, out);
@@ -1323,7 +1327,7 @@ try {
     std::string err;
     const int rc = dispersion_plan(n, set_pos, n_pos, sets, n_sets, permutations, stream, chunk_tasks, P, err);
     if (rc != ST_OK) return fail(rc, err);
-    if (device < -1) return fail(ST_ERR_ARG, "device must be -1 (host) or a device index");
+    if (device_or_host_arg(device) != ST_OK) return ST_ERR_ARG;
     if (!D) return fail(ST_ERR_ARG, "D is NULL");
     if (n_sets > 0 && !out) return fail(ST_ERR_ARG, "out is NULL");
     if (device < 0 || P.chunks.empty()) {
@@ -1348,7 +1352,7 @@ try {
     int rc = unifrac_plan(n, set_pos, n_pos, sets, n_sets, k_begin, k_count, chunk_pairs, out_pd != nullptr, out_union != nullptr, P, err);
     if (rc == ST_OK) rc = unifrac_depth_args(d_q, h_q, n, err);
     if (rc != ST_OK) return fail(rc, err);
-    if (device < -1) return fail(ST_ERR_ARG, "device must be -1 (host) or a device index");
+    if (device_or_host_arg(device) != ST_OK) return ST_ERR_ARG;
     if (P.chunks.empty()) return ST_OK;      // (no sets, an empty range or no output: nothing to launch)
     if (device < 0) {
         unifrac_host(d_q, h_q, P, set_pos, sets, out_pd, out_union);

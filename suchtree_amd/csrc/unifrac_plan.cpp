@@ -1,17 +1,12 @@
 // unifrac_plan.cpp -- see unifrac_plan.h.  Argument checks, the quantiser, the chunk cut and the restatement of the device
 // reduction: no GPU calls.
 #include "unifrac_plan.h"
+#include "plan_checks.h"
 
 #include <algorithm>
 #include <cmath>
 
 namespace st {
-
-static int fail(int code, std::string &err, const std::string &msg)
-{
-    err = msg;
-    return code;
-}
 
 static int universe_arg(int32_t n, std::string &err)
 {
@@ -25,22 +20,9 @@ int unifrac_plan(int32_t n, const int32_t *set_pos, int64_t n_pos, const int64_t
 {
     if (const int rc = universe_arg(n, err); rc != ST_OK) return rc;
     if (chunk_pairs < 0) return fail(ST_ERR_ARG, err, "chunk_pairs < 0");
-    if (n_pos < 0 || n_sets < 0) return fail(ST_ERR_ARG, err, "negative size");
     if (k_begin < 0 || k_count < 0) return fail(ST_ERR_ARG, err, "a negative triangle range");
-    if (n_pos > INT32_MAX) return fail(ST_ERR_ARG, err, "more than 2^31 - 1 positions");
     if (n_sets > ((int64_t)1 << 30)) return fail(ST_ERR_ARG, err, "more than 2^30 sets");
-    if ((n_sets > 0 && !sets) || (n_pos > 0 && !set_pos)) return fail(ST_ERR_ARG, err, "set_pos or sets is NULL");
-    for (int64_t r = 0; r < n_sets; r++) {
-        const int64_t b = sets[r], e = sets[r + 1];
-        if (b < 0 || e < b || e > n_pos)
-            return fail(ST_ERR_ARG, err, "set " + std::to_string(r) + ": offsets [" + std::to_string(b) + ", " + std::to_string(e) + ") of " +
-                                             std::to_string(n_pos) + " positions");
-        for (int64_t i = b; i < e; i++) {
-            if (set_pos[i] < 0 || set_pos[i] >= n) return fail(ST_ERR_ARG, err, "set " + std::to_string(r) + ": a position outside the universe");
-            if (i > b && set_pos[i] <= set_pos[i - 1])
-                return fail(ST_ERR_ARG, err, "set " + std::to_string(r) + ": positions must be strictly increasing");
-        }
-    }
+    if (const int rc = position_sets_args(n, set_pos, n_pos, sets, n_sets, err); rc != ST_OK) return rc;
     const int64_t total = n_sets > 0 ? n_sets * (n_sets - 1) / 2 : 0;
     if (k_begin > total || k_count > total - k_begin)
         return fail(ST_ERR_ARG, err, "pairs [" + std::to_string(k_begin) + ", +" + std::to_string(k_count) + ") of a triangle of " +

@@ -88,9 +88,9 @@ struct UnifracPlan {
 };
 
 // ST_OK, or ST_ERR_ARG with `err`.  Checks, in this order: the universe size (1 .. kUnifracMaxUniverse), nothing negative
-// (chunk_pairs, the counts, the range), NULL arrays, the offsets (sets[0 .. n_sets]: 0 <= sets[r] <= sets[r + 1] <= n_pos),
-// every set (positions inside the universe, strictly increasing), the range inside the triangle of n_sets (n_sets - 1) / 2
-// pairs.  Then the layout above: PD chunks if want_pd, pair chunks if want_union; chunk_pairs 0 = kUnifracChunkPairs.
+// (chunk_pairs, the range), at most 2^30 sets, the set table (position_sets_args, plan_checks.h: the counts, NULL arrays,
+// set by set its offsets and its positions), the range inside the triangle of n_sets (n_sets - 1) / 2 pairs.  Then the
+// layout above: PD chunks if want_pd, pair chunks if want_union; chunk_pairs 0 = kUnifracChunkPairs.
 int unifrac_plan(int32_t n, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets, int64_t k_begin, int64_t k_count,
                  int64_t chunk_pairs, bool want_pd, bool want_union, UnifracPlan &P, std::string &err);
 

@@ -14,7 +14,7 @@ from typing import Dict
 import numpy as np
 
 from . import _capi
-from .suchtree import SuchTree
+from .suchtree import SuchTree, int_arg, seed_arg
 
 
 class SuchLinkedTrees:
@@ -327,11 +327,8 @@ class SuchLinkedTrees:
         An extension: the reference has no counterpart (its notebook samples instead).
         """
         import math
-        import numbers
         from . import compare
-        if isinstance(permutations, bool) or not isinstance(permutations, numbers.Integral) or permutations < 0:
-            raise ValueError("permutations must be a non-negative integer, got %r" % (permutations,))
-        permutations = int(permutations)
+        permutations = int_arg("permutations", permutations)
         ll = np.ascontiguousarray(self.linklist, dtype=np.int64)
         L = int(ll.shape[0])
         if L < 3:
@@ -397,21 +394,13 @@ class SuchLinkedTrees:
         Returns a :class:`~suchtree_amd.compare.CladeHommola`.  An extension: the reference has no counterpart (its
         notebook loops ``subset_b`` over the clades and keeps ``pearsonr``'s parametric p).
         """
-        import numbers
         from . import compare
         if tree not in ("A", "B"):
             raise ValueError("tree must be 'A' or 'B'")
-        if isinstance(permutations, bool) or not isinstance(permutations, numbers.Integral) or permutations < 0:
-            raise ValueError("permutations must be a non-negative integer, got %r" % (permutations,))
-        permutations = int(permutations)
+        permutations = int_arg("permutations", permutations)
         limit = _capi.HOMMOLA_MAX_UNIVERSE
-        if isinstance(max_leaves, bool) or not isinstance(max_leaves, numbers.Integral) or max_leaves < 0 or max_leaves > limit:
-            raise ValueError("max_leaves must be an integer from 0 to %d, got %r" % (limit, max_leaves))
-        if seed is None:
-            seed = int(np.random.SeedSequence().generate_state(1, np.uint64)[0])
-        if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or not 0 <= seed < 1 << 64:
-            raise ValueError("seed must be an integer from 0 to 2^64 - 1, got %r" % (seed,))
-        seed = int(seed)
+        max_leaves = int_arg("max_leaves", max_leaves, limit)
+        seed = seed_arg(seed)
         A, B = self._tree_a, self._tree_b
         if tree == "B":
             col_of = np.full(B.size, -1, dtype=np.int64)
@@ -532,24 +521,33 @@ class SuchLinkedTrees:
         Returns a :class:`~suchtree_amd.compare.SetDispersion` with ``leaves`` (the rows' leaf ids) and ``names``.
         An extension: the reference has no counterpart.
         """
-        import numbers
+        def run(partner, sets, root, universe):
+            return partner.dispersion(sets, universe=universe, permutations=permutations, seed=seed, stream=root, keep_null=keep_null)
+        return self._over_partner_rows(of, min_partners, max_partners, run, pool, _capi.HOMMOLA_MAX_UNIVERSE)
+
+    def _over_partner_rows(self, of, min_partners, max_partners, run, pool="subset", pool_limit=None):
+        """What partner_dispersion and partner_unifrac share: the checks of ``of``, ``pool`` and the partner counts, the rows
+        (_partner_rows), ``run(partner tree, the rows' partner ids, partner subset root, universe)``, then the result's
+        ``leaves`` and ``names``.  With ``pool_limit`` the universe is ``pool`` of the partner tree -- "subset" = every leaf
+        of its current subset, "linked" = those with a link in it -- of at most that many leaves; without, it is None."""
         if of not in ("A", "B"):
             raise ValueError("of must be 'A' or 'B'")
         if pool not in ("subset", "linked"):
             raise ValueError("pool must be 'subset' or 'linked'")
-        for name, v in (("min_partners", min_partners), ("max_partners", max_partners)):
-            if v is not None and (isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 0):
-                raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
+        min_partners = int_arg("min_partners", min_partners, optional=True)
+        max_partners = int_arg("max_partners", max_partners, optional=True)
         ll = np.ascontiguousarray(self.linklist, dtype=np.int64)
-        if pool == "subset":
-            universe = np.asarray(self._subset_b_leafs if of == "A" else self._subset_a_leafs, dtype=np.int64)
-        else:
-            universe = np.unique(ll[:, 0 if of == "A" else 1])
-        if len(universe) > _capi.HOMMOLA_MAX_UNIVERSE:      # (before the rows are built)
-            raise ValueError("the partner tree's %s has %d leaves: at most %d (subset it first)"
-                             % ("subset" if pool == "subset" else "linked leaves", len(universe), _capi.HOMMOLA_MAX_UNIVERSE))
+        universe = None
+        if pool_limit is not None:
+            if pool == "subset":
+                universe = np.asarray(self._subset_b_leafs if of == "A" else self._subset_a_leafs, dtype=np.int64)
+            else:
+                universe = np.unique(ll[:, 0 if of == "A" else 1])
+            if len(universe) > pool_limit:      # (before the rows are built)
+                raise ValueError("the partner tree's %s has %d leaves: at most %d (subset it first)"
+                                 % ("subset" if pool == "subset" else "linked leaves", len(universe), pool_limit))
         own, partner, root, leaves, sets = self._partner_rows(of, min_partners, max_partners, ll)
-        out = partner.dispersion(sets, universe=universe, permutations=permutations, seed=seed, stream=int(root), keep_null=keep_null)
+        out = run(partner, sets, root, universe)
         out.leaves = np.asarray(leaves, dtype=np.int64)
         names = own.leaf_nodes
         out.names = [names[int(v)] for v in leaves]
@@ -596,18 +594,8 @@ class SuchLinkedTrees:
         Returns a :class:`~suchtree_amd.compare.SetUniFrac` with ``leaves`` (the rows' leaf ids), ``names`` and ``root``.
         An extension: the reference has no counterpart.
         """
-        import numbers
-        if of not in ("A", "B"):
-            raise ValueError("of must be 'A' or 'B'")
-        for name, v in (("min_partners", min_partners), ("max_partners", max_partners)):
-            if v is not None and (isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 0):
-                raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
-        own, partner, root, leaves, sets = self._partner_rows(of, min_partners, max_partners)
-        out = partner.unifrac(sets, root=root, begin=begin, count=count, shift=shift)
-        out.leaves = np.asarray(leaves, dtype=np.int64)
-        names = own.leaf_nodes
-        out.names = [names[int(v)] for v in leaves]
-        return out
+        return self._over_partner_rows(of, min_partners, max_partners,
+                                       lambda partner, sets, root, _: partner.unifrac(sets, root=root, begin=begin, count=count, shift=shift))
 
     @staticmethod
     def _leaf_counts(tree: SuchTree) -> np.ndarray:

@@ -55,6 +55,25 @@ def _deprecation_warning(old_name: str, new_name: str, version: str = "2.0") -> 
     )
 
 
+def int_arg(name, v, top=None, top_text=None, optional=False):
+    """The argument ``v`` as an int: a non-negative integer (no bool), at most ``top`` where one is given (``top_text``
+    words it in the message); None passes where ``optional``.  ValueError otherwise."""
+    if v is None and optional:
+        return None
+    if isinstance(v, bool) or not isinstance(v, Integral) or v < 0 or (top is not None and v > top):
+        if top is None:
+            raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
+        raise ValueError("%s must be an integer from 0 to %s, got %r" % (name, top_text or top, v))
+    return int(v)
+
+
+def seed_arg(seed):
+    """A 64-bit seed: the caller's, or a fresh draw where it is None."""
+    if seed is None:
+        seed = int(np.random.SeedSequence().generate_state(1, np.uint64)[0])
+    return int_arg("seed", seed, (1 << 64) - 1, "2^64 - 1")
+
+
 class SuchTree(TreeNavigation):
     """Immutable phylogenetic tree resident in GPU memory.
 
@@ -550,6 +569,16 @@ class SuchTree(TreeNavigation):
                 out[i] = int(v)
         return out
 
+    def _position_table(self, univ, rows):
+        """(set_pos int32, offsets int64): every set of ``rows`` (leaf ids, all of them in ``univ``) as increasing positions
+        of ``univ``, one set behind the other; set r is set_pos[offsets[r]:offsets[r + 1]]."""
+        where = np.full(self.size, -1, dtype=np.int64)
+        where[univ] = np.arange(len(univ))
+        pos = [np.sort(where[ids]).astype(np.int32) for ids in rows]
+        offsets = np.zeros(len(rows) + 1, dtype=np.int64)
+        np.cumsum(np.array([len(p) for p in pos], dtype=np.int64), out=offsets[1:])
+        return (np.concatenate(pos) if pos else np.empty(0, dtype=np.int32)), offsets
+
     def dispersion(self, sets, universe=None, permutations=999, seed=None, stream=0, keep_null=False, chunk_tasks=0):
         """How closely related are the members of each set of leaves: MPD and MNTD with a permutation null, on the GPU.
 
@@ -569,17 +598,9 @@ class SuchTree(TreeNavigation):
         Returns a :class:`~suchtree_amd.compare.SetDispersion`.  An extension: the reference has no counterpart.
         """
         from . import compare
-        if isinstance(permutations, bool) or not isinstance(permutations, Integral) or permutations < 0:
-            raise ValueError("permutations must be a non-negative integer, got %r" % (permutations,))
-        if seed is None:
-            seed = int(np.random.SeedSequence().generate_state(1, np.uint64)[0])
-        if isinstance(seed, bool) or not isinstance(seed, Integral) or not 0 <= seed < 1 << 64:
-            raise ValueError("seed must be an integer from 0 to 2^64 - 1, got %r" % (seed,))
-        if isinstance(stream, bool) or not isinstance(stream, Integral) or not 0 <= stream < 1 << 31:
-            raise ValueError("stream must be an integer from 0 to 2^31 - 1, got %r" % (stream,))
-        if isinstance(chunk_tasks, bool) or not isinstance(chunk_tasks, Integral) or chunk_tasks < 0:
-            raise ValueError("chunk_tasks must be a non-negative integer, got %r" % (chunk_tasks,))
-        permutations, seed = int(permutations), int(seed)
+        permutations, seed = int_arg("permutations", permutations), seed_arg(seed)
+        stream = int_arg("stream", stream, (1 << 31) - 1, "2^31 - 1")
+        chunk_tasks = int_arg("chunk_tasks", chunk_tasks)
         univ = self._depth_first_leaves()
         if universe is not None:
             inside = np.zeros(self.size, dtype=bool)
@@ -590,26 +611,24 @@ class SuchTree(TreeNavigation):
             raise ValueError("the universe has %d leaves: at least 3" % len(univ))
         if len(univ) > limit:
             raise ValueError("the universe has %d leaves: at most %d (subset it first)" % (len(univ), limit))
-        where = np.full(self.size, -1, dtype=np.int64)
-        where[univ] = np.arange(len(univ))
+        inside = np.zeros(self.size, dtype=bool)
+        inside[univ] = True
         rows = []
         for r, members in enumerate(sets):
-            pos = np.sort(where[self._leaf_ids(members, "set %d" % r)])
-            if len(pos) and pos[0] < 0:
+            ids = self._leaf_ids(members, "set %d" % r)
+            if not inside[ids].all():
                 raise ValueError("set %d: a member outside the universe" % r)
-            if np.any(pos[1:] == pos[:-1]):
+            if len(np.unique(ids)) != len(ids):
                 raise ValueError("set %d: a repeated member" % r)
-            rows.append(pos.astype(np.int32))
-        k = np.array([len(p) for p in rows], dtype=np.int64)
-        offsets = np.zeros(len(rows) + 1, dtype=np.int64)
-        np.cumsum(k, out=offsets[1:])
-        set_pos = np.concatenate(rows) if rows else np.empty(0, dtype=np.int32)
+            rows.append(ids)
+        set_pos, offsets = self._position_table(univ, rows)
+        k = np.diff(offsets)
         out = compare.SetDispersion(len(rows), permutations, seed, len(univ), keep_null)
         per_group = max(1, self._DISPERSION_GROUP_ROWS // (permutations + 1))
         for at in range(0, len(rows), per_group):      # (no sets: nothing is launched, and the tree stays where it is)
             end = min(at + per_group, len(rows))
             part = (set_pos[offsets[at]:offsets[end]], offsets[at:end + 1] - offsets[at])
-            rec = self._device_tree().partner_dispersion_host(univ, part, permutations, seed, int(stream), int(chunk_tasks))
+            rec = self._device_tree().partner_dispersion_host(univ, part, permutations, seed, stream, chunk_tasks)
             out.fill(at, k[at:end], rec)      # (each group is reduced before the next)
         return out
 
@@ -631,9 +650,8 @@ class SuchTree(TreeNavigation):
         reference has no counterpart.
         """
         from . import compare
-        for name, v in (("begin", begin), ("count", count), ("shift", shift), ("chunk_pairs", chunk_pairs)):
-            if (v is not None or name in ("begin", "chunk_pairs")) and (isinstance(v, bool) or not isinstance(v, Integral) or v < 0):
-                raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
+        begin, count = int_arg("begin", begin), int_arg("count", count, optional=True)
+        shift, chunk_pairs = int_arg("shift", shift, optional=True), int_arg("chunk_pairs", chunk_pairs)
         root = self.root_node if root is None else self._validate_node(root)
         leaf_ids = np.flatnonzero(np.asarray(self._flat.left) == -1).astype(np.int64)
         plan = _capi.clade_plan(self._flat.parent, leaf_ids)      # (one link per leaf: _depth_first_leaves, and every node's range of it)
@@ -659,16 +677,10 @@ class SuchTree(TreeNavigation):
                 raise ValueError("the whole triangle of %d sets is %d pairs, more than 2^31: ask for ranges with begin= and count=" % (len(rows), total))
         if begin + count > total or count < 0:
             raise ValueError("pairs [%d, +%d) of a triangle of %d" % (begin, count, total))
-        where = np.full(self.size, -1, dtype=np.int64)
-        where[univ] = np.arange(len(univ))
-        pos = [np.sort(where[ids]).astype(np.int32) for ids in rows]
-        offsets = np.zeros(len(rows) + 1, dtype=np.int64)
-        np.cumsum([len(p) for p in pos], out=offsets[1:])
-        set_pos = np.concatenate(pos) if pos else np.empty(0, dtype=np.int32)
         if not len(univ):      # (no member at all: nothing is launched, and the tree stays where it is)
             out = compare.SetUniFrac(len(rows), begin, shift or 0, np.zeros(len(rows), dtype=np.int64), np.zeros(count, dtype=np.int64), root)
         else:
-            pd_q, union_q, used, _, _ = self._device_tree().unifrac_host(root, univ, (set_pos.astype(np.int32), offsets), begin, count, shift,
+            pd_q, union_q, used, _, _ = self._device_tree().unifrac_host(root, univ, self._position_table(univ, rows), begin, count, shift,
                                                                          chunk_pairs)
             out = compare.SetUniFrac(len(rows), begin, used, pd_q, union_q, root)
         return out

@@ -2,6 +2,7 @@
 // AddressSanitizer + UBSan (tests/test_unifrac_host.py builds this with -fsanitize=address,undefined): the range-minimum
 // table at n = 1, 2, 3 and 2^k +- 1 against a plain minimum, the pair order, chunk cuts that tile the tasks once, the merge
 // and the successor form on their edges against a sum over distinct positions, the quantiser, and every argument error.
+// Malformed set tables go to dispersion_plan as well: the two plans share that check (plan_checks.h) and word it alike.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -10,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "../../suchtree_amd/csrc/dispersion_plan.cpp"      // (compiled in here: the program is linked with unifrac_plan.cpp alone)
 #include "../../suchtree_amd/csrc/unifrac_plan.h"
 
 using namespace st;
@@ -247,6 +249,40 @@ int main()
         CHECK(unifrac_plan(40, good.pos.data(), 3, nullptr, 1, 0, 0, 0, true, true, P, err) == ST_ERR_ARG);
         CHECK(unifrac_plan(40, nullptr, 0, nullptr, -1, 0, 0, 0, true, true, P, err) == ST_ERR_ARG);
         CHECK(unifrac_plan(40, nullptr, 0, nullptr, 0, 0, 0, 0, true, true, P, err) == ST_OK && P.chunks.empty());
+    }
+    // malformed set tables over a universe of 3: both plans refuse each, in the same words
+    {
+        struct Bad {
+            const char *what;
+            std::vector<int32_t> pos;
+            std::vector<int64_t> off;
+            bool null_pos, null_off;
+        };
+        const Bad table[] = {
+            {"a negative offset", {0, 1}, {-1, 2}, false, false},
+            {"a decreasing offset", {0, 1}, {0, 2, 1}, false, false},
+            {"an offset past n_pos", {0, 1}, {0, 3}, false, false},
+            {"a position -1", {-1, 1}, {0, 2}, false, false},
+            {"a position equal to n", {0, 3}, {0, 2}, false, false},
+            {"a repeated position", {1, 1}, {0, 2}, false, false},
+            {"a decreasing position", {2, 1}, {0, 2}, false, false},
+            {"NULL sets with n_sets = 1", {0}, {0, 1}, false, true},
+            {"NULL set_pos with n_pos = 1", {0}, {0, 1}, true, false},
+        };
+        for (const Bad &b : table) {
+            const int32_t *pos = b.null_pos ? nullptr : b.pos.data();
+            const int64_t *off = b.null_off ? nullptr : b.off.data();
+            const int64_t n_pos = (int64_t)b.pos.size(), n_sets = (int64_t)b.off.size() - 1;
+            std::string err_d, err_u;
+            DispersionPlan D;
+            UnifracPlan U;
+            const int rc_d = dispersion_plan(3, pos, n_pos, off, n_sets, 5, 0, 0, D, err_d);
+            const int rc_u = unifrac_plan(3, pos, n_pos, off, n_sets, 0, 0, 0, true, true, U, err_u);
+            if (rc_d != ST_ERR_ARG || rc_u != ST_ERR_ARG || err_d.empty() || err_d != err_u) {
+                std::printf("FAILED %s: dispersion_plan %d \"%s\", unifrac_plan %d \"%s\"\n", b.what, rc_d, err_d.c_str(), rc_u, err_u.c_str());
+                return 1;
+            }
+        }
     }
     std::printf("sanitize unifrac ok\n");
     return 0;
