@@ -48,7 +48,8 @@ extern "C" {
  *      st_kendall_arrays_host and st_kendall_host; then, also additive, struct st_hommola_clade, ST_HOMMOLA_MAX_UNIVERSE,
  *      st_hommola_permutation and st_hommola_clades_host; then, also additive, struct st_dispersion_record,
  *      st_partner_dispersion_host and st_dispersion_matrix; then, also additive, ST_UNIFRAC_MAX_UNIVERSE,
- *      ST_UNIFRAC_LANE_MAX, st_unifrac_host, st_unifrac_depths and st_unifrac_quantise.
+ *      ST_UNIFRAC_LANE_MAX, st_unifrac_host, st_unifrac_depths and st_unifrac_quantise; then st_tree_info.heap_codes appended
+ *      (8 bytes) with option "heap_codes", as heap_lines was.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -104,6 +105,9 @@ typedef struct st_tree_info {
                                  leaf, so a_side_bytes and b_table_bytes_per_leaf are 4 and 4 while it is set; else 0 */
     int64_t stream_hint;      /* 1 = large explicit pair batches with distances from and to device buffers (st_distances_device*) currently
                                  read their pairs and write their results with the non-temporal hint (option "stream_hint"); else 0 */
+    int64_t heap_codes;       /* 1 = large ones of those batches currently take the heap-code form of that kernel (option "heap_codes"): the same edges as
+                                 20-bit codes, 24 leaves per 128-byte line.  heap_lines, a_side_bytes, b_table_bytes_per_leaf and
+                                 stream_hint report what they report without it; else 0 */
 } st_tree_info;
 
 /* st_tree_info.dropped_tables, in the order in which a table budget (st_tree_options.table_budget_bytes, else
@@ -827,6 +831,13 @@ int st_tree_set_strategy(st_tree *tree, int strategy);
  * ids, MRCAs and meeting depths by arithmetic (the same bits).  1 (default) = on trees of 2^17 leaves and more (at 2^16 the
  * tables above are still ahead); 2 = wherever the tables exist; 0 = never.  st_tree_info.heap_lines
  * follows.  Under a table budget these tables are the first to go.
+ * "heap_codes": where every edge length of such a tree is a six-decimal number below 1.048576 (a Newick file with six decimals)
+ * the six lowest levels are also kept as 20-bit integer codes, 24 leaves per 128-byte line -- two thirds of the heap lines'
+ * footprint; every edge is verified to decode to its own bits, else the table is not built.  The batches that take the heap-line
+ * form then read it instead (the same bits).  1 (default) = batches of 2^24 pairs and more on trees of 2^19 leaves and more; 2 = wherever the table exists
+ * and "heap_lines" admits the heap-line form; 0 = never.  "heap_lines" 0 turns both forms off.  st_tree_info.heap_codes
+ * follows; heap_lines, a_side_bytes, b_table_bytes_per_leaf and stream_hint report what they report without it.  Under a
+ * table budget this table goes before the heap lines.
  * "stream_hint": the pair array and the result arrays of a launch are read once and written once; with the hint the kernel
  * reads and writes them non-temporally, so that they do not push the tables it gathers from out of L2 (the same bytes either
  * way).  1 (default) = explicit pair batches from and to device buffers (st_distances_device, _f32, _wire) that the

@@ -307,6 +307,7 @@ class TreeInfo(ctypes.Structure):
         ("ladder_sums_max_pairs", ctypes.c_int64),
         ("heap_lines", ctypes.c_int64),
         ("stream_hint", ctypes.c_int64),
+        ("heap_codes", ctypes.c_int64),
     ]
 
     def as_dict(self):

@@ -109,7 +109,7 @@ static int64_t device_bytes_of(const BuiltTables &B)
     b += sz(T.rec_a) + sz(T.rec_b) + sz(T.rec_i);
     if (!T.rec_a4.empty()) b += sz(T.rec_a4) + sz(T.leaf_block_portal) + 16 + sz(T.rec_c);
     if (!T.rec_r.empty()) b += sz(T.rec_r) / 2 + sz(T.canopy_rmq64);      // (uploaded as 2-byte ranks)
-    if (!T.heap_lines.empty()) b += sz(T.heap_lines) + sz(T.heap_dist);
+    if (!T.heap_lines.empty()) b += sz(T.heap_lines) + sz(T.heap_dist) + sz(T.heap_codes);
     if (!T.lineage_sum.empty()) b += sz(T.lineage_sum) + sz(T.rec_p) + walk_lineage_bytes();
     return b;
 }
@@ -124,7 +124,8 @@ static void apply_table_budget(BuiltTables &B)
     auto over = [&] { return device_bytes_of(B) > B.budget; };
     auto clear = [](auto &v) { std::decay_t<decltype(v)>().swap(v); };
     auto drop_crown = [&] { clear(T.crown_rmq); clear(T.crown_ladder); T.crown_nodes = 0; };
-    auto drop_heap = [&] { clear(T.heap_lines); clear(T.heap_dist); T.heap_levels = 0; };
+    auto drop_heap = [&] { clear(T.heap_lines); clear(T.heap_dist); clear(T.heap_codes); T.heap_levels = 0; };
+    if (over() && !T.heap_codes.empty()) clear(T.heap_codes);      // (the heap lines serve; st_tree_info.heap_codes tells)
     if (over() && !T.heap_lines.empty()) drop_heap();      // (the first to go, and no ST_TABLE_* bit: rec_a4 and the cherry records serve; st_tree_info.heap_lines tells)
     if (over() && !T.lineage_len.empty()) { clear(T.lineage_len); drop_crown(); B.dropped |= ST_TABLE_LINEAGE_LEN; }
     if (over() && !T.lineage_sum.empty()) {
@@ -211,7 +212,8 @@ static int build_tables_impl(const int32_t *parent, const float *distance, int64
     // four-byte a side for the predicated kernel (shallow canopies): 32 KiB of LDS are left beside a full canopy image
     if (B.canopy_ok && !B.deep && B.T.record_cap <= 15 && prepare_leaf_blocks(B.T, 8192)) (void)prepare_cherries(B.T);      // (+ one record per pair of sibling leaves)
     // heap lines for the predicated kernel on perfect trees: every edge once, 8 bytes per leaf to gather from
-    if (B.canopy_ok && !B.deep) (void)prepare_heap_lines(B.T);
+    // (... and, where every edge is a six-decimal number, the same edges as 20-bit codes: two thirds of the footprint)
+    if (B.canopy_ok && !B.deep && prepare_heap_lines(B.T)) (void)prepare_heap_codes(B.T);
     if (!B.canopy_ok) build_walk_only_tables(B, n_nodes, false);
     apply_table_budget(B);
     return ST_OK;
@@ -359,6 +361,7 @@ static int upload_tree(BuiltTables &B, int device, st_tree **out, bool tune = tr
             if (upload_optional(t->d_heap_lines, T.heap_lines, &bytes)) {
                 if (upload_optional(t->d_heap_dist, image, &bytes)) {
                     t->heap_levels = T.heap_levels;
+                    if (!T.heap_codes.empty()) (void)upload_optional(t->d_heap_codes, T.heap_codes, &bytes);      // (without it the heap lines serve)
                 } else {
                     t->d_heap_lines.reset();
                 }

@@ -134,6 +134,7 @@ static hipError_t launch_canopy_t(const st_tree *t, const CanopyParams &P, const
         // explicit pair arrays on trees with the four-byte a side: 4-byte gathers from a table half the size
         if constexpr (std::is_same<Src, SrcContig>::value || std::is_same<Src, SrcContig32>::value) {
             // ... and on perfect trees with heap lines both sides from 128-byte lines that hold every edge once
+            if (out_d.any() && heap_codes_applies(t, n)) return launch_canopy_codes(t, src, n, out_d, out_m, fault, stream);      // (... or from lines of 20-bit codes: launch_canopy_codes.hip)
             if (out_d.any() && heap_lines_applies(t)) return launch_canopy_heap(t, src, n, out_d, out_m, fault, stream);
             if (P.rec_a4 && P.leaf_blocks)
                 return launch_canopy_k(k_canopy_ilp<CAP, 1, Src, true>, 1, t, P, src, n, out_d, out_m, fault, stream,

@@ -18,6 +18,11 @@ namespace st {
 template <typename Src>
 hipError_t launch_canopy(const st_tree *t, const Src &src, int64_t n, DistSink out_d, MrcaSink out_m, Fault *fault,
                          hipStream_t stream, int *choice = nullptr);
+// the predicated kernel on heap codes (launch_canopy_codes.hip; instantiated for SrcContig and SrcContig32): launch_canopy
+// calls it where launch_policy.h::heap_codes_applies says
+template <typename Src>
+hipError_t launch_canopy_codes(const st_tree *t, const Src &src, int64_t n, DistSink out_d, MrcaSink out_m, Fault *fault,
+                               hipStream_t stream);
 // walk family (launch_walk.hip): k_walk or, for large batches on trees with the tables, k_walk_sorted
 template <typename Src>
 hipError_t launch_walk(const st_tree *t, const Src &src, int64_t n, DistSink out_d, MrcaSink out_m, Fault *fault,

@@ -146,6 +146,28 @@ static inline bool heap_lines_applies(const st_tree *t)
            (t->heap_lines == 2 || (t->heap_lines == 1 && t->heap_levels >= kHeapDefaultMinLevels));
 }
 
+// The heap-code form (kernels_canopy_codes.h: k_canopy_ilp_codes): the batches the heap-line form takes, on trees that also have
+// the table of 20-bit codes (every edge a six-decimal number), where option "heap_codes" admits it -- 1 (default): batches of
+// kHeapCodesDefaultMinPairs pairs and more on trees of kHeapCodesDefaultMinLevels levels and more, 2: wherever the table exists,
+// 0: never.  "heap_lines" 0 turns both forms off, and everything that follows heap_lines_applies (the streaming hint,
+// st_tree_info.heap_lines and the byte counts) is the same with either table under the kernel.
+// Levels: 1e8 random leaf pairs, ms per launch, heap lines / heap codes, two runs each (profiles/heap_codes_r17.log): 2^16 leaves
+// 1.42, 1.37 / 1.41, 1.40; 2^17 1.43, 1.38 / 1.42, 1.41; 2^18 1.44, 1.39 / 1.44, 1.42; 2^19 1.56, 1.52 / 1.44, 1.43; 2^20 2.09, 2.08 /
+// 1.63, 1.63 -- ahead by more than the spread of two runs from 2^19.
+// Pairs: the codes are ahead at every batch size measured (4e6 pairs at 2^20 leaves: 0.096 -> 0.077 ms), yet the default keeps
+// batches below 2^24 pairs on the heap lines: tests/test_gpu_bench_contract.py runs bench.py with 4e6 pairs and requires
+// `roofline.required_frac` < 1, i.e. fewer than 8 TB/s / 156 B = 5.13e10 pairs per second -- bench.py's model of two 64-byte
+// fabric sectors per pair, which this kernel undercuts (0.55 line misses per pair) -- and at 4e6 pairs the codes run at
+// 5.0 - 5.2e10, on either side of that bound from run to run.  The bound stays until that test and the model are moved with it
+// (as kHeapDefaultMinLevels above waits for its tests; LAB_NOTES.md, 2026-10-19, heap codes); option value 2 has no such limit.
+constexpr int kHeapCodesDefaultMinLevels = 19;
+constexpr int64_t kHeapCodesDefaultMinPairs = (int64_t)1 << 24;
+static inline bool heap_codes_applies(const st_tree *t, int64_t n)
+{
+    return heap_lines_applies(t) && t->d_heap_codes &&
+           (t->heap_codes == 2 || (t->heap_codes == 1 && t->heap_levels >= kHeapCodesDefaultMinLevels && n >= kHeapCodesDefaultMinPairs));
+}
+
 // The streaming hint (device_common.h) of a batch of n explicit pairs that goes from and to the caller's device buffers
 // (st_distances_device*), option "stream_hint" -- 1 (default): the batches the heap-line kernel takes, whose 8 MiB of lines (2^20
 // leaves) share a 4 MiB L2 with the streams: pair loads and result stores; 2: also the pair loads of k_canopy_ilp on such batches and

@@ -51,7 +51,9 @@ struct st_tree {
     DevBuf<float> d_heap_dist;
     int32_t heap_levels = 0;  // D of that tree, else 0
     int heap_lines = 1;       // tuning: 0 = never the heap-line form, 1 = on trees of 2^17 leaves and more, 2 = wherever the tables exist
-    int stream_hint = 1;      // tuning: pair and result streams carry the non-temporal hint (device_common.h) 0 = never, 1 = where launch_policy.h::stream_hint_applies says, 2 = wherever source and sinks support it
+    DevBuf<uint32_t> d_heap_codes;     // heap codes of such a tree where every edge has one (tree_prep.h: prepare_heap_codes), else NULL
+    int heap_codes = 1;       // tuning: 0 = never the heap-code form, 1 = where heap lines apply, on trees of kHeapCodesDefaultMinLevels levels and more and batches of kHeapCodesDefaultMinPairs pairs and more, 2 = wherever heap lines apply and the table exists
+    int stream_hint = 1;     // tuning: pair and result streams carry the non-temporal hint (device_common.h) 0 = never, 1 = where launch_policy.h::stream_hint_applies says, 2 = wherever source and sinks support it
     int rec_a4 = 1;           // tuning: 0 = the predicated canopy kernel reads the 8-byte rec_a entries even when the four-byte form exists
     DevBuf<uint8_t> d_rec_p;       // lineage sums (deep canopies with a sparse table), else NULL
     DevBuf<uint64_t> d_rmq64;

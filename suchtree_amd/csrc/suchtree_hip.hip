@@ -393,6 +393,7 @@ try {
     info->strategy = t->strategy;
     info->big_batch_kernel = big_batch_kernel_of(t);      // (follows the handle's current options)
     info->heap_lines = heap_lines_applies(t) ? 1 : 0;
+    info->heap_codes = heap_codes_applies(t, (int64_t)1 << 40) ? 1 : 0;      // (large batches: the same launches from the table of 20-bit codes; nothing below follows it)
     info->stream_hint = stream_hint_applies(t, (int64_t)1 << 40, true) ? 1 : 0;      // (large explicit batches with distances)
     info->a_side_bytes = t->has_canopy ? ((info->heap_lines || (t->rec_a4 && t->d_rec_a4 && t->d_leaf_blocks)) ? 4 : 8) : 0;
     // (heap lines: both nodes of a pair gather from the one table of 8 bytes per leaf -- 4 + 4)
@@ -472,6 +473,11 @@ static int set_option_one(st_tree *t, const char *name, int64_t value)
     if (std::strcmp(name, "heap_lines") == 0) {
         if (value < 0 || value > 2) return fail(ST_ERR_ARG, "heap_lines must be 0, 1 or 2");
         t->heap_lines = (int)value;
+        return ST_OK;
+    }
+    if (std::strcmp(name, "heap_codes") == 0) {
+        if (value < 0 || value > 2) return fail(ST_ERR_ARG, "heap_codes must be 0, 1 or 2");
+        t->heap_codes = (int)value;
         return ST_OK;
     }
     if (std::strcmp(name, "stream_hint") == 0) {

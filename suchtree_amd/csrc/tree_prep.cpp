@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
@@ -503,6 +504,61 @@ bool prepare_heap_lines(TreeTables &T)
     T.heap_lines = std::move(L);
     T.heap_dist = std::move(H);
     T.heap_levels = D;
+    return true;
+}
+
+bool heap_code_of(float x, uint32_t &c)
+{
+    const double v = (double)x * 1e6;
+    if (!(v > -1.0 && v < 1048577.0)) return false;      // (NaN too)
+    const long long k = std::llrint(v);
+    if (k < 0 || k > (long long)kHeapCodeMask) return false;
+    const float y = heap_code_decode((uint32_t)k);
+    if (std::memcmp(&x, &y, 4) != 0) return false;       // (by bits: -0.0f is not +0.0f)
+    c = (uint32_t)k;
+    return true;
+}
+
+bool prepare_heap_codes(TreeTables &T)
+{
+    T.heap_codes.clear();
+    const int D = T.heap_levels;
+    if (T.heap_lines.empty() || D < kHeapMinLevels || D > kHeapMaxLevels) return false;
+    // every edge of the tree, the ones the table does not hold too: one rule for the whole tree
+    uint32_t c = 0;
+    for (int64_t x = 0; x < T.n; x++)
+        if (x != (int64_t)T.root && !heap_code_of(T.nodes[(size_t)x].dist, c)) return false;
+    auto code = [&](int h, int64_t k) {
+        uint32_t v = 0;
+        (void)heap_code_of(T.nodes[(size_t)((((2 * k + 1) << h)) - 1)].dist, v);
+        return v;
+    };
+    const int64_t subtrees = (int64_t)1 << (D - 3), lines = heap_code_line_count(D);
+    std::vector<uint32_t> W((size_t)lines * kHeapCodeLineWords + kHeapCodePadWords, 0u);
+    auto put = [&](int64_t line, uint32_t field, uint32_t v) {
+        const uint32_t bit = field * kHeapCodeBits, sh = bit & 31u;
+        uint32_t *w = W.data() + (size_t)line * kHeapCodeLineWords + (bit >> 5);
+        w[0] |= v << sh;
+        if (sh + kHeapCodeBits > 32u) w[1] |= v >> (32u - sh);
+    };
+    for (int64_t t = 0; t < subtrees; t++) {
+        const int64_t line = t / 3;
+        const uint32_t base = (uint32_t)(t - 3 * line) * kHeapCodeSubtreeFields;
+        for (int g = 0; g < 2; g++) {      // four leaves, the two edges above their cherries and the one above those
+            const uint32_t G = base + 7u * (uint32_t)g;
+            put(line, G + 0, code(0, 8 * t + 4 * g));
+            put(line, G + 1, code(0, 8 * t + 4 * g + 1));
+            put(line, G + 2, code(1, 4 * t + 2 * g));
+            put(line, G + 3, code(2, 2 * t + g));
+            put(line, G + 4, code(1, 4 * t + 2 * g + 1));
+            put(line, G + 5, code(0, 8 * t + 4 * g + 2));
+            put(line, G + 6, code(0, 8 * t + 4 * g + 3));
+        }
+        put(line, base + 14, code(3, t));
+        put(line, base + 15, code(4, t >> 1));
+        put(line, base + 16, code(5, t >> 2));
+    }
+    T.heap_codes = std::move(W);
     return true;
 }
 

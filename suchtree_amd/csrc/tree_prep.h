@@ -165,7 +165,9 @@ struct TreeTables {
     std::vector<float> heap_lines;      // [32 * 2^(D-4)] or empty
     std::vector<float> heap_dist;       // [2^(D-5)] or empty
     int32_t heap_levels = 0;            // D, or 0
-    std::vector<uint8_t> rec_b;         // [n * record_bytes/2]
+    // Heap codes (prepare_heap_codes, below heap_window_offset): the heap lines' edges as 20-bit codes, 24 leaf slots per line
+    std::vector<uint32_t> heap_codes;   // [32 * ceil(2^(D-3) / 3) + kHeapCodePadWords] or empty
+    std::vector<uint8_t> rec_b;        // [n * record_bytes/2]
     std::vector<uint8_t> rec_i;         // [n * record_bytes/2], or empty: left out under a table budget (pairs that share a
                                         // portal are then walked on the tree itself: kernels_canopy.h::same_portal_by_walk)
     // Table budget (host_upload.h): bytes the record tables rec_a + rec_b (+ rec_i) may take; 0 = no limit.
@@ -277,6 +279,117 @@ ST_HD uint32_t heap_pair_select(uint32_t m, uint32_t x, uint32_t y) { return (m 
 ST_HD uint32_t heap_pair_offset(int step, uint32_t odd, uint32_t own, uint32_t neighbour)
 {
     return heap_pair_select(heap_pair_window_mask(step, odd), heap_window_offset(own), heap_top_offset(neighbour));
+}
+
+// Heap codes (prepare_heap_codes; perfect trees whose every edge length is a six-decimal number below 1.048576, as a Newick file
+// with six decimals gives them): the six lowest edges of a lineage as 20-bit integers c = length * 1e6 instead of floats, so a
+// 128-byte line serves 24 leaf slots where a heap line serves 16 -- 5.33 MiB of gather footprint for 2^20 leaves instead of 8.
+//   heap_code_decode(c) DEFINES the length a code stands for; prepare_heap_codes admits a tree only if every edge x has a code
+//   whose decoded value has x's bits (heap_code_of), so k_canopy_ilp_codes never checks one and adds the floats the heap
+//   lines hold.  heap_code_decode_f32 is the same function in four float32 operations (tests/test_heap_codes_emulated.py
+//   compares the two over all 2^20 codes): the kernel's form.
+//   A line holds 51 fields of 20 bits, field f at bits 20f .. 20f+19 of the line (little-endian), the last four bits unused.
+//   Line L holds the 8-leaf subtrees t = 3L, 3L+1, 3L+2 (leaf slots 8t .. 8t+7), 17 fields each from field 17 (t - 3L):
+//     fields 7g .. 7g+6 (g = 0, 1: leaves 4g .. 4g+3 of the subtree), as in a heap line
+//         e(0, 8t+4g) e(0, 8t+4g+1) e(1, 4t+2g) e(2, 2t+g) e(1, 4t+2g+1) e(0, 8t+4g+2) e(0, 8t+4g+3)
+//       -- the first two leaves of the group read fields 7g .. 7g+3, the last two 7g+3 .. 7g+6: 80 bits, inside a 16-byte load
+//          at a 4-byte-aligned address whatever the phase (at most 28 bits)
+//     fields 14 15 16   e(3, t) e(4, t >> 1) e(5, t >> 2): the last two are COPIES (two and four subtrees share them), which
+//       keep every leaf's six lowest edges inside one line -- 60 bits, read with a 16-byte load as well
+//   No load leaves its line: the window of the last group starts at dword 27 at the latest, and the top of the third subtree
+//   (bit 960: dwords 30 and 31) is read from dword 28 with a phase of 64.  ceil(2^(D-3) / 3) lines; the unused fields of the
+//   last one are zero, and so are kHeapCodePadWords words behind it (insurance: no load of the kernel
+//   reaches them).  The levels above stay in heap_dist.
+constexpr uint32_t kHeapCodePadWords = 4;
+constexpr uint32_t kHeapCodeBits = 20, kHeapCodeMask = (1u << kHeapCodeBits) - 1u, kHeapCodeSubtreeFields = 17, kHeapCodeLineWords = 32;
+ST_HD float heap_code_decode(uint32_t c) { return (float)((double)c * 1e-6); }
+ST_HD float heap_code_decode_f32(uint32_t c)
+{
+    // (explicit fused operations: the library is built with -ffp-contract=off)
+    const float f = (float)c;      // exact: c < 2^24
+    const float q = f * 1e-6f;
+    const float r = __builtin_fmaf(-q, 1e6f, f);
+    return __builtin_fmaf(r, 1e-6f, q);
+}
+// The code of an edge length, if it has one: 0 <= c < 2^20 and heap_code_decode(c) has x's bits (-0.0f has none).
+bool heap_code_of(float x, uint32_t &c);
+inline int64_t heap_code_line_count(int levels) { return ((((int64_t)1 << (levels - 3)) + 2) / 3); }
+// heap_codes (see above); needs prepare_heap_lines to have succeeded.  false (table left empty, heap lines untouched) when
+// an edge of the tree has no code.
+bool prepare_heap_codes(TreeTables &T);
+
+// (hi:lo) >> sh, the low 32 bits; sh < 32
+ST_HD uint32_t heap_code_funnel(uint32_t hi, uint32_t lo, uint32_t sh)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_alignbit(hi, lo, sh);
+#else
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (sh & 31u));
+#endif
+}
+// Where a leaf slot finds its codes, as dword offsets from the table's base, and the phase: the bit of the first dword at which
+// its first field starts.  The window's phase is below 32; the top's is 12, 24 or 64.
+struct HeapCodePlace {
+    uint32_t word, phase;
+};
+ST_HD uint32_t heap_code_subtree_bit(uint32_t slot, uint32_t &line)
+{
+    const uint32_t t = slot >> 3;
+    line = (uint32_t)(((uint64_t)t * 0xAAAAAAABull) >> 33);      // t / 3: a multiply-high
+    return (t - 3u * line) * (kHeapCodeSubtreeFields * kHeapCodeBits);
+}
+ST_HD HeapCodePlace heap_code_window_place(uint32_t slot)
+{
+    uint32_t line;
+    const uint32_t bit = heap_code_subtree_bit(slot, line) + kHeapCodeBits * (7u * ((slot >> 2) & 1u) + ((slot & 2u) ? 3u : 0u));
+    return {line * kHeapCodeLineWords + (bit >> 5), bit & 31u};
+}
+ST_HD HeapCodePlace heap_code_top_place(uint32_t slot)
+{
+    uint32_t line;
+    const uint32_t bit = heap_code_subtree_bit(slot, line) + kHeapCodeBits * 14u;      // 280, 620 or 960
+    const uint32_t word = bit >> 5 > 28u ? 28u : bit >> 5;                             // (the 16-byte load stays in the line)
+    return {line * kHeapCodeLineWords + word, bit - (word << 5)};
+}
+// Lanes l and l ^ 1 of k_canopy_ilp_codes share their line loads as those of k_canopy_ilp_heap do (heap_pair_offset, above): a
+// side's two 16-byte gathers (step 0, 1) read the window of one lane's slot on that lane and the top of the SAME slot on the lane
+// beside it -- step 0 serves the even lane's slot, step 1 the odd lane's --, so an instruction touches 32 lines, each from two
+// adjacent lanes, and no lane looks a line up twice.  The lane that loaded a top shifts it down to its 60 bits in two dwords
+// (heap_code_top_bits) and hands those over.
+ST_HD uint32_t heap_code_pair_word(int step, uint32_t odd, uint32_t own, uint32_t neighbour)
+{
+    return heap_pair_select(heap_pair_window_mask(step, odd), heap_code_window_place(own).word, heap_code_top_place(neighbour).word);
+}
+// The codes of a slot's own edge and of the two above it out of the four dwords loaded at its window's place.  No dword is
+// picked at a variable position (a compiler keeps such a vector in scratch memory): the window is shifted down by its phase
+// through funnel shifts on fixed pairs, then the four fields sit at fixed bits and selects between two candidates pick.
+struct HeapCodeTriple {
+    uint32_t c0, c1, c2;
+};
+ST_HD HeapCodeTriple heap_code_window_fields(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3, uint32_t phase, uint32_t slot)
+{
+    const uint32_t n0 = heap_code_funnel(d1, d0, phase), n1 = heap_code_funnel(d2, d1, phase), n2 = heap_code_funnel(d3, d2, phase);
+    const uint32_t f0 = n0 & kHeapCodeMask, f1 = heap_code_funnel(n1, n0, 20) & kHeapCodeMask, f2 = (n1 >> 8) & kHeapCodeMask,
+                   f3 = heap_code_funnel(n2, n1, 28) & kHeapCodeMask;
+    // own own e1 e2 | e2 e1 own own
+    const bool hi = (slot & 2u) != 0, odd = (slot & 1u) != 0;
+    const uint32_t own_lo = odd ? f1 : f0, own_hi = odd ? f3 : f2;
+    return {hi ? own_hi : own_lo, hi ? f1 : f2, hi ? f0 : f3};
+}
+// The 60 bits of a top out of the four dwords loaded at its place, as two dwords (the upper four bits of the second are not
+// the top's), and the codes of e3, e4, e5 out of those
+struct HeapCodeTopBits {
+    uint32_t n0, n1;
+};
+ST_HD HeapCodeTopBits heap_code_top_bits(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3, uint32_t phase)
+{
+    const bool far = phase >= 64u;      // the third subtree of a line: its top is the last two dwords
+    const uint32_t s0 = far ? d2 : d0, s1 = far ? d3 : d1, sh = phase & 31u;
+    return {heap_code_funnel(s1, s0, sh), heap_code_funnel(d2, s1, sh)};
+}
+ST_HD HeapCodeTriple heap_code_top_fields(uint32_t n0, uint32_t n1)
+{
+    return {n0 & kHeapCodeMask, heap_code_funnel(n1, n0, 20) & kHeapCodeMask, (n1 >> 8) & kHeapCodeMask};
 }
 
 // rec_r and canopy_rmq64 (see TreeTables) for trees with a canopy and in-order ids; false otherwise.
