@@ -49,7 +49,8 @@ extern "C" {
  *      st_hommola_permutation and st_hommola_clades_host; then, also additive, struct st_dispersion_record,
  *      st_partner_dispersion_host and st_dispersion_matrix; then, also additive, ST_UNIFRAC_MAX_UNIVERSE,
  *      ST_UNIFRAC_LANE_MAX, st_unifrac_host, st_unifrac_depths and st_unifrac_quantise; then st_tree_info.heap_codes appended
- *      (8 bytes) with option "heap_codes", as heap_lines was.
+ *      (8 bytes) with option "heap_codes", as heap_lines was; then, also additive, ST_CLADE_MATCH_MAX_LEAVES, st_clade_ranges
+ *      and st_clade_match.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -614,6 +615,63 @@ int st_unifrac_depths(int device, const int64_t *d_q, const int64_t *h_q, int32_
 
 int st_unifrac_quantise(const float *d, const float *h, int32_t n, int32_t shift, int64_t *out_dq, int64_t *out_hq,
                         int32_t *out_shift);
+
+/*
+ * Which clades of one tree are also in another, and how close is the best match where they are not: every induced clade
+ * of tree A against every induced clade of tree B over one list of m shared leaves (SuchTree.compare_clades,
+ * SuchTree.transfer_support).  The Robinson-Foulds distance, the per-clade transfer distance and the transfer bootstrap
+ * expectation (Lemoine et al. 2018) follow on the caller's side.  All integers: the host restatement, the kernels and
+ * any chunking give the same results.  Neither call needs a tree handle, only parent arrays.
+ *
+ * Order.  The m listed leaves of a tree (leaf_ids, 4 <= m <= ST_CLADE_MATCH_MAX_LEAVES = 262144) are taken depth-first,
+ * children in increasing id order (the order of st_unifrac_host's universe): position k is the k-th listed leaf met,
+ * and out_order[k] its index in leaf_ids.
+ *
+ * Induced clades.  c(v) = listed leaves under internal node v.  v is kept when c(v) >= 2 and no child of v has the same
+ * count: v is then the MRCA of its set, and unlisted leaves collapse away.  A kept node is the position range [lo, hi)
+ * of size s = hi - lo.  Kept nodes are listed breadth-first from the root, children in increasing id order (the order of
+ * SuchTree.get_internal_nodes()).  A binary tree has m - 1 of them.  Eligible, for rows and candidates alike:
+ *     rooted:   kept nodes with 2 <= s <= m - 1;
+ *     unrooted: kept nodes with 2 <= s <= m - 2, and the node whose range is [k, m) is left out when [0, k) is also
+ *               eligible (the root's two children are one bipartition).
+ *
+ * st_clade_ranges (host only) writes the order and the eligible clades of one tree: out_node / out_lo / out_hi need room
+ * for m - 1 entries (there are never more), *out_n is their number.  The parent array is that of st_clade_plan (int32,
+ * -1 at the one root; ST_ERR_TREE when it is not one rooted tree).  ST_ERR_BOUNDS with *bad_id for an id outside
+ * [0, n_nodes); ST_ERR_ARG with *bad_id for an id that is not a leaf or is listed twice, and for m out of range.
+ *
+ * Distance.  For row a of A and candidate b of B, with pos_b[k] = B's position of the leaf at A's position k:
+ *     i = |a n b| = #{k in [a_lo, a_hi) : b_lo <= pos_b[k] < b_hi},  d = s_a + s_b - 2 i,
+ *     delta(a, b) = d (rooted) or min(d, m - d) (unrooted).
+ * The row's result is the candidate of least delta, a tie going to the lower index in B's list: the minimum of the key
+ * delta << 32 | index, so no reduction order matters.  out_distance / out_match / out_intersection (n_a each) are delta,
+ * the index and i of that candidate; -1, -1 and 0 when n_b = 0.  The caller derives, with p = s_a (rooted) or
+ * min(s_a, m - s_a) (unrooted): transfer = min(delta, p - 1) (p - 1 without a candidate), support = 1 - transfer / (p - 1),
+ * exact = rows of delta 0, RF = n_a + n_b - 2 exact.
+ *
+ * st_clade_match: device = -1 is the host restatement (no GPU, one thread, a prefix count per row); device >= 0 runs
+ * k_clade_match, one row per workgroup: a bitmap of the row's B positions and one running count per 64-bit word in
+ * LDS (12 bytes per 64 leaves: 48 KiB at the cap), two rank lookups per candidate.  B's candidates are sorted by size on
+ * the host (stable); since delta >= |s_a - s_b| (and >= |m - s_a - s_b| by the complement when unrooted) a row first
+ * scans only the size windows that can beat p - 1 and falls back to all candidates when nothing there does, so the true
+ * minimum is reported either way.  The environment variable SUCHTREE_AMD_CLADE_MATCH_WINDOW (0 or 1, read at every
+ * call) turns the windows off or on for a measurement; no result depends on it.  chunk_rows: rows per launch and
+ * read-back, 0 = 65536; no result depends on it.
+ * Checked (ST_ERR_ARG): m in range, counts and chunk_rows not negative, NULL arrays, pos_b a permutation of 0 .. m - 1,
+ * every range 0 <= lo < hi <= m.  Not verified: that the ranges of either list form a laminar family, are distinct, or
+ * come from st_clade_ranges -- any list of ranges is matched as it stands.
+ * Device memory: 4 m bytes of positions, 12 bytes per candidate, 24 per row, and two chunks of 12 bytes per row of
+ * results.  An allocation that fails is ST_ERR_NOMEM with the bytes asked for, before any output is written.  n_a = 0
+ * launches nothing.  No counterpart in the reference, which offers bipartitions() as Python sets (MuchTree.pyx:1151-1200).
+ */
+#define ST_CLADE_MATCH_MAX_LEAVES 262144
+
+int st_clade_ranges(const int32_t *parent, int64_t n_nodes, const int64_t *leaf_ids, int32_t m, int32_t rooted,
+                    int32_t *out_order, int32_t *out_node, int32_t *out_lo, int32_t *out_hi, int32_t *out_n, int64_t *bad_id);
+
+int st_clade_match(int device, int32_t m, const int32_t *pos_b, const int32_t *a_lo, const int32_t *a_hi, int32_t n_a,
+                   const int32_t *b_lo, const int32_t *b_hi, int32_t n_b, int32_t unrooted, int64_t chunk_rows,
+                   int32_t *out_distance, int32_t *out_match, int32_t *out_intersection);
 
 /*
  * Exact Spearman rank correlation of the same pairs.  rank_x is the midrank of x_k among the call's n float32 distances

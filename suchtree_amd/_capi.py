@@ -47,7 +47,7 @@ SYMBOLS = (
     "st_quartet_positions", "st_compare_quartets_leaves_host", "st_compare_quartets_host",
     "st_compare_triangle_kendall_host", "st_compare_pairs_kendall_host", "st_kendall_arrays_host", "st_kendall_host",
     "st_hommola_permutation", "st_hommola_clades_host", "st_partner_dispersion_host", "st_dispersion_matrix",
-    "st_unifrac_host", "st_unifrac_depths", "st_unifrac_quantise",
+    "st_unifrac_host", "st_unifrac_depths", "st_unifrac_quantise", "st_clade_ranges", "st_clade_match",
 )
 
 CLADE_RECT, CLADE_TRI = 0, 1     # include/suchtree_hip.h: ST_CLADE_RECT / ST_CLADE_TRI
@@ -218,6 +218,49 @@ def unifrac_depths(d_q, h_q, sets, begin=0, count=None, device=-1, chunk_pairs=0
     check(load().st_unifrac_depths(int(device), _arg(d_q), _arg(h_q), len(d_q), _arg(pos), len(pos), _ptr(off), n_sets, begin, count,
                                    int(chunk_pairs), _arg(pd_q), _arg(union_q)))
     return pd_q, union_q
+
+
+CLADE_MATCH_MAX_LEAVES = 1 << 18     # ST_CLADE_MATCH_MAX_LEAVES: leaves per list of st_clade_ranges / st_clade_match
+
+
+def clade_ranges(parent, leaf_ids, rooted=False):
+    """st_clade_ranges (host only): (order, node, lo, hi) of one tree over the listed leaves -- ``order[k]`` is the index in
+    ``leaf_ids`` of the leaf at depth-first position k, and the eligible induced clades are the nodes ``node`` with the
+    position ranges [lo, hi), in ``get_internal_nodes()`` order.  InvalidNodeError for an id outside the tree, ValueError
+    for one that is not a leaf or is listed twice and for fewer than 4 or more than CLADE_MATCH_MAX_LEAVES leaves."""
+    parent = np.ascontiguousarray(parent, dtype=np.int32)
+    leaf_ids = np.ascontiguousarray(leaf_ids, dtype=np.int64)
+    if parent.ndim != 1 or leaf_ids.ndim != 1:
+        raise ValueError("parent and leaf_ids must be 1-D")
+    m = len(leaf_ids)
+    if m > CLADE_MATCH_MAX_LEAVES:      # (before the outputs are sized)
+        raise ValueError("a list of %d leaves: at most %d" % (m, CLADE_MATCH_MAX_LEAVES))
+    order = np.zeros(m, dtype=np.int32)
+    node, lo, hi = (np.zeros(max(m - 1, 1), dtype=np.int32) for _ in range(3))
+    n, bad = ctypes.c_int32(0), ctypes.c_int64(-1)
+    rc = load().st_clade_ranges(_arg(parent), len(parent), _arg(leaf_ids), m, 1 if rooted else 0, _ptr(order), _ptr(node), _ptr(lo), _ptr(hi),
+                                ctypes.byref(n), ctypes.byref(bad))
+    check(rc, len(parent), bad.value)
+    k = int(n.value)
+    return order, node[:k].copy(), lo[:k].copy(), hi[:k].copy()
+
+
+def clade_match(m, pos_b, a_lo, a_hi, b_lo, b_hi, rooted=False, device=-1, chunk_rows=0):
+    """st_clade_match: (distance, match, intersection), one int32 each per row [a_lo, a_hi) of tree A: the least delta over
+    the candidates [b_lo, b_hi) of tree B, the index of the candidate that has it (the lowest on a tie) and the leaves
+    the two share; -1, -1, 0 without candidates.  ``pos_b[k]`` is B's position of the leaf at A's position k.  ``device``
+    -1 = the host restatement (no GPU), else the kernel on that device: the same integers."""
+    arr = lambda a: np.ascontiguousarray(a, dtype=np.int32)      # noqa: E731
+    pos_b, a_lo, a_hi, b_lo, b_hi = arr(pos_b), arr(a_lo), arr(a_hi), arr(b_lo), arr(b_hi)
+    if any(v.ndim != 1 for v in (pos_b, a_lo, a_hi, b_lo, b_hi)) or len(pos_b) != int(m) or len(a_lo) != len(a_hi) or len(b_lo) != len(b_hi):
+        raise ValueError("pos_b must hold m positions, and lo and hi of a list the same number of ranges")
+    if int(chunk_rows) < 0:
+        raise ValueError("chunk_rows < 0")
+    n_a = len(a_lo)
+    out = [np.zeros(n_a, dtype=np.int32) for _ in range(3)]
+    check(load().st_clade_match(int(device), int(m), _arg(pos_b), _arg(a_lo), _arg(a_hi), n_a, _arg(b_lo), _arg(b_hi), len(b_lo),
+                                0 if rooted else 1, int(chunk_rows), _arg(out[0]), _arg(out[1]), _arg(out[2])))
+    return tuple(out)
 
 
 QUARTET_MODE = {"all": 0, "sample": 1}      # include/suchtree_hip.h: ST_QUARTET_ALL / ST_QUARTET_SAMPLE
@@ -465,6 +508,9 @@ def load():
                                       ctypes.POINTER(ctypes.c_int32), vp, vp, ctypes.POINTER(i64)]
         L.st_unifrac_depths.argtypes = [i32, vp, vp, ctypes.c_int32, vp, i64, vp, i64, i64, i64, i64, vp, vp]
         L.st_unifrac_quantise.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, ctypes.POINTER(ctypes.c_int32)]
+        L.st_clade_ranges.argtypes = [vp, i64, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int32),
+                                      ctypes.POINTER(i64)]
+        L.st_clade_match.argtypes = [i32, ctypes.c_int32, vp, vp, vp, ctypes.c_int32, vp, vp, ctypes.c_int32, ctypes.c_int32, i64, vp, vp, vp]
         L.st_clade_plan.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64),
                                     ctypes.POINTER(i64)]
         L.st_compare_clades_host.argtypes = [vp, vp, vp, i64, vp, vp, i64, i64, i64, vp, vp, ctypes.POINTER(i64)]

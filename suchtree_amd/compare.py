@@ -612,6 +612,175 @@ def unifrac_from_depths(d, h, sets, begin=0, count=None, shift=None, device=None
     return SetUniFrac(len(pd_q), begin, used, pd_q, union_q)
 
 
+def clade_side(flat, leaf_ids, rooted=False, min_branch=None):
+    """(order, node, lo, hi) of one tree over the listed leaves (``_capi.clade_ranges``): the depth-first order and the
+    eligible induced clades, without those whose branch is ``min_branch`` or shorter.  A clade's branch is the path from
+    its node up to the next node that is the MRCA of a larger set of listed leaves, summed in float64."""
+    from . import _capi
+    leaf_ids = np.ascontiguousarray(leaf_ids, dtype=np.int64)
+    order, node, lo, hi = _capi.clade_ranges(flat.parent, leaf_ids, rooted)
+    if min_branch is None or not len(node):
+        return order, node, lo, hi
+    parent, length = np.asarray(flat.parent), np.asarray(flat.distance, dtype=np.float64)
+    stop = np.zeros(len(parent), dtype=bool)      # every kept node: the eligible ones of a rooted list, and the MRCA of all
+    stop[_capi.clade_ranges(flat.parent, leaf_ids, True)[1]] = True
+    above, v = set(), int(leaf_ids[order[0]])
+    while v != -1:
+        above.add(v)
+        v = int(parent[v])
+    v = int(leaf_ids[order[-1]])      # (the first and the last leaf in depth-first order meet at the MRCA of all)
+    while v not in above:
+        v = int(parent[v])
+    stop[v] = True
+    branch = np.zeros(len(node), dtype=np.float64)
+    for r, v in enumerate(node):
+        total, u = length[v], int(parent[v])
+        while u != -1 and not stop[u]:
+            total += length[u]
+            u = int(parent[u])
+        branch[r] = total
+    keep = branch > float(min_branch)
+    return order, node[keep], lo[keep], hi[keep]
+
+
+class CladeMatches:
+    """Every induced clade of tree A matched to the closest induced clade of tree B over m shared leaves
+    (SuchTree.compare_clades).
+
+    One row per clade of A, in ``get_internal_nodes()`` order: ``nodes`` (A node ids), ``n_leaves`` (listed leaves under
+    the node), ``match`` (the B node id of the closest clade, the first in B's order on a tie; -1 where B has none),
+    ``match_leaves`` and ``intersection`` (its size and the leaves the two share, 0 without a match), ``distance`` (delta:
+    the leaves to move, d = n_leaves + match_leaves - 2 intersection, or min(d, m - d) when unrooted; -1 without a match),
+    ``transfer`` = min(distance, p - 1) with p = n_leaves (rooted) or min(n_leaves, m - n_leaves) (unrooted), the
+    transfer distance of Lemoine et al. 2018 (p - 1 without a match), ``support`` = 1 - transfer / (p - 1) and ``jaccard``
+    = intersection / (n_leaves + match_leaves - intersection) of the two leaf sets as they stand (NaN without a match).
+    Scalars over ALL clades of A, whatever ``nodes=`` kept as rows: ``n_a``, ``n_b`` (clades of either tree), ``exact``
+    (clades of A with distance 0), ``rf`` = n_a + n_b - 2 exact (Robinson-Foulds), ``rf_normalised`` = rf / (n_a + n_b)
+    (NaN when both are 0), ``mean_transfer``; ``n_leaves_shared`` = m and ``rooted`` repeat the call.  All columns but the
+    last two are integers that do not depend on the device or the chunking.
+    """
+
+    COLUMNS = ("nodes", "n_leaves", "match", "match_leaves", "intersection", "distance", "transfer", "support", "jaccard")
+
+    def __init__(self, m, rooted, side_a, side_b, distance, match, intersection, rows=None):
+        _, node_a, lo_a, hi_a = side_a
+        _, node_b, lo_b, hi_b = side_b
+        self.n_leaves_shared, self.rooted = int(m), bool(rooted)
+        self.n_a, self.n_b = len(node_a), len(node_b)
+        size_a = (hi_a - lo_a).astype(np.int64)
+        size_b = (hi_b - lo_b).astype(np.int64)
+        distance, match = np.asarray(distance, dtype=np.int64), np.asarray(match, dtype=np.int64)
+        found = match >= 0
+        p = size_a if rooted else np.minimum(size_a, m - size_a)
+        transfer = np.where(found, np.minimum(distance, p - 1), p - 1)
+        self.exact = int((found & (distance == 0)).sum())
+        self.rf = self.n_a + self.n_b - 2 * self.exact
+        self.rf_normalised = self.rf / (self.n_a + self.n_b) if self.n_a + self.n_b else float("nan")
+        self.mean_transfer = float(transfer.mean()) if self.n_a else float("nan")
+        rows = np.arange(self.n_a) if rows is None else np.asarray(rows, dtype=np.int64)
+        safe = np.where(found, match, 0)[rows]
+        found = found[rows]
+        self.nodes = node_a[rows].astype(np.int64)
+        self.n_leaves = size_a[rows]
+        self.match = np.where(found, node_b[safe] if self.n_b else -1, -1).astype(np.int64)
+        self.match_leaves = np.where(found, size_b[safe] if self.n_b else 0, 0).astype(np.int64)
+        self.intersection = np.where(found, np.asarray(intersection, dtype=np.int64)[rows], 0)
+        self.distance = distance[rows]
+        self.transfer = transfer[rows]
+        self.support = 1.0 - self.transfer / (p[rows] - 1.0)
+        union = self.n_leaves + self.match_leaves - self.intersection
+        self.jaccard = np.where(found, self.intersection / union.astype(np.float64), np.nan)
+
+    def __len__(self):
+        return len(self.nodes)
+
+    def row(self, node) -> dict:
+        """The row of A's clade ``node`` as a dict of Python scalars (KeyError when it is not a row)."""
+        at = np.flatnonzero(self.nodes == int(node))
+        if not len(at):
+            raise KeyError("node %r is not a row of this result" % (node,))
+        return {("node" if k == "nodes" else k): getattr(self, k)[at[0]].item() for k in self.COLUMNS}
+
+    def to_dataframe(self):
+        """The columns as a pandas DataFrame (pandas imported here)."""
+        import pandas as pd
+        return pd.DataFrame({k: getattr(self, k) for k in self.COLUMNS})
+
+
+def match_clades(flat_a, ids_a, flat_b, ids_b, rooted=False, nodes=None, min_branch=None, device=None, chunk_rows=0, side_a=None):
+    """:class:`CladeMatches` of two flat trees over aligned leaf-id lists (leaf k is ``ids_a[k]`` in A and ``ids_b[k]`` in
+    B).  ``device=None`` computes on the host, without a GPU; a device index runs the kernel there -- the same integers.
+    ``side_a``: A's :func:`clade_side`, where the caller has it already (transfer_support, one A against many B)."""
+    from . import _capi
+    ids_a, ids_b = (np.ascontiguousarray(v, dtype=np.int64) for v in (ids_a, ids_b))
+    if ids_a.ndim != 1 or ids_a.shape != ids_b.shape:
+        raise ValueError("the two id lists must be 1-D and of equal length")
+    m = len(ids_a)
+    if m < 4 or m > _capi.CLADE_MATCH_MAX_LEAVES:
+        raise ValueError("%d shared leaves: 4 to %d" % (m, _capi.CLADE_MATCH_MAX_LEAVES))
+    if side_a is None:
+        side_a = clade_side(flat_a, ids_a, rooted, min_branch)
+    side_b = clade_side(flat_b, ids_b, rooted, min_branch)
+    rows = None
+    if nodes is not None:
+        wanted = np.atleast_1d(np.asarray(nodes, dtype=np.int64))
+        at = {int(v): r for r, v in enumerate(side_a[1])}
+        for v in wanted:
+            if int(v) not in at:
+                raise ValueError("node %d is not a clade of this comparison" % v)
+        rows = np.array([at[int(v)] for v in wanted], dtype=np.int64)
+    where_b = np.empty(m, dtype=np.int32)
+    where_b[side_b[0]] = np.arange(m, dtype=np.int32)
+    got = _capi.clade_match(m, where_b[side_a[0]], side_a[2], side_a[3], side_b[2], side_b[3], rooted, -1 if device is None else int(device),
+                            chunk_rows)
+    return CladeMatches(m, rooted, side_a, side_b, *got, rows=rows)
+
+
+class TransferSupport:
+    """The transfer bootstrap expectation of every clade of a tree over replicate trees (SuchTree.transfer_support).
+
+    One row per clade, in ``get_internal_nodes()`` order: ``nodes``, ``n_leaves``, ``transfer_sum`` (the exact int64 sum of
+    the clade's transfer distance over the replicates), ``support`` = 1 - (transfer_sum / n_replicates) / (p - 1), the mean
+    of the per-replicate supports (NaN without replicates), and ``exact_count``, the replicates that hold the clade itself:
+    Felsenstein's bootstrap count.  ``n_replicates``, ``n_leaves_shared`` and ``rooted`` repeat the call.
+    """
+
+    COLUMNS = ("nodes", "n_leaves", "transfer_sum", "support", "exact_count")
+
+    def __init__(self, m, rooted, side_a):
+        _, node, lo, hi = side_a
+        self.n_leaves_shared, self.rooted, self.n_replicates = int(m), bool(rooted), 0
+        self.nodes = node.astype(np.int64)
+        self.n_leaves = (hi - lo).astype(np.int64)
+        self.transfer_sum = np.zeros(len(node), dtype=np.int64)
+        self.exact_count = np.zeros(len(node), dtype=np.int64)
+
+    def add(self, matches: CladeMatches):
+        self.transfer_sum += matches.transfer
+        self.exact_count += (matches.match >= 0) & (matches.distance == 0)
+        self.n_replicates += 1
+
+    @property
+    def support(self):
+        p = self.n_leaves if self.rooted else np.minimum(self.n_leaves, self.n_leaves_shared - self.n_leaves)
+        if not self.n_replicates:
+            return np.full(len(self.nodes), np.nan)
+        return 1.0 - (self.transfer_sum / float(self.n_replicates)) / (p - 1.0)
+
+    def __len__(self):
+        return len(self.nodes)
+
+    def row(self, node) -> dict:
+        at = np.flatnonzero(self.nodes == int(node))
+        if not len(at):
+            raise KeyError("node %r is not a row of this result" % (node,))
+        return {("node" if k == "nodes" else k): getattr(self, k)[at[0]].item() for k in self.COLUMNS}
+
+    def to_dataframe(self):
+        import pandas as pd
+        return pd.DataFrame({k: getattr(self, k) for k in self.COLUMNS})
+
+
 def null_summary(observed, null, degenerate=None):
     """(mean, sd, ses, n_le) per row of ``null`` (rows, draws) against ``observed`` (rows): NaN draws left out, sd with
     ddof = 1, exactly 0 where all draws are equal; rows marked ``degenerate`` have the observation as their null."""

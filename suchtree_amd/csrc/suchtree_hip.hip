@@ -52,6 +52,10 @@
 // Faith's PD of many leaf sets and the union sums of their pairs behind UniFrac (st_unifrac_host, st_unifrac_depths):
 // kernels_unifrac.h (the range-minimum table, the set merge in a lane form and a wave form), host_unifrac.h (the depths, the
 // chunk driver) and, host-only, unifrac_plan.cpp (argument checks, the quantiser, chunks, the restatement of the merge).
+// Every induced clade of one tree matched to the closest of another's, behind Robinson-Foulds and transfer support
+// (st_clade_ranges, st_clade_match): kernels_clade_match.h (a bitmap and running counts in LDS, one row per workgroup),
+// host_clade_match.h (the chunk driver) and, host-only, clade_match_plan.cpp (the range builder, the checks, the size
+// windows, the restatement).
 //
 // Host side of the C ABI: tree upload to one or several GPUs (tree_prep.cpp builds the tables, under a table budget
 // if one is given), the host path (host_pipe.h, host_copy.h: packed ids in through the copy engine, kernels write
@@ -175,6 +179,7 @@ static int device_index_arg(int device)
 #include "kernels_hommola.h"
 #include "kernels_dispersion.h"
 #include "kernels_unifrac.h"
+#include "kernels_clade_match.h"
 
 
 // --------------------------------------------------------------------------
@@ -192,6 +197,7 @@ using namespace st;
 #include "host_hommola.h"
 #include "host_dispersion.h"
 #include "host_unifrac.h"
+#include "host_clade_match.h"
 
 extern "C" {
 
@@ -1386,6 +1392,42 @@ try {
         return ST_OK;
     }
     return unifrac_tree_run(t, root, univ, P, set_pos, n_pos, sets, shift, out_pd, out_union, out_shift, out_d, out_h, bad_id);
+} ST_CATCH_ALL
+
+int st_clade_ranges(const int32_t *parent, int64_t n_nodes, const int64_t *leaf_ids, int32_t m, int32_t rooted, int32_t *out_order,
+                    int32_t *out_node, int32_t *out_lo, int32_t *out_hi, int32_t *out_n, int64_t *bad_id)
+try {
+    if (!out_order || !out_node || !out_lo || !out_hi || !out_n) return fail(ST_ERR_ARG, "an output is NULL");
+    std::vector<int32_t> order, node, lo, hi;
+    std::string err;
+    const int rc = clade_ranges(parent, n_nodes, leaf_ids, m, rooted != 0, order, node, lo, hi, bad_id, err);
+    if (rc == ST_ERR_BOUNDS) return fail(rc, "a leaf id out of bounds (tree size: " + std::to_string(n_nodes) + ")");
+    if (rc != ST_OK) return fail(rc, err);
+    std::copy(order.begin(), order.end(), out_order);
+    std::copy(node.begin(), node.end(), out_node);
+    std::copy(lo.begin(), lo.end(), out_lo);
+    std::copy(hi.begin(), hi.end(), out_hi);
+    *out_n = (int32_t)node.size();
+    return ST_OK;
+} ST_CATCH_ALL
+
+int st_clade_match(int device, int32_t m, const int32_t *pos_b, const int32_t *a_lo, const int32_t *a_hi, int32_t n_a, const int32_t *b_lo,
+                   const int32_t *b_hi, int32_t n_b, int32_t unrooted, int64_t chunk_rows, int32_t *out_distance, int32_t *out_match,
+                   int32_t *out_intersection)
+try {
+    std::string err;
+    const int rc = clade_match_args(m, pos_b, a_lo, a_hi, n_a, b_lo, b_hi, n_b, chunk_rows, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (device_or_host_arg(device) != ST_OK) return ST_ERR_ARG;
+    if (n_a > 0 && (!out_distance || !out_match || !out_intersection)) return fail(ST_ERR_ARG, "an output is NULL");
+    if (n_a == 0) return ST_OK;      // (no rows: nothing to launch)
+    if (device < 0) {
+        clade_match_host(m, pos_b, a_lo, a_hi, n_a, b_lo, b_hi, n_b, unrooted != 0, out_distance, out_match, out_intersection);
+        return ST_OK;
+    }
+    CladeMatchPlan P;
+    clade_match_plan(m, a_lo, a_hi, n_a, b_lo, b_hi, n_b, unrooted != 0, chunk_rows, clade_match_window(), P);
+    return clade_match_device(device, P, pos_b, a_lo, a_hi, out_distance, out_match, out_intersection);
 } ST_CATCH_ALL
 
 int st_graph_matrices_host(int device, int64_t n, int64_t n_edges, const int32_t *u, const int32_t *v,

@@ -539,6 +539,85 @@ class SuchTree(TreeNavigation):
                                                                  k_count=count)
         return compare.QuartetComparison.from_table(table, n_leaves=m, mode=mode, seed=seed)
 
+    def _shared_ids(self, other, leaves):
+        """(ids in self, ids in other) of a ``leaves`` argument as :meth:`compare_distances` reads it."""
+        if leaves is None:
+            _, ids_x, ids_y = self.shared_leaves(other)
+        elif isinstance(leaves, tuple) and len(leaves) == 2:
+            ids_x, ids_y = (np.ascontiguousarray(v, dtype=np.int64) for v in leaves)
+        else:
+            names = list(leaves)
+            ids_x, ids_y = self._name_ids(names), other._name_ids(names)
+        if ids_x.ndim != 1 or ids_x.shape != ids_y.shape:
+            raise ValueError("the two id lists must be 1-D and of equal length")
+        return ids_x, ids_y
+
+    def compare_clades(self, other: "SuchTree", leaves=None, rooted=False, nodes=None, min_branch=None, device=..., chunk_rows=0):
+        """Which clades of this tree are also in ``other``, and how close is the best match where they are not: every
+        induced clade of this tree (A) against every induced clade of ``other`` (B), matched on the GPU.
+
+        An extension: the reference offers only ``bipartitions()``, a generator of Python sets (MuchTree.pyx:1151-1200).
+        Returns a :class:`~suchtree_amd.compare.CladeMatches`: per clade of A the closest clade of B, the leaves to move
+        between them (``distance``), the transfer distance and support of Lemoine et al. 2018, and over all clades the
+        Robinson-Foulds distance ``rf``.
+
+        ``leaves`` as in :meth:`compare_distances`: None = every leaf name present in both trees, a list of leaf names,
+        or a tuple ``(ids_self, ids_other)`` of aligned leaf-id arrays; 4 to 262144 leaves, each once (ValueError).  Other
+        leaves collapse away: a clade is a node that is the MRCA of two or more listed leaves, taken as the set of
+        listed leaves under it.  ``rooted=False`` (the default: most such trees are arbitrarily rooted) reads clades as
+        bipartitions -- a set and its complement are the same, clades of m - 1 leaves are left out and the root's two
+        children count once; ``rooted=True`` compares the sets themselves, up to m - 1 leaves.
+        ``nodes=`` restricts the rows to the listed clades of this tree; the candidates and ``rf`` still use all of them.
+        ``min_branch=x`` leaves out of both lists every clade whose branch -- the path from its node up to the next node
+        that joins more listed leaves, summed in float64 -- is x or shorter: ``min_branch=tree.polytomy_epsilon`` keeps the
+        epsilon branches that resolve a polytomy from counting as clades.
+        ``device``: by default the tree's device; None runs the host restatement (one thread, no GPU): the same integers.
+        Neither tree is uploaded: the call needs their parent arrays alone.
+        """
+        from . import compare
+        ids_x, ids_y = self._shared_ids(other, leaves)
+        return compare.match_clades(self._flat, ids_x, other._flat, ids_y, bool(rooted), nodes, min_branch,
+                                    self._device if device is ... else device, int_arg("chunk_rows", chunk_rows))
+
+    def transfer_support(self, replicates, leaves=None, rooted=False, min_branch=None, device=...):
+        """The transfer bootstrap expectation (Lemoine et al. 2018) of every clade of this tree over replicate trees, the
+        support measure made for trees of 10^4 to 10^5 leaves, with Felsenstein's count beside it.
+
+        ``replicates`` is an iterable of :class:`SuchTree` objects, Newick texts or paths to Newick files; texts and paths
+        are parsed into flat arrays only, nothing of a replicate goes to the GPU but its clade ranges.  ``leaves``: None =
+        every leaf of this tree, else a collection of leaf names; a replicate that lacks one is a ValueError that names
+        it.  ``rooted``, ``min_branch`` and ``device`` as in :meth:`compare_clades`, which is what every replicate gets:
+        replicate r's contribution depends on (this tree, replicate r, the leaf list) alone.  Returns a
+        :class:`~suchtree_amd.compare.TransferSupport`.  An extension: the reference has no counterpart.
+        """
+        from . import compare
+        from .newick import flat_tree_from_newick
+        names = [name for name, _ in sorted(self.leaves.items(), key=lambda kv: kv[1])] if leaves is None else list(leaves)
+        ids = self._name_ids(names)
+        device = self._device if device is ... else device
+        if len(ids) < 4:
+            raise ValueError("%d listed leaves: at least 4" % len(ids))
+        side = compare.clade_side(self._flat, ids, bool(rooted), min_branch)
+        out = compare.TransferSupport(len(ids), bool(rooted), side)
+        for r, rep in enumerate(replicates):
+            if isinstance(rep, SuchTree):
+                flat = rep._flat
+            elif isinstance(rep, str):
+                text = rep.strip()
+                if not (text.startswith("(") and text.endswith(";")):
+                    with open(rep) as fh:
+                        text = fh.read()
+                flat = flat_tree_from_newick(text)
+            else:
+                raise TypeError("replicate %d must be a SuchTree, a Newick text or a path" % r)
+            where = flat.leaves
+            for name in names:
+                if name not in where:
+                    raise ValueError("replicate %d has no leaf %r" % (r, name))
+            ids_r = np.fromiter((where[name] for name in names), dtype=np.int64, count=len(names))
+            out.add(compare.match_clades(self._flat, ids, flat, ids_r, bool(rooted), None, min_branch, device, side_a=side))
+        return out
+
     _DISPERSION_GROUP_ROWS = 1 << 22      # records per library call of dispersion: bounds its host memory (16 bytes each)
 
     def _depth_first_leaves(self) -> np.ndarray:
