@@ -30,7 +30,7 @@ __device__ __forceinline__ void record_fault(Fault *f, long long a, long long b,
 // same addresses either way.  The sinks carry no field of their own: k_canopy_ilp_heap sits at its limit of scalar
 // registers (tests/test_heap_kernel_resources.py allows no spill), and one more word among its arguments, or one more
 // loop-invariant condition in its loop, makes it spill -- so that kernel tests the source's field once and runs one of two
-// copies of its loop (kernels_canopy.h: heap_pairs), and the other kernels' stores stay plain.  load() stays the plain load:
+// copies of its loop (kernels_canopy_heap.h: heap_pairs), and the other kernels' stores stay plain.  load() stays the plain load:
 // only k_canopy_ilp, measured with it, asks for load_stream(); every other kernel compiles to what it was.
 // A hinted access and its plain twin sit in the two arms of a branch, same address, same value: the optimiser hoists or sinks them
 // into ONE access and, the hint being advice, drops it on the way (seen on the pair load and on both id stores of

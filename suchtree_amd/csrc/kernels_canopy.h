@@ -1,7 +1,8 @@
 // kernels_canopy.h -- canopy family: CanopyParams, the per-pair device helpers, k_canopy_ladder, k_canopy_ilp,
 // k_canopy_ilp_heap, k_mrca_ranks (launch_canopy.hip); k_canopy_sorted lives in kernels_canopy_sorted.h
-// (launch_canopy_sorted.hip).  Include after device_common.h and pair_math.h.
+// (launch_canopy_sorted.hip), the heap family's loop in kernels_canopy_heap.h.  Include after device_common.h and pair_math.h.
 #pragma once
+#include "kernels_canopy_heap.h"
 #include "launch_geometry.h"
 
 namespace st {
@@ -70,10 +71,12 @@ struct PairRecs {
     __device__ __forceinline__ const float *chain() const { return CAP > 0 ? Db : reinterpret_cast<const float *>(rb + 4); }
 };
 
-// b's record (L.rb set): word0 + chain
-template <int CAP>
-__device__ __forceinline__ void load_rec_b(PairRecs<CAP> &L)
+// b's record (L.rb set): word0 + chain, 16-byte chunk q > 0 only where want(q, word0) says so (a chunk that is not loaded holds
+// no chain slot in use: kChainPad; a lane that does not load a chunk does not cost a cache lookup)
+template <int CAP, typename Want>
+__device__ __forceinline__ void load_rec_b_where(PairRecs<CAP> &L, Want want)
 {
+    static_assert(CAP == 0 || CAP == 1 || (CAP + 1) % 4 == 0, "record layout");
     if (CAP == 1) {
         const uint2 v = *reinterpret_cast<const uint2 *>(L.rb);
         L.wb = v.x;
@@ -82,7 +85,8 @@ __device__ __forceinline__ void load_rec_b(PairRecs<CAP> &L)
         uint32_t w[CAP + 1];
 #pragma unroll
         for (int q = 0; q < (CAP + 1) / 4; q++) {
-            const uint4 v = reinterpret_cast<const uint4 *>(L.rb)[q];
+            uint4 v = make_uint4(kChainPad, kChainPad, kChainPad, kChainPad);
+            if (q == 0 || want(q, w[0])) v = reinterpret_cast<const uint4 *>(L.rb)[q];
             w[4 * q + 0] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
         }
         L.wb = w[0];
@@ -94,26 +98,27 @@ __device__ __forceinline__ void load_rec_b(PairRecs<CAP> &L)
     }
 }
 
-// b's record (L.rb set), only its first `chunks` 16-byte chunks (the rest of the chain slots are
-// never added: zero).  A lane that does not load a chunk does not cost a cache lookup.
+// ... all of it
+template <int CAP>
+__device__ __forceinline__ void load_rec_b(PairRecs<CAP> &L)
+{
+    load_rec_b_where<CAP>(L, [](int, uint32_t) { return true; });
+}
+
+// ... the first 128-byte line at once, of a 63-slot chain's second line only the chunks that hold slots in use, once the
+// length is there (mean understory of a 1e6-leaf tree with 512-byte records: 34 nodes; 43 % of its leaves need no second
+// line, the rest a part of it; k_canopy_ilp reads its records the same way).  The same loads as load_rec_b up to 31 slots.
+template <int CAP>
+__device__ __forceinline__ void load_rec_b_lazy(PairRecs<CAP> &L)
+{
+    load_rec_b_where<CAP>(L, [](int q, uint32_t word0) { return q < 8 || (uint32_t)(4 * q) <= (word0 >> 16); });      // slots 4q-1 .. 4q+2
+}
+
+// ... only its first `chunks` chunks (at least one), for a caller that knows the count before the load
 template <int CAP>
 __device__ __forceinline__ void load_rec_b_chunks(PairRecs<CAP> &L, uint32_t chunks)
 {
-    static_assert(CAP == 0 || CAP == 1 || (CAP + 1) % 4 == 0, "record layout");
-    if (CAP <= 1) {
-        load_rec_b<CAP>(L);
-    } else {
-        uint32_t w[CAP + 1];
-#pragma unroll
-        for (int q = 0; q < (CAP + 1) / 4; q++) {
-            uint4 v = make_uint4(kChainPad, kChainPad, kChainPad, kChainPad);      // (a chunk that is not loaded holds no chain slot in use)
-            if ((uint32_t)q < chunks) v = reinterpret_cast<const uint4 *>(L.rb)[q];
-            w[4 * q + 0] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
-        }
-        L.wb = w[0];
-#pragma unroll
-        for (int q = 0; q < CAP; q++) L.Db[q] = __uint_as_float(w[q + 1]);
-    }
+    load_rec_b_where<CAP>(L, [chunks](int q, uint32_t) { return (uint32_t)q < chunks; });
 }
 
 template <int CAP>
@@ -165,33 +170,6 @@ __device__ __forceinline__ void stage_ladder(const CanopyParams &P, unsigned cha
 {
     stage_ladder_image(lds_raw, P.ladder, P.canopy_nodes);
     __syncthreads();
-}
-
-// b's record (L.rb set) for long chains: the first 128-byte line at once, of a 63-slot chain's second line only the
-// 16-byte chunks that hold slots in use, once the length is there (k_canopy_ilp reads its records the same way).
-template <int CAP>
-__device__ __forceinline__ void load_rec_b_lazy(PairRecs<CAP> &L)
-{
-    if constexpr (CAP <= 31) {
-        load_rec_b<CAP>(L);
-    } else {
-        uint32_t w[CAP + 1];
-        constexpr int kChunks = (CAP + 1) / 4, kEager = 8;
-#pragma unroll
-        for (int q = 0; q < kEager; q++) {
-            const uint4 x = reinterpret_cast<const uint4 *>(L.rb)[q];
-            w[4 * q + 0] = x.x; w[4 * q + 1] = x.y; w[4 * q + 2] = x.z; w[4 * q + 3] = x.w;
-        }
-        L.wb = w[0];
-#pragma unroll
-        for (int q = kEager; q < kChunks; q++) {
-            uint4 x = make_uint4(kChainPad, kChainPad, kChainPad, kChainPad);
-            if ((uint32_t)(4 * q) <= (L.wb >> 16)) x = reinterpret_cast<const uint4 *>(L.rb)[q];      // slots 4q-1 .. 4q+2
-            w[4 * q + 0] = x.x; w[4 * q + 1] = x.y; w[4 * q + 2] = x.z; w[4 * q + 3] = x.w;
-        }
-#pragma unroll
-        for (int q = 0; q < CAP; q++) L.Db[q] = __uint_as_float(w[q + 1]);
-    }
 }
 
 // Scalar kernel over the LADDER image (deep canopies whose records are too long for the tile-sorted kernel's second
@@ -537,141 +515,7 @@ __global__ __launch_bounds__(kCanopyBlock, ((CAP <= 7 && PPL == 1) ? 8 : 4)) voi
     }
 }
 
-// The predicated kernel on heap lines (tree_prep.h: prepare_heap_lines; perfect trees with in-order ids, the headline tree
-// among them).  Ids are arithmetic there: leaf slots sa = a >> 1 and sb = b >> 1 part ways k = bit length of (sa ^ sb)
-// edges below their MRCA, whose id is ((((sa >> k) << 1) | 1) << k) - 1; either side adds the six lowest edges of its
-// lineage from ONE 128-byte line (the line of 16 leaf slots) and the rest from the heap image in LDS, entry
-// (2^(D-6) + (slot >> 6)) >> q for its q-th edge above the line.  No portal, no block table, no depth cut, no shared-portal
-// case: one formula for every leaf pair, and a gather footprint of 8 MiB for 2^20 leaves where rec_a4 and the cherry
-// records take 20.  None of the addresses depends on a load but the pair's own, so a lane issues its four line loads
-// (two 16-byte windows per node: HeapSide) and all its LDS reads at once.  Four, because with eight narrower loads on a
-// line per 16 leaves in level order the kernel ran at the old 2.80 ms per 1e8 pairs: L1-miss latency per pair fell by 19 %
-// but the vector-memory address pipeline stayed busy 93 % of the launch (LAB_NOTES.md 9).  Sums start at +0.0f and every
-// add is predicated with -0.0f (kChainPad) as in k_canopy_ilp: the reference's adds in the reference's order, the same
-// bits.  A pair with an internal node (odd id) is walked on the tree itself (rare: a wave-level branch).
-struct HeapParams {
-    const float *lines;            // [2^(D-4) * 32] heap lines
-    const float *dist;             // [heap_image_bytes(D) / 4] heap image, staged to LDS
-    const Node8 *nodes;            // the walk family's tables (pairs with an internal node)
-    const int32_t *depth;
-    const Stride3 *stride;
-    long long n_nodes;
-    int32_t levels;                // D: edges between a leaf and the root
-};
-constexpr int kHeapLineEdges = 6;                                   // edges of a lineage that its line holds
-constexpr int kHeapClimbMax = kHeapMaxLevels - kHeapLineEdges;      // ... and the most that are left for the heap image
-
-typedef float __attribute__((ext_vector_type(4), aligned(4))) float4_align4;      // a 16-byte load at any dword
-
-// The six line values of one leaf slot (tree_prep.h: the layout of a heap line) out of two 16-byte loads, the window of the
-// slot's group of four leaves and the line's last four floats -- shared between lanes l and l ^ 1 (tree_prep.h:
-// heap_pair_offset): either gather instruction reads the window of one of the two slots on its own lane and the top of the same
-// slot on the lane beside it, so the L1 looks every line up once (a lane that read both had its second lookup behind those of
-// the 63 other lanes, and 0.18 requests per pair went out again for a tag replaced in between).  The loading lane picks the
-// neighbour's e3 and hands the three top values over by quad permutes: no LDS, and every lane of the wave must be active.
-__device__ __forceinline__ uint32_t heap_lane_swap(uint32_t v)      // lane l reads lane l ^ 1 (quad_perm:[1,0,3,2])
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);
-}
-struct HeapSide {
-    float4_align4 w;       // issue(): the loads of step 0 and 1; settle(): the slot's own window
-    float4_align4 top;     // issue(): ...; settle(): x, y, z = the slot's e3, e4, e5
-    uint32_t t, nb;
-    // odd: all ones on an odd lane, 0 on an even one
-    __device__ __forceinline__ void issue(const float *lines, uint32_t sl, uint32_t odd)
-    {
-        t = sl & 15u;
-        nb = heap_lane_swap(sl);
-        w = *reinterpret_cast<const float4_align4 *>(lines + heap_pair_offset(0, odd, sl, nb));
-        top = *reinterpret_cast<const float4_align4 *>(lines + heap_pair_offset(1, odd, sl, nb));
-    }
-    __device__ __forceinline__ void settle(uint32_t odd)
-    {
-        const uint32_t m = heap_pair_window_mask(1, odd);      // set: step 1 read the own window and step 0 the neighbour's top
-        const uint32_t a0 = __float_as_uint(w.x), a1 = __float_as_uint(w.y), a2 = __float_as_uint(w.z), a3 = __float_as_uint(w.w);
-        const uint32_t b0 = __float_as_uint(top.x), b1 = __float_as_uint(top.y), b2 = __float_as_uint(top.z), b3 = __float_as_uint(top.w);
-        w.x = __uint_as_float(heap_pair_select(m, b0, a0));
-        w.y = __uint_as_float(heap_pair_select(m, b1, a1));
-        w.z = __uint_as_float(heap_pair_select(m, b2, a2));
-        w.w = __uint_as_float(heap_pair_select(m, b3, a3));
-        const uint32_t n0 = heap_pair_select(m, a0, b0), n3 = heap_pair_select(m, a3, b3);      // the neighbour's top
-        top.x = __uint_as_float(heap_lane_swap((nb & 8u) ? n3 : n0));
-        top.y = __uint_as_float(heap_lane_swap(heap_pair_select(m, a1, b1)));
-        top.z = __uint_as_float(heap_lane_swap(heap_pair_select(m, a2, b2)));
-    }
-    // s += the first k (at most six) of the leaf's edges, in order; every add predicated (kChainPad)
-    __device__ __forceinline__ float add(float s, int k) const
-    {
-        const float pad = __uint_as_float(kChainPad);
-        // (selects between pairs of components only: a select chain over all four components of one vector can become an
-        // extract at a variable index, which the compiler keeps in scratch memory -- tests/test_heap_kernel_resources.py)
-        const float w0 = w.x, w1 = w.y, w2 = w.z, w3 = w.w;
-        const bool hi = (t & 2u) != 0, odd = (t & 1u) != 0;
-        const float own_lo = odd ? w1 : w0, own_hi = odd ? w3 : w2;
-        s += 0 < k ? (hi ? own_hi : own_lo) : pad;
-        s += 1 < k ? (hi ? w1 : w2) : pad;
-        s += 2 < k ? (hi ? w0 : w3) : pad;
-        s += 3 < k ? top.x : pad;
-        s += 4 < k ? top.y : pad;
-        s += 5 < k ? top.z : pad;
-        return s;
-    }
-};
-
-// The kernel's loop over its pairs, NT: with the streaming hint on the pair load and the result stores (device_common.h).  The hint
-// is a run-time field, but this loop has no scalar register to spare for one more loop-invariant condition (the plain form sits at
-// the limit; tests/test_heap_kernel_resources.py), so the kernel tests it once and runs one of two copies of the loop.
-template <bool NT, typename Src>
-__device__ __forceinline__ void heap_pairs(const HeapParams &P, const Src &src, long long n, const DistSink &out_d, const MrcaSink &out_m,
-                                           Fault *fault, const float *H)
-{
-    const uint32_t first = 1u << (P.levels - kHeapLineEdges);      // heap index of slot block 0 at the lowest level of the image
-    const float pad = __uint_as_float(kChainPad);
-    const uint32_t odd = 0u - (threadIdx.x & 1u);      // the lane's parity as a mask (tree_prep.h: heap_pair_offset)
-    for (long long base = (long long)blockIdx.x * blockDim.x; base < n; base += (long long)gridDim.x * blockDim.x) {
-        const long long i = base + threadIdx.x;
-        const bool live = i < n;
-        long long ida, idb;
-        src.template load_as<NT>(live ? i : n - 1, ida, idb);
-        const bool valid = (unsigned long long)ida < (unsigned long long)P.n_nodes && (unsigned long long)idb < (unsigned long long)P.n_nodes;
-        if (!valid && live) record_fault(fault, ida, idb, P.n_nodes);
-        const bool leaves = valid && !((ida | idb) & 1);
-        const uint32_t sa = leaves ? (uint32_t)ida >> 1 : 0u, sb = leaves ? (uint32_t)idb >> 1 : 0u;
-        // every load of both lines before anything uses them (converged: the lane pairs exchange slots here ...)
-        HeapSide A, B;
-        A.issue(P.lines, sa, odd);
-        B.issue(P.lines, sb, odd);
-        // ... and the heap entries of both lineages: index (first + (slot >> 6)) >> q for the q-th edge above the line (a
-        // climb that is over, or a level the tree does not have, reads an entry that is never added: entry 1 at the least)
-        const uint32_t ua = first + (sa >> kHeapLineEdges), ub = first + (sb >> kHeapLineEdges);
-        float ha[kHeapClimbMax], hb[kHeapClimbMax];
-#pragma unroll
-        for (int q = 0; q < kHeapClimbMax; q++) {
-            const uint32_t xa = ua >> q, xb = ub >> q;
-            ha[q] = H[xa ? xa : 1u];
-            hb[q] = H[xb ? xb : 1u];
-        }
-        const uint32_t x = sa ^ sb;
-        const int k = x ? 32 - __clz((int)x) : 0;      // edges either side climbs
-        A.settle(odd);                                 // (... and top values here: before the branch of the internal nodes)
-        B.settle(odd);
-        float s = A.add(0.0f, k);
-#pragma unroll
-        for (int q = 0; q < kHeapClimbMax; q++) s += kHeapLineEdges + q < k ? ha[q] : pad;
-        s = B.add(s, k);
-#pragma unroll
-        for (int q = 0; q < kHeapClimbMax; q++) s += kHeapLineEdges + q < k ? hb[q] : pad;
-        int m = k ? (int)((((((sa >> k) << 1) | 1u) << k)) - 1u) : (int)ida;
-        if (valid && !leaves) {      // an internal node (rare)
-            const PairResult r = pair_walk(P.nodes, P.depth, P.stride, (int32_t)ida, (int32_t)idb);
-            s = r.dist;
-            m = r.mrca;
-        }
-        // (converged: every lane of the workgroup is here, with consecutive pair numbers)
-        store_result_wave_as<NT>(out_d, out_m, i, valid ? s : __builtin_nanf(""), valid ? m : -1, live);
-    }
-}
-
+// The predicated kernel on heap lines (kernels_canopy_heap.h: the loop of the heap family over HeapSide)
 template <typename Src>
 __global__ __launch_bounds__(kCanopyBlock, 4) void k_canopy_ilp_heap(HeapParams P, Src src, long long n, DistSink out_d,
                                                                      MrcaSink out_m, Fault *fault)
@@ -688,12 +532,12 @@ __global__ __launch_bounds__(kCanopyBlock, 4) void k_canopy_ilp_heap(HeapParams 
     if constexpr (std::is_same<Src, SrcContig>::value) {
         // the loop's entry test in front of the choice: neither copy then keeps the other's
         if ((long long)blockIdx.x * blockDim.x >= n) return;
-        if (src.nt) heap_pairs<true>(P, src, n, out_d, out_m, fault, H);
-        else heap_pairs<false>(P, src, n, out_d, out_m, fault, H);
+        if (src.nt) heap_pairs<true, HeapSide>(P, src, n, out_d, out_m, fault, H);
+        else heap_pairs<false, HeapSide>(P, src, n, out_d, out_m, fault, H);
     } else {
         // the int32 source (the host path, never hinted by default) keeps the plain loop alone: with its format test in the loop a
         // second copy does not fit the scalar registers
-        heap_pairs<false>(P, src, n, out_d, out_m, fault, H);
+        heap_pairs<false, HeapSide>(P, src, n, out_d, out_m, fault, H);
     }
 }
 

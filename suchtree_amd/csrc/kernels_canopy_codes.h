@@ -1,6 +1,6 @@
 // kernels_canopy_codes.h -- k_canopy_ilp_codes: the predicated kernel on heap codes (tree_prep.h: prepare_heap_codes; perfect
-// trees whose edge lengths are six-decimal numbers, the headline tree among them).  The kernel of kernels_canopy.h's
-// heap_pairs with another table under it: the six lowest edges of a leaf's lineage come from ONE 128-byte line of 20-bit
+// trees whose edge lengths are six-decimal numbers, the headline tree among them).  heap_pairs of kernels_canopy_heap.h
+// with another table under it (CodeSide): the six lowest edges of a leaf's lineage come from ONE 128-byte line of 20-bit
 // codes that serves 24 leaf slots -- 5.33 MiB for 2^20 leaves where the float lines take 8, so that three of four line
 // lookups hit a 4 MiB L2 instead of two of four (scripts/l2_lru_model.py) --, the rest from the same heap image in LDS.
 // Two loads per node as there (a 16-byte window and a 16-byte top, 4-byte aligned, neither leaves its line, shared between
@@ -11,22 +11,9 @@
 #pragma once
 #include <type_traits>
 
-#include "device_common.h"
-#include "kernels_canopy.h"
-#include "pair_math.h"
-#include "tree_prep.h"
+#include "kernels_canopy_heap.h"
 
 namespace st {
-
-struct CodesParams {
-    const uint32_t *codes;         // [ceil(2^(D-3) / 3) * 32] heap codes
-    const float *dist;             // [heap_image_bytes(D) / 4] heap image, staged to LDS
-    const Node8 *nodes;            // the walk family's tables (pairs with an internal node)
-    const int32_t *depth;
-    const Stride3 *stride;
-    long long n_nodes;
-    int32_t levels;                // D: edges between a leaf and the root
-};
 
 typedef uint32_t __attribute__((ext_vector_type(4), aligned(4))) uint4_align4;      // a 16-byte load at any dword
 typedef float __attribute__((ext_vector_type(2))) float2_v;
@@ -42,7 +29,7 @@ __device__ __forceinline__ float2_v heap_code_decode2(uint32_t c0, uint32_t c1)
 }
 
 // The six line values of one leaf slot out of two 16-byte loads shared between lanes l and l ^ 1 (tree_prep.h:
-// heap_code_pair_word; HeapSide of kernels_canopy.h does the same on the float lines): either gather instruction reads the
+// heap_code_pair_word; HeapSide of kernels_canopy_heap.h does the same on the float lines): either gather instruction reads the
 // window of one of the two slots on its own lane and the top of the same slot on the lane beside it, so the L1 looks every
 // line up once (with every lane loading the window and the top of its own slot 0.45 of 2.58 L1-miss requests per pair were
 // second lookups of a line).  The loading lane shifts the neighbour's top down to its 60 bits and hands two dwords over by
@@ -91,60 +78,6 @@ struct CodeSide {
     }
 };
 
-// The kernel's loop over its pairs, NT: with the streaming hint on the pair load and the result stores (device_common.h), as
-// in heap_pairs -- one of two copies of the loop, chosen once.
-template <bool NT, typename Src>
-__device__ __forceinline__ void codes_pairs(const CodesParams &P, const Src &src, long long n, const DistSink &out_d, const MrcaSink &out_m,
-                                            Fault *fault, const float *H)
-{
-    const uint32_t first = 1u << (P.levels - kHeapLineEdges);      // heap index of slot block 0 at the lowest level of the image
-    const float pad = __uint_as_float(kChainPad);
-    const uint32_t odd = 0u - (threadIdx.x & 1u);      // the lane's parity as a mask (tree_prep.h: heap_pair_window_mask)
-    for (long long base = (long long)blockIdx.x * blockDim.x; base < n; base += (long long)gridDim.x * blockDim.x) {
-        const long long i = base + threadIdx.x;
-        const bool live = i < n;
-        long long ida, idb;
-        src.template load_as<NT>(live ? i : n - 1, ida, idb);
-        const bool valid = (unsigned long long)ida < (unsigned long long)P.n_nodes && (unsigned long long)idb < (unsigned long long)P.n_nodes;
-        if (!valid && live) record_fault(fault, ida, idb, P.n_nodes);
-        const bool leaves = valid && !((ida | idb) & 1);
-        // (anything else reads slot 0 and is answered below: no address depends on an id that was not checked)
-        const uint32_t sa = leaves ? (uint32_t)ida >> 1 : 0u, sb = leaves ? (uint32_t)idb >> 1 : 0u;
-        // every load of both lines before anything uses them (converged: the lane pairs exchange slots here ...)
-        CodeSide A, B;
-        A.issue(P.codes, sa, odd);
-        B.issue(P.codes, sb, odd);
-        // ... and the heap entries of both lineages: index (first + (slot >> 6)) >> q for the q-th edge above the line (a
-        // climb that is over, or a level the tree does not have, reads an entry that is never added: entry 1 at the least)
-        const uint32_t ua = first + (sa >> kHeapLineEdges), ub = first + (sb >> kHeapLineEdges);
-        float ha[kHeapClimbMax], hb[kHeapClimbMax];
-#pragma unroll
-        for (int q = 0; q < kHeapClimbMax; q++) {
-            const uint32_t xa = ua >> q, xb = ub >> q;
-            ha[q] = H[xa ? xa : 1u];
-            hb[q] = H[xb ? xb : 1u];
-        }
-        const uint32_t x = sa ^ sb;
-        const int k = x ? 32 - __clz((int)x) : 0;      // edges either side climbs
-        A.settle(odd);                                 // (... and tops here: before the branch of the internal nodes)
-        B.settle(odd);
-        float s = A.add(0.0f, k);
-#pragma unroll
-        for (int q = 0; q < kHeapClimbMax; q++) s += kHeapLineEdges + q < k ? ha[q] : pad;
-        s = B.add(s, k);
-#pragma unroll
-        for (int q = 0; q < kHeapClimbMax; q++) s += kHeapLineEdges + q < k ? hb[q] : pad;
-        int m = k ? (int)((((((sa >> k) << 1) | 1u) << k)) - 1u) : (int)ida;
-        if (valid && !leaves) {      // an internal node (rare)
-            const PairResult r = pair_walk(P.nodes, P.depth, P.stride, (int32_t)ida, (int32_t)idb);
-            s = r.dist;
-            m = r.mrca;
-        }
-        // (converged: every lane of the workgroup is here, with consecutive pair numbers)
-        store_result_wave_as<NT>(out_d, out_m, i, valid ? s : __builtin_nanf(""), valid ? m : -1, live);
-    }
-}
-
 template <typename Src>
 __global__ __launch_bounds__(kCanopyBlock, 4) void k_canopy_ilp_codes(CodesParams P, Src src, long long n, DistSink out_d,
                                                                       MrcaSink out_m, Fault *fault)
@@ -160,11 +93,11 @@ __global__ __launch_bounds__(kCanopyBlock, 4) void k_canopy_ilp_codes(CodesParam
     }
     if constexpr (std::is_same<Src, SrcContig>::value) {
         if ((long long)blockIdx.x * blockDim.x >= n) return;
-        if (src.nt) codes_pairs<true>(P, src, n, out_d, out_m, fault, H);
-        else codes_pairs<false>(P, src, n, out_d, out_m, fault, H);
+        if (src.nt) heap_pairs<true, CodeSide>(P, src, n, out_d, out_m, fault, H);
+        else heap_pairs<false, CodeSide>(P, src, n, out_d, out_m, fault, H);
     } else {
         // the int32 source (the host path, never hinted by default) keeps the plain loop alone, as in k_canopy_ilp_heap
-        codes_pairs<false>(P, src, n, out_d, out_m, fault, H);
+        heap_pairs<false, CodeSide>(P, src, n, out_d, out_m, fault, H);
     }
 }
 

@@ -16,6 +16,7 @@
 #include "launch_decl.h"
 #include "launch_policy.h"
 #include "kernels_canopy.h"
+#include "launch_canopy_heap.h"
 #include "launch_canopy_sorted.h"
 
 namespace st {
@@ -82,32 +83,6 @@ static hipError_t launch_canopy_ladder(const st_tree *t, const CanopyParams &P, 
     return e;
 }
 
-// k_canopy_ilp_heap: one 1024-lane workgroup per CU (the heap image of 2^20 leaves takes 128 KiB of LDS)
-template <typename Src>
-static hipError_t launch_canopy_heap(const st_tree *t, const Src &src, int64_t n, DistSink out_d, MrcaSink out_m,
-                                     Fault *fault, hipStream_t stream)
-{
-    HeapParams H;
-    H.lines = t->d_heap_lines;
-    H.dist = t->d_heap_dist;
-    H.nodes = t->d_nodes;
-    H.depth = t->d_depth;
-    H.stride = t->d_stride;
-    H.n_nodes = t->n_nodes;
-    H.levels = t->heap_levels;
-    const size_t lds = heap_image_bytes(t->heap_levels);
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_canopy_ilp_heap<Src>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    int64_t blocks = std::min<int64_t>((n + kCanopyBlock - 1) / kCanopyBlock, (int64_t)t->n_cu);
-    blocks = std::max<int64_t>(blocks, 1);
-    hipLaunchKernelGGL(k_canopy_ilp_heap<Src>, dim3((unsigned)blocks), dim3(kCanopyBlock), lds, stream, H, src, (long long)n,
-                       out_d, out_m, fault);
-    return hipGetLastError();
-}
-
 template <int CAP, typename Src>
 static hipError_t launch_canopy_t(const st_tree *t, const CanopyParams &P, const Src &src, int64_t n,
                                   DistSink out_d, MrcaSink out_m, Fault *fault, hipStream_t stream, int *choice)
@@ -135,7 +110,7 @@ static hipError_t launch_canopy_t(const st_tree *t, const CanopyParams &P, const
         if constexpr (std::is_same<Src, SrcContig>::value || std::is_same<Src, SrcContig32>::value) {
             // ... and on perfect trees with heap lines both sides from 128-byte lines that hold every edge once
             if (out_d.any() && heap_codes_applies(t, n)) return launch_canopy_codes(t, src, n, out_d, out_m, fault, stream);      // (... or from lines of 20-bit codes: launch_canopy_codes.hip)
-            if (out_d.any() && heap_lines_applies(t)) return launch_canopy_heap(t, src, n, out_d, out_m, fault, stream);
+            if (out_d.any() && heap_lines_applies(t)) return launch_heap_family(k_canopy_ilp_heap<Src>, t->d_heap_lines, t, src, n, out_d, out_m, fault, stream);
             if (P.rec_a4 && P.leaf_blocks)
                 return launch_canopy_k(k_canopy_ilp<CAP, 1, Src, true>, 1, t, P, src, n, out_d, out_m, fault, stream,
                                        canopy_lds_bytes(t) + leaf_block_image_bytes(P.leaf_block_count));

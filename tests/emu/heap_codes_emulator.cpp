@@ -3,15 +3,13 @@
 // Runs the product's heap-code table (suchtree_amd/csrc/tree_prep.cpp: prepare_heap_codes) and the place, extraction and
 // decoding functions k_canopy_ilp_codes uses over it (tree_prep.h) on the host: a lane's two loads become bounds-checked
 // copies of 16 bytes out of the table (on the lane itself, and shared between two lanes as CodeSide shares them), everything after them is the kernel's own code.  codes_emu_distances is the
-// kernel's pair function over the table and the heap image, one pair at a time (pairs with an internal node are walked on
-// the tree, as the kernel does).  Never loaded by suchtree_amd.
+// kernel's pair function over the table and the heap image (heap_pair_emu.h).  Never loaded by suchtree_amd.
 #include <cstdint>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "../../suchtree_amd/csrc/pair_math.h"
-#include "../../suchtree_amd/csrc/tree_prep.h"
+#include "heap_pair_emu.h"
 
 using namespace st;
 
@@ -78,15 +76,6 @@ static bool lane_pair_codes(const uint32_t *table, int64_t n_words, const uint32
     return true;
 }
 
-static inline float add_if(float s, bool on, float e)
-{
-    const uint32_t pad_bits = 0x80000000u;      // -0.0f: the identity of a float add
-    float pad;
-    std::memcpy(&pad, &pad_bits, 4);
-    volatile float r = s + (on ? e : pad);
-    return r;
-}
-
 extern "C" {
 
 const char *codes_emu_last_error() { return g_err.c_str(); }
@@ -148,34 +137,12 @@ int codes_emu_distances(const int32_t *parent, const float *distance, int64_t n_
     TreeTables T;
     if (!prepare_basic(parent, distance, n_nodes, T, g_err)) return 1;
     if (!prepare_heap_lines(T) || !prepare_heap_codes(T)) { g_err = "heap codes not admitted"; return 2; }
-    const int64_t n_words = (int64_t)T.heap_codes.size();
-    for (int64_t i = 0; i < n; i++) {
-        const int64_t a = pairs[2 * i], b = pairs[2 * i + 1];
-        if (a < 0 || a >= n_nodes || b < 0 || b >= n_nodes) { g_err = "id out of range"; return 3; }
-        if ((a | b) & 1) {
-            const PairResult r = pair_walk(T.nodes.data(), T.depth.data(), T.stride.data(), (int32_t)a, (int32_t)b);
-            out_d[i] = (double)r.dist;
-            out_m[i] = r.mrca;
-            continue;
-        }
-        const uint32_t sa = (uint32_t)a >> 1, sb = (uint32_t)b >> 1, x = sa ^ sb;
-        int k = 0;
-        while (k < 32 && (x >> k)) k++;
-        float s = 0.0f;
-        for (const uint32_t sl : {sa, sb}) {
-            uint32_t c[6];
-            if (!slot_codes(T.heap_codes.data(), n_words, sl, c)) return 4;
-            for (int j = 0; j < 6; j++) s = add_if(s, j < k, heap_code_decode_f32(c[j]));
-            uint32_t u = (1u << (T.heap_levels - 6)) + (sl >> 6);
-            for (int q = 6; q < k; q++) {
-                s = add_if(s, true, T.heap_dist[u]);
-                u >>= 1;
-            }
-        }
-        out_d[i] = (double)s;
-        out_m[i] = k ? (int32_t)((((((sa >> k) << 1) | 1u) << k)) - 1u) : (int32_t)a;
-    }
-    return 0;
+    return heap_pairs_emu(T, n_nodes, pairs, n, out_d, out_m, g_err, [&T](uint32_t sl, float *e) {
+        uint32_t c[6];
+        if (!slot_codes(T.heap_codes.data(), (int64_t)T.heap_codes.size(), sl, c)) return false;
+        for (int j = 0; j < 6; j++) e[j] = heap_code_decode_f32(c[j]);
+        return true;
+    });
 }
 
 }  // extern "C"

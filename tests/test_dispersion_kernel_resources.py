@@ -2,37 +2,18 @@
 task forms (packed, one wave, one workgroup) and the two instantiations of the sigma kernel (256 and 1024 lanes) keep
 nothing in scratch memory and spill no register.  The VGPR counts are those DESIGN.md section 18 records."""
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
-from conftest import ROOT
-
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from kernel_resources import HIPCC, resources
 
 VGPRS = {"k_dispersion_tasks_packed": 32, "k_dispersion_tasks_wave": 30, "k_dispersion_tasks_group": 27,
          "k_dispersion_sigmaILi256E": 16, "k_dispersion_sigmaILi1024E": 16}
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_dispersion_kernels_use_no_scratch_and_spill_nothing(tmp_path):
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
-                          "-I", os.path.join(ROOT, "include"), "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage",
-                          "-o", str(tmp_path / "unit.o"), os.path.join(ROOT, "suchtree_amd", "csrc", "suchtree_hip.hip")],
-                         capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-3000:]
-    res, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        for key, pattern in (("vgpr", r"\bVGPRs: (\d+)"), ("vgpr_spill", r"VGPRs Spill: (\d+)"), ("sgpr_spill", r"SGPRs Spill: (\d+)"),
-                             ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)")):
-            m = re.search(pattern, line)
-            if m and name:
-                res.setdefault(name, {})[key] = int(m.group(1))
+def test_dispersion_kernels_use_no_scratch_and_spill_nothing():
+    res = resources("suchtree_hip.hip")
     mine = {k: v for k, v in res.items() if "k_dispersion" in k}
     assert len(mine) == len(VGPRS), sorted(mine)
     for kernel, vgprs in VGPRS.items():

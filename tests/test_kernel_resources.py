@@ -3,43 +3,17 @@ gfx950 code objects).  A 1024-lane workgroup needs <= 128 VGPRs to launch at all
 a cold path inlined into a hot kernel has pushed one over that line before (round 4: the pipelined chain sum in
 the shared-portal path took k_canopy_ladder<15> from 51 to 77 VGPRs and ml.tree from 2.85e10 to 1.92e10 pairs/s)."""
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
-from conftest import ROOT
-
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-CSRC = os.path.join(ROOT, "suchtree_amd", "csrc")
-
-
-def _resources(unit, tmp_path):
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
-                          "-I", os.path.join(ROOT, "include"), "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage",
-                          "-o", str(tmp_path / "unit.o"), os.path.join(CSRC, unit)], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-3000:]
-    res, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"\bVGPRs: (\d+)", line)
-        if m and name:
-            res.setdefault(name, {})["vgpr"] = int(m.group(1))
-        m = re.search(r"TotalSGPRs: (\d+)", line)
-        if m and name:
-            res.setdefault(name, {})["sgpr"] = int(m.group(1))
-        m = re.search(r"VGPRs Spill: (\d+)", line)
-        if m and name:
-            assert int(m.group(1)) == 0, (name, "spills")
-    return res
+from kernel_resources import HIPCC, resources
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_register_budgets_of_the_canopy_kernels(tmp_path):
-    v = _resources("launch_canopy.hip", tmp_path)
+def test_register_budgets_of_the_canopy_kernels():
+    v = resources("launch_canopy.hip")
+    for k, n in v.items():
+        assert n["vgpr_spill"] == 0, (k, "spills")
 
     def of(fragment):
         hits = {k: n for k, n in v.items() if fragment in k}

@@ -3,34 +3,15 @@
 counts are indexed by constants only, so they stay in registers -- and stay at or below 64 VGPRs, so that eight waves
 per SIMD hide the latency of their loads."""
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
-from conftest import ROOT
-
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from kernel_resources import HIPCC, resources
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_quartet_kernels_use_no_scratch_and_at_most_64_vgprs(tmp_path):
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
-                          "-I", os.path.join(ROOT, "include"), "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage",
-                          "-o", str(tmp_path / "unit.o"), os.path.join(ROOT, "suchtree_amd", "csrc", "suchtree_hip.hip")],
-                         capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-3000:]
-    res, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        for key, pattern in (("vgpr", r"\bVGPRs: (\d+)"), ("vgpr_spill", r"VGPRs Spill: (\d+)"), ("sgpr_spill", r"SGPRs Spill: (\d+)"),
-                             ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)")):
-            m = re.search(pattern, line)
-            if m and name:
-                res.setdefault(name, {})[key] = int(m.group(1))
+def test_quartet_kernels_use_no_scratch_and_at_most_64_vgprs():
+    res = resources("suchtree_hip.hip")
     mine = {k: v for k, v in res.items() if "k_quartet_draw" in k or "k_quartet_agree" in k}
     assert len(mine) == 3, sorted(mine)      # (draw: ST_QUARTET_ALL and ST_QUARTET_SAMPLE; agree)
     for k, v in mine.items():
