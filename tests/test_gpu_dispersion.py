@@ -1,5 +1,6 @@
 """The partner-dispersion kernels on the GPU: st_dispersion_matrix(device = 0) against its host restatement bit for bit
-over the size-class edges, the tree path (st_partner_dispersion_host) on fish_worm, and the facade
+over the size-class edges (the packed class of 6 .. 30 positions among them), universes on both sides of every sort's
+limit up to 8193 positions (more than 128 KiB of sort keys), the tree path (st_partner_dispersion_host) on fish_worm, and the facade
 (SuchTree.dispersion, SuchLinkedTrees.partner_dispersion).  The bounds are those of tests/test_dispersion_host.py:
 relative k^2 2^-52 for MPD and k 2^-52 for MNTD."""
 import numpy as np
@@ -11,7 +12,7 @@ from suchtree_amd import SuchLinkedTrees, SuchTree, _capi, compare
 
 pytestmark = pytest.mark.gpu
 
-SIZES = (2, 3, 4, 5, 31, 32, 33, 63, 64, 65, 255, 256, 257, 513)
+SIZES = (2, 3, 4, 5, 8, 9, 16, 17, 31, 32, 33, 63, 64, 65, 255, 256, 257, 513)
 
 
 def _matrix(n, seed):
@@ -31,14 +32,14 @@ def _sets(n, sizes, seed):
 def cases():
     """(D, sets, the host restatement's records at 17 permutations) per universe size: computed once, never changed."""
     out = {}
-    for n in (3, 64, 65, 2049):
+    for n in (3, 64, 65, 129, 2048, 2049):
         D, sets = _matrix(n, n), _sets(n, SIZES, n + 1)
         out[n] = (D, sets, _capi.dispersion_matrix(D, sets, 17, 4242 + n, stream=6, device=-1))
     return out
 
 
 @pytest.mark.parametrize("perms", [0, 1, 17])
-@pytest.mark.parametrize("n", [3, 64, 65, 2049])
+@pytest.mark.parametrize("n", [3, 64, 65, 129, 2048, 2049])
 def test_kernels_equal_the_restatement(cases, n, perms):
     D, sets, want = cases[n]
     want = np.ascontiguousarray(want[:, : perms + 1])      # (the prefix property of the restatement: test_dispersion_host.py)
@@ -66,6 +67,21 @@ def test_special_values_and_large_universe():
     got = _capi.dispersion_matrix(D, sets, 1, 5, device=0)
     assert got.tobytes() == want.tobytes()
     assert np.isnan(want["pair_sum"][-1]).all() and np.isfinite(want["nearest_sum"][-1]).all()      # NaN entries: summed, never a minimum
+
+
+def test_universe_above_8192_positions():
+    """8193 positions: k_dispersion_sigma<1024> with more than 8 keys per lane (128 KiB of sort keys and more)."""
+    n = 8193
+    i = np.arange(n, dtype=np.int32)
+    D = ((i[:, None] * 31 + i[None, :] * 17) % 1009).astype(np.float32)
+    rng = np.random.default_rng(8193)
+    sets = [np.sort(rng.choice(n, k, replace=False)) for k in (2, 16, 65, 300)]
+    want = _capi.dispersion_matrix(D, sets, 2, 8193, stream=3, device=-1)
+    assert want.shape == (4, 3)
+    for chunk in (0, 3):
+        got = _capi.dispersion_matrix(D, sets, 2, 8193, stream=3, device=0, chunk_tasks=chunk)
+        assert got.tobytes() == want.tobytes(), "chunk_tasks %d" % chunk
+    assert want[:, 1].tobytes() != want[:, 0].tobytes() and want[:, 2].tobytes() != want[:, 1].tobytes()      # the draws differ
 
 
 def _slt(which):

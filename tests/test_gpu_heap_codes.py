@@ -2,12 +2,15 @@
 against the oracle, by bits: every leaf pair of 6- and 7-level trees in order and shifted by one position (each pair on an even
 and on an odd lane), every sink, both pair sources, with and without the streaming hint, tail tiles, internal nodes, equal ids
 and ids out of range beside leaf pairs, the form against the heap lines on the same handle, a tree that is refused, and what a
-default handle reports.  Batches have at least 4096 pairs (smaller ones go to the walk family and never reach the kernel)."""
+default handle reports.  Batches have at least 4096 pairs (smaller ones go to the walk family and never reach the kernel).  The mixed
+batch and the sinks between canaries are those of tests/heap_pair_cases.py; deeper trees, every k, more pairs than one trip of the
+grid and the default policy are in tests/test_gpu_heap_codes_depth.py."""
 import numpy as np
 import pytest
 
 from conftest import assert_bits_equal, oracle_both
-from suchtree_amd import _capi, sharding, synth
+from heap_pair_cases import _check_against_oracle, _device_sinks, _mixed_pairs
+from suchtree_amd import _capi, synth
 from suchtree_amd.exceptions import InvalidNodeError
 
 pytestmark = pytest.mark.gpu
@@ -22,21 +25,6 @@ def _codes_handle(parent, dist):
     dev.set_option("heap_lines", 2)
     dev.set_option("heap_codes", 2)
     return dev
-
-
-def _mixed_pairs(n_nodes, n, seed):
-    """Leaf pairs, pairs with internal nodes, equal ids and neighbours, shuffled."""
-    rng = np.random.default_rng(seed)
-    leaves = (n_nodes + 1) // 2
-    q = n // 4
-    rand = rng.integers(0, leaves, (n - 3 * q, 2)) * 2
-    internal = rng.integers(0, n_nodes, (q, 2))
-    internal[::3, 0] = rng.integers(0, leaves, len(internal[::3])) * 2
-    same = np.repeat(rng.integers(0, n_nodes, q)[:, None], 2, axis=1)
-    a = rng.integers(0, leaves, q)
-    near = np.stack([a, np.clip(a + rng.integers(-3, 4, q), 0, leaves - 1)], axis=1) * 2
-    pairs = np.concatenate([rand, internal, same, near]).astype(np.int64)
-    return np.ascontiguousarray(pairs[rng.permutation(len(pairs))])
 
 
 @pytest.fixture(scope="module", params=[6, 7])
@@ -62,38 +50,6 @@ def codes_tree(request):
         want[name] = (d, m)
     yield levels, dev, batches, want
     dev.close()
-
-
-def _device_sinks(dev, t_pairs, n):
-    """float64 + int32, float32 + int32 and the wire form (float32 + packed ids) for the first n pairs, between canaries."""
-    import torch
-    ptr = t_pairs.data_ptr()
-    pb = sharding.packed_bytes(n)
-    d64 = torch.full((n + 8,), -7.0, dtype=torch.float64, device="cuda")
-    m_a = torch.full((n + 8,), -9, dtype=torch.int32, device="cuda")
-    dev.distances_device(ptr, n, d64.data_ptr() + 4 * 8, m_a.data_ptr() + 4 * 4)
-    f32 = torch.full((n + 8,), -7.0, dtype=torch.float32, device="cuda")
-    m_b = torch.full((n + 8,), -9, dtype=torch.int32, device="cuda")
-    dev.distances_device(ptr, n, f32.data_ptr() + 4 * 4, m_b.data_ptr() + 4 * 4, f32=True)
-    w32 = torch.full((n + 8,), -7.0, dtype=torch.float32, device="cuda")
-    m24 = torch.full((16 + pb + 16,), 0xEE, dtype=torch.uint8, device="cuda")
-    dev.distances_device_wire(ptr, n, w32.data_ptr() + 4 * 4, m24.data_ptr() + 16)
-    m_c = torch.full((n + 8,), -9, dtype=torch.int32, device="cuda")
-    dev.unpack_mrca24_device(m24.data_ptr() + 16, n, m_c.data_ptr() + 4 * 4)
-    dev.fault_check()
-    for buf, canary in ((d64, -7.0), (f32, -7.0), (w32, -7.0), (m_a, -9), (m_b, -9), (m_c, -9)):
-        assert bool((buf[:4] == canary).all()) and bool((buf[n + 4:] == canary).all()), "a store outside [0, n)"
-    assert bool((m24[:16] == 0xEE).all()) and bool((m24[16 + pb:] == 0xEE).all()), "a store outside the packed ids"
-    return [x[4:n + 4].cpu().numpy() for x in (d64, m_a, f32, m_b, w32, m_c)]
-
-
-def _check_against_oracle(got, want_d, want_m, what):
-    d64, m_a, f32, m_b, w32, m_c = got
-    assert_bits_equal(d64, want_d, what + ": float64 sink")
-    assert_bits_equal(f32.astype(np.float64), want_d, what + ": float32 sink")
-    assert_bits_equal(w32.astype(np.float64), want_d, what + ": wire sink")
-    for m in (m_a, m_b, m_c):
-        assert np.array_equal(m, want_m), what
 
 
 def _set_hint(dev, hint):

@@ -1,6 +1,7 @@
 """Hommola's permutation test for every clade in one GPU pass (SuchLinkedTrees.hommola_by_clade, C ABI
 st_hommola_clades_host).  The yardsticks are the existing st_compare_rows_host -- on the id rows that the numpy
-restatement of the definitions gives (tests/hommola_clade_reference.py), bit for bit -- and hommola_cospeciation."""
+restatement of the definitions gives (tests/hommola_clade_reference.py), bit for bit -- and hommola_cospeciation.  Universes
+go up to 4096 leaves (the default cap) and to 8200 (k_hommola_relabel<1024> above 8192 positions, 128 KiB of sort keys)."""
 import numpy as np
 import pandas as pd
 import pytest
@@ -214,6 +215,20 @@ def test_largest_universe_of_the_default_cap():
     res = S.hommola_by_clade(permutations=5, seed=31, keep_stats=True, nodes=[root])      # (no two links on one leaf: the same layout)
     r = row_stats(got["n"], *(got[k] for k in _SUMS))[5]
     assert res.n_leaves.tolist() == [4096] and abs(res.corr_coeff[0] - r[0, 0]) < 1e-5 and res.perm_stats[0].tobytes() == r[0, 1:].tobytes()
+
+
+def test_universe_above_8192_leaves():
+    """8200 leaves under the root of a random tree: the relabelling sort with more than 8 keys per lane."""
+    ta, tb = synth.random_binary_tree(40, seed=5), synth.random_binary_tree(8200, seed=7)
+    rng = np.random.default_rng(14)
+    pairs = sorted(zip((rng.integers(0, 40, 150) * 2).tolist(), (rng.choice(8200, 150, replace=False) * 2).tolist()), key=lambda t: t[1])
+    S = _system(ta, tb, pairs)
+    layout = ref.Layout(S.TreeB._flat.parent, S.TreeA._flat.parent, np.array([b for _, b in pairs]), np.array([a for a, _ in pairs]))
+    root = int(S.TreeB.root_node)
+    assert layout.leaf_count[root] == 8200 > 8192 and layout.links(root)[1] == 150
+    got = _low_level(S, layout, [root], 2, 32)
+    assert got.shape == (1, 3)
+    _check_rows(S, layout, [root], got, 2, 32)
 
 
 @pytest.mark.parametrize("n", [1, 2, 3, 63, 64, 65, 2047, 2048, 2049, 16383, 16384])

@@ -1,6 +1,7 @@
 """Exact Kendall tau-b on the GPU (compare_distances(kendall=True), linked_distances_summary(kendall=True), C ABI
 st_compare_*_kendall_host, st_kendall_arrays_host): the integer counts against st_kendall_host on the oracle's float32
-distances -- equal, not close -- and kendall_tau against scipy."""
+distances -- equal, not close -- and kendall_tau against scipy; tie runs that span hundreds of blocks of sorted keys, so that
+a thread of k_kendall_tie_carry owns two or three blocks and carries a run start across blocks that hold none."""
 import dataclasses
 import math
 import os
@@ -11,7 +12,7 @@ import pytest
 from scipy.stats import kendalltau
 
 from conftest import golden_path
-from kendall_reference import heavy_columns
+from kendall_reference import heavy_columns, tie_sum
 from oracle.oracle import OracleTree
 from rank_reference import bit_reverse
 from suchtree_amd import SuchTree, _capi, synth
@@ -159,6 +160,23 @@ def test_arrays_against_the_host_at_the_tile_edges(n):
     _same_counts(_capi.kendall_arrays_host(x, y), _capi.kendall_host(x, y))
     hx, hy = heavy_columns(n, 200 + n, values=5)             # tie groups that span tiles and runs
     _same_counts(_capi.kendall_arrays_host(hx, hy), _capi.kendall_host(hx, hy))
+
+
+@pytest.mark.parametrize("blocks, per", [(300, 2), (600, 3)])
+def test_tie_runs_over_more_blocks_than_the_carry_kernel_has_threads(blocks, per):
+    """k_kendall_tie_carry: 256 threads own per = ceil(n_blocks / 256) consecutive blocks each.  Two tie groups in x, two
+    thirds and one third of the keys: all but two blocks of a column's sorted keys hold no run start of x, so the running
+    maximum of a thread's last loop has to pass an earlier block's start on."""
+    n = blocks * T + (5 if per == 2 else 1)
+    n_blocks = -(-n // T)
+    assert n_blocks == blocks + 1 and -(-n_blocks // 256) == per
+    x, y = heavy_columns(n, 300 + blocks, values=2)
+    groups = np.unique(x, return_counts=True)[1]
+    assert len(groups) == 2 and groups.min() > 64 * T      # (-0.0 and +0.0 are one group)
+    want = _capi.kendall_host(x, y)
+    got = _capi.kendall_arrays_host(x, y)
+    _same_counts(got, want)
+    assert (got.ties_x, got.ties_y) == (tie_sum(x), tie_sum(y))
 
 
 def test_arrays_reversed_equal_zeros_infinities_and_nan():

@@ -1,5 +1,6 @@
 """The UniFrac kernels on the GPU: st_unifrac_depths(device = 0) against its host restatement, integer for integer, on the
-shapes of tests/test_unifrac_host.py and on both sides of the lane / wave threshold; st_unifrac_host on a golden tree with
+shapes of tests/test_unifrac_host.py, on both sides of the lane / wave threshold and with more heavy pairs in a chunk than the
+wave kernel's fixed grid has waves (its loop's second trip); st_unifrac_host on a golden tree with
 an internal node as root; and the facade (SuchTree.unifrac, SuchLinkedTrees.partner_unifrac).  Every comparison of
 integers is exact."""
 import numpy as np
@@ -67,6 +68,23 @@ def test_threshold_chunks_of_one_kind_and_a_range_from_mid_row():
     # a wave-form set of 1000 positions against a set of one, an empty one and itself
     wide = [np.arange(n), np.array([5]), np.array([], dtype=np.int64), np.arange(n)]
     _same(_capi.unifrac_depths(d, h, wide, device=0), _capi.unifrac_depths(d, h, wide, device=-1), "1000 against 1")
+
+
+def test_more_heavy_pairs_in_a_chunk_than_the_wave_grid_has_waves():
+    """k_unifrac_wave drains a chunk's heavy list with kUnifracWaveBlocks * 4 = 8192 waves: 8385 heavy pairs in one chunk take
+    the first 193 waves through `w += waves` once; chunks of 8256 and 129 pairs take two trips and one."""
+    n, waves = 600, 2048 * 4      # unifrac_plan.h: kUnifracWaveBlocks workgroups of kUnifracThreads / 64 waves
+    _, _, _, d, h, _ = uc.case(n)
+    rng = np.random.default_rng(78)
+    sets = [np.sort(rng.choice(n, LANE_MAX // 2 + 1, replace=False)) for _ in range(130)]
+    pairs = len(sets) * (len(sets) - 1) // 2
+    assert pairs == 8385 > waves
+    assert all(len(a) + len(b) > LANE_MAX for a in sets for b in sets)      # every pair and every PD task is heavy
+    want = _capi.unifrac_depths(d, h, sets, device=-1)
+    assert len(want[0]) == 130 and len(want[1]) == pairs
+    _same(_capi.unifrac_depths(d, h, sets, device=0), want, "one chunk of 8385 heavy pairs")
+    assert waves < 8256 < pairs
+    _same(_capi.unifrac_depths(d, h, sets, device=0, chunk_pairs=8256), want, "chunks of 8256 and 129 heavy pairs")
 
 
 def test_seventeen_table_levels():

@@ -1,7 +1,9 @@
 """Heap codes of perfect trees (tree_prep.cpp: prepare_heap_codes; tree_prep.h: the place, extraction and decoding functions
 of k_canopy_ilp_codes) on the CPU (tests/emu/heap_codes_emulator.cpp, compiled with g++ over the same functions): the decoder
 over all 2^20 codes, the table of 6- to 9-level trees leaf slot by leaf slot, the extreme codes, the trees that must be
-refused, and the kernel's pair function against the oracle, by bits."""
+refused, and the kernel's pair function against the oracle, by bits: every node pair of small trees, uniform pairs of 2^14
+leaves, and at 8, 13, 19 and 20 levels every k (tests/heap_pair_cases.py: by_k_pairs, grouped and shuffled) and the slots at the
+edges of the code lines (edge_slot_pairs) -- the index arithmetic of tests/emu/heap_pair_emu.h and tree_prep.h at depth."""
 import ctypes
 import os
 import subprocess
@@ -10,6 +12,8 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, assert_bits_equal, oracle_both
+from heap_pair_cases import by_k_pairs, edge_slot_pairs, oracle_answers
+from oracle.oracle import OracleTree
 from suchtree_amd import synth
 
 PAD_WORDS = 4      # tree_prep.h: kHeapCodePadWords
@@ -209,3 +213,23 @@ def test_random_leaf_pairs_of_2_14_leaves_against_the_oracle(emu):
     d, m = emu.run(parent, dist, pairs)
     assert_bits_equal(d, want_d)
     assert np.array_equal(m, want_m)
+
+
+@pytest.mark.parametrize("levels", [8, 13, 19, 20])
+def test_every_k_and_the_edge_slots_at_depth_against_the_oracle(emu, levels):
+    """The climb through the heap image has levels - 6 terms per side: 2, 7, 13 and 14 here (uniform pairs of a deep tree
+    take nearly all of them nearly always: by_k_pairs stops after each number of them equally often)."""
+    parent, dist = synth.balanced_tree(levels)
+    grouped, shuffled = by_k_pairs(levels, 2048, seed=100 + levels)
+    batches = (("every k, grouped", grouped), ("every k, shuffled", shuffled), ("edge slots", edge_slot_pairs(levels, seed=200 + levels)))
+    pairs = np.concatenate([b for _, b in batches])
+    want_d, want_m = oracle_answers(OracleTree(parent, dist), pairs)
+    d, m = emu.run(parent, dist, pairs)      # (one call: the emulator prepares the tree's tables in every call)
+    lo = 0
+    for what, b in batches:
+        hi = lo + len(b)
+        assert_bits_equal(d[lo:hi], want_d[lo:hi], "%d levels, %s" % (levels, what))
+        assert np.array_equal(m[lo:hi], want_m[lo:hi]), (levels, what)
+        lo = hi
+    x = (grouped[:, 0] >> 1) ^ (grouped[:, 1] >> 1)
+    assert int(x.max()).bit_length() == levels and np.count_nonzero(x == 0) == 2048      # k from 0 to the root
