@@ -50,7 +50,7 @@ extern "C" {
  *      st_partner_dispersion_host and st_dispersion_matrix; then, also additive, ST_UNIFRAC_MAX_UNIVERSE,
  *      ST_UNIFRAC_LANE_MAX, st_unifrac_host, st_unifrac_depths and st_unifrac_quantise; then st_tree_info.heap_codes appended
  *      (8 bytes) with option "heap_codes", as heap_lines was; then, also additive, ST_CLADE_MATCH_MAX_LEAVES, st_clade_ranges
- *      and st_clade_match.
+ *      and st_clade_match; then, also additive, st_beta_dispersion_host and st_beta_dispersion_matrix.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -543,6 +543,64 @@ int st_partner_dispersion_host(st_tree *tree, const int64_t *univ, int32_t n_uni
 int st_dispersion_matrix(int device, const float *D, int32_t n, const int32_t *set_pos, int64_t n_pos, const int64_t *sets,
                          int64_t n_sets, int64_t permutations, uint64_t seed, int32_t stream, int64_t chunk_tasks,
                          st_dispersion_record *out);
+
+/*
+ * How far apart are the members of two sets of leaves: the sums behind betaMPD (the mean distance between a member of one
+ * set and a member of the other) and betaMNTD (the mean distance from a member to the nearest member of the other set) of
+ * pairs of sets, each with the taxa-labels null of st_partner_dispersion_host (picante's comdist / comdistnt with
+ * abundance.weighted = FALSE and exclude.conspecifics = exclude_shared; standardised, betaNRI and betaNTI).
+ * SuchLinkedTrees.partner_beta_dispersion asks it of every two leaves' partners; SuchTree.beta_dispersion of any sets.
+ *
+ * The universe, D (both triangles kept), the sets, sigma_p, stream and seed are exactly those of
+ * st_partner_dispersion_host; p = 0 is the identity.  Sets of 0 or 1 positions are allowed.
+ *
+ * Pairs.  Unordered pairs of sets (i, j), j < i, in the triangle order k = i (i - 1) / 2 + j of st_unifrac_host; a call
+ * covers [begin, begin + count).
+ *
+ * Directions.  A pair has two: i -> j, then j -> i.  For direction r -> c under permutation p, q_a = sigma_p[s^r_a] for
+ * a < k_r and q'_b = sigma_p[s^c_b] for b < k_c.  Entry (a, b) is included unless exclude_shared != 0 and s^r_a == s^c_b:
+ * the comparison is on positions, so it does not depend on p.
+ *     rowsum_a = sum over included b ascending of (double) D[q_a][q'_b], one by one from 0.0;
+ *     rowmin_a = m after: m = +inf; for included b ascending: v = D[q_a][q'_b]; m = v < m ? v : m
+ *                (the NaN and -0.0 rule of the dispersion record);
+ *     an element with no included entry adds +0.0 to both sums: only when k_c == 0, or when exclude_shared is set,
+ *     k_c == 1 and the single member is shared -- decided by the sets, never by the value of m;
+ *     cross_sum = sum over a of rowsum_a,  nearest_sum = sum over a of (double) rowmin_a,
+ * in the order over a of the dispersion record with k = k_r: k_r <= 64 the K'-lane butterfly, K' = max(2, the next power
+ * of two >= k_r), absent lanes +0.0; k_r > 64 the 256 striding lanes, four wave butterflies, ((w0 + w1) + w2) + w3.
+ * k_r == 0 gives a record of zeros.
+ *
+ * Output.  out holds count x 2 x (permutations + 1) records of st_dispersion_record, pair_sum holding cross_sum:
+ * out[((k - begin) * 2 + dir) * (permutations + 1) + p].  A record depends on (seed, stream, p, D, set r, set c,
+ * exclude_shared) alone -- not on the range, the other sets, permutations, chunk_tasks, the grid or the device; column p
+ * is the same for any permutations >= p.  No float atomics.
+ *
+ * The caller forms, with s = |S_i and S_j| and e = exclude_shared ? s : 0:
+ *     beta_mpd  = (cross_ij + cross_ji) / (2 (k_i k_j - e)),
+ *     beta_mntd = (near_ij + near_ji) / (k_i + k_j - z),  z = the number of elements with no included entry,
+ * either NaN where its denominator is 0.  With D[a][b] = |a - b| on 5 positions, A = {0, 1, 4} and B = {1, 2}: A -> B is
+ * (cross, near) = (9, 3) and B -> A (9, 1), beta_mpd 1.5 and beta_mntd 0.8; with exclude_shared (9, 4) and (9, 2), 1.8
+ * and 1.2.
+ *
+ * Errors are those of the dispersion pair, checked in its order (the universe size, negative permutations, chunk_tasks
+ * or stream, the set table), then the range: a negative begin or count, a range outside the triangle, more than 2^31
+ * pairs, more than 2^40 records (ST_ERR_ARG); the universe ids (ST_ERR_BOUNDS with *bad_id); an allocation that fails
+ * is ST_ERR_NOMEM with the bytes asked for, before out is written.  Beside the dispersion call's memory the host and the
+ * device hold 16 bytes per direction of the range.  chunk_tasks counts (direction, permutation) tasks.  Zero pairs, or
+ * none with a member on both sides, launch nothing.
+ *
+ * st_beta_dispersion_matrix is the same reduction over the caller's matrix: device = -1 computes it on the host, operation
+ * for operation (no GPU); device >= 0 uploads D and runs the same kernels: the same bits.  No counterpart in the reference.
+ */
+int st_beta_dispersion_host(st_tree *tree, const int64_t *univ, int32_t n_univ, const int32_t *set_pos, int64_t n_pos,
+                            const int64_t *sets, int64_t n_sets, int64_t begin, int64_t count, int32_t exclude_shared,
+                            int64_t permutations, uint64_t seed, int32_t stream, int64_t chunk_tasks,
+                            st_dispersion_record *out, int64_t *bad_id);
+
+int st_beta_dispersion_matrix(int device, const float *D, int32_t n, const int32_t *set_pos, int64_t n_pos,
+                              const int64_t *sets, int64_t n_sets, int64_t begin, int64_t count, int32_t exclude_shared,
+                              int64_t permutations, uint64_t seed, int32_t stream, int64_t chunk_tasks,
+                              st_dispersion_record *out);
 
 /*
  * How different are two sets of leaves, measured on the tree: Faith's PD of many sets over one universe and, for pairs of

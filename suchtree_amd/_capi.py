@@ -48,6 +48,7 @@ SYMBOLS = (
     "st_compare_triangle_kendall_host", "st_compare_pairs_kendall_host", "st_kendall_arrays_host", "st_kendall_host",
     "st_hommola_permutation", "st_hommola_clades_host", "st_partner_dispersion_host", "st_dispersion_matrix",
     "st_unifrac_host", "st_unifrac_depths", "st_unifrac_quantise", "st_clade_ranges", "st_clade_match",
+    "st_beta_dispersion_host", "st_beta_dispersion_matrix",
 )
 
 CLADE_RECT, CLADE_TRI = 0, 1     # include/suchtree_hip.h: ST_CLADE_RECT / ST_CLADE_TRI
@@ -188,6 +189,24 @@ def _unifrac_range(n_sets, begin, count, chunk_pairs):
     if int(chunk_pairs) < 0:
         raise ValueError("chunk_pairs < 0")
     return begin, count
+
+
+def beta_dispersion_matrix(D, sets, begin=0, count=None, exclude_shared=False, permutations=0, seed=0, stream=0, device=-1, chunk_tasks=0):
+    """st_beta_dispersion_matrix: the (count, 2, permutations + 1) array of DISPERSION_RECORD (``pair_sum`` holds the cross
+    sum) of pairs [begin, begin + count) of the triangle over the position sets ``sets`` (as in ``dispersion_matrix``),
+    directions i -> j and j -> i, over the C-order float32 (n, n) matrix ``D``; ``device`` -1 = the host restatement (no
+    GPU), else the kernels on that device."""
+    D = np.ascontiguousarray(D, dtype=np.float32)
+    if D.ndim != 2 or D.shape[0] != D.shape[1]:
+        raise ValueError("D must be a square matrix")
+    n = int(D.shape[0])
+    _dispersion_args(permutations, stream, chunk_tasks)
+    pos, off, n_sets = _dispersion_sets(sets, n)
+    begin, count = _unifrac_range(n_sets, begin, count, 0)
+    out = np.zeros((count, 2, int(permutations) + 1), dtype=DISPERSION_RECORD)
+    check(load().st_beta_dispersion_matrix(int(device), _ptr(D), n, _arg(pos), len(pos), _ptr(off), n_sets, begin, count, int(bool(exclude_shared)),
+                                           int(permutations), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(chunk_tasks), _arg(out)))
+    return out
 
 
 def unifrac_quantise(d, h, shift=None):
@@ -504,6 +523,10 @@ def load():
         L.st_partner_dispersion_host.argtypes = [vp, vp, ctypes.c_int32, vp, i64, vp, i64, i64, ctypes.c_uint64, ctypes.c_int32, i64, vp,
                                                  ctypes.POINTER(i64)]
         L.st_dispersion_matrix.argtypes = [i32, vp, ctypes.c_int32, vp, i64, vp, i64, i64, ctypes.c_uint64, ctypes.c_int32, i64, vp]
+        L.st_beta_dispersion_host.argtypes = [vp, vp, ctypes.c_int32, vp, i64, vp, i64, i64, i64, ctypes.c_int32, i64, ctypes.c_uint64,
+                                              ctypes.c_int32, i64, vp, ctypes.POINTER(i64)]
+        L.st_beta_dispersion_matrix.argtypes = [i32, vp, ctypes.c_int32, vp, i64, vp, i64, i64, i64, ctypes.c_int32, i64, ctypes.c_uint64,
+                                                ctypes.c_int32, i64, vp]
         L.st_unifrac_host.argtypes = [vp, i64, vp, ctypes.c_int32, vp, i64, vp, i64, i64, i64, ctypes.c_int32, i64, vp, vp,
                                       ctypes.POINTER(ctypes.c_int32), vp, vp, ctypes.POINTER(i64)]
         L.st_unifrac_depths.argtypes = [i32, vp, vp, ctypes.c_int32, vp, i64, vp, i64, i64, i64, i64, vp, vp]
@@ -1169,6 +1192,24 @@ class DeviceTree:
         bad = ctypes.c_int64(0)
         rc = self._lib.st_partner_dispersion_host(self.handle, _arg(univ), len(univ), _arg(pos), len(pos), _ptr(off), n_sets, int(permutations),
                                                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(chunk_tasks), _arg(out), ctypes.byref(bad))
+        check(rc, tree_size=self.size, bad_id=int(bad.value))
+        return out
+
+    def beta_dispersion_host(self, univ, sets, begin=0, count=None, exclude_shared=False, permutations=0, seed=0, stream=0, chunk_tasks=0):
+        """st_beta_dispersion_host: the (count, 2, permutations + 1) array of DISPERSION_RECORD of pairs [begin, begin + count)
+        of the triangle over the position sets ``sets`` (as in ``beta_dispersion_matrix``) over the universe ``univ`` (node
+        ids of this tree, depth-first)."""
+        univ = np.ascontiguousarray(univ, dtype=np.int64)
+        if univ.ndim != 1:
+            raise ValueError("the universe must be 1-D")
+        _dispersion_args(permutations, stream, chunk_tasks)
+        pos, off, n_sets = _dispersion_sets(sets, len(univ))
+        begin, count = _unifrac_range(n_sets, begin, count, 0)
+        out = np.zeros((count, 2, int(permutations) + 1), dtype=DISPERSION_RECORD)
+        bad = ctypes.c_int64(0)
+        rc = self._lib.st_beta_dispersion_host(self.handle, _arg(univ), len(univ), _arg(pos), len(pos), _ptr(off), n_sets, begin, count,
+                                               int(bool(exclude_shared)), int(permutations), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream),
+                                               int(chunk_tasks), _arg(out), ctypes.byref(bad))
         check(rc, tree_size=self.size, bad_id=int(bad.value))
         return out
 

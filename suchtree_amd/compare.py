@@ -601,6 +601,134 @@ class SetUniFrac:
         return pd.DataFrame(cols)
 
 
+class SetBetaDispersion:
+    """How far apart the members of every two of many leaf sets are, by distance (SuchTree.beta_dispersion,
+    SuchLinkedTrees.partner_beta_dispersion), as numpy columns, one entry per pair.
+
+    ``n_sets`` sets; the pairs are ``[begin, begin + count)`` of the triangle k = i (i - 1) / 2 + j, 0 <= j < i < n_sets
+    (:meth:`pair`).  ``n_i`` / ``n_j`` are the two sets' sizes and ``shared`` the number of members they have in common.
+    ``beta_mpd`` is the mean distance between a member of one set and a member of the other, ``beta_mntd`` the mean, over
+    the members of both sets, of the distance to the nearest member of the other set (picante's ``comdist`` /
+    ``comdistnt``, unweighted); with ``exclude_shared`` a member is not compared with itself in the other set
+    (``exclude.conspecifics``).  NaN where nothing is compared.  The null shuffles the labels of the universe, as in
+    :class:`SetDispersion`, one shuffle serving every pair.  For ``x`` in (``beta_mpd``, ``beta_mntd``): ``x_null_mean``,
+    ``x_null_sd`` (ddof = 1), ``x_ses`` = (x - mean) / sd -- betaNRI is ``beta_mpd_ses``, betaNTI ``beta_mntd_ses`` --
+    ``x_n_le`` / ``x_n_ge`` the numbers of null draws <= x / >= x, and ``x_p_le`` = (n_le + 1) / (permutations + 1), ``x_p_ge``
+    likewise: the two tails.  A pair of two sets that are both the whole universe has the observation as its null by
+    definition and is reported so: mean = x, sd = 0, SES NaN, both p = 1.  ``n_nan`` counts the null draws with a NaN in
+    either statistic.  ``null_beta_mpd`` / ``null_beta_mntd`` are the (pairs, permutations) draws with ``keep_null=True``,
+    else None.  ``begin``, ``count``, ``permutations``, ``seed``, ``n_universe`` and ``exclude_shared`` repeat the call.
+    ``leaves`` / ``names`` are filled in by ``partner_beta_dispersion``: the leaf whose partners set i is.
+    """
+
+    STATS = ("beta_mpd", "beta_mntd")
+    COLUMNS = ("n_i", "n_j", "shared") + tuple(x + s for x in STATS for s in ("", "_null_mean", "_null_sd", "_ses", "_n_le", "_n_ge", "_p_le", "_p_ge")) \
+        + ("n_nan",)
+
+    def __init__(self, n_sets, begin, count, permutations, seed, n_universe, exclude_shared=False, keep_null=False):
+        self.n_sets, self.begin, self.count = int(n_sets), int(begin), int(count)
+        self.permutations, self.seed, self.n_universe = int(permutations), int(seed), int(n_universe)
+        self.exclude_shared = bool(exclude_shared)
+        for k in self.COLUMNS:
+            whole = k in ("n_i", "n_j", "shared", "n_nan") or k.endswith("n_le") or k.endswith("n_ge")
+            setattr(self, k, np.zeros(self.count, dtype=np.int64) if whole else np.full(self.count, np.nan))
+        self.null_beta_mpd = np.full((self.count, self.permutations), np.nan) if keep_null else None
+        self.null_beta_mntd = np.full((self.count, self.permutations), np.nan) if keep_null else None
+        self.leaves = self.names = None
+
+    def __len__(self):
+        return self.count
+
+    def pair(self, k):
+        """(i, j), j < i, of pair ``k`` of this result (triangle index ``begin + k``)."""
+        if not 0 <= k < self.count:
+            raise IndexError("pair %d of %d" % (k, self.count))
+        i, j = SetUniFrac._rows(np.array([self.begin + int(k)], dtype=np.int64))
+        return int(i[0]), int(j[0])
+
+    def fill(self, at, n_i, n_j, shared, records):
+        """Reduce the (pairs, 2, permutations + 1) DISPERSION_RECORD array of pairs [at, at + pairs) of this result, whose
+        sets have ``n_i`` and ``n_j`` members, ``shared`` of them in common."""
+        n_i, n_j, shared = (np.asarray(v, dtype=np.int64) for v in (n_i, n_j, shared))
+        rows = slice(at, at + len(n_i))
+        self.n_i[rows], self.n_j[rows], self.shared[rows] = n_i, n_j, shared
+        cross = records["pair_sum"][:, 0, :] + records["pair_sum"][:, 1, :]
+        near = records["nearest_sum"][:, 0, :] + records["nearest_sum"][:, 1, :]
+        left_out = shared if self.exclude_shared else np.zeros_like(shared)
+        # members with nobody to be compared with: all of one set when the other is empty, the shared one when it is all the other has
+        alone = self.exclude_shared & (shared == 1)
+        z = np.where(n_j == 0, n_i, alone & (n_j == 1)) + np.where(n_i == 0, n_j, alone & (n_i == 1))
+        den_mpd = (2 * (n_i * n_j - left_out)).astype(np.float64)[:, None]
+        den_mntd = (n_i + n_j - z).astype(np.float64)[:, None]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mpd = np.where(den_mpd > 0, cross / den_mpd, np.nan)
+            mntd = np.where(den_mntd > 0, near / den_mntd, np.nan)
+        whole = (n_i == self.n_universe) & (n_j == self.n_universe)
+        self.n_nan[rows] = np.count_nonzero(np.isnan(mpd[:, 1:]) | np.isnan(mntd[:, 1:]), axis=1)
+        for name, x in (("beta_mpd", mpd), ("beta_mntd", mntd)):
+            mean, sd, ses, n_le = null_summary(x[:, 0], x[:, 1:], whole)
+            n_ge = np.count_nonzero(x[:, 1:] >= x[:, :1], axis=1)
+            if self.permutations:
+                n_ge = np.where(whole & ~np.isnan(x[:, 0]), self.permutations, n_ge)
+            getattr(self, name)[rows] = x[:, 0]
+            for suffix, v in (("_null_mean", mean), ("_null_sd", sd), ("_ses", ses), ("_n_le", n_le), ("_n_ge", n_ge)):
+                getattr(self, name + suffix)[rows] = v
+            for tail, v in (("_p_le", n_le), ("_p_ge", n_ge)):
+                getattr(self, name + tail)[rows] = np.where(np.isnan(x[:, 0]), np.nan, (v + 1) / (self.permutations + 1))
+            if self.null_beta_mpd is not None:
+                getattr(self, "null_" + name)[rows] = x[:, 1:]
+
+    def matrix(self, which="beta_mntd"):
+        """The square symmetric (n_sets, n_sets) form of a float column (``beta_mpd``, ``beta_mntd_ses``, ...) with a zero
+        diagonal; only where the result holds the whole triangle."""
+        if which not in self.COLUMNS or getattr(self, which).dtype != np.float64:
+            raise ValueError("which must be one of the float columns, such as 'beta_mpd', 'beta_mntd' or 'beta_mntd_ses'")
+        if self.begin != 0 or self.count != self.n_sets * (self.n_sets - 1) // 2:
+            raise ValueError("matrix() needs the whole triangle, this result holds pairs [%d, +%d)" % (self.begin, self.count))
+        out = np.zeros((self.n_sets, self.n_sets))
+        i, j = SetUniFrac._rows(np.arange(self.count, dtype=np.int64))
+        out[i, j] = out[j, i] = getattr(self, which)
+        return out
+
+    def row(self, k) -> dict:
+        """Pair k as a dict of Python scalars: ``i``, ``j`` (and the two names where the call knows them), then the columns."""
+        i, j = self.pair(k)
+        out = {"i": i, "j": j}
+        if self.names is not None:
+            out["name_i"], out["name_j"] = self.names[i], self.names[j]
+        out.update({c: getattr(self, c)[k].item() for c in self.COLUMNS})
+        return out
+
+    def to_dataframe(self):
+        """One row per pair as a pandas DataFrame (pandas imported here): i, j (and the two names where the call knows
+        them), then the columns."""
+        import pandas as pd
+        i, j = SetUniFrac._rows(self.begin + np.arange(self.count, dtype=np.int64))
+        cols = {"i": i, "j": j}
+        if self.names is not None:
+            cols["name_i"], cols["name_j"] = [self.names[v] for v in i], [self.names[v] for v in j]
+        cols.update({c: getattr(self, c) for c in self.COLUMNS})
+        return pd.DataFrame(cols)
+
+
+def set_bit_rows(set_pos, offsets, n_universe):
+    """The position sets (set_pos, offsets) over a universe of ``n_universe`` as rows of bits (uint8, eight positions each)."""
+    n_sets = len(offsets) - 1
+    bits = np.zeros((n_sets, (int(n_universe) + 7) // 8 * 8), dtype=bool)
+    bits[np.repeat(np.arange(n_sets), np.diff(offsets)), set_pos] = True
+    return np.packbits(bits, axis=1)
+
+
+def shared_counts(bit_rows, i, j):
+    """|S_i and S_j| for the pairs (i[k], j[k]) of the sets of ``set_bit_rows``: the rows ANDed a block of pairs at a time."""
+    ones = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(axis=1).astype(np.int64)
+    out = np.zeros(len(i), dtype=np.int64)
+    step = max(1, (1 << 24) // max(bit_rows.shape[1], 1))
+    for at in range(0, len(i), step):
+        out[at:at + step] = ones[bit_rows[i[at:at + step]] & bit_rows[j[at:at + step]]].sum(axis=1)
+    return out
+
+
 def unifrac_from_depths(d, h, sets, begin=0, count=None, shift=None, device=None, chunk_pairs=0):
     """:class:`SetUniFrac` of the position sets ``sets`` over a universe given by its float32 depths: ``d[k]`` the root
     distance of leaf k (leaves in depth-first order), ``h[k]`` that of the MRCA of leaves k and k + 1.  The depths are

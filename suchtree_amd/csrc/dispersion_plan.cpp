@@ -9,14 +9,40 @@
 
 namespace st {
 
-int dispersion_plan(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets, int64_t permutations,
-                    int32_t stream, int64_t chunk_tasks, DispersionPlan &P, std::string &err)
+int dispersion_call_args(int32_t n_univ, int64_t permutations, int64_t chunk_tasks, int32_t stream, std::string &err)
 {
     if (n_univ < 3 || n_univ > kPermMaxUniverse)
         return fail(ST_ERR_ARG, err, "a universe of " + std::to_string(n_univ) + " positions: 3 to " + std::to_string(kPermMaxUniverse));
     if (permutations < 0) return fail(ST_ERR_ARG, err, "permutations < 0");
     if (chunk_tasks < 0) return fail(ST_ERR_ARG, err, "chunk_tasks < 0");
     if (stream < 0) return fail(ST_ERR_ARG, err, "stream < 0");
+    return ST_OK;
+}
+
+void dispersion_cut(int32_t n_univ, int64_t rows, int64_t live, int64_t chunk_tasks, int64_t &perm_block, std::vector<DispersionChunk> &chunks,
+                    int64_t &max_chunk_tasks)
+{
+    int64_t block = std::max<int64_t>(1, kDispersionSigmaBytes / (2 * (int64_t)n_univ));
+    int64_t cap = kDispersionChunkTasks;
+    if (chunk_tasks > 0) {
+        block = std::min(block, chunk_tasks);
+        cap = std::min(chunk_tasks, kDispersionMaxChunkTasks);
+    }
+    perm_block = std::min(block, rows);
+    if (live == 0) return;
+    for (int64_t p0 = 0; p0 < rows; p0 += perm_block) {
+        const int64_t np = std::min(perm_block, rows - p0), tasks = live * np;
+        for (int64_t t = 0; t < tasks; t += cap) {
+            chunks.push_back(DispersionChunk{p0, np, t, std::min(cap, tasks - t)});
+            max_chunk_tasks = std::max(max_chunk_tasks, chunks.back().n_tasks);
+        }
+    }
+}
+
+int dispersion_plan(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets, int64_t permutations,
+                    int32_t stream, int64_t chunk_tasks, DispersionPlan &P, std::string &err)
+{
+    if (const int rc = dispersion_call_args(n_univ, permutations, chunk_tasks, stream, err); rc != ST_OK) return rc;
     const int64_t R = permutations + 1;
     if (n_sets > 0 && R > ((int64_t)1 << 40) / n_sets) return fail(ST_ERR_ARG, err, "more than 2^40 records in one call");
     if (const int rc = position_sets_args(n_univ, set_pos, n_pos, sets, n_sets, err); rc != ST_OK) return rc;
@@ -41,26 +67,11 @@ int dispersion_plan(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const
         P.sets[(size_t)c] = DispersionSetDev{(int)sets[r], (int)(sets[r + 1] - sets[r])};
         P.max_count = std::max(P.max_count, P.sets[(size_t)c].count);
     }
-    int64_t block = std::max<int64_t>(1, kDispersionSigmaBytes / (2 * (int64_t)n_univ));
-    int64_t cap = kDispersionChunkTasks;
-    if (chunk_tasks > 0) {
-        block = std::min(block, chunk_tasks);
-        cap = std::min(chunk_tasks, kDispersionMaxChunkTasks);
-    }
-    P.perm_block = std::min(block, R);
-    if (live == 0) return ST_OK;
-    for (int64_t p0 = 0; p0 < R; p0 += P.perm_block) {
-        const int64_t np = std::min(P.perm_block, R - p0), tasks = live * np;
-        for (int64_t t = 0; t < tasks; t += cap) {
-            P.chunks.push_back(DispersionChunk{p0, np, t, std::min(cap, tasks - t)});
-            P.max_chunk_tasks = std::max(P.max_chunk_tasks, P.chunks.back().n_tasks);
-        }
-    }
+    dispersion_cut(n_univ, R, live, chunk_tasks, P.perm_block, P.chunks, P.max_chunk_tasks);
     return ST_OK;
 }
 
-// what a wave does with `a += shfl_xor(a, o)` over offsets width / 2 .. 1: v[0 .. width) in, every lane's total out
-static void butterfly(double *v, int width)
+void dispersion_butterfly(double *v, int width)
 {
     double w[64];
     for (int o = width >> 1; o > 0; o >>= 1) {
@@ -96,15 +107,15 @@ st_dispersion_record dispersion_record(const float *D, int32_t n, const int32_t 
         }
     }
     if (k <= kDispersionWaveMax) {
-        butterfly(a, lanes);
-        butterfly(b, lanes);
+        dispersion_butterfly(a, lanes);
+        dispersion_butterfly(b, lanes);
         out.pair_sum = a[0];
         out.nearest_sum = b[0];
         return out;
     }
     for (int w = 0; w < kDispersionThreads / 64; w++) {      // every wave's butterfly, the wave totals in wave order
-        butterfly(a + 64 * w, 64);
-        butterfly(b + 64 * w, 64);
+        dispersion_butterfly(a + 64 * w, 64);
+        dispersion_butterfly(b + 64 * w, 64);
     }
     out.pair_sum = a[0];
     out.nearest_sum = b[0];

@@ -49,6 +49,9 @@
 // MPD / MNTD sums of many leaf sets under the taxa-labels null (st_partner_dispersion_host, st_dispersion_matrix):
 // kernels_dispersion.h (one sort per permutation, the k x k reducer in three size classes), host_dispersion.h (the chunk
 // driver) and, host-only, dispersion_plan.cpp (argument checks, size classes, chunks, the restatement of the reduction).
+// betaMPD / betaMNTD sums between every two leaf sets under the same null (st_beta_dispersion_host, st_beta_dispersion_matrix):
+// kernels_setpair.h (the k_r x k_c reducer in the same three size classes), host_setpair.h (the launches; the driver is
+// host_dispersion.h's) and, host-only, setpair_plan.cpp (argument checks, the task table, the restatement).
 // Faith's PD of many leaf sets and the union sums of their pairs behind UniFrac (st_unifrac_host, st_unifrac_depths):
 // kernels_unifrac.h (the range-minimum table, the set merge in a lane form and a wave form), host_unifrac.h (the depths, the
 // chunk driver) and, host-only, unifrac_plan.cpp (argument checks, the quantiser, chunks, the restatement of the merge).
@@ -178,6 +181,7 @@ static int device_index_arg(int device)
 #include "kernels_perm.h"
 #include "kernels_hommola.h"
 #include "kernels_dispersion.h"
+#include "kernels_setpair.h"
 #include "kernels_unifrac.h"
 #include "kernels_clade_match.h"
 
@@ -196,6 +200,7 @@ using namespace st;
 #include "host_quartets.h"
 #include "host_hommola.h"
 #include "host_dispersion.h"
+#include "host_setpair.h"
 #include "host_unifrac.h"
 #include "host_clade_match.h"
 
@@ -1347,6 +1352,44 @@ try {
         return ST_OK;
     }
     return dispersion_matrix_device(device, D, P, set_pos, n_pos, seed, stream, out);
+} ST_CATCH_ALL
+
+int st_beta_dispersion_host(st_tree *t, const int64_t *univ, int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets,
+                            int64_t n_sets, int64_t begin, int64_t count, int32_t exclude_shared, int64_t permutations, uint64_t seed, int32_t stream,
+                            int64_t chunk_tasks, st_dispersion_record *out, int64_t *bad_id)
+try {
+    SetpairPlan P;
+    std::string err;
+    int rc = setpair_plan(n_univ, set_pos, n_pos, sets, n_sets, begin, count, exclude_shared, permutations, stream, chunk_tasks, P, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (!univ) return fail(ST_ERR_ARG, "univ is NULL");
+    if (count > 0 && !out) return fail(ST_ERR_ARG, "out is NULL");
+    if (!t) return fail(ST_ERR_ARG, "tree is NULL");
+    rc = compare_check_ids(univ, n_univ, t->n_nodes, bad_id);
+    if (rc != ST_OK) return rc;
+    if (P.chunks.empty()) {      // (no pair, or none with two members to compare: nothing to launch)
+        std::fill_n(out, 2 * P.count * P.rows, st_dispersion_record{0.0, 0.0});
+        return ST_OK;
+    }
+    return setpair_run(t, univ, P, set_pos, n_pos, seed, stream, out, bad_id);
+} ST_CATCH_ALL
+
+int st_beta_dispersion_matrix(int device, const float *D, int32_t n, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets,
+                              int64_t begin, int64_t count, int32_t exclude_shared, int64_t permutations, uint64_t seed, int32_t stream,
+                              int64_t chunk_tasks, st_dispersion_record *out)
+try {
+    SetpairPlan P;
+    std::string err;
+    const int rc = setpair_plan(n, set_pos, n_pos, sets, n_sets, begin, count, exclude_shared, permutations, stream, chunk_tasks, P, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (device_or_host_arg(device) != ST_OK) return ST_ERR_ARG;
+    if (!D) return fail(ST_ERR_ARG, "D is NULL");
+    if (count > 0 && !out) return fail(ST_ERR_ARG, "out is NULL");
+    if (device < 0 || P.chunks.empty()) {
+        setpair_host(D, P, set_pos, n_pos, sets, seed, stream, out);
+        return ST_OK;
+    }
+    return setpair_matrix_device(device, D, P, set_pos, n_pos, seed, stream, out);
 } ST_CATCH_ALL
 
 int st_unifrac_quantise(const float *d, const float *h, int32_t n, int32_t shift, int64_t *out_dq, int64_t *out_hq, int32_t *out_shift)

@@ -526,7 +526,7 @@ class SuchLinkedTrees:
         return self._over_partner_rows(of, min_partners, max_partners, run, pool, _capi.HOMMOLA_MAX_UNIVERSE)
 
     def _over_partner_rows(self, of, min_partners, max_partners, run, pool="subset", pool_limit=None):
-        """What partner_dispersion and partner_unifrac share: the checks of ``of``, ``pool`` and the partner counts, the rows
+        """What partner_dispersion, partner_unifrac and partner_beta_dispersion share: the checks of ``of``, ``pool`` and the partner counts, the rows
         (_partner_rows), ``run(partner tree, the rows' partner ids, partner subset root, universe)``, then the result's
         ``leaves`` and ``names``.  With ``pool_limit`` the universe is ``pool`` of the partner tree -- "subset" = every leaf
         of its current subset, "linked" = those with a link in it -- of at most that many leaves; without, it is None."""
@@ -596,6 +596,30 @@ class SuchLinkedTrees:
         """
         return self._over_partner_rows(of, min_partners, max_partners,
                                        lambda partner, sets, root, _: partner.unifrac(sets, root=root, begin=begin, count=count, shift=shift))
+
+    def partner_beta_dispersion(self, of="A", pool="subset", min_partners=1, max_partners=None, begin=0, count=None, exclude_shared=False,
+                                permutations=999, seed=None, keep_null=False):
+        """How different are two leaves' partners, by distance: betaMPD and betaMNTD between every two leaves' partner
+        sets, measured on the partner tree, with the taxa-labels null (betaNRI = ``beta_mpd_ses``, betaNTI =
+        ``beta_mntd_ses``).
+
+        ``of="A"``: one set per TreeA leaf of the current ``subset_a`` (in ``subset_a_leafs`` order) with at least
+        ``min_partners`` -- and, unless ``max_partners`` is None, at most that many -- linked TreeB leaves inside the
+        current ``subset_b``, the row choice of :meth:`partner_unifrac`; the distances are TreeB's.  ``of="B"`` is the
+        mirror.  ``pool`` is the universe whose labels are shuffled, as in :meth:`partner_dispersion`; ``begin`` /
+        ``count`` / ``exclude_shared`` / ``permutations`` / ``seed`` / ``keep_null`` as in
+        :meth:`SuchTree.beta_dispersion`, which does the work with ``stream`` = the partner tree's subset root.  Two
+        leaves with the same partners have ``beta_mntd`` 0.  A universe of more than 16384 leaves is a ValueError:
+        subset it first.  No pair, nothing launched.
+
+        The subset state, ``linklist`` and the generator of :meth:`sample_linked_distances` are left as they were.
+        Returns a :class:`~suchtree_amd.compare.SetBetaDispersion` with ``leaves`` (the sets' leaf ids) and ``names``.
+        An extension: the reference has no counterpart.
+        """
+        def run(partner, sets, root, universe):
+            return partner.beta_dispersion(sets, universe=universe, begin=begin, count=count, exclude_shared=exclude_shared,
+                                           permutations=permutations, seed=seed, stream=root, keep_null=keep_null)
+        return self._over_partner_rows(of, min_partners, max_partners, run, pool, _capi.HOMMOLA_MAX_UNIVERSE)
 
     @staticmethod
     def _leaf_counts(tree: SuchTree) -> np.ndarray:

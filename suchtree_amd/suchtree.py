@@ -658,6 +658,31 @@ class SuchTree(TreeNavigation):
         np.cumsum(np.array([len(p) for p in pos], dtype=np.int64), out=offsets[1:])
         return (np.concatenate(pos) if pos else np.empty(0, dtype=np.int32)), offsets
 
+    def _universe_and_sets(self, sets, universe):
+        """What dispersion and beta_dispersion share: (the universe's leaf ids depth-first, every set's leaf ids), with their
+        ValueErrors -- a universe outside 3 .. 16384 leaves, a member outside it, a repeated member."""
+        univ = self._depth_first_leaves()
+        if universe is not None:
+            inside = np.zeros(self.size, dtype=bool)
+            inside[self._leaf_ids(universe, "universe")] = True
+            univ = univ[inside[univ]]
+        limit = _capi.HOMMOLA_MAX_UNIVERSE
+        if len(univ) < 3:
+            raise ValueError("the universe has %d leaves: at least 3" % len(univ))
+        if len(univ) > limit:
+            raise ValueError("the universe has %d leaves: at most %d (subset it first)" % (len(univ), limit))
+        inside = np.zeros(self.size, dtype=bool)
+        inside[univ] = True
+        rows = []
+        for r, members in enumerate(sets):
+            ids = self._leaf_ids(members, "set %d" % r)
+            if not inside[ids].all():
+                raise ValueError("set %d: a member outside the universe" % r)
+            if len(np.unique(ids)) != len(ids):
+                raise ValueError("set %d: a repeated member" % r)
+            rows.append(ids)
+        return univ, rows
+
     def dispersion(self, sets, universe=None, permutations=999, seed=None, stream=0, keep_null=False, chunk_tasks=0):
         """How closely related are the members of each set of leaves: MPD and MNTD with a permutation null, on the GPU.
 
@@ -680,26 +705,7 @@ class SuchTree(TreeNavigation):
         permutations, seed = int_arg("permutations", permutations), seed_arg(seed)
         stream = int_arg("stream", stream, (1 << 31) - 1, "2^31 - 1")
         chunk_tasks = int_arg("chunk_tasks", chunk_tasks)
-        univ = self._depth_first_leaves()
-        if universe is not None:
-            inside = np.zeros(self.size, dtype=bool)
-            inside[self._leaf_ids(universe, "universe")] = True
-            univ = univ[inside[univ]]
-        limit = _capi.HOMMOLA_MAX_UNIVERSE
-        if len(univ) < 3:
-            raise ValueError("the universe has %d leaves: at least 3" % len(univ))
-        if len(univ) > limit:
-            raise ValueError("the universe has %d leaves: at most %d (subset it first)" % (len(univ), limit))
-        inside = np.zeros(self.size, dtype=bool)
-        inside[univ] = True
-        rows = []
-        for r, members in enumerate(sets):
-            ids = self._leaf_ids(members, "set %d" % r)
-            if not inside[ids].all():
-                raise ValueError("set %d: a member outside the universe" % r)
-            if len(np.unique(ids)) != len(ids):
-                raise ValueError("set %d: a repeated member" % r)
-            rows.append(ids)
+        univ, rows = self._universe_and_sets(sets, universe)
         set_pos, offsets = self._position_table(univ, rows)
         k = np.diff(offsets)
         out = compare.SetDispersion(len(rows), permutations, seed, len(univ), keep_null)
@@ -709,6 +715,50 @@ class SuchTree(TreeNavigation):
             part = (set_pos[offsets[at]:offsets[end]], offsets[at:end + 1] - offsets[at])
             rec = self._device_tree().partner_dispersion_host(univ, part, permutations, seed, stream, chunk_tasks)
             out.fill(at, k[at:end], rec)      # (each group is reduced before the next)
+        return out
+
+    def beta_dispersion(self, sets, universe=None, begin=0, count=None, exclude_shared=False, permutations=999, seed=None, stream=0,
+                        keep_null=False, chunk_tasks=0):
+        """How far apart are the members of every two sets of leaves: betaMPD and betaMNTD with a permutation null, on the GPU.
+
+        ``sets`` and ``universe`` are those of :meth:`dispersion`, with the same checks; sets of no or one member are
+        allowed.  For a pair of sets, ``beta_mpd`` is the mean distance between a member of one and a member of the other
+        and ``beta_mntd`` the mean, over the members of both, of the distance to the nearest member of the other set
+        (picante's ``comdist`` / ``comdistnt``, unweighted), in float64 over the float32 distances of ``distances_bulk``;
+        ``exclude_shared=True`` does not compare a member with itself in the other set (``exclude.conspecifics``).  Both
+        are standardised against the null of :meth:`dispersion`, which shuffles the universe's leaf labels: betaNRI is
+        ``beta_mpd_ses``, betaNTI ``beta_mntd_ses``.
+
+        The pairs are ``[begin, begin + count)`` of the triangle k = i (i - 1) / 2 + j, j < i; ``count=None`` means the
+        whole triangle, which above 2^31 pairs is a ValueError: ask for ranges.  The shuffles, ``seed``, ``stream``,
+        ``keep_null`` and ``chunk_tasks`` are those of :meth:`dispersion`: a pair's columns depend on (seed, ``stream``, the
+        universe, its two sets, ``exclude_shared``) alone.  Returns a :class:`~suchtree_amd.compare.SetBetaDispersion`.  An
+        extension: the reference has no counterpart.
+        """
+        from . import compare
+        permutations, seed = int_arg("permutations", permutations), seed_arg(seed)
+        stream = int_arg("stream", stream, (1 << 31) - 1, "2^31 - 1")
+        chunk_tasks = int_arg("chunk_tasks", chunk_tasks)
+        begin, count = int_arg("begin", begin), int_arg("count", count, optional=True)
+        univ, rows = self._universe_and_sets(sets, universe)
+        total = len(rows) * (len(rows) - 1) // 2
+        if count is None:
+            count = total - int(begin)
+            if count > 1 << 31:
+                raise ValueError("the whole triangle of %d sets is %d pairs, more than 2^31: ask for ranges with begin= and count=" % (len(rows), total))
+        if begin + count > total or count < 0:
+            raise ValueError("pairs [%d, +%d) of a triangle of %d" % (begin, count, total))
+        set_pos, offsets = self._position_table(univ, rows)
+        k = np.diff(offsets)
+        out = compare.SetBetaDispersion(len(rows), begin, count, permutations, seed, len(univ), exclude_shared, keep_null)
+        per_group = max(1, self._DISPERSION_GROUP_ROWS // (2 * (permutations + 1)))
+        bits = compare.set_bit_rows(set_pos, offsets, len(univ)) if count else None
+        for at in range(0, count, per_group):      # (no pairs: nothing is launched, and the tree stays where it is)
+            n = min(per_group, count - at)
+            rec = self._device_tree().beta_dispersion_host(univ, (set_pos, offsets), begin + at, n, exclude_shared, permutations, seed, stream,
+                                                           chunk_tasks)
+            i, j = compare.SetUniFrac._rows(begin + at + np.arange(n, dtype=np.int64))
+            out.fill(at, k[i], k[j], compare.shared_counts(bits, i, j), rec)      # (each group is reduced before the next)
         return out
 
     def unifrac(self, sets, root=None, begin=0, count=None, shift=None, chunk_pairs=0):
