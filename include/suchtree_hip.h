@@ -50,7 +50,8 @@ extern "C" {
  *      st_partner_dispersion_host and st_dispersion_matrix; then, also additive, ST_UNIFRAC_MAX_UNIVERSE,
  *      ST_UNIFRAC_LANE_MAX, st_unifrac_host, st_unifrac_depths and st_unifrac_quantise; then st_tree_info.heap_codes appended
  *      (8 bytes) with option "heap_codes", as heap_lines was; then, also additive, ST_CLADE_MATCH_MAX_LEAVES, st_clade_ranges
- *      and st_clade_match; then, also additive, st_beta_dispersion_host and st_beta_dispersion_matrix.
+ *      and st_clade_match; then, also additive, st_beta_dispersion_host and st_beta_dispersion_matrix; then, also additive,
+ *      st_unifrac_null_host and st_unifrac_null_depths.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -673,6 +674,59 @@ int st_unifrac_depths(int device, const int64_t *d_q, const int64_t *h_q, int32_
 
 int st_unifrac_quantise(const float *d, const float *h, int32_t n, int32_t shift, int64_t *out_dq, int64_t *out_hq,
                         int32_t *out_shift);
+
+/*
+ * Faith's PD and the union sums of st_unifrac_host under the taxa-labels null of st_partner_dispersion_host: every set is
+ * relabelled by every shuffle of the universe's labels and the sums are taken again (picante's ses.pd with null.model =
+ * "taxa.labels"; the label-shuffling significance of UniFrac, Lozupone & Knight 2005).  SuchLinkedTrees.partner_unifrac_null
+ * asks it of every two leaves' partners in the other tree; SuchTree.unifrac_null of any sets.
+ *
+ * Universe.  The universe, its order, seed, stream and sigma_p are exactly those of st_partner_dispersion_host: 3 <= n <=
+ * ST_HOMMOLA_MAX_UNIVERSE leaves in depth-first order, sigma_p = st_hommola_permutation(seed, node = stream, p, side = 0,
+ * n), p = 0 the identity, one sigma_p for every set of the call.
+ *
+ * Depths.  The depths, the fixed point, the sets and the pair order are exactly those of st_unifrac_host: d[k] the root
+ * distance of univ[k], h[k] that of the MRCA of univ[k] and univ[k + 1], q(v) and shift, U(A, B) over the distinct merged
+ * positions, pair k = i (i - 1) / 2 + j.
+ *
+ * Relabelling.  Under permutation p, set r becomes R_p(r) = { sigma_p[s] : s in set r }, taken in ascending order.
+ *
+ * Results.  Both arrays are int64, permutations + 1 values a row:
+ *     out_pd[r * (permutations + 1) + p]                = U(R_p(r), R_p(r))   for every set r, whatever the range;
+ *     out_union[(k - k_begin) * (permutations + 1) + p] = U(R_p(j), R_p(i))   for pair k = i (i - 1) / 2 + j of the range.
+ * Either may be NULL, and then it is not computed.  A value depends on (the depths, shift, seed, stream, p, its one or two
+ * sets) alone -- not on the other sets, the range, permutations, chunk_tasks, the kernel form, the grid or the device.
+ * Column p is the same for any permutations >= p; column 0 is what st_unifrac_depths gives.  No float arithmetic on the
+ * device: every sum is an exact int64.
+ *
+ * st_unifrac_null_host has d and h computed on the tree's device as st_unifrac_host does, quantises them on the host and
+ * runs st_unifrac_null_depths' kernels on that device; out_shift is the shift used.  st_unifrac_null_depths takes the
+ * caller's int64 d_q[n] and h_q[n - 1]: device = -1 is the host restatement (for each p: sigma_p, every set relabelled
+ * and sorted, the merge of st_unifrac_depths; no GPU); device >= 0 runs the kernels: the same integers.
+ *
+ * Errors, in this order: those of st_partner_dispersion_host's first checks (a universe size outside 3 ..
+ * ST_HOMMOLA_MAX_UNIVERSE, negative permutations, chunk_tasks or stream), the set table (bad offsets, a position outside
+ * the universe, a set that is not strictly increasing), the range (negative, more than 2^30 sets, outside the triangle,
+ * more than 2^40 values in an output array),
+ * then the depths (st_unifrac_null_depths: NULL, a |value| of 2^40 or more; st_unifrac_null_host: a bad shift, NULL univ
+ * or tree) -- all ST_ERR_ARG; root and the universe ids, ST_ERR_BOUNDS with *bad_id.  An allocation that fails is
+ * ST_ERR_NOMEM with the bytes asked for, before any output is written.
+ *
+ * chunk_tasks: (set, permutation) and (pair, permutation) tasks per device chunk, and the most permutations the device
+ * holds at once; 0 = the default (2^20 tasks; permutations while their sigma rows and relabelled positions, 2 bytes each,
+ * stay within 64 MiB).  No result depends on it.  The relabelled positions of a block are kept on the device, set by set
+ * in ascending order, for its pair tasks: 2 (permutations of the block) x n_pos bytes.  The threshold
+ * between the lane and the wave form of a pair task is that of st_unifrac_host, SUCHTREE_AMD_UNIFRAC_LANE_MAX included.
+ * Zero sets launch nothing (out_shift is then the caller's shift, or 0).  No counterpart in the reference.
+ */
+int st_unifrac_null_host(st_tree *tree, int64_t root, const int64_t *univ, int32_t n_univ, const int32_t *set_pos, int64_t n_pos,
+                         const int64_t *sets, int64_t n_sets, int64_t k_begin, int64_t k_count, int32_t shift,
+                         int64_t permutations, uint64_t seed, int32_t stream, int64_t chunk_tasks, int64_t *out_pd,
+                         int64_t *out_union, int32_t *out_shift, int64_t *bad_id);
+
+int st_unifrac_null_depths(int device, const int64_t *d_q, const int64_t *h_q, int32_t n, const int32_t *set_pos, int64_t n_pos,
+                           const int64_t *sets, int64_t n_sets, int64_t k_begin, int64_t k_count, int64_t permutations,
+                           uint64_t seed, int32_t stream, int64_t chunk_tasks, int64_t *out_pd, int64_t *out_union);
 
 /*
  * Which clades of one tree are also in another, and how close is the best match where they are not: every induced clade

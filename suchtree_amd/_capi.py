@@ -48,7 +48,7 @@ SYMBOLS = (
     "st_compare_triangle_kendall_host", "st_compare_pairs_kendall_host", "st_kendall_arrays_host", "st_kendall_host",
     "st_hommola_permutation", "st_hommola_clades_host", "st_partner_dispersion_host", "st_dispersion_matrix",
     "st_unifrac_host", "st_unifrac_depths", "st_unifrac_quantise", "st_clade_ranges", "st_clade_match",
-    "st_beta_dispersion_host", "st_beta_dispersion_matrix",
+    "st_beta_dispersion_host", "st_beta_dispersion_matrix", "st_unifrac_null_host", "st_unifrac_null_depths",
 )
 
 CLADE_RECT, CLADE_TRI = 0, 1     # include/suchtree_hip.h: ST_CLADE_RECT / ST_CLADE_TRI
@@ -236,6 +236,28 @@ def unifrac_depths(d_q, h_q, sets, begin=0, count=None, device=-1, chunk_pairs=0
     pd_q, union_q = np.zeros(n_sets, dtype=np.int64), np.zeros(count, dtype=np.int64)
     check(load().st_unifrac_depths(int(device), _arg(d_q), _arg(h_q), len(d_q), _arg(pos), len(pos), _ptr(off), n_sets, begin, count,
                                    int(chunk_pairs), _arg(pd_q), _arg(union_q)))
+    return pd_q, union_q
+
+
+def unifrac_null_depths(d_q, h_q, sets, begin=0, count=None, permutations=0, seed=0, stream=0, device=-1, chunk_tasks=0, pd=True, union=True):
+    """st_unifrac_null_depths: (pd_q (n_sets, permutations + 1), union_q (count, permutations + 1)), the int64 PD of every
+    set and union sum of pairs [begin, begin + count) of the triangle over the position sets ``sets`` (as in
+    ``dispersion_matrix``) under every permutation p of the taxa-labels null, from the quantised depths ``d_q`` (n) and
+    ``h_q`` (n - 1); column 0 is ``unifrac_depths``.  ``device`` -1 = the host restatement (no GPU), else the kernels on
+    that device.  ``pd`` / ``union`` False: that output is not computed and comes back as None."""
+    d_q = np.ascontiguousarray(d_q, dtype=np.int64)
+    h_q = np.ascontiguousarray(h_q, dtype=np.int64)
+    if d_q.ndim != 1 or h_q.ndim != 1 or len(h_q) != max(len(d_q) - 1, 0):
+        raise ValueError("d_q must hold n depths and h_q n - 1")
+    _dispersion_args(permutations, stream, chunk_tasks)
+    pos, off, n_sets = _dispersion_sets(sets, len(d_q))
+    begin, count = _unifrac_range(n_sets, begin, count, 0)
+    R = int(permutations) + 1
+    pd_q = np.zeros((n_sets, R), dtype=np.int64) if pd else None
+    union_q = np.zeros((count, R), dtype=np.int64) if union else None
+    check(load().st_unifrac_null_depths(int(device), _arg(d_q), _arg(h_q), len(d_q), _arg(pos), len(pos), _ptr(off), n_sets, begin, count,
+                                        int(permutations), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(chunk_tasks),
+                                        _ptr(pd_q) if pd else None, _ptr(union_q) if union else None))
     return pd_q, union_q
 
 
@@ -530,6 +552,10 @@ def load():
         L.st_unifrac_host.argtypes = [vp, i64, vp, ctypes.c_int32, vp, i64, vp, i64, i64, i64, ctypes.c_int32, i64, vp, vp,
                                       ctypes.POINTER(ctypes.c_int32), vp, vp, ctypes.POINTER(i64)]
         L.st_unifrac_depths.argtypes = [i32, vp, vp, ctypes.c_int32, vp, i64, vp, i64, i64, i64, i64, vp, vp]
+        L.st_unifrac_null_host.argtypes = [vp, i64, vp, ctypes.c_int32, vp, i64, vp, i64, i64, i64, ctypes.c_int32, i64, ctypes.c_uint64,
+                                           ctypes.c_int32, i64, vp, vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(i64)]
+        L.st_unifrac_null_depths.argtypes = [i32, vp, vp, ctypes.c_int32, vp, i64, vp, i64, i64, i64, i64, ctypes.c_uint64, ctypes.c_int32, i64,
+                                             vp, vp]
         L.st_unifrac_quantise.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, ctypes.POINTER(ctypes.c_int32)]
         L.st_clade_ranges.argtypes = [vp, i64, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int32),
                                       ctypes.POINTER(i64)]
@@ -1231,6 +1257,29 @@ class DeviceTree:
                                        _arg(d), _arg(h), ctypes.byref(bad))
         check(rc, tree_size=self.size, bad_id=int(bad.value))
         return pd_q, union_q, int(used.value), d, h
+
+    def unifrac_null_host(self, root, univ, sets, begin=0, count=None, shift=None, permutations=0, seed=0, stream=0, chunk_tasks=0, pd=True,
+                          union=True):
+        """st_unifrac_null_host: (pd_q (n_sets, permutations + 1), union_q (count, permutations + 1), shift) of the position
+        sets ``sets`` (as in ``dispersion_matrix``) over the universe ``univ`` (leaf ids of this tree under ``root``,
+        depth-first) under every permutation of the taxa-labels null; column 0 is ``unifrac_host``.  ``pd`` / ``union``
+        False: that output is not computed and comes back as None."""
+        univ = np.ascontiguousarray(univ, dtype=np.int64)
+        if univ.ndim != 1:
+            raise ValueError("the universe must be 1-D")
+        n = len(univ)
+        _dispersion_args(permutations, stream, chunk_tasks)
+        pos, off, n_sets = _dispersion_sets(sets, n)
+        begin, count = _unifrac_range(n_sets, begin, count, 0)
+        R = int(permutations) + 1
+        pd_q = np.zeros((n_sets, R), dtype=np.int64) if pd else None
+        union_q = np.zeros((count, R), dtype=np.int64) if union else None
+        used, bad = ctypes.c_int32(0), ctypes.c_int64(0)
+        rc = self._lib.st_unifrac_null_host(self.handle, int(root), _arg(univ), n, _arg(pos), len(pos), _ptr(off), n_sets, begin, count,
+                                            -1 if shift is None else int(shift), int(permutations), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                            int(stream), int(chunk_tasks), _ptr(pd_q), _ptr(union_q), ctypes.byref(used), ctypes.byref(bad))
+        check(rc, tree_size=self.size, bad_id=int(bad.value))
+        return pd_q, union_q, int(used.value)
 
     def triangle_device(self, d_ids, m, k_begin, k_count, d_out_dist=0, d_out_mrca=0, stream=0, id_stride=1):
         rc = self._lib.st_triangle_device(self.handle, ctypes.c_void_p(d_ids), int(m), int(id_stride),

@@ -711,6 +711,140 @@ class SetBetaDispersion:
         return pd.DataFrame(cols)
 
 
+class SetUniFracNull:
+    """Faith's PD of many leaf sets and the UniFrac and PhyloSor of their pairs, each standardised against the null that
+    shuffles the universe's leaf labels (SuchTree.unifrac_null, SuchLinkedTrees.partner_unifrac_null): picante's ``ses.pd``
+    with ``null.model = "taxa.labels"``, and the label-shuffling significance of UniFrac (Lozupone & Knight 2005).
+
+    ``n_sets`` sets; the pairs are ``[begin, begin + count)`` of the triangle k = i (i - 1) / 2 + j, 0 <= j < i < n_sets
+    (:meth:`pair`).  Under permutation p every set is relabelled by the same shuffle, as in :class:`SetDispersion`, and
+    every sum is taken again: exact int64 sums in units of ``quantum`` = 2^-``shift``, as in :class:`SetUniFrac`.
+
+    Per set: ``n`` its size, ``pd_q`` the observed integer sum, ``pd`` = ``pd_q`` * quantum, ``pd_null_mean``,
+    ``pd_null_sd`` (ddof = 1), ``pd_ses`` = (pd - mean) / sd (NaN where the sd is 0 or undefined), ``pd_n_le`` /
+    ``pd_n_ge`` the numbers of null draws <= / >= the observation and ``pd_p_le`` = (n_le + 1) / (permutations + 1),
+    ``pd_p_ge`` likewise: the two tails.  Per pair: ``union_q`` and, for ``x`` in (``unifrac``, ``phylosor``) -- formed
+    from the integers of a draw by the expressions of :class:`SetUniFrac`, NaN where a denominator is 0 -- ``x`` and the
+    same eight null columns; ``n_nan`` counts the pair's null draws with a NaN in either statistic.  A set that is the
+    whole universe has the observation as its null by definition and is reported so: mean = x, sd = 0, SES NaN, both
+    p = 1; the same holds for a pair of two such sets.  With ``keep_null=True`` ``null_pd`` is the (sets, permutations)
+    array of draws and ``null_unifrac`` / ``null_phylosor`` the (pairs, permutations) ones, else None.  ``permutations``,
+    ``seed``, ``n_universe``, ``shift``, ``begin`` and ``count`` repeat the call; ``leaves`` / ``names`` are filled in by
+    ``partner_unifrac_null`` (the leaf whose partners a set is), ``root`` by the tree calls.
+    """
+
+    STATS = ("unifrac", "phylosor")
+    SET_COLUMNS = ("n", "pd_q", "pd", "pd_null_mean", "pd_null_sd", "pd_ses", "pd_n_le", "pd_n_ge", "pd_p_le", "pd_p_ge")
+    COLUMNS = ("union_q",) + tuple(x + s for x in STATS for s in ("", "_null_mean", "_null_sd", "_ses", "_n_le", "_n_ge", "_p_le", "_p_ge")) \
+        + ("n_nan",)
+
+    def __init__(self, n_sets, begin, count, shift, permutations, seed, n_universe, keep_null=False, root=None):
+        self.n_sets, self.begin, self.count, self.shift = int(n_sets), int(begin), int(count), int(shift)
+        self.permutations, self.seed, self.n_universe = int(permutations), int(seed), int(n_universe)
+        self.quantum = math.ldexp(1.0, -self.shift)
+        for cols, rows in ((self.SET_COLUMNS, self.n_sets), (self.COLUMNS, self.count)):
+            for k in cols:
+                whole = k in ("n", "pd_q", "union_q", "n_nan") or k.endswith("n_le") or k.endswith("n_ge")
+                setattr(self, k, np.zeros(rows, dtype=np.int64) if whole else np.full(rows, np.nan))
+        self.null_pd = np.full((self.n_sets, self.permutations), np.nan) if keep_null else None
+        self.null_unifrac = np.full((self.count, self.permutations), np.nan) if keep_null else None
+        self.null_phylosor = np.full((self.count, self.permutations), np.nan) if keep_null else None
+        self._pd_block = np.zeros((self.n_sets, self.permutations + 1), dtype=np.int64)
+        self.root = root
+        self.leaves = self.names = None
+
+    def __len__(self):
+        return self.n_sets
+
+    def pair(self, k):
+        """(i, j), j < i, of pair ``k`` of this result (triangle index ``begin + k``)."""
+        if not 0 <= k < self.count:
+            raise IndexError("pair %d of %d" % (k, self.count))
+        i, j = SetUniFrac._rows(np.array([self.begin + int(k)], dtype=np.int64))
+        return int(i[0]), int(j[0])
+
+    def _reduce(self, name, rows, x, whole):
+        """The eight null columns of statistic ``name`` over ``rows`` from x (rows, permutations + 1), column 0 observed."""
+        mean, sd, ses, n_le = null_summary(x[:, 0], x[:, 1:], whole)
+        n_ge = np.count_nonzero(x[:, 1:] >= x[:, :1], axis=1)
+        if self.permutations:
+            n_ge = np.where(whole & ~np.isnan(x[:, 0]), self.permutations, n_ge)
+        getattr(self, name)[rows] = x[:, 0]
+        for suffix, v in (("_null_mean", mean), ("_null_sd", sd), ("_ses", ses), ("_n_le", n_le), ("_n_ge", n_ge)):
+            getattr(self, name + suffix)[rows] = v
+        for tail, v in (("_p_le", n_le), ("_p_ge", n_ge)):
+            getattr(self, name + tail)[rows] = np.where(np.isnan(x[:, 0]), np.nan, (v + 1) / (self.permutations + 1))
+        if self.null_pd is not None:
+            getattr(self, "null_" + name)[rows] = x[:, 1:]
+
+    def fill_sets(self, k, pd_block):
+        """Reduce the (n_sets, permutations + 1) int64 block of PD sums of the sets, of sizes ``k``; before any fill_pairs."""
+        self.n[:] = np.asarray(k, dtype=np.int64)
+        self._pd_block[:] = pd_block
+        self.pd_q[:] = self._pd_block[:, 0]
+        self._reduce("pd", slice(0, self.n_sets), self._pd_block.astype(np.float64) * self.quantum, self.n == self.n_universe)
+
+    def fill_pairs(self, at, union_block):
+        """Reduce the (pairs, permutations + 1) int64 block of union sums of pairs [at, at + pairs) of this result."""
+        union = np.asarray(union_block, dtype=np.int64)
+        rows = slice(at, at + len(union))
+        i, j = SetUniFrac._rows(self.begin + at + np.arange(len(union), dtype=np.int64))
+        both = self._pd_block[i] + self._pd_block[j]      # (exact: below 2^62)
+        self.union_q[rows] = union[:, 0]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            unifrac = np.where(union != 0, (2 * union - both) / union.astype(np.float64), np.nan)
+            phylosor = np.where(both != 0, 2 * (both - union) / both.astype(np.float64), np.nan)
+        whole = (self.n[i] == self.n_universe) & (self.n[j] == self.n_universe)
+        self.n_nan[rows] = np.count_nonzero(np.isnan(unifrac[:, 1:]) | np.isnan(phylosor[:, 1:]), axis=1)
+        self._reduce("unifrac", rows, unifrac, whole)
+        self._reduce("phylosor", rows, phylosor, whole)
+
+    def matrix(self, which="unifrac_ses"):
+        """The square symmetric (n_sets, n_sets) form of a float pair column (``unifrac``, ``unifrac_ses``, ``phylosor_p_le``,
+        ...) with a zero diagonal; only where the result holds the whole triangle."""
+        if which not in self.COLUMNS or getattr(self, which).dtype != np.float64:
+            raise ValueError("which must be one of the float pair columns, such as 'unifrac', 'unifrac_ses' or 'phylosor_ses'")
+        if self.begin != 0 or self.count != self.n_sets * (self.n_sets - 1) // 2:
+            raise ValueError("matrix() needs the whole triangle, this result holds pairs [%d, +%d)" % (self.begin, self.count))
+        out = np.zeros((self.n_sets, self.n_sets))
+        i, j = SetUniFrac._rows(np.arange(self.count, dtype=np.int64))
+        out[i, j] = out[j, i] = getattr(self, which)
+        return out
+
+    def set_row(self, r) -> dict:
+        """Set r as a dict of Python scalars (plus ``leaf`` / ``name`` where the call knows them)."""
+        out = {c: getattr(self, c)[r].item() for c in self.SET_COLUMNS}
+        if self.leaves is not None:
+            out["leaf"], out["name"] = int(self.leaves[r]), self.names[r]
+        return out
+
+    def row(self, k) -> dict:
+        """Pair k as a dict of Python scalars: ``i``, ``j`` (and the two names where the call knows them), then the columns."""
+        i, j = self.pair(k)
+        out = {"i": i, "j": j}
+        if self.names is not None:
+            out["name_i"], out["name_j"] = self.names[i], self.names[j]
+        out.update({c: getattr(self, c)[k].item() for c in self.COLUMNS})
+        return out
+
+    def to_dataframe(self, which="pairs"):
+        """A pandas DataFrame (pandas imported here): ``which="pairs"``, one row per pair -- i, j (and the two names where
+        the call knows them), then the pair columns; ``which="sets"``, one row per set with the PD columns."""
+        import pandas as pd
+        if which == "sets":
+            cols = {} if self.leaves is None else {"name": self.names, "leaf": self.leaves}
+            cols.update({c: getattr(self, c) for c in self.SET_COLUMNS})
+            return pd.DataFrame(cols)
+        if which != "pairs":
+            raise ValueError("which must be 'pairs' or 'sets'")
+        i, j = SetUniFrac._rows(self.begin + np.arange(self.count, dtype=np.int64))
+        cols = {"i": i, "j": j}
+        if self.names is not None:
+            cols["name_i"], cols["name_j"] = [self.names[v] for v in i], [self.names[v] for v in j]
+        cols.update({c: getattr(self, c) for c in self.COLUMNS})
+        return pd.DataFrame(cols)
+
+
 def set_bit_rows(set_pos, offsets, n_universe):
     """The position sets (set_pos, offsets) over a universe of ``n_universe`` as rows of bits (uint8, eight positions each)."""
     n_sets = len(offsets) - 1

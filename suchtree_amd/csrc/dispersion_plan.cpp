@@ -20,9 +20,9 @@ int dispersion_call_args(int32_t n_univ, int64_t permutations, int64_t chunk_tas
 }
 
 void dispersion_cut(int32_t n_univ, int64_t rows, int64_t live, int64_t chunk_tasks, int64_t &perm_block, std::vector<DispersionChunk> &chunks,
-                    int64_t &max_chunk_tasks)
+                    int64_t &max_chunk_tasks, int64_t table_entries)
 {
-    int64_t block = std::max<int64_t>(1, kDispersionSigmaBytes / (2 * (int64_t)n_univ));
+    int64_t block = std::max<int64_t>(1, kDispersionSigmaBytes / (2 * ((int64_t)n_univ + table_entries)));
     int64_t cap = kDispersionChunkTasks;
     if (chunk_tasks > 0) {
         block = std::min(block, chunk_tasks);

@@ -73,11 +73,12 @@ int dispersion_plan(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const
 
 // What setpair_plan.cpp shares with this unit.  The first checks of a call, in this order: the universe size, nothing
 // negative (permutations, chunk_tasks, stream).  The cut of `live` tasks a permutation over `rows` permutations into blocks
-// and chunks by the rule above.  What a wave does with `a += shfl_xor(a, o)` over offsets width / 2 .. 1: v[0 .. width)
+// and chunks by the rule above; a caller that keeps `table_entries` further 16-bit entries a permutation beside the sigma
+// row (unifrac_null_plan.cpp) has them counted towards the block's bound.  What a wave does with `a += shfl_xor(a, o)` over offsets width / 2 .. 1: v[0 .. width)
 // in, every lane's total out.
 int dispersion_call_args(int32_t n_univ, int64_t permutations, int64_t chunk_tasks, int32_t stream, std::string &err);
 void dispersion_cut(int32_t n_univ, int64_t rows, int64_t live, int64_t chunk_tasks, int64_t &perm_block, std::vector<DispersionChunk> &chunks,
-                    int64_t &max_chunk_tasks);
+                    int64_t &max_chunk_tasks, int64_t table_entries = 0);
 void dispersion_butterfly(double *v, int width);
 
 // the record of the relabelled positions q[0 .. k) over the n x n matrix D, by the order rule of the contract

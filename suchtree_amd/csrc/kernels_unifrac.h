@@ -16,7 +16,8 @@
 //                     lanes stride over the elements of A, then over those of B not in A; each finds its successor in the
 //                     union by a binary search in the other list and adds q(d[x]) - min q(h[x .. next - 1]), or q(d[x])
 //                     for the union's last element.  An int64 butterfly finishes the task and lane 0 stores it.
-// Every result cell is written once: by its lane, or by the wave that drew it from the list.
+// Every result cell is written once: by its lane, or by the wave that drew it from the list.  The merge and the successor
+// sum are unifrac_merge and unifrac_successor below, shared with the null's pair kernels (kernels_unifrac_null.h).
 #pragma once
 
 #include "unifrac_plan.h"
@@ -52,11 +53,6 @@ struct UnifracArgs {
     int lane_max;                // tasks of more positions go to the heavy list (kUnifracLaneMax)
 };
 
-__device__ __forceinline__ int64_t unifrac_query(const UnifracArgs &a, int x, int y)
-{
-    return unifrac_rmq(a.table, a.m, x, y);
-}
-
 // the sets (j, i) of task t of the chunk, from the task of lane 0 of the wave (t0: i0, j0), `step` tasks on
 __device__ __forceinline__ void unifrac_step(long long &i, long long &j, unsigned step)
 {
@@ -65,6 +61,73 @@ __device__ __forceinline__ void unifrac_step(long long &i, long long &j, unsigne
         j -= i;
         i++;
     }
+}
+
+// U(A, B) by one lane: the two-pointer merge over the ascending lists A = pos[pa .. ea) and B = pos[pb .. eb), one gather of
+// d_q and one query per merged position.  Pos is int (the caller's positions) or unsigned short (a row of the relabelled
+// table of kernels_unifrac_null.h, laid out as the caller's positions are).
+template <typename Pos>
+__device__ __forceinline__ int64_t unifrac_merge(const int64_t *d_q, const int64_t *table, long long m, const Pos *pos, long long pa, long long ea,
+                                                 long long pb, long long eb)
+{
+    const int none = 0x7FFFFFFF;
+    int x = pa < ea ? (int)pos[pa] : none, y = pb < eb ? (int)pos[pb] : none, prev = -1;
+    int64_t sum = 0;
+    while (pa < ea || pb < eb) {
+        const int c = x < y ? x : y;
+        if (x == c) {
+            pa++;
+            x = pa < ea ? (int)pos[pa] : none;
+        }
+        if (y == c) {
+            pb++;
+            y = pb < eb ? (int)pos[pb] : none;
+        }
+        sum += d_q[c];
+        if (prev >= 0) sum -= unifrac_rmq(table, m, prev, c);
+        prev = c;
+    }
+    return sum;
+}
+
+// the first index in [lo, hi) whose position is > x (Upper) or >= x (!Upper)
+template <bool Upper, typename Pos>
+__device__ __forceinline__ long long unifrac_bound(const Pos *pos, long long lo, long long hi, int x)
+{
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        const int v = (int)pos[mid];
+        if (Upper ? v <= x : v < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// a lane's share of U(A, B) by one wave, the successor form, A = pos[a0 .. a1) and B = pos[b0 .. b1): the lanes stride over
+// the elements of A, then over those of B not in A (none where `same`: B is A); the caller adds the 64 shares up
+template <typename Pos>
+__device__ __forceinline__ int64_t unifrac_successor(const int64_t *d_q, const int64_t *table, long long m, const Pos *pos, long long a0, long long a1,
+                                                     long long b0, long long b1, bool same, unsigned lane)
+{
+    const int none = 0x7FFFFFFF;
+    int64_t sum = 0;
+    for (long long e = a0 + lane; e < a1; e += 64) {
+        const int x = (int)pos[e], in_a = e + 1 < a1 ? (int)pos[e + 1] : none;
+        const long long up = unifrac_bound<true>(pos, b0, b1, x);
+        const int in_b = up < b1 ? (int)pos[up] : none, next = in_a < in_b ? in_a : in_b;
+        sum += d_q[x];
+        if (next != none) sum -= unifrac_rmq(table, m, x, next);
+    }
+    for (long long e = b0 + lane; e < b1 && !same; e += 64) {      // (a PD task: B is A, every element is counted)
+        const int y = (int)pos[e], in_b = e + 1 < b1 ? (int)pos[e + 1] : none;
+        const long long lo = unifrac_bound<false>(pos, a0, a1, y);
+        const int in_a = lo < a1 ? (int)pos[lo] : none;
+        if (in_a == y) continue;      // (counted with A)
+        const int next = in_a < in_b ? in_a : in_b;
+        sum += d_q[y];
+        if (next != none) sum -= unifrac_rmq(table, m, y, next);
+    }
+    return sum;
 }
 
 __global__ __launch_bounds__(kUnifracThreads) void k_unifrac_lane(UnifracArgs a)
@@ -82,50 +145,18 @@ __global__ __launch_bounds__(kUnifracThreads) void k_unifrac_lane(UnifracArgs a)
         unifrac_step(i, j, t < a.count ? lane : 0);
     }
     if (t >= a.count) return;
-    long long pa = a.sets[j], pb = a.sets[i];
-    const long long ea = a.sets[j + 1], eb = a.sets[i + 1];
+    const long long pa = a.sets[j], pb = a.sets[i], ea = a.sets[j + 1], eb = a.sets[i + 1];
     if ((ea - pa) + (eb - pb) > a.lane_max) {
         a.heavy[atomicAdd(a.n_heavy, 1u)] = t;
         return;
     }
-    const int none = 0x7FFFFFFF;
-    int x = pa < ea ? a.set_pos[pa] : none, y = pb < eb ? a.set_pos[pb] : none, prev = -1;
-    int64_t sum = 0;
-    while (pa < ea || pb < eb) {
-        const int c = x < y ? x : y;
-        if (x == c) {
-            pa++;
-            x = pa < ea ? a.set_pos[pa] : none;
-        }
-        if (y == c) {
-            pb++;
-            y = pb < eb ? a.set_pos[pb] : none;
-        }
-        sum += a.d_q[c];
-        if (prev >= 0) sum -= unifrac_query(a, prev, c);
-        prev = c;
-    }
-    a.out[t] = sum;
-}
-
-// the first index in [lo, hi) whose position is > x (Upper) or >= x (!Upper)
-template <bool Upper>
-__device__ __forceinline__ long long unifrac_bound(const int *pos, long long lo, long long hi, int x)
-{
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        const int v = pos[mid];
-        if (Upper ? v <= x : v < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
+    a.out[t] = unifrac_merge(a.d_q, a.table, a.m, a.set_pos, pa, ea, pb, eb);
 }
 
 __global__ __launch_bounds__(kUnifracThreads) void k_unifrac_wave(UnifracArgs a)
 {
     const unsigned lane = threadIdx.x & 63, waves = gridDim.x * (kUnifracThreads / 64);
     const unsigned n_heavy = *a.n_heavy;      // (written by the launch before this one)
-    const int none = 0x7FFFFFFF;
     for (unsigned w = blockIdx.x * (kUnifracThreads / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); w < n_heavy; w += waves) {
         const unsigned t = (unsigned)__builtin_amdgcn_readfirstlane((int)a.heavy[w]);
         long long i, j;
@@ -137,24 +168,7 @@ __global__ __launch_bounds__(kUnifracThreads) void k_unifrac_wave(UnifracArgs a)
             i = i0;
             j = j0;
         }
-        const long long a0 = a.sets[j], a1 = a.sets[j + 1], b0 = a.sets[i], b1 = a.sets[i + 1];
-        int64_t sum = 0;
-        for (long long e = a0 + lane; e < a1; e += 64) {
-            const int x = a.set_pos[e], in_a = e + 1 < a1 ? a.set_pos[e + 1] : none;
-            const long long up = unifrac_bound<true>(a.set_pos, b0, b1, x);
-            const int in_b = up < b1 ? a.set_pos[up] : none, next = in_a < in_b ? in_a : in_b;
-            sum += a.d_q[x];
-            if (next != none) sum -= unifrac_query(a, x, next);
-        }
-        for (long long e = b0 + lane; e < b1 && i != j; e += 64) {      // (a PD task: B is A, every element is counted)
-            const int y = a.set_pos[e], in_b = e + 1 < b1 ? a.set_pos[e + 1] : none;
-            const long long lo = unifrac_bound<false>(a.set_pos, a0, a1, y);
-            const int in_a = lo < a1 ? a.set_pos[lo] : none;
-            if (in_a == y) continue;      // (counted with A)
-            const int next = in_a < in_b ? in_a : in_b;
-            sum += a.d_q[y];
-            if (next != none) sum -= unifrac_query(a, y, next);
-        }
+        int64_t sum = unifrac_successor(a.d_q, a.table, a.m, a.set_pos, a.sets[j], a.sets[j + 1], a.sets[i], a.sets[i + 1], i == j, lane);
         for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
         if (lane == 0) a.out[t] = sum;
     }

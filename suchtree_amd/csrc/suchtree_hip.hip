@@ -55,6 +55,9 @@
 // Faith's PD of many leaf sets and the union sums of their pairs behind UniFrac (st_unifrac_host, st_unifrac_depths):
 // kernels_unifrac.h (the range-minimum table, the set merge in a lane form and a wave form), host_unifrac.h (the depths, the
 // chunk driver) and, host-only, unifrac_plan.cpp (argument checks, the quantiser, chunks, the restatement of the merge).
+// The same sums under the taxa-labels null (st_unifrac_null_host, st_unifrac_null_depths): kernels_unifrac_null.h (the
+// relabelling of every set under every shuffle through an LDS bitmap, the pair kernels over the relabelled table),
+// host_unifrac_null.h (the block and chunk driver) and, host-only, unifrac_null_plan.cpp (checks, layout, restatement).
 // Every induced clade of one tree matched to the closest of another's, behind Robinson-Foulds and transfer support
 // (st_clade_ranges, st_clade_match): kernels_clade_match.h (a bitmap and running counts in LDS, one row per workgroup),
 // host_clade_match.h (the chunk driver) and, host-only, clade_match_plan.cpp (the range builder, the checks, the size
@@ -183,6 +186,7 @@ static int device_index_arg(int device)
 #include "kernels_dispersion.h"
 #include "kernels_setpair.h"
 #include "kernels_unifrac.h"
+#include "kernels_unifrac_null.h"
 #include "kernels_clade_match.h"
 
 
@@ -202,6 +206,7 @@ using namespace st;
 #include "host_dispersion.h"
 #include "host_setpair.h"
 #include "host_unifrac.h"
+#include "host_unifrac_null.h"
 #include "host_clade_match.h"
 
 extern "C" {
@@ -1435,6 +1440,47 @@ try {
         return ST_OK;
     }
     return unifrac_tree_run(t, root, univ, P, set_pos, n_pos, sets, shift, out_pd, out_union, out_shift, out_d, out_h, bad_id);
+} ST_CATCH_ALL
+
+int st_unifrac_null_depths(int device, const int64_t *d_q, const int64_t *h_q, int32_t n, const int32_t *set_pos, int64_t n_pos, const int64_t *sets,
+                           int64_t n_sets, int64_t k_begin, int64_t k_count, int64_t permutations, uint64_t seed, int32_t stream, int64_t chunk_tasks,
+                           int64_t *out_pd, int64_t *out_union)
+try {
+    UnifracNullPlan P;
+    std::string err;
+    int rc = unifrac_null_plan(n, set_pos, n_pos, sets, n_sets, k_begin, k_count, permutations, stream, chunk_tasks, out_pd != nullptr,
+                               out_union != nullptr, P, err);
+    if (rc == ST_OK) rc = unifrac_depth_args(d_q, h_q, n, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (device_or_host_arg(device) != ST_OK) return ST_ERR_ARG;
+    if (P.chunks.empty()) return ST_OK;      // (no sets, or no output asked for: nothing to launch)
+    if (device < 0) {
+        unifrac_null_host(d_q, h_q, P, set_pos, n_pos, sets, seed, stream, out_pd, out_union);
+        return ST_OK;
+    }
+    return unifrac_null_device(device, P, d_q, h_q, set_pos, n_pos, sets, seed, stream, out_pd, out_union);
+} ST_CATCH_ALL
+
+int st_unifrac_null_host(st_tree *t, int64_t root, const int64_t *univ, int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets,
+                         int64_t n_sets, int64_t k_begin, int64_t k_count, int32_t shift, int64_t permutations, uint64_t seed, int32_t stream,
+                         int64_t chunk_tasks, int64_t *out_pd, int64_t *out_union, int32_t *out_shift, int64_t *bad_id)
+try {
+    UnifracNullPlan P;
+    std::string err;
+    int rc = unifrac_null_plan(n_univ, set_pos, n_pos, sets, n_sets, k_begin, k_count, permutations, stream, chunk_tasks, out_pd != nullptr,
+                               out_union != nullptr, P, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (shift < -1 || shift > kUnifracMaxShift) return fail(ST_ERR_ARG, "shift must be -1 (automatic) or 0 to " + std::to_string(kUnifracMaxShift));
+    if (!univ) return fail(ST_ERR_ARG, "univ is NULL");
+    if (!t) return fail(ST_ERR_ARG, "tree is NULL");
+    rc = compare_check_ids(&root, 1, t->n_nodes, bad_id);
+    if (rc == ST_OK) rc = compare_check_ids(univ, n_univ, t->n_nodes, bad_id);
+    if (rc != ST_OK) return rc;
+    if (n_sets == 0) {      // (no sets: nothing to launch, and no depth is asked for)
+        if (out_shift) *out_shift = std::max(shift, 0);
+        return ST_OK;
+    }
+    return unifrac_null_tree_run(t, root, univ, P, set_pos, n_pos, sets, shift, seed, stream, out_pd, out_union, out_shift, bad_id);
 } ST_CATCH_ALL
 
 int st_clade_ranges(const int32_t *parent, int64_t n_nodes, const int64_t *leaf_ids, int32_t m, int32_t rooted, int32_t *out_order,

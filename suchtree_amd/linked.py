@@ -621,6 +621,29 @@ class SuchLinkedTrees:
                                            permutations=permutations, seed=seed, stream=root, keep_null=keep_null)
         return self._over_partner_rows(of, min_partners, max_partners, run, pool, _capi.HOMMOLA_MAX_UNIVERSE)
 
+    def partner_unifrac_null(self, of="A", pool="subset", min_partners=1, max_partners=None, begin=0, count=None, shift=None, permutations=999,
+                             seed=None, keep_null=False):
+        """Is a leaf's partner set, or the difference between two leaves' partner sets, more than its size explains:
+        Faith's PD of every leaf's partners and UniFrac / PhyloSor between every two, standardised against the taxa-labels
+        null (``pd_ses`` is picante's ``ses.pd``; ``unifrac_p_ge`` the label-shuffling significance of UniFrac).
+
+        The rows are those of :meth:`partner_unifrac`: ``of="A"``, one set per TreeA leaf of the current ``subset_a`` (in
+        ``subset_a_leafs`` order) with ``min_partners`` .. ``max_partners`` linked TreeB leaves inside the current
+        ``subset_b``; the branch lengths are TreeB's, from its current subset root.  ``of="B"`` is the mirror.  ``pool`` is
+        the universe whose labels are shuffled, as in :meth:`partner_dispersion`, and the shuffles are the same ones: the
+        same ``seed`` and ``pool`` relabel the sets exactly as there (``stream`` = the partner tree's subset root).
+        ``begin`` / ``count`` / ``shift`` / ``permutations`` / ``seed`` / ``keep_null`` as in :meth:`SuchTree.unifrac_null`,
+        which does the work.  A universe of more than 16384 leaves is a ValueError: subset it first.
+
+        The subset state, ``linklist`` and the generator of :meth:`sample_linked_distances` are left as they were.
+        Returns a :class:`~suchtree_amd.compare.SetUniFracNull` with ``leaves`` (the sets' leaf ids), ``names`` and
+        ``root``.  An extension: the reference has no counterpart.
+        """
+        def run(partner, sets, root, universe):
+            return partner.unifrac_null(sets, universe=universe, root=root, begin=begin, count=count, shift=shift, permutations=permutations,
+                                        seed=seed, stream=root, keep_null=keep_null)
+        return self._over_partner_rows(of, min_partners, max_partners, run, pool, _capi.HOMMOLA_MAX_UNIVERSE)
+
     @staticmethod
     def _leaf_counts(tree: SuchTree) -> np.ndarray:
         """Leaves under every node (st_clade_plan)."""

@@ -814,6 +814,65 @@ class SuchTree(TreeNavigation):
             out = compare.SetUniFrac(len(rows), begin, used, pd_q, union_q, root)
         return out
 
+    def unifrac_null(self, sets, universe=None, root=None, begin=0, count=None, shift=None, permutations=999, seed=None, stream=0,
+                     keep_null=False, chunk_tasks=0):
+        """Faith's PD of every set of leaves and the UniFrac and PhyloSor of every two, standardised against a permutation
+        null, on the GPU: picante's ``ses.pd`` and the label-shuffling significance of UniFrac.
+
+        ``sets`` and the sums are those of :meth:`unifrac`; the null is that of :meth:`dispersion`.  The universe is the
+        leaves under ``root`` (a node id; None = the tree's root), restricted to ``universe`` where given (a collection of
+        leaves), 3 to 16384 leaves in depth-first order; every member must be in it and a repeated member is a ValueError.
+        Shuffle p >= 1 is ``compare.hommola_permutation(seed, stream, p, 0, n)`` over the universe: set r becomes the
+        images of its members, and its PD and every pair's union sum are taken again, as exact integers over the depths
+        quantised to 2^-``shift`` (None = chosen from the largest depth of the universe).  One shuffle serves every set
+        of the call.  A set's and a pair's columns depend on (seed, ``stream``, root, the universe, shift, the one or
+        two sets) alone -- not on the other sets, the range or ``chunk_tasks`` -- and null column p is the same for any
+        ``permutations`` >= p; the observed values are those of :meth:`unifrac` at the same ``shift``.
+
+        The pairs are ``[begin, begin + count)`` of the triangle, as in :meth:`unifrac`.  ``seed=None`` draws a seed and
+        reports it; ``keep_null=True`` keeps the draws.  Returns a :class:`~suchtree_amd.compare.SetUniFracNull`.  An
+        extension: the reference has no counterpart.
+        """
+        from . import compare
+        permutations, seed = int_arg("permutations", permutations), seed_arg(seed)
+        stream = int_arg("stream", stream, (1 << 31) - 1, "2^31 - 1")
+        chunk_tasks = int_arg("chunk_tasks", chunk_tasks)
+        begin, count = int_arg("begin", begin), int_arg("count", count, optional=True)
+        shift = int_arg("shift", shift, optional=True)
+        root = self.root_node if root is None else self._validate_node(root)
+        if root != self.root_node:      # the leaves under root are one range of the depth-first order
+            leaf_ids = np.flatnonzero(np.asarray(self._flat.left) == -1).astype(np.int64)
+            plan = _capi.clade_plan(self._flat.parent, leaf_ids)
+            under = leaf_ids[plan["perm"]][int(plan["begin"][root]):int(plan["begin"][root]) + int(plan["count"][root])]
+            if universe is not None:
+                inside = np.zeros(self.size, dtype=bool)
+                inside[self._leaf_ids(universe, "universe")] = True
+                under = under[inside[under]]
+            universe = under
+        univ, rows = self._universe_and_sets(sets, universe)
+        total = len(rows) * (len(rows) - 1) // 2
+        if count is None:
+            count = total - int(begin)
+            if count > 1 << 31:
+                raise ValueError("the whole triangle of %d sets is %d pairs, more than 2^31: ask for ranges with begin= and count=" % (len(rows), total))
+        if begin + count > total or count < 0:
+            raise ValueError("pairs [%d, +%d) of a triangle of %d" % (begin, count, total))
+        table = self._position_table(univ, rows)
+        if not rows:      # (no sets: nothing is launched, and the tree stays where it is)
+            return compare.SetUniFracNull(0, begin, count, shift or 0, permutations, seed, len(univ), keep_null, root)
+        # PD of every set first (it fixes the shift), then the pairs a group at a time: a group's int64 block is bounded
+        pd_q, _, used = self._device_tree().unifrac_null_host(root, univ, table, 0, 0, shift, permutations, seed, stream, chunk_tasks, union=False)
+        out = compare.SetUniFracNull(len(rows), begin, count, used, permutations, seed, len(univ), keep_null, root)
+        out.fill_sets(np.diff(table[1]), pd_q)
+        shift = used if used >= 0 else None      # (a negative automatic shift cannot be passed: it is chosen again, the same)
+        per_group = max(1, 2 * self._DISPERSION_GROUP_ROWS // (permutations + 1))
+        for at in range(0, count, per_group):
+            n = min(per_group, count - at)
+            _, union_q, _ = self._device_tree().unifrac_null_host(root, univ, table, begin + at, n, shift, permutations, seed, stream,
+                                                                  chunk_tasks, pd=False)
+            out.fill_pairs(at, union_q)      # (each group is reduced before the next)
+        return out
+
     def common_ancestor(self, a: Union[int, str], b: Union[int, str]) -> int:
         """Most recent common ancestor of two nodes (MuchTree.pyx:1128-1149)."""
         node_a, node_b = self._validate_node_pair(a, b)
