@@ -159,14 +159,19 @@ def _dispersion_args(permutations, stream, chunk_tasks):
         raise ValueError("chunk_tasks < 0")
 
 
+def _square_matrix(D):
+    """(D as a C-order float32 array, n) of an (n, n) matrix"""
+    D = np.ascontiguousarray(D, dtype=np.float32)
+    if D.ndim != 2 or D.shape[0] != D.shape[1]:
+        raise ValueError("D must be a square matrix")
+    return D, int(D.shape[0])
+
+
 def dispersion_matrix(D, sets, permutations, seed, stream=0, device=-1, chunk_tasks=0):
     """st_dispersion_matrix: the (n_sets, permutations + 1) array of DISPERSION_RECORD of the position sets ``sets`` (an
     iterable of strictly increasing position collections, or a (set_pos, offsets) tuple of arrays) over the C-order
     float32 (n, n) matrix ``D``; ``device`` -1 = the host restatement (no GPU), else the kernels on that device."""
-    D = np.ascontiguousarray(D, dtype=np.float32)
-    if D.ndim != 2 or D.shape[0] != D.shape[1]:
-        raise ValueError("D must be a square matrix")
-    n = int(D.shape[0])
+    D, n = _square_matrix(D)
     _dispersion_args(permutations, stream, chunk_tasks)
     pos, off, n_sets = _dispersion_sets(sets, n)
     out = np.zeros((n_sets, int(permutations) + 1), dtype=DISPERSION_RECORD)
@@ -191,15 +196,21 @@ def _unifrac_range(n_sets, begin, count, chunk_pairs):
     return begin, count
 
 
+def _quantised_depths(d_q, h_q):
+    """(d_q, h_q) as C-order int64 arrays of n depths and n - 1"""
+    d_q = np.ascontiguousarray(d_q, dtype=np.int64)
+    h_q = np.ascontiguousarray(h_q, dtype=np.int64)
+    if d_q.ndim != 1 or h_q.ndim != 1 or len(h_q) != max(len(d_q) - 1, 0):
+        raise ValueError("d_q must hold n depths and h_q n - 1")
+    return d_q, h_q
+
+
 def beta_dispersion_matrix(D, sets, begin=0, count=None, exclude_shared=False, permutations=0, seed=0, stream=0, device=-1, chunk_tasks=0):
     """st_beta_dispersion_matrix: the (count, 2, permutations + 1) array of DISPERSION_RECORD (``pair_sum`` holds the cross
     sum) of pairs [begin, begin + count) of the triangle over the position sets ``sets`` (as in ``dispersion_matrix``),
     directions i -> j and j -> i, over the C-order float32 (n, n) matrix ``D``; ``device`` -1 = the host restatement (no
     GPU), else the kernels on that device."""
-    D = np.ascontiguousarray(D, dtype=np.float32)
-    if D.ndim != 2 or D.shape[0] != D.shape[1]:
-        raise ValueError("D must be a square matrix")
-    n = int(D.shape[0])
+    D, n = _square_matrix(D)
     _dispersion_args(permutations, stream, chunk_tasks)
     pos, off, n_sets = _dispersion_sets(sets, n)
     begin, count = _unifrac_range(n_sets, begin, count, 0)
@@ -227,10 +238,7 @@ def unifrac_depths(d_q, h_q, sets, begin=0, count=None, device=-1, chunk_pairs=0
     """st_unifrac_depths: (pd_q, union_q), the int64 PD of every set and union sum of pairs [begin, begin + count) of the
     triangle over the position sets ``sets`` (as in ``dispersion_matrix``), from the quantised depths ``d_q`` (n) and
     ``h_q`` (n - 1); ``device`` -1 = the host restatement (no GPU), else the kernels on that device."""
-    d_q = np.ascontiguousarray(d_q, dtype=np.int64)
-    h_q = np.ascontiguousarray(h_q, dtype=np.int64)
-    if d_q.ndim != 1 or h_q.ndim != 1 or len(h_q) != max(len(d_q) - 1, 0):
-        raise ValueError("d_q must hold n depths and h_q n - 1")
+    d_q, h_q = _quantised_depths(d_q, h_q)
     pos, off, n_sets = _dispersion_sets(sets, len(d_q))
     begin, count = _unifrac_range(n_sets, begin, count, chunk_pairs)
     pd_q, union_q = np.zeros(n_sets, dtype=np.int64), np.zeros(count, dtype=np.int64)
@@ -245,10 +253,7 @@ def unifrac_null_depths(d_q, h_q, sets, begin=0, count=None, permutations=0, see
     ``dispersion_matrix``) under every permutation p of the taxa-labels null, from the quantised depths ``d_q`` (n) and
     ``h_q`` (n - 1); column 0 is ``unifrac_depths``.  ``device`` -1 = the host restatement (no GPU), else the kernels on
     that device.  ``pd`` / ``union`` False: that output is not computed and comes back as None."""
-    d_q = np.ascontiguousarray(d_q, dtype=np.int64)
-    h_q = np.ascontiguousarray(h_q, dtype=np.int64)
-    if d_q.ndim != 1 or h_q.ndim != 1 or len(h_q) != max(len(d_q) - 1, 0):
-        raise ValueError("d_q must hold n depths and h_q n - 1")
+    d_q, h_q = _quantised_depths(d_q, h_q)
     _dispersion_args(permutations, stream, chunk_tasks)
     pos, off, n_sets = _dispersion_sets(sets, len(d_q))
     begin, count = _unifrac_range(n_sets, begin, count, 0)

@@ -52,17 +52,11 @@ int dispersion_plan(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const
     P.rows = R;
     for (int64_t r = 0; r < n_sets; r++)
         if (sets[r + 1] - sets[r] >= 2) P.order.push_back(r);
-    auto cls = [&](int64_t r) { return dispersion_class((int)(sets[r + 1] - sets[r])); };
-    std::stable_sort(P.order.begin(), P.order.end(), [&](int64_t a, int64_t b) { return cls(a) < cls(b); });
+    dispersion_order(
+        P.order, P.class_begin, [&](int64_t r) { return dispersion_class((int)(sets[r + 1] - sets[r])); }, [](int64_t, int64_t) { return false; });
     const int64_t live = (int64_t)P.order.size();
     P.sets.resize((size_t)live);
-    int64_t c = 0;
-    for (int k = 0; k < kDispersionClasses; k++) {
-        P.class_begin[k] = c;
-        while (c < live && cls(P.order[(size_t)c]) == k) c++;
-    }
-    P.class_begin[kDispersionClasses] = live;
-    for (c = 0; c < live; c++) {
+    for (int64_t c = 0; c < live; c++) {
         const int64_t r = P.order[(size_t)c];
         P.sets[(size_t)c] = DispersionSetDev{(int)sets[r], (int)(sets[r + 1] - sets[r])};
         P.max_count = std::max(P.max_count, P.sets[(size_t)c].count);
@@ -82,15 +76,10 @@ void dispersion_butterfly(double *v, int width)
 
 st_dispersion_record dispersion_record(const float *D, int32_t n, const int32_t *q, int32_t k)
 {
-    st_dispersion_record out{0.0, 0.0};
-    if (k < 2) return out;
-    const int lanes = k <= kDispersionWaveMax ? dispersion_lanes(k) : kDispersionThreads;
-    double a[kDispersionThreads], b[kDispersionThreads];
-    std::fill(a, a + lanes, 0.0);
-    std::fill(b, b + lanes, 0.0);
-    for (int32_t i = 0; i < k; i++) {
+    if (k < 2) return st_dispersion_record{0.0, 0.0};
+    return dispersion_lane_order(k, [&](int32_t i, double &sum, double &near) {
         const float *row = D + (size_t)q[i] * (size_t)n;
-        double sum = 0.0;
+        sum = 0.0;
         float m = std::numeric_limits<float>::infinity();
         for (int32_t j = 0; j < k; j++) {
             if (j == i) continue;
@@ -98,32 +87,8 @@ st_dispersion_record dispersion_record(const float *D, int32_t n, const int32_t 
             sum += (double)v;
             m = v < m ? v : m;
         }
-        if (k <= kDispersionWaveMax) {      // element i sits in lane i
-            a[i] = sum;
-            b[i] = (double)m;
-        } else {                            // lane i % 256 adds its elements in ascending order from 0.0
-            a[i % kDispersionThreads] += sum;
-            b[i % kDispersionThreads] += (double)m;
-        }
-    }
-    if (k <= kDispersionWaveMax) {
-        dispersion_butterfly(a, lanes);
-        dispersion_butterfly(b, lanes);
-        out.pair_sum = a[0];
-        out.nearest_sum = b[0];
-        return out;
-    }
-    for (int w = 0; w < kDispersionThreads / 64; w++) {      // every wave's butterfly, the wave totals in wave order
-        dispersion_butterfly(a + 64 * w, 64);
-        dispersion_butterfly(b + 64 * w, 64);
-    }
-    out.pair_sum = a[0];
-    out.nearest_sum = b[0];
-    for (int w = 1; w < kDispersionThreads / 64; w++) {
-        out.pair_sum += a[64 * w];
-        out.nearest_sum += b[64 * w];
-    }
-    return out;
+        near = (double)m;
+    });
 }
 
 void dispersion_host(const float *D, const DispersionPlan &P, const int32_t *set_pos, const int64_t *sets, uint64_t seed, int32_t stream,
@@ -137,14 +102,6 @@ void dispersion_host(const float *D, const DispersionPlan &P, const int32_t *set
             for (int64_t i = 0; i < k && k >= 2; i++) q[(size_t)i] = sigma[(size_t)set_pos[b + i]];
             out[r * P.rows + p] = dispersion_record(D, P.n_univ, q.data(), (int32_t)k);
         }
-    }
-}
-
-void dispersion_scatter(const DispersionPlan &P, const DispersionChunk &c, const st_dispersion_record *records, st_dispersion_record *out)
-{
-    for (int64_t j = 0; j < c.n_tasks; j++) {
-        const int64_t t = c.task_begin + j, s = t / c.n_perms, p = c.p_begin + (t - s * c.n_perms);
-        out[P.order[(size_t)s] * P.rows + p] = records[j];
     }
 }
 

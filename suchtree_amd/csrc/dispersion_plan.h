@@ -11,6 +11,7 @@
 // a block of n_perms permutations from p0, task t = c * n_perms + (p - p0) is set order[c] under permutation p, so a
 // class is one range of t, and a chunk is a range of t of one block.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -81,6 +82,58 @@ void dispersion_cut(int32_t n_univ, int64_t rows, int64_t live, int64_t chunk_ta
                     int64_t &max_chunk_tasks, int64_t table_entries = 0);
 void dispersion_butterfly(double *v, int width);
 
+// `order` by (size class, `before` within a class, index) and the class ranges of the layout above: cls(x) is the size
+// class of item x, before(a, b) a tie-break within a class (none: the items of a class stay in the order they came in)
+template <typename Cls, typename Before>
+void dispersion_order(std::vector<int64_t> &order, int64_t (&class_begin)[kDispersionClasses + 1], Cls cls, Before before)
+{
+    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
+        const int ca = cls(a), cb = cls(b);
+        return ca != cb ? ca < cb : before(a, b);
+    });
+    const int64_t live = (int64_t)order.size();
+    int64_t c = 0;
+    for (int k = 0; k < kDispersionClasses; k++) {
+        class_begin[k] = c;
+        while (c < live && cls(order[(size_t)c]) == k) c++;
+    }
+    class_begin[kDispersionClasses] = live;
+}
+
+// The lane-order tail of a record over k elements, by the order rule of the contract: element(i, sum, near) gives element
+// i's two terms.  Up to 64 elements, element i sits in lane i of K' lanes and one butterfly adds them; above, lane i % 256
+// adds its elements in ascending order from 0.0, every wave runs its butterfly and the wave totals are added in wave order.
+template <typename Element>
+st_dispersion_record dispersion_lane_order(int32_t k, Element element)
+{
+    const bool wave = k <= kDispersionWaveMax;
+    const int lanes = wave ? dispersion_lanes(k) : kDispersionThreads;
+    double a[kDispersionThreads], b[kDispersionThreads];
+    std::fill(a, a + lanes, 0.0);
+    std::fill(b, b + lanes, 0.0);
+    for (int32_t i = 0; i < k; i++) {
+        double sum, near;
+        element(i, sum, near);
+        if (wave) {
+            a[i] = sum;
+            b[i] = near;
+        } else {
+            a[i % kDispersionThreads] += sum;
+            b[i % kDispersionThreads] += near;
+        }
+    }
+    for (int w = 0; w < lanes; w += 64) {
+        dispersion_butterfly(a + w, std::min(lanes, 64));
+        dispersion_butterfly(b + w, std::min(lanes, 64));
+    }
+    st_dispersion_record out{a[0], b[0]};
+    for (int w = 64; w < lanes; w += 64) {
+        out.pair_sum += a[w];
+        out.nearest_sum += b[w];
+    }
+    return out;
+}
+
 // the record of the relabelled positions q[0 .. k) over the n x n matrix D, by the order rule of the contract
 st_dispersion_record dispersion_record(const float *D, int32_t n, const int32_t *q, int32_t k);
 
@@ -88,7 +141,24 @@ st_dispersion_record dispersion_record(const float *D, int32_t n, const int32_t 
 void dispersion_host(const float *D, const DispersionPlan &P, const int32_t *set_pos, const int64_t *sets, uint64_t seed, int32_t stream,
                      st_dispersion_record *out);
 
-// records[n] of tasks [task_begin, task_begin + n) of the block at p_begin into out
-void dispersion_scatter(const DispersionPlan &P, const DispersionChunk &c, const st_dispersion_record *records, st_dispersion_record *out);
+// entry j of chunk c: task t = c.task_begin + j is item `item` of the plan's order under permutation p
+inline void dispersion_task_of(const DispersionChunk &c, int64_t j, int64_t &item, int64_t &p)
+{
+    const int64_t t = c.task_begin + j;
+    item = t / c.n_perms;
+    p = c.p_begin + t % c.n_perms;
+}
+
+// records[n] of tasks [task_begin, task_begin + n) of the block at p_begin into out, for a plan of records (DispersionPlan,
+// SetpairPlan: item s of the order is row order[s] of out)
+template <typename Plan>
+void dispersion_scatter(const Plan &P, const DispersionChunk &c, const st_dispersion_record *records, st_dispersion_record *out)
+{
+    for (int64_t j = 0; j < c.n_tasks; j++) {
+        int64_t s, p;
+        dispersion_task_of(c, j, s, p);
+        out[P.order[(size_t)s] * P.rows + p] = records[j];
+    }
+}
 
 }  // namespace st

@@ -103,7 +103,7 @@ struct MomentsReduce {
     }
 };
 
-// What the chunk drivers (compare_run below, quartet_run, hommola_clades_run, partner_dispersion_run, unifrac_tree_run) share: both trees'
+// What the chunk drivers (compare_run below, quartet_run, hommola_clades_run, record_tree_run, unifrac_tree_depths) share: both trees'
 // pipe mutexes, one device block, one stream, the two host fault words.  Declared after ST_DEVICE(...) and after whatever
 // else its stream's work touches (device_res.h).  Both trees live on one device and so share its staging pipe and that
 // pipe's mutex (host_tree.h): one lock, also when tree_x == tree_y; distinct mutexes (not possible today) are taken in

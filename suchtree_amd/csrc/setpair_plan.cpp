@@ -4,18 +4,9 @@
 #include "plan_checks.h"
 
 #include <algorithm>
-#include <cmath>
 #include <limits>
 
 namespace st {
-
-void setpair_rows(int64_t k, int64_t &i, int64_t &j)
-{
-    i = (int64_t)((1.0 + std::sqrt(1.0 + 8.0 * (double)k)) / 2.0);
-    while (i > 1 && i * (i - 1) / 2 > k) i--;
-    while ((i + 1) * i / 2 <= k) i++;
-    j = k - i * (i - 1) / 2;
-}
 
 int setpair_plan(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets, int64_t begin, int64_t count,
                  int32_t exclude_shared, int64_t permutations, int32_t stream, int64_t chunk_tasks, SetpairPlan &P, std::string &err)
@@ -24,8 +15,7 @@ int setpair_plan(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const in
     if (const int rc = position_sets_args(n_univ, set_pos, n_pos, sets, n_sets, err); rc != ST_OK) return rc;
     if (begin < 0 || count < 0) return fail(ST_ERR_ARG, err, "a negative triangle range");
     const int64_t total = n_sets > ((int64_t)1 << 31) ? std::numeric_limits<int64_t>::max() : n_sets * (n_sets - 1) / 2;
-    if (begin > total || count > total - begin)
-        return fail(ST_ERR_ARG, err, "pairs [" + std::to_string(begin) + ", +" + std::to_string(count) + ") of a triangle of " + std::to_string(total));
+    if (const int rc = triangle_range_args(total, begin, count, err); rc != ST_OK) return rc;
     if (count > kSetpairMaxPairs) return fail(ST_ERR_ARG, err, "more than 2^31 pairs in one call");
     const int64_t R = permutations + 1;
     if (count > 0 && R > ((int64_t)1 << 39) / count) return fail(ST_ERR_ARG, err, "more than 2^40 records in one call");
@@ -39,7 +29,7 @@ int setpair_plan(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const in
     auto size = [&](int64_t r) { return (int)(sets[r + 1] - sets[r]); };
     std::vector<SetpairTaskDev> all((size_t)(2 * count));      // by direction u
     int64_t i = 0, j = 0;
-    if (count > 0) setpair_rows(begin, i, j);
+    if (count > 0) unifrac_pair(begin, i, j);
     for (int64_t u = 0; u < 2 * count; u += 2) {
         all[(size_t)u] = SetpairTaskDev{(int)sets[i], size(i), (int)sets[j], size(j)};
         all[(size_t)u + 1] = SetpairTaskDev{(int)sets[j], size(j), (int)sets[i], size(i)};
@@ -50,20 +40,12 @@ int setpair_plan(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const in
     }
     for (int64_t u = 0; u < 2 * count; u++)
         if (all[(size_t)u].r_count >= 1 && all[(size_t)u].c_count >= 1) P.order.push_back(u);
-    auto cls = [&](int64_t u) { return dispersion_class(all[(size_t)u].r_count); };
-    std::stable_sort(P.order.begin(), P.order.end(), [&](int64_t a, int64_t b) {
-        const int ca = cls(a), cb = cls(b);
-        return ca != cb ? ca < cb : all[(size_t)a].c_count < all[(size_t)b].c_count;
-    });
+    dispersion_order(
+        P.order, P.class_begin, [&](int64_t u) { return dispersion_class(all[(size_t)u].r_count); },
+        [&](int64_t a, int64_t b) { return all[(size_t)a].c_count < all[(size_t)b].c_count; });
     const int64_t live = (int64_t)P.order.size();
     P.tasks.resize((size_t)live);
-    int64_t c = 0;
-    for (int k = 0; k < kDispersionClasses; k++) {
-        P.class_begin[k] = c;
-        while (c < live && cls(P.order[(size_t)c]) == k) c++;
-    }
-    P.class_begin[kDispersionClasses] = live;
-    for (c = 0; c < live; c++) {
+    for (int64_t c = 0; c < live; c++) {
         P.tasks[(size_t)c] = all[(size_t)P.order[(size_t)c]];
         if (c >= P.class_begin[kDispersionClasses - 1]) P.max_walk = std::max(P.max_walk, P.tasks[(size_t)c].c_count);
     }
@@ -74,15 +56,10 @@ int setpair_plan(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const in
 st_dispersion_record setpair_record(const float *D, int32_t n, const int32_t *qr, const int32_t *sr, int32_t kr, const int32_t *qc,
                                     const int32_t *sc, int32_t kc, bool exclude)
 {
-    st_dispersion_record out{0.0, 0.0};
-    if (kr < 1) return out;
-    const int lanes = kr <= kDispersionWaveMax ? dispersion_lanes(kr) : kDispersionThreads;
-    double a[kDispersionThreads], b[kDispersionThreads];
-    std::fill(a, a + lanes, 0.0);
-    std::fill(b, b + lanes, 0.0);
-    for (int32_t i = 0; i < kr; i++) {
+    if (kr < 1) return st_dispersion_record{0.0, 0.0};
+    return dispersion_lane_order(kr, [&](int32_t i, double &sum, double &near) {
         const float *row = D + (size_t)qr[i] * (size_t)n;
-        double sum = 0.0;
+        sum = 0.0;
         float m = std::numeric_limits<float>::infinity();
         for (int32_t j = 0; j < kc; j++) {
             if (exclude && sc[j] == sr[i]) continue;
@@ -92,33 +69,8 @@ st_dispersion_record setpair_record(const float *D, int32_t n, const int32_t *qr
         }
         // no included entry: by the sets alone, never by the value of m
         const bool none = kc == 0 || (exclude && kc == 1 && sc[0] == sr[i]);
-        const double near = none ? 0.0 : (double)m;
-        if (kr <= kDispersionWaveMax) {      // element i sits in lane i
-            a[i] = sum;
-            b[i] = near;
-        } else {                             // lane i % 256 adds its elements in ascending order from 0.0
-            a[i % kDispersionThreads] += sum;
-            b[i % kDispersionThreads] += near;
-        }
-    }
-    if (kr <= kDispersionWaveMax) {
-        dispersion_butterfly(a, lanes);
-        dispersion_butterfly(b, lanes);
-        out.pair_sum = a[0];
-        out.nearest_sum = b[0];
-        return out;
-    }
-    for (int w = 0; w < kDispersionThreads / 64; w++) {      // every wave's butterfly, the wave totals in wave order
-        dispersion_butterfly(a + 64 * w, 64);
-        dispersion_butterfly(b + 64 * w, 64);
-    }
-    out.pair_sum = a[0];
-    out.nearest_sum = b[0];
-    for (int w = 1; w < kDispersionThreads / 64; w++) {
-        out.pair_sum += a[64 * w];
-        out.nearest_sum += b[64 * w];
-    }
-    return out;
+        near = none ? 0.0 : (double)m;
+    });
 }
 
 void setpair_host(const float *D, const SetpairPlan &P, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, uint64_t seed, int32_t stream,
@@ -129,7 +81,7 @@ void setpair_host(const float *D, const SetpairPlan &P, const int32_t *set_pos, 
         perm_host(seed, stream, p, 0, P.n_univ, sigma.data());      // (one sigma serves every set)
         for (int64_t x = 0; x < n_pos; x++) q[(size_t)x] = sigma[(size_t)set_pos[x]];
         int64_t i, j;
-        setpair_rows(P.begin, i, j);
+        unifrac_pair(P.begin, i, j);
         for (int64_t k = 0; k < P.count; k++) {
             const int64_t bi = sets[i], ki = sets[i + 1] - bi, bj = sets[j], kj = sets[j + 1] - bj;
             out[(2 * k) * P.rows + p] =
@@ -141,14 +93,6 @@ void setpair_host(const float *D, const SetpairPlan &P, const int32_t *set_pos, 
                 j = 0;
             }
         }
-    }
-}
-
-void setpair_scatter(const SetpairPlan &P, const DispersionChunk &c, const st_dispersion_record *records, st_dispersion_record *out)
-{
-    for (int64_t j = 0; j < c.n_tasks; j++) {
-        const int64_t t = c.task_begin + j, s = t / c.n_perms, p = c.p_begin + (t - s * c.n_perms);
-        out[P.order[(size_t)s] * P.rows + p] = records[j];
     }
 }
 

@@ -11,6 +11,7 @@
 // t = c * n_perms + (p - p0) is direction order[c] under permutation p, as in DispersionPlan.
 #pragma once
 #include "dispersion_plan.h"
+#include "plan_checks.h"      // the pair order (unifrac_pair)
 
 namespace st {
 
@@ -35,9 +36,6 @@ struct SetpairPlan {
     int64_t max_chunk_tasks = 0;
 };
 
-// (i, j), j < i, of triangle index k = i (i - 1) / 2 + j
-void setpair_rows(int64_t k, int64_t &i, int64_t &j);
-
 // ST_OK, or ST_ERR_ARG with `err`.  Checks, in this order: those of dispersion_plan -- the universe size, nothing negative
 // (permutations, chunk_tasks, stream), the set table (position_sets_args, plan_checks.h) -- then the range: nothing
 // negative, inside the triangle of n_sets (n_sets - 1) / 2 pairs, at most 2^31 pairs, at most 2^40 records.  Then the
@@ -53,8 +51,5 @@ st_dispersion_record setpair_record(const float *D, int32_t n, const int32_t *qr
 // every record of the call on the host: out[u * rows + p]
 void setpair_host(const float *D, const SetpairPlan &P, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, uint64_t seed, int32_t stream,
                   st_dispersion_record *out);
-
-// records[n] of tasks [task_begin, task_begin + n) of the block at p_begin into out
-void setpair_scatter(const SetpairPlan &P, const DispersionChunk &c, const st_dispersion_record *records, st_dispersion_record *out);
 
 }  // namespace st

@@ -33,7 +33,8 @@
 // pieces, row blocks), host_compare.h (TwoTreeSession, ReadbackRing, the chunk driver compare_run and its reducers, the pair
 // inputs, statistics and the one skeleton, compare_entry, of the triangle / pairs entry points) and,
 // host-only C++ beside tree_prep.cpp, compare_plan.cpp (argument checks, clade plan and tables, rows layout, the fold);
-// plan_checks.h is what the plan units share in their checks (how one fails, a table of position sets).
+// plan_checks.h is what the plan units share in their checks (how one fails, a table of position sets, a range of the
+// triangle of set pairs and that triangle's index, which the kernels share).
 // Exact Spearman rank sums of the same pairs (st_compare_*_ranks_host): kernels_ranks.h, the reducers at the end of
 // host_compare.h and, host-only, rank_plan.cpp (keys, bucket layout, tie arithmetic, st_spearman_host).
 // Exact Kendall tau-b counts of the same pairs (st_compare_*_kendall_host, st_kendall_arrays_host): kernels_kendall.h (keys,
@@ -50,14 +51,15 @@
 // kernels_dispersion.h (one sort per permutation, the k x k reducer in three size classes), host_dispersion.h (the chunk
 // driver) and, host-only, dispersion_plan.cpp (argument checks, size classes, chunks, the restatement of the reduction).
 // betaMPD / betaMNTD sums between every two leaf sets under the same null (st_beta_dispersion_host, st_beta_dispersion_matrix):
-// kernels_setpair.h (the k_r x k_c reducer in the same three size classes), host_setpair.h (the launches; the driver is
-// host_dispersion.h's) and, host-only, setpair_plan.cpp (argument checks, the task table, the restatement).
+// kernels_setpair.h (the k_r x k_c reducer in the same three size classes), host_dispersion.h (one launcher, chunk driver,
+// tree run and matrix run for both passes) and, host-only, setpair_plan.cpp (argument checks, the task table, the restatement).
 // Faith's PD of many leaf sets and the union sums of their pairs behind UniFrac (st_unifrac_host, st_unifrac_depths):
 // kernels_unifrac.h (the range-minimum table, the set merge in a lane form and a wave form), host_unifrac.h (the depths, the
 // chunk driver) and, host-only, unifrac_plan.cpp (argument checks, the quantiser, chunks, the restatement of the merge).
 // The same sums under the taxa-labels null (st_unifrac_null_host, st_unifrac_null_depths): kernels_unifrac_null.h (the
 // relabelling of every set under every shuffle through an LDS bitmap, the pair kernels over the relabelled table),
-// host_unifrac_null.h (the block and chunk driver) and, host-only, unifrac_null_plan.cpp (checks, layout, restatement).
+// host_unifrac_null.h (its part of the work block and its launches; the head of the block and the depths are
+// host_unifrac.h's, the loop over blocks and chunks host_dispersion.h's) and, host-only, unifrac_null_plan.cpp (checks, layout, restatement).
 // Every induced clade of one tree matched to the closest of another's, behind Robinson-Foulds and transfer support
 // (st_clade_ranges, st_clade_match): kernels_clade_match.h (a bitmap and running counts in LDS, one row per workgroup),
 // host_clade_match.h (the chunk driver) and, host-only, clade_match_plan.cpp (the range builder, the checks, the size
@@ -204,7 +206,6 @@ using namespace st;
 #include "host_quartets.h"
 #include "host_hommola.h"
 #include "host_dispersion.h"
-#include "host_setpair.h"
 #include "host_unifrac.h"
 #include "host_unifrac_null.h"
 #include "host_clade_match.h"
@@ -1322,6 +1323,17 @@ try {
     return hommola_clades_run(to, tc, univ_o, univ_c, pos_o, pos_c, n_links, P, seed, out, bad_id);
 } ST_CATCH_ALL
 
+// The tree side of a set entry's checks, after its plan's, in this order: univ NULL, out NULL where the call has records to
+// write, the tree NULL, then the ids against the tree -- the root first, where the entry takes one
+static int set_tree_args(const st_tree *t, const int64_t *univ, int32_t n_univ, bool out_missing, const int64_t *root, int64_t *bad_id)
+{
+    if (!univ) return fail(ST_ERR_ARG, "univ is NULL");
+    if (out_missing) return fail(ST_ERR_ARG, "out is NULL");
+    if (!t) return fail(ST_ERR_ARG, "tree is NULL");
+    const int rc = root ? compare_check_ids(root, 1, t->n_nodes, bad_id) : ST_OK;
+    return rc == ST_OK ? compare_check_ids(univ, n_univ, t->n_nodes, bad_id) : rc;
+}
+
 int st_partner_dispersion_host(st_tree *t, const int64_t *univ, int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets,
                                int64_t n_sets, int64_t permutations, uint64_t seed, int32_t stream, int64_t chunk_tasks,
                                st_dispersion_record *out, int64_t *bad_id)
@@ -1330,16 +1342,13 @@ try {
     std::string err;
     int rc = dispersion_plan(n_univ, set_pos, n_pos, sets, n_sets, permutations, stream, chunk_tasks, P, err);
     if (rc != ST_OK) return fail(rc, err);
-    if (!univ) return fail(ST_ERR_ARG, "univ is NULL");
-    if (n_sets > 0 && !out) return fail(ST_ERR_ARG, "out is NULL");
-    if (!t) return fail(ST_ERR_ARG, "tree is NULL");
-    rc = compare_check_ids(univ, n_univ, t->n_nodes, bad_id);
+    rc = set_tree_args(t, univ, n_univ, n_sets > 0 && !out, nullptr, bad_id);
     if (rc != ST_OK) return rc;
     if (P.chunks.empty()) {      // (no set of two positions: nothing to launch)
         std::fill_n(out, P.n_sets * P.rows, st_dispersion_record{0.0, 0.0});
         return ST_OK;
     }
-    return partner_dispersion_run(t, univ, P, set_pos, n_pos, seed, stream, out, bad_id);
+    return record_tree_run("partner dispersion", t, univ, P, set_pos, n_pos, seed, stream, out, bad_id);
 } ST_CATCH_ALL
 
 int st_dispersion_matrix(int device, const float *D, int32_t n, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets,
@@ -1356,7 +1365,7 @@ try {
         dispersion_host(D, P, set_pos, sets, seed, stream, out);
         return ST_OK;
     }
-    return dispersion_matrix_device(device, D, P, set_pos, n_pos, seed, stream, out);
+    return record_matrix_device("dispersion matrix", device, D, P, set_pos, n_pos, seed, stream, out);
 } ST_CATCH_ALL
 
 int st_beta_dispersion_host(st_tree *t, const int64_t *univ, int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets,
@@ -1367,16 +1376,13 @@ try {
     std::string err;
     int rc = setpair_plan(n_univ, set_pos, n_pos, sets, n_sets, begin, count, exclude_shared, permutations, stream, chunk_tasks, P, err);
     if (rc != ST_OK) return fail(rc, err);
-    if (!univ) return fail(ST_ERR_ARG, "univ is NULL");
-    if (count > 0 && !out) return fail(ST_ERR_ARG, "out is NULL");
-    if (!t) return fail(ST_ERR_ARG, "tree is NULL");
-    rc = compare_check_ids(univ, n_univ, t->n_nodes, bad_id);
+    rc = set_tree_args(t, univ, n_univ, count > 0 && !out, nullptr, bad_id);
     if (rc != ST_OK) return rc;
     if (P.chunks.empty()) {      // (no pair, or none with two members to compare: nothing to launch)
         std::fill_n(out, 2 * P.count * P.rows, st_dispersion_record{0.0, 0.0});
         return ST_OK;
     }
-    return setpair_run(t, univ, P, set_pos, n_pos, seed, stream, out, bad_id);
+    return record_tree_run("beta dispersion", t, univ, P, set_pos, n_pos, seed, stream, out, bad_id);
 } ST_CATCH_ALL
 
 int st_beta_dispersion_matrix(int device, const float *D, int32_t n, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets,
@@ -1394,7 +1400,7 @@ try {
         setpair_host(D, P, set_pos, n_pos, sets, seed, stream, out);
         return ST_OK;
     }
-    return setpair_matrix_device(device, D, P, set_pos, n_pos, seed, stream, out);
+    return record_matrix_device("beta dispersion matrix", device, D, P, set_pos, n_pos, seed, stream, out);
 } ST_CATCH_ALL
 
 int st_unifrac_quantise(const float *d, const float *h, int32_t n, int32_t shift, int64_t *out_dq, int64_t *out_hq, int32_t *out_shift)
@@ -1428,12 +1434,9 @@ try {
     UnifracPlan P;
     std::string err;
     int rc = unifrac_plan(n_univ, set_pos, n_pos, sets, n_sets, k_begin, k_count, chunk_pairs, out_pd != nullptr, out_union != nullptr, P, err);
+    if (rc == ST_OK) rc = unifrac_shift_arg(shift, err);
     if (rc != ST_OK) return fail(rc, err);
-    if (shift < -1 || shift > kUnifracMaxShift) return fail(ST_ERR_ARG, "shift must be -1 (automatic) or 0 to " + std::to_string(kUnifracMaxShift));
-    if (!univ) return fail(ST_ERR_ARG, "univ is NULL");
-    if (!t) return fail(ST_ERR_ARG, "tree is NULL");
-    rc = compare_check_ids(&root, 1, t->n_nodes, bad_id);
-    if (rc == ST_OK) rc = compare_check_ids(univ, n_univ, t->n_nodes, bad_id);
+    rc = set_tree_args(t, univ, n_univ, false, &root, bad_id);
     if (rc != ST_OK) return rc;
     if (n_sets == 0) {      // (no sets: nothing to launch, and no depth is asked for)
         if (out_shift) *out_shift = std::max(shift, 0);
@@ -1469,12 +1472,9 @@ try {
     std::string err;
     int rc = unifrac_null_plan(n_univ, set_pos, n_pos, sets, n_sets, k_begin, k_count, permutations, stream, chunk_tasks, out_pd != nullptr,
                                out_union != nullptr, P, err);
+    if (rc == ST_OK) rc = unifrac_shift_arg(shift, err);
     if (rc != ST_OK) return fail(rc, err);
-    if (shift < -1 || shift > kUnifracMaxShift) return fail(ST_ERR_ARG, "shift must be -1 (automatic) or 0 to " + std::to_string(kUnifracMaxShift));
-    if (!univ) return fail(ST_ERR_ARG, "univ is NULL");
-    if (!t) return fail(ST_ERR_ARG, "tree is NULL");
-    rc = compare_check_ids(&root, 1, t->n_nodes, bad_id);
-    if (rc == ST_OK) rc = compare_check_ids(univ, n_univ, t->n_nodes, bad_id);
+    rc = set_tree_args(t, univ, n_univ, false, &root, bad_id);
     if (rc != ST_OK) return rc;
     if (n_sets == 0) {      // (no sets: nothing to launch, and no depth is asked for)
         if (out_shift) *out_shift = std::max(shift, 0);

@@ -15,10 +15,7 @@ int unifrac_null_plan(int32_t n, const int32_t *set_pos, int64_t n_pos, const in
     if (const int rc = position_sets_args(n, set_pos, n_pos, sets, n_sets, err); rc != ST_OK) return rc;
     if (k_begin < 0 || k_count < 0) return fail(ST_ERR_ARG, err, "a negative triangle range");
     if (n_sets > ((int64_t)1 << 30)) return fail(ST_ERR_ARG, err, "more than 2^30 sets");
-    const int64_t total = n_sets > 0 ? n_sets * (n_sets - 1) / 2 : 0;
-    if (k_begin > total || k_count > total - k_begin)
-        return fail(ST_ERR_ARG, err, "pairs [" + std::to_string(k_begin) + ", +" + std::to_string(k_count) + ") of a triangle of " +
-                                         std::to_string(total));
+    if (const int rc = triangle_range_args(n_sets > 0 ? n_sets * (n_sets - 1) / 2 : 0, k_begin, k_count, err); rc != ST_OK) return rc;
     const int64_t R = permutations + 1, most = std::max(n_sets, k_count);
     if (most > 0 && R > ((int64_t)1 << 40) / most) return fail(ST_ERR_ARG, err, "more than 2^40 values in one output array");
     P = UnifracNullPlan{};
@@ -67,7 +64,8 @@ void unifrac_null_host(const int64_t *d_q, const int64_t *h_q, const UnifracNull
 void unifrac_null_scatter(const UnifracNullPlan &P, const DispersionChunk &c, const int64_t *results, int64_t *out_pd, int64_t *out_union)
 {
     for (int64_t j = 0; j < c.n_tasks; j++) {
-        const int64_t t = c.task_begin + j, s = t / c.n_perms, p = c.p_begin + (t - s * c.n_perms);
+        int64_t s, p;
+        dispersion_task_of(c, j, s, p);
         if (s < P.n_sets) {
             if (P.want_pd) out_pd[s * P.rows + p] = results[j];
         } else {

@@ -23,10 +23,7 @@ int unifrac_plan(int32_t n, const int32_t *set_pos, int64_t n_pos, const int64_t
     if (k_begin < 0 || k_count < 0) return fail(ST_ERR_ARG, err, "a negative triangle range");
     if (n_sets > ((int64_t)1 << 30)) return fail(ST_ERR_ARG, err, "more than 2^30 sets");
     if (const int rc = position_sets_args(n, set_pos, n_pos, sets, n_sets, err); rc != ST_OK) return rc;
-    const int64_t total = n_sets > 0 ? n_sets * (n_sets - 1) / 2 : 0;
-    if (k_begin > total || k_count > total - k_begin)
-        return fail(ST_ERR_ARG, err, "pairs [" + std::to_string(k_begin) + ", +" + std::to_string(k_count) + ") of a triangle of " +
-                                         std::to_string(total));
+    if (const int rc = triangle_range_args(n_sets > 0 ? n_sets * (n_sets - 1) / 2 : 0, k_begin, k_count, err); rc != ST_OK) return rc;
     P = UnifracPlan{};
     P.n = n;
     P.m = (int64_t)n - 1;
@@ -46,11 +43,17 @@ int unifrac_plan(int32_t n, const int32_t *set_pos, int64_t n_pos, const int64_t
     return ST_OK;
 }
 
+int unifrac_shift_arg(int32_t shift, std::string &err)
+{
+    if (shift < -1 || shift > kUnifracMaxShift) return fail(ST_ERR_ARG, err, "shift must be -1 (automatic) or 0 to " + std::to_string(kUnifracMaxShift));
+    return ST_OK;
+}
+
 int unifrac_quantise(const float *d, const float *h, int32_t n, int32_t shift, int64_t *d_q, int64_t *h_q, int32_t *shift_used, std::string &err)
 {
     if (const int rc = universe_arg(n, err); rc != ST_OK) return rc;
     if (!d || (n > 1 && !h)) return fail(ST_ERR_ARG, err, "d or h is NULL");
-    if (shift < -1 || shift > kUnifracMaxShift) return fail(ST_ERR_ARG, err, "shift must be -1 (automatic) or 0 to " + std::to_string(kUnifracMaxShift));
+    if (const int rc = unifrac_shift_arg(shift, err); rc != ST_OK) return rc;
     float top = 0.0f;
     for (int32_t k = 0; k < 2 * n - 1; k++) {
         const float v = k < n ? d[k] : h[k - n];

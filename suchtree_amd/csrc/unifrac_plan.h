@@ -13,7 +13,7 @@
 #include <string>
 #include <vector>
 
-#include "quartet_plan.h"      // ST_QUARTET_HD, the public header
+#include "plan_checks.h"      // ST_QUARTET_HD, the public header, the pair order (unifrac_pair)
 
 namespace st {
 
@@ -35,30 +35,6 @@ ST_QUARTET_HD int unifrac_levels(int64_t m)
         m >>= 1;
     }
     return L;
-}
-
-// floor(sqrt(x)), x < 2^63: integers only
-ST_QUARTET_HD uint64_t unifrac_isqrt(uint64_t x)
-{
-    uint64_t r = 0, bit = (uint64_t)1 << 62;
-    while (bit > x) bit >>= 2;
-    while (bit) {
-        if (x >= r + bit) {
-            x -= r + bit;
-            r = (r >> 1) + bit;
-        } else {
-            r >>= 1;
-        }
-        bit >>= 2;
-    }
-    return r;
-}
-
-// pair k of the triangle: k = i (i - 1) / 2 + j, 0 <= j < i.  8 k + 1 = (2 i - 1)^2 + 8 j lies in [(2 i - 1)^2, (2 i + 1)^2)
-ST_QUARTET_HD void unifrac_pair(int64_t k, int64_t &i, int64_t &j)
-{
-    i = (int64_t)((1 + unifrac_isqrt(8 * (uint64_t)k + 1)) >> 1);
-    j = k - i * (i - 1) / 2;
 }
 
 // min h_q[x .. y - 1], 0 <= x < y <= m, over the table M (level l at M + l * m: M[l][k] = min h_q[k .. k + 2^l - 1])
@@ -93,6 +69,9 @@ struct UnifracPlan {
 // layout above: PD chunks if want_pd, pair chunks if want_union; chunk_pairs 0 = kUnifracChunkPairs.
 int unifrac_plan(int32_t n, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets, int64_t k_begin, int64_t k_count,
                  int64_t chunk_pairs, bool want_pd, bool want_union, UnifracPlan &P, std::string &err);
+
+// ST_ERR_ARG unless shift is -1 (automatic) or 0 .. kUnifracMaxShift
+int unifrac_shift_arg(int32_t shift, std::string &err);
 
 // q(v) = llrint(ldexp((double) v, shift)) of d[0 .. n) and h[0 .. n - 1).  shift -1: 39 - ilogb(max |v|), 0 when that
 // maximum is 0.  ST_ERR_ARG: n outside 1 .. kUnifracMaxUniverse, a value that is not finite, a shift outside

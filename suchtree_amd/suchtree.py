@@ -67,6 +67,21 @@ def int_arg(name, v, top=None, top_text=None, optional=False):
     return int(v)
 
 
+def _null_args(permutations, seed, stream, chunk_tasks):
+    """The arguments of a permutation null (``dispersion``, ``beta_dispersion``, ``unifrac_null``), checked in this order."""
+    return (int_arg("permutations", permutations), seed_arg(seed), int_arg("stream", stream, (1 << 31) - 1, "2^31 - 1"),
+            int_arg("chunk_tasks", chunk_tasks))
+
+
+def _triangle_range(n_rows, begin, count):
+    """(begin, count) of pairs [begin, begin + count) of the triangle over ``n_rows`` sets; ``count`` None = up to the last
+    pair, which above 2^31 pairs is a ValueError."""
+    total = n_rows * (n_rows - 1) // 2
+    if count is None and total - begin > 1 << 31:
+        raise ValueError("the whole triangle of %d sets is %d pairs, more than 2^31: ask for ranges with begin= and count=" % (n_rows, total))
+    return _capi._unifrac_range(n_rows, begin, count, 0)
+
+
 def seed_arg(seed):
     """A 64-bit seed: the caller's, or a fresh draw where it is None."""
     if seed is None:
@@ -702,9 +717,7 @@ class SuchTree(TreeNavigation):
         Returns a :class:`~suchtree_amd.compare.SetDispersion`.  An extension: the reference has no counterpart.
         """
         from . import compare
-        permutations, seed = int_arg("permutations", permutations), seed_arg(seed)
-        stream = int_arg("stream", stream, (1 << 31) - 1, "2^31 - 1")
-        chunk_tasks = int_arg("chunk_tasks", chunk_tasks)
+        permutations, seed, stream, chunk_tasks = _null_args(permutations, seed, stream, chunk_tasks)
         univ, rows = self._universe_and_sets(sets, universe)
         set_pos, offsets = self._position_table(univ, rows)
         k = np.diff(offsets)
@@ -736,18 +749,10 @@ class SuchTree(TreeNavigation):
         extension: the reference has no counterpart.
         """
         from . import compare
-        permutations, seed = int_arg("permutations", permutations), seed_arg(seed)
-        stream = int_arg("stream", stream, (1 << 31) - 1, "2^31 - 1")
-        chunk_tasks = int_arg("chunk_tasks", chunk_tasks)
+        permutations, seed, stream, chunk_tasks = _null_args(permutations, seed, stream, chunk_tasks)
         begin, count = int_arg("begin", begin), int_arg("count", count, optional=True)
         univ, rows = self._universe_and_sets(sets, universe)
-        total = len(rows) * (len(rows) - 1) // 2
-        if count is None:
-            count = total - int(begin)
-            if count > 1 << 31:
-                raise ValueError("the whole triangle of %d sets is %d pairs, more than 2^31: ask for ranges with begin= and count=" % (len(rows), total))
-        if begin + count > total or count < 0:
-            raise ValueError("pairs [%d, +%d) of a triangle of %d" % (begin, count, total))
+        begin, count = _triangle_range(len(rows), begin, count)
         set_pos, offsets = self._position_table(univ, rows)
         k = np.diff(offsets)
         out = compare.SetBetaDispersion(len(rows), begin, count, permutations, seed, len(univ), exclude_shared, keep_null)
@@ -799,13 +804,7 @@ class SuchTree(TreeNavigation):
             raise ValueError("leaf %d does not lie under node %d" % (int(univ[~inside[univ]][0]), root))
         if len(univ) > _capi.UNIFRAC_MAX_UNIVERSE:
             raise ValueError("the sets hold %d distinct leaves: at most %d" % (len(univ), _capi.UNIFRAC_MAX_UNIVERSE))
-        total = len(rows) * (len(rows) - 1) // 2
-        if count is None:
-            count = total - int(begin)
-            if count > 1 << 31:
-                raise ValueError("the whole triangle of %d sets is %d pairs, more than 2^31: ask for ranges with begin= and count=" % (len(rows), total))
-        if begin + count > total or count < 0:
-            raise ValueError("pairs [%d, +%d) of a triangle of %d" % (begin, count, total))
+        begin, count = _triangle_range(len(rows), begin, count)
         if not len(univ):      # (no member at all: nothing is launched, and the tree stays where it is)
             out = compare.SetUniFrac(len(rows), begin, shift or 0, np.zeros(len(rows), dtype=np.int64), np.zeros(count, dtype=np.int64), root)
         else:
@@ -834,9 +833,7 @@ class SuchTree(TreeNavigation):
         extension: the reference has no counterpart.
         """
         from . import compare
-        permutations, seed = int_arg("permutations", permutations), seed_arg(seed)
-        stream = int_arg("stream", stream, (1 << 31) - 1, "2^31 - 1")
-        chunk_tasks = int_arg("chunk_tasks", chunk_tasks)
+        permutations, seed, stream, chunk_tasks = _null_args(permutations, seed, stream, chunk_tasks)
         begin, count = int_arg("begin", begin), int_arg("count", count, optional=True)
         shift = int_arg("shift", shift, optional=True)
         root = self.root_node if root is None else self._validate_node(root)
@@ -850,13 +847,7 @@ class SuchTree(TreeNavigation):
                 under = under[inside[under]]
             universe = under
         univ, rows = self._universe_and_sets(sets, universe)
-        total = len(rows) * (len(rows) - 1) // 2
-        if count is None:
-            count = total - int(begin)
-            if count > 1 << 31:
-                raise ValueError("the whole triangle of %d sets is %d pairs, more than 2^31: ask for ranges with begin= and count=" % (len(rows), total))
-        if begin + count > total or count < 0:
-            raise ValueError("pairs [%d, +%d) of a triangle of %d" % (begin, count, total))
+        begin, count = _triangle_range(len(rows), begin, count)
         table = self._position_table(univ, rows)
         if not rows:      # (no sets: nothing is launched, and the tree stays where it is)
             return compare.SetUniFracNull(0, begin, count, shift or 0, permutations, seed, len(univ), keep_null, root)

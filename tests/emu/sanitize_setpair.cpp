@@ -62,7 +62,7 @@ static int check_case(const Case &C, int64_t begin, int64_t count, int exclude, 
     std::vector<int64_t> set_r((size_t)dirs), set_c((size_t)dirs);
     for (int64_t k = 0; k < count; k++) {
         int64_t i, j;
-        setpair_rows(begin + k, i, j);
+        unifrac_pair(begin + k, i, j);
         CHECK(j >= 0 && j < i && i * (i - 1) / 2 + j == begin + k);
         set_r[(size_t)(2 * k)] = set_c[(size_t)(2 * k + 1)] = i;
         set_c[(size_t)(2 * k)] = set_r[(size_t)(2 * k + 1)] = j;
@@ -107,7 +107,7 @@ static int check_case(const Case &C, int64_t begin, int64_t count, int exclude, 
                 const int64_t t = k.task_begin + j, c = t / k.n_perms, p = k.p_begin + t % k.n_perms;
                 rec[(size_t)j] = want[(size_t)(Q.order[(size_t)c] * R + p)];
             }
-            setpair_scatter(Q, k, rec.data(), got.data());
+            dispersion_scatter(Q, k, rec.data(), got.data());
             t_next += k.n_tasks;
             if (t_next == live * k.n_perms) {
                 t_next = 0;
@@ -147,8 +147,34 @@ static int check_case(const Case &C, int64_t begin, int64_t count, int exclude, 
     return 0;
 }
 
+// The triangle index the plans and the kernels share (plan_checks.h: unifrac_pair) where the float square root and the
+// correction loops it replaced here were exact: the first 5,000 pairs and both sides of a row's first pair, up to rows
+// past 2^31 (a table of more than 2^31 empty sets), where 8 k + 1 no longer fits 64 bits.
+static int check_triangle_index()
+{
+    auto closed_form = [](int64_t k) {
+        int64_t i = -1, j = -1;
+        unifrac_pair(k, i, j);
+        return i >= 1 && j >= 0 && j < i && j == k - i * (i - 1) / 2;
+    };
+    for (int64_t k = 0; k < 5000; k++) CHECK(closed_form(k));
+    const int64_t two31 = (int64_t)1 << 31;
+    for (int64_t i : {(int64_t)2, (int64_t)3, (int64_t)1 << 16, ((int64_t)1 << 16) + 1, two31 - 1, two31, two31 + 1}) {
+        const int64_t first = i * (i - 1) / 2;
+        int64_t r, j;
+        unifrac_pair(first - 1, r, j);
+        CHECK(r == i - 1 && j == i - 2 && closed_form(first - 1));
+        unifrac_pair(first, r, j);
+        CHECK(r == i && j == 0 && closed_form(first));
+        unifrac_pair(first + 1, r, j);
+        CHECK(r == i && j == 1 && closed_form(first + 1));
+    }
+    return 0;
+}
+
 int main()
 {
+    if (check_triangle_index()) return 1;
     for (int32_t n : {3, 64, 65, 700}) {
         Case C;
         C.n = n;
