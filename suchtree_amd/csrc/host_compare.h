@@ -392,6 +392,45 @@ struct CladeReduce {
     }
 };
 
+// st_compare_clades_host behind its checks and its plan (red.P, red.T; at least one pair): the links staged in the plan's order, then
+// the chunks of `chunk` pairs.
+static int clades_run(st_tree *tx, st_tree *ty, const int64_t *ids_x, const int64_t *ids_y, int64_t n_links, int64_t chunk, CladeReduce &red,
+                      int64_t *bad_id)
+{
+    const CladePlan &P = red.P;
+    const CladeTables &T = red.T;
+    // device: permuted ids of X and Y and ranks (int32) | segments | tiles
+    const size_t L = (size_t)n_links;
+    const size_t o_y = align256(L * 4), o_rank = o_y + align256(L * 4), o_seg = o_rank + align256(L * 4);
+    const size_t o_tile = o_seg + align256(T.segs.size() * sizeof(CladeSeg)), extra = o_tile + align256(T.tiles.size() * sizeof(CladeTile));
+    std::vector<int32_t> sx(L), sy(L), rk(L);
+    for (size_t p = 0; p < L; p++) {
+        const int64_t j = P.perm[p];
+        sx[p] = (int32_t)ids_x[j];
+        sy[p] = (int32_t)ids_y[j];
+        rk[p] = (int32_t)j;
+    }
+    auto setup = [&](char *d, hipStream_t s) {
+        red.d_seg = reinterpret_cast<const CladeSeg *>(d + o_seg);
+        red.d_tile = reinterpret_cast<const CladeTile *>(d + o_tile);
+        hipError_t e = hipMemcpyAsync(d, sx.data(), L * 4, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d + o_y, sy.data(), L * 4, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d + o_rank, rk.data(), L * 4, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d + o_seg, T.segs.data(), T.segs.size() * sizeof(CladeSeg), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d + o_tile, T.tiles.data(), T.tiles.size() * sizeof(CladeTile), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);      // (the host vectors are pageable and go out of scope with this call)
+        return e;
+    };
+    auto prep = [](char *, hipStream_t, int64_t, int64_t) { return hipSuccess; };
+    auto src = [&](size_t o_ids) {
+        return [&, o_ids](char *d, int64_t off) {
+            return SrcSegments{reinterpret_cast<const int *>(d + o_ids), reinterpret_cast<const int *>(d + o_rank),
+                               reinterpret_cast<const CladeSeg *>(d + o_seg), reinterpret_cast<const CladeTile *>(d + o_tile), (long long)off};
+        };
+    };
+    return compare_run(tx, ty, P.total, chunk, extra, setup, prep, src(0), src(o_y), red, bad_id);
+}
+
 // The reducer of st_compare_rows_host: k_row_blocks per chunk into one of two device piece buffers, each read back into
 // its pinned host twin (ReadbackRing); the host folds a chunk's pieces into their rows (block order, clade_merge) while
 // the device works on the next chunk.  Pieces of at most two chunks exist at any time.
@@ -437,6 +476,37 @@ struct RowsReduce {
         return e == hipSuccess ? ST_OK : fail(ST_ERR_HIP, std::string("rows read-back: ") + hipGetErrorString(e));
     }
 };
+
+// st_compare_rows_host behind its checks: n_rows > 0 rows of m checked ids each (below n_nodes, so int32), staged and run.
+static int rows_run(st_tree *tx, st_tree *ty, const int64_t *ids_x, const int64_t *ids_y, int64_t n_rows, int64_t m, const RowsLayout &L,
+                    st_pair_moments *out, int64_t *bad_id)
+{
+    const int64_t n_ids = n_rows * m;
+    const std::vector<int32_t> hx(ids_x, ids_x + n_ids), hy(ids_y, ids_y + n_ids);
+    // device: the int32 ids of up to max_rows rows from row `up_lo` on, X then Y; uploaded again when a chunk needs others
+    const size_t row_bytes = (size_t)m * 4, half = align256((size_t)L.max_rows * row_bytes);
+    int64_t up_lo = -1, up_hi = -1;
+    auto setup = [](char *, hipStream_t) { return hipSuccess; };
+    auto prep = [&](char *d, hipStream_t s, int64_t off, int64_t c) {
+        const int64_t r0 = off / L.S, r1 = (off + c - 1) / L.S + 1;
+        if (r1 - r0 > L.max_rows) return hipErrorInvalidValue;
+        if (r0 >= up_lo && r1 <= up_hi) return hipSuccess;
+        up_lo = r0;
+        up_hi = std::min(n_rows, r0 + L.max_rows);
+        const size_t b = (size_t)(up_hi - up_lo) * row_bytes;
+        hipError_t e = hipMemcpyAsync(d, hx.data() + up_lo * m, b, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d + half, hy.data() + up_lo * m, b, hipMemcpyHostToDevice, s);
+        return e;
+    };
+    auto src = [&](size_t o) {
+        return [&, o](char *d, int64_t off) {
+            return SrcRows{reinterpret_cast<const int *>(d + o), (long long)m, (long long)L.P, (long long)L.S, 1.0 / (double)L.S,
+                           (long long)off, (long long)up_lo};
+        };
+    };
+    RowsReduce red(L, out);
+    return compare_run(tx, ty, n_rows * L.S, L.chunk, 2 * half, setup, prep, src(0), src(half), red, bad_id);
+}
 
 // ---- exact Spearman rank sums (st_compare_*_ranks_host; kernels_ranks.h, rank_plan.h) ------------------------------
 // What the three passes share.  It outlives each pass's compare_run (which frees its own block), so the entry point

@@ -160,6 +160,21 @@ inline void narrow_pairs_i64(int32_t *dst, const int64_t *src, int64_t m, long l
     _mm_sfence();
 }
 
+// The same for (m,2) ids of either width at any element strides s0 / s1 (a column-major array, a view of every other row):
+// int32 (m,2) in C order, the same clamp, the same exact extremes.
+template <typename Id>
+inline void narrow_pairs_strided(int32_t *dst, const Id *src, int64_t m, int64_t s0, int64_t s1, long long &hi, long long &lo)
+{
+    for (int64_t k = 0; k < m; k++)
+        for (int c = 0; c < 2; c++) {
+            const long long v = src[k * s0 + c * s1];
+            int32_t w = (int32_t)v;
+            if (v > INT32_MAX) { w = INT32_MAX; if (v > hi) hi = v; }
+            else if (v < INT32_MIN) { w = INT32_MIN; if (v < lo) lo = v; }
+            dst[2 * k + c] = w;
+        }
+}
+
 // (m,2) ids, element strides s0 / s1 -> 24 bits per id, 6 bytes per pair (the wire format of trees with fewer than
 // 2^24 nodes; device_common.h::SrcContig32::packed48).  `first` = index of the first pair in the destination (the
 // packed stream is written in 8-byte words where it can).  Ids outside [0, n_nodes) become 0xFFFFFF -- out of range

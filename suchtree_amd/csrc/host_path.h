@@ -165,17 +165,16 @@ struct HostOut {
     bool wire24 = false;      // MRCA ids cross the link as 24 bits each (device_common.h::MrcaSink)
 };
 
-// MRCA ids come back as 24 bits each on trees of fewer than 2^24 nodes (option wire24)
-static bool wire24_of(const st_tree *t, const HostOut &out)
-{
-    return out.mrca && t->wire24 && t->n_nodes <= 0xFFFFFF;
-}
-
-static HostOut make_host_out(double *out_dist, int32_t *out_mrca)
+// The prologue of a staged call of n pairs.  MRCA ids come back as 24 bits each on trees of fewer than 2^24 nodes (option
+// wire24); fresh result arrays: ask for huge pages before the first touch (a no-op on resident memory).
+static HostOut host_out_of(const st_tree *t, double *out_dist, int32_t *out_mrca, int64_t n)
 {
     HostOut o;
     o.dist = out_dist;
     o.mrca = out_mrca;
+    o.wire24 = out_mrca && t->wire24 && t->n_nodes <= 0xFFFFFF;
+    if (out_dist && !looks_resident(out_dist, n * 8)) advise_huge(out_dist, n * 8);
+    if (out_mrca && !looks_resident(out_mrca, n * 4)) advise_huge(out_mrca, n * 4);
     return o;
 }
 
@@ -232,6 +231,16 @@ static int launch_chunk(st_tree *r, PipeSlot &s, int64_t off, int64_t m, int in_
     }
     if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("device staging: ") + hipGetErrorString(e));
     return ST_OK;
+}
+
+// The way out of a pipeline with chunks in flight: every slot's stream drained, no slot left busy, then the failure.
+static int pipe_bail(HostPipe &P, int code, const std::string &msg)
+{
+    for (auto &s : P.slot) {
+        if (s.stream) (void)hipStreamSynchronize(s.stream);
+        s.busy = false;
+    }
+    return fail(code, msg);
 }
 
 // Push this device's chunks of a batch through the slots of the pipe (host_pipe.h).
@@ -327,13 +336,6 @@ static int run_pipe(st_tree *t, const ChunkSeq &seq, Pack pack, Launch launch, c
             if (pm) populate_for_write(pm + off + b, (e - b) * 4);
         }, kPopulateGrainBytes / 8);
     };
-    auto bail = [&](int code, const std::string &msg) {
-        for (auto &s : P.slot) {
-            if (s.stream) (void)hipStreamSynchronize(s.stream);
-            s.busy = false;
-        }
-        return fail(code, msg);
-    };
     // This device's chunks, the first and the last of them cut into pieces of 1/8, 1/8, 1/4, 1/2 (and the mirror
     // image): the GPU has nothing to do while the first piece is packed, and the host nothing to overlap with while
     // the last one is unpacked, so those two are kept small (5e7 pairs in 2^22-pair chunks: ~0.5 of 10 ms).
@@ -368,23 +370,23 @@ static int run_pipe(st_tree *t, const ChunkSeq &seq, Pack pack, Launch launch, c
         const int64_t off = pc.off, m = pc.m;
         PipeSlot &s = P.slot[k % kPipeSlots];
         hipError_t e = drain(s);
-        if (e != hipSuccess) return bail(ST_ERR_HIP, std::string("pipeline: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return pipe_bail(P,ST_ERR_HIP, std::string("pipeline: ") + hipGetErrorString(e));
         Clock::time_point tp = trace ? Clock::now() : Clock::time_point();
         if (!skip_cpu) pack(s, off, m);
         lap(t_pack, tp);
         if (!skip_gpu) {
             const int rc = launch(s, off, m);
-            if (rc != ST_OK) return bail(rc, g_last_error);
+            if (rc != ST_OK) return pipe_bail(P,rc, g_last_error);
             if (pc.last) {
                 // last piece of this device: fetch the fault word behind it (and behind the pieces
                 // still in flight on the other streams), so that one wait covers results and faults
                 for (PipeSlot &other : P.slot)
                     if (&other != &s && other.busy && e == hipSuccess) e = hipStreamWaitEvent(s.stream, other.done, 0);
                 if (e == hipSuccess) e = hipMemcpyAsync(P.h_fault, t->d_fault_host, sizeof(Fault), hipMemcpyDeviceToHost, s.stream);
-                if (e != hipSuccess) return bail(ST_ERR_HIP, std::string("pipeline: ") + hipGetErrorString(e));
+                if (e != hipSuccess) return pipe_bail(P,ST_ERR_HIP, std::string("pipeline: ") + hipGetErrorString(e));
             }
             e = hipEventRecord(s.done, s.stream);
-            if (e != hipSuccess) return bail(ST_ERR_HIP, std::string("pipeline: ") + hipGetErrorString(e));
+            if (e != hipSuccess) return pipe_bail(P,ST_ERR_HIP, std::string("pipeline: ") + hipGetErrorString(e));
         }
         s.busy = true;
         s.off = off;
@@ -394,11 +396,11 @@ static int run_pipe(st_tree *t, const ChunkSeq &seq, Pack pack, Launch launch, c
         lap(t_prefault, tp);
         k++;
         e = drain(P.slot[k % kPipeSlots]);   // unpack the oldest piece while the newer ones are in flight
-        if (e != hipSuccess) return bail(ST_ERR_HIP, std::string("pipeline: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return pipe_bail(P,ST_ERR_HIP, std::string("pipeline: ") + hipGetErrorString(e));
     }
     for (int j = 0; j < kPipeSlots; j++) {     // oldest first
         const hipError_t e = drain(P.slot[(k + j) % kPipeSlots]);
-        if (e != hipSuccess) return bail(ST_ERR_HIP, std::string("pipeline: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return pipe_bail(P,ST_ERR_HIP, std::string("pipeline: ") + hipGetErrorString(e));
     }
     if (k > 0 && !skip_gpu) {
         fault = *static_cast<const Fault *>(P.h_fault);
@@ -458,4 +460,143 @@ static int for_each_replica(st_tree *t, int64_t n, Fault &fault, Work work)
         merge_fault(fault, faults[(size_t)d]);
     }
     return ST_OK;
+}
+
+// One staged run of a host-path call of n pairs.  Every replica readies its pipe (ensure() creates the streams where they do not
+// exist yet) and room for n_ids ids, arms its fault word, uploads what its chunks read before the first of them --
+// upload(pipe) -- and pushes them through: chunks(replica, seq, fault), which ends in run_pipe.  Then the fault is reported.
+// (begin_host_faults fails with ST_ERR_HIP alone, its message in place.)
+template <typename Upload, typename Chunks>
+static int staged_host_run(st_tree *t, int64_t n, int64_t n_ids, Upload upload, Chunks chunks, int64_t *bad_id)
+{
+    auto work = [&](st_tree *r, const ChunkSeq &seq, Fault &fault) -> int {
+        HostPipe &P = r->dp->pipe;
+        hipError_t e = P.ensure(std::max<int64_t>(seq.chunk, 1024));
+        if (e == hipSuccess) e = P.ensure_ids(n_ids);
+        if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("host staging allocation: ") + hipGetErrorString(e));
+        int rc = begin_host_faults(r, P.slot[0].stream);
+        if (rc == ST_OK) rc = upload(P);
+        if (rc == ST_OK) rc = chunks(r, seq, fault);
+        return rc;
+    };
+    Fault fault;
+    const int rc = for_each_replica(t, n, fault, work);
+    if (rc != ST_OK) return rc;
+    return report_fault(t->n_nodes, fault, bad_id);
+}
+
+// ... of pairs generated from id lists: the lists go up once per device, nothing is packed, results stream back through the
+// pipe.  make_src(d_ids, off) is the pair source of the chunk that starts at pair `off`.
+template <typename Upload, typename MakeSrc>
+static int generated_host_run(st_tree *t, int64_t n, int64_t n_ids, const HostOut &out, Upload upload, MakeSrc make_src, int64_t *bad_id)
+{
+    auto chunks = [&](st_tree *r, const ChunkSeq &seq, Fault &fault) {
+        auto pack = [](PipeSlot &, int64_t, int64_t) {};
+        auto launch = [&](PipeSlot &s, int64_t off, int64_t c) {
+            const auto src = make_src(static_cast<long long *>(r->dp->pipe.d_ids), off);
+            return launch_chunk(r, s, off, c, 0, out, [&](const void *) { return src; });
+        };
+        return run_pipe(r, seq, pack, launch, out, fault);
+    };
+    return staged_host_run(t, n, n_ids, upload, chunks, bad_id);
+}
+
+// pairs k_begin .. k_begin + k_count of the triangle over m ids
+static int triangle_host_run(st_tree *t, const int64_t *ids, int64_t m, int64_t id_stride, int64_t k_begin, int64_t k_count,
+                             double *out_dist, int32_t *out_mrca, int64_t *bad_id)
+{
+    const HostOut out = host_out_of(t, out_dist, out_mrca, k_count);
+    std::vector<int64_t> packed;
+    const int64_t *src_ids = ids;
+    if (id_stride != 1) {
+        packed.resize((size_t)m);
+        for (int64_t i = 0; i < m; i++) packed[(size_t)i] = ids[i * id_stride];
+        src_ids = packed.data();
+    }
+    auto upload = [&](HostPipe &P) {
+        ST_HIP(hipMemcpy(P.d_ids, src_ids, (size_t)m * 8, hipMemcpyHostToDevice));
+        return ST_OK;
+    };
+    auto make_src = [&](const long long *d_ids, int64_t off) { return SrcTriangle{d_ids, 1, (long long)(k_begin + off)}; };
+    return generated_host_run(t, k_count, m, out, upload, make_src, bad_id);
+}
+
+// elements e_begin .. e_begin + e_count of the rows x columns grid (rows, then columns, in the pipe's id space)
+static int grid_host_run(st_tree *t, const int64_t *row_ids, int64_t n_rows, const int64_t *col_ids, int64_t n_cols, int symmetric,
+                         int64_t e_begin, int64_t e_count, double *out_dist, int32_t *out_mrca, int64_t *bad_id)
+{
+    const HostOut out = host_out_of(t, out_dist, out_mrca, e_count);
+    auto upload = [&](HostPipe &P) {
+        long long *d_rows = static_cast<long long *>(P.d_ids), *d_cols = d_rows + n_rows;
+        ST_HIP(hipMemcpy(d_rows, row_ids, (size_t)n_rows * 8, hipMemcpyHostToDevice));
+        ST_HIP(hipMemcpy(d_cols, col_ids, (size_t)n_cols * 8, hipMemcpyHostToDevice));
+        return ST_OK;
+    };
+    auto make_src = [&](const long long *d_ids, int64_t off) {
+        return SrcGrid{d_ids, d_ids + n_rows, (long long)n_cols, (long long)(e_begin + off), symmetric};
+    };
+    return generated_host_run(t, e_count, n_rows + n_cols, out, upload, make_src, bad_id);
+}
+
+// a lane's out-of-range extremes into its replica's, under the mutex (a lane that met none takes no lock)
+static void fold_extremes(Fault &wide, std::mutex &wide_mutex, long long hi, long long lo)
+{
+    if (hi == kFaultInit.max_bad && lo == kFaultInit.min_bad) return;
+    std::lock_guard<std::mutex> g(wide_mutex);
+    wide.max_bad = std::max(wide.max_bad, hi);
+    wide.min_bad = std::min(wide.min_bad, lo);
+}
+
+// n > 0 explicit pairs from a host buffer of int64 ids (the reference's dtype) or int32 ids.
+template <typename Id>
+static int distances_host_run(st_tree *t, const Id *pairs, int64_t n, int64_t stride0, int64_t stride1, double *out_dist, int32_t *out_mrca,
+                              int64_t *bad_id)
+{
+    // (deep canopies: beyond the walk/canopy switch the tile-sorted kernel beats the mailbox's walk)
+    // (deep canopies without lineage sums: the walk is slow there, the tile-sorted kernel takes over at 4096 pairs)
+    if (n <= (t->tile_sort && !(t->d_lineage && t->lineage_sums) ? kCanopyMinPairs - 1 : kMailboxPairs) && t->small_batch_path) {
+        ST_DEVICE(t->device);
+        return small_batch(t, pairs, n, stride0, stride1, out_dist, out_mrca, bad_id);
+    }
+    const HostOut out = host_out_of(t, out_dist, out_mrca, n);
+    // Ids cross PCIe as int32 (half the H2D bytes).  Values that do not fit are clamped to
+    // INT32_MAX / INT32_MIN -- still out of range for the kernel -- and their exact extremes
+    // are kept here so that the reported id is the one the reference would report.
+    auto chunks = [&](st_tree *r, const ChunkSeq &seq, Fault &fault) -> int {
+        CopyPool &pool = r->dp->pipe.pool;
+        std::mutex wide_mutex;
+        Fault wide = kFaultInit;
+        // trees with fewer than 2^24 nodes: 24 bits per id on the wire (6 instead of 8 bytes per pair over the link;
+        // the range check is then the host's, host_copy.h::pack_pairs48)
+        const bool wire48 = r->wire48 && r->n_nodes <= 0xFFFFFF;
+        auto pack = [&](PipeSlot &s, int64_t off, int64_t m) {
+            const Id *src = pairs + off * stride0;
+            int32_t *dst = static_cast<int32_t *>(s.h_in);
+            const bool c_order = stride0 == 2 && stride1 == 1;
+            if (sizeof(Id) == 4 && c_order && !wire48) {   // int32 C-order: already the wire format
+                pool.parallel_for(m, [=](int64_t b, int64_t e) { copy_stream(dst + 2 * b, src + 2 * b, (e - b) * 8); });
+                return;
+            }
+            const long long n_nodes = r->n_nodes;
+            pool.parallel_for(m, [&, src, dst, n_nodes](int64_t b, int64_t e) {
+                long long hi = kFaultInit.max_bad, lo = kFaultInit.min_bad;
+                if (wire48) pack_pairs48(reinterpret_cast<uint8_t *>(dst), b, src + b * stride0, e - b, stride0, stride1, n_nodes, hi, lo);
+                else if (sizeof(Id) == 8 && c_order) narrow_pairs_i64(dst + 2 * b, reinterpret_cast<const int64_t *>(src) + 2 * b, e - b, hi, lo);
+                else narrow_pairs_strided(dst + 2 * b, src + b * stride0, e - b, stride0, stride1, hi, lo);
+                fold_extremes(wide, wide_mutex, hi, lo);
+            });
+        };
+        auto launch = [&](PipeSlot &s, int64_t off, int64_t m) {
+            return launch_chunk(r, s, off, m, wire48 ? 6 : 8, out,
+                                [wire48, r](const void *in) { return SrcContig32{static_cast<const int *>(in), wire48 ? 1 : 0, stream_hint_host(r) ? 1 : 0}; });
+        };
+        const int rc = run_pipe(r, seq, pack, launch, out, fault);
+        if (rc != ST_OK) return rc;
+        // a clamped id always trips the device check as well; its exact value replaces the clamp
+        // (24-bit wire format: every id out of range was seen, and its exact value kept, by the packing step)
+        if (wire48) fault = wide;
+        else if (fault.max_bad != kFaultInit.max_bad || fault.min_bad != kFaultInit.min_bad) merge_fault(fault, wide);
+        return ST_OK;
+    };
+    return staged_host_run(t, n, 0, [](HostPipe &) { return ST_OK; }, chunks, bad_id);
 }

@@ -129,3 +129,83 @@ static int quartet_positions_device(int device, int mode, uint64_t seed, int64_t
     if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("quartet positions: ") + hipGetErrorString(e));
     return ST_OK;
 }
+
+// st_quartets_host: one tree's topologies of n > 0 explicit quartets from and to host arrays, through the slots of the
+// tree's own pipe (host_pipe.h).  Its drain copies topologies where run_pipe's unpacks distances and ids, and a chunk is
+// packed, uploaded and launched in one step, so the loop is its own; the way out on an error is run_pipe's (pipe_bail).
+static int quartets_host_run(st_tree *t, const int64_t *quartets, int64_t n, int64_t stride0, int64_t stride1, int64_t *out_topologies,
+                             int64_t *bad_id)
+{
+    ST_DEVICE(t->device);
+    std::lock_guard<std::mutex> lock(t->dp->m);
+    HostPipe &pipe = t->dp->pipe;
+    // (n,4) int64 in and out are each the size of two pair rows.  Every slot of the pipe carries
+    // one chunk: its pinned buffer holds the chunk's quartets (first half) and, later, its
+    // topologies (second half, written by the kernel); while chunk c is on the GPU the host
+    // unpacks chunk c-2 and packs chunk c+1.
+    const int64_t chunk = std::min<int64_t>(n, kHostChunk / 8);
+    {
+        hipError_t e = pipe.ensure(std::max<int64_t>(4 * chunk, 1024));
+        if (e == hipSuccess) e = pipe.ensure_device_in();
+        if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("host staging allocation: ") + hipGetErrorString(e));
+    }
+    if (begin_host_faults(t, pipe.slot[0].stream) != ST_OK) return ST_ERR_HIP;
+    const bool canopy = t->strategy == ST_STRATEGY_CANOPY && 6 * chunk >= canopy_min_pairs(t);
+    if (canopy && t->q_tmp_cap < kPipeSlots * chunk) {      // six MRCA ids per quartet, per slot
+        t->q_tmp_cap = 0;
+        ST_HIP(t->q_tmp.alloc((size_t)kPipeSlots * (size_t)chunk * 6));
+        t->q_tmp_cap = kPipeSlots * chunk;
+    }
+    auto out_of = [&](PipeSlot &s) { return reinterpret_cast<int64_t *>(static_cast<char *>(s.h_in) + (size_t)chunk * 32); };
+    auto drain = [&](PipeSlot &s) -> hipError_t {
+        if (!s.busy) return hipSuccess;
+        s.busy = false;
+        const hipError_t e = hipEventSynchronize(s.done);
+        if (e != hipSuccess) return e;
+        pipe.pool.copy(out_topologies + s.off * 4, out_of(s), s.m * 32);     // topologies were written straight into pinned memory
+        return hipSuccess;
+    };
+    int64_t k = 0;
+    for (int64_t off = 0; off < n; off += chunk, k++) {
+        const int64_t m = std::min(chunk, n - off);
+        const int slot_index = (int)(k % kPipeSlots);
+        PipeSlot &s = pipe.slot[slot_index];
+        hipError_t e = drain(s);
+        if (e != hipSuccess) return pipe_bail(pipe, ST_ERR_HIP, std::string("quartet pipeline: ") + hipGetErrorString(e));
+        int64_t *h = static_cast<int64_t *>(s.h_in);
+        const int64_t *src = quartets + off * stride0;
+        pipe.pool.parallel_for(m, [=](int64_t b, int64_t e2) {
+            for (int64_t q = b; q < e2; q++)
+                for (int c = 0; c < 4; c++) h[4 * q + c] = src[q * stride0 + c * stride1];
+        });
+        e = hipMemcpyAsync(s.d_in, s.h_in, (size_t)m * 32, hipMemcpyHostToDevice, s.stream);
+        if (e != hipSuccess) return pipe_bail(pipe, ST_ERR_HIP, std::string("quartet pipeline: ") + hipGetErrorString(e));
+        if (canopy && 6 * m >= canopy_min_pairs(t)) {
+            // six MRCA ids per quartet out of the canopy / rank-table kernels, then the pick
+            int32_t *tmp = t->q_tmp + (size_t)slot_index * (size_t)chunk * 6;
+            const int rc = enqueue_src(t, SrcQuartet{static_cast<const long long *>(s.d_in)}, 6 * m,
+                                       DistSink{nullptr, nullptr}, MrcaSink{tmp, nullptr}, t->d_fault_host, s.stream);
+            if (rc != ST_OK) return pipe_bail(pipe, rc, g_last_error);
+            e = launch_quartet_pick(t, static_cast<const long long *>(s.d_in), static_cast<const int *>(tmp), m,
+                                    reinterpret_cast<long long *>(out_of(s)), s.stream);
+        } else {
+            e = launch_quartets_walk(t, static_cast<const long long *>(s.d_in), m, reinterpret_cast<long long *>(out_of(s)),
+                                     t->d_fault_host, s.stream);
+        }
+        if (e == hipSuccess) e = hipEventRecord(s.done, s.stream);
+        if (e != hipSuccess) return pipe_bail(pipe, ST_ERR_HIP, std::string("quartet pipeline: ") + hipGetErrorString(e));
+        s.busy = true;
+        s.off = off;
+        s.m = m;
+        e = drain(pipe.slot[(k + 1) % kPipeSlots]);      // the oldest chunk, while the newer ones are in flight
+        if (e != hipSuccess) return pipe_bail(pipe, ST_ERR_HIP, std::string("quartet pipeline: ") + hipGetErrorString(e));
+    }
+    for (int j = 0; j < kPipeSlots; j++) {
+        const hipError_t e = drain(pipe.slot[(k + j) % kPipeSlots]);
+        if (e != hipSuccess) return pipe_bail(pipe, ST_ERR_HIP, std::string("quartet pipeline: ") + hipGetErrorString(e));
+    }
+    Fault f;
+    const int rc = end_host_faults(t, pipe.slot[0].stream, f);
+    if (rc != ST_OK) return rc;
+    return report_fault(t->n_nodes, f, bad_id);
+}

@@ -24,14 +24,18 @@
 //
 // Four translation units (compiled in parallel, build.py): launch_walk.hip (kernels_walk.h), launch_canopy.hip
 // (kernels_canopy.h), launch_canopy_sorted.hip (kernels_canopy_sorted.h) -- each a kernel family with its launch
-// functions, exported through launch_decl.h -- and this file: error plumbing, the C ABI and the host side in
-// between: st_tree.h / host_tree.h (handle, pipe registry), device_res.h (the owners of device and pinned memory, streams
+// functions, exported through launch_decl.h -- and this file: error plumbing and the C ABI, each export its argument
+// checks, the device scope, at most a plan call and one call into the host side, which lives in the headers included below:
+// st_tree.h / host_tree.h (handle, pipe registry), device_res.h (the owners of device and pinned memory, streams
 // and events that the handle and the host calls hold), launch_policy.h + host_launch.h (which family a request gets,
-// enqueueing, faults), host_path.h (host-buffer pipeline, mailbox, copy kernels), host_upload.h (tables -> device),
-// kernels_misc.h (k nearest, graph matrices), and the compare paths (st_compare_*: two trees' distances over the same
+// enqueueing, faults), host_upload.h (tables -> device),
+// host_options.h (the handle options of st_tree_set_option: one table, one setter),
+// host_path.h (host-buffer pipeline, mailbox, copy kernels; the one staged run behind st_distances_host[_i32], st_triangle_host, st_grid_host),
+// host_misc.h (the drivers of kernels_misc.h: 24-bit id unpack, k nearest, graph matrices),
+// and the compare paths (st_compare_*: two trees' distances over the same
 // pairs, reduced on the device): kernels_compare.h / kernels_clades.h / kernels_rows.h (moments and 2-D histogram, clade
 // pieces, row blocks), host_compare.h (TwoTreeSession, ReadbackRing, the chunk driver compare_run and its reducers, the pair
-// inputs, statistics and the one skeleton, compare_entry, of the triangle / pairs entry points) and,
+// inputs, statistics and the one skeleton, compare_entry, of the triangle / pairs entry points; clades_run and rows_run) and,
 // host-only C++ beside tree_prep.cpp, compare_plan.cpp (argument checks, clade plan and tables, rows layout, the fold);
 // plan_checks.h is what the plan units share in their checks (how one fails, a table of position sets, a range of the
 // triangle of set pairs and that triangle's index, which the kernels share).
@@ -41,7 +45,8 @@
 // tile sort, merge levels, tie scans), KendallState and its reducer at the end of host_compare.h and, host-only,
 // kendall_plan.cpp (the merge arithmetic both sides share, st_kendall_host).
 // Two trees' quartet topologies, counted on the device (st_compare_quartets_*_host, st_quartet_positions):
-// kernels_quartets.h (generator, classify-and-count), host_quartets.h (the chunk driver) and, host-only,
+// kernels_quartets.h (generator, classify-and-count), host_quartets.h (the chunk driver; quartets_host_run, one tree's
+// topologies through its own pipe: st_quartets_host) and, host-only,
 // quartet_plan.cpp (unranking, the draw, the class rule, argument checks).
 // The keyed permutation behind every null (st_hommola_permutation): keyed_perm.h (key, size classes, the host form; host
 // and device) and kernels_perm.h (the device sort).  Hommola's permutation test for many clades at once
@@ -65,10 +70,10 @@
 // host_clade_match.h (the chunk driver) and, host-only, clade_match_plan.cpp (the range builder, the checks, the size
 // windows, the restatement).
 //
-// Host side of the C ABI: tree upload to one or several GPUs (tree_prep.cpp builds the tables, under a table budget
+// What the host side does: tree upload to one or several GPUs (tree_prep.cpp builds the tables, under a table budget
 // if one is given), the host path (host_pipe.h, host_copy.h: packed ids in through the copy engine, kernels write
 // float32 + 24-bit ids straight into pinned host memory), the small-batch mailbox, fault read-back, the creation-time
-// choice of a deep tree's kernels (host_tune.h), k-nearest selection, graph matrices.
+// choice of a deep tree's kernels (host_tune.h).
 //
 // Built for gfx950 only: hipcc --offload-arch=gfx950 -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -198,8 +203,10 @@ static int device_index_arg(int device)
 using namespace st;
 
 #include "host_tree.h"
+#include "host_options.h"
 #include "host_launch.h"
 #include "host_path.h"
+#include "host_misc.h"
 #include "host_tune.h"
 #include "host_upload.h"
 #include "host_compare.h"
@@ -209,6 +216,15 @@ using namespace st;
 #include "host_unifrac.h"
 #include "host_unifrac_null.h"
 #include "host_clade_match.h"
+
+// the next link of st_link_sample_pairs (MuchTree.pyx:2946-2949)
+static int64_t link_draw(uint64_t &s, int64_t n_links)
+{
+    s ^= s >> 12;
+    s ^= s << 25;
+    s ^= s >> 27;
+    return (int64_t)((s * 2685821657736338717ull) % (uint64_t)n_links);
+}
 
 extern "C" {
 
@@ -246,14 +262,8 @@ try {
     if (!state || !linklist || n_links < 1 || count < 0 || (count > 0 && (!query_a || !query_b)))
         return fail(ST_ERR_ARG, "state / linklist / query arrays are NULL, n_links < 1 or count < 0");
     uint64_t s = *state;
-    auto draw = [&]() -> int64_t {      // MuchTree.pyx:2946-2949
-        s ^= s >> 12;
-        s ^= s << 25;
-        s ^= s >> 27;
-        return (int64_t)((s * 2685821657736338717ull) % (uint64_t)n_links);
-    };
     for (int64_t k = 0; k < count; k++) {
-        const int64_t l1 = draw(), l2 = draw();
+        const int64_t l1 = link_draw(s, n_links), l2 = link_draw(s, n_links);
         query_a[2 * k] = linklist[2 * l1 + 1];
         query_a[2 * k + 1] = linklist[2 * l2 + 1];
         query_b[2 * k] = linklist[2 * l1];
@@ -458,144 +468,6 @@ try {
     return ST_OK;
 } ST_CATCH_ALL
 
-static int set_option_one(st_tree *t, const char *name, int64_t value)
-{
-    if (std::strcmp(name, "tile_sort") == 0) {
-        if (value != 0 && value != 1) return fail(ST_ERR_ARG, "tile_sort must be 0 or 1");
-        t->tile_sort = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "ladder_scalar") == 0) {
-        if (value != 0 && value != 1) return fail(ST_ERR_ARG, "ladder_scalar must be 0 or 1");
-        t->ladder_scalar = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "reserve_cus") == 0) {
-        // the persistent kernels are sized to the CUs of the device; on a rank that also receives (the root of the
-        // multi-GPU gather) RCCL's kernels need somewhere to run beside a 1024-lane / 144 KiB workgroup per CU
-        if (value < 0 || value >= t->n_cu_device) return fail(ST_ERR_ARG, "reserve_cus must be in [0, CUs of the device)");
-        t->n_cu = t->n_cu_device - (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "ladder_dynamic") == 0) {
-        if (value != 0 && value != 1) return fail(ST_ERR_ARG, "ladder_dynamic must be 0 or 1");
-        t->ladder_dynamic = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "cherries") == 0) {
-        if (value != 0 && value != 1) return fail(ST_ERR_ARG, "cherries must be 0 or 1");
-        t->cherries = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "heap_lines") == 0) {
-        if (value < 0 || value > 2) return fail(ST_ERR_ARG, "heap_lines must be 0, 1 or 2");
-        t->heap_lines = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "heap_codes") == 0) {
-        if (value < 0 || value > 2) return fail(ST_ERR_ARG, "heap_codes must be 0, 1 or 2");
-        t->heap_codes = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "stream_hint") == 0) {
-        if (value < 0 || value > 2) return fail(ST_ERR_ARG, "stream_hint must be 0, 1 or 2");
-        t->stream_hint = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "batch_probe") == 0) {
-        if (value != 0 && value != 1) return fail(ST_ERR_ARG, "batch_probe must be 0 or 1");
-        t->batch_probe = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "measure") == 0) {      // (host_path.h::run_pipe; peers of a multi-device handle follow)
-        if (value < 0 || value > 7) return fail(ST_ERR_ARG, "measure must be a combination of 1 (trace), 2 (skip CPU passes), 4 (skip GPU side)");
-        t->measure = (int)value;
-        for (st_tree *p : t->peers) p->measure = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "ladder_min_pairs") == 0) {
-        if (value < 0) return fail(ST_ERR_ARG, "ladder_min_pairs must be >= 0");
-        t->ladder_min_pairs = value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "tree_rmq") == 0) {
-        if (value != 0 && value != 1) return fail(ST_ERR_ARG, "tree_rmq must be 0 or 1");
-        t->tree_rmq = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "mrca_ranks") == 0) {
-        if (value != 0 && value != 1) return fail(ST_ERR_ARG, "mrca_ranks must be 0 or 1");
-        t->mrca_ranks = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "rec_a4") == 0) {
-        if (value != 0 && value != 1) return fail(ST_ERR_ARG, "rec_a4 must be 0 or 1");
-        t->rec_a4 = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "walk_ladder") == 0) {
-        if (value != 0 && value != 1) return fail(ST_ERR_ARG, "walk_ladder must be 0 or 1");
-        t->walk_ladder = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "prefer_walk_sorted") == 0) {
-        if (value != 0 && value != 1) return fail(ST_ERR_ARG, "prefer_walk_sorted must be 0 or 1");
-        t->prefer_walk_sorted = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "wire48") == 0) {
-        if (value != 0 && value != 1) return fail(ST_ERR_ARG, "wire48 must be 0 or 1");
-        t->wire48 = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "wire24") == 0) {
-        if (value != 0 && value != 1) return fail(ST_ERR_ARG, "wire24 must be 0 or 1");
-        t->wire24 = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "sort_tile") == 0) {
-        if (value != 0 && value != 1 && value != 2 && value != 4) return fail(ST_ERR_ARG, "sort_tile must be 0, 1, 2 or 4");
-        t->sort_tile = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "walk_sort_min") == 0) {
-        if (value < 0) return fail(ST_ERR_ARG, "walk_sort_min must be >= 0");
-        t->walk_sort_min = value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "walk_crown") == 0) {
-        if (value != 0 && value != 1) return fail(ST_ERR_ARG, "walk_crown must be 0 or 1");
-        t->walk_crown = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "walk_sort") == 0) {
-        if (value != 0 && value != 1) return fail(ST_ERR_ARG, "walk_sort must be 0 or 1");
-        t->walk_sort = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "lineage_lens") == 0) {
-        if (value != 0 && value != 1) return fail(ST_ERR_ARG, "lineage_lens must be 0 or 1");
-        t->lineage_lens = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "lineage_sums") == 0) {
-        if (value != 0 && value != 1) return fail(ST_ERR_ARG, "lineage_sums must be 0 or 1");
-        t->lineage_sums = (int)value;
-        return ST_OK;
-    }
-    if (std::strcmp(name, "ladder_sums") == 0) {
-        if (value != 0 && value != 1) return fail(ST_ERR_ARG, "ladder_sums must be 0 or 1");
-        t->ladder_sums = (int)value;
-        t->ladder_sums_max_pairs = 0;      // (an explicit setting holds for every batch size)
-        return ST_OK;
-    }
-    if (std::strcmp(name, "small_batch_path") == 0) {
-        t->small_batch_path = value != 0;
-        return ST_OK;
-    }
-    return fail(ST_ERR_ARG, std::string("unknown option ") + name);
-}
-
 int st_tree_set_option(st_tree *t, const char *name, int64_t value)
 try {
     if (!t || !name) return fail(ST_ERR_ARG, "tree or name is NULL");
@@ -605,13 +477,21 @@ try {
     return rc;
 } ST_CATCH_ALL
 
+// what every entry over explicit pairs checks first, in this order (host and device forms)
+static int pair_batch_args(const st_tree *t, const void *pairs, int64_t n, const void *out_d, const void *out_m)
+{
+    if (!t) return fail(ST_ERR_ARG, "tree is NULL");
+    if (n < 0) return fail(ST_ERR_ARG, "n < 0");
+    if (n > 0 && !pairs) return fail(ST_ERR_ARG, "pairs is NULL");
+    if (!out_d && !out_m) return fail(ST_ERR_ARG, "both outputs are NULL");
+    return ST_OK;
+}
+
 int st_distances_device(st_tree *t, const int64_t *d_pairs, int64_t n, int64_t stride0,
                         int64_t stride1, double *d_out_dist, int32_t *d_out_mrca, void *stream)
 try {
-    if (!t) return fail(ST_ERR_ARG, "tree is NULL");
-    if (n < 0) return fail(ST_ERR_ARG, "n < 0");
-    if (n > 0 && !d_pairs) return fail(ST_ERR_ARG, "pairs is NULL");
-    if (!d_out_dist && !d_out_mrca) return fail(ST_ERR_ARG, "both outputs are NULL");
+    const int rc = pair_batch_args(t, d_pairs, n, d_out_dist, d_out_mrca);
+    if (rc != ST_OK) return rc;
     ST_DEVICE(t->device);
     return enqueue(t, d_pairs, n, stride0, stride1, DistSink{d_out_dist, nullptr}, MrcaSink{d_out_mrca, nullptr},
                    reinterpret_cast<hipStream_t>(stream));
@@ -620,10 +500,8 @@ try {
 int st_distances_device_f32(st_tree *t, const int64_t *d_pairs, int64_t n, int64_t stride0,
                             int64_t stride1, float *d_out_dist, int32_t *d_out_mrca, void *stream)
 try {
-    if (!t) return fail(ST_ERR_ARG, "tree is NULL");
-    if (n < 0) return fail(ST_ERR_ARG, "n < 0");
-    if (n > 0 && !d_pairs) return fail(ST_ERR_ARG, "pairs is NULL");
-    if (!d_out_dist && !d_out_mrca) return fail(ST_ERR_ARG, "both outputs are NULL");
+    const int rc = pair_batch_args(t, d_pairs, n, d_out_dist, d_out_mrca);
+    if (rc != ST_OK) return rc;
     ST_DEVICE(t->device);
     return enqueue(t, d_pairs, n, stride0, stride1, DistSink{nullptr, d_out_dist}, MrcaSink{d_out_mrca, nullptr},
                    reinterpret_cast<hipStream_t>(stream));
@@ -632,10 +510,8 @@ try {
 int st_distances_device_wire(st_tree *t, const int64_t *d_pairs, int64_t n, int64_t stride0, int64_t stride1,
                              float *d_out_dist, uint8_t *d_out_mrca24, void *stream)
 try {
-    if (!t) return fail(ST_ERR_ARG, "tree is NULL");
-    if (n < 0) return fail(ST_ERR_ARG, "n < 0");
-    if (n > 0 && !d_pairs) return fail(ST_ERR_ARG, "pairs is NULL");
-    if (!d_out_dist && !d_out_mrca24) return fail(ST_ERR_ARG, "both outputs are NULL");
+    const int rc = pair_batch_args(t, d_pairs, n, d_out_dist, d_out_mrca24);
+    if (rc != ST_OK) return rc;
     if (t->n_nodes > 0xFFFFFF) return fail(ST_ERR_ARG, "24-bit MRCA ids need a tree of fewer than 2^24 nodes");
     if (reinterpret_cast<uintptr_t>(d_out_mrca24) & 3) return fail(ST_ERR_ARG, "d_out_mrca24 must be 4-byte aligned");
     ST_DEVICE(t->device);
@@ -648,11 +524,7 @@ try {
     if (n < 0) return fail(ST_ERR_ARG, "n < 0");
     if (n == 0) return ST_OK;
     if (!d_packed || !d_out_mrca) return fail(ST_ERR_ARG, "buffer is NULL");
-    ST_DEVICE(device);
-    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 4096));
-    hipLaunchKernelGGL(k_unpack24, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), d_packed, (long long)n, d_out_mrca);
-    ST_HIP(hipGetLastError());
-    return ST_OK;
+    return unpack_mrca24_run(device, d_packed, n, d_out_mrca, stream);
 } ST_CATCH_ALL
 
 int st_fault_check(st_tree *t, void *stream, int64_t *bad_id)
@@ -677,120 +549,20 @@ try {
     return ST_OK;
 } ST_CATCH_ALL
 
-}  // extern "C"
-
-// Host-buffer entry point for int64 ids (the reference's dtype) and int32 ids.
-template <typename Id>
-static int distances_host_impl(st_tree *t, const Id *pairs, int64_t n, int64_t stride0, int64_t stride1,
-                               double *out_dist, int32_t *out_mrca, int64_t *bad_id)
-{
-    if (!t) return fail(ST_ERR_ARG, "tree is NULL");
-    if (n < 0) return fail(ST_ERR_ARG, "n < 0");
-    if (n > 0 && !pairs) return fail(ST_ERR_ARG, "pairs is NULL");
-    if (!out_dist && !out_mrca) return fail(ST_ERR_ARG, "both outputs are NULL");
-    if (n == 0) return ST_OK;
-    // (deep canopies: beyond the walk/canopy switch the tile-sorted kernel beats the mailbox's walk)
-    // (deep canopies without lineage sums: the walk is slow there, the tile-sorted kernel takes over at 4096 pairs)
-    if (n <= (t->tile_sort && !(t->d_lineage && t->lineage_sums) ? kCanopyMinPairs - 1 : kMailboxPairs) && t->small_batch_path) {
-        ST_DEVICE(t->device);
-        return small_batch(t, pairs, n, stride0, stride1, out_dist, out_mrca, bad_id);
-    }
-    HostOut out = make_host_out(out_dist, out_mrca);
-    out.wire24 = wire24_of(t, out);
-    // fresh result arrays: ask for huge pages before the first touch (a no-op on resident memory)
-    if (out_dist && !looks_resident(out_dist, n * 8)) advise_huge(out_dist, n * 8);
-    if (out_mrca && !looks_resident(out_mrca, n * 4)) advise_huge(out_mrca, n * 4);
-
-    // Ids cross PCIe as int32 (half the H2D bytes).  Values that do not fit are clamped to
-    // INT32_MAX / INT32_MIN -- still out of range for the kernel -- and their exact extremes
-    // are kept here so that the reported id is the one the reference would report.
-    auto work = [&](st_tree *r, const ChunkSeq &seq, Fault &fault) -> int {
-        CopyPool &pool = r->dp->pipe.pool;
-        hipStream_t s0 = nullptr;
-        std::mutex wide_mutex;
-        Fault wide = kFaultInit;
-        // trees with fewer than 2^24 nodes: 24 bits per id on the wire (6 instead of 8 bytes per pair over the link;
-        // the range check is then the host's, host_copy.h::pack_pairs48)
-        const bool wire48 = r->wire48 && r->n_nodes <= 0xFFFFFF;
-        auto pack = [&](PipeSlot &s, int64_t off, int64_t m) {
-            const Id *src = pairs + off * stride0;
-            int32_t *dst = static_cast<int32_t *>(s.h_in);
-            const bool c_order = stride0 == 2 && stride1 == 1;
-            if (wire48) {
-                const long long n_nodes = r->n_nodes;
-                pool.parallel_for(m, [&, src, dst, n_nodes](int64_t b, int64_t e) {
-                    long long hi = kFaultInit.max_bad, lo = kFaultInit.min_bad;
-                    pack_pairs48(reinterpret_cast<uint8_t *>(dst), b, src + b * stride0, e - b, stride0, stride1, n_nodes, hi, lo);
-                    if (hi != kFaultInit.max_bad || lo != kFaultInit.min_bad) {
-                        std::lock_guard<std::mutex> g(wide_mutex);
-                        wide.max_bad = std::max(wide.max_bad, hi);
-                        wide.min_bad = std::min(wide.min_bad, lo);
-                    }
-                });
-                return;
-            }
-            if (sizeof(Id) == 4 && c_order) {   // int32 C-order: already the wire format
-                pool.parallel_for(m, [=](int64_t b, int64_t e) { copy_stream(dst + 2 * b, src + 2 * b, (e - b) * 8); });
-                return;
-            }
-            pool.parallel_for(m, [&, src, dst](int64_t b, int64_t e) {
-                long long hi = kFaultInit.max_bad, lo = kFaultInit.min_bad;
-                if (sizeof(Id) == 8 && c_order) {
-                    narrow_pairs_i64(dst + 2 * b, reinterpret_cast<const int64_t *>(src) + 2 * b, e - b, hi, lo);
-                } else {
-                    for (int64_t k = b; k < e; k++) {
-                        for (int c = 0; c < 2; c++) {
-                            const long long v = src[k * stride0 + c * stride1];
-                            int32_t w = (int32_t)v;
-                            if (v > INT32_MAX) { w = INT32_MAX; hi = std::max(hi, v); }
-                            else if (v < INT32_MIN) { w = INT32_MIN; lo = std::min(lo, v); }
-                            dst[2 * k + c] = w;
-                        }
-                    }
-                }
-                if (hi != kFaultInit.max_bad || lo != kFaultInit.min_bad) {
-                    std::lock_guard<std::mutex> g(wide_mutex);
-                    wide.max_bad = std::max(wide.max_bad, hi);
-                    wide.min_bad = std::min(wide.min_bad, lo);
-                }
-            });
-        };
-        auto launch = [&](PipeSlot &s, int64_t off, int64_t m) {
-            return launch_chunk(r, s, off, m, wire48 ? 6 : 8, out,
-                                [wire48, r](const void *in) { return SrcContig32{static_cast<const int *>(in), wire48 ? 1 : 0, stream_hint_host(r) ? 1 : 0}; });
-        };
-        {   // (the pipe may not exist yet: ensure() inside run_pipe creates the streams)
-            const hipError_t e = r->dp->pipe.ensure(std::max<int64_t>(seq.chunk, 1024));
-            if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("host staging allocation: ") + hipGetErrorString(e));
-            s0 = r->dp->pipe.slot[0].stream;
-        }
-        int rc = begin_host_faults(r, s0);
-        if (rc == ST_OK) rc = run_pipe(r, seq, pack, launch, out, fault);
-        if (rc != ST_OK) return rc;
-        // a clamped id always trips the device check as well; its exact value replaces the clamp
-        // (24-bit wire format: every id out of range was seen, and its exact value kept, by the packing step)
-        if (wire48) fault = wide;
-        else if (fault.max_bad != kFaultInit.max_bad || fault.min_bad != kFaultInit.min_bad) merge_fault(fault, wide);
-        return ST_OK;
-    };
-    Fault fault;
-    const int rc = for_each_replica(t, n, fault, work);
-    if (rc != ST_OK) return rc;
-    return report_fault(t->n_nodes, fault, bad_id);
-}
-
-extern "C" {
-
 int st_distances_host(st_tree *t, const int64_t *pairs, int64_t n, int64_t stride0, int64_t stride1,
                       double *out_dist, int32_t *out_mrca, int64_t *bad_id)
 try {
-    return distances_host_impl(t, pairs, n, stride0, stride1, out_dist, out_mrca, bad_id);
+    const int rc = pair_batch_args(t, pairs, n, out_dist, out_mrca);
+    if (rc != ST_OK || n == 0) return rc;
+    return distances_host_run(t, pairs, n, stride0, stride1, out_dist, out_mrca, bad_id);
 } ST_CATCH_ALL
 
 int st_distances_host_i32(st_tree *t, const int32_t *pairs, int64_t n, int64_t stride0, int64_t stride1,
                           double *out_dist, int32_t *out_mrca, int64_t *bad_id)
 try {
-    return distances_host_impl(t, pairs, n, stride0, stride1, out_dist, out_mrca, bad_id);
+    const int rc = pair_batch_args(t, pairs, n, out_dist, out_mrca);
+    if (rc != ST_OK || n == 0) return rc;
+    return distances_host_run(t, pairs, n, stride0, stride1, out_dist, out_mrca, bad_id);
 } ST_CATCH_ALL
 
 static int triangle_args(st_tree *t, const int64_t *ids, int64_t m, int64_t k_begin, int64_t k_count,
@@ -819,40 +591,9 @@ try {
 int st_triangle_host(st_tree *t, const int64_t *ids, int64_t m, int64_t id_stride, int64_t k_begin,
                      int64_t k_count, double *out_dist, int32_t *out_mrca, int64_t *bad_id)
 try {
-    int rc = triangle_args(t, ids, m, k_begin, k_count, out_dist, out_mrca);
-    if (rc != ST_OK) return rc;
-    if (k_count == 0) return ST_OK;
-    HostOut out = make_host_out(out_dist, out_mrca);
-    out.wire24 = wire24_of(t, out);
-    if (out_dist && !looks_resident(out_dist, k_count * 8)) advise_huge(out_dist, k_count * 8);
-    if (out_mrca && !looks_resident(out_mrca, k_count * 4)) advise_huge(out_mrca, k_count * 4);
-    // the id list goes up once per device (packed); results stream back through the pipe
-    std::vector<int64_t> packed;
-    const int64_t *src_ids = ids;
-    if (id_stride != 1) {
-        packed.resize((size_t)m);
-        for (int64_t i = 0; i < m; i++) packed[(size_t)i] = ids[i * id_stride];
-        src_ids = packed.data();
-    }
-    auto work = [&](st_tree *r, const ChunkSeq &seq, Fault &fault) -> int {
-        HostPipe &P = r->dp->pipe;
-        hipError_t e = P.ensure(std::max<int64_t>(seq.chunk, 1024));
-        if (e == hipSuccess) e = P.ensure_ids(m);
-        if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("host staging allocation: ") + hipGetErrorString(e));
-        hipStream_t s0 = P.slot[0].stream;
-        if (begin_host_faults(r, s0) != ST_OK) return ST_ERR_HIP;
-        ST_HIP(hipMemcpy(P.d_ids, src_ids, (size_t)m * 8, hipMemcpyHostToDevice));
-        auto pack = [](PipeSlot &, int64_t, int64_t) {};
-        auto launch = [&](PipeSlot &s, int64_t off, int64_t c) {
-            const SrcTriangle src{static_cast<const long long *>(P.d_ids), 1, (long long)(k_begin + off)};
-            return launch_chunk(r, s, off, c, 0, out, [&](const void *) { return src; });
-        };
-        return run_pipe(r, seq, pack, launch, out, fault);
-    };
-    Fault fault;
-    rc = for_each_replica(t, k_count, fault, work);
-    if (rc != ST_OK) return rc;
-    return report_fault(t->n_nodes, fault, bad_id);
+    const int rc = triangle_args(t, ids, m, k_begin, k_count, out_dist, out_mrca);
+    if (rc != ST_OK || k_count == 0) return rc;
+    return triangle_host_run(t, ids, m, id_stride, k_begin, k_count, out_dist, out_mrca, bad_id);
 } ST_CATCH_ALL
 
 static int grid_args(st_tree *t, const int64_t *rows, int64_t n_rows, const int64_t *cols, int64_t n_cols,
@@ -871,35 +612,11 @@ int st_grid_host(st_tree *t, const int64_t *row_ids, int64_t n_rows, const int64
                  int symmetric, int64_t e_begin, int64_t e_count, double *out_dist, int32_t *out_mrca,
                  int64_t *bad_id)
 try {
-    int rc = grid_args(t, row_ids, n_rows, col_ids, n_cols, e_begin, e_count, out_dist, out_mrca);
+    const int rc = grid_args(t, row_ids, n_rows, col_ids, n_cols, e_begin, e_count, out_dist, out_mrca);
     if (rc != ST_OK) return rc;
     if (symmetric && (n_rows != n_cols)) return fail(ST_ERR_ARG, "symmetric grid needs n_rows == n_cols");
     if (e_count == 0) return ST_OK;
-    HostOut out = make_host_out(out_dist, out_mrca);
-    out.wire24 = wire24_of(t, out);
-    if (out_dist && !looks_resident(out_dist, e_count * 8)) advise_huge(out_dist, e_count * 8);
-    if (out_mrca && !looks_resident(out_mrca, e_count * 4)) advise_huge(out_mrca, e_count * 4);
-    auto work = [&](st_tree *r, const ChunkSeq &seq, Fault &fault) -> int {
-        HostPipe &P = r->dp->pipe;
-        hipError_t e = P.ensure(std::max<int64_t>(seq.chunk, 1024));
-        if (e == hipSuccess) e = P.ensure_ids(n_rows + n_cols);
-        if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("host staging allocation: ") + hipGetErrorString(e));
-        hipStream_t s0 = P.slot[0].stream;
-        if (begin_host_faults(r, s0) != ST_OK) return ST_ERR_HIP;
-        long long *d_rows = static_cast<long long *>(P.d_ids), *d_cols = d_rows + n_rows;
-        ST_HIP(hipMemcpy(d_rows, row_ids, (size_t)n_rows * 8, hipMemcpyHostToDevice));
-        ST_HIP(hipMemcpy(d_cols, col_ids, (size_t)n_cols * 8, hipMemcpyHostToDevice));
-        auto pack = [](PipeSlot &, int64_t, int64_t) {};
-        auto launch = [&](PipeSlot &s, int64_t off, int64_t c) {
-            const SrcGrid src{d_rows, d_cols, (long long)n_cols, (long long)(e_begin + off), symmetric};
-            return launch_chunk(r, s, off, c, 0, out, [&](const void *) { return src; });
-        };
-        return run_pipe(r, seq, pack, launch, out, fault);
-    };
-    Fault fault;
-    rc = for_each_replica(t, e_count, fault, work);
-    if (rc != ST_OK) return rc;
-    return report_fault(t->n_nodes, fault, bad_id);
+    return grid_host_run(t, row_ids, n_rows, col_ids, n_cols, symmetric, e_begin, e_count, out_dist, out_mrca, bad_id);
 } ST_CATCH_ALL
 
 int st_knn_host(st_tree *t, const int64_t *queries, int64_t n_queries, const int64_t *cands, int64_t n_cands,
@@ -916,51 +633,13 @@ try {
         for (int64_t i = 0; i < n_queries * k; i++) { out_index[i] = -1; out_dist[i] = std::numeric_limits<double>::quiet_NaN(); }
         return ST_OK;
     }
-    ST_DEVICE(t->device);
-    std::lock_guard<std::mutex> lock(t->dp->m);
-    // rows per launch: the distance block (float32, device only) stays under 256 MiB
-    const int64_t rows_per_block = std::max<int64_t>(1, std::min<int64_t>(n_queries, ((int64_t)1 << 26) / n_cands));
-    DevBuf<long long> d_q, d_c, d_oi;
-    DevBuf<float> d_tmp;
-    DevBuf<double> d_od;
-    DrainedStream stream;      // (every way out drains it before the buffers go)
-    hipError_t e = stream.create();
-    if (e == hipSuccess) e = d_q.alloc((size_t)n_queries);
-    if (e == hipSuccess) e = d_c.alloc((size_t)n_cands);
-    if (e == hipSuccess) e = d_tmp.alloc((size_t)rows_per_block * (size_t)n_cands);
-    if (e == hipSuccess) e = d_oi.alloc((size_t)n_queries * k);
-    if (e == hipSuccess) e = d_od.alloc((size_t)n_queries * k);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_q, queries, (size_t)n_queries * 8, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_c, cands, (size_t)n_cands * 8, hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("knn setup: ") + hipGetErrorString(e));
-    if (begin_host_faults(t, stream) != ST_OK) return ST_ERR_HIP;
-    for (int64_t r0 = 0; r0 < n_queries; r0 += rows_per_block) {
-        const int64_t rows = std::min(rows_per_block, n_queries - r0);
-        const SrcGrid src{d_q + r0, d_c, (long long)n_cands, 0, 0};
-        const int rc = enqueue_src(t, src, rows * n_cands, DistSink{nullptr, d_tmp}, MrcaSink{nullptr, nullptr}, t->d_fault_host, stream);
-        if (rc != ST_OK) return rc;
-        hipLaunchKernelGGL(k_knn_select, dim3((unsigned)rows), dim3(256), 0, stream, d_tmp, (long long)n_cands,
-                           d_q + r0, d_c, skip_self, k, d_oi + r0 * k, d_od + r0 * k);
-        e = hipGetLastError();
-        if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("knn launch: ") + hipGetErrorString(e));
-    }
-    e = hipMemcpyAsync(out_index, d_oi, (size_t)n_queries * k * 8, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_dist, d_od, (size_t)n_queries * k * 8, hipMemcpyDeviceToHost, stream);
-    if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("knn D2H: ") + hipGetErrorString(e));
-    Fault f = kFaultInit;
-    const int rc = end_host_faults(t, stream, f);
-    if (rc != ST_OK) return rc;
-    return report_fault(t->n_nodes, f, bad_id);
+    return knn_host_run(t, queries, n_queries, cands, n_cands, k, skip_self, out_index, out_dist, bad_id);
 } ST_CATCH_ALL
-
-}  // extern "C"
 
 // ---- compare paths (st_compare_*_host, st_clade_plan) ---------------------------------------------------------------
 // st_compare_{triangle,pairs}[_ranks|_kendall]_host are compare_entry (host_compare.h) over a pair input -- TriangleInput,
 // PairsInput -- and a statistic -- MomentsStat, RanksStat, KendallStat: a new input or statistic is a struct there and one
-// line here per entry point.  st_compare_clades_host and st_compare_rows_host stage their own pairs and call compare_run
-// themselves; st_compare_quartets[_leaves]_host (further down) spell the same ladder out around quartet_run.
-extern "C" {
+// line here per entry point.
 
 int st_compare_triangle_host(st_tree *tx, st_tree *ty, const int64_t *ids_x, const int64_t *ids_y, int64_t m, int64_t k_begin,
                              int64_t k_count, const double *edges_x, int32_t bins_x, const double *edges_y, int32_t bins_y,
@@ -1072,36 +751,7 @@ try {
     if (!clade_tables(P, T)) return fail(ST_ERR_ARG, "more than 2^31 - 1 pieces");
     CladeReduce red{P, T, out, max_links};
     if (P.total == 0) return red.done();      // (nothing to launch)
-    // device: permuted ids of X and Y and ranks (int32) | segments | tiles
-    const size_t L = (size_t)n_links;
-    const size_t o_y = align256(L * 4), o_rank = o_y + align256(L * 4), o_seg = o_rank + align256(L * 4);
-    const size_t o_tile = o_seg + align256(T.segs.size() * sizeof(CladeSeg)), extra = o_tile + align256(T.tiles.size() * sizeof(CladeTile));
-    std::vector<int32_t> sx(L), sy(L), rk(L);
-    for (size_t p = 0; p < L; p++) {
-        const int64_t j = P.perm[p];
-        sx[p] = (int32_t)ids_x[j];
-        sy[p] = (int32_t)ids_y[j];
-        rk[p] = (int32_t)j;
-    }
-    auto setup = [&](char *d, hipStream_t s) {
-        red.d_seg = reinterpret_cast<const CladeSeg *>(d + o_seg);
-        red.d_tile = reinterpret_cast<const CladeTile *>(d + o_tile);
-        hipError_t e = hipMemcpyAsync(d, sx.data(), L * 4, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d + o_y, sy.data(), L * 4, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d + o_rank, rk.data(), L * 4, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d + o_seg, T.segs.data(), T.segs.size() * sizeof(CladeSeg), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d + o_tile, T.tiles.data(), T.tiles.size() * sizeof(CladeTile), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);      // (the host vectors are pageable and go out of scope with this call)
-        return e;
-    };
-    auto prep = [](char *, hipStream_t, int64_t, int64_t) { return hipSuccess; };
-    auto src = [&](size_t o_ids) {
-        return [&, o_ids](char *d, int64_t off) {
-            return SrcSegments{reinterpret_cast<const int *>(d + o_ids), reinterpret_cast<const int *>(d + o_rank),
-                               reinterpret_cast<const CladeSeg *>(d + o_seg), reinterpret_cast<const CladeTile *>(d + o_tile), (long long)off};
-        };
-    };
-    return compare_run(tx, ty, P.total, chunk_pairs > 0 ? chunk_pairs : kCladeChunkPairs, extra, setup, prep, src(0), src(o_y), red, bad_id);
+    return clades_run(tx, ty, ids_x, ids_y, n_links, chunk_pairs > 0 ? chunk_pairs : kCladeChunkPairs, red, bad_id);
 } ST_CATCH_ALL
 
 int st_compare_rows_host(st_tree *tx, st_tree *ty, const int64_t *ids_x, const int64_t *ids_y, int64_t n_rows, int64_t m,
@@ -1122,30 +772,7 @@ try {
     const int64_t n_ids = n_rows * m;
     rc = compare_check_ids(tx, ty, ids_x, ids_y, n_ids, bad_id);
     if (rc != ST_OK) return rc;
-    const std::vector<int32_t> hx(ids_x, ids_x + n_ids), hy(ids_y, ids_y + n_ids);      // (checked: below n_nodes)
-    // device: the int32 ids of up to max_rows rows from row `up_lo` on, X then Y; uploaded again when a chunk needs others
-    const size_t row_bytes = (size_t)m * 4, half = align256((size_t)L.max_rows * row_bytes);
-    int64_t up_lo = -1, up_hi = -1;
-    auto setup = [](char *, hipStream_t) { return hipSuccess; };
-    auto prep = [&](char *d, hipStream_t s, int64_t off, int64_t c) {
-        const int64_t r0 = off / L.S, r1 = (off + c - 1) / L.S + 1;
-        if (r1 - r0 > L.max_rows) return hipErrorInvalidValue;
-        if (r0 >= up_lo && r1 <= up_hi) return hipSuccess;
-        up_lo = r0;
-        up_hi = std::min(n_rows, r0 + L.max_rows);
-        const size_t b = (size_t)(up_hi - up_lo) * row_bytes;
-        hipError_t e = hipMemcpyAsync(d, hx.data() + up_lo * m, b, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d + half, hy.data() + up_lo * m, b, hipMemcpyHostToDevice, s);
-        return e;
-    };
-    auto src = [&](size_t o) {
-        return [&, o](char *d, int64_t off) {
-            return SrcRows{reinterpret_cast<const int *>(d + o), (long long)m, (long long)L.P, (long long)L.S, 1.0 / (double)L.S,
-                           (long long)off, (long long)up_lo};
-        };
-    };
-    RowsReduce red(L, out);
-    return compare_run(tx, ty, n_rows * L.S, L.chunk, 2 * half, setup, prep, src(0), src(half), red, bad_id);
+    return rows_run(tx, ty, ids_x, ids_y, n_rows, m, L, out, bad_id);
 } ST_CATCH_ALL
 
 int st_quartets_host(st_tree *t, const int64_t *quartets, int64_t n, int64_t stride0, int64_t stride1,
@@ -1155,85 +782,7 @@ try {
     if (n < 0) return fail(ST_ERR_ARG, "n < 0");
     if (n > 0 && (!quartets || !out_topologies)) return fail(ST_ERR_ARG, "quartets or output is NULL");
     if (n == 0) return ST_OK;
-    ST_DEVICE(t->device);
-    std::lock_guard<std::mutex> lock(t->dp->m);
-    HostPipe &pipe = t->dp->pipe;
-    // (n,4) int64 in and out are each the size of two pair rows.  Every slot of the pipe carries
-    // one chunk: its pinned buffer holds the chunk's quartets (first half) and, later, its
-    // topologies (second half, written by the kernel); while chunk c is on the GPU the host
-    // unpacks chunk c-2 and packs chunk c+1.
-    const int64_t chunk = std::min<int64_t>(n, kHostChunk / 8);
-    {
-        hipError_t e = pipe.ensure(std::max<int64_t>(4 * chunk, 1024));
-        if (e == hipSuccess) e = pipe.ensure_device_in();
-        if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("host staging allocation: ") + hipGetErrorString(e));
-    }
-    if (begin_host_faults(t, pipe.slot[0].stream) != ST_OK) return ST_ERR_HIP;
-    const bool canopy = t->strategy == ST_STRATEGY_CANOPY && 6 * chunk >= canopy_min_pairs(t);
-    if (canopy && t->q_tmp_cap < kPipeSlots * chunk) {      // six MRCA ids per quartet, per slot
-        t->q_tmp_cap = 0;
-        ST_HIP(t->q_tmp.alloc((size_t)kPipeSlots * (size_t)chunk * 6));
-        t->q_tmp_cap = kPipeSlots * chunk;
-    }
-    auto out_of = [&](PipeSlot &s) { return reinterpret_cast<int64_t *>(static_cast<char *>(s.h_in) + (size_t)chunk * 32); };
-    auto drain = [&](PipeSlot &s) -> hipError_t {
-        if (!s.busy) return hipSuccess;
-        s.busy = false;
-        const hipError_t e = hipEventSynchronize(s.done);
-        if (e != hipSuccess) return e;
-        pipe.pool.copy(out_topologies + s.off * 4, out_of(s), s.m * 32);     // topologies were written straight into pinned memory
-        return hipSuccess;
-    };
-    auto bail = [&](int code, const std::string &msg) {
-        for (auto &s : pipe.slot) {
-            if (s.stream) (void)hipStreamSynchronize(s.stream);
-            s.busy = false;
-        }
-        return fail(code, msg);
-    };
-    int64_t k = 0;
-    for (int64_t off = 0; off < n; off += chunk, k++) {
-        const int64_t m = std::min(chunk, n - off);
-        const int slot_index = (int)(k % kPipeSlots);
-        PipeSlot &s = pipe.slot[slot_index];
-        hipError_t e = drain(s);
-        if (e != hipSuccess) return bail(ST_ERR_HIP, std::string("quartet pipeline: ") + hipGetErrorString(e));
-        int64_t *h = static_cast<int64_t *>(s.h_in);
-        const int64_t *src = quartets + off * stride0;
-        pipe.pool.parallel_for(m, [=](int64_t b, int64_t e2) {
-            for (int64_t q = b; q < e2; q++)
-                for (int c = 0; c < 4; c++) h[4 * q + c] = src[q * stride0 + c * stride1];
-        });
-        e = hipMemcpyAsync(s.d_in, s.h_in, (size_t)m * 32, hipMemcpyHostToDevice, s.stream);
-        if (e != hipSuccess) return bail(ST_ERR_HIP, std::string("quartet pipeline: ") + hipGetErrorString(e));
-        if (canopy && 6 * m >= canopy_min_pairs(t)) {
-            // six MRCA ids per quartet out of the canopy / rank-table kernels, then the pick
-            int32_t *tmp = t->q_tmp + (size_t)slot_index * (size_t)chunk * 6;
-            const int rc = enqueue_src(t, SrcQuartet{static_cast<const long long *>(s.d_in)}, 6 * m,
-                                       DistSink{nullptr, nullptr}, MrcaSink{tmp, nullptr}, t->d_fault_host, s.stream);
-            if (rc != ST_OK) return bail(rc, g_last_error);
-            e = launch_quartet_pick(t, static_cast<const long long *>(s.d_in), static_cast<const int *>(tmp), m,
-                                    reinterpret_cast<long long *>(out_of(s)), s.stream);
-        } else {
-            e = launch_quartets_walk(t, static_cast<const long long *>(s.d_in), m, reinterpret_cast<long long *>(out_of(s)),
-                                     t->d_fault_host, s.stream);
-        }
-        if (e == hipSuccess) e = hipEventRecord(s.done, s.stream);
-        if (e != hipSuccess) return bail(ST_ERR_HIP, std::string("quartet pipeline: ") + hipGetErrorString(e));
-        s.busy = true;
-        s.off = off;
-        s.m = m;
-        e = drain(pipe.slot[(k + 1) % kPipeSlots]);      // the oldest chunk, while the newer ones are in flight
-        if (e != hipSuccess) return bail(ST_ERR_HIP, std::string("quartet pipeline: ") + hipGetErrorString(e));
-    }
-    for (int j = 0; j < kPipeSlots; j++) {
-        const hipError_t e = drain(pipe.slot[(k + j) % kPipeSlots]);
-        if (e != hipSuccess) return bail(ST_ERR_HIP, std::string("quartet pipeline: ") + hipGetErrorString(e));
-    }
-    Fault f;
-    const int rc = end_host_faults(t, pipe.slot[0].stream, f);
-    if (rc != ST_OK) return rc;
-    return report_fault(t->n_nodes, f, bad_id);
+    return quartets_host_run(t, quartets, n, stride0, stride1, out_topologies, bad_id);
 } ST_CATCH_ALL
 
 int st_quartet_positions(int device, int mode, uint64_t seed, int64_t m, int64_t k_begin, int64_t k_count, int32_t *out_pos)
@@ -1527,69 +1076,7 @@ try {
     if (!out_adjacency && !out_laplacian) return fail(ST_ERR_ARG, "both outputs are NULL");
     for (int64_t e = 0; e < n_edges; e++)
         if (u[e] < 0 || u[e] >= n || v[e] < 0 || v[e] >= n) return fail(ST_ERR_ARG, "edge endpoint out of range");
-    ST_DEVICE(device);
-    // one workspace: A, L (only if asked for), column sums, edge list.  The dense matrices
-    // must fit the GPU's free memory with room to spare; beyond that the caller should not
-    // be building a dense Laplacian at all (the reference's numpy version would need the same
-    // bytes of host memory).
-    const size_t mat = (size_t)n * (size_t)n * 8;
-    const size_t edges_b = (size_t)std::max<int64_t>(n_edges, 1);
-    const size_t need = mat * (out_laplacian ? 2 : 1) + (size_t)n * 8 + edges_b * 16 + 4096;
-    size_t free_b = 0, total_b = 0;
-    ST_HIP(hipMemGetInfo(&free_b, &total_b));
-    if (need > free_b / 10 * 9)
-        return fail(ST_ERR_NOMEM, "dense " + std::to_string(n) + " x " + std::to_string(n) + " graph matrices need " +
-                                      std::to_string(need >> 20) + " MiB of device memory, " + std::to_string(free_b >> 20) + " MiB free");
-    // one grow-only workspace per device, kept between calls (a 422 x 422 Laplacian is all
-    // allocation time otherwise); calls on one device take turns
-    struct Workspace { std::mutex m; DevBuf<char> p; size_t cap = 0; };      // (never deleted: no HIP call from a static destructor)
-    static std::mutex ws_map_mutex;
-    static std::map<int, Workspace *> ws_map;
-    Workspace *W;
-    {
-        std::lock_guard<std::mutex> g(ws_map_mutex);
-        Workspace *&slot = ws_map[device];
-        if (!slot) slot = new Workspace();
-        W = slot;
-    }
-    std::lock_guard<std::mutex> ws_lock(W->m);
-    if (W->cap < need) {
-        W->cap = 0;
-        ST_HIP(W->p.alloc(need));
-        W->cap = need;
-    }
-    char *ws = W->p;
-    double *d_A = reinterpret_cast<double *>(ws);
-    double *d_L = out_laplacian ? d_A + (size_t)n * n : nullptr;
-    double *d_deg = reinterpret_cast<double *>(ws + mat * (out_laplacian ? 2 : 1));
-    double *d_w = d_deg + n;
-    int *d_u = reinterpret_cast<int *>(d_w + edges_b), *d_v = d_u + edges_b;
-    hipError_t e = hipMemsetAsync(d_A, 0, mat, nullptr);
-    if (e == hipSuccess && n_edges) e = hipMemcpyAsync(d_u, u, (size_t)n_edges * 4, hipMemcpyHostToDevice, nullptr);
-    if (e == hipSuccess && n_edges) e = hipMemcpyAsync(d_v, v, (size_t)n_edges * 4, hipMemcpyHostToDevice, nullptr);
-    if (e == hipSuccess && n_edges) e = hipMemcpyAsync(d_w, w, (size_t)n_edges * 8, hipMemcpyHostToDevice, nullptr);
-    if (e == hipSuccess) {
-        if (n_edges)
-            hipLaunchKernelGGL(k_graph_scatter, dim3((unsigned)std::min<int64_t>((n_edges + 255) / 256, 4096)),
-                               dim3(256), 0, nullptr, d_A, (long long)n, (long long)n_edges, d_u, d_v, d_w);
-        if (out_laplacian) {
-            // one lane per column, rows in increasing order (numpy's sum(axis=0) order); waves of
-            // 64 consecutive columns read each row coalesced, one wave per workgroup so that a
-            // few hundred columns already spread over the chip
-            hipLaunchKernelGGL(k_graph_degree, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, nullptr, d_A, (long long)n, d_deg);
-            hipLaunchKernelGGL(k_graph_laplacian, dim3((unsigned)std::min<int64_t>((n * n + 255) / 256, 65536)),
-                               dim3(256), 0, nullptr, d_A, d_deg, (long long)n, d_L);
-        }
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && out_adjacency) e = hipMemcpy(out_adjacency, d_A, mat, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_laplacian) e = hipMemcpy(out_laplacian, d_L, mat, hipMemcpyDeviceToHost);
-    if (W->cap > ((size_t)256 << 20)) {     // do not sit on a multi-GB workspace
-        W->p.reset();
-        W->cap = 0;
-    }
-    if (e != hipSuccess) return fail(ST_ERR_HIP, std::string("graph matrices: ") + hipGetErrorString(e));
-    return ST_OK;
+    return graph_matrices_run(device, n, n_edges, u, v, w, out_adjacency, out_laplacian);
 } ST_CATCH_ALL
 
 int st_device_malloc(int device, int64_t bytes, void **out)

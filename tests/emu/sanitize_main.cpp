@@ -287,6 +287,39 @@ static int check_host_copy(std::mt19937_64 &rng)
     return 0;
 }
 
+// narrow_pairs_strided (host_copy.h) for one id width: C order, column-major and a view of every other row and column,
+// from skewed starts and into skewed destinations, with the values at and beyond both ends of int32 (and -1) among the ids;
+// every output word, the words around them and both extremes against the restatement in the loop below.
+template <typename Id>
+static int check_narrow_strided(std::mt19937_64 &rng, int code)
+{
+    const long long edge[] = {INT32_MAX, (long long)INT32_MAX + 1, INT32_MIN, (long long)INT32_MIN - 1, -1};
+    for (const int64_t m : {1, 63, 64, 65})
+        for (int form = 0; form < 3; form++)
+            for (int skew = 0; skew < 4; skew++) {
+                const int64_t s0 = form == 0 ? 2 : form == 1 ? 1 : 4, s1 = form == 0 ? 1 : form == 1 ? m : 2;
+                std::vector<Id> src((size_t)(skew + 4 * m + 4));
+                for (auto &v : src) v = (Id)(rng() % 3000000);
+                for (const long long v : edge) {
+                    if (sizeof(Id) == 4 && (v > INT32_MAX || v < INT32_MIN)) continue;      // (not an int32 id)
+                    src[(size_t)(skew + (int64_t)(rng() % (uint64_t)m) * s0 + (int64_t)(rng() % 2) * s1)] = (Id)v;
+                }
+                const int so = (skew * 3) % 4;
+                std::vector<int32_t> got((size_t)(2 * m + 8), 77), want((size_t)(2 * m + 8), 77);
+                long long want_hi = std::numeric_limits<long long>::min(), want_lo = std::numeric_limits<long long>::max();
+                for (int64_t q = 0; q < 2 * m; q++) {
+                    const long long v = (long long)src[(size_t)(skew + (q / 2) * s0 + (q % 2) * s1)];
+                    want[(size_t)(so + q)] = (int32_t)std::min<long long>(std::max<long long>(v, INT32_MIN), INT32_MAX);
+                    if (v > INT32_MAX) want_hi = std::max(want_hi, v);
+                    if (v < INT32_MIN) want_lo = std::min(want_lo, v);
+                }
+                long long hi = std::numeric_limits<long long>::min(), lo = std::numeric_limits<long long>::max();
+                st::narrow_pairs_strided(got.data() + so, src.data() + skew, m, s0, s1, hi, lo);
+                if (got != want || hi != want_hi || lo != want_lo) return code;
+            }
+    return 0;
+}
+
 // ---- compare_plan.cpp: the clade plan, its tables and the fold; the rows layout; the merge -------------------------
 // Any rooted tree with 0-3 links per leaf in shuffled order, under no cap, 0, a small and a large one.  Exact
 // expectations throughout: the segments tile [0, total), the tile table points at the segment and the piece of every
@@ -333,7 +366,7 @@ static int check_clades(std::mt19937_64 &rng, const std::vector<int32_t> &parent
     return 0;
 }
 
-// The conditions RowsReduce::chunk and the id upload of st_compare_rows_host (host_compare.h, suchtree_hip.hip) reject
+// The conditions RowsReduce::chunk and the id upload of st_compare_rows_host (host_compare.h: rows_run) reject
 // with hipErrorInvalidValue, walked chunk by chunk as compare_run does; every row's blocks hold its P pairs.
 static int check_rows_layout()
 {
@@ -413,6 +446,8 @@ int main()
 {
     std::mt19937_64 rng(12345);
     if (const int rc = check_host_copy(rng)) { std::printf("FAILED host_copy rc=%d\n", rc); return rc; }
+    if (const int rc = check_narrow_strided<int64_t>(rng, 28)) { std::printf("FAILED narrow_pairs_strided rc=%d\n", rc); return rc; }
+    if (const int rc = check_narrow_strided<int32_t>(rng, 29)) { std::printf("FAILED narrow_pairs_strided rc=%d\n", rc); return rc; }
     const int sizes[] = {1, 2, 3, 7, 64, 1000, 20000};
     const double skews[] = {0.0, 0.5, 0.9, 0.999};
     for (int n : sizes)

@@ -31,12 +31,12 @@ WALK_SORTED_MIN_PAIRS = 262144           # launch_policy.h:148 kWalkSortedMinPai
 PREFERS_WALK_SORTED_MIN = 524288         # launch_policy.h:154 prefers_walk_sorted
 LADDER_DYNAMIC_MIN = 1 << 22             # launch_canopy.hip:48 kLadderDynamicMin (records of 512 bytes; 1 KB: half of it)
 HOST_CHUNK_MIN, HOST_CHUNK_MAX = 1 << 18, 1 << 22      # host_path.h:16-17 kHostChunkMin / kHostChunk
-QUARTET_CHUNK = HOST_CHUNK_MAX // 8      # suchtree_hip.hip:1158
-KNN_BLOCK_ELEMS = 1 << 26                # suchtree_hip.hip:881 rows_per_block
+QUARTET_CHUNK = HOST_CHUNK_MAX // 8      # host_quartets.h: quartets_host_run
+KNN_BLOCK_ELEMS = 1 << 26                # host_misc.h: knn_host_run, rows_per_block
 KNN_MAX_K = 256                          # kernels_misc.h:15 kKnnMaxK
-GRAPH_SCATTER_SPAN = 4096 * 256          # suchtree_hip.hip:1287: edges one pass of k_graph_scatter covers
-GRAPH_LAPLACIAN_SPAN = 65536 * 256       # suchtree_hip.hip:1294: elements one pass of k_graph_laplacian covers
-TRIANGLE_MAX_M = 3_000_000_000           # suchtree_hip.hip:750
+GRAPH_SCATTER_SPAN = 4096 * 256          # host_misc.h: graph_matrices_run: edges one pass of k_graph_scatter covers
+GRAPH_LAPLACIAN_SPAN = 65536 * 256       # host_misc.h: graph_matrices_run: elements one pass of k_graph_laplacian covers
+TRIANGLE_MAX_M = 3_000_000_000           # host_compare.h: triangle_range_args
 
 FULL_ORACLE_MAX = 1 << 20
 ORACLE_SAMPLE = 200_000
@@ -310,7 +310,7 @@ def _sweep(dev, ref, opt, size, seen, seed=1, wires=(1, 0)):
         assert np.array_equal(dev.quartets_host(q), ref.cache[key]), ("quartets_host", opt)
         info = dev.info()
         if info["strategy"] == "canopy" and 6 * nq >= CANOPY_MIN_PAIRS:
-            assert 6 * nq >= CANOPY_MIN_PAIRS_MAX      # (suchtree_hip.hip:1165, 1204: the canopy route for certain)
+            assert 6 * nq >= CANOPY_MIN_PAIRS_MAX      # (host_quartets.h: quartets_host_run: the canopy route for certain)
             seen.add((_kernel(info, opt, 6 * nq, False), rec, "quartet", "m32"))
         else:
             seen.add(("quartets_walk", rec, "quartet", "topology"))
@@ -784,7 +784,7 @@ def test_c_quartet_chunks_and_routes(ml_arrays):
     big[5] = big[5, 0]                                          # four equal ids
     big[-1] = rng.integers(0, len(parent), 4)
     want = _oracle_quartets(parent, dist, big)
-    # suchtree_hip.hip:1165, 1204: a chunk of m quartets takes the canopy route iff 6 m >= canopy_min_pairs(t).  (By the
+    # host_quartets.h: quartets_host_run: a chunk of m quartets takes the canopy route iff 6 m >= canopy_min_pairs(t).  (By the
     # restated thresholds only: no reported state exposes the route of a chunk, and both routes are defined to give the same
     # topologies, so forcing the tail through either is an equivalent mutant -- LAB_NOTES.md)
     assert 6 * 1 < CANOPY_MIN_PAIRS and 6 * QUARTET_CHUNK >= CANOPY_MIN_PAIRS_MAX and n % QUARTET_CHUNK == 1
@@ -926,7 +926,7 @@ def test_d_knn_row_blocks(ml_arrays):
     dev = _capi.DeviceTree(parent, dist)
     O = OracleTree(parent, dist)
     cands = leaf_ids
-    rows_per_block = max(1, KNN_BLOCK_ELEMS // len(cands))      # suchtree_hip.hip:881 (n_queries is larger)
+    rows_per_block = max(1, KNN_BLOCK_ELEMS // len(cands))      # host_misc.h: knn_host_run (n_queries is larger)
     n_q = 2 * rows_per_block + 17
     blocks = -(-n_q // rows_per_block)
     assert n_q * len(cands) > KNN_BLOCK_ELEMS and blocks == 3 and n_q % rows_per_block == 17
