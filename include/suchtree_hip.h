@@ -51,7 +51,8 @@ extern "C" {
  *      ST_UNIFRAC_LANE_MAX, st_unifrac_host, st_unifrac_depths and st_unifrac_quantise; then st_tree_info.heap_codes appended
  *      (8 bytes) with option "heap_codes", as heap_lines was; then, also additive, ST_CLADE_MATCH_MAX_LEAVES, st_clade_ranges
  *      and st_clade_match; then, also additive, st_beta_dispersion_host and st_beta_dispersion_matrix; then, also additive,
- *      st_unifrac_null_host and st_unifrac_null_depths.
+ *      st_unifrac_null_host and st_unifrac_null_depths; then, also additive, struct st_mantel_sums, struct st_mantel_moments,
+ *      ST_MANTEL_SHIFT_AUTO, st_mantel_codes and st_mantel_quantise.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -727,6 +728,81 @@ int st_unifrac_null_host(st_tree *tree, int64_t root, const int64_t *univ, int32
 int st_unifrac_null_depths(int device, const int64_t *d_q, const int64_t *h_q, int32_t n, const int32_t *set_pos, int64_t n_pos,
                            const int64_t *sets, int64_t n_sets, int64_t k_begin, int64_t k_count, int64_t permutations,
                            uint64_t seed, int32_t stream, int64_t chunk_tasks, int64_t *out_pd, int64_t *out_union);
+
+/*
+ * Is one distance matrix correlated with another over the same n objects: the Mantel test, and the partial Mantel test
+ * given a third matrix, under the relabelling null of st_partner_dispersion_host (compare.mantel, SuchTree.mantel,
+ * SuchLinkedTrees.phylosymbiosis).  Every sum is an exact integer: "r_p >= r_0" is a comparison of integers, so the
+ * p-value has no floating-point ties.
+ *
+ * Codes.  Both matrices enter as int32 codes.  For Pearson's form a code is q(v) = llrint(ldexp(v, shift)), the shift
+ * chosen per matrix; for Spearman's form it is the doubled midrank of the m = n (n - 1) / 2 off-diagonal values minus
+ * (m + 1), ranked by the caller.  Any int32 is a code.
+ *
+ * Orders.  x_sq is the square n x n matrix of x, C order; both triangles must be equal and the diagonal is ignored.  y
+ * and z are condensed in the project's triangle order: entry k = i (i - 1) / 2 + j is the pair (i, j), 0 <= j < i < n
+ * (st_triangle_host).  z = NULL is the simple test.  3 <= n <= ST_HOMMOLA_MAX_UNIVERSE.
+ *
+ * Permutations.  sigma_p = st_hommola_permutation(seed, node = stream, p, side = 0, n), p = 0 the identity.  x is the
+ * matrix that is relabelled (vegan's mantel.partial):
+ *     Sxy_p = sum over j < i of x_sq[sigma_p(i)][sigma_p(j)] * y[k(i, j)],   Sxz_p the same against z (0 without z),
+ * each a 128-bit two's-complement integer in a lo / hi pair (|Sxy_p| < 2^89).  out holds permutations + 1 records, record
+ * 0 the observation.  A record depends on (seed, stream, p, x_sq, y, z) alone -- not on permutations, chunk_tasks, the
+ * kernel form, the grid or the device; record p is the same for any permutations >= p.
+ *
+ * Moments.  The sums that do not depend on p, over the pairs j < i with x = x_sq[i][j]: Sx, Sy, Sz, Sxx, Syy, Szz, Syz,
+ * computed once on the host with __int128 (Sz, Szz, Syz are 0 without z).  With m pairs the caller forms
+ *     r_p = (m Sxy_p - Sx Sy) / sqrt((m Sxx - Sx^2) (m Syy - Sy^2)),
+ * whose order over p is that of the integers Sxy_p, and the partial coefficient from r_xy, r_xz and r_yz.
+ *
+ * Checked (ST_ERR_ARG), in this order: n outside 3 .. ST_HOMMOLA_MAX_UNIVERSE, negative permutations, chunk_tasks or
+ * stream, more than 2^31 - 1 permutations, a NULL x_sq, y, moments or out, then an x_sq that is not symmetric, naming the
+ * first cell (in row-major order) whose mirror differs; then a device below -1.  device = -1 computes every record on the
+ * host (no GPU); device >= 0 uploads the matrices and runs the kernels: the same integers.  n <= 64: one wave per
+ * permutation, x_sq in LDS.  Above: one workgroup per (permutation, row pair r: rows r and n - 1 - r), row sigma_p(i) of
+ * x_sq staged in LDS (4 n bytes), the partial sums folded per permutation on the device; only the records cross the
+ * link.  chunk_tasks: (permutation, row pair) tasks per launch, 0 = 2^20; a positive value also bounds the permutations
+ * whose sigma rows the device holds at once.  Device memory: 4 n^2 bytes of x_sq, 4 m per condensed matrix, one block of
+ * sigma rows (at most 64 MiB), at most 128 MiB of partial sums and 32 bytes per record; an allocation that fails is
+ * ST_ERR_NOMEM with the bytes asked for, before out is written.  The environment variable SUCHTREE_AMD_MANTEL_GATHER=1
+ * (read at every call) makes the row form gather from x_sq in global memory instead of staging the row, for a
+ * measurement; no result depends on it.  No counterpart in the reference.
+ *
+ * st_mantel_quantise is the fixed point on the host: out[k] = llrint(ldexp(v[k], shift)) for n values.  shift =
+ * ST_MANTEL_SHIFT_AUTO takes 30 - ilogb(max |v|), one less where the largest value would round up to 2^31, and 0 when
+ * every value is 0: the largest |code| lands in [2^30, 2^31).  A caller's shift of -2000 .. 2000 that puts a |code| at
+ * 2^31 or more is ST_ERR_ARG, as is a NaN or an infinity, naming its index.  out and out_shift may each be NULL.
+ */
+#define ST_MANTEL_SHIFT_AUTO (-2147483647 - 1)
+
+typedef struct st_mantel_sums {
+    uint64_t sxy_lo;
+    int64_t sxy_hi;
+    uint64_t sxz_lo;
+    int64_t sxz_hi;
+} st_mantel_sums;
+
+typedef struct st_mantel_moments {
+    uint64_t sx_lo;
+    int64_t sx_hi;
+    uint64_t sy_lo;
+    int64_t sy_hi;
+    uint64_t sz_lo;
+    int64_t sz_hi;
+    uint64_t sxx_lo;
+    int64_t sxx_hi;
+    uint64_t syy_lo;
+    int64_t syy_hi;
+    uint64_t szz_lo;
+    int64_t szz_hi;
+    uint64_t syz_lo;
+    int64_t syz_hi;
+} st_mantel_moments;
+
+int st_mantel_codes(int device, const int32_t *x_sq, const int32_t *y, const int32_t *z, int32_t n, int64_t permutations,
+                    uint64_t seed, int32_t stream, int64_t chunk_tasks, st_mantel_moments *moments, st_mantel_sums *out);
+
+int st_mantel_quantise(const double *v, int64_t n, int32_t shift_or_auto, int32_t *out, int32_t *out_shift);
 
 /*
  * Which clades of one tree are also in another, and how close is the best match where they are not: every induced clade

@@ -49,6 +49,7 @@ SYMBOLS = (
     "st_hommola_permutation", "st_hommola_clades_host", "st_partner_dispersion_host", "st_dispersion_matrix",
     "st_unifrac_host", "st_unifrac_depths", "st_unifrac_quantise", "st_clade_ranges", "st_clade_match",
     "st_beta_dispersion_host", "st_beta_dispersion_matrix", "st_unifrac_null_host", "st_unifrac_null_depths",
+    "st_mantel_codes", "st_mantel_quantise",
 )
 
 CLADE_RECT, CLADE_TRI = 0, 1     # include/suchtree_hip.h: ST_CLADE_RECT / ST_CLADE_TRI
@@ -264,6 +265,60 @@ def unifrac_null_depths(d_q, h_q, sets, begin=0, count=None, permutations=0, see
                                         int(permutations), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(chunk_tasks),
                                         _ptr(pd_q) if pd else None, _ptr(union_q) if union else None))
     return pd_q, union_q
+
+
+MANTEL_SHIFT_AUTO = -2147483648     # ST_MANTEL_SHIFT_AUTO
+# st_mantel_sums as a numpy record
+MANTEL_SUMS = np.dtype([("sxy_lo", np.uint64), ("sxy_hi", np.int64), ("sxz_lo", np.uint64), ("sxz_hi", np.int64)])
+MANTEL_MOMENT_NAMES = ("sx", "sy", "sz", "sxx", "syy", "szz", "syz")
+
+
+class MantelMoments(ctypes.Structure):
+    """st_mantel_moments (include/suchtree_hip.h): the sums of the Mantel test that no permutation changes, as lo / hi pairs."""
+    _fields_ = [f for k in MANTEL_MOMENT_NAMES for f in ((k + "_lo", ctypes.c_uint64), (k + "_hi", ctypes.c_int64))]
+
+    def as_dict(self):
+        return {k: (int(getattr(self, k + "_hi")) << 64) + int(getattr(self, k + "_lo")) for k in MANTEL_MOMENT_NAMES}
+
+
+def mantel_ints(records, name):
+    """The 128-bit sums ``name`` ("sxy" / "sxz") of an array of MANTEL_SUMS as a list of Python ints."""
+    lo, hi = records[name + "_lo"].tolist(), records[name + "_hi"].tolist()
+    return [(h << 64) + l for l, h in zip(lo, hi)]
+
+
+def mantel_codes(x_sq, y, z=None, permutations=0, seed=0, stream=0, device=-1, chunk_tasks=0):
+    """st_mantel_codes: (moments dict of Python ints, records) of the square int32 matrix ``x_sq`` (n, n) against the
+    condensed int32 ``y`` and, for the partial test, ``z`` (n (n - 1) / 2 each, pair (i, j) at i (i - 1) / 2 + j): the
+    permutations + 1 records of MANTEL_SUMS, record 0 the observation.  ``device`` -1 = the host restatement (no GPU),
+    else the kernels on that device."""
+    x_sq = np.ascontiguousarray(x_sq, dtype=np.int32)
+    if x_sq.ndim != 2 or x_sq.shape[0] != x_sq.shape[1]:
+        raise ValueError("x_sq must be a square matrix")
+    n = int(x_sq.shape[0])
+    m = n * (n - 1) // 2
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    z = None if z is None else np.ascontiguousarray(z, dtype=np.int32)
+    for name, v in (("y", y), ("z", z)):
+        if v is not None and (v.ndim != 1 or len(v) != m):
+            raise ValueError("%s must hold the %d pairs of %d objects" % (name, m, n))
+    _dispersion_args(permutations, stream, chunk_tasks)
+    out = np.zeros(int(permutations) + 1, dtype=MANTEL_SUMS)
+    moments = MantelMoments()
+    check(load().st_mantel_codes(int(device), _ptr(x_sq), _arg(y), None if z is None else _arg(z), n, int(permutations),
+                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(chunk_tasks), ctypes.byref(moments), _ptr(out)))
+    return moments.as_dict(), out
+
+
+def mantel_quantise(v, shift=None):
+    """st_mantel_quantise: (int32 codes llrint(ldexp(v, shift)) in the shape of ``v``, shift used); ``shift`` None = the
+    one that puts the largest |code| in [2^30, 2^31).  ValueError for a NaN or an infinity (naming its index in C order)
+    or a shift that puts a code at 2^31 or more."""
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    out = np.zeros(v.shape, dtype=np.int32)
+    used = ctypes.c_int32(0)
+    check(load().st_mantel_quantise(_arg(v), v.size, MANTEL_SHIFT_AUTO if shift is None else int(shift), _arg(out), ctypes.byref(used)))
+    return out, int(used.value)
 
 
 CLADE_MATCH_MAX_LEAVES = 1 << 18     # ST_CLADE_MATCH_MAX_LEAVES: leaves per list of st_clade_ranges / st_clade_match
@@ -562,6 +617,8 @@ def load():
         L.st_unifrac_null_depths.argtypes = [i32, vp, vp, ctypes.c_int32, vp, i64, vp, i64, i64, i64, i64, ctypes.c_uint64, ctypes.c_int32, i64,
                                              vp, vp]
         L.st_unifrac_quantise.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, ctypes.POINTER(ctypes.c_int32)]
+        L.st_mantel_codes.argtypes = [i32, vp, vp, vp, ctypes.c_int32, i64, ctypes.c_uint64, ctypes.c_int32, i64, ctypes.POINTER(MantelMoments), vp]
+        L.st_mantel_quantise.argtypes = [vp, i64, ctypes.c_int32, vp, ctypes.POINTER(ctypes.c_int32)]
         L.st_clade_ranges.argtypes = [vp, i64, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int32),
                                       ctypes.POINTER(i64)]
         L.st_clade_match.argtypes = [i32, ctypes.c_int32, vp, vp, vp, ctypes.c_int32, vp, vp, ctypes.c_int32, ctypes.c_int32, i64, vp, vp, vp]

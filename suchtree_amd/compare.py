@@ -14,7 +14,7 @@ from typing import Optional
 import numpy as np
 
 __all__ = ["DistanceComparison", "CladeComparisons", "HommolaResult", "QuartetComparison", "SetDispersion", "SetUniFrac", "quartet_positions",
-           "unifrac_from_depths"]
+           "unifrac_from_depths", "MantelResult", "mantel"]
 
 
 @dataclass(frozen=True)
@@ -1163,3 +1163,169 @@ def quartet_positions(m, samples=None, seed=0, begin=0, count=None, device=None)
         if count is None:
             count = int(samples) - begin
     return _capi.quartet_positions(mode, 0 if samples is None else seed, m, begin, count, -1 if device is None else int(device))
+
+
+MANTEL_METHODS = ("pearson", "spearman")
+MANTEL_ALTERNATIVES = ("two-sided", "greater", "less")
+
+
+class MantelResult:
+    """The Mantel test, or the partial Mantel test given a third matrix (mantel, SuchTree.mantel,
+    SuchLinkedTrees.phylosymbiosis).
+
+    ``corr_coeff`` is the correlation of the two matrices' ``n_pairs`` = n (n - 1) / 2 off-diagonal entries -- Pearson's r
+    of the values or, with ``method="spearman"``, of their midranks; with a third matrix the partial correlation of x
+    and y given z -- and ``p_value`` = (count + 1) / (permutations + 1), the count being ``n_ge`` (permuted statistic >=
+    the observed one), ``n_le`` or ``n_abs_ge`` by ``alternative`` ("greater", "less", "two-sided").  The matrices enter
+    the sums as int32 codes (``shift_x`` / ``shift_y`` / ``shift_z``: the fixed point of the Pearson form, None for
+    ranks), so ``sxy`` -- and ``sxz`` -- of every permutation and the invariant ``sx``, ``sy``, ``sz``, ``sxx``, ``syy``,
+    ``szz``, ``syz`` are exact Python ints: in the simple test the three counts compare integers.  ``perm_stats`` is the
+    float64 statistic of each permutation in draw order with ``keep_stats=True``, else None.  A constant matrix gives NaN
+    for both.  ``seed`` repeats the run.  Unpacks as ``r, p, n = result``, as scikit-bio's ``mantel`` returns.
+    ``leaves`` / ``names`` / ``measure`` are filled in by ``phylosymbiosis``.
+    """
+
+    def __init__(self, **kw):
+        self.leaves = self.names = self.measure = None
+        self.__dict__.update(kw)
+
+    def __iter__(self):
+        return iter((self.corr_coeff, self.p_value, self.n))
+
+    def __repr__(self):
+        return "MantelResult(corr_coeff=%r, p_value=%r, n=%d, method=%r, alternative=%r, permutations=%d)" % (
+            self.corr_coeff, self.p_value, self.n, self.method, self.alternative, self.permutations)
+
+
+def mantel_condensed(a, name="x"):
+    """(the float64 condensed form of ``a`` in the triangle order k = i (i - 1) / 2 + j, j < i; n): ``a`` is a square
+    symmetric (n, n) matrix, whose diagonal is ignored, or already condensed.  ValueError, naming the offender, for a
+    NaN or an infinity, a cell whose mirror differs, a length that is no triangle, n < 3 or n > 16384."""
+    from . import _capi
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim == 2:
+        if a.shape[0] != a.shape[1]:
+            raise ValueError("%s: a %d x %d matrix is not square" % ((name,) + a.shape))
+        n = int(a.shape[0])
+    elif a.ndim == 1:
+        n = (1 + math.isqrt(1 + 8 * len(a))) // 2
+        if n * (n - 1) // 2 != len(a):
+            raise ValueError("%s: %d values are not the n (n - 1) / 2 pairs of any n" % (name, len(a)))
+    else:
+        raise ValueError("%s must be a square matrix or a condensed vector" % name)
+    if n < 3 or n > _capi.HOMMOLA_MAX_UNIVERSE:
+        raise ValueError("%s: n = %d objects: 3 to %d" % (name, n, _capi.HOMMOLA_MAX_UNIVERSE))
+    if a.ndim == 1:
+        bad = np.flatnonzero(~np.isfinite(a))
+        if len(bad):
+            raise ValueError("%s[%d] = %r is not finite" % (name, int(bad[0]), float(a[bad[0]])))
+        return np.ascontiguousarray(a), n
+    i, j = np.tril_indices(n, -1)      # (row-major over the lower triangle: the triangle order)
+    low, up = a[i, j], a[j, i]
+    bad = np.flatnonzero(~(np.isfinite(low) & np.isfinite(up)))
+    if len(bad):
+        r, c = (int(i[bad[0]]), int(j[bad[0]])) if not np.isfinite(low[bad[0]]) else (int(j[bad[0]]), int(i[bad[0]]))
+        raise ValueError("%s[%d][%d] = %r is not finite" % (name, r, c, float(a[r, c])))
+    bad = np.flatnonzero(low != up)
+    if len(bad):
+        r, c = int(i[bad[0]]), int(j[bad[0]])
+        raise ValueError("%s is not symmetric: %s[%d][%d] = %r, %s[%d][%d] = %r" % (name, name, r, c, float(a[r, c]), name, c, r, float(a[c, r])))
+    return np.ascontiguousarray(low), n
+
+
+def mantel_rank_codes(v):
+    """The int32 Spearman codes of the m values ``v``: twice the midrank (1 .. m, ties averaged as
+    scipy.stats.rankdata(v, "average") does, -0.0 tied with +0.0) minus (m + 1)."""
+    v = np.asarray(v, dtype=np.float64) + 0.0      # (-0.0 + 0.0 is +0.0)
+    _, inverse, counts = np.unique(v, return_inverse=True, return_counts=True)
+    below = np.cumsum(counts) - counts
+    return (2 * below + counts - len(v))[inverse.ravel()].astype(np.int32)      # (2 (below + (count + 1) / 2) - (m + 1))
+
+
+def mantel_square(codes, n):
+    """The (n, n) int32 matrix of condensed ``codes``, both triangles, a zero diagonal."""
+    out = np.zeros((n, n), dtype=np.int32)
+    i, j = np.tril_indices(n, -1)
+    out[i, j] = out[j, i] = codes
+    return out
+
+
+def _mantel_ratio(num, den2):
+    """num / sqrt(den2) of Python ints as float64; NaN where den2 <= 0"""
+    return float("nan") if den2 <= 0 else num / math.sqrt(den2)
+
+
+def mantel(x, y, z=None, method="pearson", permutations=999, seed=None, alternative="two-sided", stream=0, keep_stats=False, device=...,
+           chunk_tasks=0):
+    """The Mantel test of two distance matrices over the same n objects and, with ``z``, the partial Mantel test of x
+    and y given z, the permutations on the GPU.
+
+    Each of ``x``, ``y``, ``z`` is a square symmetric matrix (the diagonal is ignored) or a condensed vector in the
+    project's triangle order k = i (i - 1) / 2 + j, j < i, as ``SetUniFrac.pair(k)`` gives it; 3 <= n <= 16384.
+    ``method`` is "pearson" (the values, as fixed-point int32 codes with a shift per matrix: 30 bits of the largest
+    value) or "spearman" (the midranks of the off-diagonal values, ranked here on the host).  Permutation p >= 1
+    relabels the objects of x by ``hommola_permutation(seed, stream, p, 0, n)``, as vegan's ``mantel`` and
+    ``mantel.partial`` do; every permuted sum is an exact integer computed on ``device`` (... = device 0; None = on the
+    host, without a GPU: the same integers), so the first k permutations are the same for any ``permutations`` >= k and
+    the counts behind the p-value have no floating-point ties.  ``seed=None`` draws a seed and reports it.
+    ``chunk_tasks`` bounds a launch (0 = 2^20 tasks); no result depends on it.  Returns a :class:`MantelResult`.
+    An extension: the reference has no counterpart.
+    """
+    from . import _capi
+    from .suchtree import int_arg, seed_arg
+    if method not in MANTEL_METHODS:
+        raise ValueError("method must be one of %s" % (MANTEL_METHODS,))
+    if alternative not in MANTEL_ALTERNATIVES:
+        raise ValueError("alternative must be one of %s" % (MANTEL_ALTERNATIVES,))
+    permutations, stream = int_arg("permutations", permutations, (1 << 31) - 1, "2^31 - 1"), int_arg("stream", stream, (1 << 31) - 1, "2^31 - 1")
+    chunk_tasks, seed = int_arg("chunk_tasks", chunk_tasks), seed_arg(seed)
+    vx, n = mantel_condensed(x, "x")
+    given = [("x", vx)]
+    for name, a in (("y", y), ("z", z)):
+        if a is not None:
+            v, n_a = mantel_condensed(a, name)
+            if n_a != n:
+                raise ValueError("%s has %d objects, x has %d" % (name, n_a, n))
+            given.append((name, v))
+    codes, shifts = {}, {"x": None, "y": None, "z": None}
+    for name, v in given:
+        if method == "spearman":
+            codes[name] = mantel_rank_codes(v)
+        else:
+            codes[name], shifts[name] = _capi.mantel_quantise(v)
+    dev = -1 if device is None else 0 if device is ... else int_arg("device", device)
+    mom, rec = _capi.mantel_codes(mantel_square(codes["x"], n), codes["y"], codes.get("z"), permutations, seed, stream, dev, chunk_tasks)
+    m = n * (n - 1) // 2
+    sxy = _capi.mantel_ints(rec, "sxy")
+    var_x, var_y = m * mom["sxx"] - mom["sx"] ** 2, m * mom["syy"] - mom["sy"] ** 2
+    cxy = [m * s - mom["sx"] * mom["sy"] for s in sxy]      # m^2 cov(x_p, y): Python ints
+    sums = dict(mom, sxy=sxy[0], sxz=None)
+    if z is None:
+        for k in ("sz", "szz", "syz"):
+            sums[k] = None
+        den = var_x * var_y
+        r0 = _mantel_ratio(cxy[0], den)
+        n_ge = sum(c >= cxy[0] for c in cxy[1:])
+        n_le = sum(c <= cxy[0] for c in cxy[1:])
+        n_abs_ge = sum(abs(c) >= abs(cxy[0]) for c in cxy[1:])
+        stats = np.array([_mantel_ratio(c, den) for c in cxy[1:]], dtype=np.float64) if keep_stats else None
+    else:
+        sxz = _capi.mantel_ints(rec, "sxz")
+        sums["sxz"] = sxz[0]
+        var_z = m * mom["szz"] - mom["sz"] ** 2
+        r_yz = _mantel_ratio(m * mom["syz"] - mom["sy"] * mom["sz"], var_y * var_z)
+        r_xy = np.array([_mantel_ratio(c, var_x * var_y) for c in cxy], dtype=np.float64)
+        r_xz = np.array([_mantel_ratio(m * s - mom["sx"] * mom["sz"], var_x * var_z) for s in sxz], dtype=np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            den = (1.0 - r_xz * r_xz) * (1.0 - r_yz * r_yz)
+            part = np.where(den > 0.0, (r_xy - r_xz * r_yz) / np.sqrt(np.where(den > 0.0, den, 1.0)), np.nan)
+        r0 = float(part[0])
+        n_ge = int(np.count_nonzero(part[1:] >= r0))
+        n_le = int(np.count_nonzero(part[1:] <= r0))
+        n_abs_ge = int(np.count_nonzero(np.abs(part[1:]) >= abs(r0)))
+        stats = part[1:].copy() if keep_stats else None
+    count = {"greater": n_ge, "less": n_le, "two-sided": n_abs_ge}[alternative]
+    p_value = float("nan") if math.isnan(r0) else (count + 1) / (permutations + 1)
+    return MantelResult(corr_coeff=r0, p_value=p_value, n=n, n_pairs=m, method=method, alternative=alternative, permutations=permutations,
+                        seed=seed, stream=stream, n_ge=int(n_ge), n_le=int(n_le), n_abs_ge=int(n_abs_ge), perm_stats=stats, partial=z is not None,
+                        shift_x=shifts["x"], shift_y=shifts["y"], shift_z=shifts["z"], **sums)

@@ -69,6 +69,10 @@
 // (st_clade_ranges, st_clade_match): kernels_clade_match.h (a bitmap and running counts in LDS, one row per workgroup),
 // host_clade_match.h (the chunk driver) and, host-only, clade_match_plan.cpp (the range builder, the checks, the size
 // windows, the restatement).
+// The Mantel and partial Mantel sums of two or three distance matrices under the same relabelling null (st_mantel_codes,
+// st_mantel_quantise): kernels_mantel.h (a wave form with the matrix in LDS, a row form that stages one matrix row in LDS
+// per workgroup, the fold), host_mantel.h (the loop over blocks and chunks) and, host-only, mantel_plan.cpp (the checks,
+// the invariant sums, the quantiser, the restatement).
 //
 // What the host side does: tree upload to one or several GPUs (tree_prep.cpp builds the tables, under a table budget
 // if one is given), the host path (host_pipe.h, host_copy.h: packed ids in through the copy engine, kernels write
@@ -195,6 +199,7 @@ static int device_index_arg(int device)
 #include "kernels_unifrac.h"
 #include "kernels_unifrac_null.h"
 #include "kernels_clade_match.h"
+#include "kernels_mantel.h"
 
 
 // --------------------------------------------------------------------------
@@ -216,6 +221,7 @@ using namespace st;
 #include "host_unifrac.h"
 #include "host_unifrac_null.h"
 #include "host_clade_match.h"
+#include "host_mantel.h"
 
 // the next link of st_link_sample_pairs (MuchTree.pyx:2946-2949)
 static int64_t link_draw(uint64_t &s, int64_t n_links)
@@ -1066,6 +1072,28 @@ try {
     CladeMatchPlan P;
     clade_match_plan(m, a_lo, a_hi, n_a, b_lo, b_hi, n_b, unrooted != 0, chunk_rows, clade_match_window(), P);
     return clade_match_device(device, P, pos_b, a_lo, a_hi, out_distance, out_match, out_intersection);
+} ST_CATCH_ALL
+
+int st_mantel_codes(int device, const int32_t *x_sq, const int32_t *y, const int32_t *z, int32_t n, int64_t permutations, uint64_t seed, int32_t stream,
+                    int64_t chunk_tasks, st_mantel_moments *moments, st_mantel_sums *out)
+try {
+    MantelPlan P;
+    std::string err;
+    const int rc = mantel_plan(x_sq, y, z, n, permutations, stream, chunk_tasks, moments, out, P, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (device_or_host_arg(device) != ST_OK) return ST_ERR_ARG;
+    if (device < 0) {
+        mantel_host(x_sq, y, z, P, seed, stream, out);
+        return ST_OK;
+    }
+    return mantel_device(device, P, x_sq, y, z, seed, stream, out);
+} ST_CATCH_ALL
+
+int st_mantel_quantise(const double *v, int64_t n, int32_t shift_or_auto, int32_t *out, int32_t *out_shift)
+try {
+    std::string err;
+    const int rc = mantel_quantise(v, n, shift_or_auto, out, out_shift, err);
+    return rc == ST_OK ? ST_OK : fail(rc, err);
 } ST_CATCH_ALL
 
 int st_graph_matrices_host(int device, int64_t n, int64_t n_edges, const int32_t *u, const int32_t *v,

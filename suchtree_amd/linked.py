@@ -644,6 +644,61 @@ class SuchLinkedTrees:
                                         seed=seed, stream=root, keep_null=keep_null)
         return self._over_partner_rows(of, min_partners, max_partners, run, pool, _capi.HOMMOLA_MAX_UNIVERSE)
 
+    PHYLOSYMBIOSIS_MEASURES = ("unifrac", "phylosor", "beta_mpd", "beta_mntd")
+
+    def phylosymbiosis(self, of="A", measure="unifrac", method="pearson", permutations=999, seed=None, alternative="greater", pool="subset",
+                       min_partners=1, max_partners=None, exclude_shared=False, control=None, keep_stats=False, device=..., chunk_tasks=0):
+        """Phylosymbiosis: do closely related leaves of one tree have similar partners in the other?  The Mantel test of
+        the leaves' own tree distance against the distance between their partner sets.
+
+        The rows are those of :meth:`partner_unifrac`: ``of="A"``, one per TreeA leaf of the current ``subset_a`` (in
+        ``subset_a_leafs`` order) with ``min_partners`` .. ``max_partners`` linked TreeB leaves inside the current
+        ``subset_b``; ``of="B"`` is the mirror.  x is the patristic distance between the row leaves in their own tree
+        (:meth:`SuchTree.pairwise_distances`), y the ``measure`` between their partner sets, taken from the observed
+        values of :meth:`partner_unifrac` ("unifrac", "phylosor") or :meth:`partner_beta_dispersion` ("beta_mpd",
+        "beta_mntd", with ``pool`` and ``exclude_shared``).  ``control`` is an optional third matrix over the same rows
+        (square, or condensed in the triangle order) for the partial test.  ``method``, ``permutations``, ``seed``,
+        ``alternative`` (here "greater" by default: related leaves, similar partners), ``keep_stats`` and ``chunk_tasks``
+        are those of :func:`~suchtree_amd.compare.mantel`, which relabels the row leaves on ``device`` (... = the row
+        tree's device; None = only the permutations run on the host: the two matrices still come from the trees'
+        kernels, so the call needs a GPU either way).  The call needs 3 to 16384 rows; a NaN in the measure (two
+        leaves whose partner sets give a zero denominator) is a ValueError that names the pair.
+
+        The subset state, ``linklist`` and the generator of :meth:`sample_linked_distances` are left as they were.
+        Returns a :class:`~suchtree_amd.compare.MantelResult` with ``leaves`` (the rows' leaf ids), ``names`` and
+        ``measure``.  An extension: the reference has no counterpart.
+        """
+        from . import compare
+        if measure not in self.PHYLOSYMBIOSIS_MEASURES:
+            raise ValueError("measure must be one of %s" % (self.PHYLOSYMBIOSIS_MEASURES,))
+        if method not in compare.MANTEL_METHODS or alternative not in compare.MANTEL_ALTERNATIVES:
+            raise ValueError("method must be one of %s and alternative one of %s" % (compare.MANTEL_METHODS, compare.MANTEL_ALTERNATIVES))
+        int_arg("permutations", permutations, (1 << 31) - 1, "2^31 - 1")
+        int_arg("chunk_tasks", chunk_tasks)
+        seed = seed_arg(seed)
+        by_distance = measure in ("beta_mpd", "beta_mntd")
+
+        def run(partner, sets, root, universe):
+            if len(sets) < 3 or len(sets) > _capi.HOMMOLA_MAX_UNIVERSE:      # (before anything is launched)
+                raise ValueError("%d rows: 3 to %d" % (len(sets), _capi.HOMMOLA_MAX_UNIVERSE))
+            if control is not None and compare.mantel_condensed(control, "control")[1] != len(sets):
+                raise ValueError("control is not over the %d rows" % len(sets))
+            if by_distance:
+                return partner.beta_dispersion(sets, universe=universe, exclude_shared=exclude_shared, permutations=0, seed=0, stream=root)
+            return partner.unifrac(sets, root=root)
+        observed = self._over_partner_rows(of, min_partners, max_partners, run, pool, _capi.HOMMOLA_MAX_UNIVERSE if by_distance else None)
+        y = np.asarray(getattr(observed, measure), dtype=np.float64)
+        bad = np.flatnonzero(np.isnan(y))
+        if len(bad):
+            i, j = observed.pair(int(bad[0]))
+            raise ValueError("%s of rows %d and %d (%s, %s) is NaN" % (measure, i, j, observed.names[i], observed.names[j]))
+        own = self._tree_a if of == "A" else self._tree_b
+        x = own.pairwise_distances(observed.leaves.tolist())
+        out = compare.mantel(x, y, control, method=method, permutations=permutations, seed=seed, alternative=alternative, keep_stats=keep_stats,
+                             device=own._device if device is ... else device, chunk_tasks=chunk_tasks)
+        out.leaves, out.names, out.measure = observed.leaves, observed.names, measure
+        return out
+
     @staticmethod
     def _leaf_counts(tree: SuchTree) -> np.ndarray:
         """Leaves under every node (st_clade_plan)."""

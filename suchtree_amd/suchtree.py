@@ -766,6 +766,28 @@ class SuchTree(TreeNavigation):
             out.fill(at, k[i], k[j], compare.shared_counts(bits, i, j), rec)      # (each group is reduced before the next)
         return out
 
+    def mantel(self, y, leaves, z=None, method="pearson", permutations=999, seed=None, alternative="two-sided", stream=0, keep_stats=False,
+               chunk_tasks=0):
+        """The Mantel test of this tree's distances against another distance matrix over the same objects, on the GPU.
+
+        ``leaves`` (leaf names or leaf ids, at least 3, at most 16384, none repeated) are the objects in the order of
+        ``y``'s rows; x is the tree's own distance matrix over them (:meth:`pairwise_distances`), and it is x that the
+        permutations relabel.  ``y``, ``z`` (the partial test given a third matrix) and every other argument are those of
+        :func:`~suchtree_amd.compare.mantel`, which does the work on this tree's device.  Returns a
+        :class:`~suchtree_amd.compare.MantelResult`.  An extension: the reference has no counterpart.
+        """
+        from . import compare
+        ids = self._leaf_ids(leaves, "leaves")
+        if len(np.unique(ids)) != len(ids):
+            raise ValueError("leaves: a repeated leaf")
+        if len(ids) < 3 or len(ids) > _capi.HOMMOLA_MAX_UNIVERSE:
+            raise ValueError("%d leaves: 3 to %d" % (len(ids), _capi.HOMMOLA_MAX_UNIVERSE))
+        for name, a in (("y", y), ("z", z)):      # (before the tree goes to its device)
+            if a is not None and compare.mantel_condensed(a, name)[1] != len(ids):
+                raise ValueError("%s is not over the %d leaves" % (name, len(ids)))
+        return compare.mantel(self.pairwise_distances(ids.tolist()), y, z, method=method, permutations=permutations, seed=seed, alternative=alternative,
+                              stream=stream, keep_stats=keep_stats, device=self._device, chunk_tasks=chunk_tasks)
+
     def unifrac(self, sets, root=None, begin=0, count=None, shift=None, chunk_pairs=0):
         """How different are every two sets of leaves, measured on this tree: Faith's PD and unweighted UniFrac, on the GPU.
 
