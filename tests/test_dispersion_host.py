@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from dispersion_reference import plain as _plain      # (the O(k^2) math.fsum loop, shared with tests/fuzz_analyses.py)
 from suchtree_amd import _capi, compare, build as st_build
 
 
@@ -33,22 +34,6 @@ def _matrix(n, seed):
 def _sets(n, sizes, seed):
     rng = np.random.default_rng(seed)
     return [np.sort(rng.choice(n, k, replace=False)) for k in sizes if k <= n]
-
-
-def _plain(D, q):
-    """(pair_sum, nearest_sum) of the relabelled positions q by the O(k^2) loop, in math.fsum."""
-    k = len(q)
-    if k < 2:
-        return 0.0, 0.0
-    sums, mins = [], []
-    for i in range(k):
-        vals = [float(D[q[i], q[j]]) for j in range(k) if j != i]
-        sums.append(math.fsum(vals))
-        m = math.inf
-        for v in vals:      # the stated rule: v < m ? v : m
-            m = v if v < m else m
-        mins.append(m)
-    return math.fsum(sums), math.fsum(mins)
 
 
 SIZES = (0, 1, 2, 3, 4, 5, 31, 32, 33, 63, 64, 65, 255, 256, 257)
