@@ -52,7 +52,8 @@ extern "C" {
  *      (8 bytes) with option "heap_codes", as heap_lines was; then, also additive, ST_CLADE_MATCH_MAX_LEAVES, st_clade_ranges
  *      and st_clade_match; then, also additive, st_beta_dispersion_host and st_beta_dispersion_matrix; then, also additive,
  *      st_unifrac_null_host and st_unifrac_null_depths; then, also additive, struct st_mantel_sums, struct st_mantel_moments,
- *      ST_MANTEL_SHIFT_AUTO, st_mantel_codes and st_mantel_quantise.
+ *      ST_MANTEL_SHIFT_AUTO, st_mantel_codes and st_mantel_quantise; then, also additive, ST_GROUP_MAX and
+ *      st_group_sums_codes.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -803,6 +804,41 @@ int st_mantel_codes(int device, const int32_t *x_sq, const int32_t *y, const int
                     uint64_t seed, int32_t stream, int64_t chunk_tasks, st_mantel_moments *moments, st_mantel_sums *out);
 
 int st_mantel_quantise(const double *v, int64_t n, int32_t shift_or_auto, int32_t *out, int32_t *out_shift);
+
+/*
+ * Do groups of objects differ in their distances: the within-group sums of one distance matrix under the relabelling
+ * null of st_mantel_codes, behind PERMANOVA and ANOSIM (compare.permanova, compare.anosim,
+ * SuchLinkedTrees.partner_group_differences).  Every sum is an exact integer, so "statistic_p >= statistic_0" is a
+ * comparison of integers on the caller's side.
+ *
+ * y holds the int32 codes of the matrix (st_mantel_quantise, or the doubled midranks minus (m + 1)), condensed in the
+ * project's triangle order: entry k = i (i - 1) / 2 + j is the pair (i, j), 0 <= j < i < n.  group[i] < n_groups <=
+ * ST_GROUP_MAX is the label of object i; a label that no object carries is allowed.  3 <= n <= ST_HOMMOLA_MAX_UNIVERSE.
+ *
+ * Permutations.  sigma_p = st_hommola_permutation(seed, node = stream, p, side = 0, n), p = 0 the identity: those of
+ * st_mantel_codes.  out holds (permutations + 1) x n_groups int64 values, row 0 the observation:
+ *     out[p][h] = sum over j < i with group[sigma_p(i)] == group[sigma_p(j)] == h of y[k(i, j)],
+ * |sum| < 2^58.  A row depends on (seed, stream, p, y, group) alone -- not on permutations, chunk_tasks, the device, the
+ * grid or the slice below; row p is the same for any permutations >= p.
+ *
+ * Checked (ST_ERR_ARG), in this order: n outside 3 .. ST_HOMMOLA_MAX_UNIVERSE, negative permutations, chunk_tasks or
+ * stream, more than 2^31 - 1 permutations, n_groups outside 1 .. ST_GROUP_MAX, a NULL y, group or out, then the first
+ * group[i] >= n_groups, named by its index; then a device below -1.  device = -1 computes every row on the host (no
+ * GPU); device >= 0 uploads y and the labels and runs the kernels: the same integers.  n <= 64: one wave per permutation,
+ * y in LDS.  Above: the labels are relabelled as bytes per permutation; one workgroup per (row pair r: rows r and
+ * n - 1 - r, slice of permutations) stages a row of y in LDS (4 n bytes) once for the slice and compares bytes; the rows'
+ * sums are folded by group per permutation on the device.  Only out crosses the link.  chunk_tasks: tasks per launch
+ * (permutations, or (row pair, slice) pairs above 64 objects), 0 = 2^20; a positive value also bounds the
+ * permutations whose sigma rows the device holds at once.  Device memory: 4 m bytes of y, one block of sigma rows (at
+ * most 64 MiB) and half as much of labels, at most 128 MiB of partial sums and 8 n_groups bytes per row of out; an
+ * allocation that fails is ST_ERR_NOMEM with the bytes asked for, before out is written.  The environment variable
+ * SUCHTREE_AMD_GROUP_SLICE = 1 .. 256 (read at every call) replaces the permutations per slice, for a measurement; no
+ * result depends on it.  No counterpart in the reference.
+ */
+#define ST_GROUP_MAX 256
+
+int st_group_sums_codes(int device, const int32_t *y, int32_t n, const uint8_t *group, int32_t n_groups, int64_t permutations,
+                        uint64_t seed, int32_t stream, int64_t chunk_tasks, int64_t *out);
 
 /*
  * Which clades of one tree are also in another, and how close is the best match where they are not: every induced clade

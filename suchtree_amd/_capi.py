@@ -49,7 +49,7 @@ SYMBOLS = (
     "st_hommola_permutation", "st_hommola_clades_host", "st_partner_dispersion_host", "st_dispersion_matrix",
     "st_unifrac_host", "st_unifrac_depths", "st_unifrac_quantise", "st_clade_ranges", "st_clade_match",
     "st_beta_dispersion_host", "st_beta_dispersion_matrix", "st_unifrac_null_host", "st_unifrac_null_depths",
-    "st_mantel_codes", "st_mantel_quantise",
+    "st_mantel_codes", "st_mantel_quantise", "st_group_sums_codes",
 )
 
 CLADE_RECT, CLADE_TRI = 0, 1     # include/suchtree_hip.h: ST_CLADE_RECT / ST_CLADE_TRI
@@ -321,7 +321,34 @@ def mantel_quantise(v, shift=None):
     return out, int(used.value)
 
 
-CLADE_MATCH_MAX_LEAVES = 1 << 18     # ST_CLADE_MATCH_MAX_LEAVES: leaves per list of st_clade_ranges / st_clade_match
+GROUP_MAX = 256     # ST_GROUP_MAX: labels of st_group_sums_codes are bytes
+
+
+def group_sums_codes(y, group, n_groups, permutations, seed=0, stream=0, device=-1, chunk_tasks=0):
+    """st_group_sums_codes: the int64 (permutations + 1, n_groups) sums of the condensed int32 codes ``y`` (n (n - 1) / 2,
+    pair (i, j) at i (i - 1) / 2 + j) over the pairs whose two objects carry label h under permutation p of the labels
+    ``group`` (n values below ``n_groups`` <= GROUP_MAX); row 0 is the observation.  ``device`` -1 = the host restatement
+    (no GPU), else the kernels on that device."""
+    g = np.asarray(group)
+    if g.ndim != 1:
+        raise ValueError("group must hold one label per object")
+    n = len(g)
+    if n and (g.min() < 0 or g.max() >= GROUP_MAX):
+        i = int(np.flatnonzero((g < 0) | (g >= GROUP_MAX))[0])
+        raise ValueError("group[%d] = %d: labels are 0 to %d" % (i, int(g[i]), GROUP_MAX - 1))
+    g = np.ascontiguousarray(g, dtype=np.uint8)
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    if y.ndim != 1 or len(y) != n * (n - 1) // 2:
+        raise ValueError("y must hold the %d pairs of %d objects" % (n * (n - 1) // 2, n))
+    _dispersion_args(permutations, stream, chunk_tasks)
+    n_groups = int(n_groups)
+    out = np.zeros((int(permutations) + 1, max(min(n_groups, GROUP_MAX), 0)), dtype=np.int64)
+    check(load().st_group_sums_codes(int(device), _arg(y), n, _arg(g), n_groups, int(permutations), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                     int(stream), int(chunk_tasks), _ptr(out) if out.size else None))
+    return out
+
+
+CLADE_MATCH_MAX_LEAVES = 1 << 18    # ST_CLADE_MATCH_MAX_LEAVES: leaves per list of st_clade_ranges / st_clade_match
 
 
 def clade_ranges(parent, leaf_ids, rooted=False):
@@ -619,6 +646,7 @@ def load():
         L.st_unifrac_quantise.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, ctypes.POINTER(ctypes.c_int32)]
         L.st_mantel_codes.argtypes = [i32, vp, vp, vp, ctypes.c_int32, i64, ctypes.c_uint64, ctypes.c_int32, i64, ctypes.POINTER(MantelMoments), vp]
         L.st_mantel_quantise.argtypes = [vp, i64, ctypes.c_int32, vp, ctypes.POINTER(ctypes.c_int32)]
+        L.st_group_sums_codes.argtypes = [i32, vp, ctypes.c_int32, vp, ctypes.c_int32, i64, ctypes.c_uint64, ctypes.c_int32, i64, vp]
         L.st_clade_ranges.argtypes = [vp, i64, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int32),
                                       ctypes.POINTER(i64)]
         L.st_clade_match.argtypes = [i32, ctypes.c_int32, vp, vp, vp, ctypes.c_int32, vp, vp, ctypes.c_int32, ctypes.c_int32, i64, vp, vp, vp]

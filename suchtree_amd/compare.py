@@ -1329,3 +1329,143 @@ def mantel(x, y, z=None, method="pearson", permutations=999, seed=None, alternat
     return MantelResult(corr_coeff=r0, p_value=p_value, n=n, n_pairs=m, method=method, alternative=alternative, permutations=permutations,
                         seed=seed, stream=stream, n_ge=int(n_ge), n_le=int(n_le), n_abs_ge=int(n_abs_ge), perm_stats=stats, partial=z is not None,
                         shift_x=shifts["x"], shift_y=shifts["y"], shift_z=shifts["z"], **sums)
+
+
+GROUP_TESTS = ("permanova", "anosim")
+
+
+class GroupTestResult:
+    """PERMANOVA or ANOSIM of a distance matrix against a grouping of its objects (permanova, anosim,
+    SuchLinkedTrees.partner_group_differences).
+
+    ``statistic`` is the pseudo-F of ``method`` "permanova" (with ``r2`` = 1 - SS_W / SS_T) or Clarke's R of "anosim"
+    (``r2`` None), ``p_value`` = (``n_ge`` + 1) / (``permutations`` + 1), ``n_ge`` the permutations whose statistic is
+    >= the observed one -- counted on exact integers.  ``n`` objects fall in ``n_groups`` groups of ``group_sizes``,
+    named by ``labels`` in the same order.  ``within_q`` holds the observed within-group sum of the int32 codes of each
+    group as Python ints (``shift``: the fixed point of the squared distances; None for ranks).  ``perm_stats`` is the
+    float64 statistic of each permutation in draw order with ``keep_stats=True``, else None.  ``seed`` repeats the run.
+    Unpacks as ``stat, p, n = result``.  ``leaves`` / ``names`` / ``measure`` / ``dropped`` are filled in by
+    ``partner_group_differences``.
+    """
+
+    def __init__(self, **kw):
+        self.leaves = self.names = self.measure = self.dropped = None
+        self.__dict__.update(kw)
+
+    def __iter__(self):
+        return iter((self.statistic, self.p_value, self.n))
+
+    def __repr__(self):
+        return "GroupTestResult(method=%r, statistic=%r, p_value=%r, n=%d, n_groups=%d, permutations=%d)" % (
+            self.method, self.statistic, self.p_value, self.n, self.n_groups, self.permutations)
+
+
+def group_codes(grouping, n):
+    """(labels in order of first appearance, the uint8 code of each of the ``n`` objects, group sizes).  ValueError for
+    a grouping that is not one label per object, one group, every object alone, or more than 256 groups."""
+    from . import _capi
+    grouping = list(grouping)
+    if len(grouping) != n:
+        raise ValueError("grouping holds %d labels for %d objects" % (len(grouping), n))
+    index = {}
+    codes = np.array([index.setdefault(g, len(index)) for g in grouping], dtype=np.int64)
+    a = len(index)
+    if a == 1:
+        raise ValueError("every object is in one group")
+    if a == n:
+        raise ValueError("every object is alone in its group")
+    if a > _capi.GROUP_MAX:
+        raise ValueError("%d groups: at most %d" % (a, _capi.GROUP_MAX))
+    return list(index), codes.astype(np.uint8), np.bincount(codes, minlength=a).tolist()
+
+
+def _ratio(num, den):
+    """num / den of Python ints as float64: inf, -inf or NaN where den is 0"""
+    if den == 0:
+        return float("nan") if num == 0 else math.copysign(float("inf"), num)
+    return num / den
+
+
+def group_weighted_sums(sums, weights, python_ints=None):
+    """[sum over the groups g of sums[p][g] * weights[g] for p] as Python ints: in int64 numpy where a groups of
+    |sum| < 2^58 times the largest weight stay below 2^63, else -- or with ``python_ints=True`` -- in Python ints."""
+    if python_ints is None:
+        python_ints = len(weights) * (1 << 58) * max(weights) >= (1 << 63)
+    if python_ints:
+        T = sums.astype(object) @ np.array(weights, dtype=object)
+    else:
+        T = sums @ np.array(weights, dtype=np.int64)
+    return [int(t) for t in T.tolist()]
+
+
+def _group_test(method, d, grouping, permutations, seed, stream, keep_stats, device, chunk_tasks):
+    from . import _capi
+    from .suchtree import int_arg, seed_arg
+    permutations, stream = int_arg("permutations", permutations, (1 << 31) - 1, "2^31 - 1"), int_arg("stream", stream, (1 << 31) - 1, "2^31 - 1")
+    chunk_tasks, seed = int_arg("chunk_tasks", chunk_tasks), seed_arg(seed)
+    v, n = mantel_condensed(d, "d")
+    labels, g, sizes = group_codes(grouping, n)
+    a, m = len(labels), n * (n - 1) // 2
+    n_within = sum(s * (s - 1) // 2 for s in sizes)
+    if method == "anosim" and (n_within == 0 or n_within == m):
+        raise ValueError("no within-group pair or no between-group pair")
+    if method == "permanova":
+        y, shift = _capi.mantel_quantise(v * v)
+    else:
+        y, shift = mantel_rank_codes(v), None
+    dev = -1 if device is None else 0 if device is ... else int_arg("device", device)
+    sums = _capi.group_sums_codes(y, g, a, permutations, seed, stream, dev, chunk_tasks)
+    r2 = None
+    if method == "permanova":
+        lcm = math.lcm(*sizes)
+        T = group_weighted_sums(sums, [lcm // s for s in sizes])      # L SS_W in code units
+        total = int(y.sum(dtype=np.int64))    # n SS_T
+        # F = ((SS_T - SS_W) / (a - 1)) / (SS_W / (n - a)), SS_T = total / n, SS_W = T / L: one division of integers
+        stat = lambda t: _ratio((total * lcm - t * n) * (n - a), (a - 1) * t * n)      # noqa: E731
+        r2 = _ratio(total * lcm - T[0] * n, total * lcm)
+        order = T
+    else:
+        S = [int(s) for s in sums.sum(axis=1).tolist()]
+        between = n_within * (m - n_within)
+        stat = lambda s: _ratio(-s, between)      # noqa: E731
+        order = S
+    statistic = stat(order[0])
+    n_ge = sum(t <= order[0] for t in order[1:])      # (the statistic falls strictly as the within-group sum rises)
+    stats = np.array([stat(t) for t in order[1:]], dtype=np.float64) if keep_stats else None
+    p_value = float("nan") if math.isnan(statistic) else (n_ge + 1) / (permutations + 1)
+    return GroupTestResult(statistic=statistic, p_value=p_value, n_ge=int(n_ge), n=n, n_groups=a, group_sizes=sizes, labels=labels,
+                           within_q=[int(s) for s in sums[0].tolist()], shift=shift, method=method, permutations=permutations, seed=seed,
+                           stream=stream, perm_stats=stats, r2=r2)
+
+
+def permanova(d, grouping, permutations=999, seed=None, stream=0, keep_stats=False, device=..., chunk_tasks=0):
+    """PERMANOVA (Anderson 2001; vegan's ``adonis2``, scikit-bio's ``permanova``): do the groups of ``grouping`` differ in
+    the distances ``d`` between their n objects, the permutations on the GPU.
+
+    ``d`` is a square symmetric matrix (the diagonal is ignored) or a condensed vector in the project's triangle order
+    k = i (i - 1) / 2 + j, j < i; 3 <= n <= 16384.  ``grouping`` holds one hashable label per object: at least two
+    groups, not every object alone, at most 256 groups.  The squared distances enter as fixed-point int32 codes (30 bits
+    of the largest).  Permutation p >= 1 relabels the objects by ``hommola_permutation(seed, stream, p, 0, n)`` -- the
+    permutations of ``mantel`` -- and the within-group sum of every group under every permutation is an exact integer
+    computed on ``device`` (... = device 0; None = on the host, without a GPU: the same integers).  With the sum of a
+    group divided by its size, L = the least common multiple of the sizes and T_p = sum over the groups of sum_g (L /
+    n_g), the pseudo-F falls strictly as the integer T_p rises, so ``n_ge`` counts T_p <= T_0: the counts behind the
+    p-value have no floating-point ties, and a relabelling that maps the groups onto themselves is counted, as it must
+    be.  The first k permutations are the same for any ``permutations`` >= k.  ``seed=None`` draws a seed and reports
+    it.  ``chunk_tasks`` bounds a launch (0 = 2^20 tasks); no result depends on it.  Returns a
+    :class:`GroupTestResult`.  An extension: the reference has no counterpart.
+    """
+    return _group_test("permanova", d, grouping, permutations, seed, stream, keep_stats, device, chunk_tasks)
+
+
+def anosim(d, grouping, permutations=999, seed=None, stream=0, keep_stats=False, device=..., chunk_tasks=0):
+    """ANOSIM (Clarke 1993; vegan's and scikit-bio's ``anosim``): are the distances ``d`` between groups of
+    ``grouping`` ranked above those within, the permutations on the GPU.
+
+    The arguments and the permutations are those of :func:`permanova`.  The distances enter as their midranks (ties
+    averaged, as scipy.stats.rankdata does), doubled and centred to int32 codes that sum to 0, so with S_p the sum of
+    the codes over the within-group pairs under permutation p, N_W within-group pairs and N_B between, R_p = -S_p /
+    (N_W N_B) is Clarke's (mean rank between - mean rank within) / (M / 2).  ``n_ge`` counts the integers S_p <= S_0: no
+    floating-point ties.  Returns a :class:`GroupTestResult`.  An extension: the reference has no counterpart.
+    """
+    return _group_test("anosim", d, grouping, permutations, seed, stream, keep_stats, device, chunk_tasks)

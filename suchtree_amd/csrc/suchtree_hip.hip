@@ -73,6 +73,10 @@
 // st_mantel_quantise): kernels_mantel.h (a wave form with the matrix in LDS, a row form that stages one matrix row in LDS
 // per workgroup, the fold), host_mantel.h (the loop over blocks and chunks) and, host-only, mantel_plan.cpp (the checks,
 // the invariant sums, the quantiser, the restatement).
+// The within-group sums of a distance matrix under the same relabelling null, behind PERMANOVA and ANOSIM
+// (st_group_sums_codes): kernels_group.h (a wave form with y in LDS; the relabelled labels as bytes, a row form that
+// stages a row of y in LDS once for a slice of permutations, the fold by group), host_group.h (the loop over blocks and chunks) and, host-only,
+// group_plan.cpp (the checks, the layout, the restatement).
 //
 // What the host side does: tree upload to one or several GPUs (tree_prep.cpp builds the tables, under a table budget
 // if one is given), the host path (host_pipe.h, host_copy.h: packed ids in through the copy engine, kernels write
@@ -200,6 +204,7 @@ static int device_index_arg(int device)
 #include "kernels_unifrac_null.h"
 #include "kernels_clade_match.h"
 #include "kernels_mantel.h"
+#include "kernels_group.h"
 
 
 // --------------------------------------------------------------------------
@@ -222,6 +227,7 @@ using namespace st;
 #include "host_unifrac_null.h"
 #include "host_clade_match.h"
 #include "host_mantel.h"
+#include "host_group.h"
 
 // the next link of st_link_sample_pairs (MuchTree.pyx:2946-2949)
 static int64_t link_draw(uint64_t &s, int64_t n_links)
@@ -1094,6 +1100,21 @@ try {
     std::string err;
     const int rc = mantel_quantise(v, n, shift_or_auto, out, out_shift, err);
     return rc == ST_OK ? ST_OK : fail(rc, err);
+} ST_CATCH_ALL
+
+int st_group_sums_codes(int device, const int32_t *y, int32_t n, const uint8_t *group, int32_t n_groups, int64_t permutations, uint64_t seed,
+                        int32_t stream, int64_t chunk_tasks, int64_t *out)
+try {
+    GroupPlan P;
+    std::string err;
+    const int rc = group_plan(y, n, group, n_groups, permutations, stream, chunk_tasks, group_slice(), out, P, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (device_or_host_arg(device) != ST_OK) return ST_ERR_ARG;
+    if (device < 0) {
+        group_host(y, group, P, seed, stream, out);
+        return ST_OK;
+    }
+    return group_device(device, P, y, group, seed, stream, out);
 } ST_CATCH_ALL
 
 int st_graph_matrices_host(int device, int64_t n, int64_t n_edges, const int32_t *u, const int32_t *v,

@@ -700,6 +700,88 @@ class SuchLinkedTrees:
         return out
 
     @staticmethod
+    def _row_groups(own, leaves, groups):
+        """The label of each row leaf of ``leaves`` under ``groups`` (None: in no group): a mapping from leaf name or id
+        to a label, or a sequence of node ids of ``own`` whose clades are the groups.  ValueError for clades that overlap."""
+        if hasattr(groups, "keys"):
+            ids = own.leaves
+            by_leaf = {(int(ids[k]) if isinstance(k, str) else int(k)): label for k, label in groups.items()}
+        else:
+            by_leaf = {}
+            for node in groups:
+                node = int(node)
+                for leaf in own.get_leaves(node).tolist():
+                    if leaf in by_leaf:
+                        raise ValueError("clades %d and %d overlap: both hold leaf %d (%s)" % (by_leaf[leaf], node, leaf, own.leaf_nodes[leaf]))
+                    by_leaf[leaf] = node
+        return [by_leaf.get(int(v)) for v in leaves]
+
+    def partner_group_differences(self, of="A", groups=None, measure="unifrac", test="permanova", permutations=999, seed=None, pool="subset",
+                                  min_partners=1, max_partners=None, exclude_shared=False, keep_stats=False, device=..., chunk_tasks=0):
+        """Do groups of leaves of one tree differ in their partners in the other?  PERMANOVA or ANOSIM of the distance
+        between the leaves' partner sets against a grouping of the leaves.
+
+        The rows and the ``measure`` between their partner sets are those of :meth:`phylosymbiosis`.  ``groups`` is a
+        mapping from leaf name or leaf id to a label, or a sequence of internal node ids of the row leaves' own tree: a
+        row then belongs to the listed clade that contains it, and listed clades that overlap are a ValueError that
+        names both.  Rows in no group are left out of the test and listed, as leaf ids, in ``result.dropped``.  A NaN in
+        the measure among the kept rows is a ValueError that names the pair.  ``test`` is "permanova" or "anosim";
+        ``permutations``, ``seed``, ``keep_stats`` and ``chunk_tasks`` are those of
+        :func:`~suchtree_amd.compare.permanova`, which relabels the kept rows on ``device`` (... = the row tree's
+        device; None = only the permutations run on the host: the matrix still comes from the trees' kernels).
+
+        The subset state, ``linklist`` and the generator of :meth:`sample_linked_distances` are left as they were.
+        Returns a :class:`~suchtree_amd.compare.GroupTestResult` with ``leaves`` (the kept rows' leaf ids), ``names``,
+        ``measure`` and ``dropped``.  An extension: the reference has no counterpart.
+        """
+        from . import compare
+        if measure not in self.PHYLOSYMBIOSIS_MEASURES:
+            raise ValueError("measure must be one of %s" % (self.PHYLOSYMBIOSIS_MEASURES,))
+        if test not in compare.GROUP_TESTS:
+            raise ValueError("test must be one of %s" % (compare.GROUP_TESTS,))
+        if of not in ("A", "B"):
+            raise ValueError("of must be 'A' or 'B'")
+        if groups is None:
+            raise ValueError("groups: a mapping from leaf to label, or a sequence of node ids")
+        int_arg("permutations", permutations, (1 << 31) - 1, "2^31 - 1")
+        int_arg("chunk_tasks", chunk_tasks)
+        seed = seed_arg(seed)
+        own, _, _, row_leaves, _ = self._partner_rows(of, int_arg("min_partners", min_partners, optional=True),
+                                                      int_arg("max_partners", max_partners, optional=True))
+        labels = self._row_groups(own, row_leaves, groups)      # (before anything is launched)
+        keep = np.array([k for k, g in enumerate(labels) if g is not None], dtype=np.int64)
+        grouping = [labels[k] for k in keep.tolist()]
+        if len(keep) < 3:
+            raise ValueError("%d rows in a group: at least 3" % len(keep))
+        compare.group_codes(grouping, len(keep))
+        by_distance = measure in ("beta_mpd", "beta_mntd")
+
+        def run(partner, sets, root, universe):
+            if len(sets) > _capi.HOMMOLA_MAX_UNIVERSE:
+                raise ValueError("%d rows: at most %d" % (len(sets), _capi.HOMMOLA_MAX_UNIVERSE))
+            if by_distance:
+                return partner.beta_dispersion(sets, universe=universe, exclude_shared=exclude_shared, permutations=0, seed=0, stream=root)
+            return partner.unifrac(sets, root=root)
+        observed = self._over_partner_rows(of, min_partners, max_partners, run, pool, _capi.HOMMOLA_MAX_UNIVERSE if by_distance else None)
+        y = np.asarray(getattr(observed, measure), dtype=np.float64)
+        i, j = np.tril_indices(len(keep), -1)
+        ki, kj = keep[i], keep[j]      # (keep is increasing: ki > kj)
+        sub = y[ki * (ki - 1) // 2 + kj]
+        bad = np.flatnonzero(np.isnan(sub))
+        if len(bad):
+            a, b = int(ki[bad[0]]), int(kj[bad[0]])
+            raise ValueError("%s of rows %d and %d (%s, %s) is NaN" % (measure, a, b, observed.names[a], observed.names[b]))
+        fn = compare.permanova if test == "permanova" else compare.anosim
+        out = fn(sub, grouping, permutations=permutations, seed=seed, keep_stats=keep_stats, device=own._device if device is ... else device,
+                 chunk_tasks=chunk_tasks)
+        kept = set(keep.tolist())
+        out.leaves = observed.leaves[keep]
+        out.names = [observed.names[k] for k in keep.tolist()]
+        out.dropped = np.array([int(v) for k, v in enumerate(observed.leaves.tolist()) if k not in kept], dtype=np.int64)
+        out.measure = measure
+        return out
+
+    @staticmethod
     def _leaf_counts(tree: SuchTree) -> np.ndarray:
         """Leaves under every node (st_clade_plan)."""
         return _capi.clade_plan(tree._flat.parent, np.empty(0, dtype=np.int64))["leaves"]
