@@ -705,15 +705,18 @@ class Census(dict):
         return 0
 
 
-def case_rng(family, seed, c):
-    return np.random.default_rng([int(seed), FAMILIES.index(family), int(c)])
+def case_rng(family, seed, c, families=FAMILIES):
+    return np.random.default_rng([int(seed), families.index(family), int(c)])
 
 
 def describe(case):
-    """every drawn argument on one line: scalars as they are, sets by their sizes, other arrays by their lengths"""
+    """every drawn argument on one line: scalars as they are, sets by their sizes, other arrays by their lengths.  A key
+    that begins with "_" is skipped: it is for what a family derives from its draws and keeps in the case (a layout, the
+    oracle's columns), never for a drawn argument, which would then be missing from the replay line.  No family of this
+    module has such a key."""
     out = []
     for k, v in case.items():
-        if k == "env":
+        if k == "env" or k.startswith("_"):
             continue
         if k == "sets":
             v = [len(s) for s in v]
@@ -723,16 +726,21 @@ def describe(case):
     return " ".join(out) + " env " + " ".join("%s=%s" % (k.replace("SUCHTREE_AMD_", ""), v) for k, v in case["env"].items())
 
 
-def census(family, seed, cases, layer):
+def _tables(tables):
+    """the family tables of a fuzz module (FAMILIES, LAYERS, DRAW, CENSUS, CHECK, REQUIRED): this module's by default"""
+    return tables or sys.modules[__name__]
+
+
+def census(family, seed, cases, layer, tables=None):
     """what a session would reach, from the draws alone: no library call but st_clade_ranges (clade, host only), no GPU"""
-    C = Census()
+    T, C = _tables(tables), Census()
     for c in range(cases):
-        CENSUS[family](DRAW[family](case_rng(family, seed, c), LAYERS[layer]), C)
+        T.CENSUS[family](T.DRAW[family](case_rng(family, seed, c, T.FAMILIES), T.LAYERS[layer]), C)
     return C
 
 
-def missing(family, C, layer):
-    return [k for k in REQUIRED[layer][family] if not C[k]]
+def missing(family, C, layer, tables=None):
+    return [k for k in _tables(tables).REQUIRED[layer][family] if not C[k]]
 
 
 def _setenv(name, value):
@@ -742,24 +750,26 @@ def _setenv(name, value):
         os.environ[name] = value
 
 
-def run(family, seed, cases, layer, setenv=_setenv, first=0, require=True):
+def run(family, seed, cases, layer, setenv=_setenv, first=0, require=True, tables=None):
     """One session of `cases` cases; returns its census.  A mismatch prints one line with everything needed to repeat it
-    and raises; so does an entry that refuses its arguments, and a census without one of REQUIRED."""
-    L, C = LAYERS[layer], Census()
+    and raises; so does an entry that refuses its arguments, and a census without one of REQUIRED.  `tables`: another
+    module's families (tests/fuzz_compare.py) under the same rules."""
+    T = _tables(tables)
+    L, C = T.LAYERS[layer], Census()
     for c in range(first, first + cases):
-        rng = case_rng(family, seed, c)
-        case = DRAW[family](rng, L)
-        CENSUS[family](case, C)
+        rng = case_rng(family, seed, c, T.FAMILIES)
+        case = T.DRAW[family](rng, L)
+        T.CENSUS[family](case, C)
         for name, value in case["env"].items():
             setenv(name, value)
         try:
-            bad = CHECK[family](case, rng, L)
+            bad = T.CHECK[family](case, rng, L)
         except Exception as e:      # noqa: BLE001 -- the generator draws only what an entry accepts
             bad = "raised %s: %s" % (type(e).__name__, str(e)[:300])
         if bad:
             print("MISMATCH family %s seed %d case %d layer %s: %s: %s" % (family, seed, c, layer, describe(case), bad), flush=True)
             raise AssertionError("fuzz mismatch, family %s seed %d case %d (see the line above): %s" % (family, seed, c, bad))
-    gone = missing(family, C, layer) if require else []
+    gone = missing(family, C, layer, tables) if require else []
     assert not gone, "family %s seed %d, %d cases, layer %s never reached: %s" % (family, seed, cases, layer, gone)
     return C
 
