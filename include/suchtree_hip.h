@@ -53,7 +53,7 @@ extern "C" {
  *      and st_clade_match; then, also additive, st_beta_dispersion_host and st_beta_dispersion_matrix; then, also additive,
  *      st_unifrac_null_host and st_unifrac_null_depths; then, also additive, struct st_mantel_sums, struct st_mantel_moments,
  *      ST_MANTEL_SHIFT_AUTO, st_mantel_codes and st_mantel_quantise; then, also additive, ST_GROUP_MAX and
- *      st_group_sums_codes.
+ *      st_group_sums_codes; then, also additive, struct st_parafit_sum and st_parafit_codes.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -839,6 +839,60 @@ int st_mantel_quantise(const double *v, int64_t n, int32_t shift_or_auto, int32_
 
 int st_group_sums_codes(int device, const int32_t *y, int32_t n, const uint8_t *group, int32_t n_groups, int64_t permutations,
                         uint64_t seed, int32_t stream, int64_t chunk_tasks, int64_t *out);
+
+/*
+ * Which links of a host-guest system carry its cophylogenetic signal: ParaFit's global statistic and ParaFitLink1 of every
+ * link (Legendre, Desdevises & Bazin 2002), with their permutation counts (compare.parafit, SuchLinkedTrees.parafit).
+ * Every sum is an exact integer, so every "statistic_p >= statistic_0" is a comparison of integers.
+ *
+ * Sides.  The links join an F (held) universe of n_f positions and an S (shuffled) universe of n_s positions.  g_f and
+ * g_s are the square Gower-centred matrices G = -1/2 J D2 J of the two sides as int32 codes (st_mantel_quantise, a shift
+ * per matrix), C order, both triangles equal, the diagonal meaningful.  Link l is (link_f[l], link_s[l]); the links are
+ * strictly increasing in (f, s) order, so the links of one F position are one range.  3 <= n_f, n_s, n_links <=
+ * ST_HOMMOLA_MAX_UNIVERSE.
+ *
+ * The identity.  With principal coordinates C C^T = g_s, B B^T = g_f and the link matrix A, ParaFitGlobal =
+ * || C^T A B ||_F^2 = sum over links l, k of T[l][k], T[l][k] = g_f[f_l][f_k] * g_s[s_l][s_k]; removing link l lowers
+ * it by ParaFitLink1(l) = 2 * (row sum of T at l) - T[l][l].  No eigendecomposition is needed.  Where a matrix has
+ * negative eigenvalues their axes enter with their sign.
+ *
+ * Permutations.  Permutation p >= 1 redraws, for every F position i with links separately, its partners among the S
+ * positions: sigma_{p,i} = st_hommola_permutation(seed, node = stream_f[i], p, side = 0, n_s), and link l = (f_l, s_l)
+ * becomes (f_l, r_p(l)), r_p(l) = sigma_{p,f_l}[s_l].  The links of one F position keep distinct images; different F
+ * positions draw independently (give them different stream ids).  p = 0 is the observation.  With T_p over the relabelled links:
+ *     total[p]          = sum of T_p (|total| < 2^90),
+ *     Link1_p(l)        = 2 * (row sum of T_p at l) - T_p[l][l]: the statistic of the relabelled link l in the relabelled system,
+ *     link_obs[l]       = Link1_0(l),
+ *     link_n_ge[l]      = the number of p >= 1 with Link1_p(l) >= Link1_0(l) (a tie is counted),
+ *     link_all[p][l]    = Link1_p(l) for all permutations + 1 rows, where link_all is not NULL,
+ * each sum a 128-bit two's-complement integer in a lo / hi pair.  A value depends on (seed, stream_f, p, the matrices, the
+ * links) alone -- not on permutations, chunk_tasks, the kernel form, the grid or the device; row p is the same for any
+ * permutations >= p.  ParaFitLink2 is not computed.
+ *
+ * Checked (ST_ERR_ARG), in this order: n_f, n_s, n_links outside 3 .. ST_HOMMOLA_MAX_UNIVERSE; negative permutations or
+ * chunk_tasks; more than 2^31 - 1 permutations; a NULL g_f, g_s, link_f, link_s or stream_f; a NULL total, link_obs or
+ * link_n_ge; link by link an F position, then an S position outside its universe, then a link that is not above the one
+ * before (unsorted or repeated), each naming the link; the first negative stream_f[i], naming i; a g_f, then a g_s that
+ * is not symmetric, naming the first cell (in row-major order) whose mirror differs; then a device below -1.
+ * device = -1 computes everything on the host (no GPU); device >= 0 uploads both matrices and runs the kernels: the same
+ * integers.  n_links <= 64 and n_s <= 64: one wave per permutation, g_s and the expanded held side in LDS.  Otherwise the
+ * held side is expanded once to P[l][k] = g_f[f_l][f_k] (4 n_links^2 bytes) and one workgroup per (permutation, link)
+ * stages row r_p(l) of g_s in LDS (4 n_s bytes).  Counts and totals are folded on the device per block of
+ * permutations; total, link_obs and link_n_ge cross the link once, link_all block by block.  chunk_tasks: tasks
+ * (permutations, or (permutation, link) pairs) per launch, 0 = 2^20; a positive value also bounds the permutations a
+ * block holds.  Device memory: 4 n_f^2 + 4 n_s^2 + 4 n_links^2 bytes, a block of relabelled positions (at most 64 MiB)
+ * and of link records (at most 128 MiB), 16 bytes per total; an allocation that fails is ST_ERR_NOMEM with the bytes
+ * asked for, before any output is written.  No counterpart in the reference.
+ */
+typedef struct st_parafit_sum {
+    uint64_t lo;
+    int64_t hi;
+} st_parafit_sum;
+
+int st_parafit_codes(int device, const int32_t *g_f, int32_t n_f, const int32_t *g_s, int32_t n_s, const int32_t *link_f,
+                     const int32_t *link_s, int32_t n_links, const int32_t *stream_f, int64_t permutations, uint64_t seed,
+                     int64_t chunk_tasks, st_parafit_sum *total, st_parafit_sum *link_obs, int64_t *link_n_ge,
+                     st_parafit_sum *link_all);
 
 /*
  * Which clades of one tree are also in another, and how close is the best match where they are not: every induced clade

@@ -49,7 +49,7 @@ SYMBOLS = (
     "st_hommola_permutation", "st_hommola_clades_host", "st_partner_dispersion_host", "st_dispersion_matrix",
     "st_unifrac_host", "st_unifrac_depths", "st_unifrac_quantise", "st_clade_ranges", "st_clade_match",
     "st_beta_dispersion_host", "st_beta_dispersion_matrix", "st_unifrac_null_host", "st_unifrac_null_depths",
-    "st_mantel_codes", "st_mantel_quantise", "st_group_sums_codes",
+    "st_mantel_codes", "st_mantel_quantise", "st_group_sums_codes", "st_parafit_codes",
 )
 
 CLADE_RECT, CLADE_TRI = 0, 1     # include/suchtree_hip.h: ST_CLADE_RECT / ST_CLADE_TRI
@@ -346,6 +346,50 @@ def group_sums_codes(y, group, n_groups, permutations, seed=0, stream=0, device=
     check(load().st_group_sums_codes(int(device), _arg(y), n, _arg(g), n_groups, int(permutations), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                      int(stream), int(chunk_tasks), _ptr(out) if out.size else None))
     return out
+
+
+# st_parafit_sum as a numpy record
+PARAFIT_SUM = np.dtype([("lo", np.uint64), ("hi", np.int64)])
+
+
+def parafit_ints(records):
+    """The 128-bit sums of an array of PARAFIT_SUM as a (nested) list of Python ints, in the array's shape."""
+    lo, hi = records["lo"].ravel().tolist(), records["hi"].ravel().tolist()
+    flat = [(h << 64) + l for l, h in zip(lo, hi)]
+    if records.ndim == 2:
+        w = records.shape[1]
+        return [flat[r * w:(r + 1) * w] for r in range(records.shape[0])]
+    return flat
+
+
+def parafit_codes(g_f, g_s, link_f, link_s, stream_f, permutations=0, seed=0, device=-1, chunk_tasks=0, keep=False):
+    """st_parafit_codes: (total, link_obs, link_n_ge, link_all) of the square int32 code matrices ``g_f`` (n_f, n_f) and
+    ``g_s`` (n_s, n_s), the links (``link_f[l]``, ``link_s[l]``) as positions, strictly increasing in (f, s) order, and
+    one stream id per F position: ``total`` the permutations + 1 records of PARAFIT_SUM, ``link_obs`` one per link,
+    ``link_n_ge`` int64 per link and, with ``keep``, ``link_all`` of shape (permutations + 1, L), else None.  ``device``
+    -1 = the host restatement (no GPU), else the kernels on that device."""
+    g_f = np.ascontiguousarray(g_f, dtype=np.int32)
+    g_s = np.ascontiguousarray(g_s, dtype=np.int32)
+    for name, g in (("g_f", g_f), ("g_s", g_s)):
+        if g.ndim != 2 or g.shape[0] != g.shape[1]:
+            raise ValueError("%s must be a square matrix" % name)
+    link_f = np.ascontiguousarray(link_f, dtype=np.int32)
+    link_s = np.ascontiguousarray(link_s, dtype=np.int32)
+    stream_f = np.ascontiguousarray(stream_f, dtype=np.int32)
+    if link_f.ndim != 1 or link_s.shape != link_f.shape:
+        raise ValueError("link_f and link_s must be 1-D and of one length")
+    if stream_f.shape != (g_f.shape[0],):
+        raise ValueError("stream_f must hold one stream id per F position")
+    _dispersion_args(permutations, 0, chunk_tasks)
+    L, R = len(link_f), int(permutations) + 1
+    total = np.zeros(R, dtype=PARAFIT_SUM)
+    link_obs = np.zeros(L, dtype=PARAFIT_SUM)
+    link_n_ge = np.zeros(L, dtype=np.int64)
+    link_all = np.zeros((R, L), dtype=PARAFIT_SUM) if keep else None
+    check(load().st_parafit_codes(int(device), _ptr(g_f), int(g_f.shape[0]), _ptr(g_s), int(g_s.shape[0]), _arg(link_f), _arg(link_s), L,
+                                  _arg(stream_f), int(permutations), int(seed) & 0xFFFFFFFFFFFFFFFF, int(chunk_tasks), _ptr(total), _arg(link_obs),
+                                  _arg(link_n_ge), _ptr(link_all) if keep else None))
+    return total, link_obs, link_n_ge, link_all
 
 
 CLADE_MATCH_MAX_LEAVES = 1 << 18    # ST_CLADE_MATCH_MAX_LEAVES: leaves per list of st_clade_ranges / st_clade_match
@@ -647,6 +691,7 @@ def load():
         L.st_mantel_codes.argtypes = [i32, vp, vp, vp, ctypes.c_int32, i64, ctypes.c_uint64, ctypes.c_int32, i64, ctypes.POINTER(MantelMoments), vp]
         L.st_mantel_quantise.argtypes = [vp, i64, ctypes.c_int32, vp, ctypes.POINTER(ctypes.c_int32)]
         L.st_group_sums_codes.argtypes = [i32, vp, ctypes.c_int32, vp, ctypes.c_int32, i64, ctypes.c_uint64, ctypes.c_int32, i64, vp]
+        L.st_parafit_codes.argtypes = [i32, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, ctypes.c_int32, vp, i64, ctypes.c_uint64, i64, vp, vp, vp, vp]
         L.st_clade_ranges.argtypes = [vp, i64, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int32),
                                       ctypes.POINTER(i64)]
         L.st_clade_match.argtypes = [i32, ctypes.c_int32, vp, vp, vp, ctypes.c_int32, vp, vp, ctypes.c_int32, ctypes.c_int32, i64, vp, vp, vp]

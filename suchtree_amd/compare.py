@@ -1469,3 +1469,156 @@ def anosim(d, grouping, permutations=999, seed=None, stream=0, keep_stats=False,
     floating-point ties.  Returns a :class:`GroupTestResult`.  An extension: the reference has no counterpart.
     """
     return _group_test("anosim", d, grouping, permutations, seed, stream, keep_stats, device, chunk_tasks)
+
+
+PARAFIT_TRANSFORMS = ("sqrt", "none")
+
+
+class ParaFitResult:
+    """ParaFit (Legendre, Desdevises & Bazin 2002): the global test of cophylogeny and ParaFitLink1 of every link
+    (parafit, SuchLinkedTrees.parafit).
+
+    ``statistic`` is ParaFitGlobal, the trace of (C^T A B)(C^T A B)^T with B and C the principal coordinates of the two
+    sides and A the link matrix, and ``p_value`` = (``n_ge`` + 1) / (``permutations`` + 1), ``n_ge`` counting the
+    permutations whose trace is >= the observed one.  Both centred matrices enter as int32 codes (``shift_f``,
+    ``shift_s``: the fixed point of the held and the shuffled side), so ``trace_q`` and ``link_stat_q`` are exact Python
+    ints -- the float statistics are these times 2^-(shift_f + shift_s) -- and every count compares integers: a
+    relabelling that maps the links onto themselves ties and is counted.
+
+    Per link, in the order the links were given: ``link_stat`` is ParaFitLink1, the trace minus the trace without that
+    link; ``link_n_ge`` counts the permutations p in which the statistic of the *relabelled* link l in the relabelled
+    system, Link1_p(l), is >= the observed Link1_0(l), and ``link_p`` = (``link_n_ge`` + 1) / (``permutations`` + 1).
+    This is this library's definition of the link test; it is not claimed to equal the link p-values of ape's
+    ``parafit``.  ``link_f`` / ``link_s`` are the links' positions; ``link_a`` / ``link_b`` (TreeA / TreeB leaf ids)
+    and ``link_names`` are filled in by ``SuchLinkedTrees.parafit``, as is ``shuffle``.  With ``test_links=False`` the
+    two link-test fields are None.  With ``keep_stats=True``, ``perm_stats`` is the float64 trace of each permutation
+    in draw order and ``perm_link_stats`` the (permutations, n_links) Link1_p values; else both are None.
+    ``transform`` is "sqrt" (the distances themselves are centred) or "none" (the squared distances).  ``seed``
+    repeats the run.  Unpacks as ``stat, p, n = result`` with n = ``n_links``.
+    """
+
+    def __init__(self, **kw):
+        self.shuffle = self.link_a = self.link_b = self.link_names = None
+        self.__dict__.update(kw)
+
+    def __iter__(self):
+        return iter((self.statistic, self.p_value, self.n_links))
+
+    def __len__(self):
+        return self.n_links
+
+    def __repr__(self):
+        return "ParaFitResult(statistic=%r, p_value=%r, n_links=%d, transform=%r, permutations=%d)" % (
+            self.statistic, self.p_value, self.n_links, self.transform, self.permutations)
+
+    def row(self, l) -> dict:
+        """The fields of link ``l`` as a dict."""
+        l = range(self.n_links)[l]
+        out = {"link_f": int(self.link_f[l]), "link_s": int(self.link_s[l]), "link_stat": float(self.link_stat[l]), "link_stat_q": self.link_stat_q[l]}
+        for k in ("link_a", "link_b", "link_n_ge", "link_p"):
+            v = getattr(self, k)
+            if v is not None:
+                out[k] = v[l].item()
+        if self.link_names is not None:
+            out["link_names"] = self.link_names[l]
+        return out
+
+    def to_dataframe(self):
+        """One row per link (pandas)."""
+        import pandas as pd
+        cols = {k: getattr(self, k) for k in ("link_a", "link_b", "link_f", "link_s", "link_stat", "link_n_ge", "link_p") if getattr(self, k) is not None}
+        if self.link_names is not None:
+            cols["name_a"], cols["name_b"] = [a for a, _ in self.link_names], [b for _, b in self.link_names]
+        return pd.DataFrame(cols)
+
+
+def parafit_centre(d, n, transform="sqrt"):
+    """The float64 (n, n) Gower-centred matrix G = -1/2 J D2 J of the condensed distances ``d`` (triangle order): D2 is
+    the distance itself with ``transform="sqrt"`` (the square root of the distances is what gets embedded) and its
+    square with "none".  The lower triangle is mirrored, so G is symmetric bit for bit."""
+    d2 = np.zeros((n, n), dtype=np.float64)
+    i, j = np.tril_indices(n, -1)
+    v = np.asarray(d, dtype=np.float64)
+    d2[i, j] = d2[j, i] = v if transform == "sqrt" else v * v
+    rows = d2.mean(axis=1)
+    g = -0.5 * (d2 - rows[:, None] - rows[None, :] + d2.mean())
+    g[j, i] = g[i, j]
+    return g
+
+
+def parafit(d_f, d_s, links, permutations=999, seed=None, shuffle_streams=None, transform="sqrt", test_links=True, keep_stats=False, device=...,
+            chunk_tasks=0):
+    """ParaFit of two distance matrices joined by links: the global statistic with its permutation test and
+    ParaFitLink1 of every link with its own, in one pass over the link pairs on the GPU.
+
+    ``d_f`` (the held side F) and ``d_s`` (the shuffled side S) are square symmetric matrices or condensed vectors, read
+    as :func:`mantel` reads them; ``links`` is an (L, 2) array of (F position, S position), 3 to 16384 distinct links.
+    Each matrix is Gower-centred in float64 on the host (G = -1/2 J D2 J) and quantised to int32 codes with a shift of
+    its own.  With principal coordinates C C^T = G_s and B B^T = G_f, ParaFitGlobal = ||C^T A B||_F^2 is the sum of
+    T[l][k] = G_f[f_l][f_k] G_s[s_l][s_k] over all link pairs, and ParaFitLink1(l) = 2 (row sum of T at l) - T[l][l]: no
+    eigendecomposition is made.  ``transform="sqrt"`` (default) takes D2 = the distances themselves -- the embedding
+    of their square roots (de Vienne et al. 2011), Euclidean for a tree metric, so the statistic is the PCoA definition's
+    exactly; ``"none"`` takes D2 = the squared distances, and axes with negative eigenvalues enter with their sign (as
+    vegan's ``betadisper`` treats them; ape's ``parafit`` drops them instead, so the two differ there).
+
+    Permutation p >= 1 is Legendre's null: for every F position i with links separately, its partners are redrawn among
+    the S positions -- ``sigma = hommola_permutation(seed, shuffle_streams[i], p, 0, n_s)``, link (f, s) becomes
+    (f, sigma[s]).  Links of one F position keep distinct images; ``shuffle_streams`` (default: the F positions
+    themselves) gives every F position its stream.  The link test compares Link1_p(l), the statistic of the relabelled
+    link l in the relabelled system, with the observed Link1_0(l): see :class:`ParaFitResult`; it is not claimed to equal
+    ape's link p-values.  All sums are exact integers computed on ``device`` (... = device 0; None = on the host, without
+    a GPU: the same integers), the first k permutations are the same for any ``permutations`` >= k, and nothing depends on
+    ``chunk_tasks`` (tasks per launch, 0 = 2^20).  ``seed=None`` draws a seed and reports it.  ParaFitLink2 is not
+    computed.  An extension: the reference has no counterpart.
+    """
+    from . import _capi
+    from .suchtree import int_arg, seed_arg
+    if transform not in PARAFIT_TRANSFORMS:
+        raise ValueError("transform must be one of %s" % (PARAFIT_TRANSFORMS,))
+    permutations = int_arg("permutations", permutations, (1 << 31) - 1, "2^31 - 1")
+    chunk_tasks, seed = int_arg("chunk_tasks", chunk_tasks), seed_arg(seed)
+    v_f, n_f = mantel_condensed(d_f, "d_f")
+    v_s, n_s = mantel_condensed(d_s, "d_s")
+    links = np.asarray(links)
+    if links.ndim != 2 or links.shape[1] != 2 or links.dtype.kind not in "iu":
+        raise ValueError("links must be an (L, 2) integer array of (F position, S position)")
+    L = int(links.shape[0])
+    if L < 3 or L > _capi.HOMMOLA_MAX_UNIVERSE:
+        raise ValueError("%d links: 3 to %d" % (L, _capi.HOMMOLA_MAX_UNIVERSE))
+    links = links.astype(np.int64)
+    for col, n, side in ((0, n_f, "F"), (1, n_s, "S")):
+        bad = np.flatnonzero((links[:, col] < 0) | (links[:, col] >= n))
+        if len(bad):
+            raise ValueError("link %d: the %s position %d is outside the universe of %d" % (int(bad[0]), side, int(links[bad[0], col]), n))
+    order = np.lexsort((links[:, 1], links[:, 0]))
+    srt = links[order]
+    same = np.flatnonzero((srt[1:] == srt[:-1]).all(axis=1))
+    if len(same):
+        raise ValueError("links %d and %d are the same link" % tuple(sorted((int(order[same[0]]), int(order[same[0] + 1])))))
+    if shuffle_streams is None:
+        streams = np.arange(n_f, dtype=np.int64)
+    else:
+        streams = np.asarray(shuffle_streams)
+        if streams.shape != (n_f,) or streams.dtype.kind not in "iu" or (streams.astype(np.int64) < 0).any() or (streams.astype(np.int64) > 0x7FFFFFFF).any():
+            raise ValueError("shuffle_streams must hold one non-negative int32 per F position")
+    q_f, shift_f = _capi.mantel_quantise(parafit_centre(v_f, n_f, transform))
+    q_s, shift_s = _capi.mantel_quantise(parafit_centre(v_s, n_s, transform))
+    dev = -1 if device is None else 0 if device is ... else int_arg("device", device)
+    total, obs, n_ge_l, every = _capi.parafit_codes(q_f, q_s, srt[:, 0], srt[:, 1], streams, permutations, seed, dev, chunk_tasks, keep=keep_stats)
+    back = np.empty(L, dtype=np.int64)      # the caller's link k is sorted link back[k]
+    back[order] = np.arange(L)
+    scale = -(shift_f + shift_s)
+    trace = _capi.parafit_ints(total)
+    link_q = [_capi.parafit_ints(obs)[k] for k in back.tolist()]
+    n_ge = sum(t >= trace[0] for t in trace[1:])
+    perm_stats = perm_link_stats = None
+    if keep_stats:
+        perm_stats = np.array([math.ldexp(float(t), scale) for t in trace[1:]], dtype=np.float64)
+        rows = _capi.parafit_ints(every[1:]) if permutations else []
+        perm_link_stats = np.array([[math.ldexp(float(r[k]), scale) for k in back.tolist()] for r in rows], dtype=np.float64).reshape(permutations, L)
+    return ParaFitResult(statistic=math.ldexp(float(trace[0]), scale), p_value=(n_ge + 1) / (permutations + 1), n_ge=int(n_ge), trace_q=trace[0],
+                         perm_trace_q=trace[1:], shift_f=shift_f, shift_s=shift_s, n_links=L, n_f=n_f, n_s=n_s, permutations=permutations, seed=seed,
+                         transform=transform, link_f=links[:, 0].copy(), link_s=links[:, 1].copy(), link_stat_q=link_q,
+                         link_stat=np.array([math.ldexp(float(v), scale) for v in link_q], dtype=np.float64),
+                         link_n_ge=n_ge_l[back].copy() if test_links else None,
+                         link_p=(n_ge_l[back] + 1) / (permutations + 1) if test_links else None, perm_stats=perm_stats, perm_link_stats=perm_link_stats)

@@ -8,7 +8,7 @@
 namespace st {
 
 // the first cell (i, j), j < i, whose mirror differs, scanned in tiles (the mirror of a row is a column); false: none
-static bool mantel_asymmetric(const int32_t *x, int64_t n, int64_t &bad_i, int64_t &bad_j)
+bool mantel_asymmetric(const int32_t *x, int64_t n, int64_t &bad_i, int64_t &bad_j)
 {
     constexpr int64_t T = 64;
     bool found = false;

@@ -46,6 +46,9 @@ inline st_mantel_sums mantel_sums(i128 xy, i128 xz)
 int mantel_plan(const int32_t *x_sq, const int32_t *y, const int32_t *z, int32_t n, int64_t permutations, int32_t stream, int64_t chunk_tasks,
                 st_mantel_moments *moments, const st_mantel_sums *out, MantelPlan &P, std::string &err);
 
+// the first cell (row-major) of the square matrix x whose mirror differs; false: x is symmetric (parafit_plan.cpp shares it)
+bool mantel_asymmetric(const int32_t *x, int64_t n, int64_t &bad_i, int64_t &bad_j);
+
 // the sums of x relabelled by sigma[0 .. n) against y and, where z is not NULL, z
 void mantel_record(const int32_t *x_sq, const int32_t *y, const int32_t *z, int32_t n, const int32_t *sigma, i128 &sxy, i128 &sxz);
 

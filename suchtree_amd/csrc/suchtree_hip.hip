@@ -77,6 +77,10 @@
 // (st_group_sums_codes): kernels_group.h (a wave form with y in LDS; the relabelled labels as bytes, a row form that
 // stages a row of y in LDS once for a slice of permutations, the fold by group), host_group.h (the loop over blocks and chunks) and, host-only,
 // group_plan.cpp (the checks, the layout, the restatement).
+// ParaFit's global statistic and ParaFitLink1 of every host-guest link as exact sums over link pairs (st_parafit_codes):
+// kernels_parafit.h (the held side expanded once, one sort per permutation and linked leaf, a wave form with both sides in
+// LDS, a row form that stages one matrix row in LDS per workgroup, the fold with the per-link counts), host_parafit.h (the
+// loop over blocks and chunks) and, host-only, parafit_plan.cpp (the checks, the layout, the restatement).
 //
 // What the host side does: tree upload to one or several GPUs (tree_prep.cpp builds the tables, under a table budget
 // if one is given), the host path (host_pipe.h, host_copy.h: packed ids in through the copy engine, kernels write
@@ -205,6 +209,7 @@ static int device_index_arg(int device)
 #include "kernels_clade_match.h"
 #include "kernels_mantel.h"
 #include "kernels_group.h"
+#include "kernels_parafit.h"
 
 
 // --------------------------------------------------------------------------
@@ -228,6 +233,7 @@ using namespace st;
 #include "host_clade_match.h"
 #include "host_mantel.h"
 #include "host_group.h"
+#include "host_parafit.h"
 
 // the next link of st_link_sample_pairs (MuchTree.pyx:2946-2949)
 static int64_t link_draw(uint64_t &s, int64_t n_links)
@@ -1115,6 +1121,22 @@ try {
         return ST_OK;
     }
     return group_device(device, P, y, group, seed, stream, out);
+} ST_CATCH_ALL
+
+int st_parafit_codes(int device, const int32_t *g_f, int32_t n_f, const int32_t *g_s, int32_t n_s, const int32_t *link_f, const int32_t *link_s,
+                     int32_t n_links, const int32_t *stream_f, int64_t permutations, uint64_t seed, int64_t chunk_tasks, st_parafit_sum *total,
+                     st_parafit_sum *link_obs, int64_t *link_n_ge, st_parafit_sum *link_all)
+try {
+    ParafitPlan P;
+    std::string err;
+    const int rc = parafit_plan(g_f, n_f, g_s, n_s, link_f, link_s, n_links, stream_f, permutations, chunk_tasks, total, link_obs, link_n_ge, P, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (device_or_host_arg(device) != ST_OK) return ST_ERR_ARG;
+    if (device < 0) {
+        parafit_host(g_f, g_s, P, link_f, link_s, seed, total, link_obs, link_n_ge, link_all);
+        return ST_OK;
+    }
+    return parafit_device(device, P, g_f, g_s, link_f, link_s, seed, total, link_obs, link_n_ge, link_all);
 } ST_CATCH_ALL
 
 int st_graph_matrices_host(int device, int64_t n, int64_t n_edges, const int32_t *u, const int32_t *v,

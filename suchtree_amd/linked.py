@@ -699,6 +699,59 @@ class SuchLinkedTrees:
         out.leaves, out.names, out.measure = observed.leaves, observed.names, measure
         return out
 
+    def parafit(self, permutations=999, seed=None, shuffle="A", transform="sqrt", test_links=True, keep_stats=False):
+        """ParaFit (Legendre, Desdevises & Bazin 2002) on the current subset: the global test of cophylogeny, and for every
+        link ParaFitLink1 with a permutation test of its own -- which links carry the signal that
+        :meth:`hommola_cospeciation` reports for the whole system.
+
+        The links are those of the current subsets (``linklist``), the two distance matrices come from
+        :meth:`SuchTree.pairwise_distances` over the subsets' leaves, each in its tree's depth-first order as in
+        :meth:`partner_dispersion`.  ``shuffle="A"`` (default) is Legendre's null: for every TreeB leaf separately its
+        partners are redrawn among the TreeA leaves of the current subset; ``shuffle="B"`` is the mirror.  With S the
+        shuffled side (n_s leaves) and F the held one, permutation p >= 1 relabels the links of the F leaf with id v by
+        ``compare.hommola_permutation(seed, v, p, 0, n_s)``; the links of one leaf keep distinct partners, different
+        leaves draw independently.  ``transform``, ``test_links``, ``keep_stats`` and the definitions of the statistics
+        and of the link test -- Link1_p(l), the statistic of the relabelled link l in the relabelled system, against the
+        observed Link1_0(l); not claimed to equal ape's link p-values -- are those of
+        :func:`~suchtree_amd.compare.parafit`, which does the work on the shuffled tree's device in one pass over the link
+        pairs, in exact integers.  3 to 16384 links and leaves a side, else a ValueError.
+
+        The subset state, ``linklist`` and the generator of :meth:`sample_linked_distances` are left as they were.
+        Returns a :class:`~suchtree_amd.compare.ParaFitResult` with ``link_a`` / ``link_b`` (leaf ids, in ``linklist``
+        order), ``link_names`` ((TreeA name, TreeB name) pairs) and ``shuffle``.  An extension: the reference has no
+        counterpart.
+        """
+        from . import compare
+        if shuffle not in ("A", "B"):
+            raise ValueError("shuffle must be 'A' or 'B'")
+        if transform not in compare.PARAFIT_TRANSFORMS:
+            raise ValueError("transform must be one of %s" % (compare.PARAFIT_TRANSFORMS,))
+        int_arg("permutations", permutations, (1 << 31) - 1, "2^31 - 1")
+        seed = seed_arg(seed)
+        ll = np.ascontiguousarray(self.linklist, dtype=np.int64)
+        limit = _capi.HOMMOLA_MAX_UNIVERSE
+        if len(ll) < 3 or len(ll) > limit:
+            raise ValueError("ParaFit needs 3 to %d links; the subset has %d" % (limit, len(ll)))
+        sides = {}
+        for name, tree, subset, col in (("A", self._tree_a, self._subset_a_leafs, 1), ("B", self._tree_b, self._subset_b_leafs, 0)):
+            inside = np.zeros(tree.size, dtype=bool)
+            inside[np.asarray(subset, dtype=np.int64)] = True
+            univ = tree._depth_first_leaves()
+            univ = univ[inside[univ]]
+            if len(univ) < 3 or len(univ) > limit:
+                raise ValueError("ParaFit needs 3 to %d leaves in each tree; the subset of Tree%s has %d" % (limit, name, len(univ)))
+            where = np.full(tree.size, -1, dtype=np.int64)
+            where[univ] = np.arange(len(univ))
+            sides[name] = (tree, univ, where[ll[:, col]])
+        (tree_s, univ_s, pos_s), (tree_f, univ_f, pos_f) = sides[shuffle], sides["B" if shuffle == "A" else "A"]
+        out = compare.parafit(tree_f.pairwise_distances(univ_f.tolist()), tree_s.pairwise_distances(univ_s.tolist()), np.stack([pos_f, pos_s], axis=1),
+                              permutations=permutations, seed=seed, shuffle_streams=univ_f, transform=transform, test_links=test_links,
+                              keep_stats=keep_stats, device=tree_s._device)
+        names_a, names_b = self._tree_a.leaf_nodes, self._tree_b.leaf_nodes
+        out.shuffle, out.link_a, out.link_b = shuffle, ll[:, 1].copy(), ll[:, 0].copy()
+        out.link_names = [(names_a[int(a)], names_b[int(b)]) for b, a in ll.tolist()]
+        return out
+
     @staticmethod
     def _row_groups(own, leaves, groups):
         """The label of each row leaf of ``leaves`` under ``groups`` (None: in no group): a mapping from leaf name or id
