@@ -53,7 +53,8 @@ extern "C" {
  *      and st_clade_match; then, also additive, st_beta_dispersion_host and st_beta_dispersion_matrix; then, also additive,
  *      st_unifrac_null_host and st_unifrac_null_depths; then, also additive, struct st_mantel_sums, struct st_mantel_moments,
  *      ST_MANTEL_SHIFT_AUTO, st_mantel_codes and st_mantel_quantise; then, also additive, ST_GROUP_MAX and
- *      st_group_sums_codes; then, also additive, struct st_parafit_sum and st_parafit_codes.
+ *      st_group_sums_codes; then, also additive, struct st_parafit_sum and st_parafit_codes; then, also additive,
+ *      ST_CLASS_MAX, ST_CLASS_NONE and st_class_sums_codes.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -838,6 +839,50 @@ int st_mantel_quantise(const double *v, int64_t n, int32_t shift_or_auto, int32_
 #define ST_GROUP_MAX 256
 
 int st_group_sums_codes(int device, const int32_t *y, int32_t n, const uint8_t *group, int32_t n_groups, int64_t permutations,
+                        uint64_t seed, int32_t stream, int64_t chunk_tasks, int64_t *out);
+
+/*
+ * At which distances does the signal sit: the sums of one distance matrix filed under the class of each pair, under the
+ * relabelling null of st_mantel_codes, behind the Mantel correlogram (compare.mantel_correlogram,
+ * SuchTree.mantel_correlogram, SuchLinkedTrees.phylosymbiosis_correlogram).  One pass gives every class; every sum is
+ * an exact integer, so "statistic_p >= statistic_0" is a comparison of integers on the caller's side.
+ *
+ * y holds the int32 codes of the matrix (st_mantel_quantise, or the doubled midranks minus (m + 1)), cls the class of
+ * every pair of the other matrix, both condensed in the project's triangle order: entry k = i (i - 1) / 2 + j is the
+ * pair (i, j), 0 <= j < i < n.  cls[k] < n_classes <= ST_CLASS_MAX is the class of pair k, ST_CLASS_NONE a pair that is
+ * in no class; a class that no pair carries is allowed.  3 <= n <= ST_HOMMOLA_MAX_UNIVERSE.
+ *
+ * Permutations.  sigma_p = st_hommola_permutation(seed, node = stream, p, side = 0, n), p = 0 the identity: those of
+ * st_mantel_codes, the classes relabelled as x is there.  out holds (permutations + 1) x n_classes int64 values, row 0
+ * the observation:
+ *     out[p][c] = sum over j < i with cls[k(sigma_p(i), sigma_p(j))] == c of y[k(i, j)]      (k(a, b) = k(b, a)),
+ * |sum| < 2^58.  A row depends on (seed, stream, p, y, cls) alone -- not on permutations, chunk_tasks, the device, the
+ * grid or the slice below; row p is the same for any permutations >= p.
+ *
+ * Checked (ST_ERR_ARG), in this order: n outside 3 .. ST_HOMMOLA_MAX_UNIVERSE, negative permutations, chunk_tasks or
+ * stream, more than 2^31 - 1 permutations, n_classes outside 1 .. ST_CLASS_MAX, a NULL y, cls or out, then the first
+ * cls[k] that is neither below n_classes nor ST_CLASS_NONE, named by its index; then a device below -1.  device = -1
+ * computes every row on the host (no GPU); device >= 0 uploads y and the classes and runs the kernels: the same
+ * integers.  n <= 64: one wave per permutation, y and the class square in LDS.  Above: the device expands the classes
+ * once to the symmetric n x n byte square (rows padded to 16 bytes, the diagonal ST_CLASS_NONE); one workgroup per (row
+ * pair r: rows r and n - 1 - r, slice of permutations) stages its rows of y in LDS (4 n + 16 bytes) once for the slice;
+ * each of its four waves copies the square's row of the relabelled object into LDS (n bytes, padded to 16) and adds each
+ * y to the 64-bit LDS accumulator of the relabelled pair's class, one set of accumulators per wave (8 KiB a workgroup):
+ * 136 KiB of LDS at the limit; the row pairs' sums are folded per permutation on the device.  No global atomics.  Only out crosses the
+ * link back.  chunk_tasks: tasks per launch (permutations, or (row pair, slice) pairs above 64 objects), 0 = 2^20; a
+ * positive value also bounds the permutations whose sigma rows the device holds at once.  Device memory: 4 m bytes of
+ * y, m bytes of classes as uploaded (128 MiB at the limit) and, above 64 objects, n rows of the square (256 MiB at the
+ * limit), one block of sigma rows (at most 64 MiB), at most 256 MiB of partial sums (8 n_classes bytes per row pair and
+ * permutation of a block) and 8 n_classes bytes per row of out; an allocation that fails is ST_ERR_NOMEM with the bytes
+ * asked for, before out is written.  The environment variable SUCHTREE_AMD_CLASS_SLICE = 1 .. 256 (read at every call)
+ * replaces the permutations per slice, and SUCHTREE_AMD_CLASS_ACC = compare runs the row form without LDS accumulators
+ * that the default was measured against, each for a measurement; no result depends on either.  No counterpart in the
+ * reference.
+ */
+#define ST_CLASS_MAX 64      /* classes per call */
+#define ST_CLASS_NONE 255    /* a pair that is in no class */
+
+int st_class_sums_codes(int device, const int32_t *y, const uint8_t *cls, int32_t n, int32_t n_classes, int64_t permutations,
                         uint64_t seed, int32_t stream, int64_t chunk_tasks, int64_t *out);
 
 /*

@@ -4,6 +4,7 @@ Loading fails loudly (``HipBackendError``) when the library has not been built:
 there is no CPU fallback anywhere in this package.
 """
 import ctypes
+import math
 import os
 import threading
 
@@ -49,7 +50,7 @@ SYMBOLS = (
     "st_hommola_permutation", "st_hommola_clades_host", "st_partner_dispersion_host", "st_dispersion_matrix",
     "st_unifrac_host", "st_unifrac_depths", "st_unifrac_quantise", "st_clade_ranges", "st_clade_match",
     "st_beta_dispersion_host", "st_beta_dispersion_matrix", "st_unifrac_null_host", "st_unifrac_null_depths",
-    "st_mantel_codes", "st_mantel_quantise", "st_group_sums_codes", "st_parafit_codes",
+    "st_mantel_codes", "st_mantel_quantise", "st_group_sums_codes", "st_parafit_codes", "st_class_sums_codes",
 )
 
 CLADE_RECT, CLADE_TRI = 0, 1     # include/suchtree_hip.h: ST_CLADE_RECT / ST_CLADE_TRI
@@ -344,6 +345,35 @@ def group_sums_codes(y, group, n_groups, permutations, seed=0, stream=0, device=
     n_groups = int(n_groups)
     out = np.zeros((int(permutations) + 1, max(min(n_groups, GROUP_MAX), 0)), dtype=np.int64)
     check(load().st_group_sums_codes(int(device), _arg(y), n, _arg(g), n_groups, int(permutations), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                     int(stream), int(chunk_tasks), _ptr(out) if out.size else None))
+    return out
+
+
+CLASS_MAX = 64       # ST_CLASS_MAX: classes per call of st_class_sums_codes
+CLASS_NONE = 255     # ST_CLASS_NONE: a pair that is in no class
+
+
+def class_sums_codes(y, cls, n_classes, permutations, seed=0, stream=0, device=-1, chunk_tasks=0):
+    """st_class_sums_codes: the int64 (permutations + 1, n_classes) sums of the condensed int32 codes ``y`` (n (n - 1) / 2,
+    pair (i, j) at i (i - 1) / 2 + j) filed under the class of the relabelled pair: ``cls`` holds, condensed in the same
+    order, the class of each pair (below ``n_classes`` <= CLASS_MAX) or CLASS_NONE; row 0 is the observation.  ``device``
+    -1 = the host restatement (no GPU), else the kernels on that device."""
+    c = np.asarray(cls)
+    y = np.ascontiguousarray(y, dtype=np.int32)
+    if y.ndim != 1 or c.ndim != 1 or len(c) != len(y):
+        raise ValueError("y and cls must be condensed and of one length")
+    m = len(y)
+    n = (1 + math.isqrt(8 * m + 1)) // 2
+    if n * (n - 1) // 2 != m:
+        raise ValueError("%d pairs are not the triangle of a square matrix" % m)
+    if m and (c.min() < 0 or c.max() > CLASS_NONE):
+        k = int(np.flatnonzero((c < 0) | (c > CLASS_NONE))[0])
+        raise ValueError("cls[%d] = %d: classes are bytes" % (k, int(c[k])))
+    c = np.ascontiguousarray(c, dtype=np.uint8)
+    _dispersion_args(permutations, stream, chunk_tasks)
+    n_classes = int(n_classes)
+    out = np.zeros((int(permutations) + 1, max(min(n_classes, CLASS_MAX), 0)), dtype=np.int64)
+    check(load().st_class_sums_codes(int(device), _arg(y), _arg(c), n, n_classes, int(permutations), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                      int(stream), int(chunk_tasks), _ptr(out) if out.size else None))
     return out
 
@@ -691,6 +721,7 @@ def load():
         L.st_mantel_codes.argtypes = [i32, vp, vp, vp, ctypes.c_int32, i64, ctypes.c_uint64, ctypes.c_int32, i64, ctypes.POINTER(MantelMoments), vp]
         L.st_mantel_quantise.argtypes = [vp, i64, ctypes.c_int32, vp, ctypes.POINTER(ctypes.c_int32)]
         L.st_group_sums_codes.argtypes = [i32, vp, ctypes.c_int32, vp, ctypes.c_int32, i64, ctypes.c_uint64, ctypes.c_int32, i64, vp]
+        L.st_class_sums_codes.argtypes = [i32, vp, vp, ctypes.c_int32, ctypes.c_int32, i64, ctypes.c_uint64, ctypes.c_int32, i64, vp]
         L.st_parafit_codes.argtypes = [i32, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, ctypes.c_int32, vp, i64, ctypes.c_uint64, i64, vp, vp, vp, vp]
         L.st_clade_ranges.argtypes = [vp, i64, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int32),
                                       ctypes.POINTER(i64)]

@@ -1331,6 +1331,197 @@ def mantel(x, y, z=None, method="pearson", permutations=999, seed=None, alternat
                         shift_x=shifts["x"], shift_y=shifts["y"], shift_z=shifts["z"], **sums)
 
 
+MANTEL_CORRECTIONS = ("holm", "bonferroni", None)
+
+
+class MantelCorrelogram:
+    """The Mantel correlogram of y over the distance classes of x (mantel_correlogram, SuchTree.mantel_correlogram,
+    SuchLinkedTrees.phylosymbiosis_correlogram): at which distances of x are the objects' y values alike.
+
+    One entry per class c, as numpy columns: ``breaks`` (K + 1 edges; class c holds breaks[c] <= x < breaks[c + 1], the
+    last class its upper edge too), ``class_mid``, ``n_pairs`` (m_c), ``sums_q`` (the observed sum S_c of the int32 codes
+    of y over the pairs of the class, int64; ``shift_y``: the fixed point of the Pearson form, None for ranks),
+    ``corr_coeff`` (r_c = minus Pearson's r of the class indicator against y -- the values or, with
+    ``method="spearman"``, their midranks: positive where the pairs of the class are more alike than average; NaN for an
+    empty class, one that holds every pair, or a constant y), ``n_ge`` / ``n_le`` (the permutations whose r_c is >= /
+    <= the observed one, counted on exact integers, ties in both), ``p_value`` (one-sided in the direction of the
+    observed sign: (n_ge + 1) / (permutations + 1) where r_c >= 0, else with n_le), ``p_corrected`` (``correction``,
+    ``progressive``) and ``tested`` (False: beyond the ``cutoff`` or a NaN class, both p NaN).  ``perm_stats`` is the
+    float64 (permutations, K) matrix of r_c of each permutation in draw order with ``keep_stats=True``, else None.
+    ``n`` objects; ``seed`` and ``stream`` repeat the run.  ``leaves`` / ``names`` / ``measure`` are filled in by the
+    facades.
+    """
+
+    COLUMNS = ("class_mid", "n_pairs", "sums_q", "corr_coeff", "n_ge", "n_le", "p_value", "p_corrected", "tested")
+
+    def __init__(self, **kw):
+        self.leaves = self.names = self.measure = None
+        self.__dict__.update(kw)
+
+    def __len__(self):
+        return len(self.class_mid)
+
+    def row(self, c):
+        """class ``c`` as a dict: its edges and its entry of every column"""
+        c = range(len(self))[c]
+        out = {"lower": float(self.breaks[c]), "upper": float(self.breaks[c + 1])}
+        out.update((k, getattr(self, k)[c].item()) for k in self.COLUMNS)
+        return out
+
+    def to_dataframe(self):
+        """one row per class: lower, upper and the columns"""
+        import pandas as pd
+        return pd.DataFrame(dict({"lower": self.breaks[:-1], "upper": self.breaks[1:]}, **{k: getattr(self, k) for k in self.COLUMNS}))
+
+    def __repr__(self):
+        return "MantelCorrelogram(n=%d, classes=%d, tested=%d, method=%r, permutations=%d)" % (
+            self.n, len(self), int(np.count_nonzero(self.tested)), self.method, self.permutations)
+
+
+def mantel_classes(x, breaks):
+    """The uint8 class of each value of ``x`` under the K + 1 increasing edges ``breaks``: class c holds breaks[c] <= x
+    < breaks[c + 1], the last class its upper edge too; a value outside all classes gets ST_CLASS_NONE (255)."""
+    from . import _capi
+    x, breaks = np.asarray(x, dtype=np.float64), np.asarray(breaks, dtype=np.float64)
+    K = len(breaks) - 1
+    c = np.searchsorted(breaks, x, side="right") - 1
+    c[x == breaks[-1]] = K - 1
+    c[(x < breaks[0]) | (x > breaks[-1])] = _capi.CLASS_NONE
+    return c.astype(np.uint8)
+
+
+def mantel_adjust(p, correction="holm", progressive=True):
+    """The p-values ``p`` of the tested classes, in class order, corrected for multiple tests: "bonferroni" (t p, at
+    most 1), "holm" (step-down: with p sorted, adj_(i) = max over j <= i of min(1, (t - j + 1) p_(j))) or None.
+    ``progressive``: the k-th value is corrected within the first k (t = k), as Legendre & Legendre describe for a
+    correlogram; else every value within all of them."""
+    if correction not in MANTEL_CORRECTIONS:
+        raise ValueError("correction must be one of %s" % (MANTEL_CORRECTIONS,))
+    p = np.asarray(p, dtype=np.float64)
+
+    def within(q):      # every value of q corrected within q
+        t = len(q)
+        if correction is None or t == 0:
+            return q.copy()
+        if correction == "bonferroni":
+            return np.minimum(1.0, t * q)
+        order = np.argsort(q, kind="stable")
+        adj = np.maximum.accumulate(np.minimum(1.0, (t - np.arange(t)) * q[order]))
+        out = np.empty(t, dtype=np.float64)
+        out[order] = adj
+        return out
+    if not progressive:
+        return within(p)
+    return np.array([within(p[:k + 1])[k] for k in range(len(p))], dtype=np.float64)
+
+
+def _sum_of_squares(codes):
+    """sum of codes^2 of int32 codes as a Python int: three int64 sums that cannot overflow below 2^27 codes"""
+    v = codes.astype(np.int64)
+    hi, lo = v >> 16, v & 0xFFFF      # v = hi 2^16 + lo, |hi| <= 2^15, 0 <= lo < 2^16
+    return (int((hi * hi).sum()) << 32) + (int((hi * lo).sum()) << 17) + int((lo * lo).sum())
+
+
+def mantel_correlogram(x, y, n_classes=None, breaks=None, cutoff=True, method="pearson", permutations=999, seed=None, stream=0,
+                       correction="holm", progressive=True, keep_stats=False, device=..., chunk_tasks=0):
+    """The Mantel correlogram (Oden & Sokal 1986; Legendre & Legendre 2012; vegan's ``mantel.correlog``): the pairs of n
+    objects are cut into classes of ``x``, and every class gets a Mantel statistic of ``y`` against the class indicator
+    with a permutation test of its own -- all classes in one pass over the pairs on the GPU.
+
+    ``x`` and ``y`` are read as :func:`mantel` reads them (square symmetric or condensed, 3 <= n <= 16384); y enters as
+    int32 codes by ``method`` ("pearson": fixed point; "spearman": midranks).  Classes: ``breaks`` are the K + 1
+    increasing edges -- class c holds breaks[c] <= x < breaks[c + 1], the last class its upper edge too, a pair outside
+    all classes is in none -- by default ``n_classes`` equal-width classes from min(x) to max(x), and ``n_classes=None``
+    is Sturges' rule K = ceil(1 + log2(m)) over the m = n (n - 1) / 2 pairs; at most 64 classes.  Permutation p >= 1
+    relabels the objects of x -- hence the classes -- by ``hommola_permutation(seed, stream, p, 0, n)``, the permutations
+    of :func:`mantel`.  With m_c pairs in class c and S_c(p) the exact integer sum of the codes of y over the relabelled
+    class, r_c = -Pearson(indicator_c, y) = -(m S_c - m_c Sy) / sqrt(m_c (m - m_c) (m Syy - Sy^2)), positive where the
+    pairs of the class are more alike than average.  r_c falls strictly as S_c rises, so the counts compare integers:
+    ``n_ge[c]`` is the number of p >= 1 with S_c(p) <= S_c(0), ``n_le[c]`` that with S_c(p) >= S_c(0); a relabelling
+    that maps the classes onto themselves ties and is counted in both.  ``p_value[c]`` is one-sided in the direction of
+    the observed sign: (n_ge + 1) / (permutations + 1) where r_c >= 0, else (n_le + 1) / (permutations + 1).
+
+    ``cutoff=True`` tests class c only when its upper edge is at most the smallest, over the objects, of an object's
+    largest x -- the distances every object takes part in; the classes beyond keep ``corr_coeff`` and their sums, with
+    ``tested`` False and p NaN.  ``cutoff=False`` tests every class with 0 < m_c < m.  ``correction`` ("holm",
+    "bonferroni", None) and ``progressive`` are those of :func:`mantel_adjust`, over the tested classes in class order.
+    ``device``, ``seed``, ``stream``, ``keep_stats`` and ``chunk_tasks`` are those of :func:`mantel`.
+
+    These are this library's definitions: close to vegan's ``mantel.correlog``, and not claimed to reproduce its
+    p-values.  Returns a :class:`MantelCorrelogram`.  An extension: the reference has no counterpart.
+    """
+    from . import _capi
+    from .suchtree import int_arg, seed_arg
+    if method not in MANTEL_METHODS:
+        raise ValueError("method must be one of %s" % (MANTEL_METHODS,))
+    if correction not in MANTEL_CORRECTIONS:
+        raise ValueError("correction must be one of %s" % (MANTEL_CORRECTIONS,))
+    permutations, stream = int_arg("permutations", permutations, (1 << 31) - 1, "2^31 - 1"), int_arg("stream", stream, (1 << 31) - 1, "2^31 - 1")
+    chunk_tasks, seed = int_arg("chunk_tasks", chunk_tasks), seed_arg(seed)
+    vx, n = mantel_condensed(x, "x")
+    vy, n_y = mantel_condensed(y, "y")
+    if n_y != n:
+        raise ValueError("y has %d objects, x has %d" % (n_y, n))
+    m = n * (n - 1) // 2
+    if breaks is None:
+        K = math.ceil(1 + math.log2(m)) if n_classes is None else int_arg("n_classes", n_classes)
+        if K < 1:
+            raise ValueError("n_classes must be at least 1")
+        lo, hi = float(vx.min()), float(vx.max())
+        if K <= _capi.CLASS_MAX and not lo < hi:
+            raise ValueError("x is constant: no distance classes")
+        edges = np.linspace(lo, hi, K + 1) if K <= _capi.CLASS_MAX else None
+    else:
+        edges = np.array(breaks, dtype=np.float64)
+        if edges.ndim != 1 or len(edges) < 2 or not np.isfinite(edges).all() or not (np.diff(edges) > 0).all():
+            raise ValueError("breaks must be at least two finite, strictly increasing edges")
+        K = len(edges) - 1
+        if n_classes is not None and int(n_classes) != K:
+            raise ValueError("n_classes = %d, breaks give %d classes" % (int(n_classes), K))
+    if K > _capi.CLASS_MAX:
+        raise ValueError("%d classes: at most %d" % (K, _capi.CLASS_MAX))
+    cls = mantel_classes(vx, edges)
+    if method == "spearman":
+        codes, shift = mantel_rank_codes(vy), None
+    else:
+        codes, shift = _capi.mantel_quantise(vy)
+    dev = -1 if device is None else 0 if device is ... else int_arg("device", device)
+    sums = _capi.class_sums_codes(codes, cls, K, permutations, seed, stream, dev, chunk_tasks)
+    m_c = np.bincount(cls, minlength=256)[:K].astype(np.int64)
+    sy, syy = int(codes.sum(dtype=np.int64)), _sum_of_squares(codes)
+    var_y = m * syy - sy * sy
+    obs = [int(v) for v in sums[0].tolist()]
+    sizes = [int(v) for v in m_c.tolist()]
+    num = [m * s - mc * sy for s, mc in zip(obs, sizes)]      # m^2 cov(indicator_c, y): Python ints
+    den = [mc * (m - mc) * var_y for mc in sizes]
+    corr = np.array([_mantel_ratio(-a, d) for a, d in zip(num, den)], dtype=np.float64)
+    n_ge = np.count_nonzero(sums[1:] <= sums[0], axis=0).astype(np.int64)
+    n_le = np.count_nonzero(sums[1:] >= sums[0], axis=0).astype(np.int64)
+    tested = ~np.isnan(corr)
+    if cutoff:      # the largest x of every object, row by row of the triangle
+        reach = np.full(n, -np.inf)
+        for i in range(1, n):
+            seg = vx[i * (i - 1) // 2:i * (i + 1) // 2]
+            reach[i] = max(reach[i], seg.max())
+            np.maximum(reach[:i], seg, out=reach[:i])
+        tested &= edges[1:] <= reach.min()
+    count = np.where(np.array([a <= 0 for a in num]), n_ge, n_le)
+    p_value = np.where(tested, (count + 1) / (permutations + 1), np.nan)
+    p_corrected = np.full(K, np.nan)
+    p_corrected[tested] = mantel_adjust(p_value[tested], correction, progressive)
+    stats = None
+    if keep_stats:
+        stats = np.full((permutations, K), np.nan)
+        for c in range(K):
+            if den[c] > 0:
+                root = math.sqrt(den[c])
+                stats[:, c] = [-(m * int(s) - sizes[c] * sy) / root for s in sums[1:, c].tolist()]
+    return MantelCorrelogram(breaks=edges, class_mid=(edges[:-1] + edges[1:]) / 2, n_pairs=m_c, sums_q=sums[0].copy(), corr_coeff=corr, n_ge=n_ge,
+                             n_le=n_le, p_value=p_value, p_corrected=p_corrected, tested=tested, n=n, method=method, permutations=permutations,
+                             seed=seed, stream=stream, shift_y=shift, perm_stats=stats, correction=correction, progressive=bool(progressive),
+                             cutoff=bool(cutoff))
+
+
 GROUP_TESTS = ("permanova", "anosim")
 
 

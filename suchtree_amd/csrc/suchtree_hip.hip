@@ -77,6 +77,11 @@
 // (st_group_sums_codes): kernels_group.h (a wave form with y in LDS; the relabelled labels as bytes, a row form that
 // stages a row of y in LDS once for a slice of permutations, the fold by group), host_group.h (the loop over blocks and chunks) and, host-only,
 // group_plan.cpp (the checks, the layout, the restatement).
+// The per-class sums of a distance matrix under the same relabelling null, behind the Mantel correlogram
+// (st_class_sums_codes): kernels_class.h (the class square expanded once, a wave form with y and the square in LDS, a row
+// form that stages a row pair of y in LDS once for a slice of permutations and files each pair under its class in LDS
+// accumulators, the fold), host_class.h (the loop over blocks and chunks) and, host-only, class_plan.cpp (the checks,
+// the layout, the restatement).
 // ParaFit's global statistic and ParaFitLink1 of every host-guest link as exact sums over link pairs (st_parafit_codes):
 // kernels_parafit.h (the held side expanded once, one sort per permutation and linked leaf, a wave form with both sides in
 // LDS, a row form that stages one matrix row in LDS per workgroup, the fold with the per-link counts), host_parafit.h (the
@@ -209,6 +214,7 @@ static int device_index_arg(int device)
 #include "kernels_clade_match.h"
 #include "kernels_mantel.h"
 #include "kernels_group.h"
+#include "kernels_class.h"
 #include "kernels_parafit.h"
 
 
@@ -233,6 +239,7 @@ using namespace st;
 #include "host_clade_match.h"
 #include "host_mantel.h"
 #include "host_group.h"
+#include "host_class.h"
 #include "host_parafit.h"
 
 // the next link of st_link_sample_pairs (MuchTree.pyx:2946-2949)
@@ -1121,6 +1128,21 @@ try {
         return ST_OK;
     }
     return group_device(device, P, y, group, seed, stream, out);
+} ST_CATCH_ALL
+
+int st_class_sums_codes(int device, const int32_t *y, const uint8_t *cls, int32_t n, int32_t n_classes, int64_t permutations, uint64_t seed,
+                        int32_t stream, int64_t chunk_tasks, int64_t *out)
+try {
+    ClassPlan P;
+    std::string err;
+    const int rc = class_plan(y, cls, n, n_classes, permutations, stream, chunk_tasks, class_slice(), out, P, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (device_or_host_arg(device) != ST_OK) return ST_ERR_ARG;
+    if (device < 0) {
+        class_host(y, cls, P, seed, stream, out);
+        return ST_OK;
+    }
+    return class_device(device, P, y, cls, seed, stream, out);
 } ST_CATCH_ALL
 
 int st_parafit_codes(int device, const int32_t *g_f, int32_t n_f, const int32_t *g_s, int32_t n_s, const int32_t *link_f, const int32_t *link_s,

@@ -676,6 +676,16 @@ class SuchLinkedTrees:
         int_arg("permutations", permutations, (1 << 31) - 1, "2^31 - 1")
         int_arg("chunk_tasks", chunk_tasks)
         seed = seed_arg(seed)
+        own, observed, x, y = self._phylosymbiosis_matrices(of, measure, pool, min_partners, max_partners, exclude_shared, control)
+        out = compare.mantel(x, y, control, method=method, permutations=permutations, seed=seed, alternative=alternative, keep_stats=keep_stats,
+                             device=own._device if device is ... else device, chunk_tasks=chunk_tasks)
+        out.leaves, out.names, out.measure = observed.leaves, observed.names, measure
+        return out
+
+    def _phylosymbiosis_matrices(self, of, measure, pool, min_partners, max_partners, exclude_shared, control=None):
+        """(the row tree, the observed measure over the partner rows, x: the row leaves' own tree distances, y: the
+        ``measure`` between their partner sets) of :meth:`phylosymbiosis`; a NaN in y is its ValueError."""
+        from . import compare
         by_distance = measure in ("beta_mpd", "beta_mntd")
 
         def run(partner, sets, root, universe):
@@ -693,9 +703,39 @@ class SuchLinkedTrees:
             i, j = observed.pair(int(bad[0]))
             raise ValueError("%s of rows %d and %d (%s, %s) is NaN" % (measure, i, j, observed.names[i], observed.names[j]))
         own = self._tree_a if of == "A" else self._tree_b
-        x = own.pairwise_distances(observed.leaves.tolist())
-        out = compare.mantel(x, y, control, method=method, permutations=permutations, seed=seed, alternative=alternative, keep_stats=keep_stats,
-                             device=own._device if device is ... else device, chunk_tasks=chunk_tasks)
+        return own, observed, own.pairwise_distances(observed.leaves.tolist()), y
+
+    def phylosymbiosis_correlogram(self, of="A", measure="unifrac", n_classes=None, breaks=None, cutoff=True, method="pearson", permutations=999,
+                                   seed=None, correction="holm", progressive=True, pool="subset", min_partners=1, max_partners=None,
+                                   exclude_shared=False, keep_stats=False, device=..., chunk_tasks=0):
+        """At which phylogenetic distances does phylosymbiosis sit?  The Mantel correlogram of the distance between the
+        leaves' partner sets over the classes of the leaves' own tree distance: among sister species only, across
+        genera, or with a change of sign at depth -- what the one r of :meth:`phylosymbiosis` cannot separate.
+
+        The rows, x, y and ``measure`` (with ``pool``, ``min_partners``, ``max_partners`` and ``exclude_shared``) are
+        those of :meth:`phylosymbiosis`; a NaN in the measure is the same ValueError.  ``n_classes``, ``breaks``,
+        ``cutoff``, ``method``, ``permutations``, ``seed``, ``correction``, ``progressive``, ``keep_stats`` and
+        ``chunk_tasks`` are those of :func:`~suchtree_amd.compare.mantel_correlogram`, which files every relabelled pair
+        under its distance class in one pass on ``device`` (... = the row tree's device; None = only the permutations
+        run on the host: the two matrices still come from the trees' kernels).  A class with a positive ``corr_coeff``
+        holds leaves whose partners are more alike than average.
+
+        The subset state, ``linklist`` and the generator of :meth:`sample_linked_distances` are left as they were.
+        Returns a :class:`~suchtree_amd.compare.MantelCorrelogram`, one row per class, with ``leaves`` (the rows' leaf
+        ids), ``names`` and ``measure``.  An extension: the reference has no counterpart.
+        """
+        from . import compare
+        if measure not in self.PHYLOSYMBIOSIS_MEASURES:
+            raise ValueError("measure must be one of %s" % (self.PHYLOSYMBIOSIS_MEASURES,))
+        if method not in compare.MANTEL_METHODS or correction not in compare.MANTEL_CORRECTIONS:
+            raise ValueError("method must be one of %s and correction one of %s" % (compare.MANTEL_METHODS, compare.MANTEL_CORRECTIONS))
+        int_arg("permutations", permutations, (1 << 31) - 1, "2^31 - 1")
+        int_arg("chunk_tasks", chunk_tasks)
+        seed = seed_arg(seed)
+        own, observed, x, y = self._phylosymbiosis_matrices(of, measure, pool, min_partners, max_partners, exclude_shared)
+        out = compare.mantel_correlogram(x, y, n_classes=n_classes, breaks=breaks, cutoff=cutoff, method=method, permutations=permutations, seed=seed,
+                                         correction=correction, progressive=progressive, keep_stats=keep_stats,
+                                         device=own._device if device is ... else device, chunk_tasks=chunk_tasks)
         out.leaves, out.names, out.measure = observed.leaves, observed.names, measure
         return out
 

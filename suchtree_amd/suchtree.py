@@ -788,6 +788,33 @@ class SuchTree(TreeNavigation):
         return compare.mantel(self.pairwise_distances(ids.tolist()), y, z, method=method, permutations=permutations, seed=seed, alternative=alternative,
                               stream=stream, keep_stats=keep_stats, device=self._device, chunk_tasks=chunk_tasks)
 
+    def mantel_correlogram(self, y, leaves, n_classes=None, breaks=None, cutoff=True, method="pearson", permutations=999, seed=None, stream=0,
+                           correction="holm", progressive=True, keep_stats=False, device=..., chunk_tasks=0):
+        """The Mantel correlogram of another distance matrix over the classes of this tree's distances, on the GPU: at
+        which depths of the tree are the objects' y values alike.
+
+        ``leaves`` (leaf names or leaf ids, at least 3, at most 16384, none repeated) are the objects in the order of
+        ``y``'s rows; x is the tree's own distance matrix over them (:meth:`pairwise_distances`), as in :meth:`mantel`,
+        and its classes are what the permutations relabel.  Every other argument is that of
+        :func:`~suchtree_amd.compare.mantel_correlogram`, which does the work on ``device`` (... = this tree's device;
+        None = only the permutations run on the host: x still comes from the tree's kernels).  Returns a
+        :class:`~suchtree_amd.compare.MantelCorrelogram` with ``leaves`` (leaf ids) and ``names``.  An extension: the
+        reference has no counterpart.
+        """
+        from . import compare
+        ids = self._leaf_ids(leaves, "leaves")
+        if len(np.unique(ids)) != len(ids):
+            raise ValueError("leaves: a repeated leaf")
+        if len(ids) < 3 or len(ids) > _capi.HOMMOLA_MAX_UNIVERSE:
+            raise ValueError("%d leaves: 3 to %d" % (len(ids), _capi.HOMMOLA_MAX_UNIVERSE))
+        if compare.mantel_condensed(y, "y")[1] != len(ids):      # (before the tree goes to its device)
+            raise ValueError("y is not over the %d leaves" % len(ids))
+        out = compare.mantel_correlogram(self.pairwise_distances(ids.tolist()), y, n_classes=n_classes, breaks=breaks, cutoff=cutoff, method=method,
+                                         permutations=permutations, seed=seed, stream=stream, correction=correction, progressive=progressive,
+                                         keep_stats=keep_stats, device=self._device if device is ... else device, chunk_tasks=chunk_tasks)
+        out.leaves, out.names = ids.copy(), [self.leaf_nodes[int(v)] for v in ids.tolist()]
+        return out
+
     def unifrac(self, sets, root=None, begin=0, count=None, shift=None, chunk_pairs=0):
         """How different are every two sets of leaves, measured on this tree: Faith's PD and unweighted UniFrac, on the GPU.
 
