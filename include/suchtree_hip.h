@@ -54,7 +54,8 @@ extern "C" {
  *      st_unifrac_null_host and st_unifrac_null_depths; then, also additive, struct st_mantel_sums, struct st_mantel_moments,
  *      ST_MANTEL_SHIFT_AUTO, st_mantel_codes and st_mantel_quantise; then, also additive, ST_GROUP_MAX and
  *      st_group_sums_codes; then, also additive, struct st_parafit_sum and st_parafit_codes; then, also additive,
- *      ST_CLASS_MAX, ST_CLASS_NONE and st_class_sums_codes.
+ *      ST_CLASS_MAX, ST_CLASS_NONE and st_class_sums_codes; then, also additive, st_swap_null_tables, st_swap_null_schedule,
+ *      st_dispersion_matrix_swap and st_partner_dispersion_swap_host.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -547,6 +548,63 @@ int st_partner_dispersion_host(st_tree *tree, const int64_t *univ, int32_t n_uni
 int st_dispersion_matrix(int device, const float *D, int32_t n, const int32_t *set_pos, int64_t n_pos, const int64_t *sets,
                          int64_t n_sets, int64_t permutations, uint64_t seed, int32_t stream, int64_t chunk_tasks,
                          st_dispersion_record *out);
+
+/*
+ * The degree-preserving swap null of the dispersion calls (picante's "independentswap" / "trialswap", the fixed-fixed null
+ * of bipartite network analysis).  The taxa-labels null above keeps every set's size and forgets how many sets a position
+ * belongs to; this one keeps both margins of the 0/1 link matrix whose rows are the sets and whose columns are the
+ * positions.  SuchTree.dispersion and SuchLinkedTrees.partner_dispersion take it with null = "swap".
+ *
+ * The chain.  Inputs are those of st_dispersion_matrix: n_univ (3 .. ST_HOMMOLA_MAX_UNIVERSE), the set table (set r is the
+ * strictly increasing positions set_pos[sets[r] .. sets[r + 1])), seed, stream, and `iterations` T >= 0.  The links are the
+ * L = sets[n_sets] - sets[0] entries from sets[0] on; entry e belongs to row row_of(e).  Chain p >= 1 starts from the
+ * observed entries col[e] = set_pos[sets[0] + e] with h1 = perm_stream(seed, stream, p, 1) -- the stream hash of
+ * st_hommola_permutation with side 1, which keeps it apart from the sigma rows (side 0) of the same stream; G =
+ * 0x9E3779B97F4A7C15 and mix() are its constant and its mixer.  For t = 0 .. T - 1 in order:
+ *     e1 = high 64 bits of mix(h1 + (2 t + 1) G) x L,  e2 = high 64 bits of mix(h1 + (2 t + 2) G) x L,
+ *     r1 = row_of(e1), r2 = row_of(e2), b = col[e1], d = col[e2];
+ *     accept iff r1 != r2 and b != d and d is not in row r1 and b is not in row r2;  on accept col[e1] = d, col[e2] = b.
+ * After trial T - 1 every row is sorted ascending: that is table row p, n_pos uint16 values with the offsets of `sets`
+ * (entries of set_pos outside the links are copied).  p = 0 is the observed positions; accepted[p] is the number of accepted
+ * trials (0 for p = 0).  Row sums and column sums of the 0/1 matrix are the observation's for every p.  Chain p depends on
+ * (seed, stream, p, T, the sets) alone -- not on n_perms, p_begin, chunk_tasks, the grid or the device.  L < 2 makes every
+ * chain the observation.  The facades' default, iterations = None, is max(1000, 10 L) trials: the library's own
+ * definition (picante's default is 1000 swaps).
+ *
+ * st_swap_null_tables writes table rows p_begin .. p_begin + n_perms to out (n_perms x n_pos uint16) and, where accepted
+ * is not NULL, their accepted counts.  device = -1 is the host restatement (no GPU); device >= 0 runs k_swap_chains, one
+ * wave per chain: the same values.  st_swap_null_schedule runs chain p on the host in the wave's schedule -- batches of 64
+ * trials, of which the lanes below the first one that shares a row with an earlier lane are executed -- and reports the
+ * batches as *steps (NULL allowed): the same row and count, by a different route.
+ *
+ * st_dispersion_matrix_swap and st_partner_dispersion_swap_host mirror st_dispersion_matrix and
+ * st_partner_dispersion_host: record (r, p) is the record of the dispersion calls over set r of table row p -- the same
+ * arithmetic, the same order over i.  Sets of fewer than two positions take part in the swaps and give zero records.
+ * accepted (permutations + 1 entries) may be NULL.  device = -1 is the host restatement: the same bits.
+ *
+ * Errors come in the order of the calls they mirror (st_swap_null_tables: the universe size, negative p_begin, n_perms or
+ * stream, the set table), then: negative iterations; a single chain whose state -- its table row and a bit matrix of
+ * n_sets rows of n_univ bits padded to 64 -- exceeds the work budget of 4 GiB, ST_ERR_ARG with the bytes; then the
+ * remaining checks of the mirrored call; an allocation that fails is ST_ERR_NOMEM with the bytes asked for, before out is
+ * written.  Device memory: a block of chains holds 2 n_pos + 8 n_sets ceil(n_univ / 64) bytes per chain, as many chains as
+ * the budget allows; chunk_tasks > 0 bounds the chains of a block as it bounds the sigma rows of st_dispersion_matrix.
+ * No counterpart in the reference.
+ */
+int st_swap_null_tables(int device, int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets,
+                        int64_t p_begin, int64_t n_perms, int64_t iterations, uint64_t seed, int32_t stream, uint16_t *out,
+                        int64_t *accepted);
+
+int st_swap_null_schedule(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets, int64_t p,
+                          int64_t iterations, uint64_t seed, int32_t stream, uint16_t *out, int64_t *accepted, int64_t *steps);
+
+int st_dispersion_matrix_swap(int device, const float *D, int32_t n, const int32_t *set_pos, int64_t n_pos, const int64_t *sets,
+                              int64_t n_sets, int64_t permutations, int64_t iterations, uint64_t seed, int32_t stream,
+                              int64_t chunk_tasks, st_dispersion_record *out, int64_t *accepted);
+
+int st_partner_dispersion_swap_host(st_tree *tree, const int64_t *univ, int32_t n_univ, const int32_t *set_pos, int64_t n_pos,
+                                    const int64_t *sets, int64_t n_sets, int64_t permutations, int64_t iterations, uint64_t seed,
+                                    int32_t stream, int64_t chunk_tasks, st_dispersion_record *out, int64_t *accepted,
+                                    int64_t *bad_id);
 
 /*
  * How far apart are the members of two sets of leaves: the sums behind betaMPD (the mean distance between a member of one

@@ -51,6 +51,7 @@ SYMBOLS = (
     "st_unifrac_host", "st_unifrac_depths", "st_unifrac_quantise", "st_clade_ranges", "st_clade_match",
     "st_beta_dispersion_host", "st_beta_dispersion_matrix", "st_unifrac_null_host", "st_unifrac_null_depths",
     "st_mantel_codes", "st_mantel_quantise", "st_group_sums_codes", "st_parafit_codes", "st_class_sums_codes",
+    "st_swap_null_tables", "st_swap_null_schedule", "st_dispersion_matrix_swap", "st_partner_dispersion_swap_host",
 )
 
 CLADE_RECT, CLADE_TRI = 0, 1     # include/suchtree_hip.h: ST_CLADE_RECT / ST_CLADE_TRI
@@ -180,6 +181,69 @@ def dispersion_matrix(D, sets, permutations, seed, stream=0, device=-1, chunk_ta
     check(load().st_dispersion_matrix(int(device), _ptr(D), n, _arg(pos), len(pos), _ptr(off), n_sets, int(permutations),
                                       int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(chunk_tasks), _arg(out)))
     return out
+
+
+def swap_iterations(iterations, n_links):
+    """The trials of a swap chain: ``iterations``, or for None the library's default max(1000, 10 x the links)."""
+    if iterations is None:
+        return max(1000, 10 * int(n_links))
+    if int(iterations) < 0:
+        raise ValueError("iterations < 0")
+    return int(iterations)
+
+
+def _swap_links(off):
+    return int(off[-1] - off[0])
+
+
+def swap_null_tables(sets, n_univ, permutations=0, begin=0, iterations=None, seed=0, stream=0, device=-1):
+    """st_swap_null_tables: (tables, offsets, accepted) of the degree-preserving swap null over the position sets ``sets`` (as
+    in ``dispersion_matrix``; a row per set, a column per position of the universe of ``n_univ``).  ``tables`` is the
+    (permutations + 1, n_pos) uint16 array of table rows begin .. begin + permutations -- row p holds the randomised sets
+    of chain p, sorted, at the offsets ``offsets`` of the observed ones; p = 0 is the observation -- and ``accepted`` the
+    swaps each chain made of its ``iterations`` trials (None: max(1000, 10 x the links)).  ``device`` -1 = the host
+    restatement (no GPU), else k_swap_chains on that device: the same values."""
+    n_univ = int(n_univ)
+    _dispersion_args(permutations, stream, 0)
+    if int(begin) < 0:
+        raise ValueError("begin < 0")
+    pos, off, n_sets = _dispersion_sets(sets, n_univ)
+    rows = int(permutations) + 1
+    tables = np.zeros((rows, len(pos)), dtype=np.uint16)
+    accepted = np.zeros(rows, dtype=np.int64)
+    check(load().st_swap_null_tables(int(device), n_univ, _arg(pos), len(pos), _ptr(off), n_sets, int(begin), rows,
+                                     swap_iterations(iterations, _swap_links(off)), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream),
+                                     _arg(tables), _arg(accepted)))
+    return tables, off, accepted
+
+
+def swap_null_schedule(sets, n_univ, p, iterations=None, seed=0, stream=0):
+    """st_swap_null_schedule: (table row, accepted, steps) of chain ``p`` run on the host in the schedule of the device's
+    wave -- batches of 64 trials cut at the first lane that shares a row with an earlier one; ``steps`` batches for
+    ``iterations`` trials.  The row and ``accepted`` are those of ``swap_null_tables``."""
+    n_univ = int(n_univ)
+    _dispersion_args(0, stream, 0)
+    pos, off, n_sets = _dispersion_sets(sets, n_univ)
+    row = np.zeros(len(pos), dtype=np.uint16)
+    accepted, steps = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(load().st_swap_null_schedule(n_univ, _arg(pos), len(pos), _ptr(off), n_sets, int(p), swap_iterations(iterations, _swap_links(off)),
+                                       int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), _arg(row), ctypes.byref(accepted), ctypes.byref(steps)))
+    return row, int(accepted.value), int(steps.value)
+
+
+def dispersion_matrix_swap(D, sets, permutations, seed, iterations=None, stream=0, device=-1, chunk_tasks=0):
+    """st_dispersion_matrix_swap: (records, accepted) -- the (n_sets, permutations + 1) array of DISPERSION_RECORD of
+    ``dispersion_matrix`` under the swap null (record (r, p) over set r of table row p of ``swap_null_tables``) and the
+    accepted swaps of every chain."""
+    D, n = _square_matrix(D)
+    _dispersion_args(permutations, stream, chunk_tasks)
+    pos, off, n_sets = _dispersion_sets(sets, n)
+    out = np.zeros((n_sets, int(permutations) + 1), dtype=DISPERSION_RECORD)
+    accepted = np.zeros(int(permutations) + 1, dtype=np.int64)
+    check(load().st_dispersion_matrix_swap(int(device), _ptr(D), n, _arg(pos), len(pos), _ptr(off), n_sets, int(permutations),
+                                           swap_iterations(iterations, _swap_links(off)), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream),
+                                           int(chunk_tasks), _arg(out), _arg(accepted)))
+    return out, accepted
 
 
 UNIFRAC_MAX_UNIVERSE = 1 << 20     # ST_UNIFRAC_MAX_UNIVERSE: leaves per universe of st_unifrac_host
@@ -706,6 +770,12 @@ def load():
         L.st_partner_dispersion_host.argtypes = [vp, vp, ctypes.c_int32, vp, i64, vp, i64, i64, ctypes.c_uint64, ctypes.c_int32, i64, vp,
                                                  ctypes.POINTER(i64)]
         L.st_dispersion_matrix.argtypes = [i32, vp, ctypes.c_int32, vp, i64, vp, i64, i64, ctypes.c_uint64, ctypes.c_int32, i64, vp]
+        L.st_swap_null_tables.argtypes = [i32, ctypes.c_int32, vp, i64, vp, i64, i64, i64, i64, ctypes.c_uint64, ctypes.c_int32, vp, vp]
+        L.st_swap_null_schedule.argtypes = [ctypes.c_int32, vp, i64, vp, i64, i64, i64, ctypes.c_uint64, ctypes.c_int32, vp, ctypes.POINTER(i64),
+                                            ctypes.POINTER(i64)]
+        L.st_dispersion_matrix_swap.argtypes = [i32, vp, ctypes.c_int32, vp, i64, vp, i64, i64, i64, ctypes.c_uint64, ctypes.c_int32, i64, vp, vp]
+        L.st_partner_dispersion_swap_host.argtypes = [vp, vp, ctypes.c_int32, vp, i64, vp, i64, i64, i64, ctypes.c_uint64, ctypes.c_int32, i64, vp, vp,
+                                                      ctypes.POINTER(i64)]
         L.st_beta_dispersion_host.argtypes = [vp, vp, ctypes.c_int32, vp, i64, vp, i64, i64, i64, ctypes.c_int32, i64, ctypes.c_uint64,
                                               ctypes.c_int32, i64, vp, ctypes.POINTER(i64)]
         L.st_beta_dispersion_matrix.argtypes = [i32, vp, ctypes.c_int32, vp, i64, vp, i64, i64, i64, ctypes.c_int32, i64, ctypes.c_uint64,
@@ -1386,6 +1456,23 @@ class DeviceTree:
                                                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream), int(chunk_tasks), _arg(out), ctypes.byref(bad))
         check(rc, tree_size=self.size, bad_id=int(bad.value))
         return out
+
+    def partner_dispersion_swap_host(self, univ, sets, permutations, seed, iterations=None, stream=0, chunk_tasks=0):
+        """st_partner_dispersion_swap_host: (records, accepted) of ``partner_dispersion_host`` under the swap null (as
+        ``dispersion_matrix_swap``, the matrix written by this tree's distance kernels)."""
+        univ = np.ascontiguousarray(univ, dtype=np.int64)
+        if univ.ndim != 1:
+            raise ValueError("the universe must be 1-D")
+        _dispersion_args(permutations, stream, chunk_tasks)
+        pos, off, n_sets = _dispersion_sets(sets, len(univ))
+        out = np.zeros((n_sets, int(permutations) + 1), dtype=DISPERSION_RECORD)
+        accepted = np.zeros(int(permutations) + 1, dtype=np.int64)
+        bad = ctypes.c_int64(0)
+        rc = self._lib.st_partner_dispersion_swap_host(self.handle, _arg(univ), len(univ), _arg(pos), len(pos), _ptr(off), n_sets, int(permutations),
+                                                       swap_iterations(iterations, _swap_links(off)), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream),
+                                                       int(chunk_tasks), _arg(out), _arg(accepted), ctypes.byref(bad))
+        check(rc, tree_size=self.size, bad_id=int(bad.value))
+        return out, accepted
 
     def beta_dispersion_host(self, univ, sets, begin=0, count=None, exclude_shared=False, permutations=0, seed=0, stream=0, chunk_tasks=0):
         """st_beta_dispersion_host: the (count, 2, permutations + 1) array of DISPERSION_RECORD of pairs [begin, begin + count)

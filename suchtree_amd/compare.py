@@ -443,6 +443,22 @@ def hommola_permutation(seed, node, p, side, n, device=None):
     return _capi.hommola_permutation(seed, node, p, side, n, -1 if device is None else int(device))
 
 
+def swap_null_tables(sets, n_universe, permutations=999, begin=0, iterations=None, seed=0, stream=0, device=None):
+    """The degree-preserving swap null itself: randomised copies of a 0/1 matrix that keep its row sums and column sums
+    (picante's ``independentswap`` / ``trialswap``), for any statistic of your own under the null of
+    ``SuchTree.dispersion(null="swap")``.
+
+    ``sets`` is an iterable of strictly increasing collections of positions 0 .. ``n_universe`` - 1 (3 to 16384): set r
+    is row r, a position a column.  Returns ``(tables, offsets, accepted)``: ``tables[i]`` is draw p = ``begin`` + i, a
+    uint16 array in which row r's columns, ascending, are ``tables[i, offsets[r]:offsets[r + 1]]``; p = 0 is the
+    observation; ``accepted[i]`` the swaps chain p made of its ``iterations`` trials.  ``iterations=None`` is
+    max(1000, 10 x the links), the library's own default (picante's is 1000 swaps).  Draw p depends on (seed, stream, p,
+    iterations, the sets) alone.  ``device=None`` computes it on the host, without a GPU; a device index runs one
+    wave per chain there -- the same values."""
+    from . import _capi
+    return _capi.swap_null_tables(sets, n_universe, permutations, begin, iterations, seed, stream, -1 if device is None else int(device))
+
+
 class SetDispersion:
     """How closely related the members of each of many leaf sets are (SuchTree.dispersion,
     SuchLinkedTrees.partner_dispersion), as numpy columns, one entry per set.
@@ -460,13 +476,20 @@ class SetDispersion:
     ``null_mpd`` / ``null_mntd`` are the (sets, permutations) arrays of the draws with ``keep_null=True``, else None.
     ``permutations``, ``seed`` and ``n_universe`` repeat the call.  ``leaves`` / ``names`` are filled in by
     ``partner_dispersion``: the leaf whose partners a row describes.
+
+    ``null`` is the null model, "taxa.labels" or "swap".  Under "swap" the draws are the rows of the call's 0/1 matrix
+    after a chain of ``iterations`` trial swaps that keep both of its margins (``swap_null_tables``), and
+    ``swap_accepted`` holds the swaps each chain made, entry p for null draw p (entry 0, the observation, is 0); under
+    "taxa.labels" both are None.
     """
 
     COLUMNS = ("n", "mpd", "mntd", "mpd_null_mean", "mpd_null_sd", "mpd_ses", "mpd_n_le", "mpd_p", "mntd_null_mean", "mntd_null_sd",
                "mntd_ses", "mntd_n_le", "mntd_p", "n_nan")
 
-    def __init__(self, n_sets, permutations, seed, n_universe, keep_null=False):
+    def __init__(self, n_sets, permutations, seed, n_universe, keep_null=False, null="taxa.labels", iterations=None):
         self.permutations, self.seed, self.n_universe = int(permutations), int(seed), int(n_universe)
+        self.null, self.iterations = null, iterations
+        self.swap_accepted = np.zeros(self.permutations + 1, dtype=np.int64) if null == "swap" else None
         self.n = np.zeros(n_sets, dtype=np.int64)
         for k in self.COLUMNS[1:]:
             setattr(self, k, np.zeros(n_sets, dtype=np.int64) if k.endswith("n_le") or k == "n_nan" else np.full(n_sets, np.nan))

@@ -23,11 +23,14 @@ void dispersion_cut(int32_t n_univ, int64_t rows, int64_t live, int64_t chunk_ta
                     int64_t &max_chunk_tasks, int64_t table_entries)
 {
     int64_t block = std::max<int64_t>(1, kDispersionSigmaBytes / (2 * ((int64_t)n_univ + table_entries)));
-    int64_t cap = kDispersionChunkTasks;
-    if (chunk_tasks > 0) {
-        block = std::min(block, chunk_tasks);
-        cap = std::min(chunk_tasks, kDispersionMaxChunkTasks);
-    }
+    if (chunk_tasks > 0) block = std::min(block, chunk_tasks);
+    dispersion_cut_blocks(rows, live, block, chunk_tasks, perm_block, chunks, max_chunk_tasks);
+}
+
+void dispersion_cut_blocks(int64_t rows, int64_t live, int64_t block, int64_t chunk_tasks, int64_t &perm_block, std::vector<DispersionChunk> &chunks,
+                           int64_t &max_chunk_tasks)
+{
+    const int64_t cap = chunk_tasks > 0 ? std::min(chunk_tasks, kDispersionMaxChunkTasks) : kDispersionChunkTasks;
     perm_block = std::min(block, rows);
     if (live == 0) return;
     for (int64_t p0 = 0; p0 < rows; p0 += perm_block) {

@@ -80,6 +80,9 @@ int dispersion_plan(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const
 int dispersion_call_args(int32_t n_univ, int64_t permutations, int64_t chunk_tasks, int32_t stream, std::string &err);
 void dispersion_cut(int32_t n_univ, int64_t rows, int64_t live, int64_t chunk_tasks, int64_t &perm_block, std::vector<DispersionChunk> &chunks,
                     int64_t &max_chunk_tasks, int64_t table_entries = 0);
+// the same cut for blocks of up to `block` >= 1 permutations, whatever holds a block's rows (swap_plan.cpp: chains)
+void dispersion_cut_blocks(int64_t rows, int64_t live, int64_t block, int64_t chunk_tasks, int64_t &perm_block, std::vector<DispersionChunk> &chunks,
+                           int64_t &max_chunk_tasks);
 void dispersion_butterfly(double *v, int width);
 
 // `order` by (size class, `before` within a class, index) and the class ranges of the layout above: cls(x) is the size

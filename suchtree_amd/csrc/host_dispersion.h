@@ -64,10 +64,11 @@ static hipError_t dispersion_launch_tasks(const int64_t *class_begin, const Disp
 // (d_out).  launch(chunk, results, stream) enqueues a chunk's kernels, scatter_to(results, chunk) puts its results where
 // the caller wants them; `what` names the call in messages.  Returns ST_OK or ST_ERR_HIP; on return nothing of this call
 // is pending on s unless a HIP call failed.
-template <typename T, typename Launch, typename Scatter>
-static int perm_block_chunks(ReadbackRing<T, const DispersionChunk *> &ring, const char *what, hipStream_t s, const std::vector<DispersionChunk> &chunks,
-                             unsigned short *d_sigma, T *const (&d_out)[2], int32_t n_univ, uint64_t seed, int32_t stream, Launch launch,
-                             Scatter scatter_to)
+// The block's rows come from produce(chunk, stream), enqueued when the block changes: the sigma sorts (perm_block_chunks
+// below), or the chains of the swap null (host_swap.h).
+template <typename T, typename Produce, typename Launch, typename Scatter>
+static int perm_block_chunks_of(ReadbackRing<T, const DispersionChunk *> &ring, const char *what, hipStream_t s, const std::vector<DispersionChunk> &chunks,
+                                T *const (&d_out)[2], Produce produce, Launch launch, Scatter scatter_to)
 {
     auto hip_fail = [&](const char *step, hipError_t e) { return fail(ST_ERR_HIP, std::string(what) + step + hipGetErrorString(e)); };
     auto scatter = [&](const T *results, const DispersionChunk *c) { scatter_to(results, *c); };
@@ -77,7 +78,7 @@ static int perm_block_chunks(ReadbackRing<T, const DispersionChunk *> &ring, con
         if (e != hipSuccess) return hip_fail(" read-back: ", e);
         T *const out = d_out[ring.next];
         if (c.p_begin != sigma_p) {      // (stream order: the tasks of the block before have read their rows)
-            e = dispersion_launch_sigma(DispersionSigmaArgs{d_sigma, (long long)c.p_begin, (unsigned long long)seed, (int)stream, (int)n_univ}, c.n_perms, s);
+            e = produce(c, s);
             if (e != hipSuccess) return hip_fail(" launch: ", e);
             sigma_p = c.p_begin;
         }
@@ -88,6 +89,19 @@ static int perm_block_chunks(ReadbackRing<T, const DispersionChunk *> &ring, con
     const hipError_t e = ring.drain(scatter, s);
     if (e != hipSuccess) return hip_fail(" read-back: ", e);
     return ST_OK;
+}
+
+template <typename T, typename Launch, typename Scatter>
+static int perm_block_chunks(ReadbackRing<T, const DispersionChunk *> &ring, const char *what, hipStream_t s, const std::vector<DispersionChunk> &chunks,
+                             unsigned short *d_sigma, T *const (&d_out)[2], int32_t n_univ, uint64_t seed, int32_t stream, Launch launch,
+                             Scatter scatter_to)
+{
+    return perm_block_chunks_of(
+        ring, what, s, chunks, d_out,
+        [&](const DispersionChunk &c, hipStream_t st) {
+            return dispersion_launch_sigma(DispersionSigmaArgs{d_sigma, (long long)c.p_begin, (unsigned long long)seed, (int)stream, (int)n_univ}, c.n_perms, st);
+        },
+        launch, scatter_to);
 }
 
 // A plan of records -- DispersionPlan over its sets, SetpairPlan over its directions -- on stream s, with the caller's work

@@ -15,6 +15,10 @@
 //     the first add (the row q_i is up to 64 KiB: a gather is an L2 or Infinity Cache hit whose latency only other
 //     loads in flight hide), then adds them in j order.  The j == i entry is loaded and left out of both results.
 //
+//     Each form is instantiated twice: k_dispersion_tasks_* read q_i = sigma_p[set_pos[begin + i]] (the taxa-labels null),
+//     k_swap_tasks_* read q_i = table_p[begin + i] from the table rows that k_swap_chains writes (the swap null,
+//     kernels_swap.h); everything after q_i is the same code.
+//
 // Determinism: a row's sum runs over j ascending in one lane; the order over i is that of dispersion_record
 // (dispersion_plan.cpp), operation for operation.  No float atomics.
 #pragma once
@@ -63,6 +67,7 @@ struct DispersionTaskArgs {
     long long set0, n;                   // this launch: n tasks (n < 2^31), the first one of set set0 ...
     unsigned perm0, n_perms;             // ... under row perm0 of the block's n_perms: task slot is (set0, perm0) + slot, row-fastest
     int n_univ, lanes;                   // packed form: K'
+    int n_pos;                           // table form: the entries of a table row
 };
 
 // one row's walk: `qj(j)` gives q_j for 0 <= j < k (k >= 1), i the lane's own element; a lane that is not live adds nothing
@@ -86,14 +91,25 @@ __device__ __forceinline__ void dispersion_row(const float *__restrict__ row, in
     }
 }
 
+// The two forms of a task's positions.  Sigma form (kTable = false): `sigma` holds the block's sigma rows, q_i =
+// sigma_p[set_pos[begin + i]].  Table form (kTable = true, the swap null: kernels_swap.h): `sigma` holds the block's table
+// rows of n_pos entries, the randomised sets themselves with the offsets of the observed ones, q_i = table_p[begin + i].
+template <bool kTable>
 __device__ __forceinline__ void dispersion_task(const DispersionTaskArgs &a, long long slot, DispersionSetDev &s, const unsigned short *&sig)
 {
     const unsigned u = a.perm0 + (unsigned)slot, c = u / a.n_perms;      // (32 bits: perm0 < n_perms < 2^25, slot < 2^31)
     s = a.sets[a.set0 + c];
-    sig = a.sigma + (size_t)(u - c * a.n_perms) * (size_t)a.n_univ;
+    sig = a.sigma + (size_t)(u - c * a.n_perms) * (size_t)(kTable ? a.n_pos : a.n_univ);
 }
 
-__global__ __launch_bounds__(kDispersionThreads) void k_dispersion_tasks_packed(DispersionTaskArgs a)
+template <bool kTable>
+__device__ __forceinline__ int dispersion_position(const DispersionTaskArgs &a, const unsigned short *sig, int at)
+{
+    return kTable ? (int)sig[at] : (int)sig[a.set_pos[at]];
+}
+
+template <bool kTable>
+__device__ __forceinline__ void dispersion_tasks_packed(const DispersionTaskArgs &a)
 {
     const int lane = threadIdx.x & 63, kp = a.lanes, li = lane & (kp - 1);
     const long long wave = (long long)blockIdx.x * (kDispersionThreads / 64) + (threadIdx.x >> 6);
@@ -101,9 +117,9 @@ __global__ __launch_bounds__(kDispersionThreads) void k_dispersion_tasks_packed(
     const bool task = slot < a.n;
     DispersionSetDev s{0, 1};
     const unsigned short *sig = a.sigma;
-    if (task) dispersion_task(a, slot, s, sig);
+    if (task) dispersion_task<kTable>(a, slot, s, sig);
     const bool live = task && li < s.count;
-    const int q = live ? (int)sig[a.set_pos[s.begin + li]] : 0;      // (an absent lane reads row 0, column 0, and adds nothing)
+    const int q = live ? dispersion_position<kTable>(a, sig, s.begin + li) : 0;      // (an absent lane reads row 0, column 0, and adds nothing)
     // every group walks K' columns: the exchange needs all lanes of the wave, and q_j of an absent lane j is never added
     const int group = lane - li, k = s.count;
     double sum = 0.0;
@@ -130,17 +146,18 @@ __global__ __launch_bounds__(kDispersionThreads) void k_dispersion_tasks_packed(
     if (task && li == 0) a.out[slot] = st_dispersion_record{sum, nearest};
 }
 
-__global__ __launch_bounds__(kDispersionThreads) void k_dispersion_tasks_wave(DispersionTaskArgs a)
+template <bool kTable>
+__device__ __forceinline__ void dispersion_tasks_wave(const DispersionTaskArgs &a)
 {
     const int lane = threadIdx.x & 63;
     const long long slot = (long long)blockIdx.x * (kDispersionThreads / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (slot >= a.n) return;      // (wave-uniform; no workgroup barrier below)
     DispersionSetDev s;
     const unsigned short *sig;
-    dispersion_task(a, slot, s, sig);
+    dispersion_task<kTable>(a, slot, s, sig);
     s = DispersionSetDev{__builtin_amdgcn_readfirstlane(s.begin), __builtin_amdgcn_readfirstlane(s.count)};      // (scalars: the j loop is uniform)
     const bool live = lane < s.count;
-    const int q = live ? (int)sig[a.set_pos[s.begin + lane]] : 0;
+    const int q = live ? dispersion_position<kTable>(a, sig, s.begin + lane) : 0;
     double sum;
     float m;
     dispersion_row(a.D + (size_t)q * (size_t)a.n_univ, s.count, lane, live, [&](int j) { return __builtin_amdgcn_readlane(q, j); }, sum, m);
@@ -152,18 +169,19 @@ __global__ __launch_bounds__(kDispersionThreads) void k_dispersion_tasks_wave(Di
     if (lane == 0) a.out[slot] = st_dispersion_record{sum, nearest};
 }
 
-__global__ __launch_bounds__(kDispersionThreads) void k_dispersion_tasks_group(DispersionTaskArgs a)
+template <bool kTable>
+__device__ __forceinline__ void dispersion_tasks_group(const DispersionTaskArgs &a)
 {
     extern __shared__ uint4 dispersion_q[];      // q as uint16, eight to a 16-byte read, padded with position 0
     __shared__ double wave_sum[kDispersionThreads / 64], wave_near[kDispersionThreads / 64];
     const int tid = threadIdx.x, lane = tid & 63;
     DispersionSetDev s;
     const unsigned short *sig;
-    dispersion_task(a, blockIdx.x, s, sig);      // (workgroup-uniform)
+    dispersion_task<kTable>(a, blockIdx.x, s, sig);      // (workgroup-uniform)
     s = DispersionSetDev{__builtin_amdgcn_readfirstlane(s.begin), __builtin_amdgcn_readfirstlane(s.count)};
     unsigned short *q16 = reinterpret_cast<unsigned short *>(dispersion_q);
     const int k = s.count, k8 = (k + 7) & ~7;
-    for (int i = tid; i < k8; i += kDispersionThreads) q16[i] = i < k ? sig[a.set_pos[s.begin + i]] : (unsigned short)0;
+    for (int i = tid; i < k8; i += kDispersionThreads) q16[i] = i < k ? (unsigned short)dispersion_position<kTable>(a, sig, s.begin + i) : (unsigned short)0;
     __syncthreads();
     double acc_sum = 0.0, acc_near = 0.0;
     for (int i = tid; i < k; i += kDispersionThreads) {
@@ -206,5 +224,13 @@ __global__ __launch_bounds__(kDispersionThreads) void k_dispersion_tasks_group(D
         a.out[blockIdx.x] = st_dispersion_record{t_sum, t_near};
     }
 }
+
+// the sigma form (the taxa-labels null) and the table form (the swap null) of the three task kernels
+__global__ __launch_bounds__(kDispersionThreads) void k_dispersion_tasks_packed(DispersionTaskArgs a) { dispersion_tasks_packed<false>(a); }
+__global__ __launch_bounds__(kDispersionThreads) void k_dispersion_tasks_wave(DispersionTaskArgs a) { dispersion_tasks_wave<false>(a); }
+__global__ __launch_bounds__(kDispersionThreads) void k_dispersion_tasks_group(DispersionTaskArgs a) { dispersion_tasks_group<false>(a); }
+__global__ __launch_bounds__(kDispersionThreads) void k_swap_tasks_packed(DispersionTaskArgs a) { dispersion_tasks_packed<true>(a); }
+__global__ __launch_bounds__(kDispersionThreads) void k_swap_tasks_wave(DispersionTaskArgs a) { dispersion_tasks_wave<true>(a); }
+__global__ __launch_bounds__(kDispersionThreads) void k_swap_tasks_group(DispersionTaskArgs a) { dispersion_tasks_group<true>(a); }
 
 }  // namespace st

@@ -55,6 +55,9 @@
 // MPD / MNTD sums of many leaf sets under the taxa-labels null (st_partner_dispersion_host, st_dispersion_matrix):
 // kernels_dispersion.h (one sort per permutation, the k x k reducer in three size classes), host_dispersion.h (the chunk
 // driver) and, host-only, dispersion_plan.cpp (argument checks, size classes, chunks, the restatement of the reduction).
+// The same sums under the degree-preserving swap null (st_swap_null_tables, st_dispersion_matrix_swap,
+// st_partner_dispersion_swap_host): kernels_swap.h (one wave per Markov chain of swaps), the table form of kernels_dispersion.h's
+// reducers, host_swap.h (the block of chains, the chunk loop with the chains as its producer) and, host-only, swap_plan.cpp.
 // betaMPD / betaMNTD sums between every two leaf sets under the same null (st_beta_dispersion_host, st_beta_dispersion_matrix):
 // kernels_setpair.h (the k_r x k_c reducer in the same three size classes), host_dispersion.h (one launcher, chunk driver,
 // tree run and matrix run for both passes) and, host-only, setpair_plan.cpp (argument checks, the task table, the restatement).
@@ -208,6 +211,7 @@ static int device_index_arg(int device)
 #include "kernels_perm.h"
 #include "kernels_hommola.h"
 #include "kernels_dispersion.h"
+#include "kernels_swap.h"
 #include "kernels_setpair.h"
 #include "kernels_unifrac.h"
 #include "kernels_unifrac_null.h"
@@ -234,6 +238,7 @@ using namespace st;
 #include "host_quartets.h"
 #include "host_hommola.h"
 #include "host_dispersion.h"
+#include "host_swap.h"
 #include "host_unifrac.h"
 #include "host_unifrac_null.h"
 #include "host_clade_match.h"
@@ -940,6 +945,78 @@ try {
         return ST_OK;
     }
     return record_matrix_device("dispersion matrix", device, D, P, set_pos, n_pos, seed, stream, out);
+} ST_CATCH_ALL
+
+int st_swap_null_tables(int device, int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets, int64_t p_begin,
+                        int64_t n_perms, int64_t iterations, uint64_t seed, int32_t stream, uint16_t *out, int64_t *accepted)
+try {
+    SwapPlan S;
+    std::string err;
+    const int rc = swap_tables_args(n_univ, set_pos, n_pos, sets, n_sets, p_begin, n_perms, iterations, stream, S, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (device_or_host_arg(device) != ST_OK) return ST_ERR_ARG;
+    if (n_perms > 0 && n_pos > 0 && !out) return fail(ST_ERR_ARG, "out is NULL");
+    if (n_perms == 0) return ST_OK;
+    if (device < 0) {
+        std::vector<uint16_t> none(1);
+        for (int64_t p = 0; p < n_perms; p++)
+            swap_chain_host(S, set_pos, sets, seed, stream, p_begin + p, n_pos > 0 ? out + p * n_pos : none.data(), accepted ? accepted + p : nullptr);
+        return ST_OK;
+    }
+    return swap_tables_device(device, S, set_pos, sets, p_begin, n_perms, seed, stream, out, accepted);
+} ST_CATCH_ALL
+
+int st_swap_null_schedule(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets, int64_t p, int64_t iterations,
+                          uint64_t seed, int32_t stream, uint16_t *out, int64_t *accepted, int64_t *steps)
+try {
+    SwapPlan S;
+    std::string err;
+    const int rc = swap_tables_args(n_univ, set_pos, n_pos, sets, n_sets, p, 1, iterations, stream, S, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (n_pos > 0 && !out) return fail(ST_ERR_ARG, "out is NULL");
+    std::vector<uint16_t> none(1);
+    int64_t n_steps = 0;
+    swap_chain_host(S, set_pos, sets, seed, stream, p, n_pos > 0 ? out : none.data(), accepted, true, &n_steps);
+    if (steps) *steps = n_steps;
+    return ST_OK;
+} ST_CATCH_ALL
+
+int st_dispersion_matrix_swap(int device, const float *D, int32_t n, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets,
+                              int64_t permutations, int64_t iterations, uint64_t seed, int32_t stream, int64_t chunk_tasks,
+                              st_dispersion_record *out, int64_t *accepted)
+try {
+    DispersionPlan P;
+    SwapPlan S;
+    std::string err;
+    const int rc = swap_dispersion_plan(n, set_pos, n_pos, sets, n_sets, permutations, iterations, stream, chunk_tasks, P, S, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (device_or_host_arg(device) != ST_OK) return ST_ERR_ARG;
+    if (!D) return fail(ST_ERR_ARG, "D is NULL");
+    if (n_sets > 0 && !out) return fail(ST_ERR_ARG, "out is NULL");
+    if (device < 0 || P.chunks.empty()) {
+        swap_dispersion_host(D, P, S, set_pos, sets, seed, stream, out, accepted);
+        return ST_OK;
+    }
+    return swap_record_matrix_device("swap dispersion matrix", device, D, P, S, set_pos, sets, seed, stream, out, accepted);
+} ST_CATCH_ALL
+
+int st_partner_dispersion_swap_host(st_tree *t, const int64_t *univ, int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets,
+                                    int64_t n_sets, int64_t permutations, int64_t iterations, uint64_t seed, int32_t stream, int64_t chunk_tasks,
+                                    st_dispersion_record *out, int64_t *accepted, int64_t *bad_id)
+try {
+    DispersionPlan P;
+    SwapPlan S;
+    std::string err;
+    int rc = swap_dispersion_plan(n_univ, set_pos, n_pos, sets, n_sets, permutations, iterations, stream, chunk_tasks, P, S, err);
+    if (rc != ST_OK) return fail(rc, err);
+    rc = set_tree_args(t, univ, n_univ, n_sets > 0 && !out, nullptr, bad_id);
+    if (rc != ST_OK) return rc;
+    if (P.chunks.empty()) {      // (no set of two positions: no record to compute, the chains run on the host)
+        std::fill_n(out, P.n_sets * P.rows, st_dispersion_record{0.0, 0.0});
+        swap_accepted_host(S, set_pos, sets, P.rows, seed, stream, accepted);
+        return ST_OK;
+    }
+    return swap_record_tree_run("partner dispersion (swap null)", t, univ, P, S, set_pos, sets, seed, stream, out, accepted, bad_id);
 } ST_CATCH_ALL
 
 int st_beta_dispersion_host(st_tree *t, const int64_t *univ, int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets,

@@ -502,7 +502,8 @@ class SuchLinkedTrees:
             observed = swapped
         return compare.CladeHommola(rows, leaves[rows], count[rows], observed, n_ge, n_nan, stats, permutations, seed, tree, skipped)
 
-    def partner_dispersion(self, of="A", permutations=999, seed=None, pool="subset", min_partners=2, max_partners=None, keep_null=False):
+    def partner_dispersion(self, of="A", permutations=999, seed=None, pool="subset", min_partners=2, max_partners=None, keep_null=False,
+                           null="taxa.labels", iterations=None):
         """Phylogenetic specificity: for each leaf, are its partners in the other tree close relatives of one another?
 
         ``of="A"``: one row per TreeA leaf of the current ``subset_a`` (in ``subset_a_leafs`` order) with at least
@@ -517,15 +518,35 @@ class SuchLinkedTrees:
         with ``stream`` = the partner tree's subset root.  A universe of more than 16384 leaves is a ValueError: subset it
         first.  No row, nothing launched.
 
+        ``null="swap"`` standardises against the degree-preserving swap null (:meth:`SuchTree.dispersion`): the link
+        matrix is shuffled by chains of ``iterations`` trial swaps that keep every leaf's number of partners on both
+        sides, so widespread partner leaves stay widespread in every draw.  The matrix is every leaf of the own subset
+        with at least one partner in the universe; ``min_partners`` / ``max_partners`` only choose which rows are
+        reported, a reported row's columns do not depend on them, and ``pool`` only bounds the universe (a column without
+        links stays empty).  ``iterations=None`` is max(1000, 10 x the links), the library's own default.
+
         The subset state, ``linklist`` and the generator of :meth:`sample_linked_distances` are left as they were.
         Returns a :class:`~suchtree_amd.compare.SetDispersion` with ``leaves`` (the rows' leaf ids) and ``names``.
         An extension: the reference has no counterpart.
         """
+        from .suchtree import null_model_arg
+        null, iterations = null_model_arg(null, iterations)
+        if null == "swap":
+            lo = max(int_arg("min_partners", min_partners, optional=True) or 0, 1)
+            hi = int_arg("max_partners", max_partners, optional=True)
+            reported = []      # the rows of the matrix (one partner and more) that the call reports
+
+            def run_swap(partner, sets, root, universe):
+                reported.extend(i for i, s in enumerate(sets) if len(s) >= lo and (hi is None or len(s) <= hi))
+                return partner.dispersion(sets, universe=universe, permutations=permutations, seed=seed, stream=root, keep_null=keep_null,
+                                          null="swap", iterations=iterations, _report=reported)
+            return self._over_partner_rows(of, 1, None, run_swap, pool, _capi.HOMMOLA_MAX_UNIVERSE, reported)
+
         def run(partner, sets, root, universe):
             return partner.dispersion(sets, universe=universe, permutations=permutations, seed=seed, stream=root, keep_null=keep_null)
         return self._over_partner_rows(of, min_partners, max_partners, run, pool, _capi.HOMMOLA_MAX_UNIVERSE)
 
-    def _over_partner_rows(self, of, min_partners, max_partners, run, pool="subset", pool_limit=None):
+    def _over_partner_rows(self, of, min_partners, max_partners, run, pool="subset", pool_limit=None, reported=None):
         """What partner_dispersion, partner_unifrac and partner_beta_dispersion share: the checks of ``of``, ``pool`` and the partner counts, the rows
         (_partner_rows), ``run(partner tree, the rows' partner ids, partner subset root, universe)``, then the result's
         ``leaves`` and ``names``.  With ``pool_limit`` the universe is ``pool`` of the partner tree -- "subset" = every leaf
@@ -548,6 +569,8 @@ class SuchLinkedTrees:
                                  % ("subset" if pool == "subset" else "linked leaves", len(universe), pool_limit))
         own, partner, root, leaves, sets = self._partner_rows(of, min_partners, max_partners, ll)
         out = run(partner, sets, root, universe)
+        if reported is not None:      # (the swap null: `run` reports these of the rows it was given)
+            leaves = [leaves[i] for i in reported]
         out.leaves = np.asarray(leaves, dtype=np.int64)
         names = own.leaf_nodes
         out.names = [names[int(v)] for v in leaves]

@@ -73,6 +73,16 @@ def _null_args(permutations, seed, stream, chunk_tasks):
             int_arg("chunk_tasks", chunk_tasks))
 
 
+def null_model_arg(null, iterations):
+    """The null model of ``dispersion`` / ``partner_dispersion``: "taxa.labels" or "swap"; ``iterations`` (None or a
+    non-negative integer) belongs to "swap" alone.  ValueError otherwise."""
+    if null not in ("taxa.labels", "swap"):
+        raise ValueError("null must be 'taxa.labels' or 'swap', got %r" % (null,))
+    if null == "taxa.labels" and iterations is not None:
+        raise ValueError("iterations belongs to null='swap': the taxa.labels null has no chain")
+    return null, int_arg("iterations", iterations, optional=True)
+
+
 def _triangle_range(n_rows, begin, count):
     """(begin, count) of pairs [begin, begin + count) of the triangle over ``n_rows`` sets; ``count`` None = up to the last
     pair, which above 2^31 pairs is a ValueError."""
@@ -698,7 +708,8 @@ class SuchTree(TreeNavigation):
             rows.append(ids)
         return univ, rows
 
-    def dispersion(self, sets, universe=None, permutations=999, seed=None, stream=0, keep_null=False, chunk_tasks=0):
+    def dispersion(self, sets, universe=None, permutations=999, seed=None, stream=0, keep_null=False, chunk_tasks=0, null="taxa.labels",
+                   iterations=None, _report=None):
         """How closely related are the members of each set of leaves: MPD and MNTD with a permutation null, on the GPU.
 
         ``sets`` is an iterable of collections of leaf names or leaf ids.  For each, ``mpd`` is the mean pairwise distance
@@ -714,13 +725,34 @@ class SuchTree(TreeNavigation):
         order (children in increasing id order); a set's columns depend on (seed, ``stream``, the universe, the set)
         alone -- not on the other sets or ``chunk_tasks`` -- and null column p is the same for any ``permutations`` >= p.
         ``seed=None`` draws a seed and reports it.  ``keep_null=True`` keeps the (sets, permutations) null draws.
+
+        ``null="swap"`` standardises against the degree-preserving swap null instead (picante's ``independentswap`` /
+        ``trialswap``, the fixed-fixed null of bipartite networks): the sets are the rows of a 0/1 matrix over the
+        universe, and null draw p is that matrix after a chain of ``iterations`` trial swaps
+        (:func:`~suchtree_amd.compare.swap_null_tables`), which keeps every set's size *and* the number of sets each leaf
+        belongs to.  A clustered set that is only the signature of a few widespread leaves is not significant under it.
+        ``iterations=None`` is max(1000, 10 x the links of the matrix) trials, the library's own default (picante's is
+        1000 swaps); with the default null it must stay None.  All sets of the call form one matrix, so a set's null
+        columns depend on the other sets; they do not depend on ``chunk_tasks``, and column p is the same for any
+        ``permutations`` >= p.  ``swap_accepted`` of the result holds the swaps each chain made.
+
         Returns a :class:`~suchtree_amd.compare.SetDispersion`.  An extension: the reference has no counterpart.
         """
         from . import compare
+        null, iterations = null_model_arg(null, iterations)
         permutations, seed, stream, chunk_tasks = _null_args(permutations, seed, stream, chunk_tasks)
         univ, rows = self._universe_and_sets(sets, universe)
         set_pos, offsets = self._position_table(univ, rows)
         k = np.diff(offsets)
+        if null == "swap":      # one matrix, one call: the chains run over every row, `_report` (partner_dispersion) picks the rows kept
+            keep = np.arange(len(rows)) if _report is None else np.asarray(_report, dtype=np.int64)
+            iterations = _capi.swap_iterations(iterations, len(set_pos))
+            out = compare.SetDispersion(len(keep), permutations, seed, len(univ), keep_null, null, iterations)
+            if len(keep):      # (no row to report: nothing is launched, and the tree stays where it is)
+                rec, out.swap_accepted = self._device_tree().partner_dispersion_swap_host(univ, (set_pos, offsets), permutations, seed, iterations,
+                                                                                         stream, chunk_tasks)
+                out.fill(0, k[keep], rec[keep])
+            return out
         out = compare.SetDispersion(len(rows), permutations, seed, len(univ), keep_null)
         per_group = max(1, self._DISPERSION_GROUP_ROWS // (permutations + 1))
         for at in range(0, len(rows), per_group):      # (no sets: nothing is launched, and the tree stays where it is)
