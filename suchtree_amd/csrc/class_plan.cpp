@@ -8,8 +8,7 @@ namespace st {
 int class_plan(const int32_t *y, const uint8_t *cls, int32_t n, int32_t n_classes, int64_t permutations, int32_t stream, int64_t chunk_tasks,
                int32_t slice, const int64_t *out, ClassPlan &P, std::string &err)
 {
-    if (const int rc = dispersion_call_args(n, permutations, chunk_tasks, stream, err); rc != ST_OK) return rc;
-    if (permutations > INT32_MAX) return fail(ST_ERR_ARG, err, "more than 2^31 - 1 permutations");
+    if (const int rc = matrix_call_args(n, permutations, chunk_tasks, stream, err); rc != ST_OK) return rc;
     if (n_classes < 1 || n_classes > kClassMax) return fail(ST_ERR_ARG, err, std::to_string(n_classes) + " classes: 1 to " + std::to_string(kClassMax));
     if (!y || !cls) return fail(ST_ERR_ARG, err, "y or cls is NULL");
     if (!out) return fail(ST_ERR_ARG, err, "out is NULL");
@@ -26,20 +25,7 @@ int class_plan(const int32_t *y, const uint8_t *cls, int32_t n, int32_t n_classe
     P.items = P.wave ? 1 : ((int64_t)n + 1) / 2;
     P.slice = slice;
 
-    int64_t block = std::max<int64_t>(1, std::min(kDispersionSigmaBytes / (2 * (int64_t)n), kClassPartBytes / (8 * (int64_t)n_classes * P.items)));
-    int64_t cap = kDispersionChunkTasks;
-    if (chunk_tasks > 0) {
-        block = std::min(block, chunk_tasks);
-        cap = std::min(chunk_tasks, kDispersionMaxChunkTasks);
-    }
-    P.perm_block = std::min(block, P.rows);
-    for (int64_t p0 = 0; p0 < P.rows; p0 += P.perm_block) {
-        const int64_t np = std::min(P.perm_block, P.rows - p0), tasks = class_block_tasks(P, np);
-        for (int64_t t = 0; t < tasks; t += cap) {
-            P.chunks.push_back(DispersionChunk{p0, np, t, std::min(cap, tasks - t)});
-            P.max_chunk_tasks = std::max(P.max_chunk_tasks, P.chunks.back().n_tasks);
-        }
-    }
+    matrix_cut(P, std::min(kDispersionSigmaBytes / (2 * (int64_t)n), kClassPartBytes / (8 * (int64_t)n_classes * P.items)), chunk_tasks, P.wave ? 1 : slice);
     return ST_OK;
 }
 

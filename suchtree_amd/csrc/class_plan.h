@@ -2,7 +2,7 @@
 // compare.mantel_correlogram), plain C++17.  No GPU calls in here (class_plan.cpp): the "not gpu" tests run it under the
 // address / undefined-behaviour sanitizers (tests/emu/sanitize_class.cpp).  The definitions are the contract of
 // include/suchtree_hip.h (st_class_sums_codes); the permutation, its blocks and the chunk record are those of
-// dispersion_plan.h, the cut into tasks that of group_plan.h.
+// dispersion_plan.h, the cut into tasks that of its SlicedPlan.
 //
 // Layout.  n > kClassWaveMax: the row form.  An item is a row pair r < (n + 1) / 2 -- rows r and n - 1 - r, the middle
 // row alone when n is odd -- so that every item has n - 1 pairs (the middle row half as many).  A block of n_perms
@@ -27,21 +27,10 @@ constexpr int kClassSlice = 32;                           // permutations per ta
 constexpr int kClassSliceMax = 256;                       // bound of SUCHTREE_AMD_CLASS_SLICE
 constexpr int64_t kClassPartBytes = (int64_t)256 << 20;   // bound of a block's partial sums (8 n_classes bytes per row pair and permutation)
 
-struct ClassPlan {
-    int32_t n = 0, n_classes = 0;
-    int64_t rows = 0;             // permutations + 1 rows of out
-    bool wave = false;
-    int64_t items = 0;            // 1 (wave form) or (n + 1) / 2 row pairs
-    int32_t slice = 0;            // permutations per task of the row form
-    int64_t perm_block = 0;
-    std::vector<DispersionChunk> chunks;      // n_tasks and task_begin count the block's tasks of the layout above
-    int64_t max_chunk_tasks = 0;
+struct ClassPlan : SlicedPlan {      // rows of out; a row of the class square is sliced_stride(n) bytes
+    int32_t n_classes = 0;
 };
 
-inline int64_t class_slices(int64_t n_perms, int32_t slice) { return (n_perms + slice - 1) / slice; }
-// the tasks of a block of n_perms permutations
-inline int64_t class_block_tasks(const ClassPlan &P, int64_t n_perms) { return P.wave ? n_perms : P.items * class_slices(n_perms, P.slice); }
-inline size_t class_stride(int32_t n) { return ((size_t)n + 15) & ~(size_t)15; }      // bytes of a row of the class square
 // pair (a, b), a != b, of the triangle
 inline size_t class_pair(int32_t a, int32_t b) { return a > b ? (size_t)a * (size_t)(a - 1) / 2 + (size_t)b : (size_t)b * (size_t)(b - 1) / 2 + (size_t)a; }
 

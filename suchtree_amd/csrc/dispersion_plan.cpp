@@ -19,22 +19,67 @@ int dispersion_call_args(int32_t n_univ, int64_t permutations, int64_t chunk_tas
     return ST_OK;
 }
 
+int matrix_call_args(int32_t n, int64_t permutations, int64_t chunk_tasks, int32_t stream, std::string &err)
+{
+    if (const int rc = dispersion_call_args(n, permutations, chunk_tasks, stream, err); rc != ST_OK) return rc;
+    if (permutations > INT32_MAX) return fail(ST_ERR_ARG, err, "more than 2^31 - 1 permutations");
+    return ST_OK;
+}
+
+// the first cell (row-major) of the square matrix x whose mirror differs, scanned in tiles (the mirror of a row is a
+// column); false: x is symmetric
+static bool asymmetric(const int32_t *x, int64_t n, int64_t &bad_i, int64_t &bad_j)
+{
+    constexpr int64_t T = 64;
+    bool found = false;
+    for (int64_t i0 = 0; i0 < n && !found; i0 += T)
+        for (int64_t j0 = 0; j0 <= i0 && !found; j0 += T)
+            for (int64_t i = i0; i < std::min(i0 + T, n) && !found; i++)
+                for (int64_t j = j0; j < std::min(j0 + T, i); j++)
+                    if (x[i * n + j] != x[j * n + i]) {
+                        found = true;
+                        break;
+                    }
+    if (!found) return false;
+    for (int64_t i = 0; i < n; i++)      // (the error path: which one comes first)
+        for (int64_t j = 0; j < n; j++)
+            if (x[i * n + j] != x[j * n + i]) {
+                bad_i = i;
+                bad_j = j;
+                return true;
+            }
+    return false;
+}
+
+int symmetric_arg(const char *name, const int32_t *x, int32_t n, std::string &err)
+{
+    int64_t bi = 0, bj = 0;
+    if (!asymmetric(x, n, bi, bj)) return ST_OK;
+    const std::string g(name);
+    return fail(ST_ERR_ARG, err, g + " is not symmetric: " + g + "[" + std::to_string(bi) + "][" + std::to_string(bj) + "] = " +
+                                     std::to_string(x[bi * n + bj]) + ", " + g + "[" + std::to_string(bj) + "][" + std::to_string(bi) + "] = " +
+                                     std::to_string(x[bj * n + bi]));
+}
+
 void dispersion_cut(int32_t n_univ, int64_t rows, int64_t live, int64_t chunk_tasks, int64_t &perm_block, std::vector<DispersionChunk> &chunks,
                     int64_t &max_chunk_tasks, int64_t table_entries)
 {
-    int64_t block = std::max<int64_t>(1, kDispersionSigmaBytes / (2 * ((int64_t)n_univ + table_entries)));
-    if (chunk_tasks > 0) block = std::min(block, chunk_tasks);
-    dispersion_cut_blocks(rows, live, block, chunk_tasks, perm_block, chunks, max_chunk_tasks);
+    dispersion_cut_blocks(rows, live, kDispersionSigmaBytes / (2 * ((int64_t)n_univ + table_entries)), chunk_tasks, perm_block, chunks, max_chunk_tasks);
 }
 
 void dispersion_cut_blocks(int64_t rows, int64_t live, int64_t block, int64_t chunk_tasks, int64_t &perm_block, std::vector<DispersionChunk> &chunks,
-                           int64_t &max_chunk_tasks)
+                           int64_t &max_chunk_tasks, int32_t slice)
 {
-    const int64_t cap = chunk_tasks > 0 ? std::min(chunk_tasks, kDispersionMaxChunkTasks) : kDispersionChunkTasks;
+    block = std::max<int64_t>(1, block);
+    int64_t cap = kDispersionChunkTasks;
+    if (chunk_tasks > 0) {
+        block = std::min(block, chunk_tasks);
+        cap = std::min(chunk_tasks, kDispersionMaxChunkTasks);
+    }
     perm_block = std::min(block, rows);
     if (live == 0) return;
     for (int64_t p0 = 0; p0 < rows; p0 += perm_block) {
-        const int64_t np = std::min(perm_block, rows - p0), tasks = live * np;
+        const int64_t np = std::min(perm_block, rows - p0), tasks = live * dispersion_slices(np, slice);
         for (int64_t t = 0; t < tasks; t += cap) {
             chunks.push_back(DispersionChunk{p0, np, t, std::min(cap, tasks - t)});
             max_chunk_tasks = std::max(max_chunk_tasks, chunks.back().n_tasks);

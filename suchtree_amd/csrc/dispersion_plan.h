@@ -72,17 +72,59 @@ struct DispersionPlan {
 int dispersion_plan(int32_t n_univ, const int32_t *set_pos, int64_t n_pos, const int64_t *sets, int64_t n_sets, int64_t permutations,
                     int32_t stream, int64_t chunk_tasks, DispersionPlan &P, std::string &err);
 
-// What setpair_plan.cpp shares with this unit.  The first checks of a call, in this order: the universe size, nothing
-// negative (permutations, chunk_tasks, stream).  The cut of `live` tasks a permutation over `rows` permutations into blocks
-// and chunks by the rule above; a caller that keeps `table_entries` further 16-bit entries a permutation beside the sigma
-// row (unifrac_null_plan.cpp) has them counted towards the block's bound.  What a wave does with `a += shfl_xor(a, o)` over offsets width / 2 .. 1: v[0 .. width)
-// in, every lane's total out.
+// What the other plan units share with this one.  The first checks of a call, in this order: the universe size, nothing
+// negative (permutations, chunk_tasks, stream).  What a wave does with `a += shfl_xor(a, o)` over offsets width / 2 .. 1:
+// v[0 .. width) in, every lane's total out.
 int dispersion_call_args(int32_t n_univ, int64_t permutations, int64_t chunk_tasks, int32_t stream, std::string &err);
+
+// permutations per task `slice` >= 1: the slices of n_perms permutations, the last one shorter (group_plan.h, class_plan.h)
+inline int64_t dispersion_slices(int64_t n_perms, int32_t slice) { return (n_perms + slice - 1) / slice; }
+
+// The one cut of `rows` permutations into blocks and chunks, by the rule above.  A block is up to `block` permutations (the
+// caller's bound, whatever holds a block's rows; below 1 counts as 1) and has live * dispersion_slices(its permutations,
+// slice) tasks: `live` tasks a permutation where slice = 1.  chunk_tasks 0 = chunks of kDispersionChunkTasks tasks;
+// chunk_tasks > 0 = at most that many tasks per chunk and permutations per block.  live = 0: no chunk.
+void dispersion_cut_blocks(int64_t rows, int64_t live, int64_t block, int64_t chunk_tasks, int64_t &perm_block, std::vector<DispersionChunk> &chunks,
+                           int64_t &max_chunk_tasks, int32_t slice = 1);
+// the cut of the set plans: blocks of up to kDispersionSigmaBytes of sigma rows; a caller that keeps `table_entries` further
+// 16-bit entries a permutation beside the sigma row (unifrac_null_plan.cpp) has them counted towards the block's bound
 void dispersion_cut(int32_t n_univ, int64_t rows, int64_t live, int64_t chunk_tasks, int64_t &perm_block, std::vector<DispersionChunk> &chunks,
                     int64_t &max_chunk_tasks, int64_t table_entries = 0);
-// the same cut for blocks of up to `block` >= 1 permutations, whatever holds a block's rows (swap_plan.cpp: chains)
-void dispersion_cut_blocks(int64_t rows, int64_t live, int64_t block, int64_t chunk_tasks, int64_t &perm_block, std::vector<DispersionChunk> &chunks,
-                           int64_t &max_chunk_tasks);
+
+// What the matrix permutation plans have in common (MantelPlan, GroupPlan, ClassPlan, ParafitPlan): a statistic of whole
+// matrices under every permutation, one item (the wave form) or `items` rows of work a permutation, folded block by block
+// on the device (matrix_block_chunks, host_dispersion.h).
+struct MatrixPlan {
+    int64_t rows = 0;             // permutations + 1 records
+    bool wave = false;
+    int64_t items = 0;            // 1 (wave form), or the row form's items a permutation
+    int64_t perm_block = 0;
+    std::vector<DispersionChunk> chunks;
+    int64_t max_chunk_tasks = 0;
+};
+// its cut: dispersion_cut_blocks over its rows and items
+inline void matrix_cut(MatrixPlan &P, int64_t block, int64_t chunk_tasks, int32_t slice = 1)
+{
+    dispersion_cut_blocks(P.rows, P.items, block, chunk_tasks, P.perm_block, P.chunks, P.max_chunk_tasks, slice);
+}
+
+// A matrix plan whose row form gives a task `slice` permutations of one row pair (GroupPlan, ClassPlan).  n > 64: an item is
+// a row pair r < (n + 1) / 2 -- rows r and n - 1 - r, the middle row alone when n is odd; a block of n_perms permutations
+// from p0 is cut into n_slices = dispersion_slices(n_perms, slice) and task t = r * n_slices + s is row pair r under slice
+// s.  Up to 64: the wave form, one item, task t is permutation p0 + t of the block.
+struct SlicedPlan : MatrixPlan {
+    int32_t n = 0;
+    int32_t slice = 0;            // permutations per task of the row form
+};
+// the tasks of a block of n_perms permutations
+inline int64_t sliced_block_tasks(const SlicedPlan &P, int64_t n_perms) { return P.items * dispersion_slices(n_perms, P.wave ? 1 : P.slice); }
+inline size_t sliced_stride(int32_t n) { return ((size_t)n + 15) & ~(size_t)15; }      // bytes of a row of n bytes that 16-byte loads read
+
+// The first checks of the matrix plans over one universe (mantel, group, class): those of dispersion_call_args, then at
+// most 2^31 - 1 permutations.
+int matrix_call_args(int32_t n, int64_t permutations, int64_t chunk_tasks, int32_t stream, std::string &err);
+// ST_OK, or ST_ERR_ARG naming the first cell (row-major) of the n x n matrix x, called `name`, whose mirror differs
+int symmetric_arg(const char *name, const int32_t *x, int32_t n, std::string &err);
 void dispersion_butterfly(double *v, int width);
 
 // `order` by (size class, `before` within a class, index) and the class ranges of the layout above: cls(x) is the size

@@ -29,21 +29,9 @@ struct GroupPart {      // the partial record of (row i, permutation p): the sum
     int32_t reserved;
 };
 
-struct GroupPlan {
-    int32_t n = 0, n_groups = 0;
-    int64_t rows = 0;             // permutations + 1 rows of out
-    bool wave = false;
-    int64_t items = 0;            // 1 (wave form) or (n + 1) / 2 row pairs
-    int32_t slice = 0;            // permutations per task of the row form
-    int64_t perm_block = 0;
-    std::vector<DispersionChunk> chunks;      // n_tasks and task_begin count the block's tasks of the layout above
-    int64_t max_chunk_tasks = 0;
+struct GroupPlan : SlicedPlan {      // rows of out; a row of relabelled labels is sliced_stride(n) bytes
+    int32_t n_groups = 0;
 };
-
-inline int64_t group_slices(int64_t n_perms, int32_t slice) { return (n_perms + slice - 1) / slice; }
-// the tasks of a block of n_perms permutations
-inline int64_t group_block_tasks(const GroupPlan &P, int64_t n_perms) { return P.wave ? n_perms : P.items * group_slices(n_perms, P.slice); }
-inline size_t group_stride(int32_t n) { return ((size_t)n + 15) & ~(size_t)15; }      // bytes of a row of relabelled labels
 
 // ST_OK, or ST_ERR_ARG with `err`.  Checks, in this order: those of dispersion_call_args (n in 3 .. kPermMaxUniverse,
 // nothing negative among permutations, chunk_tasks, stream), at most 2^31 - 1 permutations, n_groups in 1 .. kGroupMax,

@@ -104,6 +104,56 @@ static int perm_block_chunks(ReadbackRing<T, const DispersionChunk *> &ring, con
         launch, scatter_to);
 }
 
+// Every chunk of a matrix plan (MatrixPlan, dispersion_plan.h: host_mantel.h, host_group.h, host_class.h, host_parafit.h)
+// on stream s: the loop over blocks of permutations and their chunks of the calls that fold a block on the device and
+// read nothing back per chunk (which is why it is not perm_block_chunks_of: no ring).  produce(chunk, stream) enqueues a
+// new block's rows, launch(chunk, stream) a chunk's tasks, fold(chunk) whatever completes the block of its last chunk.
+// Stream order carries the loop: a block's fold is enqueued after its last chunk and before the next block's rows, so it
+// reads what the block's tasks left, and the rows that those tasks read are overwritten only behind them.  A fold that
+// hands a block to the host (ParaFit's link records) synchronises before it returns.  Returns ST_OK, or ST_ERR_HIP with
+// `what` and " launch: "; the read-back is the caller's.
+template <typename Produce, typename Launch, typename Fold>
+static int matrix_block_chunks(const char *what, hipStream_t s, const std::vector<DispersionChunk> &chunks, Produce produce, Launch launch, Fold fold)
+{
+    hipError_t e = hipSuccess;
+    const DispersionChunk *prev = nullptr;
+    for (const DispersionChunk &c : chunks) {
+        if (!prev || c.p_begin != prev->p_begin) {
+            if (prev) e = fold(*prev);
+            if (e == hipSuccess) e = produce(c, s);
+        }
+        if (e == hipSuccess) e = launch(c, s);
+        if (e != hipSuccess) break;
+        prev = &c;
+    }
+    if (e == hipSuccess && prev) e = fold(*prev);
+    if (e != hipSuccess) return fail(ST_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+    return ST_OK;
+}
+
+// the stream and the work block of `total` bytes of such a call (the caller declares d_work before s): ST_OK, ST_ERR_HIP
+// or ST_ERR_NOMEM
+static int open_work_block(const char *what, DrainedStream &s, DevBuf<char> &d_work, size_t total)
+{
+    hipError_t e = s.create();
+    if (e != hipSuccess) return fail(ST_ERR_HIP, std::string(what) + " setup: " + hipGetErrorString(e));
+    e = d_work.alloc(total);
+    if (e == hipSuccess) return ST_OK;
+    (void)hipGetLastError();
+    return fail(ST_ERR_NOMEM, std::string(what) + ": a work block of " + std::to_string(total) + " bytes: " + hipGetErrorString(e));
+}
+
+// the permutations per task of a sliced plan: `dflt`, or the environment variable `name` = 1 .. max (read at every call; a
+// measurement's: no result depends on it; anything else falls back to dflt)
+static int32_t perm_slice_env(const char *name, int32_t dflt, int32_t max)
+{
+    const char *v = std::getenv(name);
+    if (!v || !*v) return dflt;
+    char *end = nullptr;
+    const long s = std::strtol(v, &end, 10);
+    return (*end == 0 && s >= 1 && s <= max) ? (int32_t)s : dflt;
+}
+
 // A plan of records -- DispersionPlan over its sets, SetpairPlan over its directions -- on stream s, with the caller's work
 // block and ring (declared before the stream's owner): the positions, `table` beside them, one block of sigma rows and two
 // chunks of records, then perm_block_chunks.  launch(chunk, sigma, set_pos, table, records, stream) enqueues a chunk's

@@ -1,4 +1,5 @@
-// host_mantel.h -- part of suchtree_hip.hip (included after host_dispersion.h, whose dispersion_launch_sigma it uses).
+// host_mantel.h -- part of suchtree_hip.hip (included after host_dispersion.h, whose dispersion_launch_sigma, work block
+// opener and loop over blocks and chunks -- matrix_block_chunks -- it uses).
 // The device side of st_mantel_codes (kernels_mantel.h; the plan and the host restatement: mantel_plan.cpp).  One work
 // block: x_sq, y and z as uploaded, one block of sigma rows, the block's partial records (row form) and the call's
 // records.  Per block of permutations: its sorts (k_dispersion_sigma); per chunk of tasks one launch; after a block's
@@ -40,16 +41,10 @@ static int mantel_device(int device, const MantelPlan &P, const int32_t *x_sq, c
     const size_t o_part = o_sigma + align256((size_t)P.perm_block * n * 2);
     const size_t o_out = o_part + align256(P.wave ? 0 : (size_t)(P.items * P.perm_block) * sizeof(st_mantel_sums));
     const size_t total = o_out + align256((size_t)P.rows * sizeof(st_mantel_sums));
-    hipError_t e = s.create();
-    if (e != hipSuccess) return fail(ST_ERR_HIP, std::string(what) + " setup: " + hipGetErrorString(e));
-    e = d_work.alloc(total);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ST_ERR_NOMEM, std::string(what) + ": a work block of " + std::to_string(total) + " bytes: " + hipGetErrorString(e));
-    }
+    if (const int rc = open_work_block(what, s, d_work, total); rc != ST_OK) return rc;
     char *const d = d_work;
     const size_t row_lds = (n * 4 + 15) & ~(size_t)15;
-    e = hipMemcpyAsync(d, x_sq, n * n * 4, hipMemcpyHostToDevice, s);
+    hipError_t e = hipMemcpyAsync(d, x_sq, n * n * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d + o_y, y, m * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && P.partial) e = hipMemcpyAsync(d + o_z, z, m * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = perm_lds_opt_in(k_dispersion_sigma<kPermLargeThreads>, perm_lds_bytes((int)n));      // (above 32 KiB: the large class)
@@ -64,23 +59,15 @@ static int mantel_device(int device, const MantelPlan &P, const int32_t *x_sq, c
         hipLaunchKernelGGL(k_mantel_fold, dim3((unsigned)c.n_perms), dim3(64), 0, s, d_part, (int)P.items, (unsigned)c.n_perms, d_out + c.p_begin);
         return hipGetLastError();
     };
-    const DispersionChunk *prev = nullptr;
-    for (const DispersionChunk &c : P.chunks) {
-        if (!prev || c.p_begin != prev->p_begin) {      // (stream order: the tasks of the block before have read their rows)
-            if (prev) e = fold(*prev);
-            if (e == hipSuccess)
-                e = dispersion_launch_sigma(DispersionSigmaArgs{d_sigma, (long long)c.p_begin, (unsigned long long)seed, (int)stream, (int)n}, c.n_perms, s);
-        }
-        if (e == hipSuccess) {
-            const MantelArgs a{reinterpret_cast<const int *>(d), reinterpret_cast<const int *>(d + o_y), reinterpret_cast<const int *>(d + o_z), d_sigma,
-                               P.wave ? d_out + c.p_begin : d_part, (long long)c.task_begin, (long long)c.n_tasks, (unsigned)c.n_perms, (int)n};
-            e = P.partial ? mantel_launch_chunk<true>(P, a, row_lds, gather, s) : mantel_launch_chunk<false>(P, a, row_lds, gather, s);
-        }
-        if (e != hipSuccess) return fail(ST_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
-        prev = &c;
-    }
-    if (prev) e = fold(*prev);
-    if (e != hipSuccess) return fail(ST_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+    auto produce = [&](const DispersionChunk &c, hipStream_t st) {
+        return dispersion_launch_sigma(DispersionSigmaArgs{d_sigma, (long long)c.p_begin, (unsigned long long)seed, (int)stream, (int)n}, c.n_perms, st);
+    };
+    auto launch = [&](const DispersionChunk &c, hipStream_t st) {
+        const MantelArgs a{reinterpret_cast<const int *>(d), reinterpret_cast<const int *>(d + o_y), reinterpret_cast<const int *>(d + o_z), d_sigma,
+                           P.wave ? d_out + c.p_begin : d_part, (long long)c.task_begin, (long long)c.n_tasks, (unsigned)c.n_perms, (int)n};
+        return P.partial ? mantel_launch_chunk<true>(P, a, row_lds, gather, st) : mantel_launch_chunk<false>(P, a, row_lds, gather, st);
+    };
+    if (const int rc = matrix_block_chunks(what, s, P.chunks, produce, launch, fold); rc != ST_OK) return rc;
     e = hipMemcpyAsync(out, d_out, (size_t)P.rows * sizeof(st_mantel_sums), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return fail(ST_ERR_HIP, std::string(what) + " read-back: " + hipGetErrorString(e));

@@ -1,4 +1,5 @@
-// host_parafit.h -- part of suchtree_hip.hip (included after host_mantel.h, whose shape it follows).
+// host_parafit.h -- part of suchtree_hip.hip (included after host_dispersion.h, whose work block opener and loop over
+// blocks and chunks -- matrix_block_chunks -- it uses).
 // The device side of st_parafit_codes (kernels_parafit.h; the plan and the host restatement: parafit_plan.cpp).  One work
 // block: g_s and g_f as uploaded, P (row form), the links, one block of R rows, the block's link records, the call's
 // totals, the observation's records and the counts.  Once: k_parafit_expand (row form).  Per block of permutations: its
@@ -49,13 +50,7 @@ static int parafit_device(int device, const ParafitPlan &P, const int32_t *g_f, 
     h_group.resize(G);
     for (size_t g = 0; g < G; g++) h_group[g] = ParafitGroupDev{P.groups[g].stream, P.groups[g].begin, P.groups[g].count};
     h_part.resize(link_all ? (size_t)P.perm_block * L : 0);
-    hipError_t e = s.create();
-    if (e != hipSuccess) return fail(ST_ERR_HIP, std::string(what) + " setup: " + hipGetErrorString(e));
-    e = d_work.alloc(bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ST_ERR_NOMEM, std::string(what) + ": a work block of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
-    }
+    if (const int rc = open_work_block(what, s, d_work, bytes); rc != ST_OK) return rc;
     char *const d = d_work;
     const int *const d_gs = reinterpret_cast<const int *>(d), *const d_gf = reinterpret_cast<const int *>(d + o_gf);
     int *const d_P = reinterpret_cast<int *>(d + o_P);
@@ -66,7 +61,7 @@ static int parafit_device(int device, const ParafitPlan &P, const int32_t *g_f, 
     st_parafit_sum *const d_total = reinterpret_cast<st_parafit_sum *>(d + o_total), *const d_obs = reinterpret_cast<st_parafit_sum *>(d + o_obs);
     long long *const d_nge = reinterpret_cast<long long *>(d + o_nge);
     const size_t row_lds = (n_s * 4 + 15) & ~(size_t)15;
-    e = hipMemcpyAsync(d, g_s, n_s * n_s * 4, hipMemcpyHostToDevice, s);
+    hipError_t e = hipMemcpyAsync(d, g_s, n_s * n_s * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d + o_gf, g_f, n_f * n_f * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_lf, h_lf.data(), L * 2, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_ls, h_ls.data(), L * 2, hipMemcpyHostToDevice, s);
@@ -97,30 +92,22 @@ static int parafit_device(int device, const ParafitPlan &P, const int32_t *g_f, 
             }
         return hipSuccess;
     };
-    const DispersionChunk *prev = nullptr;
-    for (const DispersionChunk &c : P.chunks) {
-        if (!prev || c.p_begin != prev->p_begin) {      // (stream order: the tasks of the block before have read their rows)
-            if (prev) e = fold(*prev);
-            if (e == hipSuccess)
-                e = parafit_launch_relabel(ParafitRelabelArgs{d_group, d_ls, d_R, (unsigned long long)seed, (long long)c.p_begin,
-                                                              (long long)(c.n_perms * (int64_t)G), (int)G, (int)n_s, (int)L}, s);
+    auto produce = [&](const DispersionChunk &c, hipStream_t st) {      // the block's sorts: R
+        return parafit_launch_relabel(ParafitRelabelArgs{d_group, d_ls, d_R, (unsigned long long)seed, (long long)c.p_begin,
+                                                         (long long)(c.n_perms * (int64_t)G), (int)G, (int)n_s, (int)L}, st);
+    };
+    auto launch = [&](const DispersionChunk &c, hipStream_t st) {
+        const ParafitArgs a{d_gs, d_P, d_gf, d_lf, d_R, d_part, d_total + c.p_begin, (long long)c.task_begin, (long long)c.n_tasks, (unsigned)c.n_perms,
+                            (int)n_f, (int)n_s, (int)L};
+        if (P.wave) {
+            const int64_t per = kParafitThreads / 64;
+            hipLaunchKernelGGL(k_parafit_wave, dim3((unsigned)((a.n_tasks + per - 1) / per)), dim3(kParafitThreads), 0, st, a);
+        } else {
+            hipLaunchKernelGGL(k_parafit_rows, dim3((unsigned)a.n_tasks), dim3(kParafitThreads), row_lds, st, a);
         }
-        if (e == hipSuccess) {
-            const ParafitArgs a{d_gs, d_P, d_gf, d_lf, d_R, d_part, d_total + c.p_begin, (long long)c.task_begin, (long long)c.n_tasks, (unsigned)c.n_perms,
-                                (int)n_f, (int)n_s, (int)L};
-            if (P.wave) {
-                const int64_t per = kParafitThreads / 64;
-                hipLaunchKernelGGL(k_parafit_wave, dim3((unsigned)((a.n_tasks + per - 1) / per)), dim3(kParafitThreads), 0, s, a);
-            } else {
-                hipLaunchKernelGGL(k_parafit_rows, dim3((unsigned)a.n_tasks), dim3(kParafitThreads), row_lds, s, a);
-            }
-            e = hipGetLastError();
-        }
-        if (e != hipSuccess) return fail(ST_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
-        prev = &c;
-    }
-    if (prev) e = fold(*prev);
-    if (e != hipSuccess) return fail(ST_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+        return hipGetLastError();
+    };
+    if (const int rc = matrix_block_chunks(what, s, P.chunks, produce, launch, fold); rc != ST_OK) return rc;
     e = hipMemcpyAsync(total, d_total, (size_t)P.rows * sizeof(st_parafit_sum), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(link_obs, d_obs, L * sizeof(st_parafit_sum), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(link_n_ge, d_nge, L * 8, hipMemcpyDeviceToHost, s);

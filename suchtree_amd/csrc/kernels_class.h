@@ -4,7 +4,7 @@
 // relabels the pairs' classes through sigma_p; out[p][c] = sum over j < i of y[k(i, j)] where the class of the pair
 // (sigma_p(i), sigma_p(j)) is c, in 64 bits.
 //
-//   k_class_expand   n > 64.  The symmetric n x n byte square of the condensed classes, once a call: rows of class_stride(n)
+//   k_class_expand   n > 64.  The symmetric n x n byte square of the condensed classes, once a call: rows of sliced_stride(n)
 //                    bytes (a multiple of 16), the diagonal and the padding kClassNone.
 //   k_class_wave     n <= 64: one permutation per wave, four per workgroup.  y (row stride 65 words) and the class square
 //                    (row stride 68 bytes: 17 words, odd) sit in LDS; lane l takes row l and s_l = sigma_p(l), sigma_p(j)
@@ -13,7 +13,7 @@
 //   k_class_rows     n > 64.  One workgroup per task (row pair r, slice s).  It stages rows r and n - 1 - r of y in LDS --
 //                    n - 1 words together, the second row from a quad boundary -- once for the slice; its four waves
 //                    then share out the slice's permutations.  For permutation p and row i a wave copies row sigma_p(i)
-//                    of the class square into an LDS row of its own (16-byte loads, class_stride(n) bytes), then its
+//                    of the class square into an LDS row of its own (16-byte loads, sliced_stride(n) bytes), then its
 //                    lanes stride over j < i: sigma_p(j) (2 bytes, coalesced), the class byte at it in LDS, one LDS
 //                    word of y, one 64-bit LDS add to the wave's accumulator of that class.  No global gather: the
 //                    first build gathered the byte from the row in global memory and spent its time there (DESIGN.md
@@ -131,7 +131,7 @@ struct ClassArgs {
 
 // the LDS of k_class_rows: rows r and n - 1 - r of y, the second from a quad boundary, then one row of the class square per wave
 ST_QUARTET_HD size_t class_y_lds(int n) { return (((size_t)n + 3) * 4 + 15) & ~(size_t)15; }
-inline size_t class_row_lds(int32_t n) { return class_y_lds(n) + (kClassThreads / 64) * class_stride(n); }
+inline size_t class_row_lds(int32_t n) { return class_y_lds(n) + (kClassThreads / 64) * sliced_stride(n); }
 
 // row `src` of the class square (stride bytes, 16-byte aligned) into the wave's LDS row: the wave alone reads and writes it
 __device__ __forceinline__ void class_stage_row(uint4 *dst, const unsigned char *__restrict__ src, unsigned stride, int lane)

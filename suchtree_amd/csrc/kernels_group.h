@@ -11,7 +11,7 @@
 //                     lane by lane, and writes out[p][h] -- 64 columns a pass.  No relabel, no partial records, no fold.
 //                     The row form below leaves 48 lanes of every wave idle at this size and was measured at twice
 //                     the Mantel wave form's time.
-//   k_group_relabel   n > 64.  G[p][j] = group[sigma_p(j)] as bytes for the block's permutations, rows of group_stride(n) bytes
+//   k_group_relabel   n > 64.  G[p][j] = group[sigma_p(j)] as bytes for the block's permutations, rows of sliced_stride(n) bytes
 //                     (a multiple of 16: a row starts 16-byte aligned), the padding zero.
 //   k_group_rows      n > 64.  One workgroup per task (row pair r, slice s).  For each of its rows i = r and n - 1 - r (the middle
 //                     row once) it stages y[k0 .. k0 + i) in LDS at word j, once for the slice; its four waves then share

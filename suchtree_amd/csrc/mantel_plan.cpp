@@ -7,30 +7,6 @@
 
 namespace st {
 
-// the first cell (i, j), j < i, whose mirror differs, scanned in tiles (the mirror of a row is a column); false: none
-bool mantel_asymmetric(const int32_t *x, int64_t n, int64_t &bad_i, int64_t &bad_j)
-{
-    constexpr int64_t T = 64;
-    bool found = false;
-    for (int64_t i0 = 0; i0 < n && !found; i0 += T)
-        for (int64_t j0 = 0; j0 <= i0 && !found; j0 += T)
-            for (int64_t i = i0; i < std::min(i0 + T, n) && !found; i++)
-                for (int64_t j = j0; j < std::min(j0 + T, i); j++)
-                    if (x[i * n + j] != x[j * n + i]) {
-                        found = true;
-                        break;
-                    }
-    if (!found) return false;
-    for (int64_t i = 0; i < n; i++)      // (the error path: which one comes first)
-        for (int64_t j = 0; j < n; j++)
-            if (x[i * n + j] != x[j * n + i]) {
-                bad_i = i;
-                bad_j = j;
-                return true;
-            }
-    return false;
-}
-
 static void mantel_put(i128 v, uint64_t &lo, int64_t &hi)
 {
     lo = (uint64_t)v;
@@ -40,15 +16,10 @@ static void mantel_put(i128 v, uint64_t &lo, int64_t &hi)
 int mantel_plan(const int32_t *x_sq, const int32_t *y, const int32_t *z, int32_t n, int64_t permutations, int32_t stream, int64_t chunk_tasks,
                 st_mantel_moments *moments, const st_mantel_sums *out, MantelPlan &P, std::string &err)
 {
-    if (const int rc = dispersion_call_args(n, permutations, chunk_tasks, stream, err); rc != ST_OK) return rc;
-    if (permutations > INT32_MAX) return fail(ST_ERR_ARG, err, "more than 2^31 - 1 permutations");
+    if (const int rc = matrix_call_args(n, permutations, chunk_tasks, stream, err); rc != ST_OK) return rc;
     if (!x_sq || !y) return fail(ST_ERR_ARG, err, "x_sq or y is NULL");
     if (!moments || !out) return fail(ST_ERR_ARG, err, "moments or out is NULL");
-    int64_t bi = 0, bj = 0;
-    if (mantel_asymmetric(x_sq, n, bi, bj))
-        return fail(ST_ERR_ARG, err, "x_sq is not symmetric: x_sq[" + std::to_string(bi) + "][" + std::to_string(bj) + "] = " +
-                                         std::to_string(x_sq[bi * n + bj]) + ", x_sq[" + std::to_string(bj) + "][" + std::to_string(bi) + "] = " +
-                                         std::to_string(x_sq[bj * n + bi]));
+    if (const int rc = symmetric_arg("x_sq", x_sq, n, err); rc != ST_OK) return rc;
     P = MantelPlan{};
     P.n = n;
     P.rows = permutations + 1;
@@ -92,20 +63,7 @@ int mantel_plan(const int32_t *x_sq, const int32_t *y, const int32_t *z, int32_t
     mantel_put(szz, moments->szz_lo, moments->szz_hi);
     mantel_put(syz, moments->syz_lo, moments->syz_hi);
 
-    int64_t block = std::max<int64_t>(1, std::min(kDispersionSigmaBytes / (2 * (int64_t)n), kMantelBlockTasks / P.items));
-    int64_t cap = kDispersionChunkTasks;
-    if (chunk_tasks > 0) {
-        block = std::min(block, chunk_tasks);
-        cap = std::min(chunk_tasks, kDispersionMaxChunkTasks);
-    }
-    P.perm_block = std::min(block, P.rows);
-    for (int64_t p0 = 0; p0 < P.rows; p0 += P.perm_block) {
-        const int64_t np = std::min(P.perm_block, P.rows - p0), tasks = P.items * np;
-        for (int64_t t = 0; t < tasks; t += cap) {
-            P.chunks.push_back(DispersionChunk{p0, np, t, std::min(cap, tasks - t)});
-            P.max_chunk_tasks = std::max(P.max_chunk_tasks, P.chunks.back().n_tasks);
-        }
-    }
+    matrix_cut(P, std::min(kDispersionSigmaBytes / (2 * (int64_t)n), kMantelBlockTasks / P.items), chunk_tasks);
     return ST_OK;
 }
 

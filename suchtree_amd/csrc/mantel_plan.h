@@ -21,15 +21,9 @@ constexpr int32_t kMantelShiftLimit = 2000;               // |shift| of a caller
 
 using i128 = __int128;
 
-struct MantelPlan {
+struct MantelPlan : MatrixPlan {      // items: 1 (wave form) or (n + 1) / 2 row pairs
     int32_t n = 0;
-    int64_t rows = 0;             // permutations + 1 records
     bool partial = false;
-    bool wave = false;
-    int64_t items = 0;            // tasks per permutation: 1 (wave form) or (n + 1) / 2 row pairs
-    int64_t perm_block = 0;
-    std::vector<DispersionChunk> chunks;
-    int64_t max_chunk_tasks = 0;
 };
 
 inline st_mantel_sums mantel_sums(i128 xy, i128 xz)
@@ -45,9 +39,6 @@ inline st_mantel_sums mantel_sums(i128 xy, i128 xz)
 // of kDispersionChunkTasks tasks; chunk_tasks > 0 = at most that many tasks per chunk and permutations per block.
 int mantel_plan(const int32_t *x_sq, const int32_t *y, const int32_t *z, int32_t n, int64_t permutations, int32_t stream, int64_t chunk_tasks,
                 st_mantel_moments *moments, const st_mantel_sums *out, MantelPlan &P, std::string &err);
-
-// the first cell (row-major) of the square matrix x whose mirror differs; false: x is symmetric (parafit_plan.cpp shares it)
-bool mantel_asymmetric(const int32_t *x, int64_t n, int64_t &bad_i, int64_t &bad_j);
 
 // the sums of x relabelled by sigma[0 .. n) against y and, where z is not NULL, z
 void mantel_record(const int32_t *x_sq, const int32_t *y, const int32_t *z, int32_t n, const int32_t *sigma, i128 &sxy, i128 &sxz);

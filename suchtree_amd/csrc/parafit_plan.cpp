@@ -6,16 +6,6 @@
 
 namespace st {
 
-static int parafit_asymmetric(const char *name, const int32_t *x, int32_t n, std::string &err)
-{
-    int64_t bi = 0, bj = 0;
-    if (!mantel_asymmetric(x, n, bi, bj)) return ST_OK;
-    const std::string g(name);
-    return fail(ST_ERR_ARG, err, g + " is not symmetric: " + g + "[" + std::to_string(bi) + "][" + std::to_string(bj) + "] = " +
-                                     std::to_string(x[bi * n + bj]) + ", " + g + "[" + std::to_string(bj) + "][" + std::to_string(bi) + "] = " +
-                                     std::to_string(x[bj * n + bi]));
-}
-
 int parafit_plan(const int32_t *g_f, int32_t n_f, const int32_t *g_s, int32_t n_s, const int32_t *link_f, const int32_t *link_s, int32_t n_links,
                  const int32_t *stream_f, int64_t permutations, int64_t chunk_tasks, const st_parafit_sum *total, const st_parafit_sum *link_obs,
                  const int64_t *link_n_ge, ParafitPlan &P, std::string &err)
@@ -37,8 +27,8 @@ int parafit_plan(const int32_t *g_f, int32_t n_f, const int32_t *g_s, int32_t n_
     }
     for (int32_t i = 0; i < n_f; i++)
         if (stream_f[i] < 0) return fail(ST_ERR_ARG, err, "stream_f[" + std::to_string(i) + "] < 0");
-    if (const int rc = parafit_asymmetric("g_f", g_f, n_f, err); rc != ST_OK) return rc;
-    if (const int rc = parafit_asymmetric("g_s", g_s, n_s, err); rc != ST_OK) return rc;
+    if (const int rc = symmetric_arg("g_f", g_f, n_f, err); rc != ST_OK) return rc;
+    if (const int rc = symmetric_arg("g_s", g_s, n_s, err); rc != ST_OK) return rc;
 
     P = ParafitPlan{};
     P.n_f = n_f;
@@ -53,20 +43,7 @@ int parafit_plan(const int32_t *g_f, int32_t n_f, const int32_t *g_s, int32_t n_
     }
 
     const int64_t L = n_links;
-    int64_t block = std::max<int64_t>(1, std::min(kDispersionSigmaBytes / (2 * L), kParafitBlockTasks / L));
-    int64_t cap = kDispersionChunkTasks;
-    if (chunk_tasks > 0) {
-        block = std::min(block, chunk_tasks);
-        cap = std::min(chunk_tasks, kDispersionMaxChunkTasks);
-    }
-    P.perm_block = std::min(block, P.rows);
-    for (int64_t p0 = 0; p0 < P.rows; p0 += P.perm_block) {
-        const int64_t np = std::min(P.perm_block, P.rows - p0), tasks = P.items * np;
-        for (int64_t t = 0; t < tasks; t += cap) {
-            P.chunks.push_back(DispersionChunk{p0, np, t, std::min(cap, tasks - t)});
-            P.max_chunk_tasks = std::max(P.max_chunk_tasks, P.chunks.back().n_tasks);
-        }
-    }
+    matrix_cut(P, std::min(kDispersionSigmaBytes / (2 * L), kParafitBlockTasks / L), chunk_tasks);
     return ST_OK;
 }
 

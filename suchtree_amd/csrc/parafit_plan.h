@@ -1,7 +1,7 @@
 // parafit_plan.h -- the host-only side of ParaFit's global and link statistics (st_parafit_codes), plain C++17.  No GPU
 // calls in here (parafit_plan.cpp): the "not gpu" tests run it under the address / undefined-behaviour sanitizers
 // (tests/emu/sanitize_parafit.cpp).  The definitions are the contract of include/suchtree_hip.h (st_parafit_codes); the
-// permutation is keyed_perm.h's, the chunk record dispersion_plan.h's, the blocks and chunks follow mantel_plan.h.
+// permutation is keyed_perm.h's, the chunk record and the cut into blocks and chunks dispersion_plan.h's.
 //
 // Layout.  The links are sorted by (f, s), so the links of one F position are one range; `groups` lists the F positions
 // that have links.  Within a block of n_perms permutations from p0 the relabelled S positions are R[(p - p0) * L + l] and
@@ -32,15 +32,9 @@ struct ParafitGroup {
     int32_t begin, count;          // its links [begin, begin + count)
 };
 
-struct ParafitPlan {
+struct ParafitPlan : MatrixPlan {      // items: 1 (wave form) or L
     int32_t n_f = 0, n_s = 0, n_links = 0;
-    int64_t rows = 0;                     // permutations + 1
-    bool wave = false;
-    int64_t items = 0;                    // tasks per permutation: 1 (wave form) or L
-    int64_t perm_block = 0;
     std::vector<ParafitGroup> groups;     // the F positions with links, ascending
-    std::vector<DispersionChunk> chunks;
-    int64_t max_chunk_tasks = 0;
 };
 
 inline st_parafit_sum parafit_sum(i128 v) { return st_parafit_sum{(uint64_t)v, (int64_t)(v >> 64)}; }

@@ -54,7 +54,7 @@
 // host_hommola.h (the chunk driver) and, host-only, hommola_plan.cpp (argument checks, ranges, block and chunk tables, the fold).
 // MPD / MNTD sums of many leaf sets under the taxa-labels null (st_partner_dispersion_host, st_dispersion_matrix):
 // kernels_dispersion.h (one sort per permutation, the k x k reducer in three size classes), host_dispersion.h (the chunk
-// driver) and, host-only, dispersion_plan.cpp (argument checks, size classes, chunks, the restatement of the reduction).
+// drivers) and, host-only, dispersion_plan.cpp (argument checks, size classes, chunks, the restatement of the reduction).
 // The same sums under the degree-preserving swap null (st_swap_null_tables, st_dispersion_matrix_swap,
 // st_partner_dispersion_swap_host): kernels_swap.h (one wave per Markov chain of swaps), the table form of kernels_dispersion.h's
 // reducers, host_swap.h (the block of chains, the chunk loop with the chains as its producer) and, host-only, swap_plan.cpp.
@@ -74,21 +74,23 @@
 // windows, the restatement).
 // The Mantel and partial Mantel sums of two or three distance matrices under the same relabelling null (st_mantel_codes,
 // st_mantel_quantise): kernels_mantel.h (a wave form with the matrix in LDS, a row form that stages one matrix row in LDS
-// per workgroup, the fold), host_mantel.h (the loop over blocks and chunks) and, host-only, mantel_plan.cpp (the checks,
-// the invariant sums, the quantiser, the restatement).
+// per workgroup, the fold), host_mantel.h (the layout, the launches) and, host-only, mantel_plan.cpp (the checks, the
+// invariant sums, the quantiser, the restatement).  This and the next three are the matrix permutation tests: their plans
+// derive from MatrixPlan and are cut by dispersion_cut_blocks (dispersion_plan.cpp), their device sides open the work block
+// and walk blocks and chunks with host_dispersion.h's open_work_block and matrix_block_chunks.
 // The within-group sums of a distance matrix under the same relabelling null, behind PERMANOVA and ANOSIM
 // (st_group_sums_codes): kernels_group.h (a wave form with y in LDS; the relabelled labels as bytes, a row form that
-// stages a row of y in LDS once for a slice of permutations, the fold by group), host_group.h (the loop over blocks and chunks) and, host-only,
+// stages a row of y in LDS once for a slice of permutations, the fold by group), host_group.h (the layout, the launches) and, host-only,
 // group_plan.cpp (the checks, the layout, the restatement).
 // The per-class sums of a distance matrix under the same relabelling null, behind the Mantel correlogram
 // (st_class_sums_codes): kernels_class.h (the class square expanded once, a wave form with y and the square in LDS, a row
 // form that stages a row pair of y in LDS once for a slice of permutations and files each pair under its class in LDS
-// accumulators, the fold), host_class.h (the loop over blocks and chunks) and, host-only, class_plan.cpp (the checks,
+// accumulators, the fold), host_class.h (the layout, the launches) and, host-only, class_plan.cpp (the checks,
 // the layout, the restatement).
 // ParaFit's global statistic and ParaFitLink1 of every host-guest link as exact sums over link pairs (st_parafit_codes):
 // kernels_parafit.h (the held side expanded once, one sort per permutation and linked leaf, a wave form with both sides in
 // LDS, a row form that stages one matrix row in LDS per workgroup, the fold with the per-link counts), host_parafit.h (the
-// loop over blocks and chunks) and, host-only, parafit_plan.cpp (the checks, the layout, the restatement).
+// layout, the launches) and, host-only, parafit_plan.cpp (the checks, the layout, the restatement).
 //
 // What the host side does: tree upload to one or several GPUs (tree_prep.cpp builds the tables, under a table budget
 // if one is given), the host path (host_pipe.h, host_copy.h: packed ids in through the copy engine, kernels write
@@ -1197,7 +1199,7 @@ int st_group_sums_codes(int device, const int32_t *y, int32_t n, const uint8_t *
 try {
     GroupPlan P;
     std::string err;
-    const int rc = group_plan(y, n, group, n_groups, permutations, stream, chunk_tasks, group_slice(), out, P, err);
+    const int rc = group_plan(y, n, group, n_groups, permutations, stream, chunk_tasks, perm_slice_env("SUCHTREE_AMD_GROUP_SLICE", kGroupSlice, kGroupSliceMax), out, P, err);
     if (rc != ST_OK) return fail(rc, err);
     if (device_or_host_arg(device) != ST_OK) return ST_ERR_ARG;
     if (device < 0) {
@@ -1212,7 +1214,7 @@ int st_class_sums_codes(int device, const int32_t *y, const uint8_t *cls, int32_
 try {
     ClassPlan P;
     std::string err;
-    const int rc = class_plan(y, cls, n, n_classes, permutations, stream, chunk_tasks, class_slice(), out, P, err);
+    const int rc = class_plan(y, cls, n, n_classes, permutations, stream, chunk_tasks, perm_slice_env("SUCHTREE_AMD_CLASS_SLICE", kClassSlice, kClassSliceMax), out, P, err);
     if (rc != ST_OK) return fail(rc, err);
     if (device_or_host_arg(device) != ST_OK) return ST_ERR_ARG;
     if (device < 0) {

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../suchtree_amd/csrc/class_plan.h"
+#include "chunks_tile.h"
 
 using namespace st;
 
@@ -57,26 +58,13 @@ static int check_case(const Case &C, int64_t perms, int64_t chunk, int32_t slice
     CHECK(P.items == (P.wave ? 1 : (n + 1) / 2));
     CHECK(P.wave || P.perm_block * P.items * K * 8 <= kClassPartBytes);
     // the chunks tile every block's (row pair, slice) tasks once, in order
-    int64_t p_next = 0, t_next = 0;
+    if (chunks_tile(P, chunk, [&](int64_t n_perms) { return sliced_block_tasks(P, n_perms); })) return 1;
     for (const DispersionChunk &c : P.chunks) {
-        if (c.task_begin == 0) {
-            CHECK(t_next == 0 && c.p_begin == p_next);
-        } else {
-            CHECK(c.task_begin == t_next);
-        }
-        CHECK(c.n_perms >= 1 && c.n_perms <= P.perm_block && c.n_tasks >= 1 && c.n_tasks <= P.max_chunk_tasks);
-        if (chunk > 0) CHECK(c.n_tasks <= chunk && c.n_perms <= chunk);
-        const int64_t n_slices = class_slices(c.n_perms, slice);
+        const int64_t n_slices = dispersion_slices(c.n_perms, slice);
         CHECK(n_slices >= 1 && (n_slices - 1) * slice < c.n_perms && n_slices * slice >= c.n_perms);
-        t_next = c.task_begin + c.n_tasks;
-        CHECK(class_block_tasks(P, c.n_perms) == (P.wave ? c.n_perms : P.items * n_slices));
-        if (t_next == class_block_tasks(P, c.n_perms)) {
-            t_next = 0;
-            p_next = c.p_begin + c.n_perms;
-        }
+        CHECK(sliced_block_tasks(P, c.n_perms) == (P.wave ? c.n_perms : P.items * n_slices));
     }
-    CHECK(p_next == P.rows && t_next == 0);
-    CHECK(class_stride(n) % 16 == 0 && class_stride(n) >= (size_t)n && class_stride(n) < (size_t)n + 16);
+    CHECK(sliced_stride(n) % 16 == 0 && sliced_stride(n) >= (size_t)n && sliced_stride(n) < (size_t)n + 16);
     // the restatement against the definition: the square written out, the pairs in another order
     class_host(C.y.data(), C.cls.data(), P, seed, stream, out.data());
     std::vector<uint8_t> sq((size_t)n * (size_t)n, (uint8_t)kClassNone);
@@ -92,6 +80,26 @@ static int check_case(const Case &C, int64_t perms, int64_t chunk, int32_t slice
                 if (c != kClassNone) want[c] += C.y[(size_t)i * (size_t)(i - 1) / 2 + (size_t)j];
             }
         for (int32_t c = 0; c < K; c++) CHECK(out[(size_t)p * (size_t)K + (size_t)c] == want[(size_t)c]);
+    }
+    return 0;
+}
+
+// the default block (chunk_tasks 0) where each of its two bounds binds, with more permutations than the bound
+static int check_blocks()
+{
+    struct Want {
+        int32_t K;
+        int64_t perm_block;
+    };
+    for (const Want w : {Want{1, 516222} /* the sigma rows: 2^26 / (2 x 65) */, Want{64, 15887} /* the partial sums: 2^28 / (8 x 64 classes x 33 row pairs) */}) {
+        const Case C = make_case(65, w.K, 0);
+        std::string err;
+        ClassPlan P;
+        int64_t out = 0;
+        CHECK(class_plan(C.y.data(), C.cls.data(), 65, w.K, 600000, 0, 0, kClassSlice, &out, P, err) == ST_OK);
+        CHECK(P.perm_block == w.perm_block);
+        CHECK(w.perm_block == std::min(kDispersionSigmaBytes / (2 * 65), kClassPartBytes / (8 * w.K * P.items)));
+        if (chunks_tile(P, 0, [&](int64_t n_perms) { return sliced_block_tasks(P, n_perms); })) return 1;
     }
     return 0;
 }
@@ -162,7 +170,7 @@ int main()
         CHECK(class_plan(C.y.data(), C.cls.data(), 2049, 64, 999, 0, 0, kClassSlice, &out, P, err) == ST_OK);
         CHECK(P.perm_block == std::min<int64_t>(kClassPartBytes / (8 * 64 * 1025), 1000) && P.perm_block * 1025 * 64 * 8 <= kClassPartBytes);
     }
-    if (check_rows() || check_errors()) return 1;
+    if (check_blocks() || check_rows() || check_errors()) return 1;
     std::printf("sanitize class ok\n");
     return 0;
 }

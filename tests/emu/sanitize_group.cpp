@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../suchtree_amd/csrc/group_plan.h"
+#include "chunks_tile.h"
 
 using namespace st;
 
@@ -52,26 +53,13 @@ static int check_case(const Case &C, int64_t perms, int64_t chunk, int32_t slice
     CHECK(P.n == n && P.n_groups == a && P.rows == perms + 1 && P.wave == (n <= kGroupWaveMax) && P.slice == slice);
     CHECK(P.items == (P.wave ? 1 : (n + 1) / 2));
     // the chunks tile every block's (row pair, slice) tasks once, in order
-    int64_t p_next = 0, t_next = 0;
+    if (chunks_tile(P, chunk, [&](int64_t n_perms) { return sliced_block_tasks(P, n_perms); })) return 1;
     for (const DispersionChunk &c : P.chunks) {
-        if (c.task_begin == 0) {
-            CHECK(t_next == 0 && c.p_begin == p_next);
-        } else {
-            CHECK(c.task_begin == t_next);
-        }
-        CHECK(c.n_perms >= 1 && c.n_perms <= P.perm_block && c.n_tasks >= 1 && c.n_tasks <= P.max_chunk_tasks);
-        if (chunk > 0) CHECK(c.n_tasks <= chunk && c.n_perms <= chunk);
-        const int64_t n_slices = group_slices(c.n_perms, slice);
+        const int64_t n_slices = dispersion_slices(c.n_perms, slice);
         CHECK(n_slices >= 1 && (n_slices - 1) * slice < c.n_perms && n_slices * slice >= c.n_perms);
-        t_next = c.task_begin + c.n_tasks;
-        CHECK(group_block_tasks(P, c.n_perms) == (P.wave ? c.n_perms : P.items * n_slices));
-        if (t_next == group_block_tasks(P, c.n_perms)) {
-            t_next = 0;
-            p_next = c.p_begin + c.n_perms;
-        }
+        CHECK(sliced_block_tasks(P, c.n_perms) == (P.wave ? c.n_perms : P.items * n_slices));
     }
-    CHECK(p_next == P.rows && t_next == 0);
-    CHECK(group_stride(n) % 16 == 0 && group_stride(n) >= (size_t)n && group_stride(n) < (size_t)n + 16);
+    CHECK(sliced_stride(n) % 16 == 0 && sliced_stride(n) >= (size_t)n && sliced_stride(n) < (size_t)n + 16);
     // the restatement against the definition, the pairs in another order
     group_host(C.y.data(), C.group.data(), P, seed, stream, out.data());
     std::vector<int32_t> sigma((size_t)n);
@@ -84,6 +72,26 @@ static int check_case(const Case &C, int64_t perms, int64_t chunk, int32_t slice
                 if (gi == gj) want[gi] += C.y[(size_t)i * (size_t)(i - 1) / 2 + (size_t)j];
             }
         for (int32_t h = 0; h < a; h++) CHECK(out[(size_t)p * (size_t)a + (size_t)h] == want[(size_t)h]);
+    }
+    return 0;
+}
+
+// the default block (chunk_tasks 0) where each of its two bounds binds, with more permutations than the bound
+static int check_blocks()
+{
+    struct Want {
+        int32_t n;
+        int64_t perm_block;
+    };
+    for (const Want w : {Want{64, 524288} /* the sigma rows: 2^26 / (2 x 64) */, Want{65, 127100} /* row pairs x permutations: 2^22 / 33 */}) {
+        const Case C = make_case(w.n, 3, 0);
+        std::string err;
+        GroupPlan P;
+        int64_t out = 0;
+        CHECK(group_plan(C.y.data(), w.n, C.group.data(), 3, 600000, 0, 0, kGroupSlice, &out, P, err) == ST_OK);
+        CHECK(P.perm_block == w.perm_block);
+        CHECK(w.perm_block == std::min(kDispersionSigmaBytes / (2 * w.n), kGroupBlockItems / P.items));
+        if (chunks_tile(P, 0, [&](int64_t n_perms) { return sliced_block_tasks(P, n_perms); })) return 1;
     }
     return 0;
 }
@@ -143,7 +151,7 @@ int main()
                     if (n < 100 && a == 6 && check_case(C, 7, chunk, slice, rnd(), 0)) return 1;
         }
     if (check_case(make_case(257, 1, 1), 2, 16, 3, 11, 0) || check_case(make_case(257, 2, -1), 2, 0, 16, 12, 0)) return 1;
-    if (check_rows() || check_errors()) return 1;
+    if (check_blocks() || check_rows() || check_errors()) return 1;
     std::printf("sanitize group ok\n");
     return 0;
 }

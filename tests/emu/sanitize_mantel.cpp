@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../suchtree_amd/csrc/mantel_plan.h"
+#include "chunks_tile.h"
 
 using namespace st;
 
@@ -66,22 +67,7 @@ static int check_case(const Case &C, bool partial, int64_t perms, int64_t chunk,
     CHECK(P.n == n && P.rows == perms + 1 && P.partial == partial && P.wave == (n <= kMantelWaveMax));
     CHECK(P.items == (P.wave ? 1 : (n + 1) / 2));
     // the chunks tile every block once, in order
-    int64_t p_next = 0, t_next = 0;
-    for (const DispersionChunk &c : P.chunks) {
-        if (c.task_begin == 0) {
-            CHECK(t_next == 0 && c.p_begin == p_next);
-        } else {
-            CHECK(c.task_begin == t_next);
-        }
-        CHECK(c.n_perms >= 1 && c.n_perms <= P.perm_block && c.n_tasks >= 1 && c.n_tasks <= P.max_chunk_tasks);
-        if (chunk > 0) CHECK(c.n_tasks <= chunk && c.n_perms <= chunk);
-        t_next = c.task_begin + c.n_tasks;
-        if (t_next == P.items * c.n_perms) {
-            t_next = 0;
-            p_next = c.p_begin + c.n_perms;
-        }
-    }
-    CHECK(p_next == P.rows && t_next == 0);
+    if (chunks_tile(P, chunk, [&](int64_t n_perms) { return P.items * n_perms; })) return 1;
     // the invariant sums
     i128 sx = 0, sy = 0, sz = 0, sxx = 0, syy = 0, szz = 0, syz = 0;
     size_t k = 0;
@@ -130,6 +116,27 @@ static int check_carry()
     CHECK(one > (i128)INT64_MAX);
     for (int p = 0; p < 3; p++) CHECK(of(out[p].sxy_lo, out[p].sxy_hi) == one && of(out[p].sxz_lo, out[p].sxz_hi) == -one);
     CHECK(of(M.sxx_lo, M.sxx_hi) == one && of(M.syz_lo, M.syz_hi) == -one);
+    return 0;
+}
+
+// the default block (chunk_tasks 0) where each of its two bounds binds, with more permutations than the bound
+static int check_blocks()
+{
+    struct Want {
+        int32_t n;
+        int64_t perm_block;
+    };
+    for (const Want w : {Want{64, 524288} /* the sigma rows: 2^26 / (2 x 64) */, Want{65, 127100} /* the partial records: 2^22 / 33 row pairs */}) {
+        const Case C = make_case(w.n, false);
+        std::string err;
+        MantelPlan P;
+        st_mantel_moments M;
+        st_mantel_sums out;
+        CHECK(mantel_plan(C.x.data(), C.y.data(), nullptr, w.n, 600000, 0, 0, &M, &out, P, err) == ST_OK);
+        CHECK(P.perm_block == w.perm_block);
+        CHECK(w.perm_block == std::min(kDispersionSigmaBytes / (2 * w.n), kMantelBlockTasks / P.items));
+        if (chunks_tile(P, 0, [&](int64_t n_perms) { return P.items * n_perms; })) return 1;
+    }
     return 0;
 }
 
@@ -204,7 +211,7 @@ int main()
             if (check_case(C, partial != 0, 7, n > 64 ? 16 : 3, rnd(), 0)) return 1;
         }
     if (check_case(make_case(65, true), true, 3, 1, 11, 0)) return 1;
-    if (check_carry() || check_quantise() || check_errors()) return 1;
+    if (check_blocks() || check_carry() || check_quantise() || check_errors()) return 1;
     std::printf("sanitize mantel ok\n");
     return 0;
 }

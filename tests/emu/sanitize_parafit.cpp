@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../suchtree_amd/csrc/parafit_plan.h"
+#include "chunks_tile.h"
 
 using namespace st;
 
@@ -75,17 +76,7 @@ static int check_case(const Case &C, int64_t perms, int64_t chunk, uint64_t seed
     }
     CHECK(at == C.L);
     // the chunks tile every block once
-    int64_t p_next = 0, t_next = 0;
-    for (const DispersionChunk &c : P.chunks) {
-        if (t_next == 0) CHECK(c.p_begin == p_next && c.n_perms >= 1 && c.n_perms <= P.perm_block);
-        CHECK(c.task_begin == t_next && c.n_tasks >= 1 && (chunk == 0 || c.n_tasks <= chunk));
-        t_next += c.n_tasks;
-        if (t_next == P.items * c.n_perms) {
-            p_next = c.p_begin + c.n_perms;
-            t_next = 0;
-        }
-    }
-    CHECK(p_next == P.rows && t_next == 0);
+    if (chunks_tile(P, chunk, [&](int64_t n_perms) { return P.items * n_perms; })) return 1;
     parafit_host(C.g_f.data(), C.g_s.data(), P, C.link_f.data(), C.link_s.data(), seed, total.data(), obs.data(), n_ge.data(), every.data());
     // a plain loop over the definition
     std::vector<int32_t> r(L), sigma((size_t)C.n_s);
@@ -120,6 +111,25 @@ static int check_case(const Case &C, int64_t perms, int64_t chunk, uint64_t seed
         CHECK(parafit_i128(total[(size_t)p].lo, total[(size_t)p].hi) == sum);
     }
     CHECK(want_ge == n_ge);
+    return 0;
+}
+
+// the default block (chunk_tasks 0), with more permutations than its bound: the link records' bound, 2^22 / L, binds at
+// every L (the R rows' is 2^26 / (2 L)), in the wave form and in the row form
+static int check_blocks()
+{
+    for (const int32_t n_s : {3, 65}) {
+        const Case C = make_case(3, n_s, 3, false);
+        std::string err;
+        ParafitPlan P;
+        st_parafit_sum total, obs;
+        int64_t n_ge = 0;
+        CHECK(parafit_plan(C.g_f.data(), 3, C.g_s.data(), n_s, C.link_f.data(), C.link_s.data(), 3, C.stream.data(), 1500000, 0, &total, &obs, &n_ge, P, err) ==
+              ST_OK);
+        CHECK(P.wave == (n_s <= kParafitWaveMax) && P.perm_block == 1398101);
+        CHECK(P.perm_block == std::min(kDispersionSigmaBytes / (2 * 3), kParafitBlockTasks / 3));
+        if (chunks_tile(P, 0, [&](int64_t n_perms) { return P.items * n_perms; })) return 1;
+    }
     return 0;
 }
 
@@ -186,7 +196,7 @@ int main()
         for (const int64_t chunk : {(int64_t)0, (int64_t)1, (int64_t)3, (int64_t)70})
             if (check_case(make_case(shape[0], shape[1], shape[2], false), 5, chunk, 99 + (uint64_t)chunk)) return 1;
     if (check_case(make_case(20, 66, 257, true), 2, 0, 5)) return 1;      // 257^2 terms of +-(2^31 - 1)^2: past 64 bits
-    if (check_errors()) return 1;
+    if (check_blocks() || check_errors()) return 1;
     std::printf("sanitize parafit ok\n");
     return 0;
 }
