@@ -55,7 +55,8 @@ extern "C" {
  *      ST_MANTEL_SHIFT_AUTO, st_mantel_codes and st_mantel_quantise; then, also additive, ST_GROUP_MAX and
  *      st_group_sums_codes; then, also additive, struct st_parafit_sum and st_parafit_codes; then, also additive,
  *      ST_CLASS_MAX, ST_CLASS_NONE and st_class_sums_codes; then, also additive, st_swap_null_tables, st_swap_null_schedule,
- *      st_dispersion_matrix_swap and st_partner_dispersion_swap_host.
+ *      st_dispersion_matrix_swap and st_partner_dispersion_swap_host; then, also additive, struct st_linkage_row, the
+ *      ST_LINKAGE_* constants and st_linkage_codes.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -1053,6 +1054,51 @@ int st_clade_ranges(const int32_t *parent, int64_t n_nodes, const int64_t *leaf_
 int st_clade_match(int device, int32_t m, const int32_t *pos_b, const int32_t *a_lo, const int32_t *a_hi, int32_t n_a,
                    const int32_t *b_lo, const int32_t *b_hi, int32_t n_b, int32_t unrooted, int64_t chunk_rows,
                    int32_t *out_distance, int32_t *out_match, int32_t *out_intersection);
+
+/*
+ * Exact agglomerative clustering of a distance matrix of int32 codes: UPGMA ("average"), single and complete linkage.
+ * Every quantity is an integer, so the dendrogram is a function of the codes alone: a tie is a real tie, broken by the
+ * rule below, on the host and on the device alike.
+ *
+ * Input: n objects, 2 <= n <= ST_LINKAGE_MAX_OBJECTS; codes[i (i - 1) / 2 + j] >= 0 is the code of pair (i, j), j < i;
+ * weights is NULL or n values >= 1 with a total of at most ST_LINKAGE_MAX_WEIGHT -- object i then stands for weights[i]
+ * coincident objects.  The bound keeps every pair sum below 2^62 and every cross product below 2^92.
+ *
+ * Clusters live in slots.  Slot i starts as object i: size s_i = weights[i] (1 without weights), cluster id i.  S(i, j)
+ * starts as codes(i, j) s_i s_j for ST_LINKAGE_AVERAGE and as codes(i, j) for ST_LINKAGE_SINGLE and ST_LINKAGE_COMPLETE.
+ * The value of an active pair is the fraction S(a, b) / (s_a s_b) (average) or S(a, b) / 1 (single, complete); two
+ * values compare by cross-multiplication in 128 bits.  Step t = 0 .. n - 2:
+ *   1. of the active pairs a < b take the one of least value; on a tie the least a, then the least b;
+ *   2. out_rows[t] = {num, den, left, right, size}: num / den the value as above (not reduced), left < right the two
+ *      cluster ids, size = s_a + s_b;
+ *   3. slot a holds the merged cluster, id n + t, size s_a + s_b; slot b dies; every other active slot k gets
+ *      S(k, a) = S(k, a) + S(k, b) (average), min (single) or max (complete) of the two.
+ * The three methods are reducible, so the values never decrease along t.  left, right and size are those of
+ * scipy.cluster.hierarchy.linkage's Z where scipy meets no tie.
+ *
+ * Checked (ST_ERR_ARG), in this order: n out of range, an unknown method, codes or out_rows NULL, the first negative code
+ * (naming its index), the first weight below 1 (naming its index), a total weight above ST_LINKAGE_MAX_WEIGHT.
+ * device = -1 is the host restatement (no GPU: a nearest-later-partner cache per slot, repaired after every merge, not
+ * the scan of all pairs); device >= 0 runs the kernels there -- the same integers.  Device memory is the square int64
+ * S, 8 n (n + 63) bytes at most (2 GiB at the limit), the codes and 16 n bytes of cache; an allocation that fails is ST_ERR_NOMEM with
+ * the bytes asked for, before out_rows is written.  The chain of merges is serial: on the device it is one workgroup
+ * that synchronises with workgroup barriers only.  The environment variable SUCHTREE_AMD_LINKAGE_CACHE = lds / global
+ * (read at every call) says where that workgroup keeps the cache, for a test or a measurement: no result depends on it,
+ * and above the n that fits LDS it is global whatever is asked.  No counterpart in the reference.
+ */
+#define ST_LINKAGE_MAX_OBJECTS 16384
+#define ST_LINKAGE_MAX_WEIGHT  65536
+#define ST_LINKAGE_AVERAGE  0
+#define ST_LINKAGE_SINGLE   1
+#define ST_LINKAGE_COMPLETE 2
+
+typedef struct st_linkage_row {
+    int64_t num, den;       /* the value of the merge: num / den, den = s_a s_b (average) or 1 */
+    int32_t left, right;    /* the two cluster ids, left < right */
+    int64_t size;           /* s_a + s_b */
+} st_linkage_row;
+
+int st_linkage_codes(int device, const int32_t *codes, int32_t n, const int32_t *weights, int32_t method, st_linkage_row *out_rows);
 
 /*
  * Exact Spearman rank correlation of the same pairs.  rank_x is the midrank of x_k among the call's n float32 distances

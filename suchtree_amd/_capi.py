@@ -52,6 +52,7 @@ SYMBOLS = (
     "st_beta_dispersion_host", "st_beta_dispersion_matrix", "st_unifrac_null_host", "st_unifrac_null_depths",
     "st_mantel_codes", "st_mantel_quantise", "st_group_sums_codes", "st_parafit_codes", "st_class_sums_codes",
     "st_swap_null_tables", "st_swap_null_schedule", "st_dispersion_matrix_swap", "st_partner_dispersion_swap_host",
+    "st_linkage_codes",
 )
 
 CLADE_RECT, CLADE_TRI = 0, 1     # include/suchtree_hip.h: ST_CLADE_RECT / ST_CLADE_TRI
@@ -529,7 +530,50 @@ def clade_match(m, pos_b, a_lo, a_hi, b_lo, b_hi, rooted=False, device=-1, chunk
     return tuple(out)
 
 
-QUARTET_MODE = {"all": 0, "sample": 1}      # include/suchtree_hip.h: ST_QUARTET_ALL / ST_QUARTET_SAMPLE
+LINKAGE_METHODS = {"average": 0, "single": 1, "complete": 2}      # include/suchtree_hip.h: ST_LINKAGE_AVERAGE / _SINGLE / _COMPLETE
+LINKAGE_MAX_OBJECTS = 16384      # ST_LINKAGE_MAX_OBJECTS
+LINKAGE_MAX_WEIGHT = 65536       # ST_LINKAGE_MAX_WEIGHT: the total of the weights
+# st_linkage_row as a numpy record
+LINKAGE_ROW = np.dtype([("num", np.int64), ("den", np.int64), ("left", np.int32), ("right", np.int32), ("size", np.int64)])
+
+
+def linkage_codes(codes, weights=None, method="average", device=-1):
+    """st_linkage_codes: the n - 1 records of LINKAGE_ROW of the exact agglomerative clustering of the condensed int32
+    ``codes`` (n (n - 1) / 2 values >= 0, pair (i, j) at i (i - 1) / 2 + j) under ``method`` ("average" = UPGMA, "single",
+    "complete"): row t merges the clusters ``left`` < ``right`` (ids below n are objects, n + s is the cluster of row s)
+    at the value ``num`` / ``den`` into one of ``size`` objects; of the pairs of least value the one with the least
+    slots is taken.  ``weights``: n int32 >= 1, object i stands for that many coincident objects.  ``device`` -1 = the
+    host restatement (no GPU), else the kernels on that device: the same integers."""
+    if method not in LINKAGE_METHODS:
+        raise ValueError("method must be one of %s" % (tuple(LINKAGE_METHODS),))
+    codes = np.asarray(codes)
+    if codes.ndim != 1:
+        raise ValueError("codes must be condensed")
+    m = len(codes)
+    n = (1 + math.isqrt(8 * m + 1)) // 2
+    if n * (n - 1) // 2 != m:
+        raise ValueError("%d pairs are not the triangle of a square matrix" % m)
+    if n > LINKAGE_MAX_OBJECTS:      # (before the square is sized)
+        raise ValueError("n = %d objects: 2 to %d" % (n, LINKAGE_MAX_OBJECTS))
+    if m and (codes.min() < 0 or codes.max() > 0x7FFFFFFF):
+        k = int(np.flatnonzero((codes < 0) | (codes > 0x7FFFFFFF))[0])
+        raise ValueError("codes[%d] = %d %s" % (k, int(codes[k]), "is negative" if codes[k] < 0 else "does not fit int32"))
+    codes = np.ascontiguousarray(codes, dtype=np.int32)
+    if weights is not None:
+        weights = np.asarray(weights)
+        if weights.shape != (n,):
+            raise ValueError("weights must hold one value per object (%d)" % n)
+        if n and (weights.min() < 1 or weights.max() > LINKAGE_MAX_WEIGHT):
+            i = int(np.flatnonzero((weights < 1) | (weights > LINKAGE_MAX_WEIGHT))[0])
+            raise ValueError("weights[%d] = %d: 1 to %d" % (i, int(weights[i]), LINKAGE_MAX_WEIGHT))
+        weights = np.ascontiguousarray(weights, dtype=np.int32)
+    out = np.zeros(max(n - 1, 0), dtype=LINKAGE_ROW)
+    check(load().st_linkage_codes(int(device), _arg(codes), n, None if weights is None else _arg(weights), LINKAGE_METHODS[method],
+                                  _ptr(out) if len(out) else None))
+    return out
+
+
+QUARTET_MODE = {"all": 0, "sample": 1}     # include/suchtree_hip.h: ST_QUARTET_ALL / ST_QUARTET_SAMPLE
 QUARTET_MAX_LEAVES_ALL = 65536
 
 
@@ -796,6 +840,7 @@ def load():
         L.st_clade_ranges.argtypes = [vp, i64, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int32),
                                       ctypes.POINTER(i64)]
         L.st_clade_match.argtypes = [i32, ctypes.c_int32, vp, vp, vp, ctypes.c_int32, vp, vp, ctypes.c_int32, ctypes.c_int32, i64, vp, vp, vp]
+        L.st_linkage_codes.argtypes = [i32, vp, ctypes.c_int32, vp, ctypes.c_int32, vp]
         L.st_clade_plan.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64),
                                     ctypes.POINTER(i64)]
         L.st_compare_clades_host.argtypes = [vp, vp, vp, i64, vp, vp, i64, i64, i64, vp, vp, ctypes.POINTER(i64)]

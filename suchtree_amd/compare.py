@@ -14,7 +14,7 @@ from typing import Optional
 import numpy as np
 
 __all__ = ["DistanceComparison", "CladeComparisons", "HommolaResult", "QuartetComparison", "SetDispersion", "SetUniFrac", "quartet_positions",
-           "unifrac_from_depths", "MantelResult", "mantel"]
+           "unifrac_from_depths", "MantelResult", "mantel", "Dendrogram", "TopologyTestResult", "linkage", "dendrogram_congruence"]
 
 
 @dataclass(frozen=True)
@@ -1220,10 +1220,10 @@ class MantelResult:
             self.corr_coeff, self.p_value, self.n, self.method, self.alternative, self.permutations)
 
 
-def mantel_condensed(a, name="x"):
+def mantel_condensed(a, name="x", least=3):
     """(the float64 condensed form of ``a`` in the triangle order k = i (i - 1) / 2 + j, j < i; n): ``a`` is a square
     symmetric (n, n) matrix, whose diagonal is ignored, or already condensed.  ValueError, naming the offender, for a
-    NaN or an infinity, a cell whose mirror differs, a length that is no triangle, n < 3 or n > 16384."""
+    NaN or an infinity, a cell whose mirror differs, a length that is no triangle, n < ``least`` or n > 16384."""
     from . import _capi
     a = np.asarray(a, dtype=np.float64)
     if a.ndim == 2:
@@ -1236,8 +1236,8 @@ def mantel_condensed(a, name="x"):
             raise ValueError("%s: %d values are not the n (n - 1) / 2 pairs of any n" % (name, len(a)))
     else:
         raise ValueError("%s must be a square matrix or a condensed vector" % name)
-    if n < 3 or n > _capi.HOMMOLA_MAX_UNIVERSE:
-        raise ValueError("%s: n = %d objects: 3 to %d" % (name, n, _capi.HOMMOLA_MAX_UNIVERSE))
+    if n < least or n > _capi.HOMMOLA_MAX_UNIVERSE:
+        raise ValueError("%s: n = %d objects: %d to %d" % (name, n, least, _capi.HOMMOLA_MAX_UNIVERSE))
     if a.ndim == 1:
         bad = np.flatnonzero(~np.isfinite(a))
         if len(bad):
@@ -1836,3 +1836,254 @@ def parafit(d_f, d_s, links, permutations=999, seed=None, shuffle_streams=None, 
                          link_stat=np.array([math.ldexp(float(v), scale) for v in link_q], dtype=np.float64),
                          link_n_ge=n_ge_l[back].copy() if test_links else None,
                          link_p=(n_ge_l[back] + 1) / (permutations + 1) if test_links else None, perm_stats=perm_stats, perm_link_stats=perm_link_stats)
+
+
+LINKAGE_METHODS = ("average", "single", "complete")
+# compare.linkage(device=...) runs the host restatement below this n and the kernels on device 0 from it on: the n from
+# which the device call beat the host restatement beyond both spreads (profiles/linkage_r32.log; README, "Dendrograms")
+LINKAGE_DEVICE_MIN = 4096
+
+
+def _linkage_device(device, n):
+    """The ``device`` of _capi.linkage_codes for the ``device`` of a caller: ... follows LINKAGE_DEVICE_MIN."""
+    from .suchtree import int_arg
+    if device is ...:
+        return 0 if n >= LINKAGE_DEVICE_MIN else -1
+    return -1 if device is None else int_arg("device", device)
+
+
+class Dendrogram:
+    """An exact dendrogram of n objects (linkage, SuchLinkedTrees.partner_dendrogram): n - 1 merges in the order they were
+    made, as scipy.cluster.hierarchy.linkage numbers them -- ids below n are objects, n + t is the cluster of merge t.
+
+    ``left`` < ``right`` (int64) are the two clusters of a merge and ``size`` (int64) the objects -- with weights, the
+    weight -- of the result; its value is the fraction ``num`` / ``den`` (int64: integers of the codes, not reduced),
+    ``heights`` = ldexp(num / den, -shift) in float64, ``shift`` being the fixed point of the codes.  Heights never
+    decrease; equal fractions are real ties, broken towards the lower slots (include/suchtree_hip.h, st_linkage_codes).
+    ``Z`` is the (n - 1, 4) float64 array scipy's ``dendrogram``, ``fcluster`` and ``cophenet`` take.  ``leaves`` /
+    ``names`` / ``measure`` are filled in by ``partner_dendrogram``.
+    """
+
+    def __init__(self, n, method, shift, rows):
+        self.n, self.method, self.shift = int(n), method, shift
+        self.left, self.right, self.size = (np.asarray(rows[k], dtype=np.int64).copy() for k in ("left", "right", "size"))
+        self.num, self.den = np.asarray(rows["num"], dtype=np.int64).copy(), np.asarray(rows["den"], dtype=np.int64).copy()
+        self.heights = np.array([math.ldexp(a / b, -(shift or 0)) for a, b in zip(self.num.tolist(), self.den.tolist())], dtype=np.float64)
+        self.leaves = self.names = self.measure = None
+
+    def __len__(self):
+        return self.n - 1
+
+    def __repr__(self):
+        return "Dendrogram(n=%d, method=%r, shift=%r)" % (self.n, self.method, self.shift)
+
+    @property
+    def Z(self):
+        return np.column_stack([self.left, self.right, self.heights, self.size]).astype(np.float64)
+
+    def members(self, t):
+        """The objects under merge ``t``, 0 <= t < n - 1, increasing."""
+        t = int(t)
+        if not 0 <= t < self.n - 1:
+            raise IndexError("merge %d of %d" % (t, self.n - 1))
+        out, stack = [], [self.n + t]
+        while stack:
+            c = stack.pop()
+            if c < self.n:
+                out.append(c)
+            else:
+                stack += (int(self.left[c - self.n]), int(self.right[c - self.n]))
+        return sorted(out)
+
+    def cophenetic(self):
+        """The cophenetic distances -- the height of the merge that first joins two objects -- condensed in this
+        library's pair order k = i (i - 1) / 2 + j, j < i."""
+        n = self.n
+        sq = np.zeros((n, n), dtype=np.float64)
+        lists = [np.array([i]) for i in range(n)]
+        for t, (l, r) in enumerate(zip(self.left.tolist(), self.right.tolist())):
+            a, b = lists[l], lists[r]
+            sq[np.ix_(a, b)] = sq[np.ix_(b, a)] = self.heights[t]
+            lists.append(np.concatenate([a, b]))
+            lists[l] = lists[r] = None
+        i, j = np.tril_indices(n, -1)
+        return sq[i, j]
+
+    def _names(self, names):
+        names = [str(i) for i in range(self.n)] if names is None else [str(v) for v in names]
+        if len(names) != self.n or len(set(names)) != self.n:
+            raise ValueError("names must be %d distinct names" % self.n)
+        return names
+
+    def to_newick(self, names=None):
+        """The ultrametric tree as Newick text: the node of a merge sits at half its height, leaves at 0, a branch is
+        the difference -- so two leaves are as far apart as the height of their merge.  ``names``: one per object
+        (default "0", "1", ...); a name with Newick punctuation is quoted."""
+        import re
+        names = self._names(names)
+        label = [v if re.fullmatch(r"[^\s()\[\],:;']+", v) else "'" + v.replace("'", "''") + "'" for v in names]
+        n, half = self.n, (self.heights / 2.0).tolist()
+        at = lambda c: 0.0 if c < n else half[c - n]      # noqa: E731
+        out, stack = [], [(2 * n - 2, None, "")]      # (cluster, its parent, what follows it); a text alone is written out
+        while stack:
+            item = stack.pop()
+            if isinstance(item, str):
+                out.append(item)
+                continue
+            c, up, after = item
+            tail = (";" if up is None else ":%r" % (at(up) - at(c))) + after
+            if c < n:
+                out.append(label[c] + tail)
+            else:
+                out.append("(")
+                stack.append(")" + tail)
+                stack.append((int(self.right[c - n]), c, ""))
+                stack.append((int(self.left[c - n]), c, ","))
+        return "".join(out)
+
+    def to_flat(self, names=None):
+        """The tree of :meth:`to_newick` as a FlatTree, through the Newick ingest: no GPU.  The ingest reads a zero length
+        as epsilon, as the reference does for a polytomy; a dendrogram's zero is a tie -- two merges at one height --
+        and is put back, so that ``min_branch=0.0`` of :func:`clade_side` finds it."""
+        from .newick import EPSILON, flat_tree_from_newick
+        flat = flat_tree_from_newick(self.to_newick(names))
+        length = np.array(flat.distance, dtype=np.float32)
+        length[length == np.float32(EPSILON)] = 0.0
+        flat.distance = length
+        return flat
+
+    def to_tree(self, names=None, device=0):
+        """The tree of :meth:`to_newick` as a :class:`SuchTree` on ``device``."""
+        from .suchtree import SuchTree
+        return SuchTree(self.to_flat(names), device=device)
+
+
+def linkage(d, method="average", weights=None, device=...):
+    """The exact dendrogram of a distance matrix: UPGMA (``method="average"``), single or complete linkage.
+
+    ``d`` is a square symmetric matrix (the diagonal is ignored) or a condensed vector in the project's triangle order
+    k = i (i - 1) / 2 + j, j < i; 2 <= n <= 16384; a NaN, an infinity, a cell whose mirror differs or a negative value is
+    a ValueError that names the cell.  The values become int32 codes (``_capi.mantel_quantise``: the largest one lands in
+    [2^30, 2^31), ``shift`` is reported) and the clustering is carried out on the codes in integers alone: pair sums in
+    int64, averages compared by cross-multiplication in 128 bits, so no rounding decides a merge and tied averages are
+    ties, broken towards the lower slots (include/suchtree_hip.h, st_linkage_codes, has the chain).  ``weights``: one
+    integer >= 1 per object, total at most 65536 -- object i stands for that many coincident objects.  ``device``:
+    None runs the host restatement, an index the kernels on that device -- the same integers; ... takes the host below
+    LINKAGE_DEVICE_MIN objects and device 0 from there.  Returns a :class:`Dendrogram`.  WPGMA, Ward and neighbour joining
+    are not exact in integers and are not offered.  An extension: the reference has no counterpart.
+    """
+    from . import _capi
+    if method not in LINKAGE_METHODS:
+        raise ValueError("method must be one of %s" % (LINKAGE_METHODS,))
+    square = np.ndim(d) == 2
+    v, n = mantel_condensed(d, "d", least=2)
+    bad = np.flatnonzero(v < 0)
+    if len(bad):
+        k = int(bad[0])
+        i = (1 + math.isqrt(8 * k + 1)) // 2
+        where = "d[%d][%d]" % (i, k - i * (i - 1) // 2) if square else "d[%d]" % k
+        raise ValueError("%s = %r is negative" % (where, float(v[k])))
+    codes, shift = _capi.mantel_quantise(v)
+    rows = _capi.linkage_codes(codes, weights, method, _linkage_device(device, n))
+    return Dendrogram(n, method, shift, rows)
+
+
+_linkage = linkage      # (dendrogram_congruence has an argument of that name)
+
+
+class TopologyTestResult:
+    """The topology test of phylosymbiosis (SuchTree.dendrogram_congruence, SuchLinkedTrees.phylosymbiosis_topology): is
+    the dendrogram of a distance matrix closer to the tree than the dendrogram with its objects relabelled?
+
+    Tree A of the match is the dendrogram, tree B the tree: ``rf``, ``rf_normalised``, ``exact``, ``n_a``, ``n_b`` and
+    ``mean_transfer`` are those of :class:`CladeMatches` (``matches``, the observed one), ``transfer_total`` the integer
+    sum of the transfer distances of the dendrogram's clades.  ``n_le`` counts the relabellings with rf_p <= rf,
+    ``transfer_n_le`` those with transfer_total_p <= transfer_total -- integers against integers, a relabelling that maps
+    the dendrogram onto itself ties and counts -- and ``p_value`` = (n_le + 1) / (permutations + 1), ``transfer_p_value``
+    likewise.  ``perm_rf`` / ``perm_transfer`` (int64, in draw order) with ``keep_stats=True``, else None.
+    ``dendrogram``, ``linkage``, ``rooted``, ``permutations``, ``seed``, ``stream`` repeat the run; ``leaves`` / ``names``
+    / ``measure`` are filled in by the facades.  Unpacks as ``rf, p, n = result``.  These are this library's
+    definitions: not claimed to reproduce another package's p-values.
+    """
+
+    def __init__(self, **kw):
+        self.leaves = self.names = self.measure = None
+        self.__dict__.update(kw)
+
+    def __iter__(self):
+        return iter((self.rf, self.p_value, self.n))
+
+    def __repr__(self):
+        return "TopologyTestResult(rf=%d, p_value=%r, transfer_total=%d, transfer_p_value=%r, n=%d, linkage=%r, permutations=%d)" % (
+            self.rf, self.p_value, self.transfer_total, self.transfer_p_value, self.n, self.linkage, self.permutations)
+
+
+def _topology_counts(m, rooted, size_a, n_b, distance, match):
+    """(rf, transfer_total) of one st_clade_match result, as CladeMatches defines them, in Python ints"""
+    distance = distance.astype(np.int64)
+    found = match >= 0
+    p = size_a if rooted else np.minimum(size_a, m - size_a)
+    transfer = np.where(found, np.minimum(distance, p - 1), p - 1)
+    return len(size_a) + n_b - 2 * int((found & (distance == 0)).sum()), int(transfer.sum())
+
+
+def dendrogram_congruence(flat, leaf_ids, y, linkage="average", rooted=True, min_branch=None, permutations=999, seed=None, stream=0,
+                          keep_stats=False, device=..., match_device=...):
+    """The topology test behind SuchTree.dendrogram_congruence: the dendrogram of ``y`` (:func:`linkage` with method
+    ``linkage``; a :class:`Dendrogram` is taken as it is) against the flat tree ``flat`` over ``leaf_ids``, object k of y
+    being listed leaf k.
+
+    The observed match is ``match_clades(dendrogram, tree)`` with ``rooted`` and ``min_branch`` (``min_branch=0.0``
+    leaves out, on both sides, the clades that exist only because a tie was broken: their branch is 0).  Relabelling
+    p = 1 .. permutations is sigma_p = ``hommola_permutation(seed, stream, p, 0, n)``, numbered as :func:`mantel` numbers
+    its permutations: object sigma_p[k] of the dendrogram is aligned with listed leaf k.  Both trees' clade ranges are
+    computed once; a relabelling is one ``_capi.clade_match`` call with another alignment, so the first k relabellings
+    are the same for any ``permutations`` >= k.  ``device``: None = everything on the host; an index = the linkage and
+    the matches on that device; ... = the linkage as :func:`linkage` decides and the matches on ``match_device`` (... =
+    device 0).  The same integers either way.  Returns a :class:`TopologyTestResult`.
+    """
+    from . import _capi
+    from .suchtree import int_arg, seed_arg
+    if linkage not in LINKAGE_METHODS:
+        raise ValueError("linkage must be one of %s" % (LINKAGE_METHODS,))
+    permutations, stream = int_arg("permutations", permutations, (1 << 31) - 1, "2^31 - 1"), int_arg("stream", stream, (1 << 31) - 1, "2^31 - 1")
+    seed = seed_arg(seed)
+    ids = np.ascontiguousarray(leaf_ids, dtype=np.int64)
+    n = len(ids)
+    if ids.ndim != 1 or n < 4 or n > _capi.LINKAGE_MAX_OBJECTS:
+        raise ValueError("%d leaves: 4 to %d" % (n, _capi.LINKAGE_MAX_OBJECTS))
+    if device is ...:
+        dev = 0 if match_device is ... else -1 if match_device is None else int_arg("match_device", match_device)
+        link_device = dev if dev >= 0 and n >= LINKAGE_DEVICE_MIN else None
+    else:
+        dev = -1 if device is None else int_arg("device", device)
+        link_device = device
+    dend = y if isinstance(y, Dendrogram) else _linkage(y, linkage, device=link_device)
+    if dend.n != n:
+        raise ValueError("y is over %d objects, not over the %d leaves" % (dend.n, n))
+    rooted = bool(rooted)
+    d_flat = dend.to_flat()
+    d_ids = np.fromiter((d_flat.leaves[str(i)] for i in range(n)), dtype=np.int64, count=n)
+    side_a = clade_side(d_flat, d_ids, rooted, min_branch)
+    observed = match_clades(d_flat, d_ids, flat, ids, rooted, None, min_branch, None if dev < 0 else dev, side_a=side_a)
+    side_b = clade_side(flat, ids, rooted, min_branch)
+    where_b = np.empty(n, dtype=np.int32)
+    where_b[side_b[0]] = np.arange(n, dtype=np.int32)
+    size_a = (side_a[3] - side_a[2]).astype(np.int64)
+    n_b = len(side_b[1])
+
+    def counts(pos_b):
+        distance, match, _ = _capi.clade_match(n, pos_b, side_a[2], side_a[3], side_b[2], side_b[3], rooted, dev)
+        return _topology_counts(n, rooted, size_a, n_b, distance, match)
+    rf0, transfer0 = counts(where_b[side_a[0]])
+    perm_rf, perm_transfer = np.zeros(permutations, dtype=np.int64), np.zeros(permutations, dtype=np.int64)
+    inverse = np.empty(n, dtype=np.int64)
+    for p in range(1, permutations + 1):
+        inverse[hommola_permutation(seed, stream, p, 0, n)] = np.arange(n)      # (listed leaf inverse[o] meets object o)
+        perm_rf[p - 1], perm_transfer[p - 1] = counts(where_b[inverse[side_a[0]]])
+    n_le, transfer_n_le = int((perm_rf <= rf0).sum()), int((perm_transfer <= transfer0).sum())
+    return TopologyTestResult(rf=rf0, rf_normalised=observed.rf_normalised, exact=observed.exact, n_a=observed.n_a, n_b=observed.n_b,
+                              transfer_total=transfer0, mean_transfer=observed.mean_transfer, n_le=n_le, transfer_n_le=transfer_n_le,
+                              p_value=(n_le + 1) / (permutations + 1), transfer_p_value=(transfer_n_le + 1) / (permutations + 1),
+                              perm_rf=perm_rf if keep_stats else None, perm_transfer=perm_transfer if keep_stats else None, matches=observed,
+                              dendrogram=dend, linkage=dend.method, rooted=rooted, permutations=permutations, seed=seed, stream=stream, n=n)

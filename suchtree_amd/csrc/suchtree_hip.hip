@@ -91,6 +91,9 @@
 // kernels_parafit.h (the held side expanded once, one sort per permutation and linked leaf, a wave form with both sides in
 // LDS, a row form that stages one matrix row in LDS per workgroup, the fold with the per-link counts), host_parafit.h (the
 // layout, the launches) and, host-only, parafit_plan.cpp (the checks, the layout, the restatement).
+// Exact UPGMA, single and complete linkage of a matrix of codes (st_linkage_codes): kernels_linkage.h (the square of pair
+// sums, every row's nearest later partner, the chain of merges as one workgroup), host_linkage.h (the layout, the three
+// launches, where the cache lives) and, host-only, linkage_plan.cpp (the checks, the restatement with the same cache).
 //
 // What the host side does: tree upload to one or several GPUs (tree_prep.cpp builds the tables, under a table budget
 // if one is given), the host path (host_pipe.h, host_copy.h: packed ids in through the copy engine, kernels write
@@ -222,6 +225,7 @@ static int device_index_arg(int device)
 #include "kernels_group.h"
 #include "kernels_class.h"
 #include "kernels_parafit.h"
+#include "kernels_linkage.h"
 
 
 // --------------------------------------------------------------------------
@@ -248,6 +252,7 @@ using namespace st;
 #include "host_group.h"
 #include "host_class.h"
 #include "host_parafit.h"
+#include "host_linkage.h"
 
 // the next link of st_link_sample_pairs (MuchTree.pyx:2946-2949)
 static int64_t link_draw(uint64_t &s, int64_t n_links)
@@ -1238,6 +1243,19 @@ try {
         return ST_OK;
     }
     return parafit_device(device, P, g_f, g_s, link_f, link_s, seed, total, link_obs, link_n_ge, link_all);
+} ST_CATCH_ALL
+
+int st_linkage_codes(int device, const int32_t *codes, int32_t n, const int32_t *weights, int32_t method, st_linkage_row *out_rows)
+try {
+    std::string err;
+    const int rc = linkage_args(codes, n, weights, method, out_rows, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (device_or_host_arg(device) != ST_OK) return ST_ERR_ARG;
+    if (device < 0) {
+        linkage_host(codes, n, weights, method, out_rows);
+        return ST_OK;
+    }
+    return linkage_device(device, codes, n, weights, method, out_rows);
 } ST_CATCH_ALL
 
 int st_graph_matrices_host(int device, int64_t n, int64_t n_edges, const int32_t *u, const int32_t *v,

@@ -705,9 +705,10 @@ class SuchLinkedTrees:
         out.leaves, out.names, out.measure = observed.leaves, observed.names, measure
         return out
 
-    def _phylosymbiosis_matrices(self, of, measure, pool, min_partners, max_partners, exclude_shared, control=None):
-        """(the row tree, the observed measure over the partner rows, x: the row leaves' own tree distances, y: the
-        ``measure`` between their partner sets) of :meth:`phylosymbiosis`; a NaN in y is its ValueError."""
+    def _phylosymbiosis_matrices(self, of, measure, pool, min_partners, max_partners, exclude_shared, control=None, with_x=True):
+        """(the row tree, the observed measure over the partner rows, x: the row leaves' own tree distances -- None
+        without ``with_x`` --, y: the ``measure`` between their partner sets) of :meth:`phylosymbiosis`; a NaN in y is its
+        ValueError."""
         from . import compare
         by_distance = measure in ("beta_mpd", "beta_mntd")
 
@@ -726,7 +727,7 @@ class SuchLinkedTrees:
             i, j = observed.pair(int(bad[0]))
             raise ValueError("%s of rows %d and %d (%s, %s) is NaN" % (measure, i, j, observed.names[i], observed.names[j]))
         own = self._tree_a if of == "A" else self._tree_b
-        return own, observed, own.pairwise_distances(observed.leaves.tolist()), y
+        return own, observed, own.pairwise_distances(observed.leaves.tolist()) if with_x else None, y
 
     def phylosymbiosis_correlogram(self, of="A", measure="unifrac", n_classes=None, breaks=None, cutoff=True, method="pearson", permutations=999,
                                    seed=None, correction="holm", progressive=True, pool="subset", min_partners=1, max_partners=None,
@@ -759,6 +760,65 @@ class SuchLinkedTrees:
         out = compare.mantel_correlogram(x, y, n_classes=n_classes, breaks=breaks, cutoff=cutoff, method=method, permutations=permutations, seed=seed,
                                          correction=correction, progressive=progressive, keep_stats=keep_stats,
                                          device=own._device if device is ... else device, chunk_tasks=chunk_tasks)
+        out.leaves, out.names, out.measure = observed.leaves, observed.names, measure
+        return out
+
+    def _dendrogram_rows(self, of, measure, linkage, pool, min_partners, max_partners, exclude_shared):
+        """(the row tree, the observed measure, y) of :meth:`partner_dendrogram` and :meth:`phylosymbiosis_topology`"""
+        from . import compare
+        if measure not in self.PHYLOSYMBIOSIS_MEASURES:
+            raise ValueError("measure must be one of %s" % (self.PHYLOSYMBIOSIS_MEASURES,))
+        if linkage not in compare.LINKAGE_METHODS:
+            raise ValueError("linkage must be one of %s" % (compare.LINKAGE_METHODS,))
+        own, observed, _, y = self._phylosymbiosis_matrices(of, measure, pool, min_partners, max_partners, exclude_shared, with_x=False)
+        if len(observed.leaves) < 4:
+            raise ValueError("%d rows: 4 to %d" % (len(observed.leaves), _capi.LINKAGE_MAX_OBJECTS))
+        return own, observed, y
+
+    def partner_dendrogram(self, of="A", measure="unifrac", linkage="average", pool="subset", min_partners=1, max_partners=None,
+                           exclude_shared=False, device=...):
+        """The dendrogram of the leaves of one tree by the similarity of their partners in the other: the partner-set
+        distances of :meth:`phylosymbiosis`, clustered exactly.
+
+        The rows and ``measure`` (with ``pool``, ``min_partners``, ``max_partners`` and ``exclude_shared``) are those of
+        :meth:`phylosymbiosis`, a NaN in the measure is the same ValueError; 4 to 16384 rows.  ``linkage`` ("average" =
+        UPGMA, "single", "complete") and ``device`` are those of :func:`~suchtree_amd.compare.linkage` (... = the host
+        restatement below ``compare.LINKAGE_DEVICE_MIN`` rows, the row tree's device from there; the matrix still comes
+        from the trees' kernels, so the call needs a GPU either way).
+
+        The subset state, ``linklist`` and the generator of :meth:`sample_linked_distances` are left as they were.
+        Returns a :class:`~suchtree_amd.compare.Dendrogram` with ``leaves`` (the rows' leaf ids), ``names`` and
+        ``measure``.  An extension: the reference has no counterpart.
+        """
+        from . import compare
+        own, observed, y = self._dendrogram_rows(of, measure, linkage, pool, min_partners, max_partners, exclude_shared)
+        if device is ... and len(observed.leaves) >= compare.LINKAGE_DEVICE_MIN:
+            device = own._device
+        out = compare.linkage(y, linkage, device=device)
+        out.leaves, out.names, out.measure = observed.leaves, observed.names, measure
+        return out
+
+    def phylosymbiosis_topology(self, of="A", measure="unifrac", linkage="average", rooted=True, min_branch=None, permutations=999, seed=None,
+                                stream=0, pool="subset", min_partners=1, max_partners=None, exclude_shared=False, keep_stats=False, device=...):
+        """Phylosymbiosis by topology (Brooks et al. 2016): is the dendrogram of the leaves' partner sets
+        (:meth:`partner_dendrogram`) closer to the leaves' own tree than chance -- by Robinson-Foulds and by the transfer
+        distance, against relabellings of the dendrogram's objects.  :meth:`phylosymbiosis` asks the same of the two
+        distance matrices; this asks it of the two branching orders.
+
+        The rows, ``measure``, ``pool``, ``min_partners``, ``max_partners`` and ``exclude_shared`` are those of
+        :meth:`phylosymbiosis` (4 to 16384 rows); ``linkage``, ``rooted``, ``min_branch``, ``permutations``, ``seed``,
+        ``stream``, ``keep_stats`` and ``device`` those of :meth:`SuchTree.dendrogram_congruence` on the row tree
+        (``min_branch=0.0`` leaves out the clades that a broken tie made: leaves with identical partner sets).
+
+        The subset state, ``linklist`` and the generator of :meth:`sample_linked_distances` are left as they were.
+        Returns a :class:`~suchtree_amd.compare.TopologyTestResult` with ``leaves``, ``names`` and ``measure``.  An
+        extension: the reference has no counterpart.
+        """
+        int_arg("permutations", permutations, (1 << 31) - 1, "2^31 - 1")
+        seed = seed_arg(seed)
+        own, observed, y = self._dendrogram_rows(of, measure, linkage, pool, min_partners, max_partners, exclude_shared)
+        out = own.dendrogram_congruence(y, observed.leaves, linkage=linkage, rooted=rooted, min_branch=min_branch, permutations=permutations, seed=seed,
+                                        stream=stream, keep_stats=keep_stats, device=device)
         out.leaves, out.names, out.measure = observed.leaves, observed.names, measure
         return out
 

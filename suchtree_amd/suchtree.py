@@ -847,6 +847,32 @@ class SuchTree(TreeNavigation):
         out.leaves, out.names = ids.copy(), [self.leaf_nodes[int(v)] for v in ids.tolist()]
         return out
 
+    def dendrogram_congruence(self, y, leaves, linkage="average", rooted=True, min_branch=None, permutations=999, seed=None, stream=0,
+                              keep_stats=False, device=...):
+        """Does the dendrogram of another distance matrix over the same objects share this tree's topology?  The
+        topology test of phylosymbiosis (Brooks et al. 2016): ``y`` is clustered exactly (UPGMA by default) and the
+        dendrogram is matched against this tree by Robinson-Foulds and the transfer distance, against relabellings of
+        the dendrogram's objects.
+
+        ``leaves`` (leaf names or leaf ids, 4 to 16384, none repeated) are the objects in the order of ``y``'s rows.
+        ``y`` (square symmetric or condensed in the triangle order; or a :class:`~suchtree_amd.compare.Dendrogram`),
+        ``linkage``, ``rooted``, ``min_branch``, ``permutations``, ``seed``, ``stream`` and ``keep_stats`` are those of
+        :func:`~suchtree_amd.compare.dendrogram_congruence`, which does the work: ``device`` ... = the clade matches on
+        this tree's device and the linkage where :func:`~suchtree_amd.compare.linkage` puts it by n; None = all of it
+        on the host, without a GPU; an index = all of it there.  The same integers either way: the tree is not
+        uploaded, the call needs its parent array and branch lengths alone.  Returns a
+        :class:`~suchtree_amd.compare.TopologyTestResult` with ``leaves`` (leaf ids) and ``names``.  An extension: the
+        reference has no counterpart.
+        """
+        from . import compare
+        ids = self._leaf_ids(leaves, "leaves")
+        if len(np.unique(ids)) != len(ids):
+            raise ValueError("leaves: a repeated leaf")
+        out = compare.dendrogram_congruence(self._flat, ids, y, linkage=linkage, rooted=rooted, min_branch=min_branch, permutations=permutations,
+                                            seed=seed, stream=stream, keep_stats=keep_stats, device=device, match_device=self._device)
+        out.leaves, out.names = ids.copy(), [self.leaf_nodes[int(v)] for v in ids.tolist()]
+        return out
+
     def unifrac(self, sets, root=None, begin=0, count=None, shift=None, chunk_pairs=0):
         """How different are every two sets of leaves, measured on this tree: Faith's PD and unweighted UniFrac, on the GPU.
 
