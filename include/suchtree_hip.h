@@ -56,7 +56,7 @@ extern "C" {
  *      st_group_sums_codes; then, also additive, struct st_parafit_sum and st_parafit_codes; then, also additive,
  *      ST_CLASS_MAX, ST_CLASS_NONE and st_class_sums_codes; then, also additive, st_swap_null_tables, st_swap_null_schedule,
  *      st_dispersion_matrix_swap and st_partner_dispersion_swap_host; then, also additive, struct st_linkage_row, the
- *      ST_LINKAGE_* constants and st_linkage_codes.
+ *      ST_LINKAGE_* constants and st_linkage_codes; then, also additive, ST_RF_MAX_LEAVES and st_rf_tasks.
  *   6 (round 6): st_api_version, st_tree_info_get_sized, st_probe_last_choice, option "ladder_sums" added; st_tree_info.reserved0
  *                is now ladder_sums, ladder_sums_max_pairs appended (8 bytes); option "tile_sort" selects nothing on records of 128 bytes and more (kernel forms removed).
  *   5 (round 5): st_tree_info grew by 8 bytes (b_table_bytes_per_leaf, reserved0); st_host_alloc / st_host_free,
@@ -1099,6 +1099,59 @@ typedef struct st_linkage_row {
 } st_linkage_row;
 
 int st_linkage_codes(int device, const int32_t *codes, int32_t n, const int32_t *weights, int32_t method, st_linkage_row *out_rows);
+
+/*
+ * Which clades do the trees of a set share, pair by pair: the exact count behind the Robinson-Foulds distance between
+ * every two trees of a set (bootstrap replicates, a posterior sample, dendrograms under several measures), behind the
+ * number of trees that hold each clade, and behind the Robinson-Foulds column of a relabelling test (compare.tree_set,
+ * compare.rf_relabelled).  Only identical clades are counted, not the closest one (that is st_clade_match), so the method
+ * is Day's: near-linear per pair of trees, all integers.  The call needs no tree handle, only positions and ranges.
+ *
+ * Input.  One list of m common leaves, 4 <= m <= ST_RF_MAX_LEAVES = 16384 (a position fits 16 bits; above it
+ * st_clade_match per pair is the route), and n_trees trees.  For tree t, where[t * m + k] is the depth-first position in
+ * t of common leaf k (the inverse of st_clade_ranges' out_order), and its eligible clades are the ranges lo / hi at
+ * [clade_offsets[t], clade_offsets[t + 1]) of one concatenated list: what st_clade_ranges writes for the same `unrooted`
+ * flag, after any filter of the caller's.  align is NULL or n_align rows of m int32, each a permutation of 0 .. m - 1.
+ * Tasks come in one of two forms: the arrays task_i, task_j (and task_p, which may be NULL: the identity everywhere) of
+ * length n_tasks, task_p[t] = -1 being the identity and begin being 0; or, with all three NULL, the n_tasks pairs
+ * [begin, begin + n_tasks) of the triangle in the order k = i (i - 1) / 2 + j, j < i, under the identity.
+ *
+ * A task (i, j, p), with a = align[p] or the identity: common leaf k of tree i meets common leaf a[k] of tree j.  For
+ * clade b of j, Q_b = { where_i[k] : lo_b <= where_j[a[k]] < hi_b }.  b is shared when some clade c of i has
+ * [lo_c, hi_c) = Q_b (rooted), or = Q_b or its complement in [0, m) (unrooted).  out_shared[task] is the number of shared
+ * b.  With lists from st_clade_ranges this is the number of rows of delta 0 of st_clade_match over the same two sides and
+ * alignment, in either direction, and RF = n_i + n_j - 2 shared.  i = j with the identity gives n_i.
+ * out_count (int64, one per clade of the concatenated list; NULL skips it) is zeroed, then every shared b of every task
+ * adds 1 to its own entry and 1 to the entry of the matching c (the first in i's list, should a caller's list repeat a
+ * set).  The additions are integers: their order does not matter.  Over the whole triangle, entry c of tree t ends as
+ * the number of other trees that hold the clade.
+ *
+ * Method.  q[where_j[a[k]]] = where_i[k] is one scatter of m entries; Q_b = q[lo_b .. hi_b) is a range if and only if
+ * max - min + 1 = size, and then the range [min, max + 1) is looked up in tree i's list, sorted once per call.  Unrooted,
+ * every key is the side without i's position 0: a range of i's list that starts at 0 is stored as [hi, m), and a clade of
+ * j that holds the leaf at i's position 0 is tested through its complement, the two ranges [0, lo_b) and [hi_b, m).
+ * device = -1 is the host restatement (no GPU, one thread, the same tables); device >= 0 runs k_rf_tasks, one task per
+ * workgroup: q as 16-bit entries in LDS, min and max per block of 64 positions, a sparse table over the at most 256 blocks
+ * (9 levels), so that the extrema of a range are two partial blocks and two table entries; a binary search per clade in
+ * tree i's keys (global memory); 2 m + 16 bytes of LDS and at most 9 KiB of table, 42,000 bytes at the cap.
+ * chunk_tasks: tasks per launch and read-back, 0 = 65536, at most 2^24 (more is cut to that); no result depends on it.
+ *
+ * Checked, before anything is launched or written (ST_ERR_ARG, naming the cell): m in range; no negative count, begin or
+ * chunk_tasks; no NULL where an array is needed; clade_offsets from 0, non-decreasing, below 2^31; every row of where a
+ * permutation of 0 .. m - 1; every range 0 <= lo < hi <= m; every row of align a permutation; task_i and task_j given
+ * together and begin = 0 with them; every tree index and every alignment index of a task in range (ST_ERR_BOUNDS, naming
+ * the task); the triangle range inside n_trees (n_trees - 1) / 2; out_shared.  Not verified: that a tree's ranges form a
+ * laminar family, are distinct, or come from st_clade_ranges -- any list of ranges is processed as it stands.
+ * Device memory: 2 m bytes per tree and per alignment row, 12 bytes per clade, 4 (n_trees + 1) bytes of offsets, 12 bytes
+ * per explicit task, 8 bytes per clade with out_count, and two chunks of 4 bytes per task of results.  An allocation that
+ * fails is ST_ERR_NOMEM with the bytes asked for, before any output is written.  n_tasks = 0 launches nothing.  A tree
+ * without clades (a star) shares 0.  No counterpart in the reference, which offers bipartitions() as Python sets.
+ */
+#define ST_RF_MAX_LEAVES 16384
+
+int st_rf_tasks(int device, int32_t m, int32_t n_trees, const int32_t *where, const int64_t *clade_offsets, const int32_t *lo,
+                const int32_t *hi, int32_t unrooted, const int32_t *align, int32_t n_align, const int32_t *task_i, const int32_t *task_j,
+                const int32_t *task_p, int64_t n_tasks, int64_t begin, int64_t chunk_tasks, int32_t *out_shared, int64_t *out_count);
 
 /*
  * Exact Spearman rank correlation of the same pairs.  rank_x is the midrank of x_k among the call's n float32 distances

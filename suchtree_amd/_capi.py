@@ -52,7 +52,7 @@ SYMBOLS = (
     "st_beta_dispersion_host", "st_beta_dispersion_matrix", "st_unifrac_null_host", "st_unifrac_null_depths",
     "st_mantel_codes", "st_mantel_quantise", "st_group_sums_codes", "st_parafit_codes", "st_class_sums_codes",
     "st_swap_null_tables", "st_swap_null_schedule", "st_dispersion_matrix_swap", "st_partner_dispersion_swap_host",
-    "st_linkage_codes",
+    "st_linkage_codes", "st_rf_tasks",
 )
 
 CLADE_RECT, CLADE_TRI = 0, 1     # include/suchtree_hip.h: ST_CLADE_RECT / ST_CLADE_TRI
@@ -573,6 +573,65 @@ def linkage_codes(codes, weights=None, method="average", device=-1):
     return out
 
 
+RF_MAX_LEAVES = 16384      # ST_RF_MAX_LEAVES: common leaves of st_rf_tasks
+
+
+def rf_tasks(m, where, clade_offsets, lo, hi, rooted=False, align=None, task_i=None, task_j=None, task_p=None, begin=0, count=None,
+             want_count=True, device=-1, chunk_tasks=0):
+    """st_rf_tasks: (shared, counts).  ``where`` is (n_trees, m) int32 -- row t takes common leaf k to its depth-first
+    position in tree t -- and tree t's clades are the ranges ``lo`` / ``hi`` at ``clade_offsets[t] : clade_offsets[t + 1]``
+    (n_trees + 1 int64 offsets from 0).  Tasks: ``task_i`` / ``task_j`` (and ``task_p``: a row of ``align`` -- (n_align, m)
+    int32 permutations -- or -1 for the identity), or without them the pairs [begin, begin + count) of the triangle
+    k = i (i - 1) / 2 + j, j < i (``count=None``: to its end).  ``shared[t]`` (int32) is the number of clades of tree j
+    that are clades of tree i under the task's alignment: common leaf k of i meets common leaf a[k] of j.  ``counts``
+    (int64 per clade of the concatenated list, None with ``want_count=False``): every shared clade adds 1 to its own
+    entry and 1 to its match's.  ``device`` -1 = the host restatement (no GPU), else the kernel on that device: the same
+    integers.  ValueError for a bad argument, IndexError for a task that names a tree or an alignment out of range."""
+    arr = lambda a: np.ascontiguousarray(a, dtype=np.int32)      # noqa: E731
+    m = int(m)
+    if m > RF_MAX_LEAVES:      # (before anything is sized by it)
+        raise ValueError("a list of %d leaves: at most %d" % (m, RF_MAX_LEAVES))
+    where, lo, hi = arr(where), arr(lo), arr(hi)
+    offsets = np.ascontiguousarray(clade_offsets, dtype=np.int64)
+    if where.ndim != 2 or where.shape[1] != m or offsets.ndim != 1 or len(offsets) != len(where) + 1 or lo.ndim != 1 or lo.shape != hi.shape:
+        raise ValueError("where must be (n_trees, m), clade_offsets n_trees + 1 offsets, and lo and hi the same number of ranges")
+    if len(lo) != int(offsets[-1]):
+        raise ValueError("clade_offsets end at %d, lo and hi hold %d ranges" % (int(offsets[-1]), len(lo)))
+    n_trees = len(where)
+    if align is not None:
+        align = arr(align)
+        if align.ndim != 2 or align.shape[1] != m:
+            raise ValueError("align must be (n_align, m)")
+    if int(chunk_tasks) < 0:
+        raise ValueError("chunk_tasks < 0")
+    if task_i is None and task_j is None:
+        if task_p is not None:
+            raise ValueError("task_p without task_i and task_j")
+        total = n_trees * (n_trees - 1) // 2
+        begin = int(begin)
+        n_tasks = max(total - begin, 0) if count is None else int(count)
+    else:
+        if task_i is None or task_j is None:
+            raise ValueError("task_i and task_j come together")
+        task_i, task_j = arr(task_i), arr(task_j)
+        task_p = None if task_p is None else arr(task_p)
+        if task_i.ndim != 1 or task_i.shape != task_j.shape or (task_p is not None and task_p.shape != task_i.shape):
+            raise ValueError("the task arrays must be 1-D and of equal length")
+        if int(begin) != 0 or (count is not None and int(count) != len(task_i)):
+            raise ValueError("begin and count belong to the triangle form")
+        begin, n_tasks = 0, len(task_i)
+    shared = np.zeros(max(n_tasks, 0), dtype=np.int32)
+    counts = np.zeros(len(lo), dtype=np.int64) if want_count else None
+    opt = lambda a: None if a is None or not a.size else _arg(a)      # noqa: E731
+    rc = load().st_rf_tasks(int(device), m, n_trees, opt(where), _arg(offsets), opt(lo), opt(hi), 0 if rooted else 1, opt(align),
+                            0 if align is None else len(align), opt(task_i), opt(task_j), opt(task_p), n_tasks, begin, int(chunk_tasks),
+                            opt(shared), opt(counts))
+    if rc == ST_ERR_BOUNDS:
+        raise IndexError(last_error())
+    check(rc)
+    return shared, counts
+
+
 QUARTET_MODE = {"all": 0, "sample": 1}     # include/suchtree_hip.h: ST_QUARTET_ALL / ST_QUARTET_SAMPLE
 QUARTET_MAX_LEAVES_ALL = 65536
 
@@ -841,6 +900,7 @@ def load():
                                       ctypes.POINTER(i64)]
         L.st_clade_match.argtypes = [i32, ctypes.c_int32, vp, vp, vp, ctypes.c_int32, vp, vp, ctypes.c_int32, ctypes.c_int32, i64, vp, vp, vp]
         L.st_linkage_codes.argtypes = [i32, vp, ctypes.c_int32, vp, ctypes.c_int32, vp]
+        L.st_rf_tasks.argtypes = [i32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int32, vp, vp, vp, i64, i64, i64, vp, vp]
         L.st_clade_plan.argtypes = [vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64),
                                     ctypes.POINTER(i64)]
         L.st_compare_clades_host.argtypes = [vp, vp, vp, i64, vp, vp, i64, i64, i64, vp, vp, ctypes.POINTER(i64)]

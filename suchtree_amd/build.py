@@ -15,13 +15,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsuchtree_hip.so")
 # Five HIP translation units (each kernel family with its launch functions + the C ABI and host side; launch_canopy.hip in four
-# parts) and eighteen host-only C++ files: compiled to objects in parallel, then linked.
+# parts) and nineteen host-only C++ files: compiled to objects in parallel, then linked.
 HIP_SOURCES = [os.path.join(CSRC, f) for f in ("suchtree_hip.hip", "launch_walk.hip", "launch_canopy.hip",
                                                "launch_canopy_sorted.hip", "launch_canopy_codes.hip")]
 CPP_SOURCES = [os.path.join(CSRC, f) for f in ("tree_prep.cpp", "newick_parse.cpp", "compare_plan.cpp", "rank_plan.cpp",
                                                "kendall_plan.cpp", "quartet_plan.cpp", "hommola_plan.cpp", "dispersion_plan.cpp", "setpair_plan.cpp",
                                                "unifrac_plan.cpp", "unifrac_null_plan.cpp", "clade_match_plan.cpp", "mantel_plan.cpp", "group_plan.cpp",
-                                               "parafit_plan.cpp", "class_plan.cpp", "swap_plan.cpp", "linkage_plan.cpp")]
+                                               "parafit_plan.cpp", "class_plan.cpp", "swap_plan.cpp", "linkage_plan.cpp", "rf_plan.cpp")]
 SOURCES = HIP_SOURCES + CPP_SOURCES
 # (source, extra flags, object name): launch_canopy.hip holds the slowest instantiations (the scalar ladder kernel's two forms, the
 # predicated kernel's long-chain forms) and is compiled in four parts, two pair sources each

@@ -1066,6 +1066,243 @@ class TransferSupport:
         return pd.DataFrame({k: getattr(self, k) for k in self.COLUMNS})
 
 
+def read_flat_tree(tree, extended=False):
+    """The flat arrays of one tree of a collection (transfer_support's replicates, :func:`tree_set`'s trees): a SuchTree's
+    own, a Newick text or the path of a Newick file parsed to flat arrays only -- nothing goes to a GPU.  ``extended``
+    also takes a :class:`Dendrogram` (through ``to_flat()``) and a flat tree itself.  None for anything else."""
+    from .newick import flat_tree_from_newick
+    from .suchtree import SuchTree
+    if isinstance(tree, SuchTree):
+        return tree._flat
+    if isinstance(tree, str):
+        text = tree.strip()
+        if not (text.startswith("(") and text.endswith(";")):
+            with open(tree) as fh:
+                text = fh.read()
+        return flat_tree_from_newick(text)
+    if extended and isinstance(tree, Dendrogram):
+        return tree.to_flat()
+    if extended and all(hasattr(tree, k) for k in ("parent", "distance", "leaves")):
+        return tree
+    return None
+
+
+# compare.tree_set(device=...) and compare.rf_relabelled(device=...) run the host restatement while tasks x leaves is
+# below this and the kernel on device 0 from it on.  A device call costs 0.8 ms at 64 leaves to 2.6 ms at 16384 whatever it
+# computes (the work block, the stream, the read-back ring), the host restatement about 0.02 to 0.06 microseconds per
+# task and leaf.  Measured (profiles/tree_set_r33.log; medians of 5, beyond both spreads): the host wins up to 496 tasks
+# of 64 leaves, 28 of 1024 and 1 of 16384 (31,744 / 28,672 / 16,384 tasks x leaves); the device wins from 1128 tasks of 64
+# leaves, 66 of 1024 and 3 of 16384 (72,192 / 67,584 / 49,152).  72 x 1024 is at or above the first point the device won
+# at in every column (README, "A whole set of trees"; DESIGN.md section 29)
+RF_DEVICE_MIN_WORK = 73728
+
+
+def _rf_device(device, n_tasks, m):
+    """The ``device`` of _capi.rf_tasks for the ``device`` of a caller: ... follows RF_DEVICE_MIN_WORK."""
+    from .suchtree import int_arg
+    if device is ...:
+        return 0 if n_tasks * m >= RF_DEVICE_MIN_WORK else -1
+    return -1 if device is None else int_arg("device", device)
+
+
+def _rf_sides(sides, m):
+    """(where, offsets, lo, hi) of st_rf_tasks from one :func:`clade_side` per tree"""
+    where = np.empty((len(sides), m), dtype=np.int32)
+    for t, side in enumerate(sides):
+        where[t, side[0]] = np.arange(m, dtype=np.int32)
+    offsets = np.zeros(len(sides) + 1, dtype=np.int64)
+    np.cumsum([len(side[1]) for side in sides], out=offsets[1:])
+    cat = lambda k: np.concatenate([side[k] for side in sides]).astype(np.int32) if sides else np.zeros(0, dtype=np.int32)      # noqa: E731
+    return where, offsets, cat(2), cat(3)
+
+
+class TreeSetComparison:
+    """Every two trees of a set compared by the clades they share (:func:`tree_set`).
+
+    ``n_trees``, ``n_leaves_shared`` (m), ``rooted``, and the range ``begin`` / ``count`` of the triangle of pairs in the
+    order k = i (i - 1) / 2 + j, j < i.  ``n_clades`` (int64, per tree) are the eligible clades.  Per pair of the range,
+    condensed: ``shared`` (int64, the clades the two trees have in common), ``rf`` = n_i + n_j - 2 shared (int64, the
+    Robinson-Foulds distance) and ``rf_normalised`` = rf / (n_i + n_j) (NaN where neither tree has a clade).  All
+    integers: they do not depend on the device or the chunking.  ``leaves`` are the common leaf names, ``names`` one label
+    per tree (its index, unless the caller set others).
+    """
+
+    COLUMNS = ("i", "j", "shared", "rf", "rf_normalised")
+
+    def __init__(self, sides, m, rooted, begin, shared, counts, leaves):
+        self.n_trees, self.n_leaves_shared, self.rooted = len(sides), int(m), bool(rooted)
+        self.begin, self.count = int(begin), len(shared)
+        self.n_clades = np.array([len(side[1]) for side in sides], dtype=np.int64)
+        self.leaves, self.names = list(leaves), [str(t) for t in range(len(sides))]
+        self._sides = sides
+        k = np.arange(self.begin, self.begin + self.count, dtype=np.int64)
+        i = ((1 + np.sqrt(8.0 * k + 1.0)) // 2).astype(np.int64)
+        i = np.where(i * (i - 1) // 2 > k, i - 1, i)
+        i = np.where((i + 1) * i // 2 <= k, i + 1, i)
+        self.i, self.j = i, k - i * (i - 1) // 2
+        self.shared = np.asarray(shared, dtype=np.int64)
+        total = self.n_clades[self.i] + self.n_clades[self.j]
+        self.rf = total - 2 * self.shared
+        with np.errstate(invalid="ignore", divide="ignore"):
+            self.rf_normalised = np.where(total > 0, self.rf / total.astype(np.float64), np.nan)
+        self._frequency = None
+        if counts is not None:
+            offsets = np.concatenate([[0], np.cumsum(self.n_clades)])
+            self._frequency = [np.asarray(counts[offsets[t]:offsets[t + 1]], dtype=np.int64) + 1 for t in range(self.n_trees)]
+
+    def __len__(self):
+        return self.count
+
+    def __repr__(self):
+        return "TreeSetComparison(n_trees=%d, n_leaves_shared=%d, rooted=%r, begin=%d, count=%d)" % (
+            self.n_trees, self.n_leaves_shared, self.rooted, self.begin, self.count)
+
+    def pair(self, k):
+        """(i, j), j < i, of pair ``k`` of the range."""
+        k = int(k)
+        if not 0 <= k < self.count:
+            raise IndexError("pair %d of %d" % (k, self.count))
+        return int(self.i[k]), int(self.j[k])
+
+    def matrix(self, which="rf"):
+        """The square symmetric matrix of ``rf``, ``rf_normalised`` or ``shared`` with a zero diagonal: the whole triangle only."""
+        if which not in ("rf", "rf_normalised", "shared"):
+            raise ValueError("which must be 'rf', 'rf_normalised' or 'shared'")
+        if self.begin != 0 or self.count != self.n_trees * (self.n_trees - 1) // 2:
+            raise ValueError("a matrix needs the whole triangle, this result holds pairs [%d, %d)" % (self.begin, self.begin + self.count))
+        v = getattr(self, which)
+        M = np.zeros((self.n_trees, self.n_trees), dtype=v.dtype)
+        M[self.i, self.j] = M[self.j, self.i] = v
+        return M
+
+    def clades(self, t):
+        """(``nodes``, ``n_leaves``, ``frequency``) of tree ``t``'s eligible clades in ``get_internal_nodes()`` order:
+        ``frequency`` (int64) is the number of trees of the set that hold the clade, the tree itself included -- None
+        unless the call had ``frequencies=True`` and the whole triangle."""
+        t = int(t)
+        if not 0 <= t < self.n_trees:
+            raise IndexError("tree %d of %d" % (t, self.n_trees))
+        _, node, lo, hi = self._sides[t]
+        return node.astype(np.int64), (hi - lo).astype(np.int64), None if self._frequency is None else self._frequency[t]
+
+    def to_dataframe(self):
+        """One row per pair of the range as a pandas DataFrame (pandas imported here)."""
+        import pandas as pd
+        frame = pd.DataFrame({k: getattr(self, k) for k in self.COLUMNS})
+        frame.insert(2, "name_i", [self.names[v] for v in self.i])
+        frame.insert(3, "name_j", [self.names[v] for v in self.j])
+        return frame
+
+
+def tree_set(trees, leaves=None, rooted=False, min_branch=None, begin=0, count=None, frequencies=True, device=..., chunk_tasks=0):
+    """Every two trees of a set compared by the clades they share, in one pass: the Robinson-Foulds distance between every
+    two of them and, per clade, the number of trees that hold it (Felsenstein's count for every tree of the set at once:
+    what a majority-rule consensus is read from).
+
+    ``trees``: a sequence of :class:`SuchTree` objects, Newick texts, paths to Newick files, :class:`Dendrogram`s or flat
+    trees; texts and paths are parsed into flat arrays only.  ``leaves``: None = the names every tree holds, else a list
+    of names -- a tree that lacks one is a ValueError naming the tree and the leaf; 4 to 16384 of them.  ``rooted`` and
+    ``min_branch`` as in :meth:`SuchTree.compare_clades`: one :func:`clade_side` per tree.  ``begin`` / ``count``: a range
+    of the triangle of pairs k = i (i - 1) / 2 + j, j < i (``count=None``: to its end).  ``frequencies``: also count, per
+    clade, the trees that hold it (whole triangle only).  ``device``: None runs the host restatement, an index the kernel
+    on that device -- the same integers; ... takes the host while pairs x leaves is below RF_DEVICE_MIN_WORK and device 0 from there.
+    Returns a :class:`TreeSetComparison`.  An extension: the reference has no counterpart.
+    """
+    from . import _capi
+    from .suchtree import int_arg
+    flats = []
+    for t, tree in enumerate(trees):
+        flat = read_flat_tree(tree, extended=True)
+        if flat is None:
+            raise TypeError("tree %d must be a SuchTree, a Newick text, a path, a Dendrogram or a flat tree" % t)
+        flats.append(flat)
+    if not flats:
+        raise ValueError("no trees")
+    if leaves is None:
+        common = set(flats[0].leaves)
+        for flat in flats[1:]:
+            common &= set(flat.leaves)
+        names = [name for name, _ in sorted(flats[0].leaves.items(), key=lambda kv: kv[1]) if name in common]
+    else:
+        names = list(leaves)
+    m = len(names)
+    if m < 4 or m > _capi.RF_MAX_LEAVES:
+        raise ValueError("%d common leaves: 4 to %d" % (m, _capi.RF_MAX_LEAVES))
+    rooted = bool(rooted)
+    sides = []
+    for t, flat in enumerate(flats):
+        where = flat.leaves
+        for name in names:
+            if name not in where:
+                raise ValueError("tree %d has no leaf %r" % (t, name))
+        ids = np.fromiter((where[name] for name in names), dtype=np.int64, count=m)
+        sides.append(clade_side(flat, ids, rooted, min_branch))
+    total = len(flats) * (len(flats) - 1) // 2
+    begin = int_arg("begin", begin)
+    count = total - begin if count is None else int_arg("count", count)
+    if begin > total or count < 0 or count > total - begin:
+        raise ValueError("pairs [%d, +%d) of a triangle of %d" % (begin, count, total))
+    whole = begin == 0 and count == total
+    shared, counts = _capi.rf_tasks(m, *_rf_sides(sides, m), rooted=rooted, begin=begin, count=count, want_count=bool(frequencies) and whole,
+                                    device=_rf_device(device, count, m), chunk_tasks=int_arg("chunk_tasks", chunk_tasks))
+    return TreeSetComparison(sides, m, rooted, begin, shared, counts, names)
+
+
+class RelabelledRF:
+    """The Robinson-Foulds half of the topology test in one call (:func:`rf_relabelled`): ``rf``, ``shared``, ``n_a``,
+    ``n_b`` of the two trees as aligned, ``perm_rf`` (int64, in draw order; None without ``keep_stats``), ``n_le`` = the
+    relabellings with rf_p <= rf and ``p_value`` = (n_le + 1) / (permutations + 1); ``rooted``, ``permutations``, ``seed``,
+    ``stream`` and ``n`` repeat the run.  Unpacks as ``rf, p, n = result``."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __iter__(self):
+        return iter((self.rf, self.p_value, self.n))
+
+    def __repr__(self):
+        return "RelabelledRF(rf=%d, p_value=%r, n=%d, permutations=%d)" % (self.rf, self.p_value, self.n, self.permutations)
+
+
+def rf_relabelled(flat_a, ids_a, flat_b, ids_b, permutations=999, seed=None, stream=0, rooted=True, min_branch=None, keep_stats=True, device=...,
+                  chunk_tasks=0):
+    """The Robinson-Foulds distance of two flat trees over aligned leaf-id lists (leaf k is ``ids_a[k]`` in A and
+    ``ids_b[k]`` in B) against B relabelled, every relabelling in one batch.
+
+    Relabelling p = 1 .. permutations is sigma_p = ``hommola_permutation(seed, stream, p, 0, n)``, numbered as
+    :func:`dendrogram_congruence` numbers them: leaf sigma_p[k] of B is aligned with leaf k of A.  With A the tree and B
+    the dendrogram this is that test's ``rf``, ``perm_rf`` and ``n_le``.  Both :func:`clade_side`s are built once; the
+    alignment rows are generated on the host (4 n bytes each).  ``device`` as in :func:`tree_set`, the tasks being the
+    relabellings and the observed pair.  Returns a :class:`RelabelledRF`.
+    """
+    from . import _capi
+    from .suchtree import int_arg, seed_arg
+    permutations, stream = int_arg("permutations", permutations, (1 << 31) - 1, "2^31 - 1"), int_arg("stream", stream, (1 << 31) - 1, "2^31 - 1")
+    seed = seed_arg(seed)
+    ids_a, ids_b = (np.ascontiguousarray(v, dtype=np.int64) for v in (ids_a, ids_b))
+    if ids_a.ndim != 1 or ids_a.shape != ids_b.shape:
+        raise ValueError("the two id lists must be 1-D and of equal length")
+    n = len(ids_a)
+    if n < 4 or n > _capi.RF_MAX_LEAVES:
+        raise ValueError("%d leaves: 4 to %d" % (n, _capi.RF_MAX_LEAVES))
+    rooted = bool(rooted)
+    sides = [clade_side(flat_a, ids_a, rooted, min_branch), clade_side(flat_b, ids_b, rooted, min_branch)]
+    align = np.empty((permutations, n), dtype=np.int32)
+    for p in range(1, permutations + 1):
+        align[p - 1] = hommola_permutation(seed, stream, p, 0, n)
+    tasks = permutations + 1
+    task_p = np.arange(-1, permutations, dtype=np.int32)
+    shared, _ = _capi.rf_tasks(n, *_rf_sides(sides, n), rooted=rooted, align=align if permutations else None, task_i=np.zeros(tasks, dtype=np.int32),
+                               task_j=np.ones(tasks, dtype=np.int32), task_p=task_p, want_count=False, device=_rf_device(device, tasks, n),
+                               chunk_tasks=int_arg("chunk_tasks", chunk_tasks))
+    n_a, n_b = len(sides[0][1]), len(sides[1][1])
+    rf_all = n_a + n_b - 2 * shared.astype(np.int64)
+    rf, perm_rf = int(rf_all[0]), rf_all[1:]
+    n_le = int((perm_rf <= rf).sum())
+    return RelabelledRF(rf=rf, shared=int(shared[0]), n_a=n_a, n_b=n_b, perm_rf=perm_rf if keep_stats else None, n_le=n_le,
+                        p_value=(n_le + 1) / (permutations + 1), rooted=rooted, permutations=permutations, seed=seed, stream=stream, n=n)
+
+
 def null_summary(observed, null, degenerate=None):
     """(mean, sd, ses, n_le) per row of ``null`` (rows, draws) against ``observed`` (rows): NaN draws left out, sd with
     ddof = 1, exactly 0 where all draws are equal; rows marked ``degenerate`` have the observation as their null."""

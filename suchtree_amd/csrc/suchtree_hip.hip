@@ -94,6 +94,9 @@
 // Exact UPGMA, single and complete linkage of a matrix of codes (st_linkage_codes): kernels_linkage.h (the square of pair
 // sums, every row's nearest later partner, the chain of merges as one workgroup), host_linkage.h (the layout, the three
 // launches, where the cache lives) and, host-only, linkage_plan.cpp (the checks, the restatement with the same cache).
+// The clades a whole set of trees shares, pair by pair (st_rf_tasks): kernels_rf.h (Day's method, one task per workgroup:
+// a scatter, block extrema and a sparse table in LDS, a binary search per clade), host_rf.h (the work block and the chunk
+// driver) and, host-only, rf_plan.cpp (the checks, the sorted keys, the restatement of the method).
 //
 // What the host side does: tree upload to one or several GPUs (tree_prep.cpp builds the tables, under a table budget
 // if one is given), the host path (host_pipe.h, host_copy.h: packed ids in through the copy engine, kernels write
@@ -226,6 +229,7 @@ static int device_index_arg(int device)
 #include "kernels_class.h"
 #include "kernels_parafit.h"
 #include "kernels_linkage.h"
+#include "kernels_rf.h"
 
 
 // --------------------------------------------------------------------------
@@ -253,6 +257,7 @@ using namespace st;
 #include "host_class.h"
 #include "host_parafit.h"
 #include "host_linkage.h"
+#include "host_rf.h"
 
 // the next link of st_link_sample_pairs (MuchTree.pyx:2946-2949)
 static int64_t link_draw(uint64_t &s, int64_t n_links)
@@ -1256,6 +1261,23 @@ try {
         return ST_OK;
     }
     return linkage_device(device, codes, n, weights, method, out_rows);
+} ST_CATCH_ALL
+
+int st_rf_tasks(int device, int32_t m, int32_t n_trees, const int32_t *where, const int64_t *clade_offsets, const int32_t *lo, const int32_t *hi,
+                int32_t unrooted, const int32_t *align, int32_t n_align, const int32_t *task_i, const int32_t *task_j, const int32_t *task_p,
+                int64_t n_tasks, int64_t begin, int64_t chunk_tasks, int32_t *out_shared, int64_t *out_count)
+try {
+    RfPlan P;
+    std::string err;
+    const int rc = rf_plan(m, n_trees, where, clade_offsets, lo, hi, unrooted != 0, align, n_align, task_i, task_j, task_p, n_tasks, begin, chunk_tasks,
+                           out_shared, P, err);
+    if (rc != ST_OK) return fail(rc, err);
+    if (device_or_host_arg(device) != ST_OK) return ST_ERR_ARG;
+    if (device < 0 || n_tasks == 0) {      // (no tasks: nothing to launch; the counts are zeros)
+        rf_host(P, task_i, task_j, task_p, out_shared, out_count);
+        return ST_OK;
+    }
+    return rf_device(device, P, task_i, task_j, task_p, out_shared, out_count);
 } ST_CATCH_ALL
 
 int st_graph_matrices_host(int device, int64_t n, int64_t n_edges, const int32_t *u, const int32_t *v,

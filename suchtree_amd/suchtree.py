@@ -616,7 +616,6 @@ class SuchTree(TreeNavigation):
         :class:`~suchtree_amd.compare.TransferSupport`.  An extension: the reference has no counterpart.
         """
         from . import compare
-        from .newick import flat_tree_from_newick
         names = [name for name, _ in sorted(self.leaves.items(), key=lambda kv: kv[1])] if leaves is None else list(leaves)
         ids = self._name_ids(names)
         device = self._device if device is ... else device
@@ -625,15 +624,8 @@ class SuchTree(TreeNavigation):
         side = compare.clade_side(self._flat, ids, bool(rooted), min_branch)
         out = compare.TransferSupport(len(ids), bool(rooted), side)
         for r, rep in enumerate(replicates):
-            if isinstance(rep, SuchTree):
-                flat = rep._flat
-            elif isinstance(rep, str):
-                text = rep.strip()
-                if not (text.startswith("(") and text.endswith(";")):
-                    with open(rep) as fh:
-                        text = fh.read()
-                flat = flat_tree_from_newick(text)
-            else:
+            flat = compare.read_flat_tree(rep)
+            if flat is None:
                 raise TypeError("replicate %d must be a SuchTree, a Newick text or a path" % r)
             where = flat.leaves
             for name in names:
